@@ -2,13 +2,17 @@
 """Headline benchmark: training samples/s of FFNO2D on 256^2 Navier-Stokes-like
 synthetic fields (BASELINE.json configs[2]), one process per GPU.
 
-    python bench.py --gpus N --steps K --warmup W [--batch B]
+    python bench.py --gpus N --steps K --warmup W [--batch B] [--dump-outputs DIR] [--full]
 
 A step = forward + relative-L2 loss + backward + gradient all-reduce (N>1) +
 AdamW on one batch of B samples per GPU, inputs resident in HBM.  With --gpus N
 and no WORLD_SIZE in the environment the script spawns its N ranks itself
 (rpde/launch.py); under torch.distributed.run it is one of them.  Rank 0 prints
-ONE JSON line.  It also carries
+ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the
+headline (samples/s, ms_per_step, step percentiles, losses).  --dump-outputs DIR
+writes what the last timed step handed its caller as DIR/<name>.npy (float32):
+loss, prediction, parameters (after the update), gradients.  With --full the line
+also carries
   * roofline: the dominant kernel -- k_ff3_fwd_h2<1>, the fused FeedForward
     64->256->256->64 forward of one layer in training mode -- timed live with
     HIP events on the launch stream.  SURVEY 8(d) prices FeedForward against
@@ -37,6 +41,7 @@ ONE JSON line.  It also carries
     ResolutionGroupedDataLoader, pinned host batches, host-to-device copies inside the timed region (all ranks);
   * parity: the headline model at B = 8 (forward, loss, every gradient) against the digests the imported reference
     produced (tests/golden/ffno2d_cfg3_256_b8.npz).
+The --no-* switches leave single legs of --full out.
 """
 from __future__ import annotations
 
@@ -528,6 +533,28 @@ def parity_check(device):
             "tolerance": {"fwd": 1e-5, "grad": 2e-5}, "tensors_compared": len(errs)}
 
 
+DUMP_CAP_ELEMS = 8 << 20        # 32 MB of float32 per array: the four arrays stay under 64 MB at any batch
+
+
+def dump_outputs(out_dir, loss, pred, model):
+    """What the last timed step handed its caller, as float32 DIR/<name>.npy: loss (the step's relative-L2 loss),
+    prediction (the model's output), parameters (after the AdamW update) and gradients (model.parameters() order,
+    flattened and concatenated; a parameter without a gradient contributes zeros).  An array above DUMP_CAP_ELEMS
+    elements is replaced by a fixed, seeded sample of its flattened elements, the same indices at every run."""
+    import numpy as np
+    flat = lambda ts: torch.cat([(torch.view_as_real(t) if t.is_complex() else t).detach().reshape(-1) for t in ts])  # noqa: E731
+    params = list(model.parameters())
+    arrays = {"loss": loss.detach().reshape(1), "prediction": pred.detach(), "parameters": flat(params),
+              "gradients": flat(p.grad if p.grad is not None else torch.zeros_like(p) for p in params)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.float().cpu()
+        if t.numel() > DUMP_CAP_ELEMS:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_CAP_ELEMS].sort().values
+            t = t.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), t.numpy())
+
+
 _T0 = time.time()
 
 
@@ -542,13 +569,19 @@ def main():
     ap.add_argument("--steps", type=int, default=50)      # 10 warm-up + 50 timed
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=32, help="samples per GPU per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-aten-baseline", action="store_true", help="skip the stock-ATen-on-GPU A/B leg")
-    ap.add_argument("--no-graph", action="store_true", help="skip the hipGraph-replayed step leg")
-    ap.add_argument("--no-mres", action="store_true", help="skip the BASELINE configs[3] leg (mixed resolutions, grouped loader)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the other legs: in-step kernel timing, hipGraph step, mixed resolutions, kernel "
+                         "microbenchmarks and rooflines, CPU and stock-ATen baselines, parity")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU-oracle leg")
+    ap.add_argument("--no-aten-baseline", action="store_true", help="--full without the stock-ATen-on-GPU A/B leg")
+    ap.add_argument("--no-graph", action="store_true", help="--full without the hipGraph-replayed step leg")
+    ap.add_argument("--no-mres", action="store_true", help="--full without the BASELINE configs[3] leg (mixed resolutions, grouped loader)")
     ap.add_argument("--steps-only", action="store_true",
-                    help="profiling aid: stop after the timed training steps (no kernel microbenchmarks, no parity leg)")
+                    help="profiling aid: stop after the timed training steps and print a short line")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # --gpus N without a launcher: this (GPU-free) parent starts the N ranks itself and returns their exit code
     env_world = os.environ.get("WORLD_SIZE")
@@ -600,10 +633,14 @@ def main():
     losses = torch.zeros(args.warmup + args.steps, device=device)
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     ar_ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+    last = {}                                  # the last timed step's loss and prediction, for --dump-outputs
 
     def step(i, timed=-1):
         bucket.zero()
-        loss = loss_fn(model(x), y)
+        pred = model(x)
+        loss = loss_fn(pred, y)
+        if timed == args.steps - 1:
+            last.update(loss=loss, pred=pred)
         loss.backward()
         if world > 1 and timed >= 0:
             ar_ev[timed][0].record()
@@ -642,12 +679,16 @@ def main():
     ar_ms = sum(a.elapsed_time(b) for a, b in ar_ev) / len(ar_ev) if world > 1 else 0.0
     lh = losses.cpu().tolist()
     log(f"timed region: {elapsed:.3f}s for {args.steps} steps; rel-L2 {lh[0]:.4f} -> {lh[-1]:.4f}")
+    if args.dump_outputs and rank == 0:        # before any leg of --full moves the weights on
+        dump_outputs(args.dump_outputs, last["loss"], last["pred"], model)
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
+    last.clear()
     # FSpectralConv2d.forward_fourier timed WHERE IT RUNS: four more training steps (every rank: the all-reduce is in the
     # step) with an event pair around each of the layer's forward calls.  The stand-alone loop of time_spectral() runs
     # the same four launches back to back, and every one of them slows by 10-20 % within its first 5 ms (the clock
     # settling under sustained matrix + memory load); inside a step they run at the step's clock.
     spec_in_step = ff_in_step = None
-    if not args.steps_only:
+    if args.full and not args.steps_only:
         from rpde import ops as _ops
         pairs = {"fspectral2d": [], "feedforward": []}
         real = {k: getattr(_ops, k) for k in pairs}
@@ -678,11 +719,11 @@ def main():
     graphed = None
     # (at N > 1 only on request: a capture that RCCL refused on one box would hang the other ranks, and N > 1 cannot be
     #  rehearsed on the 1-GPU boxes this is built on -- tests/test_gpu_rccl.py captures the collective in a world of one)
-    if not args.steps_only and not args.no_graph and (world == 1 or os.environ.get("RPDE_BENCH_GRAPH") == "1"):
+    if args.full and not args.steps_only and not args.no_graph and (world == 1 or os.environ.get("RPDE_BENCH_GRAPH") == "1"):
         graphed = graph_leg(model, bucket, opt, loss_fn, x, y, world, device, min(args.steps, 20))
         log(f"graphed step: {json.dumps(graphed)}")
     mres = None
-    if not args.steps_only and not args.no_mres:
+    if args.full and not args.steps_only and not args.no_mres:
         mres = mres_leg(model, bucket, opt, loss_fn, B, world, rank, device)          # every rank takes part
         log(f"config 4 (mixed resolutions through the grouped loader): {json.dumps(mres)}")
 
@@ -692,38 +733,9 @@ def main():
     elif rank == 0:
         ms_step = elapsed / args.steps * 1e3
         value = B * world * args.steps / elapsed
-        ff = time_feedforward(B, device)
-        log(f"FeedForward: fwd(train) {ff['fwd_train_ms']:.3f} ms, fwd(eval) {ff['fwd_eval_ms']:.3f} ms, "
-            f"bwd chain {ff['bwd_chain_ms']:.3f} ms, wgrad {ff['wgrad_ms']:.3f} ms")
-        s_ms, s_gbs, s_bytes, s_bwd_ms, s_fb_ms = time_spectral(B, device)
-        log(f"spectral fwd {s_ms:.3f} ms = {s_gbs:.0f} GB/s algorithmic; bwd {s_bwd_ms:.3f} ms")
-        c5_ms, c5_bytes, c5_model_ms, c5_model16_ms = time_cfg5(device)
-        log(f"config 5: SpectralConv2d 512^2 forward {c5_ms:.3f} ms, FNO2d eval forward {c5_model_ms:.3f} ms (B=8), "
-            f"{c5_model16_ms:.3f} ms (B=16)")
-        sy = time_shipped_yamls(B, device)
-        log(f"shipped yamls: FFNO2D n_modes 64: layer forward {sy['spec_ms']:.3f} ms, step {sy['step2_ms']:.3f} ms; FFNO1D step "
-            f"{sy['ffno1d_eager_ms']:.3f} ms eager, {sy['ffno1d_graph_ms']:.3f} ms as a hipGraph")
-        traffic = step_traffic = traffic_src = spec_traffic = None
-        tpath = os.path.join(REPO, "profiles", "traffic.json")
-        if os.path.exists(tpath):
-            try:
-                blob = json.load(open(tpath))
-                traffic = blob.get("dominant_kernel", {}).get(f"B{B}")
-                spec_traffic = blob.get("spectral_forward", {}).get(f"B{B}")
-                step_traffic = blob.get("train_step", {}).get(f"B{B}", {}).get("hbm_bytes_per_step")
-                traffic_src = blob.get("source")
-            except Exception:
-                traffic = step_traffic = spec_traffic = None
-
-        def hbm(kernel, byt, ms, **extra):
-            gbs = byt / (ms * 1e-3) / 1e9
-            d = {"kernel": kernel, "bound": "hbm", "achieved": round(gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                 "frac": round(gbs / PEAK_HBM_GBS, 4), "algorithmic_bytes_per_launch": byt, "ms_per_launch": round(ms, 4)}
-            d.update(extra)
-            return d
-
-        tf = lambda fl, ms: round(fl / (ms * 1e-3) / 1e12, 2)                                  # noqa: E731
-        ff_ms = ff_in_step if ff_in_step else ff["fwd_train_ms"]
+        # fp32 in / out / accumulate everywhere.  Products run on the f16 matrix pipe by two-piece splitting with
+        # dynamic power-of-two scaling (3 MFMA terms, csrc/h2.h) in the fused kernels and on the bf16 pipe by
+        # three-piece splitting (6 terms) in the remaining GEMMs.
         line = {
             "metric": "training samples/sec, FFNO2D NS 256^2", "value": round(value, 3), "unit": "samples/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 3),
@@ -737,105 +749,137 @@ def main():
                        "step_ms_p10_p50_p90": [round(pct(0.1), 3), round(pct(0.5), 3), round(pct(0.9), 3)],
                        "train_rel_l2_first_last": [round(lh[0], 6), round(lh[-1], 6)],
                        "target": "input advanced by a fixed spectral filter (utils/synthetic.py:advance)"},
-            # fp32 in / out / accumulate everywhere.  Products run on the f16 matrix pipe by two-piece splitting with
-            # dynamic power-of-two scaling (3 MFMA terms, csrc/h2.h) in the fused kernels and on the bf16 pipe by
-            # three-piece splitting (6 terms) in the remaining GEMMs.
-            # FeedForward is priced against the matrix roof.  flops_per_launch = 2*P*(64*256 + 256*256 +
-            # 256*64) = 12.88 GFLOP * B; the kernel issues every fp32 product as THREE f16 MFMA products (h2.h), so the
-            # matrix pipe executes 3x that: achieved = issued flops / time, peak = 2.5 PFLOP/s dense f16
-            "roofline": {"kernel": "k_ff3_fwd_h2<train>: fused FeedForward 64->256->256->64 forward of one layer (+ its weight "
-                                   "preparation launch)",
-                         "bound": "mfma", "achieved": tf(3.0 * ff["flops_fwd"], ff_ms), "peak": PEAK_BF16_MFMA_TF,
-                         "unit": "TFLOP/s", "frac": round(tf(3.0 * ff["flops_fwd"], ff_ms) / PEAK_BF16_MFMA_TF, 4),
-                         "flops_per_launch": ff["flops_fwd"], "issued_flops_per_launch": 3.0 * ff["flops_fwd"],
-                         "issued_flops": "3x: a_hi*b_hi + a_hi*b_lo + a_lo*b_hi on v_mfma_f32_16x16x32_f16, fp32 accumulate",
-                         "fp32_equiv_tflops": tf(ff["flops_fwd"], ff_ms),
-                         "frac_of_fp32_mfma_peak": round(tf(ff["flops_fwd"], ff_ms) / PEAK_F32_MFMA_TF, 4),
-                         "ms_per_launch": round(ff_ms, 4),
-                         "timed": ("HIP event pairs around the layer's forward call inside 4 training steps (16 calls: preparation "
-                                   "launch + the kernel), i.e. over the timed region's own launches" if ff_in_step
-                                   else "stand-alone loop of 10 launches"),
-                         "ms_per_launch_back_to_back_loop": round(ff["fwd_train_ms"], 4),
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "note": "fp32 in / out / accumulate; hidden activations never leave the CU.  Neither roof is near: "
-                                 "the kernel is bound by VALU issue (bias, dropout, GELU + GELU', f16 splitting, LayerNorm) -- "
-                                 "SQ counters in profiles/"},
-            "roofline_extra": [
-                hbm("k_ff3_fwd_h2<train>, HBM view: reads x, residual; writes out, z3 (algorithmic: 4*P*2C + weights = "
-                    f"{(4.0 * B * RES * RES * 2 * 64 + 4 * 98304) / 1e9:.2f} GB) plus the saved-for-backward stash h1, d1, h2, d2 "
-                    "(DESIGN TRAFFIC, not algorithmic: 4 x [P,256] fp32)", ff["bytes_train"], ff["fwd_train_ms"],
-                    algorithmic_bytes_8d=4.0 * B * RES * RES * 2 * 64 + 4 * 98304, design_stash_bytes=4.0 * B * RES * RES * 4 * 256,
-                    traffic=traffic),
-                hbm("k_ff3_fwd_h2<eval>: the same forward in evaluation (writes nothing but the output)", ff["bytes_eval"],
-                    ff["fwd_eval_ms"], fp32_equiv_tflops=tf(ff["flops_fwd"], ff["fwd_eval_ms"])),
-                hbm("k_ff3_bwd_h2: LayerNorm/dropout adjoint + data-gradient chain (reads g, z3, d2, d1; writes dz3, du2, du1)",
-                    ff["bytes_chain"], ff["bwd_chain_ms"]),
-                hbm("k_wgrad_h2 + reduce_slabs: weight gradient [256,P]x[P,256] (reads du2 and h1 once; 256 slabs of 256 KB)",
-                    ff["bytes_wgrad"], ff["wgrad_ms"], fp32_equiv_tflops=tf(ff["flops_wgrad"], ff["wgrad_ms"])),
-                hbm("FSpectralConv2d backward (adjoint analysis, mode mix^T + weight gradients, adjoint synthesis + skip)",
-                    2 * s_bytes, s_bwd_ms),
-                hbm("BASELINE config 5: SpectralConv2d(32,32,12,12) forward at [8,32,512,512] (k_cf_analysis_h2, row DFT, "
-                    "mode mix, row DFT, k_cf_synthesis_h2), SURVEY 8(d): 67.11 MB*B + 2.36 MB", c5_bytes, c5_ms,
-                    fno2d_512_eval_forward_ms_B8=round(c5_model_ms, 3),
-                    fno2d_512_eval_samples_per_s=round(8 / c5_model_ms * 1e3, 1)),
-                # the whole evaluation forward of BASELINE config 5 against ITS ideal traffic: per sample 4 blocks x 67.11 MB
-                # (read x, write the activated block output) + lifting (write 33.55 MB) + projection (read 33.55 MB) + the
-                # 1-channel input and output (2 x 1.05 MB) = 337.6 MB
-                hbm("BASELINE config 5: FNO2d(1,1,12,12,32) evaluation forward at [16,1,512,512] (per block: k_cf_analysis_h2, two row "
-                    "DFTs + mode mix on the small spectra, then ONE pass for inverse DFT + bypass conv + GELU; fused projection MLP)",
-                    16 * 337.6e6, c5_model16_ms, samples_per_s=round(16 / c5_model16_ms * 1e3, 1)),
-                hbm("the reference's SHIPPED ffno_2d.yaml (n_modes 64, off the fused spectral path): FSpectralConv2d.forward_fourier "
-                    f"at [{B},256,256,64], K = 64 (truncated-DFT GEMMs + per-mode GEMM), SURVEY 8(d) bytes", sy["spec_bytes"], sy["spec_ms"],
-                    ffno2d_n_modes64_train_step_ms=round(sy["step2_ms"], 3),
-                    ffno2d_n_modes64_samples_per_s=round(B / sy["step2_ms"] * 1e3, 1)),
-            ],
-            "config2_ffno1d": {"workload": "BASELINE configs[1] with the reference's ffno_1d.yaml: FFNO1D(width 128, 4 layers, 64 modes, "
-                               "3-layer FeedForward, LayerNorm, weight norm, dropout 0.2) training step at [16,1,512]",
-                               "eager_ms_per_step": round(sy["ffno1d_eager_ms"], 3), "graphed_ms_per_step": round(sy["ffno1d_graph_ms"], 3),
-                               "samples_per_s_graphed": round(16 / sy["ffno1d_graph_ms"] * 1e3, 1),
-                               "note": "launch-bound: ~100 dispatches per step (profiles/r04_ffno1d_sequence_after.txt)"},
-            "roofline_spectral": hbm("FSpectralConv2d.forward_fourier: k_mix_prep + k_dft_analysis_rr_h2 (both axes, the field read "
-                                     "from HBM once, no cross-wave sums) + k_mix_h2 (mode mix of both axes, writes the synthesis "
-                                     "operands) + k_dft_synthesis4_h2 (field written once, whole 128-byte lines)",
-                                     s_bytes, spec_in_step if spec_in_step else s_ms, traffic=spec_traffic,
-                                     timed="HIP event pairs around the layer's forward call inside 4 training steps (16 calls): the "
-                                     "four launches at the clock the step runs at" if spec_in_step else "stand-alone loop",
-                                     ms_per_launch_back_to_back_loop=round(s_ms, 4),
-                                     frac_back_to_back_loop=round(s_bytes / (s_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4),
-                                     traffic_over_algorithmic=(round(spec_traffic / s_bytes, 3) if spec_traffic else None),
-                                     backward_ms=round(s_bwd_ms, 4), backward_frac=round(2 * s_bytes / (s_bwd_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4),
-                                     note="HBM traffic of the four launches (PMC, profiles/): field 1x in + 1x out, spectra "
-                                     "written and read once as fp32 and once as operand fragments; the second read of the field "
-                                     "(the other axis) is served by the L2 of the XCD that read it first.  What bounds the two big "
-                                     "kernels is the rate at which a CU's vector-memory pipeline moves bytes (~10 B/cycle from HBM, "
-                                     "~23 from L2): every field byte is LOADED twice by the analysis, 2.25 fragment bytes per byte "
-                                     "stored by the synthesis -- DESIGN.md section 4.1"),
         }
-        if step_traffic:
-            # whole training step against the HBM roof: PMC-measured bytes of one step / this run's step time
-            gbs = step_traffic / (ms_step * 1e-3) / 1e9
-            line["roofline_step"] = {"bound": "hbm", "traffic_bytes_per_step": step_traffic, "traffic_source": traffic_src,
-                                     "achieved": round(gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                                     "frac": round(gbs / PEAK_HBM_GBS, 4),
-                                     "note": "all kernels of one step; PMC bytes from the committed profile, time from this run"}
-        if graphed is not None:
-            graphed["eager_ms_per_step"] = round(ms_step, 3)
-            line["graphed_step"] = graphed
-        if mres is not None:
-            line["config4_mres"] = mres
-        # (the other ranks wait at the final barrier meanwhile: their host threads sleep, so the CPU baseline has the
-        #  box's cores to itself at every N)
-        if not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline()
-            log(f"cpu baseline {line['cpu_baseline']['value']} samples/s")
-            line["speedup_vs_cpu_baseline"] = round(value / line["cpu_baseline"]["value"], 1)
-        if world == 1:
-            line["parity"] = parity_check(device)
-            log(f"parity {line['parity']}")
-            if not args.no_aten_baseline:
-                line["gpu_aten_baseline"] = gpu_aten_baseline(B, device, s_ms, s_fb_ms, ff["fwd_train_ms"],
-                                                              ff["fwd_train_ms"] + ff["bwd_full_ms"], ms_step)
-                log(f"stock ATen on this GPU: {json.dumps(line['gpu_aten_baseline'])}")
+        if args.full:
+            ff = time_feedforward(B, device)
+            log(f"FeedForward: fwd(train) {ff['fwd_train_ms']:.3f} ms, fwd(eval) {ff['fwd_eval_ms']:.3f} ms, "
+                f"bwd chain {ff['bwd_chain_ms']:.3f} ms, wgrad {ff['wgrad_ms']:.3f} ms")
+            s_ms, s_gbs, s_bytes, s_bwd_ms, s_fb_ms = time_spectral(B, device)
+            log(f"spectral fwd {s_ms:.3f} ms = {s_gbs:.0f} GB/s algorithmic; bwd {s_bwd_ms:.3f} ms")
+            c5_ms, c5_bytes, c5_model_ms, c5_model16_ms = time_cfg5(device)
+            log(f"config 5: SpectralConv2d 512^2 forward {c5_ms:.3f} ms, FNO2d eval forward {c5_model_ms:.3f} ms (B=8), "
+                f"{c5_model16_ms:.3f} ms (B=16)")
+            sy = time_shipped_yamls(B, device)
+            log(f"shipped yamls: FFNO2D n_modes 64: layer forward {sy['spec_ms']:.3f} ms, step {sy['step2_ms']:.3f} ms; FFNO1D step "
+                f"{sy['ffno1d_eager_ms']:.3f} ms eager, {sy['ffno1d_graph_ms']:.3f} ms as a hipGraph")
+            traffic = step_traffic = traffic_src = spec_traffic = None
+            tpath = os.path.join(REPO, "profiles", "traffic.json")
+            if os.path.exists(tpath):
+                try:
+                    blob = json.load(open(tpath))
+                    traffic = blob.get("dominant_kernel", {}).get(f"B{B}")
+                    spec_traffic = blob.get("spectral_forward", {}).get(f"B{B}")
+                    step_traffic = blob.get("train_step", {}).get(f"B{B}", {}).get("hbm_bytes_per_step")
+                    traffic_src = blob.get("source")
+                except Exception:
+                    traffic = step_traffic = spec_traffic = None
+
+            def hbm(kernel, byt, ms, **extra):
+                gbs = byt / (ms * 1e-3) / 1e9
+                d = {"kernel": kernel, "bound": "hbm", "achieved": round(gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                     "frac": round(gbs / PEAK_HBM_GBS, 4), "algorithmic_bytes_per_launch": byt, "ms_per_launch": round(ms, 4)}
+                d.update(extra)
+                return d
+
+            tf = lambda fl, ms: round(fl / (ms * 1e-3) / 1e12, 2)                                  # noqa: E731
+            ff_ms = ff_in_step if ff_in_step else ff["fwd_train_ms"]
+            line.update({
+                # FeedForward is priced against the matrix roof.  flops_per_launch = 2*P*(64*256 + 256*256 +
+                # 256*64) = 12.88 GFLOP * B; the kernel issues every fp32 product as THREE f16 MFMA products (h2.h), so the
+                # matrix pipe executes 3x that: achieved = issued flops / time, peak = 2.5 PFLOP/s dense f16
+                "roofline": {"kernel": "k_ff3_fwd_h2<train>: fused FeedForward 64->256->256->64 forward of one layer (+ its weight "
+                                       "preparation launch)",
+                             "bound": "mfma", "achieved": tf(3.0 * ff["flops_fwd"], ff_ms), "peak": PEAK_BF16_MFMA_TF,
+                             "unit": "TFLOP/s", "frac": round(tf(3.0 * ff["flops_fwd"], ff_ms) / PEAK_BF16_MFMA_TF, 4),
+                             "flops_per_launch": ff["flops_fwd"], "issued_flops_per_launch": 3.0 * ff["flops_fwd"],
+                             "issued_flops": "3x: a_hi*b_hi + a_hi*b_lo + a_lo*b_hi on v_mfma_f32_16x16x32_f16, fp32 accumulate",
+                             "fp32_equiv_tflops": tf(ff["flops_fwd"], ff_ms),
+                             "frac_of_fp32_mfma_peak": round(tf(ff["flops_fwd"], ff_ms) / PEAK_F32_MFMA_TF, 4),
+                             "ms_per_launch": round(ff_ms, 4),
+                             "timed": ("HIP event pairs around the layer's forward call inside 4 training steps (16 calls: preparation "
+                                       "launch + the kernel), i.e. over the timed region's own launches" if ff_in_step
+                                       else "stand-alone loop of 10 launches"),
+                             "ms_per_launch_back_to_back_loop": round(ff["fwd_train_ms"], 4),
+                             "traffic": traffic, "traffic_source": traffic_src,
+                             "note": "fp32 in / out / accumulate; hidden activations never leave the CU.  Neither roof is near: "
+                                     "the kernel is bound by VALU issue (bias, dropout, GELU + GELU', f16 splitting, LayerNorm) -- "
+                                     "SQ counters in profiles/"},
+                "roofline_extra": [
+                    hbm("k_ff3_fwd_h2<train>, HBM view: reads x, residual; writes out, z3 (algorithmic: 4*P*2C + weights = "
+                        f"{(4.0 * B * RES * RES * 2 * 64 + 4 * 98304) / 1e9:.2f} GB) plus the saved-for-backward stash h1, d1, h2, d2 "
+                        "(DESIGN TRAFFIC, not algorithmic: 4 x [P,256] fp32)", ff["bytes_train"], ff["fwd_train_ms"],
+                        algorithmic_bytes_8d=4.0 * B * RES * RES * 2 * 64 + 4 * 98304, design_stash_bytes=4.0 * B * RES * RES * 4 * 256,
+                        traffic=traffic),
+                    hbm("k_ff3_fwd_h2<eval>: the same forward in evaluation (writes nothing but the output)", ff["bytes_eval"],
+                        ff["fwd_eval_ms"], fp32_equiv_tflops=tf(ff["flops_fwd"], ff["fwd_eval_ms"])),
+                    hbm("k_ff3_bwd_h2: LayerNorm/dropout adjoint + data-gradient chain (reads g, z3, d2, d1; writes dz3, du2, du1)",
+                        ff["bytes_chain"], ff["bwd_chain_ms"]),
+                    hbm("k_wgrad_h2 + reduce_slabs: weight gradient [256,P]x[P,256] (reads du2 and h1 once; 256 slabs of 256 KB)",
+                        ff["bytes_wgrad"], ff["wgrad_ms"], fp32_equiv_tflops=tf(ff["flops_wgrad"], ff["wgrad_ms"])),
+                    hbm("FSpectralConv2d backward (adjoint analysis, mode mix^T + weight gradients, adjoint synthesis + skip)",
+                        2 * s_bytes, s_bwd_ms),
+                    hbm("BASELINE config 5: SpectralConv2d(32,32,12,12) forward at [8,32,512,512] (k_cf_analysis_h2, row DFT, "
+                        "mode mix, row DFT, k_cf_synthesis_h2), SURVEY 8(d): 67.11 MB*B + 2.36 MB", c5_bytes, c5_ms,
+                        fno2d_512_eval_forward_ms_B8=round(c5_model_ms, 3),
+                        fno2d_512_eval_samples_per_s=round(8 / c5_model_ms * 1e3, 1)),
+                    # the whole evaluation forward of BASELINE config 5 against ITS ideal traffic: per sample 4 blocks x 67.11 MB
+                    # (read x, write the activated block output) + lifting (write 33.55 MB) + projection (read 33.55 MB) + the
+                    # 1-channel input and output (2 x 1.05 MB) = 337.6 MB
+                    hbm("BASELINE config 5: FNO2d(1,1,12,12,32) evaluation forward at [16,1,512,512] (per block: k_cf_analysis_h2, two row "
+                        "DFTs + mode mix on the small spectra, then ONE pass for inverse DFT + bypass conv + GELU; fused projection MLP)",
+                        16 * 337.6e6, c5_model16_ms, samples_per_s=round(16 / c5_model16_ms * 1e3, 1)),
+                    hbm("the reference's SHIPPED ffno_2d.yaml (n_modes 64, off the fused spectral path): FSpectralConv2d.forward_fourier "
+                        f"at [{B},256,256,64], K = 64 (truncated-DFT GEMMs + per-mode GEMM), SURVEY 8(d) bytes", sy["spec_bytes"], sy["spec_ms"],
+                        ffno2d_n_modes64_train_step_ms=round(sy["step2_ms"], 3),
+                        ffno2d_n_modes64_samples_per_s=round(B / sy["step2_ms"] * 1e3, 1)),
+                ],
+                "config2_ffno1d": {"workload": "BASELINE configs[1] with the reference's ffno_1d.yaml: FFNO1D(width 128, 4 layers, 64 modes, "
+                                   "3-layer FeedForward, LayerNorm, weight norm, dropout 0.2) training step at [16,1,512]",
+                                   "eager_ms_per_step": round(sy["ffno1d_eager_ms"], 3), "graphed_ms_per_step": round(sy["ffno1d_graph_ms"], 3),
+                                   "samples_per_s_graphed": round(16 / sy["ffno1d_graph_ms"] * 1e3, 1),
+                                   "note": "launch-bound: ~100 dispatches per step (profiles/r04_ffno1d_sequence_after.txt)"},
+                "roofline_spectral": hbm("FSpectralConv2d.forward_fourier: k_mix_prep + k_dft_analysis_rr_h2 (both axes, the field read "
+                                         "from HBM once, no cross-wave sums) + k_mix_h2 (mode mix of both axes, writes the synthesis "
+                                         "operands) + k_dft_synthesis4_h2 (field written once, whole 128-byte lines)",
+                                         s_bytes, spec_in_step if spec_in_step else s_ms, traffic=spec_traffic,
+                                         timed="HIP event pairs around the layer's forward call inside 4 training steps (16 calls): the "
+                                         "four launches at the clock the step runs at" if spec_in_step else "stand-alone loop",
+                                         ms_per_launch_back_to_back_loop=round(s_ms, 4),
+                                         frac_back_to_back_loop=round(s_bytes / (s_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4),
+                                         traffic_over_algorithmic=(round(spec_traffic / s_bytes, 3) if spec_traffic else None),
+                                         backward_ms=round(s_bwd_ms, 4), backward_frac=round(2 * s_bytes / (s_bwd_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4),
+                                         note="HBM traffic of the four launches (PMC, profiles/): field 1x in + 1x out, spectra "
+                                         "written and read once as fp32 and once as operand fragments; the second read of the field "
+                                         "(the other axis) is served by the L2 of the XCD that read it first.  What bounds the two big "
+                                         "kernels is the rate at which a CU's vector-memory pipeline moves bytes (~10 B/cycle from HBM, "
+                                         "~23 from L2): every field byte is LOADED twice by the analysis, 2.25 fragment bytes per byte "
+                                         "stored by the synthesis -- DESIGN.md section 4.1"),
+            })
+            if step_traffic:
+                # whole training step against the HBM roof: PMC-measured bytes of one step / this run's step time
+                gbs = step_traffic / (ms_step * 1e-3) / 1e9
+                line["roofline_step"] = {"bound": "hbm", "traffic_bytes_per_step": step_traffic, "traffic_source": traffic_src,
+                                         "achieved": round(gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                                         "frac": round(gbs / PEAK_HBM_GBS, 4),
+                                         "note": "all kernels of one step; PMC bytes from the committed profile, time from this run"}
+            if graphed is not None:
+                graphed["eager_ms_per_step"] = round(ms_step, 3)
+                line["graphed_step"] = graphed
+            if mres is not None:
+                line["config4_mres"] = mres
+            # (the other ranks wait at the final barrier meanwhile: their host threads sleep, so the CPU baseline has the
+            #  box's cores to itself at every N)
+            if not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline()
+                log(f"cpu baseline {line['cpu_baseline']['value']} samples/s")
+                line["speedup_vs_cpu_baseline"] = round(value / line["cpu_baseline"]["value"], 1)
+            if world == 1:
+                line["parity"] = parity_check(device)
+                log(f"parity {line['parity']}")
+                if not args.no_aten_baseline:
+                    line["gpu_aten_baseline"] = gpu_aten_baseline(B, device, s_ms, s_fb_ms, ff["fwd_train_ms"],
+                                                                  ff["fwd_train_ms"] + ff["bwd_full_ms"], ms_step)
+                    log(f"stock ATen on this GPU: {json.dumps(line['gpu_aten_baseline'])}")
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()

@@ -7,14 +7,14 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 SQ="SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT"
 python -m pytest tests -m gpu -q > $O/gpu_tests.log 2>&1 &&
-python3 bench.py > $O/bench.json 2> $O/bench.err &&
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -o bench -- python3 bench.py > $O/bench_prof.json 2> $O/bench_prof.err &&
+python3 bench.py --full > $O/bench.json 2> $O/bench.err &&
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -o bench -- python3 bench.py --full > $O/bench_prof.json 2> $O/bench_prof.err &&
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_kf -o k -- python3 profiles/pmc_target.py 32 > $O/pmc_kf.log 2>&1 &&
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_kw -o k -- python3 profiles/pmc_target.py 32 > $O/pmc_kw.log 2>&1 &&
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_sf -o s -- python3 bench.py --steps-only --steps 3 --warmup 1 > $O/pmc_sf.log 2>&1 &&
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_sw -o s -- python3 bench.py --steps-only --steps 3 --warmup 1 > $O/pmc_sw.log 2>&1 &&
 rocprofv3 --pmc $SQ --output-format csv -d $O/pmc_sq -o q -- python3 profiles/pmc_target.py 32 > $O/pmc_sq.log 2>&1 &&
 python3 profiles/other_configs.py > $O/other_configs.txt 2>&1 &&
-RPDE_SHARE_GPU=1 RPDE_DIST_BACKEND=gloo python3 bench.py --gpus 2 --steps 3 --warmup 1 > $O/bench_2rank.json 2> $O/bench_2rank.err
+RPDE_SHARE_GPU=1 RPDE_DIST_BACKEND=gloo python3 bench.py --full --gpus 2 --steps 3 --warmup 1 > $O/bench_2rank.json 2> $O/bench_2rank.err
 echo "rc=$?" > $O/done.txt
 tail -2 $O/gpu_tests.log

@@ -129,7 +129,7 @@ def test_sharded_evaluation_counts_every_sample_once(tmp_path):
     mp.spawn(_eval_worker, args=(2, free_port(), str(tmp_path)), nprocs=2, join=True)
 
 
-def test_untouched_parameters_keep_grad_none_and_reference_modules_stay_importable():
+def test_untouched_parameters_keep_grad_none_and_reference_modules_stay_importable(tmp_path):
     from rpde.parallel import FlatGradBucket
     a, b = torch.nn.Linear(3, 2), torch.nn.Linear(3, 2)           # b takes no part in the graph
     params = list(a.parameters()) + list(b.parameters())
@@ -151,17 +151,23 @@ def test_untouched_parameters_keep_grad_none_and_reference_modules_stay_importab
     assert b.weight.grad is not None and b.weight.grad.data_ptr() >= bucket.flat.data_ptr()
     assert torch.equal(bucket.flat[bucket.offsets[2]:bucket.offsets[2] + 6].view(2, 3), torch.ones(2, 3))
     # drop-in route of INTEGRATION.md A.2: with this tree ahead of the reference root the shared package names are
-    # namespace packages, so the reference's own modules (utils/naive_utils.py ...) still resolve
+    # namespace packages, so the reference's own modules (utils/naive_utils.py ...) still resolve.  The reference
+    # root is stood in for by a tree of the same layout: package directories without __init__.py, one module the
+    # drop-in lacks and one it shadows.
     import importlib.util
-    ref = "/root/reference"
-    if os.path.isdir(ref):
-        sys.path.append(ref)
-        try:
-            importlib.invalidate_caches()
-            for pkg in ("utils", "models", "train"):
-                sys.modules.pop(pkg, None) if not hasattr(sys.modules.get(pkg), "__file__") else None
-            spec = importlib.util.find_spec("utils.naive_utils")
-            assert spec is not None and spec.origin.startswith(ref)
-            assert importlib.util.find_spec("utils.loss").origin.startswith(DROPIN)
-        finally:
-            sys.path.remove(ref)
+    ref = str(tmp_path / "reference")
+    for pkg in ("utils", "models", "train"):
+        os.makedirs(os.path.join(ref, pkg))
+    for mod in ("naive_utils", "loss"):
+        with open(os.path.join(ref, "utils", mod + ".py"), "w") as f:
+            f.write("")
+    sys.path.append(ref)
+    try:
+        importlib.invalidate_caches()
+        for pkg in ("utils", "models", "train"):
+            sys.modules.pop(pkg, None) if not hasattr(sys.modules.get(pkg), "__file__") else None
+        spec = importlib.util.find_spec("utils.naive_utils")
+        assert spec is not None and spec.origin.startswith(ref)
+        assert importlib.util.find_spec("utils.loss").origin.startswith(DROPIN)
+    finally:
+        sys.path.remove(ref)
