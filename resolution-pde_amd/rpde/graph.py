@@ -50,9 +50,11 @@ class GraphedTrainStep:
     With warmup = 0 the caller must not keep a loss / output tensor of an earlier eager step alive across the
     construction: its autograd graph pins the parameters' gradient accumulators to the stream it ran on, and the
     captured backward would then synchronise with that stream -- an illegal dependency inside a capture.
-    A learning-rate schedule: with rpde.optim.FlatAdamW(capturable=True) the values live on the device and are
-    refreshed before a replay when a scheduler has moved them; other optimizers bake them into the graph, and the
-    replay is refused once they change."""
+    A learning-rate schedule: with rpde.optim.FlatAdamW(capturable=True) lr / weight decay live on the device and a
+    replay reads whatever is there.  The optimizer records what it last wrote (eager steps of any shape, other
+    instances, load_state_dict); the construction writes the current values before the capture, and every call
+    writes them again when they differ from that record -- so a replay trains at the group's values of that moment,
+    whoever moved them.  Other optimizers bake the values into the graph, and the replay is refused once they change."""
 
     def __init__(self, model, loss_fn, optimizer, x: torch.Tensor, y: torch.Tensor, warmup: int = 3,
                  after_backward: Optional[Callable[[], None]] = None):
@@ -73,14 +75,20 @@ class GraphedTrainStep:
             for _ in range(max(0, warmup)):      # creates DFT plans, sizes the allocator pools, primes optimizer state
                 self._eager()
         torch.cuda.current_stream(x.device).wait_stream(side)
+        # lr / weight decay on the device (FlatAdamW): the captured step does not write them, so they must be right
+        # before the first replay even when the scheduler moved them after the last eager step
+        self._device_hyper = hasattr(optimizer, "refresh_device_hyper")
+        if self._device_hyper:
+            optimizer.sync_hyper_to_device()
         torch.cuda.synchronize(x.device)
         self.graph = torch.cuda.CUDAGraph()
-        self._captured_hyper = self._hyper()
+        self._baked_hyper = None if self._device_hyper else self._hyper()
         with torch.cuda.graph(self.graph):
             self.loss = self._eager()
 
     def _hyper(self):
-        """learning rate / weight decay reach the optimizer kernel as launch arguments: a replay repeats the captured ones"""
+        """other optimizers: learning rate / weight decay reach the kernels as launch arguments, a replay repeats the
+        captured ones"""
         return [(float(g.get("lr", 0.0)), float(g.get("weight_decay", 0.0))) for g in self.optimizer.param_groups]
 
     def _eager(self) -> torch.Tensor:
@@ -97,11 +105,10 @@ class GraphedTrainStep:
     def __call__(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         if x.shape != self.x.shape or y.shape != self.y.shape:
             raise ValueError(f"GraphedTrainStep was captured for {tuple(self.x.shape)} / {tuple(self.y.shape)}")
-        if self._hyper() != self._captured_hyper and hasattr(self.optimizer, "sync_hyper_to_device"):
-            self.optimizer.sync_hyper_to_device()          # device-side lr / weight decay: the graph reads them
-            self._captured_hyper = self._hyper()
-        if self._hyper() != self._captured_hyper:
-            raise RuntimeError(f"GraphedTrainStep: lr / weight_decay changed after capture ({self._captured_hyper} -> "
+        if self._device_hyper:
+            self.optimizer.refresh_device_hyper()          # writes lr / weight decay only when the device holds others
+        elif self._hyper() != self._baked_hyper:
+            raise RuntimeError(f"GraphedTrainStep: lr / weight_decay changed after capture ({self._baked_hyper} -> "
                                f"{self._hyper()}); the graph would keep training at the captured values -- build a new "
                                "GraphedTrainStep (one per learning-rate plateau) or step eagerly")
         self.x.copy_(x, non_blocking=True)

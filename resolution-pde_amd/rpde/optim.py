@@ -15,14 +15,18 @@ no moment update, no weight decay, its step count stands still.
 
 ``capturable=True`` keeps the step counter on the device (``rpde_adamw_step_dev``), which lets
 ``rpde.graph.GraphedTrainStep`` capture the step; it requires every parameter to take part in every step.
-``lr`` and ``weight_decay`` live in that device state too: an eager ``step()`` stores the group's current values there, a
-captured one reads them, and ``GraphedTrainStep`` calls ``sync_hyper_to_device()`` before a replay once a scheduler has
-moved them -- a captured step follows the schedule without being captured again.
+``lr`` and ``weight_decay`` live in that device state too: an eager ``step()``, ``sync_hyper_to_device()`` and
+``load_state_dict()`` store the group's current values there, a captured step reads whatever is there when it replays.
+The optimizer keeps a host record of the values it last stored (``device_hyper``): every writer of the device words
+goes through it -- eager steps of any batch shape, several ``GraphedTrainStep`` instances -- so before a replay
+``refresh_device_hyper()`` (called by ``GraphedTrainStep``) compares the group's values with that record and writes
+them only when they differ.  A captured step follows the schedule without being captured again, and a replay with
+nothing changed costs no extra launch.
 """
 from __future__ import annotations
 
 import math
-from typing import List, Optional
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -56,6 +60,8 @@ class FlatAdamW(torch.optim.Optimizer):
         self._sizes: List[int] = [p.numel() * (2 if p.is_complex() else 1) for p in group_params]
         self._steps: List[int] = [0] * len(group_params)
         self._step_dev = torch.zeros(8, dtype=torch.float32, device=dev) if capturable else None
+        # (lr, weight_decay) last written to _step_dev[3:5] (the zeros it starts with): what a replay would read now
+        self._dev_hyper: Optional[Tuple[float, float]] = (0.0, 0.0) if capturable else None
         for i, (p, gview) in enumerate(zip(group_params, self.bucket._views)):
             r = 1 if p.is_complex() else 0
             off, size = self._offsets[i] - bounds[r][0], self._sizes[i]
@@ -117,6 +123,8 @@ class FlatAdamW(torch.optim.Optimizer):
                 check(fn(self._p[r].data_ptr(), base_g + 4 * lo, self._m[r].data_ptr(), self._v[r].data_ptr(), hi - lo,
                          lr, b1, b2, eps, wd, self._step_dev.data_ptr(), st), "adamw_step_dev")
                 ticked = True
+            if not torch.cuda.is_current_stream_capturing():      # an eager step stored its lr / wd; a captured one did not
+                self._dev_hyper = (lr, wd)
             return loss
         # runs of parameters that are neighbours in a region, live, and share a step count -> one launch each
         # (normally: one per region)
@@ -143,14 +151,34 @@ class FlatAdamW(torch.optim.Optimizer):
             k = j + 1
         return loss
 
+    def _group_hyper(self) -> Tuple[float, float]:
+        g = self.param_groups[0]
+        return float(g["lr"]), float(g["weight_decay"])
+
+    @property
+    def device_hyper(self) -> Optional[Tuple[float, float]]:
+        """capturable: the (lr, weight_decay) a captured step reads when it replays now -- the values last written to
+        the device (None without capturable)"""
+        return self._dev_hyper
+
     def sync_hyper_to_device(self) -> None:
-        """capturable only: put the group's current lr / weight_decay where captured steps read them (rpde.graph calls
-        this before a replay when a scheduler has moved them)"""
+        """capturable only: put the group's current lr / weight_decay where captured steps read them (outside a capture;
+        one tiny launch)"""
         if self._step_dev is None:
             raise RuntimeError("FlatAdamW.sync_hyper_to_device: build the optimizer with capturable=True")
-        g = self.param_groups[0]
-        check(load().rpde_adamw_set_hyper_dev(self._step_dev.data_ptr(), float(g["lr"]), float(g["weight_decay"]), stream_ptr()),
-              "adamw_set_hyper_dev")
+        lr, wd = self._group_hyper()
+        check(load().rpde_adamw_set_hyper_dev(self._step_dev.data_ptr(), lr, wd, stream_ptr()), "adamw_set_hyper_dev")
+        self._dev_hyper = (lr, wd)
+
+    def refresh_device_hyper(self) -> bool:
+        """capturable only: sync_hyper_to_device() when the group's lr / weight_decay differ from what the device holds
+        (rpde.graph.GraphedTrainStep calls this before every replay); True when it wrote them"""
+        if self._step_dev is None:
+            raise RuntimeError("FlatAdamW.refresh_device_hyper: build the optimizer with capturable=True")
+        if self._group_hyper() == self._dev_hyper:
+            return False
+        self.sync_hyper_to_device()
+        return True
 
     # ---- torch.optim.AdamW-compatible checkpoints ---------------------------------------------------------------
     def state_dict(self):
@@ -181,3 +209,4 @@ class FlatAdamW(torch.optim.Optimizer):
         if self._step_dev is not None:
             self._step_dev.zero_()
             self._step_dev[0] = float(self._steps[0]) if self._steps else 0.0
+            self.sync_hyper_to_device()                         # the loaded group's lr / wd, not the zeros, for replays
