@@ -198,7 +198,8 @@ int rpde_spectral2d_bwd(const float* grad_out, const float* spec_in, const float
  * by; pass ds = NULL or ds[l] = NULL when no gradient is needed).  The last layer
  * stores z_last ([P,dim]) and out = residual + post_act( LayerNorm( dropout(z_last) ) )
  * (LN optional, residual may be NULL).  Dropout masks come from a counter hash of
- * (seed, layer, element). */
+ * (seed, layer, element) defined in csrc/drop_hash.h and restated in oracle/dropout_mask.py.
+ * Any n_layers >= 1 is accepted, forward and backward alike. */
 typedef struct {
   int n_layers; int dim; int factor;
   int layer_norm; float ln_eps;
@@ -211,7 +212,8 @@ typedef struct {
    * A hipGraph replays its launch arguments, so a host-drawn seed alone would repeat one mask for ever; the training
    * step advances this counter on the device once per step (between backward and the next forward), and forward and
    * backward of a step read the same value.  The reference draws its masks from torch's generator
-   * (models/custom_layer.py:60, nn.Dropout): parity is statistical either way. */
+   * (models/custom_layer.py:60, nn.Dropout): against it parity is statistical; against the float64 oracle fed the
+   * restated masks it is element by element (tests/test_gpu_dropout_parity.py). */
   const uint64_t* seed_epoch;
 } rpde_ff_params;
 size_t rpde_feedforward_ws_bytes(int64_t P, int dim, int factor, int n_layers);      /* backward */

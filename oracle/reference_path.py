@@ -131,12 +131,18 @@ def fspectral2d_fourier(x: Tensor, w_y: Tensor, w_x: Tensor, n_modes: int,
 # FeedForward  (models/custom_layer.py:49-68)
 # --------------------------------------------------------------------------
 def feedforward(x: Tensor, sd: Mapping[str, Tensor], prefix: str, n_layers: int,
-                layer_norm: bool, dropout: float = 0.0, training: bool = False) -> Tensor:
+                layer_norm: bool, dropout: float = 0.0, training: bool = False,
+                masks: Optional[Sequence[Tensor]] = None) -> Tensor:
     """Linear -> Dropout -> GELU (Identity on the last) -> LayerNorm (last, optional).
-    ``ff_weight_norm`` is accepted by the reference and ignored (quirk Q3)."""
+    ``ff_weight_norm`` is accepted by the reference and ignored (quirk Q3).
+    ``masks``: one factor tensor per layer (0 or the keep scale, shaped like that layer's output, e.g. from
+    ``oracle.dropout_mask``), multiplied in where the reference applies ``F.dropout``; it replaces ``F.dropout``
+    whatever ``dropout`` / ``training`` say."""
     for i in range(n_layers):
         x = F.linear(x, sd[f"{prefix}layers.{i}.0.weight"], sd[f"{prefix}layers.{i}.0.bias"])
-        if dropout > 0.0 and training:
+        if masks is not None:
+            x = x * masks[i].to(dtype=x.dtype).reshape(x.shape)
+        elif dropout > 0.0 and training:
             x = F.dropout(x, dropout, True)
         if i < n_layers - 1:
             x = F.gelu(x)
@@ -211,15 +217,21 @@ def fno2d_forward(sd: Mapping[str, Tensor], x: Tensor, n_blocks: int = 4,
     return conv_mlp(sd, h, "projection.")
 
 
+def _block_masks(masks, block: int, n_ff_layers: int):
+    return None if masks is None else [masks(block, l) for l in range(n_ff_layers)]
+
+
 # --------------------------------------------------------------------------
 # FFNO1D / FFNO2D forward  (models/ffno.py:96-125, 210-237)
 # --------------------------------------------------------------------------
 def ffno1d_forward(sd: Mapping[str, Tensor], x: Tensor, n_layers: int, n_modes: int,
                    n_ff_layers: int, layer_norm: bool, dropout: float = 0.0,
                    mode: str = "full", fft_norm: str = "ortho", activation: str = "identity",
-                   grid=None, training: bool = False) -> Tensor:
+                   grid=None, training: bool = False, masks=None) -> Tensor:
     """``use_grid`` is not a parameter: the reference overwrites it with
-    ``grid`` (quirk Q1), so the grid channel exists iff ``grid`` is truthy."""
+    ``grid`` (quirk Q1), so the grid channel exists iff ``grid`` is truthy.
+    ``masks``: optional callable ``(block, layer) -> factor tensor`` used instead of ``F.dropout``
+    in the FeedForward of every block (see ``feedforward``)."""
     b, _, n = x.shape
     if grid:
         g = torch.as_tensor(grid, dtype=torch.float).reshape(1, 1, n).repeat(b, 1, 1)
@@ -231,14 +243,16 @@ def ffno1d_forward(sd: Mapping[str, Tensor], x: Tensor, n_layers: int, n_modes: 
         t = h
         if mode != "no-fourier":
             t = fspectral1d_fourier(t, sd[p + "fourier_weight.0"], n_modes, mode, fft_norm)
-        t = feedforward(t, sd, p + "backcast_ff.", n_ff_layers, layer_norm, dropout, training)
+        t = feedforward(t, sd, p + "backcast_ff.", n_ff_layers, layer_norm, dropout, training,
+                        _block_masks(masks, i, n_ff_layers))
         h = h + act(t)
     return wn_linear(h, sd, "out_proj.").permute(0, 2, 1)
 
 
 def ffno2d_forward(sd: Mapping[str, Tensor], x: Tensor, n_layers: int, n_modes: int,
                    n_ff_layers: int, layer_norm: bool, dropout: float = 0.0,
-                   mode: str = "full", use_grid: bool = True, training: bool = False) -> Tensor:
+                   mode: str = "full", use_grid: bool = True, training: bool = False, masks=None) -> Tensor:
+    """``masks``: as in ``ffno1d_forward``."""
     b, _, m, n = x.shape
     if use_grid:
         gx = _lin(0.0, 1.0, m).reshape(1, 1, m, 1).repeat(b, 1, 1, n).to(x.device)
@@ -251,7 +265,8 @@ def ffno2d_forward(sd: Mapping[str, Tensor], x: Tensor, n_layers: int, n_modes: 
         if mode != "no-fourier":
             t = fspectral2d_fourier(t, sd[p + "fourier_weight.0"], sd[p + "fourier_weight.1"],
                                     n_modes, mode)
-        t = feedforward(t, sd, p + "backcast_ff.", n_ff_layers, layer_norm, dropout, training)
+        t = feedforward(t, sd, p + "backcast_ff.", n_ff_layers, layer_norm, dropout, training,
+                        _block_masks(masks, i, n_ff_layers))
         h = h + t
     return wn_linear(h, sd, "out_proj.").permute(0, 3, 1, 2)
 

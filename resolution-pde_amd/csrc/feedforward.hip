@@ -15,14 +15,9 @@
 #include "thin_linear.h"
 #include "conv_small.h"
 
-namespace rpde {
+#include <vector>
 
-static inline uint64_t layer_seed(uint64_t seed, int l) {
-  uint64_t z = seed + 0x9E3779B97F4A7C15ull * (uint64_t)(l + 1);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
+namespace rpde {
 
 // the thin-linear kernels move the wide operand as float4: a view with an odd storage offset takes the GEMM path
 static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -262,13 +257,13 @@ int rpde_feedforward_bwd(const rpde_ff_params* p, const float* x, const float* c
   hipStream_t st = as_stream(stream);
   const int L = p->n_layers;
   const int hid = L > 1 ? p->dim * p->factor : p->dim;
-  RPDE_CHECK_ARG(L <= 8, "feedforward_bwd: %d layers", L);
   Arena ar(ws, ws_bytes);
   float* buf0 = ar.take((size_t)P * hid);
   float* buf1 = ar.take((size_t)P * hid);
   // per layer: weight-gradient slabs, column-sum slabs, weight image (rpde_feedforward_ws_bytes) -- the regions of layer
   // 0 are followed by the others', so the fused path below may use them as one region of the largest layer's size
-  float* slabs_l[8]; float* csum_l[8]; float* wt_l[8];
+  // (any depth: folds and splits beyond the one-launch capacities of FoldJobs / SplitJobs run per layer)
+  std::vector<float*> slabs_l(L), csum_l(L), wt_l(L);
   for (int l = 0; l < L; ++l) slabs_l[l] = ar.take(wgrad_ws_floats(P, ff_in(p, l), ff_out(p, l)));
   for (int l = 0; l < L; ++l) csum_l[l] = ar.take((size_t)(colsum_tiles(P) + REDUCE_CHUNKS) * hid);
   for (int l = 0; l < L; ++l) wt_l[l] = ar.take(ff_wimg_floats(hid));

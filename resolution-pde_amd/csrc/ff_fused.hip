@@ -1039,10 +1039,7 @@ int ff3_fused_fwd(const rpde_ff_params* p, const float* x, const float* residual
   A.P = P; A.layer_norm = p->layer_norm; A.eps = p->ln_eps; A.post_act = p->post_act;
   for (int l = 0; l < 3; ++l) {
     // same (seed, layer) -> mask mapping as the per-GEMM path, so that rpde_feedforward_bwd regenerates the same masks
-    uint64_t z = p->seed + 0x9E3779B97F4A7C15ull * (uint64_t)(l + 1);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    A.drop[l] = make_drop(p->dropout_p, z ^ (z >> 31), p->seed_epoch);
+    A.drop[l] = make_drop(p->dropout_p, layer_seed(p->seed, l), p->seed_epoch);
   }
   A.ntiles = (int)((P + 31) / 32);
   int dev = 0, cus = 256;
@@ -1073,12 +1070,8 @@ int ff3_fused_bwd_launch(const rpde_ff_params* p, const float* const* ds, int re
   A.wimg = img; A.consts = consts; A.gamma = p->ln_gamma; A.beta = p->ln_beta; A.part = part;
   A.P = P; A.layer_norm = p->layer_norm; A.eps = p->ln_eps; A.post_act = p->post_act;
   DropCfg dc[3];
-  for (int l = 0; l < 3; ++l) {            // the forward's (seed, layer) -> mask mapping
-    uint64_t z = p->seed + 0x9E3779B97F4A7C15ull * (uint64_t)(l + 1);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    dc[l] = make_drop(p->dropout_p, z ^ (z >> 31), p->seed_epoch);
-  }
+  for (int l = 0; l < 3; ++l)              // the forward's (seed, layer) -> mask mapping
+    dc[l] = make_drop(p->dropout_p, layer_seed(p->seed, l), p->seed_epoch);
   A.drop0 = dc[0]; A.drop1 = dc[1]; A.drop2 = dc[2];
   A.dmax = 1.13f * A.drop2.scale;          // |gelu'| <= 1.129, times the dropout scale folded into d
   A.ntiles = (int)((P + 31) / 32);
