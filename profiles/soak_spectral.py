@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Soak of the fused spectral layer (k_dft_analysis_sq_h2 waits for its asm loads with hand-counted vmcnt): forward +
+"""Soak of the fused spectral layer (k_dft_analysis_rr_h2 waits for its asm loads with hand-counted vmcnt): forward +
 backward on grids of 64 .. 256 incl. those that leave waves without a duty, every result computed twice -- once with a
 copy stream hammering HBM beside it -- and compared bitwise (all reductions run in fixed order), and against the
 per-GEMM path.

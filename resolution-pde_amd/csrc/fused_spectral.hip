@@ -36,7 +36,7 @@ __device__ unsigned long long g_fstamps[2][64 * 32];
 // analysis operand of T[r][y] = src[r*rs + y*cs] (r < R, y < n): fragment (s, mt, piece) holds for lane l the
 // eight entries T[16 mt + (l & 15)][32 s + 8 (l >> 4) + j] * 2^12
 // perm: slot j of lane group g holds reduction index 32 s + 4 j + g instead of 32 s + 8 g + j (the points a lane of
-// k_dft_analysis_sq_h2 loads)
+// k_dft_analysis_rr_h2 loads)
 __global__ __launch_bounds__(64) void k_h2_table_ana(const float* __restrict__ src, long rs, long cs, int R, int n, int MT,
                                                      char* __restrict__ out, int perm) {
   const int f = blockIdx.x, l = threadIdx.x;
@@ -345,337 +345,37 @@ __global__ __launch_bounds__(64 * ANA_WAVES, 2) void k_dft_analysis_h2(const Ana
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// analysis of square grids, both axes out of ONE pass over HBM (round 3)
+// analysis of square grids, both axes out of ONE pass over HBM: the round-robin schedule (round 4)
 // ------------------------------------------------------------------------------------------------------------
 // k_dft_analysis_h2 reads the field twice -- once per axis -- and the second read comes from the Infinity Cache at
 // best, which streams no faster than HBM (profiles/r03_mall_bandwidth.txt: 6.1 vs 5.4 TB/s).  An L2 does (12 TB/s),
-// but it holds 4 MB per XCD.  So the two reads of every 32-row block (2 MB at 256^2) are brought together in time and
-// in place: the 32 workgroups of one XCD group (blockIdx % 8; placement is a speed matter only) walk through a sample
-// row block by row block, and in step t
-//   * every wave owns one COLUMN of the sample for the whole sample (256 waves per group = 256 columns) and adds the
-//     32 rows of block t to its x-axis accumulators (one chunk of 32 points, 256 B apart by the row length);
-//   * every workgroup owns one ROW of the block: its eight waves take one 32-point chunk of the row each, and the eight
-//     partial y-axis spectra are summed through LDS (two halves of the channels, 48 KB).
-// Each step reads its 2 MB row block once by rows and once by columns, within microseconds of each other, on one
-// XCD.  No inter-workgroup synchronisation: the workgroups of a group run the same schedule and drift only by
-// scheduling noise.  Needs M = N (one table for both axes).
-// Grids below 256: a row has n / 32 < 8 chunks, so a workgroup takes rpw = 8 / (n / 32) rows of the block (wave ->
-// (row, chunk)) and a group is 32 / rpw workgroups -- 8 * 32 / rpw waves >= n columns -- so that at 128^2 and 64^2 every
-// wave has a column and a chunk as well; the chip then holds 8 rpw groups, each walking through its own samples
-// (with one row per workgroup whatever the grid, 128^2 ran at 81 us for a quarter of the bytes of 256^2's 212 us).
-struct AnaSqP {
-  const float* x; const char* timg;
-  float* spec_y; float* spec_x; float* amax_y; float* amax_x;
-  int B, n, ks, R, ng, rpw;
-  int b1;          // 1: keep the (redundant) barrier in front of the partial-spectrum writes
-};
-
-template <int MT>
-__global__ __launch_bounds__(64 * ANA_WAVES, 2) void k_dft_analysis_sq_h2(const AnaSqP P) {
-  constexpr int TAB = ANA_MAXKS * MT * 2048, STG = ANA_WAVES * 8192, RED = ANA_WAVES * MT * 2 * 1024;
-  __shared__ __attribute__((aligned(16))) char smem[TAB + STG + RED];         // 160 KB at MT = 3: all of it
-  // (wave through readfirstlane: everything derived from it -- duties, wait counts -- is then uniform for the compiler
-  //  too: scalar branches instead of exec masks, and the if / else chain of waits below is one the ISA test can follow)
-  const int tid = threadIdx.x, l = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), g = l >> 4, li = l & 15;
-  char* const stage = smem + TAB + wave * 8192;
-  // per-wave partial maxima of a row's spectrum: the last 32 bytes of the reduction area (the landing zone of the
-  // partial spectra ends 16 KB before it)
-  float* const wmax = reinterpret_cast<float*>(smem + TAB + STG + RED - 256);     // [row of the workgroup][wave]
-  const int q = li >> 2, pp = li & 3;
-  const int tsw = ((q >> 1) & 1) | ((g & 1) << 1);
-  const int trow = (8 * g + q) * 128 + pp * 8;
-  typedef s16x4v __attribute__((address_space(3))) * lds_tr;
-
-  const int n = P.n, steps = P.ks;                 // rows per sample = columns = n; row blocks = chunks per row = n / 32
-  const int xg = blockIdx.x % P.ng, jw = blockIdx.x / P.ng, gw = jw * ANA_WAVES + wave;
-  const int nsamp = (P.B - xg + P.ng - 1) / P.ng;
-  const long units = (long)nsamp * steps;           // (sample, row block) pairs of this group, in order
-  const int rpw = P.rpw, yr = wave / steps, yc = wave - yr * steps;      // this wave's row of the workgroup's rows, its chunk
-  const bool has_x = gw < n, has_y = wave < rpw * steps;
-  if (units <= 0) return;                           // (more groups than samples)
-  {
-    const uint4* src = reinterpret_cast<const uint4*>(P.timg);
-    uint4* dst = reinterpret_cast<uint4*>(smem);
-    for (int i = tid; i < steps * MT * 128; i += 64 * ANA_WAVES) dst[i] = src[i];
-    if (tid < 64) wmax[tid] = 0.f;
-    __syncthreads();
-  }
-  const long rowf = (long)n * 64;                   // floats per row of the field
-  // The field comes through registers, one unit ahead -- by loads the compiler does not see (asm) and waits counted by
-  // hand.  Left to the compiler every use of a prefetched chunk is preceded by s_waitcnt vmcnt(0..7): it takes the
-  // chunk for the youngest thing in flight, so each phase also waits for the OTHER axis's chunk, requested only a
-  // phase ago, and for the spectrum stores in between -- the prefetch distance shrinks from a unit to nothing (this
-  // kernel ran at 219 us, latency-bound).  The queue is in order: behind the x chunk of unit u there are always the 8
-  // loads of the y chunk of u (and some stores), behind the y chunk of u the 8 loads of the x chunk of u + 1; so
-  // vmcnt(8) is enough in both places.  Every wave issues exactly 8 loads per phase (past the end: a
-  // clamped re-read; without a duty: a neighbour's chunk), so the count holds for all.
-  auto gload = [](const float* p) {
-    f32x4v v;
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v) : "v"(p) : "memory");
-    return v;
-  };
-  // (a wave without a column or without a chunk -- grids that are no power of two -- loads a neighbour's: every wave
-  //  issues the same 16 loads per unit and the counts below hold for all)
-  const int gwc = has_x ? gw : n - 1, yrc = has_y ? yr : 0, ycc = has_y ? yc : 0;
-  auto issue_x = [&](f32x4v (&buf)[8], long u) {    // column gw, rows of block t: lane (g, li) takes rows 4i + g
-    u = u < units ? u : units - 1;
-    const int sb = (int)(u / steps), t = (int)(u - (long)sb * steps);
-    const float* q0 = P.x + (((long)(xg + P.ng * sb) * n + 32 * t + g) * n + gwc) * 64 + li * 4;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) buf[i] = gload(q0 + i * 4 * rowf);
-  };
-  auto issue_y = [&](f32x4v (&buf)[8], long u) {    // row 32 t + rpw jw + yr, points 32 yc ..: lane (g, li) takes points 4i + g
-    u = u < units ? u : units - 1;
-    const int sb = (int)(u / steps), t = (int)(u - (long)sb * steps);
-    const float* q0 = P.x + (((long)(xg + P.ng * sb) * n + 32 * t + rpw * jw + yrc) * n + 32 * ycc + g) * 64 + li * 4;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) buf[i] = gload(q0 + i * 256);
-  };
-  // The chunk in buf has landed once at most N later vector-memory instructions are outstanding.  N counts what is
-  // CERTAIN to have been issued behind it: the other axis's 8 loads and this wave's spectrum stores of the reduction in
-  // between (`nst`, wave-uniform: the items of the reduction loop whose first lane group has a valid row, plus the line
-  // maximum written by wave 0) -- with the stores counted in, a wave no longer waits for their acknowledgement before
-  // it may touch data that arrived long ago (1.2-1.7 K of 13 K cycles per step).
-  int nst_wave = 0;
-  for (int e = 64 * wave; e < rpw * MT * 256; e += 64 * ANA_WAVES) {
-    const int rem = e % (MT * 256);
-    nst_wave += (16 * (rem >> 8) + ((rem >> 6) & 3)) < P.R ? 1 : 0;
-  }
-  if (wave == 0 && P.amax_y) ++nst_wave;
-  nst_wave = __builtin_amdgcn_readfirstlane(nst_wave);
-  // ONE statement per wait, the choice of the count inside it (scalar compare + branch on nst): the chunk's registers
-  // pass through it as tied operands -- that is what orders their uses behind the wait -- and with one statement per
-  // alternative count the register allocator gave the four statements' operands other registers than the loads' and
-  // copied in front of the wait, i.e. read registers whose loads were in flight (seen in the MT = 1 instance;
-  // tests/test_isa_pending_loads_cpu.py follows the `landed` comment, which names the registers).  The very first
-  // chunks have no stores behind them: the loop waits for everything before its first unit instead.
-  auto landed = [&](f32x4v (&buf)[8]) {
-    asm volatile(
-        "s_cmp_lt_u32 %8, 2\n\t"
-        "s_cbranch_scc1 1f\n\t"
-        "s_cmp_eq_u32 %8, 2\n\t"
-        "s_cbranch_scc1 2f\n\t"
-        "s_waitcnt vmcnt(11)\n\t"
-        "s_branch 4f\n"
-        "2:\n\t"
-        "s_waitcnt vmcnt(10)\n\t"
-        "s_branch 4f\n"
-        "1:\n\t"
-        "s_cmp_eq_u32 %8, 1\n\t"
-        "s_cbranch_scc1 3f\n\t"
-        "s_waitcnt vmcnt(8)\n\t"
-        "s_branch 4f\n"
-        "3:\n\t"
-        "s_waitcnt vmcnt(9)\n"
-        "4:\n\t"
-        "s_nop 0 ; landed %0 %1 %2 %3 %4 %5 %6 %7"
-        : "+v"(buf[0]), "+v"(buf[1]), "+v"(buf[2]), "+v"(buf[3]), "+v"(buf[4]), "+v"(buf[5]), "+v"(buf[6]), "+v"(buf[7])
-        : "s"(nst_wave)
-        : "memory", "scc");
-  };
-  // one 32-point chunk into accumulators that stay in scaled units for the whole line (k_dft_analysis_h2's scheme)
-  auto process = [&](f32x4v (&buf)[8], int s, f32x4v (&tot)[MT][4], int& line_E) {
-    float m = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-      m = fmaxf(m, fmaxf(fmaxf(fabsf(buf[i].x), fabsf(buf[i].y)), fmaxf(fabsf(buf[i].z), fabsf(buf[i].w))));
-    m = wave_max(m);
-    {
-      const int E = max((int)(__float_as_uint(m) >> 23) & 0xff, 15 + H2_TABLE_EXP);
-      if (E > line_E) {
-        if (line_E > 0) {
-          const float f = __uint_as_float((unsigned)(127 + line_E - E) << 23);
-#pragma unroll
-          for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-              for (int j = 0; j < 4; ++j) tot[mt][nt][j] *= (E - line_E < 126 ? f : 0.f);
-        }
-        line_E = E;
-      }
-    }
-    // No staging: the eight points a lane loaded for channel 4 li + e (buf[0..7], component e) ARE the eight reduction
-    // slots of its lane group in a B fragment whose column li stands for channel 4 li + e -- the table image carries the
-    // matching permutation of the reduction index (h2_ana_p).  Four fragments (e = 0..3) instead of four channel tiles;
-    // accumulator column li of tot[mt][e] is channel 4 li + e.
-    const float scale = __uint_as_float((unsigned)(268 - line_E) << 23);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      union { f16x8 v; struct { uint2 a, b; } u; } H, L;
-      h2_split4(buf[0][e] * scale, buf[1][e] * scale, buf[2][e] * scale, buf[3][e] * scale, H.u.a, L.u.a);
-      h2_split4(buf[4][e] * scale, buf[5][e] * scale, buf[6][e] * scale, buf[7][e] * scale, H.u.b, L.u.b);
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) {
-        const char* ta = smem + (s * MT + mt) * 2048 + l * 16;
-        const f16x8 ah = *reinterpret_cast<const f16x8*>(ta), al = *reinterpret_cast<const f16x8*>(ta + 1024);
-        tot[mt][e] = h2_mfma32(ah, al, H.v, L.v, tot[mt][e]);
-      }
-    }
-  };
-
-  f32x4v totx[MT][4], toty[MT][4];
-  int Ex = 0;
-  f32x4v bx[8], by[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) bx[i] = by[i] = (f32x4v){0.f, 0.f, 0.f, 0.f};
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // (the table copy above: from here on the queue is counted by hand)
-  issue_x(bx, 0);
-  issue_y(by, 0);
-#ifdef RPDE_STAMPS
-  const bool stamp_wave = l == 0 && wave == 3 && blockIdx.x >= 96 && blockIdx.x < 160;
-  const int stamp_slot = (int)blockIdx.x - 96;
-#endif
-  for (long u = 0; u < units; ++u) {
-    const int sb = (int)(u / steps), t = (int)(u - (long)sb * steps);
-    const int b = xg + P.ng * sb;
-#ifdef RPDE_STAMPS
-    // units 9, 10, 11 (second sample, mid-line): 10 stamps each
-    const bool stamp_on = stamp_wave && u >= 9 && u < 12;
-    const int sq0 = (int)(u - 9) * 10;
-#endif
-    FSTAMP(0, sq0 + 0);
-    // (x first.  The other order -- whole 64 KB rows going to HBM, the x axis's 256-byte pieces finding them in L2 -- was
-    //  measured: same time, but 604 instead of 553 MB fetched per launch)
-    // ---- x axis: this wave's column, rows of block t ----
-    // EVERY wave waits for its chunk, with or without a duty: once the asm statement has returned the compiler takes
-    // the registers for filled, and where the values are not used it hands the registers to something else -- here the
-    // 64-bit division of the next address computation -- which a load still in flight then overwrites (found as a
-    // memory-aperture fault at 96^2 in training, never in the tests: a wave without a column skipped the wait)
-    if (u == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // (no stores behind the first chunks yet)
-    landed(bx);
-    if (has_x) {
-      if (t == 0) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < 4; ++nt) totx[mt][nt] = (f32x4v){0.f, 0.f, 0.f, 0.f};
-        Ex = 0;
-      }
-      FSTAMP(0, sq0 + 8);
-      process(bx, t, totx, Ex);
-    }
-    issue_x(bx, u + 1);                               // (every wave, with or without a column: the counts rely on it)
-    if (has_x) {
-      if (t == steps - 1) {
-        const long z = (long)b * n + gw;
-        float* __restrict__ sp = P.spec_x + z * (long)P.R * 64;
-        const float inv = __uint_as_float((unsigned)(Ex - 14 - H2_TABLE_EXP) << 23);
-        float am = 0.f;
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const int row = 16 * mt + 4 * g + j;
-            if (row < P.R)
-              *reinterpret_cast<float4*>(sp + row * 64 + 4 * li) =
-                  make_float4(totx[mt][0][j] * inv, totx[mt][1][j] * inv, totx[mt][2][j] * inv, totx[mt][3][j] * inv);
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) am = fmaxf(am, fabsf(totx[mt][nt][j]));
-          }
-        am = wave_max(am);
-        if (l == 0 && P.amax_x) P.amax_x[z] = am * inv;
-      }
-    }
-    // ---- y axis: row 32 t + jw of the block; this wave's chunk of it, then the sum over the chunks ----
-    float invy = 0.f;
-    landed(by);
-    if (has_y) {
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) toty[mt][nt] = (f32x4v){0.f, 0.f, 0.f, 0.f};
-      int Ey = 0;
-      FSTAMP(0, sq0 + 1);
-      process(by, yc, toty, Ey);
-      invy = __uint_as_float((unsigned)(Ey - 14 - H2_TABLE_EXP) << 23);
-    }
-    issue_y(by, u + 1);
-    const long zy = (long)b * n + 32 * t + rpw * jw;      // the first of this workgroup's rows
-    // the eight partial spectra of the row -> one: every wave is done with its staging area until the next step, so the
-    // staging areas + the reduction area together take all partials at once ([wave][mt][nt][lane] float4, 4 MT KB per
-    // wave), one pass, two barriers
-    char* const land = smem + TAB;                  // STG + RED = 112 KB >= 8 waves x 12 KB
-    FSTAMP(0, sq0 + 2);
-    // (round 3 had a barrier here, from the time the chunks went through the staging areas that are now part of the landing
-    //  zone; since the chunks stay in registers nothing reads or writes the zone between the previous step's last barrier
-    //  and these writes.  RPDE_ANA_B1=1 brings it back for an A/B.)
-    if (P.b1) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    FSTAMP(0, sq0 + 3);
-    // a lane's four fragments e = 0..3 hold channels 4 li .. 4 li + 3 of its rows: the partials land as
-    // [wave][mt][j][lane] float4 over those four channels, so the sum over the waves is a float4 per (row, li) and the
-    // spectrum leaves in 16-byte pieces, 256 contiguous bytes per 16 lanes (4-byte scattered stores made this phase the
-    // longest of a step: 3-3.8 K of 13.5 K cycles)
-    if (has_y) {
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          *reinterpret_cast<float4*>(land + ((wave * MT + mt) * 4 + j) * 1024 + l * 16) =
-              make_float4(toty[mt][0][j] * invy, toty[mt][1][j] * invy, toty[mt][2][j] * invy, toty[mt][3][j] * invy);
-    }
-    FSTAMP(0, sq0 + 4);
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    FSTAMP(0, sq0 + 5);
-    for (int e = tid; e < rpw * MT * 256; e += 64 * ANA_WAVES) {            // (a wave's 64 items of a pass share the row)
-      const int rr = e / (MT * 256), rem = e - rr * (MT * 256);
-      const int mt = rem >> 8, j = (rem >> 6) & 3, ln = rem & 63;
-      float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-      for (int c2 = 0; c2 < ANA_WAVES; ++c2) {             // (all reads in flight: the row's chunks sit in consecutive waves)
-        if (c2 < steps) {
-          const float4 v = *reinterpret_cast<const float4*>(land + (((rr * steps + c2) * MT + mt) * 4 + j) * 1024 + ln * 16);
-          a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-        }
-      }
-      const int row = 16 * mt + 4 * (ln >> 4) + j;
-      float am = 0.f;
-      if (row < P.R) {
-        *reinterpret_cast<float4*>(P.spec_y + (zy + rr) * (long)P.R * 64 + row * 64 + 4 * (ln & 15)) = a;
-        am = fmaxf(fmaxf(fabsf(a.x), fabsf(a.y)), fmaxf(fabsf(a.z), fabsf(a.w)));
-      }
-      am = wave_max(am);
-      if (l == 0) wmax[rr * ANA_WAVES + wave] = fmaxf(wmax[rr * ANA_WAVES + wave], am);   // (its own 256 bytes behind the landing zone)
-    }
-    FSTAMP(0, sq0 + 6);
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // the landing zone has been read: staging may be reused
-    FSTAMP(0, sq0 + 7);
-    if (tid < rpw) {                                  // (the next step's maxima are written two barriers from here)
-      float a8 = 0.f;
-      for (int i = 0; i < ANA_WAVES; ++i) { a8 = fmaxf(a8, wmax[tid * ANA_WAVES + i]); wmax[tid * ANA_WAVES + i] = 0.f; }
-      if (P.amax_y) P.amax_y[zy + tid] = a8;
-    }
-    FSTAMP(0, sq0 + 9);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // (the re-reads past the end)
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// analysis of square grids, one pass over HBM and NO cross-wave reduction: the round-robin schedule (round 4)
-// ------------------------------------------------------------------------------------------------------------
-// k_dft_analysis_sq_h2 reads the field once, but a row's eight 32-point chunks sit in eight waves and their partial
-// spectra are summed through 96 KB of LDS behind two barriers per step -- in-kernel stamps put 5.8 K of a step's 12.3 K
-// cycles there, against 4.3 K for the chunks themselves.  The sum exists because in a 32-row block every wave has one
-// chunk of a column (32 rows) but only an eighth of a row.  It goes away if a wave meets its WHOLE row over the rounds of
-// a sample the way it already meets its whole column: cut the sample into nb x nb tiles of 32 x 32 points (nb = n / 32)
-// and let wave gw of a group own row gw AND column gw.  In round t the wave in band i = gw / 32 adds
+// but it holds 4 MB per XCD, so the two reads of a piece of the field must come close together in time and place.
+// The retired row-block kernel (round 3) walked a sample 32-row block by block and read the field
+// once, but a row's eight 32-point chunks sat in eight waves and their partial spectra were summed through 96 KB of LDS
+// behind two barriers per step -- in-kernel stamps put 5.8 K of a step's 12.3 K cycles there, against 4.3 K for the
+// chunks themselves.  The sum exists because in a 32-row block every wave has one chunk of a column (32 rows) but only
+// an eighth of a row.  It goes away if a wave meets its WHOLE row over the rounds of a sample the way it already meets
+// its whole column: cut the sample into nb x nb tiles of 32 x 32 points (nb = n / 32) and let wave gw of a group own
+// row gw AND column gw.  In round t the wave in band i = gw / 32 adds
 //   * to its row accumulators    the 32 points of its row    that lie in tile (i, i + t),      and
 //   * to its column accumulators the 32 points of its column that lie in tile (i - t, i)       (indices mod nb).
 // Tile (a, b) is then read in round b - a by the waves of band a (as rows) and by the waves of band b (as columns): both
 // in the SAME round -- a tournament schedule -- so the second read finds the tile in the L2 of the XCD that the group's
-// workgroups share (placement is a speed matter only), exactly the 2 MB per round that the row-block walk keeps there.
+// workgroups share (placement is a speed matter only), exactly the 2 MB per round that the row-block walk kept there.
 // After nb rounds every wave holds one finished row spectrum and one finished column spectrum.  No landing zone, no
 // partial sums, no barrier after the table is in LDS; the table (48 KB) is all the LDS the kernel uses; every wave has a
 // row and a column on every grid (a group is exactly n waves = n / 8 workgroups), so the idle-wave cases of the
 // row-block kernel (and the memory fault they once caused) do not exist here.
-// Loads: inline asm one round ahead, as there; behind a chunk there are always the 8 loads of the other axis's chunk, so
-// a fixed vmcnt(8) covers it (the 20-odd spectrum stores of a sample's last round only make that wait longer).
+// Loads: inline asm one round ahead, waits counted by hand (left to the compiler, every use of a prefetched chunk also
+// waits for everything issued behind it: DESIGN.md section 3.1); behind a chunk there are always the 8 loads of the
+// other axis's chunk, so a fixed vmcnt(8) covers it (the 20-odd spectrum stores of a sample's last round only make that
+// wait longer).
 // Measured (profiles/r04_analysis_variants.txt; 256^2, B = 32, same box within a pair; FETCH = 2 x FETCH_SIZE):
-//   row-block kernel k_dft_analysis_sq_h2 ............................ 208 us, 551 MB fetched
+//   the retired row-block kernel ..................................... 208 us, 551 MB fetched
 //   this kernel, every wave free-running ............................. 213 us, 847 MB  (waves of a workgroup drift apart:
 //                                                                              the second reader of a tile comes too late)
-//   + odd bands take their row chunk first (RPDE_RR_PARITY) .......... 226 us, 838 MB
-//   + ONE s_barrier per round (RPDE_RR_BARRIER; no LDS traffic) ...... 196 us, 565 MB  <- shipped
+//   + odd bands take their row chunk first ........................... 226 us, 838 MB
+//   + ONE s_barrier per round (no LDS traffic) ....................... 196 us, 565 MB  <- shipped
 // In-kernel stamps of the shipped form (profiles/fused_stamps.py): of a round's ~13 K cycles the two chunks take 2 x 1.6 K;
 // ISSUING a chunk's eight loads takes 1.5-4 K -- the CU's vector-memory pipeline accepts a 1 KB wave-load every ~100
 // cycles once its queues are full, i.e. ~10 bytes per cycle and CU (the HBM-bound streaming rate of
@@ -683,12 +383,6 @@ __global__ __launch_bounds__(64 * ANA_WAVES, 2) void k_dft_analysis_sq_h2(const 
 // that pipeline TWICE (once per axis; the second time from L2 at about twice the rate): 2.1 MB / 10 + 2.1 MB / 23 +
 // 0.66 MB / 10 bytes per cycle = 0.37 M cycles = 185 us at 2 GHz.  The kernel is at the rate of the bytes its CUs load,
 // not of the bytes HBM delivers; only loading each byte once per CU would change that.
-#ifndef RPDE_RR_PARITY
-#define RPDE_RR_PARITY 1
-#endif
-#ifndef RPDE_RR_BARRIER
-#define RPDE_RR_BARRIER 1
-#endif
 struct AnaRrP {
   const float* x; const char* timg;
   float* spec_y; float* spec_x; float* amax_y; float* amax_x;
@@ -723,7 +417,7 @@ __global__ __launch_bounds__(64 * ANA_WAVES, 2) void k_dft_analysis_rr_h2(const 
   // Odd bands therefore take their row chunk first, even bands their column chunk: every tile of an odd round (a and
   // a + t of different parity) is then requested by both its readers in the same half.  The order is fixed per wave --
   // the two accumulator sets are bound to "first" and "second", so nothing in the loop depends on it but addresses.
-  const bool row_first = RPDE_RR_PARITY && (band & 1);
+  const bool row_first = band & 1;
   // chunk `half` (0: first, 1: second) of round u into buf: a row chunk (points of band (band + t) mod nb, lane (g, li)
   // takes points 4 i + g, channels 4 li ..) or a column chunk (rows of band (band - t) mod nb).  Past the end: a clamped
   // re-read, so that every round issues the same 16 loads.  Returns the table chunk that goes with it.
@@ -752,8 +446,10 @@ __global__ __launch_bounds__(64 * ANA_WAVES, 2) void k_dft_analysis_rr_h2(const 
                  :
                  : "memory");
   };
-  // one 32-point chunk into accumulators that stay in scaled units for the whole line (k_dft_analysis_sq_h2's scheme:
-  // running power-of-two scale, no staging -- the loaded registers ARE the B fragments under the permuted table image)
+  // one 32-point chunk into accumulators that stay in scaled units for the whole line (k_dft_analysis_h2's running
+  // power-of-two scale).  No staging: the eight points a lane loaded for channel 4 li + e (buf[0..7], component e) ARE
+  // the eight reduction slots of its lane group in a B fragment whose column li stands for channel 4 li + e -- the table
+  // image carries the matching permutation of the reduction index (h2_ana_p)
   auto process = [&](f32x4v (&buf)[8], int s, f32x4v (&tot)[MT][4], int& line_E) {
     float m = 0.f;
 #pragma unroll
@@ -834,7 +530,7 @@ __global__ __launch_bounds__(64 * ANA_WAVES, 2) void k_dft_analysis_rr_h2(const 
     const int stamp_slot = (int)blockIdx.x - 96, sq0 = (int)(u - 9) * 7;
 #endif
     FSTAMP(0, sq0 + 0);
-    if (RPDE_RR_BARRIER) asm volatile("s_barrier" ::: "memory");      // (keeps the eight waves of a workgroup in one round)
+    asm volatile("s_barrier" ::: "memory");      // (keeps the eight waves of a workgroup in one round)
     FSTAMP(0, sq0 + 1);
     landed(ba);
     FSTAMP(0, sq0 + 2);
@@ -1079,10 +775,10 @@ __global__ __launch_bounds__(256, 2) void k_dft_synthesis2_h2(const SynP P) {
 //     stages (and the tables) of the NEXT tile are requested during the last stages of the current one.  In-kernel
 //     stamps of the first, one-tile-per-workgroup version: 33 % of a workgroup's life was the cold start of its DMA
 //     queue, 29 % the burst of stores at its end.
-//   * forward: the stores of a tile are spread over eight stages, four 16-byte stores per wave and stage (a 4 x 4
-//     transpose inside each quad of lanes gives every lane four consecutive channels of one point); column block 1 of
-//     a tile leaves during the x stages of the next tile.  Adjoint with a skip gradient: loads + stores in four batches
-//     after the last stage.
+//   * it serves the adjoint with a skip gradient (the forward and the adjoint without one run k_dft_synthesis4_h2):
+//     loads of the skip gradient + stores in four batches after the last stage, 16 bytes per lane (a 4 x 4 transpose
+//     inside each quad of lanes gives every lane four consecutive channels of one point).  (The retired forward
+//     instances spread the stores over the eight stages instead; the measurements below are theirs.)
 //   * what bounds it now (measured with the parts switched off one at a time, 256^2, B = 32): DMA skeleton alone 76 us,
 //     + MFMAs 25 us, + stores 130 us; HBM traffic 0.30 GB read + 0.54 GB written in 215-230 us.  Burst or spread, in step
 //     or staggered across XCDs, 4-byte or 16-byte stores: the store time adds to the rest (a CU's memory pipeline
@@ -1136,7 +832,7 @@ struct Syn3Item {
   long o;                               // float offset of the tile's first point, first channel of the block
 };
 
-template <int K32, int TG, bool SKIP>
+template <int K32, int TG>
 __global__ __launch_bounds__(64 * SYN3_WAVES, 2) void k_dft_synthesis3_h2(const SynP P) {
   constexpr int NP = h2_np(TG), NF = 2 * K32 + NP;
   constexpr int BB = NF * 1024;
@@ -1144,7 +840,6 @@ __global__ __launch_bounds__(64 * SYN3_WAVES, 2) void k_dft_synthesis3_h2(const 
   constexpr int SLOT = 16 * BB;                 // one stage: 16 lines
   static_assert(NF <= 3, "ring of three 16-line slots + the table corner must fit 160 KB");
   constexpr int TAB = 3 * SLOT, INV = TAB + 4 * BB, LDS_BYTES = INV + 512;
-  constexpr int NST = SKIP ? 0 : 8;             // stores a wave issues at the end of a y stage
   __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
   const int tid = threadIdx.x, l = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), g = l >> 4, li = l & 15;
   const int mt = w & 3, p = w >> 2;
@@ -1247,10 +942,8 @@ __global__ __launch_bounds__(64 * SYN3_WAVES, 2) void k_dft_synthesis3_h2(const 
   bool first = true;
   const int qd = li >> 2, pl = li & 3;
   // acc[a][i][jj]: x phase -- column i of column block a, rows m = 4g + jj; after the turn, physical register
-  // [a][4 (r >> 2) + j][r & 3] holds row r, column 4g + j.  Lives across tiles: column block 1 of a finished tile is
-  // stored while the x stages of the next tile refill column block 0 (below).
+  // [a][4 (r >> 2) + j][r & 3] holds row r, column 4g + j
   float acc[2][16][4];
-  long o_prev = 0;
 
   while (true) {
     const long qn = q + nj;
@@ -1271,20 +964,6 @@ __global__ __launch_bounds__(64 * SYN3_WAVES, 2) void k_dft_synthesis3_h2(const 
       quad_transpose(v.x, v.y, v.z, v.w);
       return v;
     };
-    // forward: the stores of a tile are spread evenly over EIGHT stages, four per wave and stage -- a CU's store path
-    // takes ~60-90 cycles per 16-segment store instruction, so the 256 KB of a tile need about as long as all its other
-    // work, and issued in one burst (at the end of the tile, or over its four y stages) they simply added their time
-    // to it (measured: 139 of 229 us).  Rows 4k .. 4k + 3 of column block 0 leave at the end of y stage k (they are
-    // final then), rows 4k .. 4k + 3 of column block 1 at the START of x stage k of the NEXT tile: x stage s refills
-    // the registers of rows 8 (s & 1) .. + 7 of column block s >> 1, so block 0 is free when the next tile begins and
-    // every row group of block 1 has left before its registers are written again.
-    auto store_rows = [&](long obase, int k, int a) {
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        const int r = 4 * k + rr;
-        *reinterpret_cast<float4*>(P.out + obase + ((long)r * P.N + 32 * a) * 64) = tile_out(r, a);
-      }
-    };
 #ifdef RPDE_STAMPS
     const bool stamp_on = l == 0 && w == 5 && blockIdx.x >= 96 && blockIdx.x < 160 && q == jw + 2 * (long)nj;
     const int stamp_slot = (int)blockIdx.x - 96;
@@ -1293,23 +972,19 @@ __global__ __launch_bounds__(64 * SYN3_WAVES, 2) void k_dft_synthesis3_h2(const 
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
       // ---- this wave's pieces of stage s have landed.  vmcnt(N): everything but the N youngest operations of this wave
-      // is done; younger than the pieces of stage s are the pieces of stage s + 1 (2 NF) and the stores of the y stages
-      // in between (NST each); a wait that also covers table / scale pieces issued in between only over-waits
-      // (forward: + the stores in between: 4 at the end of every y stage, 4 at the start of every x stage but the first tile's)
+      // is done; younger than the pieces of stage s are the pieces of stage s + 1 (2 NF); a wait that also covers table /
+      // scale pieces issued in between only over-waits
       // (cw.h: the requests of stage s are marked with the tag s % 3 behind their last piece, and the ISA test checks
       //  these counts on the compiled code)
-      constexpr int Q = SKIP ? 0 : 4;
       const int T = s % 3;
       // (every stage requests its pieces, the last tile's stages 6 / 7 a harmless re-read: no count depends on has_next.
-      //  The forward instances' counts for stages 2 .. 5 still depend on `first` through the stores at the start of the x
-      //  stages, which the path-insensitive ISA check cannot follow: it covers the SKIP instances -- the ones the default
-      //  dispatch uses; the forward runs k_dft_synthesis4_h2.)
-      if (SKIP && !first && s < 2) cw_wait_t<63>(T);                       // (behind the 64 loads / stores of the epilogue)
+      //  The arms below that wait alike are kept apart on purpose: merged, they compile to other register assignments.)
+      if (!first && s < 2) cw_wait_t<63>(T);                       // (behind the 64 loads / stores of the epilogue)
       else if (first && s < 2) { if (s == 0) cw_wait<3, 2 * NF>(); else cw_wait<4, 2 * NF>(); }
       else if (first && s < 5) cw_wait_t<2 * NF>(T);
-      else if (s == 0 || s == 1 || s == 6) cw_wait_t<2 * NF + 2 * Q>(T);
-      else if (s <= 5) cw_wait_t<2 * NF + Q>(T);
-      else cw_wait_t<2 * NF + 2 * Q>(T);
+      else if (s == 0 || s == 1 || s == 6) cw_wait_t<2 * NF>(T);
+      else if (s <= 5) cw_wait_t<2 * NF>(T);
+      else cw_wait_t<2 * NF>(T);
       FSTAMP(1, 1 + 3 * s);
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // everyone's have; everyone is done with stage s - 1
       FSTAMP(1, 2 + 3 * s);
@@ -1322,7 +997,6 @@ __global__ __launch_bounds__(64 * SYN3_WAVES, 2) void k_dft_synthesis3_h2(const 
       };
       // tables: the y-axis blocks replace the x-axis blocks once every wave has its x block in registers (stage 0); the
       // next tile's x blocks and scales replace them once every wave has its y blocks (stage 4)
-      if (!SKIP && s < 4 && !first) store_rows(o_prev, s, 1);
       if (s == 1) issue_table(cur.ty, true);
       if (s == 5 && has_next) { issue_table(nxt.tx, false); issue_inv(nxt); }
       const char* slot = smem + slot_s * SLOT + l * 16;
@@ -1395,11 +1069,10 @@ __global__ __launch_bounds__(64 * SYN3_WAVES, 2) void k_dft_synthesis3_h2(const 
           }
         }
         cw_mark_t(s + 2 < 8 ? (s + 2) % 3 : (s - 6) % 3);      // the pieces of stage s + 2 (of the next tile: s - 6)
-        if (!SKIP) store_rows(o, sy, 0);
       }
       FSTAMP(1, 3 + 3 * s);
     }
-    if (SKIP) {
+    {
       // the tensor added to the result (the gradient that arrives through the skip connection) is fetched in four
       // batches of 8 float4, each batch a step ahead of the additions and stores it feeds: loads and stores share
       // one in-order counter, so load - add - store per element would wait for every store before the next load
@@ -1424,14 +1097,9 @@ __global__ __launch_bounds__(64 * SYN3_WAVES, 2) void k_dft_synthesis3_h2(const 
     }
     FSTAMP(1, 26);
     if (!has_next) {
-      if (!SKIP) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) store_rows(o, k, 1);        // the last tile's column block 1
-      }
       wait_vmcnt<0>();          // (the re-reads of the last two stages must have landed before the LDS is given back)
       break;
     }
-    o_prev = o;
     cur = nxt;
     q = qn;
     ring = (ring + 8) % 3;
@@ -1457,7 +1125,7 @@ __global__ __launch_bounds__(64 * SYN3_WAVES, 2) void k_dft_synthesis3_h2(const 
 //     eight points x 128 bytes.  The 4 x 4 quad transpose that gives a lane four consecutive channels of one point
 //     takes its four inputs from BOTH channel blocks -- (a, column) = (0, 0), (0, 1), (1, 0), (1, 1) -- so the lanes
 //     of a quad end up with the two 64-byte halves of two points' lines: no exchange beyond the transpose itself.
-//   * forward and adjoint without a skip gradient (with one: k_dft_synthesis3_h2<.., true>).
+//   * forward and adjoint without a skip gradient (with one: k_dft_synthesis3_h2).
 template <int S> struct StageC { static constexpr int value = S; };
 
 // Tried on top and dropped (same-box, 256^2, B = 32; profiles/r04_synthesis_variants.txt): requesting ALL pieces of stage
@@ -1727,18 +1395,12 @@ size_t fused2d_img_bytes(long lines, int R) { return (size_t)lines * 4 * h2_bloc
   } while (0)
 
 // RPDE_ANA_SQ=0: keep the two-read analysis kernel for every shape (A/B, tests).  Default: the one-pass kernel on every
-// square grid (with a workgroup's rows matched to the grid it is level with the two-read kernel at 64^2 and 128^2 for
-// B = 32 and ahead at B = 8: 2.03 vs 2.25 ms per training step at 64^2).
+// square grid (its round-3 predecessor, with a workgroup's rows matched to the grid, was level with the two-read kernel
+// at 64^2 and 128^2 for B = 32 and ahead at B = 8: 2.03 vs 2.25 ms per training step at 64^2).
 static bool ana_sq_ok(int M, int N, int cus) {
   const char* e = getenv("RPDE_ANA_SQ");
   if (e && e[0] == '0') return false;
   return M == N && cus >= 256;
-}
-
-// RPDE_ANA_RR=0: the row-block kernel k_dft_analysis_sq_h2 (cross-wave sums through LDS) instead of the round-robin one
-static bool ana_rr_on() {
-  const char* e = getenv("RPDE_ANA_RR");
-  return !(e && e[0] == '0');
 }
 
 int fused2d_analysis(const float* x, float* spec_y, float* spec_x, float* amax_y, float* amax_x, const rpde_plan* py,
@@ -1747,7 +1409,7 @@ int fused2d_analysis(const float* x, float* spec_y, float* spec_x, float* amax_y
     int dev = 0, cus = 256;
     RPDE_HIP(hipGetDevice(&dev));
     RPDE_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    if (ana_sq_ok(M, N, cus) && ana_rr_on() && py->h2_ana[adjoint] == px->h2_ana[adjoint]) {
+    if (ana_sq_ok(M, N, cus) && py->h2_ana[adjoint] == px->h2_ana[adjoint]) {
       // the round-robin schedule: a group = N waves = N / 8 workgroups; as many groups as fit (never more than samples)
       AnaRrP Q;
       Q.x = x; Q.timg = (const char*)py->h2_ana_p[adjoint]; Q.spec_y = spec_y; Q.spec_x = spec_x; Q.amax_y = amax_y; Q.amax_x = amax_x;
@@ -1761,22 +1423,6 @@ int fused2d_analysis(const float* x, float* spec_y, float* spec_x, float* amax_y
       if (MTq == 1) hipLaunchKernelGGL(k_dft_analysis_rr_h2<1>, grid, blk, 0, st, Q);
       else if (MTq == 2) hipLaunchKernelGGL(k_dft_analysis_rr_h2<2>, grid, blk, 0, st, Q);
       else hipLaunchKernelGGL(k_dft_analysis_rr_h2<3>, grid, blk, 0, st, Q);
-      RPDE_LAUNCH_CHECK();
-      return RPDE_OK;
-    }
-    if (ana_sq_ok(M, N, cus) && py->h2_ana[adjoint] == px->h2_ana[adjoint]) {
-      AnaSqP Q;
-      Q.x = x; Q.timg = (const char*)py->h2_ana_p[adjoint]; Q.spec_y = spec_y; Q.spec_x = spec_x; Q.amax_y = amax_y; Q.amax_x = amax_x;
-      Q.B = B; Q.n = N; Q.ks = N / 32; Q.R = 2 * py->kp;
-      { const char* e = getenv("RPDE_ANA_B1"); Q.b1 = (e && e[0] == '1') ? 1 : 0; }
-      Q.rpw = ANA_WAVES / Q.ks;                            // rows of a block per workgroup; 32 / rpw workgroups per group
-      const int wpg = 32 / Q.rpw;
-      Q.ng = B < 256 / wpg ? B : 256 / wpg;
-      const dim3 grid(wpg * Q.ng), blk(64 * ANA_WAVES);
-      const int MTq = (Q.R + 15) / 16;
-      if (MTq == 1) hipLaunchKernelGGL(k_dft_analysis_sq_h2<1>, grid, blk, 0, st, Q);
-      else if (MTq == 2) hipLaunchKernelGGL(k_dft_analysis_sq_h2<2>, grid, blk, 0, st, Q);
-      else hipLaunchKernelGGL(k_dft_analysis_sq_h2<3>, grid, blk, 0, st, Q);
       RPDE_LAUNCH_CHECK();
       return RPDE_OK;
     }
@@ -1816,12 +1462,6 @@ int fused2d_split(const float* spec, void* img, float* inv, long lines, int R, h
   return RPDE_OK;
 }
 
-// RPDE_SYN4=0: keep the 64 x 64 x 16-channel tile kernel where the 64 x 32 x 32-channel one would run (A/B, tests)
-static bool syn4_on() {
-  const char* e = getenv("RPDE_SYN4");
-  return !(e && e[0] == '0');
-}
-
 // RPDE_SYN3=0: keep the 16 x 16 tile kernel for every shape (A/B, tests)
 static bool syn3_ok(int M, int N) {
   if (const char* e = getenv("RPDE_SYN3")) if (e[0] == '0') return false;
@@ -1840,7 +1480,7 @@ int fused2d_synthesis(const void* imgy, const void* imgx, const float* invy, con
     int dev = 0, cus = 256;
     RPDE_HIP(hipGetDevice(&dev));
     RPDE_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    if (!skip && syn4_on()) {
+    if (!skip) {
       // 64 x 32 x 32-channel tiles, whole 128-byte lines per store: (M / 64) (N / 32) 2 items per sample
       const int ng = B < 8 ? B : 8;
       P.sy = ng;
@@ -1861,8 +1501,9 @@ int fused2d_synthesis(const void* imgy, const void* imgx, const float* invy, con
       RPDE_LAUNCH_CHECK();
       return RPDE_OK;
     }
-    // persistent: one workgroup per CU, in 8 groups (one per XCD; fewer when the batch is smaller); never more per group
-    // than the busiest group has tiles
+    // with the skip gradient: 64 x 64 x 16-channel tiles, (M / 64) (N / 64) 4 items per sample.  Persistent: one workgroup
+    // per CU, in 8 groups (one per XCD; fewer when the batch is smaller); never more per group than the busiest group
+    // has tiles
     const int ng = B < 8 ? B : 8;
     P.sy = ng;
     P.sx = 1;
@@ -1872,19 +1513,13 @@ int fused2d_synthesis(const void* imgy, const void* imgx, const float* invy, con
     if (per_group > most) per_group = most;
     if (per_group < 1) per_group = 1;
     const dim3 grid3((unsigned)(ng * per_group)), blk3(64 * SYN3_WAVES);
-#define RPDE_SYN3_LAUNCH(K32_, TG_)                                                                                     \
-    do {                                                                                                                \
-      if (skip) hipLaunchKernelGGL((k_dft_synthesis3_h2<K32_, TG_, true>), grid3, blk3, 0, st, P);                      \
-      else hipLaunchKernelGGL((k_dft_synthesis3_h2<K32_, TG_, false>), grid3, blk3, 0, st, P);                          \
-    } while (0)
     switch (R3 / 8) {
-      case 1: RPDE_SYN3_LAUNCH(0, 1); break;
-      case 2: RPDE_SYN3_LAUNCH(0, 2); break;
-      case 3: RPDE_SYN3_LAUNCH(0, 3); break;
-      case 4: RPDE_SYN3_LAUNCH(1, 0); break;
-      default: RPDE_SYN3_LAUNCH(1, 1); break;
+      case 1: hipLaunchKernelGGL((k_dft_synthesis3_h2<0, 1>), grid3, blk3, 0, st, P); break;
+      case 2: hipLaunchKernelGGL((k_dft_synthesis3_h2<0, 2>), grid3, blk3, 0, st, P); break;
+      case 3: hipLaunchKernelGGL((k_dft_synthesis3_h2<0, 3>), grid3, blk3, 0, st, P); break;
+      case 4: hipLaunchKernelGGL((k_dft_synthesis3_h2<1, 0>), grid3, blk3, 0, st, P); break;
+      default: hipLaunchKernelGGL((k_dft_synthesis3_h2<1, 1>), grid3, blk3, 0, st, P); break;
     }
-#undef RPDE_SYN3_LAUNCH
     RPDE_LAUNCH_CHECK();
     return RPDE_OK;
   }

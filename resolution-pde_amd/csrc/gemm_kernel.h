@@ -526,44 +526,32 @@ inline void launch_pro(const GemmK& g, int pro, dim3 grid, hipStream_t st) {
   }
 }
 
-int gemm_variant();   // experiment switch (env RPDE_GEMM_VARIANT) for the 128 x 128 tile
-
 template <bool AK, bool BKM, int PM>
 inline int launch_layout_impl(const GemmK& g, int bm, int bn, int pro, bool vec, dim3 grid, hipStream_t st) {
   if (!((PM >> pro) & 1)) {
     set_error("gemm: staged activation on operand %d is not built for layout a_kmajor=%d b_kmajor=%d", pro, (int)AK, (int)BKM);
     return RPDE_ERR_ARG;
   }
-  // RPDE_GEMM_VARIANT (A/B experiments, same-box numbers in profiles/r01_c_gemm_variants.txt):
-  //   0 default: two-deep software pipeline on every vector tile;  1: lean loop on the small tiles;
-  //   2: lean loop everywhere;  3: no lean single-stage kernel for short reductions;  4: no epilogue prefetch.  (Smaller-LDS variants -- BK16 x 2, BK32 x 1 -- were within 2 %: the
-  //   resident-wave count is not what limits this kernel.)
-  const int v = gemm_variant();
-  const bool pipe_big = v != 2, pipe_small = v != 1 && v != 2;
+  // the 128 x 128, 128 x 64, 64 x 128 and 64 x 64 vector tiles run the two-deep software pipeline (same-box A/B against
+  // the lean loop and the other variants of round 1: profiles/r01_c_*; smaller-LDS variants -- BK16 x 2, BK32 x 1 -- were
+  // within 2 %: the resident-wave count is not what limits this kernel)
   if (!vec) launch_pro<2, 2, 1, 1, AK, BKM, PM, false>(g, pro, grid, st);            // 64 x 64, scalar loads
   else if (bm == 128 && bn == 128) {
     // reductions of <= 2 stages are epilogue / HBM-latency bound: lean single-stage kernel (~90 VGPRs,
-    // 37 KB LDS -> 4 workgroups per CU) keeps more memory requests in flight  (variant 3 disables)
-    const bool preaux = g.cvec && pro == 0 && v != 4 && !g.write_act &&
+    // 37 KB LDS -> 4 workgroups per CU) keeps more memory requests in flight
+    const bool preaux = g.cvec && pro == 0 && !g.write_act &&
                         ((g.epi_dact == RPDE_EPI_MULAUX) != (g.accumulate != 0));   // exactly one of the two
-    if (g.kchunk <= 64 && v != 3 && v != 2) {
+    if (g.kchunk <= 64) {
       if constexpr ((PM & 1) != 0) {
         if (preaux) launch_pro<2, 2, 2, 2, AK, BKM, 1, true, 32, 1, false, true>(g, pro, grid, st);
         else launch_pro<2, 2, 2, 2, AK, BKM, PM, true, 32, 1, false>(g, pro, grid, st);
       }
     }
-    else if (pipe_big) launch_pro<2, 2, 2, 2, AK, BKM, PM, true, 32, 2, true>(g, pro, grid, st);
-    else launch_pro<2, 2, 2, 2, AK, BKM, PM, true>(g, pro, grid, st);
-  } else if (bm == 128 && bn == 64) {
-    if (pipe_small) launch_pro<4, 1, 1, 2, AK, BKM, PM, true, 32, 2, true>(g, pro, grid, st);
-    else launch_pro<4, 1, 1, 2, AK, BKM, PM, true>(g, pro, grid, st);
-  } else if (bm == 64 && bn == 128) {
-    if (pipe_small) launch_pro<1, 4, 2, 1, AK, BKM, PM, true, 32, 2, true>(g, pro, grid, st);
-    else launch_pro<1, 4, 2, 1, AK, BKM, PM, true>(g, pro, grid, st);
-  } else if (bm == 64 && bn == 64) {
-    if (pipe_small) launch_pro<2, 2, 1, 1, AK, BKM, PM, true, 32, 2, true>(g, pro, grid, st);
-    else launch_pro<2, 2, 1, 1, AK, BKM, PM, true>(g, pro, grid, st);
-  } else if (bm == 128 && bn == 32) launch_pro<4, 1, 1, 1, AK, BKM, PM, true>(g, pro, grid, st);
+    else launch_pro<2, 2, 2, 2, AK, BKM, PM, true, 32, 2, true>(g, pro, grid, st);
+  } else if (bm == 128 && bn == 64) launch_pro<4, 1, 1, 2, AK, BKM, PM, true, 32, 2, true>(g, pro, grid, st);
+  else if (bm == 64 && bn == 128) launch_pro<1, 4, 2, 1, AK, BKM, PM, true, 32, 2, true>(g, pro, grid, st);
+  else if (bm == 64 && bn == 64) launch_pro<2, 2, 1, 1, AK, BKM, PM, true, 32, 2, true>(g, pro, grid, st);
+  else if (bm == 128 && bn == 32) launch_pro<4, 1, 1, 1, AK, BKM, PM, true>(g, pro, grid, st);
   else launch_pro<1, 4, 1, 1, AK, BKM, PM, true>(g, pro, grid, st);                   // 32 x 128
   RPDE_LAUNCH_CHECK();
   return RPDE_OK;

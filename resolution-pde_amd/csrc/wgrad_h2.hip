@@ -24,7 +24,6 @@
 // are scaled by it, and a consumer wave whose panels' exponents moved rescales its accumulators once (a wave-uniform
 // branch that is taken a handful of times per launch).  No pass over the data to find a global maximum, no
 // per-step accumulator arithmetic, robust to isolated huge points.
-#include <stdio.h>
 #include "h2.h"
 #include "pointwise.h"
 #include "wgrad_h2.h"
@@ -303,15 +302,12 @@ bool wgrad_h2_ok(long P, int out_f, int in_f) {
 
 static int wg_chunks(int, int) { return WG_BLOCKS; }
 
-// Which waves convert early (k_wgrad_h2), measured same-box with rocprofv3 over the masks (RPDE_WG_EARLY=<hex 256x256>,
-// <hex 64x256>,<hex 256x64> overrides, for such sweeps): 256x256 (eight loaders) waves 4-7 early 820-834 us, all in one
-// order 878-898, waves 0-3 early 942 (the lower wave of a SIMD pair seems to win the matrix pipe: it should be the one
-// that goes there first); 64x256 (loaders 0-4) waves 1-3 early 490 vs 513-518 us; 256x64 with the data gradient: no
-// mask beat the common order (753-762 us), most lost.
+// Which waves convert early (k_wgrad_h2), measured same-box with rocprofv3 over the masks: 256x256 (eight loaders)
+// waves 4-7 early 820-834 us, all in one order 878-898, waves 0-3 early 942 (the lower wave of a SIMD pair seems to win
+// the matrix pipe: it should be the one that goes there first); 64x256 (loaders 0-4) waves 1-3 early 490 vs 513-518 us;
+// 256x64 with the data gradient: no mask beat the common order (753-762 us), most lost.
 static int wg_early_mask(int out_f, int in_f) {
-  int m[3] = {0xF0, 0x0E, 0x00};
-  if (const char* e = getenv("RPDE_WG_EARLY")) sscanf(e, "%x,%x,%x", &m[0], &m[1], &m[2]);
-  return out_f == 256 && in_f == 256 ? m[0] : (out_f == 64 ? m[1] : m[2]);
+  return out_f == 256 && in_f == 256 ? 0xF0 : (out_f == 64 ? 0x0E : 0x00);
 }
 
 size_t wgrad_h2_slab_floats(long P, int out_f, int in_f) {

@@ -100,7 +100,8 @@ def test_product_tree_never_imports_the_oracle():
 
 
 def test_every_environment_switch_is_documented():
-    """every RPDE_* variable the library or the host code reads appears in INTEGRATION.md"""
+    """every RPDE_* variable the library or the host code reads appears in INTEGRATION.md, and every variable that
+    INTEGRATION.md's switch table lists is read by one of them (a row for a retired switch fails)"""
     import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     names = set()
@@ -117,3 +118,10 @@ def test_every_environment_switch_is_documented():
     doc = open(os.path.join(root, "INTEGRATION.md")).read()
     missing = sorted(n for n in names if n not in doc and not any(n.startswith(p[:-1]) and p in doc for p in ("RPDE_BENCH_*",)))
     assert names and not missing, missing
+    documented = set()
+    for line in doc.splitlines():
+        if line.startswith("| `RPDE_"):                    # a row of the switch table: names in its first column
+            documented.update(re.findall(r"RPDE_[A-Z0-9_]+\*?", line.split("|")[1]))
+    stale = sorted(d for d in documented
+                   if not (any(n.startswith(d[:-1]) for n in names) if d.endswith("*") else d in names))
+    assert len(documented) >= 20 and not stale, stale

@@ -1,5 +1,6 @@
 """Kernels that wait for prefetched operands with HAND-COUNTED `s_waitcnt vmcnt(N)` (DESIGN.md section 3.1:
-k_dft_analysis_sq_h2, k_ff3_bwd_h2, k_conv_syn_h2) reduce in fixed order, so two runs on the same data are bitwise
+k_dft_analysis_rr_h2, k_dft_synthesis3_h2 / k_dft_synthesis4_h2, k_ff3_bwd_h2, k_conv_syn_h2) reduce in fixed order,
+so two runs on the same data are bitwise
 equal -- unless a count is too small and a value is read before it has landed.  Each case runs twice, the second time
 with a copy stream hammering HBM beside the kernels (later arrivals), and must repeat itself exactly; the value itself is
 pinned by the parity tests.  profiles/soak_ff_bwd.py and profiles/soak_spectral.py are the long versions

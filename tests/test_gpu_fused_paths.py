@@ -362,10 +362,12 @@ def test_small_channel_conv_kernel(gpu_device, cin, cout, act_in, act_out):
                                    (1, 192, 192, 20), (17, 64, 64, 4), (2, 256, 256, 20), (3, 96, 96, 12), (2, 160, 160, 20),
                                    (40, 32, 32, 8), (70, 64, 64, 20)])
 def test_round3_spectral_kernels_over_batch_grid_and_mode_variants(gpu_device, shape):
-    """the round-3 kernels (k_dft_analysis_sq_h2: XCD groups with uneven sample counts, grids of 32 .. 256 incl. those whose
-    rows do not fill a workgroup's eight waves, more groups than samples and fewer; k_mix_h2 /
-    k_mix_wgrad_h2: every (K32, TG) operand layout incl. the packed tails; k_dft_synthesis3_h2: persistent tiles with
-    1 .. many tiles per workgroup, with and without the skip gradient) against the per-GEMM path"""
+    """the fused spectral kernels (k_dft_analysis_rr_h2 on the square grids: XCD groups with uneven sample counts, grids of
+    32 .. 256 incl. 96 and 160, more groups than samples and fewer; k_dft_analysis_h2 on the others and in the
+    RPDE_ANA_SQ=0 leg; k_mix_h2 / k_mix_wgrad_h2: every (K32, TG) operand layout incl. the packed tails; on grids of
+    multiples of 64 the persistent synthesis kernels with 1 .. many tiles per workgroup -- k_dft_synthesis4_h2 forward,
+    k_dft_synthesis3_h2 for the adjoint with the skip gradient -- and k_dft_synthesis2_h2 elsewhere) against the
+    per-GEMM path"""
     B, M, N, K = shape
     torch.manual_seed(B * 1000 + M + N + K)
     x = torch.randn(B, M, N, 64, device=gpu_device)

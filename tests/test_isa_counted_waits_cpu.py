@@ -7,8 +7,8 @@ behind a branch changes the count without any parity test noticing.  No GPU need
 What counts as certain: global_/buffer_/scratch_ loads, stores, atomics and LDS-DMA outside any exec-masked region (an
 instruction whose lanes are all off is not issued and not counted by the hardware).  The analysis is a forward
 data-flow over the kernel's basic blocks (minimum over paths, loops to a fixed point), so it proves `>= N`; it cannot
-prove counts that depend on run-time values (k_dft_analysis_sq_h2 picks vmcnt(8..11) by a wave-uniform store count: its
-floor of 8 is what is checked there)."""
+prove counts that depend on run-time values (k_ff3_bwd_h2's depend on the tile: it is left to
+tests/test_isa_pending_loads_cpu.py)."""
 import os
 import re
 import shutil
@@ -195,11 +195,10 @@ def _kernel_bodies(tmp_path, source, prefixes):
 
 CASES = [
     # source, mangled-name prefixes, minimum (marks, waits) per instance, assume_live
-    # (k_dft_synthesis3_h2: the instances with the skip gradient -- <.., true>, mangled ..Lb1E -- are the ones dispatched by
-    #  default; the forward instances' counts depend on a flag the path-insensitive analysis cannot follow)
-    ("fused_spectral", ("19k_dft_synthesis3_h2ILi0ELi1ELb1E", "19k_dft_synthesis3_h2ILi0ELi2ELb1E",
-                        "19k_dft_synthesis3_h2ILi0ELi3ELb1E", "19k_dft_synthesis3_h2ILi1ELi0ELb1E",
-                        "19k_dft_synthesis3_h2ILi1ELi1ELb1E", "19k_dft_synthesis4_h2"), 8, 8, False),
+    # (k_dft_synthesis3_h2: the adjoint with the skip gradient, every (K32, TG) instance)
+    ("fused_spectral", ("19k_dft_synthesis3_h2ILi0ELi1E", "19k_dft_synthesis3_h2ILi0ELi2E",
+                        "19k_dft_synthesis3_h2ILi0ELi3E", "19k_dft_synthesis3_h2ILi1ELi0E",
+                        "19k_dft_synthesis3_h2ILi1ELi1E", "19k_dft_synthesis4_h2"), 8, 8, False),
     # (the instances without FULL drain the queue instead -- a predicated store may not issue: no counted wait in them)
     ("conv_syn_h2", ("13k_conv_syn_h2",), 1, 0, False),
     # the training forward: the input DMA of the next tile against the saved-tensor stores of this one (lane-predicated

@@ -1,7 +1,7 @@
-"""k_dft_analysis_sq_h2 issues its field loads from inline asm and waits for them with a hand-counted s_waitcnt
+"""k_dft_analysis_rr_h2 issues its field loads from inline asm and waits for them with a hand-counted s_waitcnt
 (DESIGN.md section 3.1): the compiler does not know that the destination registers are pending, so nothing may read,
-copy OR REUSE them between the load and the wait that covers it -- on any path.  (Round 3: waves without a duty
-branched around the wait; the compiler, for which the registers were filled and dead, used them for the next address
+copy OR REUSE them between the load and the wait that covers it -- on any path.  (Round 3, in the analysis kernel of
+the time: waves without a duty branched around the wait; the compiler, for which the registers were filled and dead, used them for the next address
 computation, and a load that landed late overwrote the address: a memory fault in training at 96^2 that no parity test
 showed.)  This test compiles the kernel to gfx950 assembly (no GPU needed) and follows the set of pending registers
 through the code in layout order, merging it into the target of every forward branch: a load adds its destination, the
@@ -108,9 +108,8 @@ def _kernel_bodies(tmp_path, source, names):
 
 @pytest.mark.skipif(_hipcc() is None, reason="hipcc not available")
 def test_no_use_of_asm_loaded_registers_before_the_counted_wait(tmp_path):
-    for name, body in _kernel_bodies(tmp_path, "fused_spectral", ("20k_dft_analysis_sq_h2ILi1E", "20k_dft_analysis_sq_h2ILi2E",
-                                                                  "20k_dft_analysis_sq_h2ILi3E", "20k_dft_analysis_rr_h2ILi1E",
-                                                                  "20k_dft_analysis_rr_h2ILi2E", "20k_dft_analysis_rr_h2ILi3E")):
+    for name, body in _kernel_bodies(tmp_path, "fused_spectral", ("20k_dft_analysis_rr_h2ILi1E", "20k_dft_analysis_rr_h2ILi2E",
+                                                                  "20k_dft_analysis_rr_h2ILi3E")):
         bad, nloads, nlanded = _pending_violations(body)
         assert nloads >= 32, (name, nloads)              # 8 per axis, prologue + loop
         assert nlanded >= 2, (name, nlanded)
