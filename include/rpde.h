@@ -338,6 +338,32 @@ size_t rpde_resize2d_ws_bytes(int64_t rows, int M, int N, int Mo, int No);
 int rpde_resize2d(const float* x, float* out, int64_t rows, int M, int N, int Mo, int No,
                   void* ws, size_t ws_bytes, void* stream);
 
+/* ---- error by frequency (reference: utils/frequency_error.py `decompose_error_by_frequency_1d`, one irfft of the
+ * batch and one .item() per mode, and `decompose_error_by_frequency_2d`, two irfft2 and two .item() per radial bin;
+ * driven by frequency_evaluation.py / utils/multiresolution_analysis.py).  By Parseval those norms are weighted sums
+ * of |rfft|^2: one forward transform of (pred - target) -- the difference is formed in fp32 BEFORE the transform --
+ * and of target, squared and reduced on the device.
+ *   acc [2, n_out] float64: row 0 error energy, row 1 solution energy, ADDED TO (zero it before the first batch);
+ *   the reference's magnitudes are sqrt(acc) once the test set has streamed through.  No floating-point atomics:
+ *   identical calls give identical bits.
+ * 1-D: pred, target [rows, n] (rows = batch * channels), n_out = num_modes <= n/2+1 (more: RPDE_ERR_MODES),
+ *   acc[.][k] += w_k / n * sum_rows |Z[row,k]|^2, w_k = 1 at DC and (even n) Nyquist, else 2.
+ * 2-D: pred, target [images, H, W]; bins [H, W/2+1] int32 on the device, the radial bin of every half-spectrum entry
+ *   or -1 for none, -1 <= bin < n_bins (built and range-checked by the caller: rpde/ops.py radial_bins), n_out = n_bins,
+ *   acc[.][i] += 1/(H W) * sum_{(ky,kx) in bin i} w_kx sum_images |Z[image,ky,kx]|^2.
+ *   The batch goes through the workspace in chunks of images: rpde_freq_energy2d_ws_bytes stops growing with
+ *   `images` once a chunk (16 MiB of half-spectra) is full.
+ * Sizes: 2 <= n, H, W <= 4096 (the full-spectrum tables grow with the square of the axis; they are cached per
+ * (n, num_modes) for the life of the process); the workspace must be 16-byte aligned.
+ * Argument errors (null pointers, sizes out of range, n_bins < 1, short or misaligned workspace) are reported before
+ * any device work. */
+size_t rpde_freq_energy1d_ws_bytes(int64_t rows, int n, int num_modes);
+int rpde_freq_energy1d(const float* pred, const float* target, double* acc, int64_t rows, int n, int num_modes,
+                       void* ws, size_t ws_bytes, void* stream);
+size_t rpde_freq_energy2d_ws_bytes(int64_t images, int H, int W);
+int rpde_freq_energy2d(const float* pred, const float* target, const int32_t* bins, double* acc, int64_t images,
+                       int H, int W, int n_bins, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- elementwise activation: out = act(x); backward dx = g * act'(x) */
 int rpde_act_fwd(const float* x, float* out, int64_t n, int act, void* stream);
 int rpde_act_bwd(const float* x, const float* g, float* dx, int64_t n, int act, void* stream);

@@ -61,6 +61,16 @@ __global__ __launch_bounds__(64) void k_cf_table_syn(const float* __restrict__ s
   *reinterpret_cast<uint4*>(p + 1024) = make_uint4(l0.x, l0.y, l1.x, l1.y);
 }
 
+// the analysis-type fragments of any [R, n] table (zero-padded to whole 16 x 32 fragments) into `out`,
+// cf_table_bytes(R, n) bytes: for callers that stream a table too large for LDS (freq_energy.hip)
+size_t cf_table_bytes(int R, int n) { return (size_t)((n + 31) / 32) * ((R + 15) / 16) * 2048; }
+int cf_table_fragments(const float* src, long rs, long cs, int R, int n, char* out, hipStream_t st) {
+  const int NT = (R + 15) / 16;
+  hipLaunchKernelGGL(k_cf_table_ana, dim3(((n + 31) / 32) * NT), dim3(64), 0, st, src, rs, cs, R, n, NT, out);
+  RPDE_LAUNCH_CHECK();
+  return RPDE_OK;
+}
+
 bool cf_h2_eligible(int n, int R) {
   if (const char* e = getenv("RPDE_FUSED_CF")) if (e[0] == '0') return false;
   const int NT = (R + 15) / 16;

@@ -125,6 +125,10 @@ _SIGNATURES = {
     "rpde_resize1d": (_I, [_P, _P, _L, _I, _I, _P, _Z, _P]),
     "rpde_resize2d_ws_bytes": (_Z, [_L, _I, _I, _I, _I]),
     "rpde_resize2d": (_I, [_P, _P, _L, _I, _I, _I, _I, _P, _Z, _P]),
+    "rpde_freq_energy1d_ws_bytes": (_Z, [_L, _I, _I]),
+    "rpde_freq_energy1d": (_I, [_P, _P, _P, _L, _I, _I, _P, _Z, _P]),
+    "rpde_freq_energy2d_ws_bytes": (_Z, [_L, _I, _I]),
+    "rpde_freq_energy2d": (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _P, _Z, _P]),
     "rpde_concat_grid": (_I, [_P, _P, _I, _I, _I, _I, _I, _D, _D, _I, _P, _P, _P]),
     "rpde_transpose_cs": (_I, [_P, _P, _I, _L, _I, _I, _P]),
     "rpde_act_fwd": (_I, [_P, _P, _L, _I, _P]),

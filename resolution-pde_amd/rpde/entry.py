@@ -34,6 +34,36 @@ def _init_distributed():
     return world, rank, local
 
 
+def _sweep_fields(args, test_set, x_normalizer, y_normalizer, min_model, max_model, device):
+    """What the post-training sweeps (every resolution, error by frequency) evaluate on: (test inputs as the model takes
+    them, test targets in physical units, decoder of the model's output or None, evaluation_type, top resolution)."""
+    dp = args.dataset.get("dataset_params") or {}
+    raw_eval = None
+    if dp.get("eval_dataset_target") and args.dataset.get("train_mres"):
+        # multi-resolution training evaluates on ONE single-resolution file through another loader (reference
+        # utils/naive_utils.py:322-350): un-normalised pairs, encoded here with the training statistics
+        keep = ("reduced_batch", "reduced_resolution_t", "use_low_pass_filter", "lowpass_cutoff_ratio", "num_samples_max")
+        node = {"_target_": dp["eval_dataset_target"], "filename": dp["eval_filename"],
+                "saved_folder": dp.get("eval_saved_folder", dp.get("saved_folder")), "data_normalizer": False,
+                **{k: dp[k] for k in keep if k in dp}}
+        raw_eval = instantiate(node)[2]
+    pairs = [(raw_eval or test_set)[i] for i in range(len(raw_eval or test_set))]
+    top_res = max(int(x.shape[-1]) for x, _ in pairs)
+    pairs = [(torch.as_tensor(x), torch.as_tensor(y)) for x, y in pairs if int(x.shape[-1]) == top_res]   # a mixed test
+    tx, ty = torch.stack([x for x, _ in pairs]), torch.stack([y for _, y in pairs])        # split: highest resolution only
+    if raw_eval is not None and x_normalizer is not None:
+        tx, ty = x_normalizer.encode(tx), y_normalizer.encode(ty)
+    how = str(args.dataset.get("evaluation_type", "naive_downsample"))
+    if y_normalizer is not None:
+        dec = lambda t: y_normalizer.decode(t, device=device)                                    # noqa: E731
+    elif min_model is not None:
+        dec = lambda t: t * (max_model - min_model) + min_model                                  # noqa: E731
+    else:
+        dec = None
+    ty_phys = dec(ty.to(device)).cpu() if dec else ty
+    return tx, ty_phys, dec, how, top_res
+
+
 def run(dims: int, argv=None):
     here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     args = compose(os.path.join(here, "conf"), "config", list(sys.argv[1:] if argv is None else argv))
@@ -126,30 +156,7 @@ def run(dims: int, argv=None):
     # ---- the reference's post-training sequence: every resolution [32, .., max] (main_2d.py:287, main_1d.py:250),
     # ---- and in 1-D the autoregressive rollout (main_1d.py:272; utils/autoregressive_step.py:284-309)
     from utils.resize_utils import evaluate_all_resolutions, to_resolution
-    dp = args.dataset.get("dataset_params") or {}
-    raw_eval = None
-    if dp.get("eval_dataset_target") and args.dataset.get("train_mres"):
-        # multi-resolution training evaluates on ONE single-resolution file through another loader (reference
-        # utils/naive_utils.py:322-350): un-normalised pairs, encoded here with the training statistics
-        keep = ("reduced_batch", "reduced_resolution_t", "use_low_pass_filter", "lowpass_cutoff_ratio", "num_samples_max")
-        node = {"_target_": dp["eval_dataset_target"], "filename": dp["eval_filename"],
-                "saved_folder": dp.get("eval_saved_folder", dp.get("saved_folder")), "data_normalizer": False,
-                **{k: dp[k] for k in keep if k in dp}}
-        raw_eval = instantiate(node)[2]
-    pairs = [(raw_eval or test_set)[i] for i in range(len(raw_eval or test_set))]
-    top_res = max(int(x.shape[-1]) for x, _ in pairs)
-    pairs = [(torch.as_tensor(x), torch.as_tensor(y)) for x, y in pairs if int(x.shape[-1]) == top_res]   # a mixed test
-    tx, ty = torch.stack([x for x, _ in pairs]), torch.stack([y for _, y in pairs])        # split: highest resolution only
-    if raw_eval is not None and x_normalizer is not None:
-        tx, ty = x_normalizer.encode(tx), y_normalizer.encode(ty)
-    how = str(args.dataset.get("evaluation_type", "naive_downsample"))
-    if y_normalizer is not None:
-        dec = lambda t: y_normalizer.decode(t, device=device)                                    # noqa: E731
-    elif min_model is not None:
-        dec = lambda t: t * (max_model - min_model) + min_model                                  # noqa: E731
-    else:
-        dec = None
-    ty_phys = dec(ty.to(device)).cpu() if dec else ty
+    tx, ty_phys, dec, how, top_res = _sweep_fields(args, test_set, x_normalizer, y_normalizer, min_model, max_model, device)
     resolution_results = evaluate_all_resolutions(model, tx, ty_phys, max_resolution=top_res, min_resolution=min(32, top_res),
                                                   how=how, batch_size=bs, y_decode=dec, device=device)
     rollout_results = None
@@ -210,3 +217,62 @@ def run(dims: int, argv=None):
         dist.barrier()
         dist.destroy_process_group()
     return test_l2
+
+
+def run_frequency(argv=None):
+    """Body of frequency_evaluation.py (reference: frequency_evaluation.py / utils/multiresolution_analysis.py, minus the
+    plots): load the checkpoint(s) the training entry points write, take the test split through
+    utils.frequency_error.evaluate_frequency_error at every resolution [32, .., max] and print ONE JSON document.
+
+    Overrides as in main_1d.py / main_2d.py, plus ``checkpoints=[a.pt,b.pt]`` (default: the reference's
+    dataset.model_checkpoints {name: path}, else dataset.saved_checkpoint_path, else
+    <checkpoint_dir>/<project_name>_<dims>d.pt), ``num_modes=K`` (1-D) and ``num_radial_bins=N`` (2-D, default 64)."""
+    here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    args = compose(os.path.join(here, "conf"), "config", list(sys.argv[1:] if argv is None else argv))
+    dims = int(args.dataset.dims)
+    world, rank, local = _init_distributed()
+    device = torch.device("cuda", local)
+    torch.cuda.set_device(device)
+    from utils.frequency_error import evaluate_frequency_error
+    from utils.resize_utils import get_lower_resolutions
+    from utils.synthetic import markov_pairs
+
+    seed = int(args.training.get("seed", 0))
+    x_normalizer = y_normalizer = min_model = max_model = None
+    if args.dataset.get("dataset_params"):
+        data_ = instantiate(args.dataset.dataset_params)
+        test_set = data_[2]
+        stats = data_[4 if dims == 1 else 3:]
+        if len(stats) == 4:
+            min_model, max_model = stats[2], stats[3]
+        elif len(stats) == 2:
+            x_normalizer, y_normalizer = stats
+    else:
+        top = max(int(r) for r in dict(args.dataset.resolutions))
+        test_set = markov_pairs({top: int(args.dataset.n_test)}, dims, seed + 60000)
+    tx, ty_phys, dec, how, top_res = _sweep_fields(args, test_set, x_normalizer, y_normalizer, min_model, max_model, device)
+
+    ckpts = args.get("checkpoints") or args.dataset.get("model_checkpoints") or args.dataset.get("saved_checkpoint_path") or \
+        os.path.join(args.checkpoint_dir, f"{args.project_name}_{dims}d.pt")
+    if isinstance(ckpts, dict):                 # the reference's dataset.model_checkpoints: {name: path}
+        ckpts = {str(k): str(v) for k, v in ckpts.items()}
+    else:
+        ckpts = {str(c): str(c) for c in (ckpts if isinstance(ckpts, (list, tuple)) else [ckpts])}
+    resolutions = get_lower_resolutions(top_res, min(32, top_res))
+    doc = {"dims": dims, "evaluation_type": how,
+           "n_test": int(tx.shape[0]), "resolutions": resolutions, "models": {}}
+    for name, path in ckpts.items():
+        model = instantiate(args.model).to(device)
+        state = torch.load(path, map_location=device, weights_only=True)
+        model.load_state_dict(state["model_state_dict"])
+        res = evaluate_frequency_error(model, tx, ty_phys, resolutions=resolutions, how=doc["evaluation_type"],
+                                       batch_size=int(args.training.batch_size), num_modes=args.get("num_modes"),
+                                       num_radial_bins=int(args.get("num_radial_bins", 64)), y_decode=dec, device=device)
+        doc["models"][name] = {str(r): {"error": e.tolist(), "solution": s.tolist(), "frequencies": f.tolist()}
+                               for r, (e, s, f) in res.items()}
+    if rank == 0:
+        print(json.dumps(doc), flush=True)
+    if dist.is_initialized():
+        dist.barrier()
+        dist.destroy_process_group()
+    return doc

@@ -832,6 +832,110 @@ def resize2d(x: torch.Tensor, out_size) -> torch.Tensor:
     return out
 
 
+# ----------------------------------------------------------------------------
+# error by frequency (evaluators: no autograd).  Reference utils/frequency_error.py decompose_error_by_frequency_1d /
+# _2d take one inverse FFT and one .item() per mode or bin; here it is one call that ADDS the batch's error and solution
+# energy per mode / radial bin into a float64 device accumulator (csrc/freq_energy.hip) -- sqrt of it is the reference's
+# magnitude -- so a test set streams through in batches with no host synchronisation.
+# ----------------------------------------------------------------------------
+_RADIAL_BINS: dict = {}
+
+
+def radial_bins(H: int, W: int, num_radial_bins: int = 64):
+    """(bins, centres): bins int32 [H, W//2+1], the radial frequency bin of every rfft2 entry or -1 (entries with
+    r >= 0.5, the corners and the on-axis Nyquist lines, belong to no bin); centres float64 [num_radial_bins].  Built
+    with the reference's dtypes -- r a float32 tensor, edges np.linspace in float64, membership edges[i] <= r <
+    edges[i+1] -- so that entries on an edge fall where the reference puts them.  Host tensors, cached."""
+    import numpy as np
+    key = (int(H), int(W), int(num_radial_bins))
+    hit = _RADIAL_BINS.get(key)
+    if hit is not None:
+        return hit
+    if key[2] < 1 or key[0] < 2 or key[1] < 2:
+        raise ValueError(f"radial_bins: bad H={H} W={W} num_radial_bins={num_radial_bins}")
+    fy = torch.fft.fftfreq(key[0]).view(-1, 1)
+    fx = torch.fft.rfftfreq(key[1]).view(1, -1)
+    r = torch.sqrt(fy ** 2 + fx ** 2)
+    edges = np.linspace(0, 0.5, key[2] + 1)
+    bins = torch.full(r.shape, -1, dtype=torch.int32)
+    for i in range(key[2]):
+        bins[(r >= edges[i]) & (r < edges[i + 1])] = i
+    assert int(bins.min()) >= -1 and int(bins.max()) < key[2]       # the kernel trusts this range
+    centres = (edges[:-1] + edges[1:]) / 2
+    _RADIAL_BINS[key] = (bins.contiguous(), centres)
+    return _RADIAL_BINS[key]
+
+
+_RADIAL_BINS_DEV: dict = {}
+
+
+def _radial_bins_on(device, H: int, W: int, nb: int) -> torch.Tensor:
+    key = (torch.device(device), int(H), int(W), int(nb))
+    t = _RADIAL_BINS_DEV.get(key)
+    if t is None:
+        t = _RADIAL_BINS_DEV[key] = radial_bins(H, W, nb)[0].to(device)
+    return t
+
+
+def _channels_first(t: torch.Tensor, channels_last: bool) -> torch.Tensor:
+    """[B, ..., C] -> [B, C, ...]: a view when C == 1, otherwise a permuted copy made by _f32c"""
+    if not channels_last:
+        return t
+    if t.shape[-1] == 1:
+        return t.reshape(t.shape[0], 1, *t.shape[1:-1]) if t.is_contiguous() else t.movedim(-1, 1)
+    return t.movedim(-1, 1)
+
+
+def _freq_acc(acc, n_out: int, device) -> torch.Tensor:
+    if acc is None:
+        return torch.zeros(2, n_out, dtype=torch.float64, device=device)
+    if acc.dtype != torch.float64 or tuple(acc.shape) != (2, n_out) or not acc.is_contiguous() or acc.device != device:
+        raise ValueError(f"acc must be a contiguous float64 [2, {n_out}] tensor on {device}")
+    return acc
+
+
+def freq_energy1d(pred: torch.Tensor, target: torch.Tensor, acc: Optional[torch.Tensor] = None,
+                  num_modes: Optional[int] = None, channels_last: bool = False) -> torch.Tensor:
+    """pred, target [B, C, n] (channels_last: [B, n, C]).  Adds into acc [2, num_modes] float64 (created zeroed when
+    None) and returns it: acc[0, k] += w_k / n sum_{b,c} |rfft(pred - target)[b,c,k]|^2, acc[1, k] the same of target;
+    the difference is formed in fp32 before the transform.  num_modes (None or 0: all) is clamped to n // 2 + 1."""
+    lib = load()
+    if pred.shape != target.shape or pred.dim() != 3:
+        raise ValueError(f"freq_energy1d: pred {tuple(pred.shape)} / target {tuple(target.shape)}, expected equal 3-D shapes")
+    p = _f32c(_channels_first(pred.detach(), channels_last))
+    t = _f32c(_channels_first(target.detach(), channels_last))
+    n = p.shape[-1]
+    rows = p.numel() // n
+    k = min(int(num_modes or n // 2 + 1), n // 2 + 1)             # None or 0: every mode, as the reference's `or`
+    acc = _freq_acc(acc, k, p.device)
+    nws = lib.rpde_freq_energy1d_ws_bytes(rows, n, k)
+    ws = workspace(nws, p.device)
+    check(lib.rpde_freq_energy1d(ptr(p), ptr(t), acc.data_ptr(), rows, n, k, ws.data_ptr(), nws, stream_ptr()), "freq_energy1d")
+    return acc
+
+
+def freq_energy2d(pred: torch.Tensor, target: torch.Tensor, num_radial_bins: int = 64,
+                  acc: Optional[torch.Tensor] = None, channels_last: bool = False) -> torch.Tensor:
+    """pred, target [B, C, H, W] (channels_last: [B, H, W, C]).  Adds into acc [2, num_radial_bins] float64 and returns
+    it: acc[0, i] += 1/(H W) sum_{(ky,kx) in bin i} w_kx sum_{b,c} |rfft2(pred - target)[b,c,ky,kx]|^2, acc[1, i] the
+    same of target; bins as radial_bins() defines them."""
+    lib = load()
+    if pred.shape != target.shape or pred.dim() != 4:
+        raise ValueError(f"freq_energy2d: pred {tuple(pred.shape)} / target {tuple(target.shape)}, expected equal 4-D shapes")
+    p = _f32c(_channels_first(pred.detach(), channels_last))
+    t = _f32c(_channels_first(target.detach(), channels_last))
+    H, W = p.shape[-2], p.shape[-1]
+    images = p.numel() // (H * W)
+    nb = int(num_radial_bins)
+    bins = _radial_bins_on(p.device, H, W, nb)
+    acc = _freq_acc(acc, nb, p.device)
+    nws = lib.rpde_freq_energy2d_ws_bytes(images, H, W)
+    ws = workspace(nws, p.device)
+    check(lib.rpde_freq_energy2d(ptr(p), ptr(t), bins.data_ptr(), acc.data_ptr(), images, H, W, nb, ws.data_ptr(), nws,
+                                 stream_ptr()), "freq_energy2d")
+    return acc
+
+
 def warm_plans(model, resolutions, dims: int, in_channels: int = 1, device="cuda") -> None:
     """Build every DFT plan (tables, adjoint tables, operand images: hipMalloc + one stream sync each,
     csrc/core.hip get_plan) and size the workspaces the model needs at the given grid resolutions, with one
