@@ -10,7 +10,7 @@ bool cf_h2_eligible(int n, int R);
 bool cf_h2_syn_eligible(int n, int R);
 int cf_build_tables(rpde_plan* p, hipStream_t st);
 // B (or, the MFMA operands being symmetric, A) fragments of the table entry(k = y, col = r) = src[r*rs + y*cs], r < R,
-// y < n, in the layout of the kernels above ([n/32 up][R/16 up][hi|lo][1 KB], 2^12-scaled, cf_perm order inside a
+// y < n, in the layout of the kernels above ([n/32 up][R/16 up][hi|lo][1 KB], 2^12-scaled, frag_perm order inside a
 // 32-step), zero-padded; any R and n
 size_t cf_table_bytes(int R, int n);
 int cf_table_fragments(const float* src, long rs, long cs, int R, int n, char* out, hipStream_t st);

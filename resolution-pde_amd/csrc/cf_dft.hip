@@ -10,7 +10,7 @@
 // lines: analysis streams them in 128-point chunks (scale from the chunk's maximum, split, 4 x NT x 3 MFMAs, fp32
 // accumulation of the chunk results); synthesis forms 16 x 128 output blocks, turns them through 8 KB of LDS and
 // stores whole 512-byte row pieces.  The field is read once / written once; everything else is ~5 % of it.
-// Inside a 32-deep reduction step lane group g holds entries {4g..4g+3} and {16+4g..16+4g+3} (ff_perm order, the
+// Inside a 32-deep reduction step lane group g holds entries {4g..4g+3} and {16+4g..16+4g+3} (frag_perm order, the
 // table fragments are built to match), so that a load instruction covers 64 contiguous bytes per line.
 #include "cf_dft.h"
 #include "h2.h"
@@ -19,8 +19,6 @@ namespace rpde {
 
 constexpr int CF_WAVES = 8;
 constexpr int CF_CHUNK = 4;            // reduction steps (of 32) per analysis chunk
-
-__device__ __forceinline__ int cf_perm(int g, int j) { return 16 * (j >> 2) + 4 * g + (j & 3); }
 
 // B fragments of a table for the analysis-type product: entry (k = field index y, col = r) = src[r*rs + y*cs];
 // layout [ks][nt][hi|lo][1 KB], scaled by 2^12
@@ -32,15 +30,10 @@ __global__ __launch_bounds__(64) void k_cf_table_ana(const float* __restrict__ s
   float v[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    const int y = 32 * ks + cf_perm(g, j);
+    const int y = 32 * ks + frag_perm(g, j);
     v[j] = (r < R && y < n) ? src[r * rs + y * cs] * (float)(1 << H2_TABLE_EXP) : 0.f;
   }
-  uint2 h0, l0, h1, l1;
-  h2_split4(v[0], v[1], v[2], v[3], h0, l0);
-  h2_split4(v[4], v[5], v[6], v[7], h1, l1);
-  char* p = out + (long)f * 2048 + l * 16;
-  *reinterpret_cast<uint4*>(p) = make_uint4(h0.x, h0.y, h1.x, h1.y);
-  *reinterpret_cast<uint4*>(p + 1024) = make_uint4(l0.x, l0.y, l1.x, l1.y);
+  h2_put_frag(out + (long)f * 2048 + l * 16, v);
 }
 // B fragments for the synthesis-type product: entry (k = r, col = y) = src[y*rs + r*cs]; layout [yt][hi|lo][1 KB]
 __global__ __launch_bounds__(64) void k_cf_table_syn(const float* __restrict__ src, long rs, long cs, int R, int n,
@@ -50,15 +43,10 @@ __global__ __launch_bounds__(64) void k_cf_table_syn(const float* __restrict__ s
   float v[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    const int r = cf_perm(g, j);
+    const int r = frag_perm(g, j);
     v[j] = (r < R && y < n) ? src[y * rs + r * cs] * (float)(1 << H2_TABLE_EXP) : 0.f;
   }
-  uint2 h0, l0, h1, l1;
-  h2_split4(v[0], v[1], v[2], v[3], h0, l0);
-  h2_split4(v[4], v[5], v[6], v[7], h1, l1);
-  char* p = out + (long)yt * 2048 + l * 16;
-  *reinterpret_cast<uint4*>(p) = make_uint4(h0.x, h0.y, h1.x, h1.y);
-  *reinterpret_cast<uint4*>(p + 1024) = make_uint4(l0.x, l0.y, l1.x, l1.y);
+  h2_put_frag(out + (long)yt * 2048 + l * 16, v);
 }
 
 // the analysis-type fragments of any [R, n] table (zero-padded to whole 16 x 32 fragments) into `out`,
@@ -72,7 +60,7 @@ int cf_table_fragments(const float* src, long rs, long cs, int R, int n, char* o
 }
 
 bool cf_h2_eligible(int n, int R) {
-  if (const char* e = getenv("RPDE_FUSED_CF")) if (e[0] == '0') return false;
+  if (switch_off("RPDE_FUSED_CF")) return false;
   const int NT = (R + 15) / 16;
   return n % 128 == 0 && R <= 32 && (n / 32) * NT * 2048 <= 65536;
 }
@@ -205,7 +193,7 @@ __global__ __launch_bounds__(64 * CF_WAVES, 2) void k_cf_synthesis_h2(const CfP 
     const float* __restrict__ sp = P.in + row * P.ldo;
     float v[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { const int r = cf_perm(g, j); v[j] = r < P.R ? sp[r] : 0.f; }
+    for (int j = 0; j < 8; ++j) { const int r = frag_perm(g, j); v[j] = r < P.R ? sp[r] : 0.f; }
     float m = 0.f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf(v[j]));
@@ -242,9 +230,8 @@ __global__ __launch_bounds__(64 * CF_WAVES, 2) void k_cf_synthesis_h2(const CfP 
 }
 
 static int cf_grid(long rows) {
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  int cus;
+  (void)cu_count(&cus);
   const long need = ((rows + 15) / 16 + CF_WAVES - 1) / CF_WAVES;
   return (int)(need < cus ? need : cus);
 }

@@ -10,8 +10,6 @@
 // training path (which needs the hidden tensor for backward) and other shapes keep the two-convolution sequence.
 #include "h2.h"
 
-#include <stdlib.h>
-
 namespace rpde {
 
 template <int KS, int MT, int CO>
@@ -41,10 +39,7 @@ __global__ __launch_bounds__(256) void k_conv_mlp_h2(const float* __restrict__ x
       float v[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] = row < Cmid ? w1[row * CIN + 32 * ks + 8 * g + j] * wsc : 0.f;
-      union { f16x8 v; struct { uint2 a, b; } u; } H, L;
-      h2_split4(v[0], v[1], v[2], v[3], H.u.a, L.u.a);
-      h2_split4(v[4], v[5], v[6], v[7], H.u.b, L.u.b);
-      wh[mt][ks] = H.v; wl[mt][ks] = L.v;
+      h2_frag(v, wh[mt][ks], wl[mt][ks]);
     }
     // accumulator rows of this lane: hidden features 16 mt + 4g + j
     float bb[4], ww[CO][4];
@@ -131,7 +126,7 @@ __global__ __launch_bounds__(256) void k_conv_mlp_h2(const float* __restrict__ x
 }
 
 bool conv_mlp_ok(int Cin, int Cmid, int Cout, long S) {
-  if (const char* e = getenv("RPDE_CONV_MLP")) if (e[0] == '0') return false;
+  if (switch_off("RPDE_CONV_MLP")) return false;
   if (Cout < 1 || Cout > 4 || S % 16 != 0 || Cmid < 1) return false;
   if (Cin == 32) return Cmid <= 128;
   if (Cin == 64) return Cmid <= 64;
@@ -164,9 +159,8 @@ int rpde_conv_mlp_fwd(const float* x, const float* w1, const float* b1, const fl
   RPDE_CHECK_ARG(conv_mlp_ok(Cin, Cmid, Cout, (long)S), "conv_mlp_fwd: unsupported shape %d -> %d -> %d on %ld points", Cin, Cmid,
                  Cout, (long)S);
   hipStream_t st = as_stream(stream);
-  int dev = 0, cus = 256;
-  RPDE_HIP(hipGetDevice(&dev));
-  RPDE_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  int cus;
+  RPDE_HIP(cu_count(&cus));
   const long tiles = (long)B * (S / 16);
   long grid = (tiles + 3) / 4;
   if (grid > 8L * cus) grid = 8L * cus;

@@ -13,17 +13,14 @@
 // Everything is an h2 product (h2.h) in the transposed form of ff_fused.hip: a wave owns whole rows (b, m) and walks
 // along n in tiles of 16 points; the 32 x 16 accumulator pair of the tail (lane (g, li): channels 16 mt + 4 g + j of point
 // li) IS the B operand of the projection's first product once W1's fragments carry the matching permutation of the
-// reduction index (ff_perm), so H never changes lanes.  Resident per wave: Wc and W1 as A fragments (registers), the
+// reduction index (frag_perm), so H never changes lanes.  Resident per wave: Wc and W1 as A fragments (registers), the
 // row's spectra t_bm as A fragments (4 loads per row); shared by the workgroup in LDS: the synthesis table Fs as ready B
 // fragments per 16-point tile, b1 and W2.  Plain loads one tile ahead; no hand-counted waits.
 #include "conv_small.h"
 #include "h2.h"
 
-#include <stdlib.h>
-
 namespace rpde {
 
-__device__ __forceinline__ int cp_perm(int g, int j) { return 16 * (j >> 2) + 4 * g + (j & 3); }     // = ff_fused.hip's ff_perm
 
 struct ConvProjP {
   const float* x; const float* wc; const float* bc; const float* t; const float* fs_t;
@@ -74,20 +71,20 @@ __global__ __launch_bounds__(512, 2) void k_conv_syn_proj_h2(const ConvProjP P) 
       const int r = 8 * gg + j;
       v[j] = r < R2 ? P.fs_t[(long)r * N + point] * fsc : 0.f;
     }
-    uint2 h0, l0, h1, l1;
+    uint2 h0, l0, h1, l1;        // (h2_put_frag written out, here and below: through the helper the kernel is scheduled differently)
     h2_split4(v[0], v[1], v[2], v[3], h0, l0);
     h2_split4(v[4], v[5], v[6], v[7], h1, l1);
     *reinterpret_cast<uint4*>(smem + tq * 2048 + ln * 16) = make_uint4(h0.x, h0.y, h1.x, h1.y);
     *reinterpret_cast<uint4*>(smem + tq * 2048 + 1024 + ln * 16) = make_uint4(l0.x, l0.y, l1.x, l1.y);
   }
-  // W1 (rows = hidden, k = H channel in the slot order of the tail's accumulators: cp_perm)
+  // W1 (rows = hidden, k = H channel in the slot order of the tail's accumulators: frag_perm)
   for (int it = tid; it < MT * 64; it += 512) {
     const int mt = it >> 6, ln = it & 63, gg = ln >> 4, ll = ln & 15;
     const int hrow = 16 * mt + ll;
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const int c = cp_perm(gg, j);
+      const int c = frag_perm(gg, j);
       v[j] = (hrow < P.Cmid && c < P.Cout) ? P.w1[hrow * P.Cout + c] * s1c : 0.f;
     }
     uint2 h0, l0, h1, l1;
@@ -109,10 +106,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_syn_proj_h2(const ConvProjP P) 
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = o < P.Cout ? P.wc[o * 32 + 8 * g + j] * csc : 0.f;
-    union { f16x8 v; struct { uint2 a, b; } u; } H, L;
-    h2_split4(v[0], v[1], v[2], v[3], H.u.a, L.u.a);
-    h2_split4(v[4], v[5], v[6], v[7], H.u.b, L.u.b);
-    wch[mt] = H.v; wcl[mt] = L.v;
+    h2_frag(v, wch[mt], wcl[mt]);
   }
   float bb[2][4], b2v[CO];
 #pragma unroll
@@ -196,9 +190,8 @@ __global__ __launch_bounds__(512, 2) void k_conv_syn_proj_h2(const ConvProjP P) 
         float v[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = (q4 == 0 ? xc[j].x : (q4 == 1 ? xc[j].y : (q4 == 2 ? xc[j].z : xc[j].w))) * xs;
-        union { f16x8 v; struct { uint2 a, b; } u; } XH, XL;
-        h2_split4(v[0], v[1], v[2], v[3], XH.u.a, XL.u.a);
-        h2_split4(v[4], v[5], v[6], v[7], XH.u.b, XL.u.b);
+        f16x8 xh, xl;
+        h2_frag(v, xh, xl);
         const char* tf = smem + (T * 4 + q4) * 2048 + l * 16;
         const f16x8 fh = *reinterpret_cast<const f16x8*>(tf), fl = *reinterpret_cast<const f16x8*>(tf + 1024);
         // ---- the block's tail: H[c = 16 mt + 4 g + j][column li] ----
@@ -206,7 +199,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_syn_proj_h2(const ConvProjP P) 
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
           f32x4v a1 = {0.f, 0.f, 0.f, 0.f}, a2 = {0.f, 0.f, 0.f, 0.f};
-          a1 = h2_mfma32(wch[mt], wcl[mt], XH.v, XL.v, a1);
+          a1 = h2_mfma32(wch[mt], wcl[mt], xh, xl, a1);
           a2 = h2_mfma32(th[mt], tl[mt], fh, fl, a2);
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
@@ -216,7 +209,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_syn_proj_h2(const ConvProjP P) 
           }
         }
         // ---- projection: the eight H values of a lane are the slots (g, j) of a B fragment whose slot -> channel map is
-        // cp_perm, the map W1's fragments were built with ----
+        // frag_perm, the map W1's fragments were built with ----
         float hs, hi_;
         h2_scale(wave_max(hm), 0, hs, hi_);
         union { f16x8 v; struct { uint2 a, b; } u; } PH, PL;
@@ -266,7 +259,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_syn_proj_h2(const ConvProjP P) 
 }
 
 bool conv_syn_proj_ok(int Cin, int Cout, int M, int N, int R2, int Cmid, int Cq) {
-  if (const char* e = getenv("RPDE_CONV_PROJ")) if (e[0] == '0') return false;
+  if (switch_off("RPDE_CONV_PROJ")) return false;
   return Cin == 32 && Cout >= 1 && Cout <= 32 && Cmid >= 1 && Cmid <= 128 && Cq >= 1 && Cq <= 4 && N % 64 == 0 && N >= 64 &&
          N <= 1024 && R2 >= 8 && R2 <= 32 && R2 % 8 == 0 && M >= 1;
 }
@@ -293,9 +286,8 @@ int conv_syn_proj(const float* x, const float* wc, const float* bc, const float*
                   const float* b1, const float* w2, const float* b2, float* out, int B, int Cout, int M, int N, int R2, int Cmid,
                   int Cq, int act, hipStream_t st) {
   ConvProjP P{x, wc, bc, t, fs_t, w1, b1, w2, b2, out, B, Cout, M, N, R2, Cmid, Cq, act};
-  int dev = 0, cus = 256;
-  RPDE_HIP(hipGetDevice(&dev));
-  RPDE_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  int cus;
+  RPDE_HIP(cu_count(&cus));
   const long rows = (long)B * M;
   long grid = (rows + 7) / 8;
   if (grid > cus) grid = cus;                           // one workgroup of eight waves per CU

@@ -10,8 +10,6 @@
 #include "rpde_internal.h"
 #include "conv_small.h"
 
-#include <stdlib.h>
-
 namespace rpde {
 
 // the last stage of a channels-first spectral convolution folded into the same pass (evaluation-mode FNO block,
@@ -106,8 +104,7 @@ __global__ __launch_bounds__(256) void k_conv1x1_small(const float* __restrict__
 }
 
 bool conv1x1_small_ok(const float* x, const float* out, int Cin, int Cout, long S) {
-  const char* e = getenv("RPDE_CONV_SMALL");
-  if (e && e[0] == '0') return false;
+  if (switch_off("RPDE_CONV_SMALL")) return false;
   return Cout >= 1 && Cout <= 32 && Cin >= 1 && Cin <= 512 && S % 4 == 0 &&
          ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
 }

@@ -25,59 +25,7 @@
 #include "cw.h"
 #include "h2.h"
 
-#include <stdlib.h>
-
 namespace rpde {
-
-// offset of 4 consecutive f16 (columns 4 c8 ..) of row k in a [32][64] f16 tile with 128-byte rows, XOR-swizzled so
-// that the transposing reads below spread over all banks (the layout of fused_spectral.hip's staging area)
-__device__ __forceinline__ int cs_stage_off(int k, int c8) {
-  return k * 128 + ((c8 ^ ((((k >> 1) & 1) << 2) | (((k >> 3) & 1) << 3))) << 3);
-}
-
-// LDS stores the compiler does not see as such: with an LDS-DMA in flight it would put s_waitcnt vmcnt(0) in front of
-// every ordinary ds_write (it cannot tell that the DMA's landing area and the staging area are disjoint) and so drain
-// the prefetch.  A wave's DS instructions execute in order, so later reads of the same wave see these without a wait.
-typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned cs_lds_addr(const void* p) {
-  return (unsigned)(unsigned long)(const __attribute__((address_space(3))) char*)p;
-}
-__device__ __forceinline__ void cs_lds_write_b64(unsigned addr, uint2 v) {
-  const u32x2v t = {v.x, v.y};
-  asm volatile("ds_write_b64 %0, %1" ::"v"(addr), "v"(t) : "memory");
-}
-__device__ __forceinline__ void cs_lds_write_b32(unsigned addr, float v) {
-  asm volatile("ds_write_b32 %0, %1" ::"v"(addr), "v"(v) : "memory");
-}
-
-// The transposing read likewise (the builtin carries no memory operand, so with a DMA in flight the compiler waits for
-// vmcnt(0) in front of it): issued as asm, completed by cs_lds_wait4 on the four results.
-template <int OFF>
-__device__ __forceinline__ u32x2v cs_lds_read_tr16(unsigned addr) {
-  u32x2v r;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF) : "memory");
-  return r;
-}
-__device__ __forceinline__ void cs_lds_wait4(u32x2v& a, u32x2v& b, u32x2v& c, u32x2v& d) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d)::"memory");
-}
-
-// ... and the 16-byte reads of the output staging
-__device__ __forceinline__ f32x4v cs_lds_read_b128(unsigned addr) {
-  f32x4v r;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(r) : "v"(addr) : "memory");
-  return r;
-}
-__device__ __forceinline__ void cs_lds_wait8(f32x4v (&v)[8]) {
-  asm volatile("s_waitcnt lgkmcnt(0)"
-               : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7])::"memory");
-}
-
-template <int N>
-__device__ __forceinline__ void cs_wait_vmcnt() {
-  static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit counter");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // Cin = 32, R2 <= 32.  ACT: the activation; FULL: Cout = 32 (no predicate on the stores)
 //
@@ -116,7 +64,7 @@ __global__ __launch_bounds__(512) void k_conv_syn_h2(const float* __restrict__ x
   char* const raw = smem + wave * WAVE_LDS;
   char* const traw = raw + RAW;
   char* const stage = traw + TRAW;
-  const unsigned stage_a = cs_lds_addr(stage), raw_a = cs_lds_addr(raw);
+  const unsigned stage_a = lds_addr(stage), raw_a = lds_addr(raw);
   const int q = li >> 2, pp = li & 3;
   const int tsw = ((q >> 1) & 1) | ((g & 1) << 1);
   const int trow = (8 * g + q) * 128 + pp * 8;
@@ -140,10 +88,7 @@ __global__ __launch_bounds__(512) void k_conv_syn_h2(const float* __restrict__ x
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = o < Cout ? w[o * CIN + 8 * g + j] * wsc : 0.f;
-    union { f16x8 v; struct { uint2 a, b; } u; } H, L;
-    h2_split4(v[0], v[1], v[2], v[3], H.u.a, L.u.a);
-    h2_split4(v[4], v[5], v[6], v[7], H.u.b, L.u.b);
-    wh[mt] = H.v; wl[mt] = L.v;
+    h2_frag(v, wh[mt], wl[mt]);
   }
   f16x8 fh[4], fl[4];
   float finv;
@@ -196,7 +141,7 @@ __global__ __launch_bounds__(512) void k_conv_syn_h2(const float* __restrict__ x
     gy4 = *reinterpret_cast<const f32x4v*>(L.gy + n0 + 4 * li);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   }
-  cs_wait_vmcnt<0>();                                  // (the prologue's loads: from here on the queue is counted by hand)
+  wait_vmcnt<0>();                                  // (the prologue's loads: from here on the queue is counted by hand)
 
   // 12 DMA pieces of 1 KB (LIFT: 5): x slab piece i = channels 4 i + g, points n0 + 4 li .. + 3; spectra piece (mt, h)
   auto issue = [&](int r) {
@@ -226,27 +171,27 @@ __global__ __launch_bounds__(512) void k_conv_syn_h2(const float* __restrict__ x
     // this row's 12 pieces are in; the previous row's 8 stores may still be out (a predicated store that no lane takes is
     // not issued at all, so without FULL the count is unknown and the queue is drained)
     // (cw.h: the request is marked behind its last piece; tests/test_isa_counted_waits_cpu.py checks the 8 on the ISA)
-    if (first || !FULL) cs_wait_vmcnt<0>(); else cw_wait<0, 8>();
+    if (first || !FULL) wait_vmcnt<0>(); else cw_wait<0, 8>();
     first = false;
     // ---- x slab -> scaled f16 pieces in the staging area; spectra -> A fragments ----
     // (asm reads: an ordinary LDS load of a DMA's landing area makes the compiler wait for vmcnt(0), stores included)
     f32x4v xb[8], tq[8];
     if (LIFT) {
       // piece 0: u of this lane's four points; then (wl, bl) of channels 4 i + g; tq[4]: gx[m] (every lane the same)
-      tq[5] = cs_lds_read_b128(raw_a + l * 16);
+      tq[5] = lds_read_b128(raw_a + l * 16);
 #pragma unroll
-      for (int i = 0; i < 8; ++i) xb[i] = cs_lds_read_b128(raw_a + 1024 + (4 * i + g) * 16);
+      for (int i = 0; i < 8; ++i) xb[i] = lds_read_b128(raw_a + 1024 + (4 * i + g) * 16);
     } else {
 #pragma unroll
-      for (int i = 0; i < 8; ++i) xb[i] = cs_lds_read_b128(raw_a + i * 1024 + l * 16);
+      for (int i = 0; i < 8; ++i) xb[i] = lds_read_b128(raw_a + i * 1024 + l * 16);
     }
 #pragma unroll
-    for (int i = 0; i < 4; ++i) tq[i] = cs_lds_read_b128(raw_a + RAW + i * 1024 + l * 16);
-    if (LIFT) tq[4] = cs_lds_read_b128(raw_a + 2048 + (int)(m & ~3L) * 4); else tq[4] = tq[0];
+    for (int i = 0; i < 4; ++i) tq[i] = lds_read_b128(raw_a + RAW + i * 1024 + l * 16);
+    if (LIFT) tq[4] = lds_read_b128(raw_a + 2048 + (int)(m & ~3L) * 4); else tq[4] = tq[0];
     if (!LIFT) tq[5] = tq[0];
     tq[6] = tq[0]; tq[7] = tq[0];
-    cs_lds_wait8(xb);
-    cs_lds_wait8(tq);
+    lds_wait(xb);
+    lds_wait(tq);
     if (LIFT) {
       const int mm = (int)(m & 3);
       const float gxm = mm == 0 ? tq[4].x : (mm == 1 ? tq[4].y : (mm == 2 ? tq[4].z : tq[4].w));
@@ -277,9 +222,9 @@ __global__ __launch_bounds__(512) void k_conv_syn_h2(const float* __restrict__ x
     for (int i = 0; i < 8; ++i) {
       uint2 hi, lo;
       h2_split4(xb[i].x * xsc, xb[i].y * xsc, xb[i].z * xsc, xb[i].w * xsc, hi, lo);
-      const int off = cs_stage_off(4 * i + g, li);
-      cs_lds_write_b64(stage_a + off, hi);
-      cs_lds_write_b64(stage_a + 4096 + off, lo);
+      const int off = stage_off(4 * i + g, li);
+      lds_write_b64(stage_a + off, hi);
+      lds_write_b64(stage_a + 4096 + off, lo);
     }
     f16x8 th[2], tl[2];
 #pragma unroll
@@ -300,11 +245,11 @@ __global__ __launch_bounds__(512) void k_conv_syn_h2(const float* __restrict__ x
     for (int nt = 0; nt < 4; ++nt) {
       const unsigned ts = stage_a + trow + ((nt ^ tsw) << 5);
       union { struct { u32x2v a, b; } h; f16x8 v; } bh, bl;
-      bh.h.a = cs_lds_read_tr16<0>(ts);
-      bh.h.b = cs_lds_read_tr16<512>(ts);
-      bl.h.a = cs_lds_read_tr16<4096>(ts);
-      bl.h.b = cs_lds_read_tr16<4096 + 512>(ts);
-      cs_lds_wait4(bh.h.a, bh.h.b, bl.h.a, bl.h.b);
+      bh.h.a = lds_read_tr16<0>(ts);
+      bh.h.b = lds_read_tr16<512>(ts);
+      bl.h.a = lds_read_tr16<4096>(ts);
+      bl.h.b = lds_read_tr16<4096 + 512>(ts);
+      lds_wait(bh.h.a, bh.h.b, bl.h.a, bl.h.b);
 #pragma unroll
       for (int mt = 0; mt < 2; ++mt) {
         a1[mt][nt] = h2_mfma32(wh[mt], wl[mt], bh.v, bl.v, a1[mt][nt]);
@@ -324,14 +269,14 @@ __global__ __launch_bounds__(512) void k_conv_syn_h2(const float* __restrict__ x
           float v = fmaf(a1[mt][nt][j], i1, fmaf(a2[mt][nt][j], i2, bb[mt][j]));
           v = act_f(ACT, v);
           const int row = 16 * mt + 4 * g + j;
-          cs_lds_write_b32(stage_a + row * 256 + (((4 * nt + (li >> 2)) ^ (g << 2)) << 4) + (li & 3) * 4, v);
+          lds_write_b32(stage_a + row * 256 + (((4 * nt + (li >> 2)) ^ (g << 2)) << 4) + (li & 3) * 4, v);
         }
     wave_lds_fence();
     float* po = out + (b * Cout * M + m) * N + n0 + 4 * li;
     f32x4v ov[8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) ov[i] = cs_lds_read_b128(stage_a + (4 * i + g) * 256 + ((li ^ ((i & 3) << 2)) << 4));
-    cs_lds_wait8(ov);
+    for (int i = 0; i < 8; ++i) ov[i] = lds_read_b128(stage_a + (4 * i + g) * 256 + ((li ^ ((i & 3) << 2)) << 4));
+    lds_wait(ov);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const int row = 4 * i + g;
@@ -340,11 +285,11 @@ __global__ __launch_bounds__(512) void k_conv_syn_h2(const float* __restrict__ x
     }
     wave_lds_fence();
   }
-  cs_wait_vmcnt<0>();                                  // (the last issue() ran past the end: let it land before the LDS is released)
+  wait_vmcnt<0>();                                  // (the last issue() ran past the end: let it land before the LDS is released)
 }
 
 bool conv_syn_h2_ok(const float* x, const float* out, const float* t, int Cin, int Cout, int M, int N, int R2) {
-  if (const char* e = getenv("RPDE_CONV_SYN_H2")) if (e[0] == '0') return false;
+  if (switch_off("RPDE_CONV_SYN_H2")) return false;
   const bool nok = N == 64 || N == 128 || N == 256 || N == 512;
   // (the templates for Cin = 64 / R2 > 32 exist but spill registers: the multiply-add kernel keeps those shapes)
   return nok && (long)M < (1L << 20) && Cin == 32 && Cout >= 1 && Cout <= 32 && R2 >= 8 && R2 <= 32 && R2 % 8 == 0 && M >= 1 &&
@@ -360,9 +305,8 @@ int conv_syn_h2(const float* x, const float* w, const float* bias, const float* 
     set_error("conv_syn_h2: bad lifting arguments");
     return RPDE_ERR_ARG;
   }
-  int dev = 0, cus = 256;
-  RPDE_HIP(hipGetDevice(&dev));
-  RPDE_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  int cus;
+  RPDE_HIP(cu_count(&cus));
   const int rpi = 8 / (N / 64);
   long grid = ((long)B * M + rpi - 1) / rpi;
   if (grid > cus) grid = cus;

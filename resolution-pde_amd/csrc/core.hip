@@ -130,8 +130,8 @@ static int build_plan(rpde_plan** out, int n, int modes, int norm, int planar, i
   norm_scales(n, norm, sf, si);
   if (kind == PLAN_REAL) {
     RPDE_CHECK_ARG(modes <= n / 2 + 1, "plan: modes %d exceed n/2+1 = %d", modes, n / 2 + 1);
-    p->kp = (modes + 3) / 4 * 4;
-    p->ldn = (n + 3) / 4 * 4;
+    p->kp = r4(modes);
+    p->ldn = r4(n);
     RPDE_HIP(hipMalloc(&p->fa, sizeof(float) * 2 * p->kp * p->ldn));
     RPDE_HIP(hipMalloc(&p->fs, sizeof(float) * (size_t)n * 2 * p->kp));
     const int t1 = p->kp * p->ldn, t2 = n * p->kp;

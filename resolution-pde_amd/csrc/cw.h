@@ -33,4 +33,12 @@ __device__ __forceinline__ void cw_mark_t(int tag) {
   if (tag == 0) cw_mark<0>(); else if (tag == 1) cw_mark<1>(); else cw_mark<2>();
 }
 
+// s_waitcnt vmcnt(N) without a tag, which the ISA test does not look at: only where the count is not one the test can
+// prove (the instructions behind the data are issued by asm or sit on another path) or where the site drains to 0
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() {
+  static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit counter");
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
 }  // namespace rpde

@@ -20,7 +20,6 @@
 namespace rpde {
 
 // the thin-linear kernels move the wide operand as float4: a view with an odd storage offset takes the GEMM path
-static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 static inline int ff_in(const rpde_ff_params* p, int l) { return l == 0 ? p->dim : p->dim * p->factor; }
 static inline int ff_out(const rpde_ff_params* p, int l) { return l == p->n_layers - 1 ? p->dim : p->dim * p->factor; }
@@ -97,12 +96,11 @@ static int linear_wgrad_impl(const float* x, const float* gy, float* gw, float* 
 }
 
 // gx[P,in] = gy[P,out] . W[out,in]   (optionally through act': * act'(drop(z)) * dropscale)
-static inline bool al16p(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static inline long colsum_tiles(long P) { return (P + 127) / 128; }
 // the backward-data GEMM can hand back per-tile column sums of gx (= the bias gradient of the layer below)
 static inline bool can_fuse_colsum(const float* gy, const float* w, const float* gx, const float* z, long P, int in_f,
                                    int out_f) {
-  return P > 64 && in_f % 4 == 0 && out_f % 4 == 0 && al16p(gy) && al16p(w) && al16p(gx) && (!z || al16p(z));
+  return P > 64 && in_f % 4 == 0 && out_f % 4 == 0 && al16(gy) && al16(w) && al16(gx) && (!z || al16(z));
 }
 
 // gx[P,in] = (gy[P,out] . W[out,in]) (* dstored[P,in] when given: the derivative saved by the forward epilogue)

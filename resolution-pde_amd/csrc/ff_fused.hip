@@ -46,9 +46,6 @@ constexpr int FF_IMG_BYTES = FF_WAVES * FF_FRAGS * 2048;
 constexpr int FF_NCONST = 16;
 constexpr int FF_PREP_BLOCKS = FF_WAVES * FF_FRAGS * 64 / 1024;      // 12: one fragment item per thread
 
-// reduction-slot -> hidden feature inside a 32-wide slice, for operands built from two accumulator tiles
-__device__ __forceinline__ int ff_perm(int g, int j) { return 16 * (j >> 2) + 4 * g + (j & 3); }
-
 // ---- weight preparation: FF_PREP_BLOCKS blocks; each finds the maxima (all of the 98 K weights: cheap, and no grid
 // ---- synchronisation needed), then builds its share of the fragments in per-wave register order ----
 __global__ __launch_bounds__(1024) void k_ff3_prep(const float* __restrict__ w1, const float* __restrict__ w2,
@@ -121,18 +118,13 @@ __global__ __launch_bounds__(1024) void k_ff3_prep(const float* __restrict__ w1,
     } else if (f < 20) {         // W2, permuted: tile 2w + ((f-4)>>3), slice kappa = (f-4)&7
       const int row = 16 * (2 * w + ((f - 4) >> 3)) + li, kap = (f - 4) & 7;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) x[j] = w2[row * 256 + 32 * kap + ff_perm(g, j)] * sc[1];
+      for (int j = 0; j < 8; ++j) x[j] = w2[row * 256 + 32 * kap + frag_perm(g, j)] * sc[1];
     } else {                     // W3, permuted: output tile f-20, slice kappa = w
       const int row = 16 * (f - 20) + li;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) x[j] = w3[row * 256 + 32 * w + ff_perm(g, j)] * sc[2];
+      for (int j = 0; j < 8; ++j) x[j] = w3[row * 256 + 32 * w + frag_perm(g, j)] * sc[2];
     }
-    uint2 h0, l0, h1, l1;
-    h2_split4(x[0], x[1], x[2], x[3], h0, l0);
-    h2_split4(x[4], x[5], x[6], x[7], h1, l1);
-    char* p = img + ((long)(w * FF_FRAGS + f)) * 2048 + ln * 16;
-    *reinterpret_cast<uint4*>(p) = make_uint4(h0.x, h0.y, h1.x, h1.y);
-    *reinterpret_cast<uint4*>(p + 1024) = make_uint4(l0.x, l0.y, l1.x, l1.y);
+    h2_put_frag(img + ((long)(w * FF_FRAGS + f)) * 2048 + ln * 16, x);
   }
 }
 
@@ -157,10 +149,6 @@ constexpr int FF_STAT = FF_VEC + 2816;            // [2 blk][4 tile][16 points][
 constexpr int FF_INFO = FF_STAT + 1024;           // [2 parity][2 blk][16 points] floats: maximum of each input point
 constexpr int FF_LDS = FF_INFO + 256;
 
-// workgroup barrier that orders LDS traffic only: __syncthreads() would also wait for every outstanding global
-// store (the h / d tensors a training forward writes) several times per tile
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 // bias, dropout, GELU on four consecutive features of one point; u = dropout(z), h = gelu(u) and
 // d = gelu'(u) * dropscale out (whatever the caller does not use is dead code)
 __device__ __forceinline__ void ff_act4(const f32x4v acc, float inv, const float4 b, const DropCfg& drop, uint64_t id,
@@ -180,15 +168,6 @@ __device__ __forceinline__ float4 ff_dact4(const float4 u, const DropCfg& drop, 
   float s[4] = {1.f, 1.f, 1.f, 1.f};
   if (drop.on()) drop_scale4(drop, id, s);
   return make_float4(dgelu_f(u.x) * s[0], dgelu_f(u.y) * s[1], dgelu_f(u.z) * s[2], dgelu_f(u.w) * s[3]);
-}
-
-// eight scaled activations of a lane (two accumulator tiles) -> one B fragment (hi, lo) at dst / dst + 1 KB
-__device__ __forceinline__ void ff_put_frag(char* dst, const float (&v)[8]) {
-  uint2 h0, l0, h1, l1;
-  h2_split4(v[0], v[1], v[2], v[3], h0, l0);
-  h2_split4(v[4], v[5], v[6], v[7], h1, l1);
-  *reinterpret_cast<uint4*>(dst) = make_uint4(h0.x, h0.y, h1.x, h1.y);
-  *reinterpret_cast<uint4*>(dst + 1024) = make_uint4(l0.x, l0.y, l1.x, l1.y);
 }
 
 // MODE 0: evaluation (only `out` is written); 1: training, h and d = gelu'(u) * dropscale of both hidden layers stored
@@ -277,7 +256,7 @@ __global__ __launch_bounds__(64 * FF_WAVES, 2) void k_ff3_fwd_h2(const FF3P A0) 
     for (int ks = 0; ks < 2; ++ks) {
       const float v[8] = {sn[2 * ks].x * sc, sn[2 * ks].y * sc, sn[2 * ks].z * sc, sn[2 * ks].w * sc,
                           sn[2 * ks + 1].x * sc, sn[2 * ks + 1].y * sc, sn[2 * ks + 1].z * sc, sn[2 * ks + 1].w * sc};
-      ff_put_frag(dst + ks * 2048, v);
+      h2_put_frag(dst + ks * 2048, v);
     }
     if (g == 0) info[(par * 2 + w) * 16 + li] = m;
   };
@@ -356,7 +335,7 @@ __global__ __launch_bounds__(64 * FF_WAVES, 2) void k_ff3_fwd_h2(const FF3P A0) 
 #pragma unroll
         for (int r = 0; r < 4; ++r) hv[4 * t + r] = h[r] * sh1;
       }
-      ff_put_frag(smem + FF_HBUF + ((blk * 8 + w) * 2) * 1024 + l * 16, hv);
+      h2_put_frag(smem + FF_HBUF + ((blk * 8 + w) * 2) * 1024 + l * 16, hv);
     }
     FFSTAMP(2);
     lds_barrier();                         // B1: all eight slices of h1 are in LDS
@@ -396,7 +375,7 @@ __global__ __launch_bounds__(64 * FF_WAVES, 2) void k_ff3_fwd_h2(const FF3P A0) 
 #pragma unroll
         for (int r = 0; r < 4; ++r) hv[4 * t + r] = h[r] * sh2;
       }
-      ff_put_frag(smem + FF_H2BUF + ((blk * 8 + w) * 2) * 1024 + l * 16, hv);
+      h2_put_frag(smem + FF_H2BUF + ((blk * 8 + w) * 2) * 1024 + l * 16, hv);
     }
     FFSTAMP(4);
     lds_barrier();                         // B2: all eight slices of h2 are in LDS
@@ -551,22 +530,17 @@ __global__ __launch_bounds__(1024) void k_ff3_prep_bwd(const float* __restrict__
     if (f < 4) {                 // W3^T: hidden tile 2w + (f>>1), reduction over the 64 output features, half f&1
       const int hid = 16 * (2 * w + (f >> 1)) + li;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) x[j] = w3[(32 * (f & 1) + ff_perm(g, j)) * 256 + hid] * sc[2];
+      for (int j = 0; j < 8; ++j) x[j] = w3[(32 * (f & 1) + frag_perm(g, j)) * 256 + hid] * sc[2];
     } else if (f < 20) {         // W2^T: hidden-1 tile 2w + ((f-4)>>3), reduction slice kappa of hidden-2
       const int hid1 = 16 * (2 * w + ((f - 4) >> 3)) + li, kap = (f - 4) & 7;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) x[j] = w2[(32 * kap + ff_perm(g, j)) * 256 + hid1] * sc[1];
+      for (int j = 0; j < 8; ++j) x[j] = w2[(32 * kap + frag_perm(g, j)) * 256 + hid1] * sc[1];
     } else {                     // W1^T: input-feature tile f-20, reduction slice kappa = w of hidden-1
       const int feat = 16 * (f - 20) + li;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) x[j] = w1[(32 * w + ff_perm(g, j)) * 64 + feat] * sc[0];
+      for (int j = 0; j < 8; ++j) x[j] = w1[(32 * w + frag_perm(g, j)) * 64 + feat] * sc[0];
     }
-    uint2 h0, l0, h1, l1;
-    h2_split4(x[0], x[1], x[2], x[3], h0, l0);
-    h2_split4(x[4], x[5], x[6], x[7], h1, l1);
-    char* p = img + ((long)(w * FF_FRAGS + f)) * 2048 + ln * 16;
-    *reinterpret_cast<uint4*>(p) = make_uint4(h0.x, h0.y, h1.x, h1.y);
-    *reinterpret_cast<uint4*>(p + 1024) = make_uint4(l0.x, l0.y, l1.x, l1.y);
+    h2_put_frag(img + ((long)(w * FF_FRAGS + f)) * 2048 + ln * 16, x);
   }
 }
 
@@ -593,59 +567,6 @@ constexpr int FB_VEC = FB_D1 + 32768;              // gamma[64] beta[64]
 constexpr int FB_ACC = FB_VEC + 512;               // db1[256] db2[256] | db3, dgamma, dbeta: [3][8 wave][64]         = 8 KB
 constexpr int FB_INFO = FB_ACC + 8192;             // [2 blk][16 points] bound of |dz3|
 constexpr int FB_LDS = FB_INFO + 128;
-
-// sum over the 16 lanes of a row (one point block), valid in lane 15 of the row
-__device__ __forceinline__ float row_sum15(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x111, 0xf, 0xf, true));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x112, 0xf, 0xf, true));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x114, 0xf, 0xf, true));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x118, 0xf, 0xf, true));
-  return v;
-}
-
-// LDS reads / global loads the compiler does not see as such.  An ordinary read of an LDS-DMA landing area makes it wait
-// for vmcnt(0) -- stores included, and again after every store in between -- and an ordinary load that is one tile in
-// flight is answered with vmcnt(0) at its use, i.e. with a wait for the DMA issued just before.  Results pass through
-// the wait statements as tied operands (what orders their uses behind the wait); ONE statement per wait, and the
-// in-flight registers are followed through the ISA by tests/test_isa_pending_loads_cpu.py.
-__device__ __forceinline__ f32x4v fb_lds_read_b128(unsigned addr) {
-  f32x4v r;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(r) : "v"(addr) : "memory");
-  return r;
-}
-__device__ __forceinline__ void fb_lds_wait2(f32x4v& a, f32x4v& b) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b)::"memory");
-}
-__device__ __forceinline__ void fb_lds_write_b128(unsigned addr, f32x4v v) {
-  asm volatile("ds_write_b128 %0, %1" ::"v"(addr), "v"(v) : "memory");
-}
-__device__ __forceinline__ void fb_lds_write_b64(unsigned addr, uint2 v) {
-  asm volatile("ds_write_b64 %0, %1" ::"v"(addr), "v"(v) : "memory");
-}
-__device__ __forceinline__ void fb_lds_write_b32(unsigned addr, float v) {
-  asm volatile("ds_write_b32 %0, %1" ::"v"(addr), "v"(v) : "memory");
-}
-__device__ __forceinline__ f32x4v fb_gload(const float* p) {
-  f32x4v v;
-  asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v) : "v"(p) : "memory");
-  return v;
-}
-
-// sum / maximum over the 16 lanes of a row, in every lane (quad butterflies, then the two mirrors)
-template <bool MAX>
-__device__ __forceinline__ float row_all16(float v) {
-#define RPDE_ROW_STEP(CTRL)                                                                               \
-  {                                                                                                       \
-    const float o_ = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true)); \
-    v = MAX ? fmaxf(v, o_) : v + o_;                                                                      \
-  }
-  RPDE_ROW_STEP(0xB1)      // quad_perm [1,0,3,2]
-  RPDE_ROW_STEP(0x4E)      // quad_perm [2,3,0,1]
-  RPDE_ROW_STEP(0x141)     // row_half_mirror
-  RPDE_ROW_STEP(0x140)     // row_mirror
-#undef RPDE_ROW_STEP
-  return v;
-}
 
 // RECOMP: A.d2 / A.d1 hold u = dropout(z) of the hidden layers (forward mode 2); the derivative factors are
 // re-evaluated here from u and the regenerated dropout masks
@@ -681,7 +602,7 @@ __global__ __launch_bounds__(64 * FF_WAVES, 2) void k_ff3_bwd_h2(const FF3B A0) 
   float* const acc_dbt = acc_db1 + 1536;       // [8 wave][64]
   float* const info = reinterpret_cast<float*>(smem + FB_INFO);
   const float winv1 = A.consts[0], winv2 = A.consts[1], winv3 = A.consts[2], c3t = A.consts[3], c2t = A.consts[4];
-  const unsigned lds0 = (unsigned)(uintptr_t)smem;
+  const unsigned lds0 = lds_addr(smem);
   // role in the last-layer adjoint: one POINT per 16-lane row (point 4 w + q of the tile), lane li takes features
   // 4 li .. 4 li + 3 -- the LayerNorm statistics are sums over a row (DPP), no exchange between waves
   const int q3 = l >> 4, feat = 4 * li;
@@ -690,8 +611,8 @@ __global__ __launch_bounds__(64 * FF_WAVES, 2) void k_ff3_bwd_h2(const FF3B A0) 
   f32x4v g4n = {0.f, 0.f, 0.f, 0.f}, z4n = g4n;
   auto in_issue = [&](int tile) {
     const long p = min((long)tile * 32 + 4 * w + q3, A.P - 1);
-    g4n = fb_gload(A.g + p * 64 + feat);
-    z4n = fb_gload(A.z3 + p * 64 + feat);
+    g4n = global_load_b128(A.g + p * 64 + feat);
+    z4n = global_load_b128(A.z3 + p * 64 + feat);
   };
   // d2 / d1 of this wave's hidden slice for one tile: four 1 KB pieces (block, row tile), each lane's float4 at [piece][lane]
   typedef __attribute__((address_space(3))) void* lds_ptr;
@@ -746,9 +667,9 @@ __global__ __launch_bounds__(64 * FF_WAVES, 2) void k_ff3_bwd_h2(const FF3B A0) 
       const float m2 = row_all16<false>((tz[0] - mean) * (tz[0] - mean) + (tz[1] - mean) * (tz[1] - mean) +
                                         (tz[2] - mean) * (tz[2] - mean) + (tz[3] - mean) * (tz[3] - mean));
       const float rstd = rsqrtf(m2 * (1.f / 64.f) + A.eps);
-      f32x4v gm = fb_lds_read_b128(lds0 + FB_VEC + feat * 4);
-      f32x4v bt = fb_lds_read_b128(lds0 + FB_VEC + 256 + feat * 4);
-      fb_lds_wait2(gm, bt);
+      f32x4v gm = lds_read_b128(lds0 + FB_VEC + feat * 4);
+      f32x4v bt = lds_read_b128(lds0 + FB_VEC + 256 + feat * 4);
+      lds_wait(gm, bt);
       const float gmv[4] = {gm.x, gm.y, gm.z, gm.w}, btv[4] = {bt.x, bt.y, bt.z, bt.w};
       float xh[4], dxh[4], s1 = 0.f, s2 = 0.f, am = 0.f;
 #pragma unroll
@@ -793,16 +714,16 @@ __global__ __launch_bounds__(64 * FF_WAVES, 2) void k_ff3_bwd_h2(const FF3B A0) 
         // (asm: an ordinary access here is preceded by vmcnt(0) -- the compiler cannot tell these addresses from the
         //  DMA's landing areas -- i.e. by a wait for the d1 pieces requested a moment ago)
         const unsigned a0 = lds0 + FB_ACC + (512 + w * 64 + feat) * 4;
-        f32x4v v3 = fb_lds_read_b128(a0), vg = fb_lds_read_b128(a0 + 2048), vb = fb_lds_read_b128(a0 + 4096);
-        fb_lds_wait2(v3, vg);
-        fb_lds_wait2(vb, vb);
+        f32x4v v3 = lds_read_b128(a0), vg = lds_read_b128(a0 + 2048), vb = lds_read_b128(a0 + 4096);
+        lds_wait(v3, vg);
+        lds_wait(vb, vb);
         v3.x += b[0]; v3.y += b[1]; v3.z += b[2]; v3.w += b[3];
-        fb_lds_write_b128(a0, v3);
+        lds_write_b128(a0, v3);
         if (A.layer_norm) {
           vg.x += dgm[0]; vg.y += dgm[1]; vg.z += dgm[2]; vg.w += dgm[3];
           vb.x += dbt[0]; vb.y += dbt[1]; vb.z += dbt[2]; vb.w += dbt[3];
-          fb_lds_write_b128(a0 + 2048, vg);
-          fb_lds_write_b128(a0 + 4096, vb);
+          lds_write_b128(a0 + 2048, vg);
+          lds_write_b128(a0 + 4096, vb);
         }
       }
     }
@@ -821,9 +742,9 @@ __global__ __launch_bounds__(64 * FF_WAVES, 2) void k_ff3_bwd_h2(const FF3B A0) 
       const int ksz = li >> 3, cz = li & 3;
       const unsigned dst = lds0 + FB_DZBUF + (((ptl >> 4) * 2 + ksz) * 2) * 1024 + (cz * 16 + ((ptl & 15) ^ cz ^ (4 * ksz))) * 16 +
                            ((li >> 2) & 1) * 8;
-      fb_lds_write_b64(dst, hi);
-      fb_lds_write_b64(dst + 1024, lo);
-      if (li == 0) fb_lds_write_b32(lds0 + FB_INFO + ptl * 4, dzb);
+      lds_write_b64(dst, hi);
+      lds_write_b64(dst + 1024, lo);
+      if (li == 0) lds_write_b32(lds0 + FB_INFO + ptl * 4, dzb);
     }
     lds_barrier();                                                                    // C: dz3 fragments + bounds in LDS
     FBSTAMP(3);
@@ -852,9 +773,9 @@ __global__ __launch_bounds__(64 * FF_WAVES, 2) void k_ff3_bwd_h2(const FF3B A0) 
 #pragma unroll
     for (int blk = 0; blk < 2; ++blk) {
       f32x4v dq[2];                                // the wave's two pieces [t] of d2 for this block
-      dq[0] = fb_lds_read_b128(lds0 + FB_D2 + (w * 4 + blk * 2) * 1024 + l * 16);
-      dq[1] = fb_lds_read_b128(lds0 + FB_D2 + (w * 4 + blk * 2 + 1) * 1024 + l * 16);
-      fb_lds_wait2(dq[0], dq[1]);
+      dq[0] = lds_read_b128(lds0 + FB_D2 + (w * 4 + blk * 2) * 1024 + l * 16);
+      dq[1] = lds_read_b128(lds0 + FB_D2 + (w * 4 + blk * 2 + 1) * 1024 + l * 16);
+      lds_wait(dq[0], dq[1]);
       const int zu = (l & 48) | ((l & 15) ^ (l >> 4));             // this lane's unit in the ks = 0 pieces; ks = 1: ^ 4
       const char* zb = smem + FB_DZBUF + (blk * 2) * 2048;
       const f16x8 zh0 = *reinterpret_cast<const f16x8*>(zb + zu * 16), zl0 = *reinterpret_cast<const f16x8*>(zb + 1024 + zu * 16);
@@ -882,7 +803,7 @@ __global__ __launch_bounds__(64 * FF_WAVES, 2) void k_ff3_bwd_h2(const FF3B A0) 
 #pragma unroll
         for (int r = 0; r < 4; ++r) hv[4 * t + r] = u[r] * s_du2;
       }
-      {                                            // (ff_put_frag through asm writes: see fb_lds_read_b128)
+      {                                            // (h2_put_frag through asm writes: wave.h, lds_read_b128)
         uint2 h0, l0, h1, l1;
         h2_split4(hv[0], hv[1], hv[2], hv[3], h0, l0);
         h2_split4(hv[4], hv[5], hv[6], hv[7], h1, l1);
@@ -890,8 +811,8 @@ __global__ __launch_bounds__(64 * FF_WAVES, 2) void k_ff3_bwd_h2(const FF3B A0) 
         f32x4v ph, pl;
         ph.x = __uint_as_float(h0.x); ph.y = __uint_as_float(h0.y); ph.z = __uint_as_float(h1.x); ph.w = __uint_as_float(h1.y);
         pl.x = __uint_as_float(l0.x); pl.y = __uint_as_float(l0.y); pl.z = __uint_as_float(l1.x); pl.w = __uint_as_float(l1.y);
-        fb_lds_write_b128(dst, ph);
-        fb_lds_write_b128(dst + 1024, pl);
+        lds_write_b128(dst, ph);
+        lds_write_b128(dst + 1024, pl);
       }
     }
 #pragma unroll
@@ -933,9 +854,9 @@ __global__ __launch_bounds__(64 * FF_WAVES, 2) void k_ff3_bwd_h2(const FF3B A0) 
 #pragma unroll
       for (int blk = 0; blk < 2; ++blk) {
         f32x4v dq[2];
-        dq[0] = fb_lds_read_b128(lds0 + FB_D1 + (w * 4 + blk * 2) * 1024 + l * 16);
-        dq[1] = fb_lds_read_b128(lds0 + FB_D1 + (w * 4 + blk * 2 + 1) * 1024 + l * 16);
-        fb_lds_wait2(dq[0], dq[1]);
+        dq[0] = lds_read_b128(lds0 + FB_D1 + (w * 4 + blk * 2) * 1024 + l * 16);
+        dq[1] = lds_read_b128(lds0 + FB_D1 + (w * 4 + blk * 2 + 1) * 1024 + l * 16);
+        lds_wait(dq[0], dq[1]);
         const long pt = p0 + 16 * blk + li;
         float q0, q1, inv_b, s_du1, q2;
         bscales(blk, q0, q1, inv_b, s_du1, q2);
@@ -989,7 +910,7 @@ __global__ __launch_bounds__(64 * FF_WAVES, 2) void k_ff3_bwd_h2(const FF3B A0) 
 
 // ------------------------------------------------------------------------------------------------------------
 bool ff3_fused_ok(const rpde_ff_params* p, long P) {
-  if (const char* e = getenv("RPDE_FUSED_FF")) if (e[0] == '0') return false;
+  if (switch_off("RPDE_FUSED_FF")) return false;
   // (the preparation kernels read the weight matrices 16 bytes at a time: a view with an odd storage offset takes the
   //  per-GEMM path)
   for (int l = 0; l < 3 && p->weights; ++l)
@@ -1032,9 +953,8 @@ int ff3_fused_fwd(const rpde_ff_params* p, const float* x, const float* residual
     A.drop[l] = make_drop(p->dropout_p, layer_seed(p->seed, l), p->seed_epoch);
   }
   A.ntiles = (int)((P + 31) / 32);
-  int dev = 0, cus = 256;
-  RPDE_HIP(hipGetDevice(&dev));
-  RPDE_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  int cus;
+  RPDE_HIP(cu_count(&cus));
   const int grid = A.ntiles < cus ? A.ntiles : cus;
   if (mode == 1) hipLaunchKernelGGL(k_ff3_fwd_h2<1>, dim3(grid), dim3(64 * FF_WAVES), 0, st, A);
   else if (mode == 2) hipLaunchKernelGGL(k_ff3_fwd_h2<2>, dim3(grid), dim3(64 * FF_WAVES), 0, st, A);
@@ -1065,9 +985,8 @@ int ff3_fused_bwd_launch(const rpde_ff_params* p, const float* const* ds, int re
   A.drop0 = dc[0]; A.drop1 = dc[1]; A.drop2 = dc[2];
   A.dmax = 1.13f * A.drop2.scale;          // |gelu'| <= 1.129, times the dropout scale folded into d
   A.ntiles = (int)((P + 31) / 32);
-  int dev = 0, cus = 256;
-  RPDE_HIP(hipGetDevice(&dev));
-  RPDE_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  int cus;
+  RPDE_HIP(cu_count(&cus));
   if (cus > 1024) cus = 1024;
   const int grid = A.ntiles < cus ? A.ntiles : cus;
   if (recompute) hipLaunchKernelGGL(k_ff3_bwd_h2<true>, dim3(grid), dim3(64 * FF_WAVES), 0, st, A);

@@ -86,7 +86,7 @@ __global__ __launch_bounds__(256) void k_fe(const FeP P) {
     f32x4v tot[NTW][2];
 #pragma unroll
     for (int i = 0; i < NTW; ++i) tot[i][0] = tot[i][1] = (f32x4v){0.f, 0.f, 0.f, 0.f};
-    // wave w stages the half-steps q = w + 4 i of a block: step q >> 1, points 16 (q & 1) + 4 g .. + 3 of it (cf_perm)
+    // wave w stages the half-steps q = w + 4 i of a block: step q >> 1, points 16 (q & 1) + 4 g .. + 3 of it (frag_perm)
     float4 na[4], nb[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -270,13 +270,6 @@ static int fe_fragments(const char** out, const float* src, long rs, int R, int 
   return RPDE_OK;
 }
 
-static int fe_cus() {
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  return cus;
-}
-
 // output tiles per wave.  Few workgroups (a Burgers batch is four row tiles): one, so that the tiles spread over the
 // chip.  Otherwise four or five, whichever needs fewer workgroups along the outputs -- every one of them stages the row
 // tile again, and the power-of-two grids have one tile more than a multiple of 16 (NT = 17 at W = 256, 65 at n = 1024,
@@ -285,16 +278,15 @@ template <bool DIFF, bool SPEC>
 static int fe_launch(const FeP& P, int groups, hipStream_t st) {
   const int ng4 = (P.NT + 15) / 16, ng5 = (P.NT + 19) / 20;
   const int ng = ng5 < ng4 ? ng5 : ng4;
-  if ((long)P.S * ng * groups < fe_cus())
+  int cus;
+  (void)cu_count(&cus);
+  if ((long)P.S * ng * groups < cus)
     hipLaunchKernelGGL((k_fe<DIFF, SPEC, 1>), dim3(P.S, (P.NT + 3) / 4, groups), dim3(256), 0, st, P);
   else if (ng5 < ng4) hipLaunchKernelGGL((k_fe<DIFF, SPEC, 5>), dim3(P.S, ng5, groups), dim3(256), 0, st, P);
   else hipLaunchKernelGGL((k_fe<DIFF, SPEC, 4>), dim3(P.S, ng4, groups), dim3(256), 0, st, P);
   RPDE_LAUNCH_CHECK();
   return RPDE_OK;
 }
-
-static inline int r4i(int v) { return (v + 3) / 4 * 4; }
-static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 int fe_chunk_images(long images, int H, int W) {
   const size_t per = (size_t)2 * (W / 2 + 1) * 2 * H * sizeof(float);
@@ -314,7 +306,7 @@ size_t rpde_freq_energy1d_ws_bytes(int64_t rows, int n, int num_modes) {
   if (rows < 1 || n < 2 || n > FE_MAX_N || num_modes < 1) return 0;
   const long tiles = (rows + 15) / 16;
   const int S = (int)(tiles < FE_SLOTS_1D ? tiles : FE_SLOTS_1D);
-  const int NT = (2 * r4i(num_modes) + 15) / 16;
+  const int NT = (2 * r4(num_modes) + 15) / 16;
   return arena_bytes((size_t)S * 2 * NT * 16);
 }
 

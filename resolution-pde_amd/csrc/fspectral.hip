@@ -18,8 +18,6 @@
 #include "fused_spectral.h"
 #include "mix1d.h"
 
-#include <stdlib.h>
-
 namespace rpde {
 
 struct Axis {
@@ -105,14 +103,14 @@ static int wgrad_tiles(int C) { const int t = (2 * C + 127) / 128; return t * t;
 static int make_axis(Axis& ax, int n, int K, int norm, int rows, int zdiv, long s1, long s2, long ld, hipStream_t st) {
   ax.n = n;
   ax.keff = K < n / 2 + 1 ? K : n / 2 + 1;
-  ax.kp = (ax.keff + 3) / 4 * 4;
+  ax.kp = r4(ax.keff);
   ax.rows = rows; ax.zdiv = zdiv; ax.s1 = s1; ax.s2 = s2; ax.ld = ld;
   return get_plan(&ax.plan, n, ax.keff, norm, 0, PLAN_REAL, st);
 }
 
 // geometry without touching the device (for the size queries)
 static void axis_dims(Axis& ax, int n, int K, int rows) {
-  ax.n = n; ax.keff = K < n / 2 + 1 ? K : n / 2 + 1; ax.kp = (ax.keff + 3) / 4 * 4; ax.rows = rows;
+  ax.n = n; ax.keff = K < n / 2 + 1 ? K : n / 2 + 1; ax.kp = r4(ax.keff); ax.rows = rows;
   ax.zdiv = 1; ax.s1 = ax.s2 = ax.ld = 0; ax.plan = nullptr;
 }
 
@@ -190,8 +188,7 @@ static int axis_bwd(const Axis& ax, const float* g, const float* spec_in, const 
 // ---- one synthesis launch that writes the field once
 // RPDE_FUSED_MIX=0: mode mix by pack + GEMM + split per axis (the round-2 sequence; A/B and tests)
 static bool fused_mix_on() {
-  const char* e = getenv("RPDE_FUSED_MIX");
-  return !(e && e[0] == '0');
+  return !switch_off("RPDE_FUSED_MIX");
 }
 
 // slabs of lines for the h2 weight gradient of the mix: enough workgroups to fill the chip (keff x S x 2), at least four

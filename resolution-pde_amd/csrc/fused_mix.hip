@@ -19,8 +19,6 @@
 #include "fused_spectral.h"
 #include "h2.h"
 
-#include <stdlib.h>
-
 namespace rpde {
 
 // ------------------------------------------------------------------------------------------------------------
@@ -88,12 +86,11 @@ __global__ __launch_bounds__(256) void k_mix_prep(const float* __restrict__ w_y,
         if (conj_t && part) x = -x;
         v[j] = x * sc;
       }
-      uint2 h0, l0, h1, l1;
-      h2_split4(v[0], v[1], v[2], v[3], h0, l0);
-      h2_split4(v[4], v[5], v[6], v[7], h1, l1);
+      uint4 hi, lo;
+      h2_split8(v, hi, lo);
       char* p = out + (((cb * 2 + part) * 2 + ks) * 2) * 1024 + l * 16;
-      *reinterpret_cast<uint4*>(p) = make_uint4(h0.x, h0.y, h1.x, h1.y);
-      *reinterpret_cast<uint4*>(p + 1024) = make_uint4(l0.x, l0.y, l1.x, l1.y);
+      *reinterpret_cast<uint4*>(p) = hi;
+      *reinterpret_cast<uint4*>(p + 1024) = lo;
     }
 }
 
@@ -119,8 +116,6 @@ struct MixP {
   const char* wimg; const float* wc;
   int kp, R, nq;
 };
-
-__device__ __forceinline__ void lds_barrier_mix() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // LDS: A fragments of one line tile: [mode 4][re, im, -im][ks 2][hi|lo][1 KB] = 48 KB
 constexpr int MIX_LDS = 4 * 3 * 2 * 2 * 1024;
@@ -204,7 +199,7 @@ __global__ __launch_bounds__(256, 2) void k_mix_h2(const MixP P) {
         }
     }
     if (t + 1 < t1) issue(t + 1);
-    lds_barrier_mix();                                   // fragments of all four modes are in LDS
+    lds_barrier();                                       // fragments of all four modes are in LDS
     f32x4v cre[4], cim[4];
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
@@ -222,7 +217,7 @@ __global__ __launch_bounds__(256, 2) void k_mix_h2(const MixP P) {
         cim[kk] = h2_mfma32(imh, iml, wf[kk][0][ks][0], wf[kk][0][ks][1], cim[kk]);
       }
     }
-    lds_barrier_mix();                                   // everyone has its fragments in registers: LDS is free again
+    lds_barrier();                                       // everyone has its fragments in registers: LDS is free again
     // ---- epilogue: lane (g, li) holds, for lines 4g+jj, channel 16cb+li, the eight rows 8q..8q+7 ----
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) {
@@ -240,7 +235,7 @@ __global__ __launch_bounds__(256, 2) void k_mix_h2(const MixP P) {
         v[2 * kk] = cre[kk][jj] * fk;
         v[2 * kk + 1] = cim[kk][jj] * fk;
       }
-      uint2 h0, l0, h1, l1;
+      uint2 h0, l0, h1, l1;      // (h2_split8 written out: through the helper k_mix_h2<1, 0> is scheduled differently)
       h2_split4(v[0], v[1], v[2], v[3], h0, l0);
       h2_split4(v[4], v[5], v[6], v[7], h1, l1);
       const uint4 hi = make_uint4(h0.x, h0.y, h1.x, h1.y), lo = make_uint4(l0.x, l0.y, l1.x, l1.y);
@@ -287,10 +282,6 @@ struct MixWgP {
   int kp, keff, R, S;
 };
 
-__device__ __forceinline__ int mixw_stage_off(int k, int c8) {      // = stage_off of fused_spectral.hip
-  return k * 128 + ((c8 ^ ((((k >> 1) & 1) << 2) | (((k >> 3) & 1) << 3))) << 3);
-}
-
 __global__ __launch_bounds__(256, 2) void k_mix_wgrad_h2(const MixWgP P) {
   __shared__ __attribute__((aligned(16))) char smem[4 * 8192];      // pieces spec re, spec im, g re, g im: [hi 4 KB | lo 4 KB]
   __shared__ float red[2][4];
@@ -329,7 +320,7 @@ __global__ __launch_bounds__(256, 2) void k_mix_wgrad_h2(const MixWgP P) {
     for (int i = 0; i < 4; ++i) {
       uint2 hi, lo;
       h2_split4(r[i].x * sc, r[i].y * sc, r[i].z * sc, r[i].w * sc, hi, lo);
-      const int off = mixw_stage_off(sl, c80 + i);
+      const int off = stage_off(sl, c80 + i);
       *reinterpret_cast<uint2*>(base + off) = hi;
       *reinterpret_cast<uint2*>(base + 4096 + off) = lo;
     }
@@ -354,7 +345,7 @@ __global__ __launch_bounds__(256, 2) void k_mix_wgrad_h2(const MixWgP P) {
     put(rs, part, sc_s);              // pieces 0 / 1: spectra re / im
     put(rg, 2 + part, sc_g);          // pieces 2 / 3: gradient spectra re / im
     if (t + 1 < t1) issue(t + 1);
-    lds_barrier_mix();
+    lds_barrier();
     // A operands: this wave's 16 channels i of the saved spectra
     const f16x8 reh = frag(0, 0, w), rel = frag(0, 1, w), imh = frag(1, 0, w), iml = frag(1, 1, w);
     f16x8 nih, nil;
@@ -373,7 +364,7 @@ __global__ __launch_bounds__(256, 2) void k_mix_wgrad_h2(const MixWgP P) {
       ci[ot] = h2_mfma32(reh, rel, gih, gil, ci[ot]);
       ci[ot] = h2_mfma32(nih, nil, grh, grl, ci[ot]);
     }
-    lds_barrier_mix();
+    lds_barrier();
   }
   // rows i = 16 w + 4 g + jj, column o = 16 ot + li: (gWr, gWi) pairs
   const float inv = iv_s * iv_g;
@@ -439,9 +430,8 @@ int mix_h2(const float* spec_y, const float* spec_x, const float* amax_y, const 
   P.spec[0] = spec_y; P.spec[1] = spec_x; P.img[0] = (char*)img_y; P.img[1] = (char*)img_x;
   P.amax[0] = amax_y; P.amax[1] = amax_x; P.inv[0] = inv_y; P.inv[1] = inv_x;
   P.wimg = (const char*)wimg; P.wc = wc; P.kp = kp; P.R = 2 * kp; P.nq = kp / 4;
-  int dev = 0, cus = 256;
-  RPDE_HIP(hipGetDevice(&dev));
-  RPDE_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  int cus;
+  RPDE_HIP(cu_count(&cus));
   // two workgroups per CU in one round: slices per (axis, quad) so that 2 * nq * slices ~ 2 * CUs
   const long lines[2] = {lines_y, lines_x};
   int nblk[2];

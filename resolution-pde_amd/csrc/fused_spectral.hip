@@ -17,8 +17,6 @@
 #include "cw.h"
 #include "h2.h"
 
-#include <stdlib.h>
-
 namespace rpde {
 
 // RPDE_STAMPS (debug build, rpde/build.py --stamps): lane 0 of waves from the middle of a launch records s_memtime at
@@ -48,12 +46,11 @@ __global__ __launch_bounds__(64) void k_h2_table_ana(const float* __restrict__ s
     const int y = 32 * s + (perm ? 4 * j + g : 8 * g + j);
     v[j] = (r < R && y < n) ? src[r * rs + y * cs] * (float)(1 << H2_TABLE_EXP) : 0.f;
   }
-  uint2 h0, l0, h1, l1;
-  h2_split4(v[0], v[1], v[2], v[3], h0, l0);
-  h2_split4(v[4], v[5], v[6], v[7], h1, l1);
+  uint4 hi, lo;
+  h2_split8(v, hi, lo);
   char* p = out + (long)f * 2048 + l * 16;
-  *reinterpret_cast<uint4*>(p) = make_uint4(h0.x, h0.y, h1.x, h1.y);
-  *reinterpret_cast<uint4*>(p + 1024) = make_uint4(l0.x, l0.y, l1.x, l1.y);
+  *reinterpret_cast<uint4*>(p) = hi;
+  *reinterpret_cast<uint4*>(p + 1024) = lo;
 }
 
 // ---- operand blocks of the synthesis MFMAs ----
@@ -70,10 +67,8 @@ __global__ __launch_bounds__(64) void k_h2_table_ana(const float* __restrict__ s
 
 // 8 values of group q (rows 32 K32 + 8 q ..) -> the 16-byte pieces of the three slots they occupy
 __device__ __forceinline__ void h2_store_tail(char* __restrict__ blk, int K32, int TG, int q, int c, bool table, const float (&v)[8]) {
-  uint2 h0, l0, h1, l1;
-  h2_split4(v[0], v[1], v[2], v[3], h0, l0);
-  h2_split4(v[4], v[5], v[6], v[7], h1, l1);
-  const uint4 hi = make_uint4(h0.x, h0.y, h1.x, h1.y), lo = make_uint4(l0.x, l0.y, l1.x, l1.y);
+  uint4 hi, lo;
+  h2_split8(v, hi, lo);
 #pragma unroll
   for (int t = 0; t < 3; ++t) {
     const int slot = t * TG + q;
@@ -99,7 +94,7 @@ __global__ __launch_bounds__(64) void k_h2_table_syn(const float* __restrict__ s
       v[j] = (y < n && r < R) ? src[y * rs + r * cs] * (float)(1 << H2_TABLE_EXP) : 0.f;
     }
     if (s < K32) {
-      uint2 h0, l0, h1, l1;
+      uint2 h0, l0, h1, l1;      // (h2_split8 written out: through the helper this loop gets another register assignment)
       h2_split4(v[0], v[1], v[2], v[3], h0, l0);
       h2_split4(v[4], v[5], v[6], v[7], h1, l1);
       *reinterpret_cast<uint4*>(blk + s * 1024 + l * 16) = make_uint4(h0.x, h0.y, h1.x, h1.y);
@@ -154,13 +149,6 @@ struct AnaP {
   int naxes, B, chunk, R;
   int items;          // rounds in the launch, ordered chunk of samples by chunk: all y rounds, then all x rounds
 };
-
-// byte offset of the 8-byte chunk c8 (channels 4 c8 .. 4 c8 + 3) of point-row k inside one staged piece
-// ([32 points][64 channels] f16, 128-byte rows): chunks are XOR-swizzled so that the transposing reads, which
-// fetch rows 8g+q / 8g+4+q per 16-lane group, spread over all 64 banks
-__device__ __forceinline__ int stage_off(int k, int c8) {
-  return k * 128 + ((c8 ^ ((((k >> 1) & 1) << 2) | (((k >> 3) & 1) << 3))) << 3);
-}
 
 template <int MT>
 __global__ __launch_bounds__(64 * ANA_WAVES, 2) void k_dft_analysis_h2(const AnaP P) {
@@ -406,11 +394,6 @@ __global__ __launch_bounds__(64 * ANA_WAVES, 2) void k_dft_analysis_rr_h2(const 
     __syncthreads();
   }
   const long rowf = (long)n * 64;                    // floats per row of the field
-  auto gload = [](const float* p) {
-    f32x4v v;
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v) : "v"(p) : "memory");
-    return v;
-  };
   // Which chunk a wave takes first.  Tile (a, a + t) is read by band a as a ROW chunk and by band a + t as a COLUMN chunk;
   // the second read finds the tile in L2 more surely when both are requested in the same half of the round than half a
   // round apart (with "column first" everywhere 58 % of the second reads missed: 847 MB fetched for a 537 MB field).
@@ -436,7 +419,7 @@ __global__ __launch_bounds__(64 * ANA_WAVES, 2) void k_dft_analysis_rr_h2(const 
     const float* q0; long st;
     chunk_of(u, half, q0, st);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) buf[i] = gload(q0 + i * st);
+    for (int i = 0; i < 8; ++i) buf[i] = global_load_b128(q0 + i * st);
   };
   // the chunk in buf has landed once at most 8 later vector-memory instructions are outstanding: the other axis's chunk
   // (tests/test_isa_pending_loads_cpu.py follows the `landed` comment, which names the registers)
@@ -586,11 +569,10 @@ __global__ __launch_bounds__(256) void k_spec_split_h2(const float* __restrict__
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[s][j] *= scale;
     if (s < K32) {
-      uint2 h0, l0, h1, l1;
-      h2_split4(v[s][0], v[s][1], v[s][2], v[s][3], h0, l0);
-      h2_split4(v[s][4], v[s][5], v[s][6], v[s][7], h1, l1);
-      *reinterpret_cast<uint4*>(blk + s * 1024 + l * 16) = make_uint4(h0.x, h0.y, h1.x, h1.y);
-      *reinterpret_cast<uint4*>(blk + (K32 + s) * 1024 + l * 16) = make_uint4(l0.x, l0.y, l1.x, l1.y);
+      uint4 hi, lo;
+      h2_split8(v[s], hi, lo);
+      *reinterpret_cast<uint4*>(blk + s * 1024 + l * 16) = hi;
+      *reinterpret_cast<uint4*>(blk + (K32 + s) * 1024 + l * 16) = lo;
     } else if (g < TG) {
       h2_store_tail(blk, K32, TG, g, li, false, v[s]);
     }
@@ -786,44 +768,6 @@ __global__ __launch_bounds__(256, 2) void k_dft_synthesis2_h2(const SynP P) {
 //   * every line carries its own power-of-two scale (undone on the accumulators, as before).
 constexpr int SYN3_WAVES = 8;
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit counter");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// a and b hold one value per lane; afterwards a's upper half (lane-rows 2, 3) and b's lower half (rows 0, 1) have changed
-// places / a's odd lane-rows and b's even lane-rows have changed places
-__device__ __forceinline__ void swap_halves(float& a, float& b) {
-  typedef unsigned u2v __attribute__((ext_vector_type(2)));
-  const u2v r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  a = __uint_as_float(r.x); b = __uint_as_float(r.y);
-}
-__device__ __forceinline__ void swap_rows(float& a, float& b) {
-  typedef unsigned u2v __attribute__((ext_vector_type(2)));
-  const u2v r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  a = __uint_as_float(r.x); b = __uint_as_float(r.y);
-}
-
-// 4 x 4 transpose inside every quad of lanes: afterwards register c of lane p (p = lane & 3) holds what register p of
-// lane c held.  Two butterfly stages on DPP quad permutes (lane ^ 1, then lane ^ 2).
-template <int CTRL>
-__device__ __forceinline__ float quad_dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ void quad_transpose(float& v0, float& v1, float& v2, float& v3) {
-  const bool b0 = threadIdx.x & 1, b1 = threadIdx.x & 2;
-  { const float a = quad_dpp<0xB1>(v0), c = quad_dpp<0xB1>(v1); v1 = b0 ? v1 : a; v0 = b0 ? c : v0; }   // quad_perm [1,0,3,2]
-  { const float a = quad_dpp<0xB1>(v2), c = quad_dpp<0xB1>(v3); v3 = b0 ? v3 : a; v2 = b0 ? c : v2; }
-  { const float a = quad_dpp<0x4E>(v0), c = quad_dpp<0x4E>(v2); v2 = b1 ? v2 : a; v0 = b1 ? c : v0; }   // quad_perm [2,3,0,1]
-  { const float a = quad_dpp<0x4E>(v1), c = quad_dpp<0x4E>(v3); v3 = b1 ? v3 : a; v1 = b1 ? c : v1; }
-}
-
-// makes the compiler produce x here, in program order relative to the other volatile asm statements (barriers, waits):
-// without it the VALU work between the two phases (scaling, turn, the y phase's multiply-adds) is sunk to the end of
-// the kernel and both phases' 128 accumulators are alive at once (80 spilled registers)
-__device__ __forceinline__ void pin(float& x) { asm volatile("" : "+v"(x)); }
-
 // one tile of one channel block of one sample
 struct Syn3Item {
   const char* gx; const char* gy;       // fragment pieces of the tile's first column / first row (this channel block)
@@ -986,7 +930,7 @@ __global__ __launch_bounds__(64 * SYN3_WAVES, 2) void k_dft_synthesis3_h2(const 
       else if (s <= 5) cw_wait_t<2 * NF>(T);
       else cw_wait_t<2 * NF>(T);
       FSTAMP(1, 1 + 3 * s);
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // everyone's have; everyone is done with stage s - 1
+      lds_barrier();                                               // everyone's have; everyone is done with stage s - 1
       FSTAMP(1, 2 + 3 * s);
       const int slot_s = (ring + s) % 3, slot_n = (ring + s + 2) % 3;
       // what this stage requests (spread between its MFMA chains): stage s + 2 of this tile, or stage s - 6 of the next
@@ -1274,7 +1218,7 @@ __global__ __launch_bounds__(64 * SYN3_WAVES, 2) void k_dft_synthesis4_h2(const 
       else if (s <= 4) cw_wait<T, 2 * NF>();
       else if (s == 5) cw_wait<T, 2 * NF + 4>();
       else cw_wait<T, 2 * NF + 8>();
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // everyone's have; everyone is done with stage s - 1
+      lds_barrier();                                               // everyone's have; everyone is done with stage s - 1
       const int slot_s = s % 3, slot_n = (s + 2) % 3;
       auto request = [&](int i) {
         if (i >= 2 * NF) return;
@@ -1370,8 +1314,8 @@ __global__ __launch_bounds__(64 * SYN3_WAVES, 2) void k_dft_synthesis4_h2(const 
 // host side
 // ------------------------------------------------------------------------------------------------------------
 bool fused2d_ok(int M, int N, int C, int keff_y, int keff_x) {
-  const int Ry = 2 * ((keff_y + 3) / 4 * 4), Rx = 2 * ((keff_x + 3) / 4 * 4);
-  if (const char* e = getenv("RPDE_FUSED_SPECTRAL")) if (e[0] == '0') return false;
+  const int Ry = 2 * r4(keff_y), Rx = 2 * r4(keff_x);
+  if (switch_off("RPDE_FUSED_SPECTRAL")) return false;
   // keff_y == keff_x, not only equal padded counts: the h2 mode mix (k_mix_prep, k_mix_wgrad_fold) zeroes the weights and
   // gradients of modes >= keff with ONE keff for both axes, while the reference clamps each axis by its own length
   // (spectral_convolution.py:269-300) -- e.g. a [64, 32] grid with 20 modes keeps 17 along y and 20 along x
@@ -1398,17 +1342,15 @@ size_t fused2d_img_bytes(long lines, int R) { return (size_t)lines * 4 * h2_bloc
 // square grid (its round-3 predecessor, with a workgroup's rows matched to the grid, was level with the two-read kernel
 // at 64^2 and 128^2 for B = 32 and ahead at B = 8: 2.03 vs 2.25 ms per training step at 64^2).
 static bool ana_sq_ok(int M, int N, int cus) {
-  const char* e = getenv("RPDE_ANA_SQ");
-  if (e && e[0] == '0') return false;
+  if (switch_off("RPDE_ANA_SQ")) return false;
   return M == N && cus >= 256;
 }
 
 int fused2d_analysis(const float* x, float* spec_y, float* spec_x, float* amax_y, float* amax_x, const rpde_plan* py,
                      const rpde_plan* px, int adjoint, int B, int M, int N, hipStream_t st) {
   {
-    int dev = 0, cus = 256;
-    RPDE_HIP(hipGetDevice(&dev));
-    RPDE_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    int cus;
+    RPDE_HIP(cu_count(&cus));
     if (ana_sq_ok(M, N, cus) && py->h2_ana[adjoint] == px->h2_ana[adjoint]) {
       // the round-robin schedule: a group = N waves = N / 8 workgroups; as many groups as fit (never more than samples)
       AnaRrP Q;
@@ -1443,9 +1385,8 @@ int fused2d_analysis(const float* x, float* spec_y, float* spec_x, float* amax_y
   ax.rps = (N + ANA_WAVES - 1) / ANA_WAVES; ax.zdiv = N; ax.s1 = (long)M * N * 64; ax.s2 = 64; ax.ldk = (long)N * 64;
   P.items = ((B + P.chunk - 1) / P.chunk) * P.chunk * (ay.rps + ax.rps);
   // one persistent workgroup per CU (the table + 8 staging areas take 80-112 KB of LDS)
-  int dev = 0, cus = 256;
-  RPDE_HIP(hipGetDevice(&dev));
-  RPDE_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  int cus;
+  RPDE_HIP(cu_count(&cus));
   const int grid = P.items < cus ? P.items : cus;
   const int MT = (P.R + 15) / 16;
   if (MT == 1) hipLaunchKernelGGL(k_dft_analysis_h2<1>, dim3(grid), dim3(64 * ANA_WAVES), 0, st, P);
@@ -1464,7 +1405,7 @@ int fused2d_split(const float* spec, void* img, float* inv, long lines, int R, h
 
 // RPDE_SYN3=0: keep the 16 x 16 tile kernel for every shape (A/B, tests)
 static bool syn3_ok(int M, int N) {
-  if (const char* e = getenv("RPDE_SYN3")) if (e[0] == '0') return false;
+  if (switch_off("RPDE_SYN3")) return false;
   return M % 64 == 0 && N % 64 == 0;
 }
 
@@ -1477,9 +1418,8 @@ int fused2d_synthesis(const void* imgy, const void* imgx, const float* invy, con
   const int R3 = 2 * py->kp;
   const int NF3 = 2 * (R3 / 32) + (3 * ((R3 % 32) / 8) + 3) / 4;
   if (syn3_ok(M, N) && NF3 <= 3) {
-    int dev = 0, cus = 256;
-    RPDE_HIP(hipGetDevice(&dev));
-    RPDE_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    int cus;
+    RPDE_HIP(cu_count(&cus));
     if (!skip) {
       // 64 x 32 x 32-channel tiles, whole 128-byte lines per store: (M / 64) (N / 32) 2 items per sample
       const int ng = B < 8 ? B : 8;

@@ -3,11 +3,7 @@
 // layout in gemm_{nt,nn,tn,tt}.hip.
 #include "gemm_kernel.h"
 
-#include <stdlib.h>
-
 namespace rpde {
-
-static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 int launch_gemm(const rpde_gemm_desc& d, hipStream_t st) {
   RPDE_CHECK_ARG(d.A && d.B && d.C, "gemm: null operand");
@@ -51,7 +47,7 @@ int launch_gemm(const rpde_gemm_desc& d, hipStream_t st) {
     // small problems (the 1-D configurations), fewer than 384 tiles of 128x128: those would leave most of the 256 CUs
     // idle, or give each just one four-wave workgroup (FFNO1D at B = 16: 256 tiles; 64x64 tiles: 1.50 -> 1.44 ms per
     // step under a HIP graph)
-    static const bool small_tiles = [] { const char* e = getenv("RPDE_SMALL_TILES"); return !(e && e[0] == '0'); }();
+    static const bool small_tiles = !switch_off("RPDE_SMALL_TILES");
     if (small_tiles && BMc == 128 && BNc == 128 && !d.colsum &&
         (long)((d.M + 127) / 128) * ((d.N + 127) / 128) * d.batch * d.ksplit < 384) { BMc = 64; BNc = 64; }
   }

@@ -10,12 +10,12 @@
 // with half the matrix instructions of the three-piece bf16 split (gemm_bf16x3.hip), which stays the generic path.
 #pragma once
 #include "rpde_internal.h"
+#include "wave.h"
 
 namespace rpde {
 
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 typedef short s16x4v __attribute__((ext_vector_type(4)));
 
 constexpr int H2_TABLE_EXP = 12;     // DFT tables (|entry| <= 2/sqrt(n) <= 1) are stored times 2^12
@@ -40,51 +40,28 @@ __device__ __forceinline__ void h2_split4(float a, float b, float c, float d, ui
   hi = h.u; lo = l.u;
 }
 
-// maximum over the wave of non-negative values, returned in every lane.  Six DPP steps on the VALU (row shifts, then
-// the two row broadcasts) and one v_readlane -- __shfl_xor would make six dependent round trips through the LDS crossbar
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_max_step(float v) {
-  const int t = __builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, ROW_MASK, 0xf, false);
-  return fmaxf(v, __int_as_float(t));
+// eight scaled floats of a lane (the eight reduction slots it supplies to a 32-deep MFMA) -> the 16-byte hi and lo
+// pieces of one fragment
+__device__ __forceinline__ void h2_split8(const float (&v)[8], uint4& hi, uint4& lo) {
+  uint2 h0, l0, h1, l1;
+  h2_split4(v[0], v[1], v[2], v[3], h0, l0);
+  h2_split4(v[4], v[5], v[6], v[7], h1, l1);
+  hi = make_uint4(h0.x, h0.y, h1.x, h1.y);
+  lo = make_uint4(l0.x, l0.y, l1.x, l1.y);
 }
-__device__ __forceinline__ float wave_max(float v) {
-  v = dpp_max_step<0x111, 0xf>(v);     // row_shr:1
-  v = dpp_max_step<0x112, 0xf>(v);     // row_shr:2
-  v = dpp_max_step<0x114, 0xf>(v);     // row_shr:4
-  v = dpp_max_step<0x118, 0xf>(v);     // row_shr:8   -> lane 15 of each row of 16 holds the row maximum
-  v = dpp_max_step<0x142, 0xa>(v);     // row_bcast:15 into rows 1 and 3
-  v = dpp_max_step<0x143, 0xc>(v);     // row_bcast:31 into rows 2 and 3 -> lane 63 holds the wave maximum
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+// ... stored as one fragment in memory or LDS: lane l's hi piece at dst (= fragment base + 16 l), its lo piece 1 KB on
+__device__ __forceinline__ void h2_put_frag(char* dst, const float (&v)[8]) {
+  uint4 hi, lo;
+  h2_split8(v, hi, lo);
+  *reinterpret_cast<uint4*>(dst) = hi;
+  *reinterpret_cast<uint4*>(dst + 1024) = lo;
 }
-
-// sum over the wave, returned in every lane: the same six DPP steps with additions (out-of-row sources read as zero)
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_add_step(float v) {
-  return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, true));
-}
-__device__ __forceinline__ float wave_sum_dpp(float v) {
-  v = dpp_add_step<0x111, 0xf>(v);
-  v = dpp_add_step<0x112, 0xf>(v);
-  v = dpp_add_step<0x114, 0xf>(v);
-  v = dpp_add_step<0x118, 0xf>(v);     // lane 15 of each row: the row's sum
-  v = dpp_add_step<0x142, 0xa>(v);     // row_bcast:15 into rows 1 and 3: lane 31 = rows 0+1, lane 63 = rows 2+3 (so far)
-  v = dpp_add_step<0x143, 0xc>(v);     // row_bcast:31 into rows 2 and 3: lane 63 = everything
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-
-// the value held by lane l ^ 16 / l ^ 32, by gfx950's v_permlane16_swap / v_permlane32_swap (vector ALU: no trip through
-// the LDS crossbar as __shfl_xor takes).  swap(v, v) returns {v with its odd rows (upper half) replaced by the even rows
-// (lower half), v with its even rows (lower half) replaced by the odd rows (upper half)}: each lane picks the copy in
-// which its own position was overwritten by its partner.
-__device__ __forceinline__ float lane_xor16(float v) {
-  typedef unsigned u2v __attribute__((ext_vector_type(2)));
-  const u2v r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float((threadIdx.x & 16) ? r.x : r.y);
-}
-__device__ __forceinline__ float lane_xor32(float v) {
-  typedef unsigned u2v __attribute__((ext_vector_type(2)));
-  const u2v r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float((threadIdx.x & 32) ? r.x : r.y);
+// ... as a pair of MFMA operands in registers
+__device__ __forceinline__ void h2_frag(const float (&v)[8], f16x8& hi, f16x8& lo) {
+  union { f16x8 v; struct { uint2 a, b; } u; } H, L;
+  h2_split4(v[0], v[1], v[2], v[3], H.u.a, L.u.a);
+  h2_split4(v[4], v[5], v[6], v[7], H.u.b, L.u.b);
+  hi = H.v; lo = L.v;
 }
 
 // three-term product of split operands, small terms first
@@ -101,12 +78,5 @@ __device__ __forceinline__ f32x4v h2_mfma32(f16x8 ah, f16x8 al, f16x8 bh, f16x8 
 //  shorter instruction reads its SrcC before the longer one has written all of it, and neither the hardware nor the
 //  compiler's hazard recognizer waits for this opcode pair.  Same-shape chains are handled.  Short reduction tails are
 //  therefore packed into 32-deep fragments -- fused_spectral.hip, h2_store_tail -- which also costs no padding.)
-
-// LDS accesses of one wave to its private staging area: the hardware executes a wave's DS instructions in order;
-// this only keeps the compiler from reordering a lane's read above another lane's write
-__device__ __forceinline__ void wave_lds_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
 
 }  // namespace rpde

@@ -17,8 +17,6 @@
 #include "rpde_internal.h"
 #include "mix1d.h"
 
-#include <stdlib.h>
-
 namespace rpde {
 
 constexpr int MX_R = 16, MX_K = 8, MX_Q = 8, MX_WAVES = 8;
@@ -170,7 +168,7 @@ __global__ __launch_bounds__(64 * MX_WAVES) void k_mix1d_wgrad(const Mix1dP P) {
 }
 
 bool mix1d_ok(int rows, int C) {
-  static const int on = [] { const char* e = getenv("RPDE_MIX1D"); return (e && e[0] == '0') ? 0 : 1; }();
+  static const bool on = !switch_off("RPDE_MIX1D");
   return on && rows >= 1 && rows <= 64 && (C == 32 || C == 64 || C == 128);
 }
 

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include <math.h>
 #include <string>
@@ -43,6 +44,26 @@ void set_error(const char* fmt, ...);
   } while (0)
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
+// ---- host helpers ----------------------------------------------------------
+// 16-byte aligned: what the 16-byte loads and stores of the vectorised kernels need
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// v rounded up to a multiple of 4 (mode counts and leading dimensions are padded to whole float4s)
+inline int r4(int v) { return (v + 3) / 4 * 4; }
+// compute units of the current device, for the grids of the persistent kernels; 256 (an MI355X) is left in *cus when
+// the query fails, for the callers that go on regardless
+inline hipError_t cu_count(int* cus) {
+  int dev = 0;
+  *cus = 256;
+  const hipError_t e = hipGetDevice(&dev);
+  return e != hipSuccess ? e : hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev);
+}
+// whether the environment switch `name` (RPDE_X, default on) is set to 0.  Reads the environment at every call:
+// tests and A/B runs flip switches inside one process
+inline bool switch_off(const char* name) {
+  const char* e = getenv(name);
+  return e && e[0] == '0';
+}
 
 // ---- device math -----------------------------------------------------------
 // Phi(x) and the normal density phi(x) from ONE exponential and one reciprocal (Abramowitz & Stegun 26.2.17, the

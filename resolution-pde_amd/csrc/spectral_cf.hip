@@ -454,7 +454,7 @@ __global__ __launch_bounds__(256) void k_lift_const_spectra(const float* __restr
 
 // kp in {4, 8, 12, 16}, the staged block within 64 KB, 16-byte aligned workspaces; RPDE_COL_FUSED=0: the three GEMM-shaped steps
 static bool col_stage_ok(int M, int m1, int kp, const float* s1, const float* t1) {
-  if (const char* e = getenv("RPDE_COL_FUSED")) if (e[0] == '0') return false;
+  if (switch_off("RPDE_COL_FUSED")) return false;
   return kp >= 4 && kp <= 16 && kp % 4 == 0 && (size_t)2 * M * kp * 4 <= 65536 && m1 >= 1 &&
          ((reinterpret_cast<uintptr_t>(s1) | reinterpret_cast<uintptr_t>(t1)) & 15) == 0;
 }
@@ -502,7 +502,7 @@ extern "C" {
 
 // --------------------------------- 1-D --------------------------------------
 size_t rpde_spectral1d_ws_bytes(int B, int Cin, int Cout, int n, int K) {
-  const int kp = (K + 3) / 4 * 4;
+  const int kp = r4(K);
   const int cm = Cin > Cout ? Cin : Cout;
   const size_t a = thin_slab_floats((long)B * Cin, 2 * kp, n), b = thin_slab_floats((long)B * Cout, 2 * kp, n);
   return 2 * arena_bytes((size_t)B * cm * 2 * kp) + arena_bytes(a > b ? a : b);
@@ -554,7 +554,6 @@ int rpde_spectral1d_bwd(const float* grad_out, const float* spec_in, const float
 }
 
 // --------------------------------- 2-D --------------------------------------
-static inline int r4(int v) { return (v + 3) / 4 * 4; }
 
 size_t rpde_spectral2d_spec_elems(int B, int Cin, int M, int N, int m1, int m2) {
   (void)M; (void)N;
@@ -609,7 +608,7 @@ size_t rpde_fnoblock2d_eval_ws_bytes(int B, int Cin, int Cout, int M, int N, int
 
 int rpde_fnoblock2d_eval_ok(int Cin, int Cout, int M, int N, int m2) {
   // (pointer alignment is checked at the call; torch allocations are 256-byte aligned)
-  return conv1x1_syn_ok(nullptr, nullptr, Cin, Cout, M, N, 2 * ((m2 + 3) / 4 * 4)) ? 1 : 0;
+  return conv1x1_syn_ok(nullptr, nullptr, Cin, Cout, M, N, 2 * r4(m2)) ? 1 : 0;
 }
 
 int rpde_fnoblock2d_eval_fwd(const float* x, const float* w1, const float* w2, const float* wc, const float* bc, float* out, int B,
@@ -621,7 +620,7 @@ int rpde_fnoblock2d_eval_fwd(const float* x, const float* w1, const float* w2, c
     set_error("SpectralConv2d: modes (%d,%d) exceed the spectrum (%d,%d)", m1, m2, M, N / 2 + 1);
     return RPDE_ERR_MODES;
   }
-  RPDE_CHECK_ARG(conv1x1_syn_ok(x, out, Cin, Cout, M, N, 2 * ((m2 + 3) / 4 * 4)), "fnoblock2d_eval_fwd: shape not covered (%d -> %d on %d x %d)", Cin, Cout, M, N);
+  RPDE_CHECK_ARG(conv1x1_syn_ok(x, out, Cin, Cout, M, N, 2 * r4(m2)), "fnoblock2d_eval_fwd: shape not covered (%d -> %d on %d x %d)", Cin, Cout, M, N);
   hipStream_t st = as_stream(stream);
   const rpde_plan *pn, *pm;
   RPDE_TRY(get_plan(&pn, N, m2, RPDE_NORM_BACKWARD, 1, PLAN_REAL, st));
@@ -653,7 +652,7 @@ int rpde_fnoblock2d_eval_fwd(const float* x, const float* w1, const float* w2, c
 // transform, the bypass convolution, the activation and both projection layers are ONE pass over x (conv_proj_h2.hip):
 // the block's output is never written.
 int rpde_fnoblock2d_proj_eval_ok(int Cin, int Cout, int M, int N, int m1, int m2, int Cmid, int Cq) {
-  const int kp = (m2 + 3) / 4 * 4;
+  const int kp = r4(m2);
   return m2 <= N / 2 + 1 && m1 <= M && conv_syn_proj_ok(Cin, Cout, M, N, 2 * kp, Cmid, Cq) ? 1 : 0;
 }
 
@@ -691,14 +690,14 @@ int rpde_fnoblock2d_proj_eval_fwd(const float* x, const float* w1, const float* 
 // ---- evaluation-mode FNO2d: lifting + first block without the lifted field (reference models/fno.py:121-147:
 // cat(x, gridx, gridy) -> lifting -> fno_blocks[0]); u [B,1,M,N], gx [M], gy [N], wl [C,3], bl [C] ----
 size_t rpde_fno2d_lift_block_eval_ws_bytes(int B, int C, int Cout, int M, int N, int m1, int m2) {
-  const size_t kp = (size_t)((m2 + 3) / 4 * 4), R = 2 * (size_t)m1;
+  const size_t kp = (size_t)r4(m2), R = 2 * (size_t)m1;
   return arena_bytes((size_t)B * M * 2 * kp) + arena_bytes(4 * kp) +
          arena_bytes((size_t)B * C * 2 * R * kp) + arena_bytes((size_t)B * Cout * M * 2 * kp) + 4096;
 }
 
 int rpde_fno2d_lift_block_eval_ok(int Cu, int C, int Cout, int M, int N, int m1, int m2) {
-  if (const char* e = getenv("RPDE_LIFT_FUSED")) if (e[0] == '0') return 0;
-  const int kp = (m2 + 3) / 4 * 4;
+  if (switch_off("RPDE_LIFT_FUSED")) return 0;
+  const int kp = r4(m2);
   return Cu == 1 && M <= 1024 && m2 <= N / 2 + 1 && m1 <= M && conv_syn_h2_ok(nullptr, nullptr, nullptr, C, Cout, M, N, 2 * kp) &&
          col_stage_ok(M, m1, kp, nullptr, nullptr) ? 1 : 0;
 }

@@ -13,8 +13,7 @@
 #include "rpde_internal.h"
 #include "pointwise.h"
 #include "thin_linear.h"
-
-#include <stdlib.h>
+#include "wave.h"
 
 namespace rpde {
 
@@ -47,15 +46,6 @@ __global__ __launch_bounds__(TL_THREADS) void k_thin_expand(const float* __restr
     }
     *reinterpret_cast<float4*>(y + p * O + 4 * og) = make_float4(o[0], o[1], o[2], o[3]);
   }
-}
-
-// sum over the 16 lanes of a DPP row, valid in lane 15 of the row
-__device__ __forceinline__ float tl_row_sum15(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x111, 0xf, 0xf, true));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x112, 0xf, 0xf, true));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x114, 0xf, 0xf, true));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x118, 0xf, 0xf, true));
-  return v;
 }
 
 // 16 lanes per point, lane j owns features 4j + 64q (q < NQ = ceil(O / 64)); four points per wave instruction
@@ -95,7 +85,7 @@ __global__ __launch_bounds__(TL_THREADS) void k_thin_contract(const float* __res
         s[t] += (v.x * wr[t][q][0] + v.y * wr[t][q][1]) + (v.z * wr[t][q][2] + v.w * wr[t][q][3]);
     }
 #pragma unroll
-    for (int t = 0; t < T; ++t) s[t] = tl_row_sum15(s[t]);
+    for (int t = 0; t < T; ++t) s[t] = row_sum15(s[t]);
     if (live && li == 15) {
 #pragma unroll
       for (int t = 0; t < T; ++t) y[p * T + t] = s[t] + br[t];
@@ -179,8 +169,7 @@ __global__ __launch_bounds__(TL_THREADS) void k_thin_outer(const float* __restri
 }
 
 bool thin_linear_ok(int thin, int wide) {
-  const char* e = getenv("RPDE_THIN_LINEAR");
-  if (e && e[0] == '0') return false;
+  if (switch_off("RPDE_THIN_LINEAR")) return false;
   return thin >= 1 && thin <= 4 && wide >= 4 && wide <= 256 && wide % 4 == 0 && TL_THREADS % (wide / 4) == 0;
 }
 

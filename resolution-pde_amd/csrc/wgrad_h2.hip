@@ -28,22 +28,11 @@
 #include "pointwise.h"
 #include "wgrad_h2.h"
 
-#include <stdlib.h>
-
 namespace rpde {
 
 constexpr int WG_WAVES = 8;
 constexpr int WG_PANEL = 8192;                 // bytes per panel stage: [hi | lo][32 points][64 channels] f16
 constexpr int WG_BLOCKS = 256;                 // one workgroup per CU
-
-// byte offset of 8-byte chunk c8 (channels 4 c8 .. 4 c8 + 3) of point-row k in one piece of a panel (128-byte rows);
-// XOR swizzle so that the transposing reads (rows 8g+q and 8g+4+q per 16-lane group) cover all banks
-__device__ __forceinline__ int wg_off(int k, int c8) {
-  return k * 128 + ((c8 ^ ((((k >> 1) & 1) << 2) | (((k >> 3) & 1) << 3))) << 3);
-}
-
-// LDS traffic done + workgroup barrier, without waiting for outstanding global loads (as __syncthreads() would)
-__device__ __forceinline__ void wg_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 struct WgP {
   const float* a;      // gy  [P, M]
@@ -56,20 +45,6 @@ struct WgP {
   float* gx;           // DG only: gx[P, N] = gy[P, M] . w
   int early;           // bit w: wave w converts the next step's panel BEFORE this step's products
 };
-
-// 4 x 4 transpose inside every quad of lanes: afterwards register c of lane p (p = lane & 3) holds what register p of
-// lane c held (two butterfly stages on DPP quad permutes; the synthesis kernel's output uses the same)
-template <int CTRL>
-__device__ __forceinline__ float wg_quad_dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ void wg_quad_transpose(float& v0, float& v1, float& v2, float& v3) {
-  const bool b0 = threadIdx.x & 1, b1 = threadIdx.x & 2;
-  { const float a = wg_quad_dpp<0xB1>(v0), c = wg_quad_dpp<0xB1>(v1); v1 = b0 ? v1 : a; v0 = b0 ? c : v0; }   // quad_perm [1,0,3,2]
-  { const float a = wg_quad_dpp<0xB1>(v2), c = wg_quad_dpp<0xB1>(v3); v3 = b0 ? v3 : a; v2 = b0 ? c : v2; }
-  { const float a = wg_quad_dpp<0x4E>(v0), c = wg_quad_dpp<0x4E>(v2); v2 = b1 ? v2 : a; v0 = b1 ? c : v0; }   // quad_perm [2,3,0,1]
-  { const float a = wg_quad_dpp<0x4E>(v1), c = wg_quad_dpp<0x4E>(v3); v3 = b1 ? v3 : a; v1 = b1 ? c : v1; }
-}
 
 // PA / PB: 64-channel panels of the A block / of B; waves WM x WN, each TM x TN tiles of 16 x 16; ACT: B = gelu(b).
 // DG: the layer's data gradient rides along -- gx[p, :] = gy[p, :] . W for the 32 points of every step, from the gy
@@ -128,7 +103,7 @@ __global__ __launch_bounds__(64 * WG_WAVES, 2) void k_wgrad_h2(const WgP P) {
     for (int i = 0; i < 8; ++i) {
       uint2 hi, lo;
       h2_split4(buf[i].x * scale, buf[i].y * scale, buf[i].z * scale, buf[i].w * scale, hi, lo);
-      const int off = wg_off(4 * i + g, li);
+      const int off = stage_off(4 * i + g, li);
       *reinterpret_cast<uint2*>(dst + off) = hi;
       *reinterpret_cast<uint2*>(dst + 4096 + off) = lo;
     }
@@ -207,7 +182,7 @@ __global__ __launch_bounds__(64 * WG_WAVES, 2) void k_wgrad_h2(const WgP P) {
     issue(s0);
     convert(0);
     issue(s0 + 1);
-    wg_barrier();                            // the stage (and the weight fragments) are written; global loads stay in flight
+    lds_barrier();                            // the stage (and the weight fragments) are written; global loads stay in flight
     for (long s = s0; s < s1; ++s) {
       const int cur = (int)(s - s0) & 1;
       const char* const stage = smem + cur * STAGE;
@@ -254,7 +229,7 @@ __global__ __launch_bounds__(64 * WG_WAVES, 2) void k_wgrad_h2(const WgP P) {
           f32x4v part = (f32x4v){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
           for (int h = 0; h < 2; ++h) {
-            const char* pa_ = stage + k * WG_PANEL + wg_off(row, 2 * (4 * h + g));
+            const char* pa_ = stage + k * WG_PANEL + stage_off(row, 2 * (4 * h + g));
             const f16x8 ah = *reinterpret_cast<const f16x8*>(pa_), al = *reinterpret_cast<const f16x8*>(pa_ + 4096);
             const char* wb = wfrag + ((2 * k + h) * 4 + dg_nt) * 2048 + l * 16;
             const f16x8 bh = *reinterpret_cast<const f16x8*>(wb), bl = *reinterpret_cast<const f16x8*>(wb + 1024);
@@ -267,7 +242,7 @@ __global__ __launch_bounds__(64 * WG_WAVES, 2) void k_wgrad_h2(const WgP P) {
         // lane (g, li) holds points 4 g + r (r = 0..3) of channel li; a 4 x 4 transpose inside every quad of lanes turns
         // that into four consecutive channels of ONE point per lane: one 16-byte store instead of four 4-byte ones
         float t0 = tot[0], t1 = tot[1], t2 = tot[2], t3 = tot[3];
-        wg_quad_transpose(t0, t1, t2, t3);
+        quad_transpose(t0, t1, t2, t3);
         const long pq = s * 32 + 16 * dg_mt + 4 * g + (li & 3);
         if (pq < P.npts) *reinterpret_cast<float4*>(P.gx + pq * P.N + 16 * dg_nt + 4 * (li >> 2)) = make_float4(t0, t1, t2, t3);
       }
@@ -277,7 +252,7 @@ __global__ __launch_bounds__(64 * WG_WAVES, 2) void k_wgrad_h2(const WgP P) {
         convert(cur ^ 1);                    // waits for the loads of step s + 1
         issue(s + 2);
       }
-      wg_barrier();
+      lds_barrier();
     }
   }
 
@@ -295,8 +270,7 @@ __global__ __launch_bounds__(64 * WG_WAVES, 2) void k_wgrad_h2(const WgP P) {
 }
 
 bool wgrad_h2_ok(long P, int out_f, int in_f) {
-  const char* e = getenv("RPDE_WGRAD_H2");
-  if ((e && e[0] == '0') || P < 32L * WG_BLOCKS) return false;
+  if (switch_off("RPDE_WGRAD_H2") || P < 32L * WG_BLOCKS) return false;
   return (out_f == 256 && in_f == 256) || (out_f == 256 && in_f == 64) || (out_f == 64 && in_f == 256);
 }
 

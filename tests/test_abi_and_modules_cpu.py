@@ -105,7 +105,7 @@ def test_every_environment_switch_is_documented():
     import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     names = set()
-    for base, pat in (("resolution-pde_amd/csrc", r'getenv\("(RPDE_[A-Z0-9_]+)"\)'),
+    for base, pat in (("resolution-pde_amd/csrc", r'(?:getenv|switch_off)\("(RPDE_[A-Z0-9_]+)"\)'),
                       ("resolution-pde_amd", r'environ(?:\.get)?[\(\[]"(RPDE_[A-Z0-9_]+)"'), (".", None)):
         if pat is None:
             files, pat = [os.path.join(root, "bench.py")], r'environ(?:\.get)?[\(\[]"(RPDE_[A-Z0-9_]+)"'

@@ -118,7 +118,7 @@ def test_no_use_of_asm_loaded_registers_before_the_counted_wait(tmp_path):
 
 @pytest.mark.skipif(_hipcc() is None, reason="hipcc not available")
 def test_feedforward_backward_kernel_keeps_its_asm_loads_untouched_until_the_wait(tmp_path):
-    """k_ff3_bwd_h2 fetches g and z3 a tile ahead with asm loads (csrc/ff_fused.hip: fb_gload) and waits with a counted
+    """k_ff3_bwd_h2 fetches g and z3 a tile ahead with asm loads (csrc/wave.h: global_load_b128) and waits with a counted
     vmcnt; the same rule applies.  Its tile loop must also be free of compiler-inserted `vmcnt(0)` (each one is a wait
     for the LDS-DMA requested a moment earlier: the default instance lost 10 % to five of them) and of spill reloads."""
     for name, body in _kernel_bodies(tmp_path, "ff_fused", ("12k_ff3_bwd_h2ILb0E", "12k_ff3_bwd_h2ILb1E")):
