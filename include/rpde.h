@@ -400,6 +400,33 @@ int rpde_adamw_apply_dev(float* p, const float* g, float* m, float* v, int64_t n
                          float lr, float b1, float b2, float eps, float weight_decay,
                          const float* step_dev, void* stream);
 
+/* ---- gradient-norm clipping and non-finite step skipping, on the device (csrc/adamw_clip.hip).
+ * rpde_grad_norm: norm = sqrt(sum g^2) over n (multiple of 4) floats, squares and sums in float64, two deterministic
+ * stages without atomics (one double per workgroup in ws, added in fixed order), rounded to fp32 once; then
+ * torch.nn.utils.clip_grad_norm_'s rule  scale = min(1, max_norm / (norm + 1e-6))  with NaN propagating as in
+ * torch.clamp and an infinite norm giving 0.  max_norm <= 0 or +inf: measure only, scale 1.  The result is the device
+ * record clip_dev, 8 floats:
+ *   [0] this step's norm   [1] the scale applied   [2] 1.0 when this step is skipped (skip_nonfinite != 0 and the norm
+ *   is NaN or inf), else 0.0   [3] steps seen   [4] steps clipped (scale < 1, not skipped)   [5] steps skipped
+ *   [6] largest finite norm seen   [7] sum of the finite norms.
+ * [3..7] accumulate over calls until the caller zeroes them; the counters are fp32 and exact up to 2^24 steps.
+ * ws: rpde_grad_norm_ws_bytes(n) bytes, 8-byte aligned (0 for an n the call would refuse). */
+size_t rpde_grad_norm_ws_bytes(int64_t n);
+int rpde_grad_norm(const float* g, int64_t n, float max_norm, int skip_nonfinite, float* clip_dev,
+                   void* ws, size_t ws_bytes, void* stream);
+/* rpde_adamw_step / _step_dev / _apply_dev behind such a record: the update uses clip_dev[1] * g (g itself is not
+ * rewritten), and when clip_dev[2] is set the call changes nothing -- parameters, moments, and for _step_dev the step
+ * counter and the words derived from it, stay bit for bit.  With scale 1 the results equal the plain calls' bit for bit. */
+int rpde_adamw_step_clip(float* p, const float* g, float* m, float* v, int64_t n,
+                         float one_minus_lr_wd, float one_minus_b1, float b2, float one_minus_b2,
+                         float step_size, float bc2_sqrt, float eps, const float* clip_dev, void* stream);
+int rpde_adamw_step_dev_clip(float* p, const float* g, float* m, float* v, int64_t n,
+                             float lr, float b1, float b2, float eps, float weight_decay,
+                             float* step_dev, const float* clip_dev, void* stream);
+int rpde_adamw_apply_dev_clip(float* p, const float* g, float* m, float* v, int64_t n,
+                              float lr, float b1, float b2, float eps, float weight_decay,
+                              const float* step_dev, const float* clip_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -127,6 +127,11 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
 
 int launch_gemm(const rpde_gemm_desc& d, hipStream_t stream);
 // pre-split operands of the split-bf16 GEMM (gemm_bf16x3.hip)

@@ -140,6 +140,11 @@ _SIGNATURES = {
     "rpde_adamw_step_dev": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _P, _P]),
     "rpde_adamw_set_hyper_dev": (_I, [_P, _F, _F, _P]),
     "rpde_adamw_apply_dev": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _P, _P]),
+    "rpde_grad_norm_ws_bytes": (_Z, [_L]),
+    "rpde_grad_norm": (_I, [_P, _L, _F, _I, _P, _P, _Z, _P]),
+    "rpde_adamw_step_clip": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _F, _F, _P, _P]),
+    "rpde_adamw_step_dev_clip": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _P, _P, _P]),
+    "rpde_adamw_apply_dev_clip": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _P, _P, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

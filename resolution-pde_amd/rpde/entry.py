@@ -129,11 +129,17 @@ def run(dims: int, argv=None):
     # training.graph=true (or RPDE_TRAIN_GRAPH=1): train() replays each batch shape's step as one hipGraph -- the optimizer's
     # step state (count, learning rate, weight decay) then lives on the device
     use_graph = bool(args.training.get("graph", False)) or os.environ.get("RPDE_TRAIN_GRAPH") == "1"
+    # optional guards of the step (no yaml carries them by default): training.max_grad_norm clips the gradient norm,
+    # training.skip_nonfinite drops a step whose norm is NaN / inf; the latter needs the device-side step counter
+    max_grad_norm = args.training.get("max_grad_norm", None)
+    skip_nonfinite = bool(args.training.get("skip_nonfinite", False))
+    guard = dict(max_grad_norm=None if max_grad_norm is None else float(max_grad_norm), skip_nonfinite=skip_nonfinite,
+                 capturable=use_graph or skip_nonfinite)
     if dims == 2:     # reference main_2d.py:173-174
-        optimizer = FlatAdamW(model.parameters(), lr=lr, capturable=use_graph)
+        optimizer = FlatAdamW(model.parameters(), lr=lr, **guard)
         scheduler = optim.lr_scheduler.StepLR(optimizer, step_size=30, gamma=0.5)
     else:             # reference main_1d.py:144-145
-        optimizer = FlatAdamW(model.parameters(), lr=lr, weight_decay=1e-4, capturable=use_graph)
+        optimizer = FlatAdamW(model.parameters(), lr=lr, weight_decay=1e-4, **guard)
         scheduler = optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=100, eta_min=1e-5)
 
     n_params = sum(p.numel() for p in model.parameters())

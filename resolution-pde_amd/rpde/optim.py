@@ -22,6 +22,21 @@ goes through it -- eager steps of any batch shape, several ``GraphedTrainStep`` 
 ``refresh_device_hyper()`` (called by ``GraphedTrainStep``) compares the group's values with that record and writes
 them only when they differ.  A captured step follows the schedule without being captured again, and a replay with
 nothing changed costs no extra launch.
+
+``max_grad_norm`` / ``skip_nonfinite`` guard the step on the device (csrc/adamw_clip.hip), with no host read and inside
+a captured step as well.  ``max_grad_norm=c`` is ``torch.nn.utils.clip_grad_norm_(params, c)``: norm = sqrt(sum g^2)
+over the whole flat gradient buffer (after ``bucket.all_reduce_mean()`` under data parallelism, so every rank forms the
+same number from the same bytes; idle slots and padding are zero), scale = min(1, c / (norm + 1e-6)), and the update
+runs on ``scale * g``.  The norm is summed in float64 and rounded to fp32 once, so gradients whose fp32 squares
+overflow still have their true norm.  ONE DIFFERENCE from torch's in-place clip: the bucket is not rewritten --
+``p.grad`` after ``step()`` holds the unclipped gradient; the scale that was applied is ``grad_stats()[1]``.
+``skip_nonfinite=True`` (needs ``capturable=True``: only the device-side step counter can stand still) makes a step
+whose norm is NaN or inf do nothing: parameters, moments, the step counter and the words derived from it stay bit for
+bit, and ``state_dict()`` -- whose ``step`` comes from that counter -- does not show the step at all.  Without it a
+non-finite norm does what it does in torch: it reaches the parameters.  ``grad_stats()`` is the 8-float device record
+(norm, scale, skipped, steps seen / clipped / skipped, largest finite norm, sum of the finite norms), returned without
+a sync; ``reset_grad_stats()`` zeroes its counters.  With both options at their defaults nothing of this is allocated
+or launched.
 """
 from __future__ import annotations
 
@@ -36,7 +51,13 @@ from .parallel import FlatGradBucket
 
 class FlatAdamW(torch.optim.Optimizer):
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
-                 bucket: Optional[FlatGradBucket] = None, capturable: bool = False):
+                 bucket: Optional[FlatGradBucket] = None, capturable: bool = False,
+                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:      # (NaN fails the comparison too)
+            raise ValueError(f"FlatAdamW: max_grad_norm must be a positive number or None, got {max_grad_norm!r}")
+        if skip_nonfinite and not capturable:
+            raise ValueError("FlatAdamW: skip_nonfinite=True needs capturable=True (a skipped step leaves the step count "
+                             "where it is, which only the device-side counter can do without a host read)")
         if lr < 0 or eps < 0 or weight_decay < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
             raise ValueError("FlatAdamW: invalid hyper-parameters")
         super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, capturable=capturable))
@@ -62,6 +83,14 @@ class FlatAdamW(torch.optim.Optimizer):
         self._step_dev = torch.zeros(8, dtype=torch.float32, device=dev) if capturable else None
         # (lr, weight_decay) last written to _step_dev[3:5] (the zeros it starts with): what a replay would read now
         self._dev_hyper: Optional[Tuple[float, float]] = (0.0, 0.0) if capturable else None
+        # gradient-norm record and the norm's workspace (one double per workgroup): allocated here, never inside a capture
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._clip_dev = self._clip_ws = None
+        if self.max_grad_norm is not None or self.skip_nonfinite:
+            self._clip_dev = torch.zeros(8, dtype=torch.float32, device=dev)
+            self._clip_ws = torch.empty(int(load().rpde_grad_norm_ws_bytes(self.bucket.flat.numel())) // 8,
+                                        dtype=torch.float64, device=dev)
         for i, (p, gview) in enumerate(zip(group_params, self.bucket._views)):
             r = 1 if p.is_complex() else 0
             off, size = self._offsets[i] - bounds[r][0], self._sizes[i]
@@ -110,6 +139,11 @@ class FlatAdamW(torch.optim.Optimizer):
             if p.grad.data_ptr() != base_g + 4 * self._offsets[i]:     # .grad replaced after gather(): bring it in
                 self.bucket._views[i].copy_(p.grad)
             live.append(i)
+        clip = None
+        if self._clip_dev is not None:                         # one norm per step(); every update launch reads it
+            clip = self._clip_dev.data_ptr()
+            check(lib.rpde_grad_norm(base_g, self.bucket.flat.numel(), self.max_grad_norm or 0.0, int(self.skip_nonfinite),
+                                     clip, self._clip_ws.data_ptr(), self._clip_ws.numel() * 8, st), "grad_norm")
         if self._step_dev is not None:
             if len(live) != len(params):
                 raise RuntimeError("FlatAdamW(capturable=True): every parameter must receive a gradient in every step")
@@ -119,9 +153,14 @@ class FlatAdamW(torch.optim.Optimizer):
             for r, (lo, hi) in enumerate(self._bounds):          # the counter advances once per step, not per region
                 if hi == lo:
                     continue
-                fn = lib.rpde_adamw_apply_dev if ticked else lib.rpde_adamw_step_dev
-                check(fn(self._p[r].data_ptr(), base_g + 4 * lo, self._m[r].data_ptr(), self._v[r].data_ptr(), hi - lo,
-                         lr, b1, b2, eps, wd, self._step_dev.data_ptr(), st), "adamw_step_dev")
+                args = (self._p[r].data_ptr(), base_g + 4 * lo, self._m[r].data_ptr(), self._v[r].data_ptr(), hi - lo,
+                        lr, b1, b2, eps, wd, self._step_dev.data_ptr())
+                if clip is None:
+                    fn = lib.rpde_adamw_apply_dev if ticked else lib.rpde_adamw_step_dev
+                    check(fn(*args, st), "adamw_step_dev")
+                else:
+                    fn = lib.rpde_adamw_apply_dev_clip if ticked else lib.rpde_adamw_step_dev_clip
+                    check(fn(*args, clip, st), "adamw_step_dev_clip")
                 ticked = True
             if not torch.cuda.is_current_stream_capturing():      # an eager step stored its lr / wd; a captured one did not
                 self._dev_hyper = (lr, wd)
@@ -143,13 +182,29 @@ class FlatAdamW(torch.optim.Optimizer):
             lo = self._offsets[i0]
             rl = lo - self._bounds[r][0]
             bc1, bc2 = 1.0 - b1 ** t, 1.0 - b2 ** t
-            check(lib.rpde_adamw_step(self._p[r].data_ptr() + 4 * rl, base_g + 4 * lo, self._m[r].data_ptr() + 4 * rl,
-                                      self._v[r].data_ptr() + 4 * rl, end - lo, 1.0 - lr * wd, 1.0 - b1, b2, 1.0 - b2,
-                                      lr / bc1, math.sqrt(bc2), eps, st), "adamw_step")
+            args = (self._p[r].data_ptr() + 4 * rl, base_g + 4 * lo, self._m[r].data_ptr() + 4 * rl,
+                    self._v[r].data_ptr() + 4 * rl, end - lo, 1.0 - lr * wd, 1.0 - b1, b2, 1.0 - b2,
+                    lr / bc1, math.sqrt(bc2), eps)
+            if clip is None:
+                check(lib.rpde_adamw_step(*args, st), "adamw_step")
+            else:
+                check(lib.rpde_adamw_step_clip(*args, clip, st), "adamw_step_clip")
             for i in order[k:j + 1]:
                 self._steps[i] = t
             k = j + 1
         return loss
+
+    def grad_stats(self) -> Optional[torch.Tensor]:
+        """the device record of the gradient norm, 8 floats, as it stands in stream order -- no sync, no copy: [0] the
+        last step's norm, [1] the scale it applied, [2] 1.0 when it was skipped, [3] steps seen, [4] steps clipped,
+        [5] steps skipped, [6] largest finite norm, [7] sum of the finite norms ([3:] since the last
+        reset_grad_stats()).  None when neither max_grad_norm nor skip_nonfinite is set."""
+        return self._clip_dev
+
+    def reset_grad_stats(self) -> None:
+        """zero the counters [3:] of grad_stats() (outside a capture; one tiny launch)"""
+        if self._clip_dev is not None:
+            self._clip_dev[3:].zero_()
 
     def _group_hyper(self) -> Tuple[float, float]:
         g = self.param_groups[0]

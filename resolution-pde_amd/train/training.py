@@ -55,7 +55,12 @@ def train(model, train_loader, val_loader, optimizer, scheduler, y_normalizer=No
     steps of that shape have run.  The small 1-D configurations are bound by the host's launches (FNO1d-1024 at
     batch 16: 1.1-1.3 ms per eager step, 0.69 ms replayed); same arithmetic, same order.  Needs
     rpde.optim.FlatAdamW(capturable=True) (its learning rate lives on the device, so the per-epoch scheduler step is
-    followed without a new capture); silently stays eager otherwise."""
+    followed without a new capture); silently stays eager otherwise.
+
+    An optimizer with a gradient-norm record (rpde.optim.FlatAdamW(max_grad_norm=..., skip_nonfinite=...): its
+    grad_stats() is not None) adds grad_norm_mean / grad_norm_max (over the epoch's finite norms), clipped_steps and
+    skipped_steps to the epoch record; the record is read once per epoch, next to the loss, and reset.  The loss mean
+    is NOT corrected for skipped steps: a skipped step's NaN loss still shows in train_loss."""
     loss_fn = RelativeL2Loss(size_average=True)
     # rpde.optim.FlatAdamW brings its own bucket (its gradients, parameters and moments share one flat layout)
     bucket = getattr(optimizer, "bucket", None) or FlatGradBucket(model.parameters())
@@ -125,6 +130,14 @@ def train(model, train_loader, val_loader, optimizer, scheduler, y_normalizer=No
             del loss, pred_y
         avg_train = _mean_over_ranks(running, n_batches)
         loss_history.append(avg_train)
+        grad_rec = {}
+        stats = optimizer.grad_stats() if hasattr(optimizer, "grad_stats") else None
+        if stats is not None:                  # every rank holds the same record: the norm is taken after the all-reduce
+            s = stats.tolist()
+            finite = s[3] - s[5]               # (with skip_nonfinite off a non-finite norm is counted here, too)
+            grad_rec = {"grad_norm_mean": s[7] / finite if finite > 0 else float("nan"), "grad_norm_max": s[6],
+                        "clipped_steps": int(s[4]), "skipped_steps": int(s[5])}
+            optimizer.reset_grad_stats()
 
         model.eval()
         vrun = torch.zeros((), device=device)
@@ -145,7 +158,7 @@ def train(model, train_loader, val_loader, optimizer, scheduler, y_normalizer=No
             scheduler.step(avg_val)
         elif scheduler is not None:
             scheduler.step()
-        rec = {"epoch": epoch, "train_loss": avg_train, "val_loss": avg_val}
+        rec = {"epoch": epoch, "train_loss": avg_train, "val_loss": avg_val, **grad_rec}
         if log is not None:
             log(rec)
         if epoch % 10 == 0 and (not _dist_on() or dist.get_rank() == 0):
