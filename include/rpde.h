@@ -380,6 +380,27 @@ int rpde_rel_l2_bwd(const float* x, const float* y, const float* stats,
                     const float* grad_loss, const float* grad_rel, float* grad_x,
                     int B, int64_t per, int size_average, void* stream);
 
+/* ---- mode-weighted relative L2 loss (utils/loss.py SpectralRelativeL2Loss; an interface addition, the reference has
+ * none).  x, y [B, C, M, N] fp32 channels-first, M = 1 for one-dimensional fields [B, C, N]; omega [M, N/2+1] >= 0, rows
+ * in fft order.  With Z = rfft / rfft2 (unnormalised) and c_kx = 1 at kx = 0 and (even N) kx = N/2, else 2:
+ *   E(z)[b] = sum_c sum_k omega_k c_kx / (M N) |Z[b,c,k]|^2,   rel[b] = sqrt(E(x - y)[b]) / (sqrt(E(y)[b]) + 1e-8);
+ * x - y is formed in fp32 before the transform; the sums are float64, two deterministic stages without atomics.
+ * rel [B] or NULL; loss: device scalar = mean (size_average) or sum, NULL for reduction=False; stats: 2 B floats
+ * (sqrt E_d, sqrt E_y per sample) and spec_d (the spec_elems query's count of floats: the spectrum of x - y) are kept for backward.
+ * Backward: grad_x[b] = coef_b irfft(omega . spec_d[b]), coef_b = g_b / (sqrt(E_d) (sqrt(E_y) + 1e-8)), 0 where
+ * E_d = 0, formed on the device; g_b = grad_rel[b], or grad_loss[0] (/ B when size_average) with grad_rel NULL.
+ * No gradient for y.  In 2-D the columns kx = 0 and (even N) kx = N/2 of omega must be symmetric in ky
+ * (omega[ky] == omega[(M - ky) % M]): the caller checks it.  Axes 2 .. 4096; the full-spectrum plans are those of the
+ * resizers at equal sizes (first use of a grid allocates and synchronises).  Argument errors are reported before any
+ * device work. */
+size_t rpde_wrel_l2_ws_bytes(int B, int C, int M, int N);
+size_t rpde_wrel_l2_spec_elems(int B, int C, int M, int N);
+int rpde_wrel_l2_fwd(const float* x, const float* y, const float* omega, float* rel, float* loss, float* stats,
+                     float* spec_d, int B, int C, int M, int N, int size_average, void* ws, size_t ws_bytes, void* stream);
+int rpde_wrel_l2_bwd(const float* spec_d, const float* omega, const float* stats, const float* grad_loss,
+                     const float* grad_rel, float* grad_x, int B, int C, int M, int N, int size_average,
+                     void* ws, size_t ws_bytes, void* stream);
+
 /* ---- optimizer step: torch.optim.AdamW as built at main_1d.py:144 / main_2d.py:173 (decoupled weight decay,
  * bias-corrected moments, no amsgrad), one streaming kernel over flat fp32 buffers of n (multiple of 4) elements.
  * The caller passes the step's scalars: 1 - lr*wd, 1 - b1, b2, 1 - b2, lr / (1 - b1^t), sqrt(1 - b2^t), eps. */

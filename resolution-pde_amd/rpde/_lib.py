@@ -136,6 +136,10 @@ _SIGNATURES = {
     "rpde_rel_l2_stats_elems": (_L, [_I]),
     "rpde_rel_l2_fwd": (_I, [_P, _P, _P, _P, _P, _I, _L, _I, _P]),
     "rpde_rel_l2_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _L, _I, _P]),
+    "rpde_wrel_l2_ws_bytes": (_Z, [_I, _I, _I, _I]),
+    "rpde_wrel_l2_spec_elems": (_Z, [_I, _I, _I, _I]),
+    "rpde_wrel_l2_fwd": (_I, [_P] * 7 + [_I] * 5 + [_P, _Z, _P]),
+    "rpde_wrel_l2_bwd": (_I, [_P] * 6 + [_I] * 5 + [_P, _Z, _P]),
     "rpde_adamw_step": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _F, _F, _P]),
     "rpde_adamw_step_dev": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _P, _P]),
     "rpde_adamw_set_hyper_dev": (_I, [_P, _F, _F, _P]),

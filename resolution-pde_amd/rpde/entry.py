@@ -142,6 +142,21 @@ def run(dims: int, argv=None):
         optimizer = FlatAdamW(model.parameters(), lr=lr, weight_decay=1e-4, **guard)
         scheduler = optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=100, eta_min=1e-5)
 
+    # optional training objective (no yaml carries it): training.loss=sobolev trains on the H^s relative loss
+    # (utils.loss.SpectralRelativeL2Loss) with training.loss_s (default 1.0) and training.loss_length (a float or one
+    # per axis, default 1.0); absent or "l2": RelativeL2Loss.  Validation, the test score and the sweeps stay relative L2.
+    loss_fn = None
+    loss_name = str(args.training.get("loss", "l2"))
+    if loss_name == "sobolev":
+        from utils.loss import SpectralRelativeL2Loss
+        length = args.training.get("loss_length", 1.0)
+        length = [float(v) for v in length] if isinstance(length, (list, tuple)) else float(length)
+        loss_fn = SpectralRelativeL2Loss(dims, "sobolev", s=float(args.training.get("loss_s", 1.0)), length=length)
+        for r in train_loader.resolution_groups:
+            loss_fn.warm((int(r),) * dims, device)
+    elif loss_name != "l2":
+        raise SystemExit(f"training.loss={loss_name}: expected l2 or sobolev")
+
     n_params = sum(p.numel() for p in model.parameters())
     if rank == 0:
         print(json.dumps({"model": args.model["_target_"], "params": n_params, "world": world,
@@ -151,7 +166,7 @@ def run(dims: int, argv=None):
     t0 = time.time()
     loss_hist, val_hist = train(model, train_loader, val_loader, optimizer, scheduler, y_normalizer=y_normalizer,
                                 use_normalizer=bool(args.training.use_normalizer), epochs=int(args.training.epochs),
-                                device=device, graph=use_graph)
+                                device=device, graph=use_graph, loss_fn=loss_fn)
     torch.cuda.synchronize()
     test_l2 = evaluate(model, test_loader, normalization_type=normalization_type, min_data=min_data, max_data=max_data,
                        min_model=min_model, max_model=max_model, y_normalizer=y_normalizer, device=device)

@@ -803,6 +803,60 @@ def relative_l2(x, y, size_average: bool = True, reduction: bool = True):
 
 
 # ----------------------------------------------------------------------------
+# mode-weighted relative L2 loss (csrc/spectral_cf.hip, rpde_wrel_l2_*; utils/loss.py SpectralRelativeL2Loss)
+# ----------------------------------------------------------------------------
+class _WRelL2(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, omega, dims: int, size_average: bool, reduction: bool):
+        lib = load()
+        if x.dim() != dims + 2 or x.shape != y.shape:
+            raise ValueError(f"weighted_relative_l2: x {tuple(x.shape)} / y {tuple(y.shape)}, expected equal "
+                             f"{dims + 2}-D channels-first shapes")
+        B, Cc = x.shape[0], x.shape[1]
+        M, N = (1, x.shape[2]) if dims == 1 else (x.shape[2], x.shape[3])
+        want = (N // 2 + 1,) if dims == 1 else (M, N // 2 + 1)
+        if tuple(omega.shape) != want:
+            raise ValueError(f"weighted_relative_l2: omega {tuple(omega.shape)}, expected {want} for the grid {tuple(x.shape[2:])}")
+        x, y = _f32c(x), _f32c(y)
+        px, py, pw = ptr(x), ptr(y), ptr(omega)               # raises for CPU tensors: there is no fallback
+        stats = torch.empty(2 * B, dtype=torch.float32, device=x.device)
+        rel = torch.empty(B, dtype=torch.float32, device=x.device)
+        loss = torch.empty((), dtype=torch.float32, device=x.device) if reduction else None
+        spec = torch.empty(lib.rpde_wrel_l2_spec_elems(B, Cc, M, N), dtype=torch.float32, device=x.device)
+        nws = lib.rpde_wrel_l2_ws_bytes(B, Cc, M, N)
+        ws = workspace(nws, x.device)
+        check(lib.rpde_wrel_l2_fwd(px, py, pw, ptr(rel), ptr(loss), ptr(stats), ptr(spec), B, Cc, M, N, int(size_average),
+                                   ws.data_ptr(), nws, stream_ptr()), "wrel_l2_fwd")
+        ctx.save_for_backward(spec, omega, stats)
+        ctx.meta = (tuple(x.shape), B, Cc, M, N, size_average, reduction)
+        return loss if reduction else rel
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = load()
+        spec, omega, stats = ctx.saved_tensors
+        shape, B, Cc, M, N, size_average, reduction = ctx.meta
+        g = _f32c(g)
+        gx = torch.empty(shape, dtype=torch.float32, device=spec.device)
+        nws = lib.rpde_wrel_l2_ws_bytes(B, Cc, M, N)
+        ws = workspace(nws, spec.device)
+        check(lib.rpde_wrel_l2_bwd(ptr(spec), ptr(omega), ptr(stats), ptr(g) if reduction else None,
+                                   None if reduction else ptr(g), ptr(gx), B, Cc, M, N, int(size_average),
+                                   ws.data_ptr(), nws, stream_ptr()), "wrel_l2_bwd")
+        return gx, None, None, None, None, None
+
+
+def weighted_relative_l2(x, y, omega, dims: int, size_average: bool = True, reduction: bool = True):
+    """rel[b] = sqrt(E(x - y)[b]) / (sqrt(E(y)[b]) + 1e-8), E(z)[b] = sum_c sum_k omega_k c_kx / N |rfft(z)[b,c,k]|^2, then
+    mean / sum / the per-sample vector as relative_l2.  x, y [B, C, n] (dims=1) or [B, C, H, W] (dims=2) and omega
+    [n//2+1] / [H, W//2+1] (>= 0, rows in fft order; validated by utils.loss.SpectralRelativeL2Loss) are contiguous
+    fp32 tensors on the GPU.  Gradient for x only."""
+    if dims not in (1, 2):
+        raise ValueError(f"weighted_relative_l2: dims must be 1 or 2, got {dims}")
+    return _WRelL2.apply(x, y, omega, int(dims), bool(size_average), bool(reduction))
+
+
+# ----------------------------------------------------------------------------
 # spectral resize (evaluation-time data path; no autograd)
 # ----------------------------------------------------------------------------
 def resize1d(x: torch.Tensor, out_size: int) -> torch.Tensor:

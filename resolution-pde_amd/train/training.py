@@ -49,8 +49,13 @@ GRAPH_AFTER = 2          # eager steps of a batch shape before its step is captu
 
 def train(model, train_loader, val_loader, optimizer, scheduler, y_normalizer=None, use_normalizer=False, time=1,
           model_type="ffno", epochs=100, device="cuda", log: Optional[Callable[[dict], None]] = None,
-          graph: Optional[bool] = None):
-    """graph (default: environment RPDE_TRAIN_GRAPH=1): replay the step -- zero_grad, forward, loss, backward, gradient
+          graph: Optional[bool] = None, loss_fn=None):
+    """loss_fn (default: RelativeL2Loss(size_average=True)): the training objective, a callable (prediction, target) ->
+    device scalar, e.g. utils.loss.SpectralRelativeL2Loss; validation and evaluate() stay plain relative L2 whatever
+    trains the model, so reported metrics compare across objectives.  For graph=True its plans and tables must exist
+    before the capture: the GRAPH_AFTER eager steps of a batch shape see to that.
+
+    graph (default: environment RPDE_TRAIN_GRAPH=1): replay the step -- zero_grad, forward, loss, backward, gradient
     all-reduce, optimizer -- as one hipGraph per batch shape (rpde.graph.GraphedTrainStep) once GRAPH_AFTER eager
     steps of that shape have run.  The small 1-D configurations are bound by the host's launches (FNO1d-1024 at
     batch 16: 1.1-1.3 ms per eager step, 0.69 ms replayed); same arithmetic, same order.  Needs
@@ -61,7 +66,9 @@ def train(model, train_loader, val_loader, optimizer, scheduler, y_normalizer=No
     grad_stats() is not None) adds grad_norm_mean / grad_norm_max (over the epoch's finite norms), clipped_steps and
     skipped_steps to the epoch record; the record is read once per epoch, next to the loss, and reset.  The loss mean
     is NOT corrected for skipped steps: a skipped step's NaN loss still shows in train_loss."""
-    loss_fn = RelativeL2Loss(size_average=True)
+    val_loss_fn = RelativeL2Loss(size_average=True)
+    if loss_fn is None:
+        loss_fn = val_loss_fn
     # rpde.optim.FlatAdamW brings its own bucket (its gradients, parameters and moments share one flat layout)
     bucket = getattr(optimizer, "bucket", None) or FlatGradBucket(model.parameters())
     if graph is None:
@@ -149,7 +156,7 @@ def train(model, train_loader, val_loader, optimizer, scheduler, y_normalizer=No
                 if use_normalizer and y_normalizer is not None:
                     val_pred = y_normalizer.decode(val_pred, device=device)
                     val_y = y_normalizer.decode(val_y, device=device)
-                vrun += loss_fn(val_pred, val_y) * val_x.shape[0]     # sample-weighted: ranks may hold ragged shares
+                vrun += val_loss_fn(val_pred, val_y) * val_x.shape[0]     # sample-weighted: ranks may hold ragged shares
                 vn += val_x.shape[0]
         avg_val = _mean_over_ranks(vrun, vn)
         val_loss_history.append(avg_val)

@@ -1,8 +1,15 @@
 """RelativeL2Loss (reference: utils/loss.py:17-59): per-sample
 |x - y|_2 / (|y|_2 + 1e-8), then mean / sum / none -- one fused HIP pass over
-prediction and target (wavefront-shuffle reductions, deterministic)."""
+prediction and target (wavefront-shuffle reductions, deterministic).
+
+SpectralRelativeL2Loss (no counterpart in the reference): the same ratio with a non-negative weight per Fourier
+mode -- the H^s / Sobolev relative loss of operator learning is the preset -- forward and backward on the device
+(rpde.ops.weighted_relative_l2, csrc/spectral_cf.hip)."""
 from __future__ import annotations
 
+import math
+
+import torch
 import torch.nn as nn
 
 from rpde import ops
@@ -16,3 +23,106 @@ class RelativeL2Loss(nn.Module):
 
     def forward(self, x, y):
         return ops.relative_l2(x, y, self.size_average, self.reduction)
+
+
+def sobolev_weights(spatial_shape, s=1.0, length=1.0) -> torch.Tensor:
+    """omega = (1 + sum_axes (2 pi k_axis / L_axis)^2)^s on the half spectrum of a grid: float64 [n//2+1] for (n,),
+    [H, W//2+1] for (H, W) with ky signed in fft order (fftfreq(H) * H) and kx = 0 .. W//2; the Nyquist bin of an even
+    axis counts with |k| = n/2.  s = 1 is H^1; length: one float, or one per axis."""
+    shape = tuple(int(n) for n in spatial_shape)
+    if len(shape) not in (1, 2) or min(shape) < 2:
+        raise ValueError(f"sobolev_weights: spatial_shape {spatial_shape}, expected (n,) or (H, W) with every axis >= 2")
+    L = [float(length)] * len(shape) if isinstance(length, (int, float)) else [float(v) for v in length]
+    if len(L) != len(shape) or not all(math.isfinite(v) and v > 0 for v in L):
+        raise ValueError(f"sobolev_weights: length {length} for a {len(shape)}-D grid")
+    kx = torch.arange(shape[-1] // 2 + 1, dtype=torch.float64)
+    q = (2.0 * math.pi * kx / L[-1]) ** 2
+    if len(shape) == 2:
+        ky = torch.fft.fftfreq(shape[0], dtype=torch.float64) * shape[0]
+        q = (2.0 * math.pi * ky / L[0]).view(-1, 1) ** 2 + q.view(1, -1)
+    return (1.0 + q) ** float(s)
+
+
+def check_mode_weights(omega: torch.Tensor, spatial_shape) -> None:
+    """ValueError unless omega is a finite, non-negative table of the half spectrum of this grid whose self-conjugate
+    columns (kx = 0 and, for even W, kx = W/2) are symmetric in ky: otherwise omega * rfft2(d) is not the spectrum of
+    a real field and the inverse transform is not the gradient"""
+    shape = tuple(int(n) for n in spatial_shape)
+    want = (shape[0] // 2 + 1,) if len(shape) == 1 else (shape[0], shape[1] // 2 + 1)
+    if tuple(omega.shape) != want:
+        raise ValueError(f"mode weights of shape {tuple(omega.shape)}: the grid {shape} needs {want}")
+    w = omega.detach().double().cpu()
+    if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+        raise ValueError("mode weights must be finite and >= 0")
+    if len(shape) == 2:
+        H, W = shape
+        flip = (H - torch.arange(H)) % H
+        for kx in [0] + ([W // 2] if W % 2 == 0 else []):
+            if not torch.equal(w[:, kx], w[flip, kx]):
+                raise ValueError(f"mode weights: column kx={kx} is not symmetric in ky (omega[ky] != omega[(H - ky) % H])")
+
+
+class SpectralRelativeL2Loss(nn.Module):
+    """rel[b] = sqrt(E(x - y)[b]) / (sqrt(E(y)[b]) + 1e-8) with E(z)[b] = sum_c sum_k omega_k c_kx / N |rfft(z)[b,c,k]|^2
+    (rfft2 for dims=2; c_kx the Hermitian multiplicity of the half axis), then mean / sum / per-sample vector as
+    RelativeL2Loss.  omega == 1 is RelativeL2Loss by Parseval.  x, y: channels-first fp32 tensors on the GPU.
+
+    weights="sobolev": sobolev_weights(grid, s, length), built per grid and cached per (grid, device), so one object
+    serves mixed-resolution batches.  weights=Tensor: an explicit table for ONE grid ([n//2+1] or [H, W//2+1], rows
+    in fft order), validated on the host at first use; another grid raises ValueError.
+
+    The first call at a grid builds the transform plans and the device table (allocation, one synchronisation);
+    warm(spatial_shape, device) does that ahead of a hipGraph capture."""
+
+    def __init__(self, dims, weights="sobolev", s=1.0, length=1.0, size_average=True, reduction=True):
+        super().__init__()
+        if int(dims) not in (1, 2):
+            raise ValueError(f"SpectralRelativeL2Loss: dims must be 1 or 2, got {dims}")
+        self.dims = int(dims)
+        if isinstance(weights, str):
+            if weights != "sobolev":
+                raise ValueError(f"SpectralRelativeL2Loss: unknown weights preset {weights!r} (presets: 'sobolev')")
+            sobolev_weights((4,) * self.dims, s, length)          # validates s / length now
+            self._explicit = None
+        elif torch.is_tensor(weights):
+            if weights.dim() != self.dims:
+                raise ValueError(f"SpectralRelativeL2Loss: a {weights.dim()}-D weight table for dims={self.dims}")
+            self._explicit = weights.detach()
+            self._explicit_grid = None
+        else:
+            raise ValueError("SpectralRelativeL2Loss: weights must be 'sobolev' or a tensor")
+        self.s, self.length = float(s), length
+        self.size_average = size_average
+        self.reduction = reduction
+        self._tables: dict = {}
+
+    def _table(self, grid, device) -> torch.Tensor:
+        key = (grid, torch.device(device))
+        t = self._tables.get(key)
+        if t is None:
+            if self._explicit is None:
+                w = sobolev_weights(grid, self.s, self.length)
+            else:
+                w = self._explicit
+                if self._explicit_grid not in (None, grid):
+                    raise ValueError(f"SpectralRelativeL2Loss: the explicit weight table serves the grid "
+                                     f"{self._explicit_grid}, got {grid}")
+                check_mode_weights(w, grid)
+                self._explicit_grid = grid
+            t = self._tables[key] = w.to(device=device, dtype=torch.float32).contiguous()
+        return t
+
+    def warm(self, spatial_shape, device="cuda") -> None:
+        """plans, workspaces and the weight table of one grid, outside any capture"""
+        grid = tuple(int(n) for n in spatial_shape)
+        if len(grid) != self.dims:
+            raise ValueError(f"SpectralRelativeL2Loss.warm: grid {grid} for dims={self.dims}")
+        z = torch.zeros((1, 1) + grid, dtype=torch.float32, device=device, requires_grad=True)
+        ops.weighted_relative_l2(z, torch.ones_like(z), self._table(grid, z.device), self.dims, True, True).backward()
+        torch.cuda.synchronize(z.device)
+
+    def forward(self, x, y):
+        if x.dim() != self.dims + 2:
+            raise ValueError(f"SpectralRelativeL2Loss(dims={self.dims}): expected [B, C, *grid], got {tuple(x.shape)}")
+        omega = self._table(tuple(x.shape[2:]), x.device)
+        return ops.weighted_relative_l2(x, y, omega, self.dims, self.size_average, self.reduction)
