@@ -765,9 +765,14 @@ __global__ void k_concat_grid(const float* __restrict__ x, float* __restrict__ o
     const float* tab = axis == 0 ? gx : gy;
     if (tab) v = tab[pos];
     else {
-      // numpy.linspace(lo, hi, len) in double, then cast (quirk Q10)
+      // numpy.linspace(lo, hi, len) in double, then cast (quirk Q10): pos * step is rounded BEFORE lo is added, as numpy
+      // does it -- a contracted fma differs in the last fp32 place at some positions when lo != 0
+      // (tests/test_gpu_pointwise.py, lo = -1, hi = 2.5).  hipcc contracts by default, through __dmul_rn / __dadd_rn
+      // too; the pragma is what keeps v_mul_f64 and v_add_f64 apart
+#pragma clang fp contract(off)
       const double step = len > 1 ? (hi - lo) / (double)(len - 1) : 0.0;
-      v = (pos == len - 1 && len > 1) ? (float)hi : (float)(lo + step * pos);
+      const double scaled = (double)pos * step;
+      v = (pos == len - 1 && len > 1) ? (float)hi : (float)(scaled + lo);
     }
   }
   out[idx] = v;

@@ -70,7 +70,9 @@ inline bool switch_off(const char* name) {
 // normal-distribution form of 7.1.26):  1 - Phi(|x|) = phi(x) (b1 s + ... + b5 s^5),  s = 1 / (1 + 0.2316419 |x|).
 // About 14 VALU instructions for Phi, 3 more for GELU and GELU' together, instead of the device library's erff
 // (~100).  Measured in fp32 against scipy over [-9, 9]: |Phi error| <= 3.0e-7, |gelu error| <= 4.2e-7,
-// |gelu' error| <= 3.1e-7 (parity budget of the hot path: 1e-5).
+// |gelu' error| <= 3.1e-7 (parity budget of the hot path: 1e-5).  On the MI355X itself, against float64 on 4e6 points of
+// [-14, 14] (tests/test_gpu_pointwise.py, which pins 1.5 x these bounds): max |gelu error| 4.21e-7 at x = 3.07496,
+// max |gelu' error| 2.76e-7 at x = 0.25471; beyond |x| = 9 gelu is exactly x or below 1e-12, gelu' 1 or 0.
 // gk = exp(-x^2/2) / sqrt(2 pi) = the normal density (the 1/sqrt(2 pi) rides in the exponent: exp2(-x^2 c + log2 k)),
 // and the polynomial coefficients carry sqrt(2 pi) / 2 so that half = (p s) gk = 0.5 erfc(|x| / sqrt 2)
 __device__ __forceinline__ void phi_parts(float x, float& cdf, float& gk) {

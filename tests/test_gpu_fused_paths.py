@@ -169,7 +169,11 @@ def test_fused_feedforward_is_reproducible_and_tail_safe(gpu_device):
 
 @pytest.mark.parametrize("scale", [1.0, 1e-6, 1e5])
 def test_channels_first_h2_dft_equals_gemm_path(gpu_device, scale):
-    """cf_dft.hip (SpectralConv1d/2d stage along the contiguous axis, spectral resize) against the GEMM path"""
+    """cf_dft.hip (SpectralConv1d/2d stage along the contiguous axis, spectral resize) against the GEMM path.
+    Eligible for the h2 kernels (cf_h2_eligible: n % 128 == 0, at most 32 table rows, table <= 64 KB): the 2-D layer
+    (N = 256, 12 modes) and the two small resizes, 128 -> 16 (analysis) and 16x16 -> 128x128 (synthesis, alpha != 1).
+    The 1-D layer (n = 1024, 16 modes: a 128 KB table) and the two large resizes (65 and 193 bins kept) run the generic
+    GEMM on both legs; tests/test_gpu_resize.py covers the resizers' fast path shape by shape."""
     from rpde import ops
     torch.manual_seed(9)
     x2 = torch.randn(2, 8, 64, 256, device=gpu_device) * scale
@@ -193,8 +197,10 @@ def test_channels_first_h2_dft_equals_gemm_path(gpu_device, scale):
         with torch.no_grad():
             rz = ops.resize2d(x2, (128, 128))
             rz1 = ops.resize1d(x1, 384)
+            rz1s = ops.resize1d(x1[..., :128].contiguous(), 16)
+            rzs = ops.resize2d(x2[:, :, :16, :16].contiguous(), (128, 128))
         return [o2.detach(), a.grad, torch.view_as_real(p.grad), torch.view_as_real(q.grad), o1.detach(), b.grad,
-                torch.view_as_real(r.grad), rz, rz1]
+                torch.view_as_real(r.grad), rz, rz1, rz1s, rzs]
 
     fused = run()
     with _env(RPDE_FUSED_CF="0"):
