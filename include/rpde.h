@@ -401,6 +401,38 @@ int rpde_wrel_l2_bwd(const float* spec_d, const float* omega, const float* stats
                      const float* grad_rel, float* grad_x, int B, int C, int M, int N, int size_average,
                      void* ws, size_t ws_bytes, void* stream);
 
+/* ---- NS vorticity generator (reference: data_generation/ns_2d.py, random_fields.py): 2-D Navier-Stokes in vorticity
+ * form on the periodic unit square, pseudo-spectral, and the Gaussian random field that seeds it (csrc/ns_solver.hip).
+ * Grids M x N, both axes even, 4 .. 4096.  A half spectrum is [images][M][re|im][kp] floats: rows ky in fft order
+ * (signed k1 = ky < M/2 ? ky : ky - M), kx = k2 = 0 .. N/2 contiguous, kp = N/2+1 rounded up to 4, padded columns zero;
+ * the spec_elems query gives the floats of B images.  The rfft2 / irfft2 calls are torch.fft.rfft2 (unnormalised) and
+ * irfft2 (1 / (M N); Im of the self-conjugate bins of the last axis ignored) between w [B, M, N] and that layout.
+ * The steps call advances W in place by nsteps steps of
+ *   psi = W inv_lap,  q = irfft2(2 pi i k2 psi),  v = irfft2(-2 pi i k1 psi),  w_x = irfft2(2 pi i k1 W),
+ *   w_y = irfft2(2 pi i k2 W),  F = rfft2(q w_x + v w_y),  W <- c_w W - c_f F + g_h
+ * with the tables c_w, c_f, inv_lap [M][kp] (padded columns zero) formed by the caller in float64 and rounded once:
+ *   a = dt visc lap / 2, lap = 4 pi^2 (k1^2 + k2^2):  c_w = (1 - a) / (1 + a),  c_f = dt dealias / (1 + a),
+ *   inv_lap = 1 / lap (1 at the mean mode),  dealias = |k1| <= (2/3)(M/2) and |k2| <= (2/3)(N/2);
+ * g_h = dt / (1 + a) rfft2(f): one spectrum (g_batched = 0) or B (g_batched = 1); the scale call forms it, out =
+ * table . spec, once per solve.  Six launches per step on the caller's stream, no host synchronisation, no atomics:
+ * identical calls give identical bits, and k calls of n steps equal one call of k n steps bit for bit.
+ * The grf2d call: noise [B, M, N, 2] (the complex coefficients of the full grid), sqrt_eig [M, N] -> out [B, M, N] =
+ * Re ifft2(sqrt_eig . noise) with 1 / (M N), through the Hermitian-symmetrised half spectrum and the same inverse.
+ * State, forcing and tables 16-byte aligned, workspaces (the ns2d ws query covers all four ns2d calls) 256-byte
+ * aligned; the ws / spec queries return 0 for sizes the calls refuse (odd or out-of-range axes, 4 B max(M, N) >= 2^31).
+ * The full-spectrum plans are those of the mode-weighted loss: the first use of a grid allocates and synchronises.
+ * Argument errors are reported before any device work. */
+size_t rpde_ns2d_ws_bytes(int B, int M, int N);
+size_t rpde_ns2d_spec_elems(int B, int M, int N);
+int rpde_ns2d_rfft2(const float* w, float* W, int B, int M, int N, void* ws, size_t ws_bytes, void* stream);
+int rpde_ns2d_irfft2(const float* W, float* w, int B, int M, int N, void* ws, size_t ws_bytes, void* stream);
+int rpde_ns2d_scale(const float* spec, const float* table, float* out, int B, int M, int N, void* stream);
+int rpde_ns2d_steps(float* W, const float* g_h, int g_batched, const float* c_w, const float* c_f, const float* inv_lap,
+                    int B, int M, int N, int nsteps, void* ws, size_t ws_bytes, void* stream);
+size_t rpde_grf2d_ws_bytes(int B, int M, int N);
+int rpde_grf2d(const float* noise, const float* sqrt_eig, float* out, int B, int M, int N,
+               void* ws, size_t ws_bytes, void* stream);
+
 /* ---- optimizer step: torch.optim.AdamW as built at main_1d.py:144 / main_2d.py:173 (decoupled weight decay,
  * bias-corrected moments, no amsgrad), one streaming kernel over flat fp32 buffers of n (multiple of 4) elements.
  * The caller passes the step's scalars: 1 - lr*wd, 1 - b1, b2, 1 - b2, lr / (1 - b1^t), sqrt(1 - b2^t), eps. */

@@ -18,6 +18,7 @@
 #include "pointwise.h"
 #include "cf_dft.h"
 #include "h2.h"
+#include "ns_solver.h"
 
 namespace rpde {
 
@@ -930,19 +931,26 @@ static Wl2Geom wl2_geom(int B, int C, int M, int N) {
   g.S = (int)((per + 2047) / 2048 < WL2_SLOTS ? (per + 2047) / 2048 : WL2_SLOTS);
   return g;
 }
-// the plans of rpde_resize1d / rpde_resize2d at equal sizes; pm stays null for M = 1
-static int wl2_plans(const rpde_plan** pn, const rpde_plan** pm, int M, int N, hipStream_t st) {
+// the plans of rpde_resize1d / rpde_resize2d at equal sizes; pm stays null for M = 1 (shared with ns_solver.hip)
+int wl2_plans(const rpde_plan** pn, const rpde_plan** pm, int M, int N, hipStream_t st) {
   RPDE_TRY(get_plan(pn, N, N / 2 + 1, RPDE_NORM_BACKWARD, 1, PLAN_REAL, st));
   *pm = nullptr;
   if (M > 1) RPDE_TRY(get_plan(pm, M, (M + 1) / 2, RPDE_NORM_BACKWARD, 0, PLAN_CPLX, st, M / 2));
   return RPDE_OK;
 }
 // z [rows, M, N] -> spec [rows][2M][kp]; s1: scratch of the same size (unused for M = 1)
-static int wl2_forward_dft(const rpde_plan* pn, const rpde_plan* pm, const float* z, float* s1, float* spec, long rows, int M,
-                           int N, hipStream_t st) {
+int wl2_forward_dft(const rpde_plan* pn, const rpde_plan* pm, const float* z, float* s1, float* spec, long rows, int M,
+                    int N, hipStream_t st) {
   if (!pm) return cf_analysis(pn, z, spec, rows, N, 0, st);
   RPDE_TRY(cf_analysis(pn, z, s1, rows * M, N, 0, st));
   return cf_rowdft(pm->fa, 2L * M, false, 2 * M, 2 * M, s1, spec, (int)rows, pn->kp, st);
+}
+// spec [rows][2M][kp] -> z [rows, M, N], 1 / (M N) from the plans' tables; t1: scratch of the spectrum's size (unused for M = 1)
+int wl2_inverse_dft(const rpde_plan* pn, const rpde_plan* pm, const float* spec, float* t1, float* z, long rows, int M, int N,
+                    hipStream_t st) {
+  if (!pm) return cf_synthesis(pn, spec, z, rows, N, st);
+  RPDE_TRY(cf_rowdft(pm->fs, 2L * M, false, 2 * M, 2 * M, spec, t1, (int)rows, pn->kp, st));
+  return cf_synthesis(pn, t1, z, rows * M, N, st);
 }
 
 }  // namespace rpde
@@ -1014,9 +1022,7 @@ int rpde_wrel_l2_bwd(const float* spec_d, const float* omega, const float* stats
   hipLaunchKernelGGL(k_wl2_weight, dim3((unsigned)nb, B), dim3(256), 0, st, spec_d, omega, stats, grad_loss, grad_rel, w, g,
                      size_average);
   RPDE_LAUNCH_CHECK();
-  if (!pm) return cf_synthesis(pn, w, grad_x, rows, N, st);
-  RPDE_TRY(cf_rowdft(pm->fs, 2L * M, false, 2 * M, 2 * M, w, t1, (int)rows, g.kp, st));
-  return cf_synthesis(pn, t1, grad_x, rows * M, N, st);
+  return wl2_inverse_dft(pn, pm, w, t1, grad_x, rows, M, N, st);
 }
 
 }  // extern "C"

@@ -1,0 +1,59 @@
+"""Gaussian random fields on the periodic unit square, sampled on the GPU (reference: data_generation/random_fields.py,
+whose sampler needs the removed torch.ifft).  Same constructor as the reference; only dim = 2 with periodic boundary is
+built here.
+
+    sqrt_eig[k] = size^2 sqrt(2) sigma (4 pi^2 |k|^2 + tau^2)^(-alpha/2),  0 at the mean mode,  sigma = tau^(alpha - 1)
+    sample      = Re ifft2(sqrt_eig . (xi_re + i xi_im)),  xi standard normal,  torch's 1/size^2 in the inverse
+
+The noise comes from torch.randn on the device; the transform is rpde.ops.grf2d (csrc/ns_solver.hip)."""
+from __future__ import annotations
+
+import math
+from typing import Optional
+
+import torch
+
+
+def sqrt_eig_2d(M: int, N: int, alpha: float, tau: float, sigma: float) -> torch.Tensor:
+    """float32 [M, N] host tensor, formed in float64 and rounded once; signed wavenumbers in fft order on both axes
+    (Nyquist -n/2); the factor M N is size^2 on the reference's square grid"""
+    k1 = (torch.fft.fftfreq(M, dtype=torch.float64) * M).round().view(M, 1)
+    k2 = (torch.fft.fftfreq(N, dtype=torch.float64) * N).round().view(1, N)
+    e = M * N * math.sqrt(2.0) * float(sigma) * (4.0 * math.pi ** 2 * (k1 ** 2 + k2 ** 2) + float(tau) ** 2) ** (-float(alpha) / 2.0)
+    e[0, 0] = 0.0
+    return e.to(torch.float32)
+
+
+class GaussianRF(object):
+
+    def __init__(self, dim, size, alpha=2, tau=3, sigma=None, boundary="periodic", device=None):
+        if dim != 2:
+            raise ValueError(f"GaussianRF: only dim=2 is built on the device (got dim={dim}); the 1-D and 3-D fields of "
+                             "the reference are not ported")
+        if boundary != "periodic":
+            raise ValueError(f"GaussianRF: only boundary='periodic' is supported (got {boundary!r})")
+        self.dim = dim
+        self.device = torch.device("cuda" if device is None else device)
+        if sigma is None:
+            sigma = tau ** (0.5 * (2 * alpha - self.dim))
+        self.alpha, self.tau, self.sigma = alpha, tau, sigma
+        self.size = (int(size), int(size))
+        self._sqrt_eig_host = sqrt_eig_2d(self.size[0], self.size[1], alpha, tau, sigma)
+        self._sqrt_eig = None
+
+    @property
+    def sqrt_eig(self) -> torch.Tensor:
+        """[size, size] fp32 on the device (moved there at first use)"""
+        if self._sqrt_eig is None:
+            self._sqrt_eig = self._sqrt_eig_host.to(self.device)
+        return self._sqrt_eig
+
+    def sample(self, N, generator: Optional[torch.Generator] = None, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """[N, size, size] samples.  The noise [N, size, size, 2] is drawn with torch.randn on the device (from
+        `generator`, a device generator, when given: equal seeds give equal samples) or passed in."""
+        from rpde import ops
+        if noise is None:
+            noise = torch.randn(int(N), *self.size, 2, device=self.device, dtype=torch.float32, generator=generator)
+        elif tuple(noise.shape) != (int(N), *self.size, 2):
+            raise ValueError(f"GaussianRF.sample: noise {tuple(noise.shape)}, expected {(int(N), *self.size, 2)}")
+        return ops.grf2d(noise.to(self.device), self.sqrt_eig)

@@ -140,6 +140,14 @@ _SIGNATURES = {
     "rpde_wrel_l2_spec_elems": (_Z, [_I, _I, _I, _I]),
     "rpde_wrel_l2_fwd": (_I, [_P] * 7 + [_I] * 5 + [_P, _Z, _P]),
     "rpde_wrel_l2_bwd": (_I, [_P] * 6 + [_I] * 5 + [_P, _Z, _P]),
+    "rpde_ns2d_ws_bytes": (_Z, [_I, _I, _I]),
+    "rpde_ns2d_spec_elems": (_Z, [_I, _I, _I]),
+    "rpde_ns2d_rfft2": (_I, [_P, _P, _I, _I, _I, _P, _Z, _P]),
+    "rpde_ns2d_irfft2": (_I, [_P, _P, _I, _I, _I, _P, _Z, _P]),
+    "rpde_ns2d_scale": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "rpde_ns2d_steps": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
+    "rpde_grf2d_ws_bytes": (_Z, [_I, _I, _I]),
+    "rpde_grf2d": (_I, [_P, _P, _P, _I, _I, _I, _P, _Z, _P]),
     "rpde_adamw_step": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _F, _F, _P]),
     "rpde_adamw_step_dev": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _P, _P]),
     "rpde_adamw_set_hyper_dev": (_I, [_P, _F, _F, _P]),

@@ -990,6 +990,102 @@ def freq_energy2d(pred: torch.Tensor, target: torch.Tensor, num_radial_bins: int
     return acc
 
 
+# ----------------------------------------------------------------------------
+# Navier-Stokes vorticity generator and its Gaussian random field (csrc/ns_solver.hip, rpde_ns2d_* / rpde_grf2d;
+# data_generation/ns_2d.py and random_fields.py are the callers).  Data production: no autograd, GPU tensors only,
+# no CPU fallback.
+# ----------------------------------------------------------------------------
+def ns2d_tables(M: int, N: int, visc: float, dt: float):
+    """(c_w, c_f, c_g, inv_lap): the step's coefficient tables, float32 [M, kp] host tensors (kp = N//2+1 rounded up to
+    4, padded columns zero), formed in float64 and rounded once.  k1 = fftfreq(M) M (signed, Nyquist -M/2),
+    k2 = 0 .. N/2, lap = 4 pi^2 (k1^2 + k2^2), a = dt visc lap / 2, dealias = |k1| <= (2/3)(M/2) and |k2| <= (2/3)(N/2):
+    c_w = (1 - a)/(1 + a), c_f = dt dealias/(1 + a), c_g = dt/(1 + a), inv_lap = 1/lap with the mean mode's lap set to
+    1 for this division only."""
+    import math
+    M, N = int(M), int(N)
+    K, kp = N // 2 + 1, (N // 2 + 1 + 3) // 4 * 4
+    k1 = (torch.fft.fftfreq(M, dtype=torch.float64) * M).round().view(M, 1)
+    k2 = torch.arange(K, dtype=torch.float64).view(1, K)
+    lap = 4.0 * math.pi ** 2 * (k1 ** 2 + k2 ** 2)
+    a = 0.5 * float(dt) * float(visc) * lap
+    dealias = ((k1.abs() <= (2.0 / 3.0) * (M // 2)) & (k2.abs() <= (2.0 / 3.0) * (N // 2))).to(torch.float64)
+    poisson = lap.clone()
+    poisson[0, 0] = 1.0
+    out = []
+    for t in ((1.0 - a) / (1.0 + a), float(dt) * dealias / (1.0 + a), float(dt) / (1.0 + a), 1.0 / poisson):
+        p = torch.zeros(M, kp, dtype=torch.float32)
+        p[:, :K] = t.to(torch.float32)
+        out.append(p)
+    return tuple(out)
+
+
+def _grid3(t: torch.Tensor, what: str):
+    if t.dim() != 3:
+        raise ValueError(f"{what}: expected [B, M, N], got {tuple(t.shape)}")
+    B, M, N = (int(v) for v in t.shape)
+    if load().rpde_ns2d_ws_bytes(B, M, N) == 0:
+        raise ValueError(f"{what}: unsupported grid B={B} M={M} N={N} (even axes 4 .. 4096)")
+    return B, M, N
+
+
+def grf2d(noise: torch.Tensor, sqrt_eig: torch.Tensor) -> torch.Tensor:
+    """noise [B, M, N, 2] (real and imaginary part of the coefficients of the full M x N grid, standard normal),
+    sqrt_eig [M, N] -> [B, M, N] = Re ifft2(sqrt_eig . noise), torch's 1/(M N) included.  The HIP side is deterministic
+    given the noise.  Contiguous fp32 tensors on the GPU; no autograd, no CPU fallback."""
+    lib = load()
+    if noise.dim() != 4 or noise.shape[-1] != 2 or tuple(sqrt_eig.shape) != tuple(noise.shape[1:3]):
+        raise ValueError(f"grf2d: noise {tuple(noise.shape)} / sqrt_eig {tuple(sqrt_eig.shape)}, expected [B, M, N, 2] and [M, N]")
+    noise, sqrt_eig = _f32c(noise.detach()), _f32c(sqrt_eig.detach())
+    pn, ps = ptr(noise), ptr(sqrt_eig)                     # raises for CPU tensors: there is no fallback
+    B, M, N = _grid3(noise[..., 0], "grf2d")
+    out = torch.empty(B, M, N, dtype=torch.float32, device=noise.device)
+    nws = lib.rpde_grf2d_ws_bytes(B, M, N)
+    ws = workspace(nws, noise.device)
+    check(lib.rpde_grf2d(pn, ps, ptr(out), B, M, N, ws.data_ptr(), nws, stream_ptr()), "grf2d")
+    return out
+
+
+def ns2d_solve(w0: torch.Tensor, f: torch.Tensor, visc: float, dt: float, steps: int, record_every: int) -> torch.Tensor:
+    """2-D Navier-Stokes in vorticity form on the periodic unit square from w0 [B, M, N] with forcing f ([M, N] for the
+    whole batch or [B, M, N]): `steps` pseudo-spectral steps of size dt (Crank-Nicolson diffusion, explicit advection and
+    forcing, 2/3 de-aliasing; include/rpde.h has the formulas), a snapshot after every `record_every`-th.  Returns
+    [B, M, N, steps // record_every].  Six launches per step, no host synchronisation between them.  Contiguous fp32
+    tensors on the GPU; no autograd, no CPU fallback."""
+    lib = load()
+    steps, record_every = int(steps), int(record_every)
+    if steps < 0 or record_every < 1:
+        raise ValueError(f"ns2d_solve: bad steps={steps} record_every={record_every}")
+    w0, f = _f32c(w0.detach()), _f32c(f.detach())
+    pw, _ = ptr(w0), ptr(f)                                # raises for CPU tensors: there is no fallback
+    B, M, N = _grid3(w0, "ns2d_solve")
+    if tuple(f.shape) not in ((M, N), (B, M, N)):
+        raise ValueError(f"ns2d_solve: forcing {tuple(f.shape)}, expected {(M, N)} or {(B, M, N)}")
+    fb = 1 if f.dim() == 2 else B
+    dev = w0.device
+    c_w, c_f, c_g, inv_lap = (t.to(dev) for t in ns2d_tables(M, N, visc, dt))
+    nws = lib.rpde_ns2d_ws_bytes(B, M, N)
+    ws = workspace(nws, dev)
+    st = stream_ptr()
+    W = torch.empty(lib.rpde_ns2d_spec_elems(B, M, N), dtype=torch.float32, device=dev)
+    check(lib.rpde_ns2d_rfft2(pw, ptr(W), B, M, N, ws.data_ptr(), nws, st), "ns2d_rfft2")
+    # g_h = dt / (1 + a) rfft2(f), once per solve.  The forcing is transformed one image at a time, so that a sample's
+    # forcing spectrum does not depend on the batch around it: f [M, N] and the same f repeated B times give the same bits
+    per = lib.rpde_ns2d_spec_elems(1, M, N)
+    f_h = torch.empty(fb * per, dtype=torch.float32, device=dev)
+    g_h = torch.empty_like(f_h)
+    f3 = f.view(fb, M, N)
+    for i in range(fb):
+        check(lib.rpde_ns2d_rfft2(ptr(f3[i]), ptr(f_h[i * per:(i + 1) * per]), 1, M, N, ws.data_ptr(), nws, st), "ns2d_rfft2")
+    check(lib.rpde_ns2d_scale(ptr(f_h), ptr(c_g), ptr(g_h), fb, M, N, st), "ns2d_scale")
+    n_rec = steps // record_every
+    snaps = torch.empty(max(n_rec, 1), B, M, N, dtype=torch.float32, device=dev)
+    for c in range(n_rec):
+        check(lib.rpde_ns2d_steps(ptr(W), ptr(g_h), int(f.dim() == 3), ptr(c_w), ptr(c_f), ptr(inv_lap), B, M, N,
+                                  record_every, ws.data_ptr(), nws, st), "ns2d_steps")
+        check(lib.rpde_ns2d_irfft2(ptr(W), ptr(snaps[c]), B, M, N, ws.data_ptr(), nws, st), "ns2d_irfft2")
+    return snaps[:n_rec].permute(1, 2, 3, 0).contiguous()
+
+
 def warm_plans(model, resolutions, dims: int, in_channels: int = 1, device="cuda") -> None:
     """Build every DFT plan (tables, adjoint tables, operand images: hipMalloc + one stream sync each,
     csrc/core.hip get_plan) and size the workspaces the model needs at the given grid resolutions, with one
