@@ -329,7 +329,8 @@ int rpde_transpose_cs(const float* in, float* out, int B, int64_t S, int C, int 
 
 /* ---- spectral resize: rfft -> shared bins -> irfft at the new size, x out/in
  * (reference: utils/res_utils.py:29-50 `resize`, :93-125 `resize_1d`; used by the
- * all-resolution evaluators, utils/naive_utils.py, utils/resize_utils.py).
+ * all-resolution evaluators, utils/naive_utils.py, utils/resize_utils.py;
+ * csrc/resize.hip on the transforms of csrc/cf_dft.h).
  * x [rows, n_in] -> out [rows, n_out];  x [rows, M, N] -> out [rows, Mo, No]. */
 size_t rpde_resize1d_ws_bytes(int64_t rows, int n_in, int n_out);
 int rpde_resize1d(const float* x, float* out, int64_t rows, int n_in, int n_out,
@@ -380,8 +381,8 @@ int rpde_rel_l2_bwd(const float* x, const float* y, const float* stats,
                     const float* grad_loss, const float* grad_rel, float* grad_x,
                     int B, int64_t per, int size_average, void* stream);
 
-/* ---- mode-weighted relative L2 loss (utils/loss.py SpectralRelativeL2Loss; an interface addition, the reference has
- * none).  x, y [B, C, M, N] fp32 channels-first, M = 1 for one-dimensional fields [B, C, N]; omega [M, N/2+1] >= 0, rows
+/* ---- mode-weighted relative L2 loss (csrc/spectral_loss.hip, utils/loss.py SpectralRelativeL2Loss; an interface
+ * addition, the reference has none).  x, y [B, C, M, N] fp32 channels-first, M = 1 for one-dimensional fields [B, C, N]; omega [M, N/2+1] >= 0, rows
  * in fft order.  With Z = rfft / rfft2 (unnormalised) and c_kx = 1 at kx = 0 and (even N) kx = N/2, else 2:
  *   E(z)[b] = sum_c sum_k omega_k c_kx / (M N) |Z[b,c,k]|^2,   rel[b] = sqrt(E(x - y)[b]) / (sqrt(E(y)[b]) + 1e-8);
  * x - y is formed in fp32 before the transform; the sums are float64, two deterministic stages without atomics.
@@ -391,7 +392,7 @@ int rpde_rel_l2_bwd(const float* x, const float* y, const float* stats,
  * E_d = 0, formed on the device; g_b = grad_rel[b], or grad_loss[0] (/ B when size_average) with grad_rel NULL.
  * No gradient for y.  In 2-D the columns kx = 0 and (even N) kx = N/2 of omega must be symmetric in ky
  * (omega[ky] == omega[(M - ky) % M]): the caller checks it.  Axes 2 .. 4096; the full-spectrum plans are those of the
- * resizers at equal sizes (first use of a grid allocates and synchronises).  Argument errors are reported before any
+ * resizers at equal sizes (cf_rfft2_plans, csrc/cf_dft.h; first use of a grid allocates and synchronises).  Argument errors are reported before any
  * device work. */
 size_t rpde_wrel_l2_ws_bytes(int B, int C, int M, int N);
 size_t rpde_wrel_l2_spec_elems(int B, int C, int M, int N);
@@ -402,7 +403,8 @@ int rpde_wrel_l2_bwd(const float* spec_d, const float* omega, const float* stats
                      void* ws, size_t ws_bytes, void* stream);
 
 /* ---- NS vorticity generator (reference: data_generation/ns_2d.py, random_fields.py): 2-D Navier-Stokes in vorticity
- * form on the periodic unit square, pseudo-spectral, and the Gaussian random field that seeds it (csrc/ns_solver.hip).
+ * form on the periodic unit square, pseudo-spectral, and the Gaussian random field that seeds it (csrc/ns_solver.hip, on the 2-D
+ * transforms of csrc/cf_dft.h).
  * Grids M x N, both axes even, 4 .. 4096.  A half spectrum is [images][M][re|im][kp] floats: rows ky in fft order
  * (signed k1 = ky < M/2 ? ky : ky - M), kx = k2 = 0 .. N/2 contiguous, kp = N/2+1 rounded up to 4, padded columns zero;
  * the spec_elems query gives the floats of B images.  The rfft2 / irfft2 calls are torch.fft.rfft2 (unnormalised) and

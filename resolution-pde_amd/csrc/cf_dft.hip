@@ -14,6 +14,7 @@
 // table fragments are built to match), so that a load instruction covers 64 contiguous bytes per line.
 #include "cf_dft.h"
 #include "h2.h"
+#include "pointwise.h"
 
 namespace rpde {
 
@@ -254,6 +255,103 @@ int cf_synthesis_h2(const rpde_plan* pl, int adjoint, const float* spec, float* 
   hipLaunchKernelGGL(k_cf_synthesis_h2, dim3(cf_grid(rows)), dim3(64 * CF_WAVES), 0, st, P);
   RPDE_LAUNCH_CHECK();
   return RPDE_OK;
+}
+
+// ---- host layer (cf_dft.h has what each routine computes) ----
+// Thin products -- a long reduction onto few output tiles (the 1-D layers at small batch: [1024 x 1024] . [1024 x 32]
+// is 8 workgroups) -- split the reduction over the grid into slabs and fold them in fixed order; `slabs` is the
+// caller's scratch of thin_slab_floats() entries (nullptr: never split).
+int thin_ksplit(long rows, int ncols, int kred) {
+  if (ncols > 32 || kred < 256) return 1;
+  const long tiles = (rows + 127) / 128;
+  if (tiles >= 64) return 1;
+  int ks = 1;
+  while (ks < 16 && tiles * ks < 64 && kred / (2 * ks) >= 64) ks *= 2;
+  return ks;
+}
+size_t thin_slab_floats(long rows, int ncols, int kred) {
+  const int ks = thin_ksplit(rows, ncols, kred);
+  return ks > 1 ? (size_t)ks * rows * ncols : 0;
+}
+int thin_gemm(rpde_gemm_desc& d, float* slabs, hipStream_t st) {
+  const int ks = slabs ? thin_ksplit(d.M, d.N, d.K) : 1;
+  if (ks == 1 || d.ldc != d.N) return launch_gemm(d, st);
+  float* out = d.C;
+  const float alpha = d.alpha;
+  d.C = slabs; d.ksplit = ks; d.sCk = (long)d.M * d.N; d.alpha = 1.f;
+  RPDE_TRY(launch_gemm(d, st));
+  return reduce_slabs(slabs, out, (long)d.M * d.N, ks, (long)d.M * d.N, alpha, 0, st);
+}
+
+int cf_analysis(const rpde_plan* pl, const float* x, float* spec, long rows, int n, int act_in, hipStream_t st, float* slabs) {
+  if (!act_in && pl->cf_ana[0] && rows >= 16 && cf_h2_eligible(n, 2 * pl->kp)) return cf_analysis_h2(pl, 0, x, spec, rows, 1.f, st);
+  rpde_gemm_desc d = gemm_desc();
+  d.A = x; d.a_kmajor = 1; d.lda = n; d.act_a = act_in;
+  d.B = pl->fa; d.b_kmajor = 1; d.ldb = pl->ldn;
+  d.C = spec; d.ldc = 2L * pl->kp;
+  d.M = (int)rows; d.N = 2 * pl->kp; d.K = n;
+  return thin_gemm(d, slabs, st);
+}
+int cf_synthesis(const rpde_plan* pl, const float* spec, float* out, long rows, int n, hipStream_t st, float alpha) {
+  if (pl->cf_syn[0] && rows >= 16 && cf_h2_syn_eligible(n, 2 * pl->kp)) return cf_synthesis_h2(pl, 0, spec, out, rows, alpha, st);
+  rpde_gemm_desc d = gemm_desc();
+  d.alpha = alpha;
+  d.A = spec; d.a_kmajor = 1; d.lda = 2L * pl->kp;
+  d.B = pl->fs; d.b_kmajor = 1; d.ldb = 2L * pl->kp;
+  d.C = out; d.ldc = n;
+  d.M = (int)rows; d.N = n; d.K = 2 * pl->kp;
+  return launch_gemm(d, st);
+}
+int cf_synthesis_T(const rpde_plan* pl, const float* g, float* gspec, long rows, int n, hipStream_t st, float* slabs) {
+  if (pl->cf_ana[1] && rows >= 16 && cf_h2_eligible(n, 2 * pl->kp)) return cf_analysis_h2(pl, 1, g, gspec, rows, 1.f, st);
+  rpde_gemm_desc d = gemm_desc();
+  d.A = g; d.a_kmajor = 1; d.lda = n;
+  d.B = pl->fs; d.b_kmajor = 0; d.ldb = 2L * pl->kp;
+  d.C = gspec; d.ldc = 2L * pl->kp;
+  d.M = (int)rows; d.N = 2 * pl->kp; d.K = n;
+  return thin_gemm(d, slabs, st);
+}
+int cf_analysis_T(const rpde_plan* pl, const float* dspec, float* gx, long rows, int n, int act_in, const float* x, hipStream_t st) {
+  if (!act_in && pl->cf_syn[1] && rows >= 16 && cf_h2_syn_eligible(n, 2 * pl->kp)) return cf_synthesis_h2(pl, 1, dspec, gx, rows, 1.f, st);
+  rpde_gemm_desc d = gemm_desc();
+  d.A = dspec; d.a_kmajor = 1; d.lda = 2L * pl->kp;
+  d.B = pl->fa; d.b_kmajor = 0; d.ldb = pl->ldn;
+  d.C = gx; d.ldc = n;
+  d.M = (int)rows; d.N = n; d.K = 2 * pl->kp;
+  if (act_in) { d.epi_dact = act_in; d.aux = x; d.ldaux = n; }
+  return launch_gemm(d, st);
+}
+
+int cf_rowdft(const float* table, long ld_table, bool transpose, int m_out, int k_red, const float* in, float* out,
+              int nblocks, int width, hipStream_t st) {
+  rpde_gemm_desc d = gemm_desc();
+  d.A = table; d.a_kmajor = transpose ? 0 : 1; d.lda = ld_table;
+  d.B = in; d.b_kmajor = 0; d.ldb = width;
+  d.C = out; d.ldc = width;
+  d.M = m_out; d.N = width; d.K = k_red;
+  d.batch = nblocks; d.sB1 = (long)k_red * width; d.sC1 = (long)m_out * width;
+  return launch_gemm(d, st);
+}
+
+// ---- real 2-D DFT: analysis along N, then the complex column DFT to the 2 pm->kp row slots the column plan keeps ----
+int cf_rfft2_plans(const rpde_plan** pn, const rpde_plan** pm, int M, int N, hipStream_t st) {
+  RPDE_TRY(get_plan(pn, N, N / 2 + 1, RPDE_NORM_BACKWARD, 1, PLAN_REAL, st));
+  *pm = nullptr;
+  if (M > 1) RPDE_TRY(get_plan(pm, M, (M + 1) / 2, RPDE_NORM_BACKWARD, 0, PLAN_CPLX, st, M / 2));
+  return RPDE_OK;
+}
+int cf_rfft2(const rpde_plan* pn, const rpde_plan* pm, const float* z, float* s1, float* spec, long rows, hipStream_t st) {
+  if (!pm) return cf_analysis(pn, z, spec, rows, pn->n, 0, st);
+  const int M = pm->n;
+  RPDE_TRY(cf_analysis(pn, z, s1, rows * M, pn->n, 0, st));
+  return cf_rowdft(pm->fa, 2L * M, false, 2 * pm->kp, 2 * M, s1, spec, (int)rows, pn->kp, st);
+}
+int cf_irfft2(const rpde_plan* pn, const rpde_plan* pm, const float* spec, float* t1, float* z, long rows, hipStream_t st,
+              float alpha) {
+  if (!pm) return cf_synthesis(pn, spec, z, rows, pn->n, st, alpha);
+  const int M = pm->n;
+  RPDE_TRY(cf_rowdft(pm->fs, 2L * pm->kp, false, 2 * M, 2 * pm->kp, spec, t1, (int)rows, pn->kp, st));
+  return cf_synthesis(pn, t1, z, rows * M, pn->n, st, alpha);
 }
 
 }  // namespace rpde

@@ -10,10 +10,11 @@
 //   k_ns_update_fanout   W <- c_w W - c_f F + g_h, and from the NEW W the four derivative spectra of the next step
 // with the coefficient tables formed by the caller in float64 and rounded to fp32 once:
 //   a = dt visc lap / 2,  c_w = (1 - a) / (1 + a),  c_f = dt dealias / (1 + a),  g_h = dt / (1 + a) f_h,  inv_lap = 1 / lap.
-// The transforms are the full-spectrum GEMM-form plans of the mode-weighted loss (spectral_cf.hip); everything else here
+// The transforms are the full-spectrum real 2-D DFT of cf_dft.h (cf_rfft2 / cf_irfft2, GEMM form); everything else here
 // streams: a thread owns one 16-byte group of kx for both re and im, so a wave covers whole 128-byte lines of every
 // array it reads or writes.  No atomics anywhere: identical calls give identical bits.
 #include "ns_solver.h"
+#include "cf_dft.h"
 #include "pointwise.h"
 
 namespace rpde {
@@ -186,8 +187,8 @@ int rpde_ns2d_rfft2(const float* w, float* W, int B, int M, int N, void* ws, siz
   if (!ar.ok()) { set_error("ns2d_rfft2: workspace too small"); return RPDE_ERR_WORKSPACE; }
   hipStream_t st = as_stream(stream);
   const rpde_plan *pn, *pm;
-  RPDE_TRY(wl2_plans(&pn, &pm, M, N, st));
-  return wl2_forward_dft(pn, pm, w, s1, W, B, M, N, st);
+  RPDE_TRY(cf_rfft2_plans(&pn, &pm, M, N, st));
+  return cf_rfft2(pn, pm, w, s1, W, B, st);
 }
 
 int rpde_ns2d_irfft2(const float* W, float* w, int B, int M, int N, void* ws, size_t ws_bytes, void* stream) {
@@ -199,8 +200,8 @@ int rpde_ns2d_irfft2(const float* W, float* w, int B, int M, int N, void* ws, si
   if (!ar.ok()) { set_error("ns2d_irfft2: workspace too small"); return RPDE_ERR_WORKSPACE; }
   hipStream_t st = as_stream(stream);
   const rpde_plan *pn, *pm;
-  RPDE_TRY(wl2_plans(&pn, &pm, M, N, st));
-  return wl2_inverse_dft(pn, pm, W, t1, w, B, M, N, st);
+  RPDE_TRY(cf_rfft2_plans(&pn, &pm, M, N, st));
+  return cf_irfft2(pn, pm, W, t1, w, B, st);
 }
 
 int rpde_ns2d_scale(const float* spec, const float* table, float* out, int B, int M, int N, void* stream) {
@@ -235,17 +236,17 @@ int rpde_ns2d_steps(float* W, const float* g_h, int g_batched, const float* c_w,
   if (nsteps == 0) return RPDE_OK;
   hipStream_t st = as_stream(stream);
   const rpde_plan *pn, *pm;
-  RPDE_TRY(wl2_plans(&pn, &pm, M, N, st));
+  RPDE_TRY(cf_rfft2_plans(&pn, &pm, M, N, st));
   const dim3 ug(ns_blocks((long)M * (g.kp / 4), 256), B);
   const long gstride = g_batched ? (long)M * 2 * g.kp : 0;
   const long n4 = (long)phys / 4;
   hipLaunchKernelGGL(k_ns_update_fanout<0>, ug, dim3(256), 0, st, W, F, g_h, gstride, c_w, c_f, inv_lap, D, g);
   RPDE_LAUNCH_CHECK();
   for (int j = 0; j < nsteps; ++j) {
-    RPDE_TRY(wl2_inverse_dft(pn, pm, D, T1, P, 4L * B, M, N, st));
+    RPDE_TRY(cf_irfft2(pn, pm, D, T1, P, 4L * B, st));
     hipLaunchKernelGGL(k_ns_advect, dim3(ns_blocks(n4, 2048)), dim3(256), 0, st, P, Fp, n4);
     RPDE_LAUNCH_CHECK();
-    RPDE_TRY(wl2_forward_dft(pn, pm, Fp, S1, F, B, M, N, st));
+    RPDE_TRY(cf_rfft2(pn, pm, Fp, S1, F, B, st));
     if (j + 1 < nsteps) hipLaunchKernelGGL(k_ns_update_fanout<1>, ug, dim3(256), 0, st, W, F, g_h, gstride, c_w, c_f, inv_lap, D, g);
     else hipLaunchKernelGGL(k_ns_update_fanout<2>, ug, dim3(256), 0, st, W, F, g_h, gstride, c_w, c_f, inv_lap, D, g);
     RPDE_LAUNCH_CHECK();
@@ -270,10 +271,10 @@ int rpde_grf2d(const float* noise, const float* sqrt_eig, float* out, int B, int
   if (!ar.ok()) { set_error("grf2d: workspace too small"); return RPDE_ERR_WORKSPACE; }
   hipStream_t st = as_stream(stream);
   const rpde_plan *pn, *pm;
-  RPDE_TRY(wl2_plans(&pn, &pm, M, N, st));
+  RPDE_TRY(cf_rfft2_plans(&pn, &pm, M, N, st));
   hipLaunchKernelGGL(k_grf_half, dim3(ns_blocks((long)M * g.kp, 256), B), dim3(256), 0, st, noise, sqrt_eig, h, g);
   RPDE_LAUNCH_CHECK();
-  return wl2_inverse_dft(pn, pm, h, t1, out, B, M, N, st);
+  return cf_irfft2(pn, pm, h, t1, out, B, st);
 }
 
 }  // extern "C"

@@ -12,13 +12,16 @@
 //
 // irfft2 = complex inverse over M then C2R over N, so Im(DC)/Im(Nyquist) along N
 // are ignored by the synthesis table exactly as torch does (quirk Q7).
+//
+// Here: the mode-mix kernel k_cmix, the two-launch column stage of the 2-D layer, the training entry points and the
+// evaluation entry points that hand the last transform to a fused tail (conv_small / conv_syn_h2 / conv_proj_h2.hip).
+// The transforms along the contiguous axis and the batched row DFT are the host layer of cf_dft.h.
 #include "rpde_internal.h"
 #include "plan.h"
 #include "conv_small.h"
 #include "pointwise.h"
 #include "cf_dft.h"
 #include "h2.h"
-#include "ns_solver.h"
 
 namespace rpde {
 
@@ -174,90 +177,6 @@ static int launch_mix(int which, const float* a, const float* b, const float* w1
 #undef RPDE_CMIX
   RPDE_LAUNCH_CHECK();
   return RPDE_OK;
-}
-
-// Thin products -- a long reduction onto few output tiles (the 1-D layers at small batch: [1024 x 1024] . [1024 x 32]
-// is 8 workgroups) -- split the reduction over the grid into slabs and fold them in fixed order; `slabs` is the
-// caller's scratch of thin_slab_floats() entries (nullptr: never split).
-static int thin_ksplit(long rows, int ncols, int kred) {
-  if (ncols > 32 || kred < 256) return 1;
-  const long tiles = (rows + 127) / 128;
-  if (tiles >= 64) return 1;
-  int ks = 1;
-  while (ks < 16 && tiles * ks < 64 && kred / (2 * ks) >= 64) ks *= 2;
-  return ks;
-}
-static size_t thin_slab_floats(long rows, int ncols, int kred) {
-  const int ks = thin_ksplit(rows, ncols, kred);
-  return ks > 1 ? (size_t)ks * rows * ncols : 0;
-}
-static int thin_gemm(rpde_gemm_desc& d, float* slabs, hipStream_t st) {
-  const int ks = slabs ? thin_ksplit(d.M, d.N, d.K) : 1;
-  if (ks == 1 || d.ldc != d.N) return launch_gemm(d, st);
-  float* out = d.C;
-  const float alpha = d.alpha;
-  d.C = slabs; d.ksplit = ks; d.sCk = (long)d.M * d.N; d.alpha = 1.f;
-  RPDE_TRY(launch_gemm(d, st));
-  return reduce_slabs(slabs, out, (long)d.M * d.N, ks, (long)d.M * d.N, alpha, 0, st);
-}
-
-// rows x n  ->  rows x 2kp   (forward real DFT along the contiguous axis), optional act on the input
-static int cf_analysis(const rpde_plan* pl, const float* x, float* spec, long rows, int n, int act_in, hipStream_t st,
-                       float* slabs = nullptr) {
-  if (!act_in && pl->cf_ana[0] && rows >= 16 && cf_h2_eligible(n, 2 * pl->kp)) return cf_analysis_h2(pl, 0, x, spec, rows, 1.f, st);
-  rpde_gemm_desc d = gemm_desc();
-  d.A = x; d.a_kmajor = 1; d.lda = n; d.act_a = act_in;
-  d.B = pl->fa; d.b_kmajor = 1; d.ldb = pl->ldn;
-  d.C = spec; d.ldc = 2L * pl->kp;
-  d.M = (int)rows; d.N = 2 * pl->kp; d.K = n;
-  return thin_gemm(d, slabs, st);
-}
-// rows x 2kp -> rows x n  (C2R synthesis)
-static int cf_synthesis(const rpde_plan* pl, const float* spec, float* out, long rows, int n, hipStream_t st,
-                        float alpha = 1.f) {
-  if (pl->cf_syn[0] && rows >= 16 && cf_h2_syn_eligible(n, 2 * pl->kp)) return cf_synthesis_h2(pl, 0, spec, out, rows, alpha, st);
-  rpde_gemm_desc d = gemm_desc();
-  d.alpha = alpha;
-  d.A = spec; d.a_kmajor = 1; d.lda = 2L * pl->kp;
-  d.B = pl->fs; d.b_kmajor = 1; d.ldb = 2L * pl->kp;
-  d.C = out; d.ldc = n;
-  d.M = (int)rows; d.N = n; d.K = 2 * pl->kp;
-  return launch_gemm(d, st);
-}
-// adjoint of synthesis: g[rows,n] . Fs -> [rows, 2kp]
-static int cf_synthesis_T(const rpde_plan* pl, const float* g, float* gspec, long rows, int n, hipStream_t st,
-                          float* slabs = nullptr) {
-  if (pl->cf_ana[1] && rows >= 16 && cf_h2_eligible(n, 2 * pl->kp)) return cf_analysis_h2(pl, 1, g, gspec, rows, 1.f, st);
-  rpde_gemm_desc d = gemm_desc();
-  d.A = g; d.a_kmajor = 1; d.lda = n;
-  d.B = pl->fs; d.b_kmajor = 0; d.ldb = 2L * pl->kp;
-  d.C = gspec; d.ldc = 2L * pl->kp;
-  d.M = (int)rows; d.N = 2 * pl->kp; d.K = n;
-  return thin_gemm(d, slabs, st);
-}
-// adjoint of analysis: dspec[rows,2kp] . Fa -> gx[rows,n], through act'(x) when act_in
-static int cf_analysis_T(const rpde_plan* pl, const float* dspec, float* gx, long rows, int n, int act_in, const float* x,
-                         hipStream_t st) {
-  if (!act_in && pl->cf_syn[1] && rows >= 16 && cf_h2_syn_eligible(n, 2 * pl->kp)) return cf_synthesis_h2(pl, 1, dspec, gx, rows, 1.f, st);
-  rpde_gemm_desc d = gemm_desc();
-  d.A = dspec; d.a_kmajor = 1; d.lda = 2L * pl->kp;
-  d.B = pl->fa; d.b_kmajor = 0; d.ldb = pl->ldn;
-  d.C = gx; d.ldc = n;
-  d.M = (int)rows; d.N = n; d.K = 2 * pl->kp;
-  if (act_in) { d.epi_dact = act_in; d.aux = x; d.ldaux = n; }
-  return launch_gemm(d, st);
-}
-
-// per (b,c) block GEMM with a shared [rowsA, colsA] table: out_z = T . in_z  (or T^T . in_z)
-static int cf_rowdft(const float* table, long ld_table, bool transpose, int m_out, int k_red, const float* in, float* out,
-                     int nblocks, int width, hipStream_t st) {
-  rpde_gemm_desc d = gemm_desc();
-  d.A = table; d.a_kmajor = transpose ? 0 : 1; d.lda = ld_table;
-  d.B = in; d.b_kmajor = 0; d.ldb = width;
-  d.C = out; d.ldc = width;
-  d.M = m_out; d.N = width; d.K = k_red;
-  d.batch = nblocks; d.sB1 = (long)k_red * width; d.sC1 = (long)m_out * width;
-  return launch_gemm(d, st);
 }
 
 // ---- column stage of SpectralConv2d in two launches (evaluation paths) ------------------------------------------
@@ -465,32 +384,18 @@ static int col_stage(const rpde_plan* pm, const float* s1, float* s2, const floa
                      const MixGeom& g, int M, hipStream_t st, const ColLift* lift = nullptr) {
   const int M2 = 2 * M, R2 = 2 * g.R;
   const size_t lds_a = sizeof(float) * (size_t)M2 * g.kp, lds_b = sizeof(float) * (size_t)R2 * g.kp;
-  const dim3 ga((unsigned)(g.B * g.Ci)), gb((unsigned)(g.B * g.Co)), bk(COL_THREADS);
+  const dim3 ga((unsigned)(g.B * g.Ci)), gb((unsigned)(g.B * g.Co));
   const dim3 bkm(g.R * g.kp > COL_THREADS ? COL_MIX_THREADS : COL_THREADS);
   const int wa = (R2 / 4 + 0) < 4 ? 4 : (R2 / 4 > COL_ANA_THREADS / 64 ? COL_ANA_THREADS / 64 : R2 / 4);
   const dim3 bka(64 * wa);
-  switch (g.kp) {
-    case 4:
-      if (lift) hipLaunchKernelGGL((k_col_analysis<4, true>), ga, bka, lds_a, st, pm->fa, s1, s2, M2, R2, *lift);
-      else hipLaunchKernelGGL((k_col_analysis<4, false>), ga, bka, lds_a, st, pm->fa, s1, s2, M2, R2, ColLift{});
-      hipLaunchKernelGGL((k_col_mix_synthesis<4>), gb, bkm, lds_b, st, s2, w1, w2, pm->fs_t, t1, g, M2);
-      break;
-    case 8:
-      if (lift) hipLaunchKernelGGL((k_col_analysis<8, true>), ga, bka, lds_a, st, pm->fa, s1, s2, M2, R2, *lift);
-      else hipLaunchKernelGGL((k_col_analysis<8, false>), ga, bka, lds_a, st, pm->fa, s1, s2, M2, R2, ColLift{});
-      hipLaunchKernelGGL((k_col_mix_synthesis<8>), gb, bkm, lds_b, st, s2, w1, w2, pm->fs_t, t1, g, M2);
-      break;
-    case 12:
-      if (lift) hipLaunchKernelGGL((k_col_analysis<12, true>), ga, bka, lds_a, st, pm->fa, s1, s2, M2, R2, *lift);
-      else hipLaunchKernelGGL((k_col_analysis<12, false>), ga, bka, lds_a, st, pm->fa, s1, s2, M2, R2, ColLift{});
-      hipLaunchKernelGGL((k_col_mix_synthesis<12>), gb, bkm, lds_b, st, s2, w1, w2, pm->fs_t, t1, g, M2);
-      break;
-    default:
-      if (lift) hipLaunchKernelGGL((k_col_analysis<16, true>), ga, bka, lds_a, st, pm->fa, s1, s2, M2, R2, *lift);
-      else hipLaunchKernelGGL((k_col_analysis<16, false>), ga, bka, lds_a, st, pm->fa, s1, s2, M2, R2, ColLift{});
-      hipLaunchKernelGGL((k_col_mix_synthesis<16>), gb, bkm, lds_b, st, s2, w1, w2, pm->fs_t, t1, g, M2);
-      break;
+#define RPDE_COL(KP)                                                                                                 \
+  {                                                                                                                  \
+    if (lift) hipLaunchKernelGGL((k_col_analysis<KP, true>), ga, bka, lds_a, st, pm->fa, s1, s2, M2, R2, *lift);     \
+    else hipLaunchKernelGGL((k_col_analysis<KP, false>), ga, bka, lds_a, st, pm->fa, s1, s2, M2, R2, ColLift{});     \
+    hipLaunchKernelGGL((k_col_mix_synthesis<KP>), gb, bkm, lds_b, st, s2, w1, w2, pm->fs_t, t1, g, M2);              \
   }
+  if (g.kp == 4) RPDE_COL(4) else if (g.kp == 8) RPDE_COL(8) else if (g.kp == 12) RPDE_COL(12) else RPDE_COL(16)
+#undef RPDE_COL
   RPDE_LAUNCH_CHECK();
   return RPDE_OK;
 }
@@ -555,7 +460,6 @@ int rpde_spectral1d_bwd(const float* grad_out, const float* spec_in, const float
 }
 
 // --------------------------------- 2-D --------------------------------------
-
 size_t rpde_spectral2d_spec_elems(int B, int Cin, int M, int N, int m1, int m2) {
   (void)M; (void)N;
   return (size_t)B * Cin * 2 * (2 * m1) * r4(m2);
@@ -569,35 +473,53 @@ size_t rpde_spectral2d_ws_bytes(int B, int Cin, int Cout, int M, int N, int m1, 
   return 2 * stage1 + 2 * small;
 }
 
-int rpde_spectral2d_fwd(const float* x, const float* w1, const float* w2, float* out, float* spec_in, int B, int Cin,
-                        int Cout, int M, int N, int m1, int m2, int act_in, void* ws, size_t ws_bytes, void* stream) {
-  RPDE_CHECK_ARG(x && w1 && w2 && out && spec_in && B > 0 && Cin > 0 && Cout > 0 && M > 0 && N > 0 && m1 > 0 && m2 > 0,
-                 "spectral2d_fwd: bad arguments");
-  if (m2 > N / 2 + 1 || m1 > M) {
-    set_error("SpectralConv2d: modes (%d,%d) exceed the spectrum (%d,%d)", m1, m2, M, N / 2 + 1);
-    return RPDE_ERR_MODES;
-  }
-  hipStream_t st = as_stream(stream);
+static bool modes_fit(int M, int N, int m1, int m2) { return m2 <= N / 2 + 1 && m1 <= M; }
+static int check_modes2d(int M, int N, int m1, int m2) {
+  if (modes_fit(M, N, m1, m2)) return RPDE_OK;
+  set_error("SpectralConv2d: modes (%d,%d) exceed the spectrum (%d,%d)", m1, m2, M, N / 2 + 1);
+  return RPDE_ERR_MODES;
+}
+
+// SpectralConv2d up to the row spectra: x [B,Ci,M,N] -> t1 [B*Co][2M][kp], ready for the synthesis along N with *pn.
+// The retained-mode spectra [B*Ci][2R][kp] go to `s2` (the training forward: the caller's spec_in, kept for the backward)
+// or, when s2 is null, to the workspace: rpde_spectral2d_ws_bytes above covers s1, t1 and o2 (and the backward's
+// four buffers), rpde_fnoblock2d_eval_ws_bytes adds the spectra.
+struct Rows2d { const rpde_plan* pn; float* t1; };
+static int spectral2d_rows(const char* who, const float* x, const float* w1, const float* w2, float* s2, int B, int Ci, int Co,
+                           int M, int N, int m1, int m2, int act_in, void* ws, size_t ws_bytes, hipStream_t st, Rows2d* out) {
   const rpde_plan *pn, *pm;
   RPDE_TRY(get_plan(&pn, N, m2, RPDE_NORM_BACKWARD, 1, PLAN_REAL, st));
   RPDE_TRY(get_plan(&pm, M, m1, RPDE_NORM_BACKWARD, 0, PLAN_CPLX, st));
   const int kp = pn->kp, R = 2 * m1;
   Arena ar(ws, ws_bytes);
-  float* s1 = ar.take((size_t)B * Cin * M * 2 * kp);
-  float* t1 = ar.take((size_t)B * Cout * M * 2 * kp);
-  float* o2 = ar.take((size_t)B * Cout * 2 * R * kp);
-  if (!ar.ok()) { set_error("spectral2d_fwd: workspace too small"); return RPDE_ERR_WORKSPACE; }
-  RPDE_TRY(cf_analysis(pn, x, s1, (long)B * Cin * M, N, act_in, st));
-  MixGeom g{B, Cin, Cout, R, m1, m2, kp};
+  float* s1 = ar.take((size_t)B * Ci * M * 2 * kp);
+  float* t1 = ar.take((size_t)B * Co * M * 2 * kp);
+  float* o2 = ar.take((size_t)B * Co * 2 * R * kp);
+  if (!s2) s2 = ar.take((size_t)B * Ci * 2 * R * kp);
+  if (!ar.ok()) { set_error("%s: workspace too small", who); return RPDE_ERR_WORKSPACE; }
+  RPDE_TRY(cf_analysis(pn, x, s1, (long)B * Ci * M, N, act_in, st));
+  MixGeom g{B, Ci, Co, R, m1, m2, kp};
   if (col_stage_ok(M, m1, kp, s1, t1)) {
-    RPDE_TRY(col_stage(pm, s1, spec_in, w1, w2, t1, g, M, st));
+    RPDE_TRY(col_stage(pm, s1, s2, w1, w2, t1, g, M, st));
   } else {
-    RPDE_TRY(cf_rowdft(pm->fa, 2L * M, false, 2 * R, 2 * M, s1, spec_in, B * Cin, kp, st));
-    if (kp != m2) RPDE_HIP(hipMemsetAsync(o2, 0, sizeof(float) * (size_t)B * Cout * 2 * R * kp, st));
-    RPDE_TRY(launch_mix(0, spec_in, nullptr, w1, w2, o2, nullptr, g, st));
-    RPDE_TRY(cf_rowdft(pm->fs, 2L * R, false, 2 * M, 2 * R, o2, t1, B * Cout, kp, st));
+    RPDE_TRY(cf_rowdft(pm->fa, 2L * M, false, 2 * R, 2 * M, s1, s2, B * Ci, kp, st));
+    if (kp != m2) RPDE_HIP(hipMemsetAsync(o2, 0, sizeof(float) * (size_t)B * Co * 2 * R * kp, st));
+    RPDE_TRY(launch_mix(0, s2, nullptr, w1, w2, o2, nullptr, g, st));
+    RPDE_TRY(cf_rowdft(pm->fs, 2L * R, false, 2 * M, 2 * R, o2, t1, B * Co, kp, st));
   }
-  return cf_synthesis(pn, t1, out, (long)B * Cout * M, N, st);
+  *out = Rows2d{pn, t1};
+  return RPDE_OK;
+}
+
+int rpde_spectral2d_fwd(const float* x, const float* w1, const float* w2, float* out, float* spec_in, int B, int Cin,
+                        int Cout, int M, int N, int m1, int m2, int act_in, void* ws, size_t ws_bytes, void* stream) {
+  RPDE_CHECK_ARG(x && w1 && w2 && out && spec_in && B > 0 && Cin > 0 && Cout > 0 && M > 0 && N > 0 && m1 > 0 && m2 > 0,
+                 "spectral2d_fwd: bad arguments");
+  RPDE_TRY(check_modes2d(M, N, m1, m2));
+  hipStream_t st = as_stream(stream);
+  Rows2d r;
+  RPDE_TRY(spectral2d_rows("spectral2d_fwd", x, w1, w2, spec_in, B, Cin, Cout, M, N, m1, m2, act_in, ws, ws_bytes, st, &r));
+  return cf_synthesis(r.pn, r.t1, out, (long)B * Cout * M, N, st);
 }
 
 // ---- evaluation-mode FNOBlock2d in the library: activation(SpectralConv2d(x) + bypass_conv(x)), reference
@@ -617,35 +539,15 @@ int rpde_fnoblock2d_eval_fwd(const float* x, const float* w1, const float* w2, c
                              void* stream) {
   RPDE_CHECK_ARG(x && w1 && w2 && wc && out && B > 0 && Cin > 0 && Cout > 0 && M > 0 && N > 0 && m1 > 0 && m2 > 0,
                  "fnoblock2d_eval_fwd: bad arguments");
-  if (m2 > N / 2 + 1 || m1 > M) {
-    set_error("SpectralConv2d: modes (%d,%d) exceed the spectrum (%d,%d)", m1, m2, M, N / 2 + 1);
-    return RPDE_ERR_MODES;
-  }
+  RPDE_TRY(check_modes2d(M, N, m1, m2));
   RPDE_CHECK_ARG(conv1x1_syn_ok(x, out, Cin, Cout, M, N, 2 * r4(m2)), "fnoblock2d_eval_fwd: shape not covered (%d -> %d on %d x %d)", Cin, Cout, M, N);
   hipStream_t st = as_stream(stream);
-  const rpde_plan *pn, *pm;
-  RPDE_TRY(get_plan(&pn, N, m2, RPDE_NORM_BACKWARD, 1, PLAN_REAL, st));
-  RPDE_TRY(get_plan(&pm, M, m1, RPDE_NORM_BACKWARD, 0, PLAN_CPLX, st));
-  const int kp = pn->kp, R = 2 * m1;
-  Arena ar(ws, ws_bytes);
-  float* s1 = ar.take((size_t)B * Cin * M * 2 * kp);
-  float* t1 = ar.take((size_t)B * Cout * M * 2 * kp);
-  float* o2 = ar.take((size_t)B * Cout * 2 * R * kp);
-  float* s2 = ar.take((size_t)B * Cin * 2 * R * kp);
-  if (!ar.ok()) { set_error("fnoblock2d_eval_fwd: workspace too small"); return RPDE_ERR_WORKSPACE; }
-  RPDE_TRY(cf_analysis(pn, x, s1, (long)B * Cin * M, N, 0, st));
-  MixGeom g{B, Cin, Cout, R, m1, m2, kp};
-  if (col_stage_ok(M, m1, kp, s1, t1)) {
-    RPDE_TRY(col_stage(pm, s1, s2, w1, w2, t1, g, M, st));
-  } else {
-    RPDE_TRY(cf_rowdft(pm->fa, 2L * M, false, 2 * R, 2 * M, s1, s2, B * Cin, kp, st));
-    if (kp != m2) RPDE_HIP(hipMemsetAsync(o2, 0, sizeof(float) * (size_t)B * Cout * 2 * R * kp, st));
-    RPDE_TRY(launch_mix(0, s2, nullptr, w1, w2, o2, nullptr, g, st));
-    RPDE_TRY(cf_rowdft(pm->fs, 2L * R, false, 2 * M, 2 * R, o2, t1, B * Cout, kp, st));
-  }
-  if (conv_syn_h2_ok(x, out, t1, Cin, Cout, M, N, 2 * kp))
-    return conv_syn_h2(x, wc, bc, t1, pn->fs_t, out, B, Cin, Cout, M, N, 2 * kp, act_out, st);
-  return conv1x1_syn(x, wc, bc, t1, pn->fs_t, out, B, Cin, Cout, M, N, 2 * kp, act_out, st);
+  Rows2d r;
+  RPDE_TRY(spectral2d_rows("fnoblock2d_eval_fwd", x, w1, w2, nullptr, B, Cin, Cout, M, N, m1, m2, 0, ws, ws_bytes, st, &r));
+  const int kp = r.pn->kp;
+  if (conv_syn_h2_ok(x, out, r.t1, Cin, Cout, M, N, 2 * kp))
+    return conv_syn_h2(x, wc, bc, r.t1, r.pn->fs_t, out, B, Cin, Cout, M, N, 2 * kp, act_out, st);
+  return conv1x1_syn(x, wc, bc, r.t1, r.pn->fs_t, out, B, Cin, Cout, M, N, 2 * kp, act_out, st);
 }
 
 // ---- the LAST block and the projection MLP in one entry point (evaluation): out = mlp2(gelu(mlp1(act(SpectralConv2d(x) +
@@ -654,7 +556,7 @@ int rpde_fnoblock2d_eval_fwd(const float* x, const float* w1, const float* w2, c
 // the block's output is never written.
 int rpde_fnoblock2d_proj_eval_ok(int Cin, int Cout, int M, int N, int m1, int m2, int Cmid, int Cq) {
   const int kp = r4(m2);
-  return m2 <= N / 2 + 1 && m1 <= M && conv_syn_proj_ok(Cin, Cout, M, N, 2 * kp, Cmid, Cq) ? 1 : 0;
+  return modes_fit(M, N, m1, m2) && conv_syn_proj_ok(Cin, Cout, M, N, 2 * kp, Cmid, Cq) ? 1 : 0;
 }
 
 int rpde_fnoblock2d_proj_eval_fwd(const float* x, const float* w1, const float* w2, const float* wc, const float* bc,
@@ -665,27 +567,9 @@ int rpde_fnoblock2d_proj_eval_fwd(const float* x, const float* w1, const float* 
   RPDE_CHECK_ARG(rpde_fnoblock2d_proj_eval_ok(Cin, Cout, M, N, m1, m2, Cmid, Cq), "fnoblock2d_proj_eval_fwd: shape not covered");
   RPDE_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & 15) == 0, "fnoblock2d_proj_eval_fwd: x must be 16-byte aligned");
   hipStream_t st = as_stream(stream);
-  const rpde_plan *pn, *pm;
-  RPDE_TRY(get_plan(&pn, N, m2, RPDE_NORM_BACKWARD, 1, PLAN_REAL, st));
-  RPDE_TRY(get_plan(&pm, M, m1, RPDE_NORM_BACKWARD, 0, PLAN_CPLX, st));
-  const int kp = pn->kp, R = 2 * m1;
-  Arena ar(ws, ws_bytes);
-  float* s1 = ar.take((size_t)B * Cin * M * 2 * kp);
-  float* t1 = ar.take((size_t)B * Cout * M * 2 * kp);
-  float* o2 = ar.take((size_t)B * Cout * 2 * R * kp);
-  float* s2 = ar.take((size_t)B * Cin * 2 * R * kp);
-  if (!ar.ok()) { set_error("fnoblock2d_proj_eval_fwd: workspace too small"); return RPDE_ERR_WORKSPACE; }
-  RPDE_TRY(cf_analysis(pn, x, s1, (long)B * Cin * M, N, 0, st));
-  MixGeom g{B, Cin, Cout, R, m1, m2, kp};
-  if (col_stage_ok(M, m1, kp, s1, t1)) {
-    RPDE_TRY(col_stage(pm, s1, s2, w1, w2, t1, g, M, st));
-  } else {
-    RPDE_TRY(cf_rowdft(pm->fa, 2L * M, false, 2 * R, 2 * M, s1, s2, B * Cin, kp, st));
-    if (kp != m2) RPDE_HIP(hipMemsetAsync(o2, 0, sizeof(float) * (size_t)B * Cout * 2 * R * kp, st));
-    RPDE_TRY(launch_mix(0, s2, nullptr, w1, w2, o2, nullptr, g, st));
-    RPDE_TRY(cf_rowdft(pm->fs, 2L * R, false, 2 * M, 2 * R, o2, t1, B * Cout, kp, st));
-  }
-  return conv_syn_proj(x, wc, bc, t1, pn->fs_t, pw1, pb1, pw2, pb2, out, B, Cout, M, N, 2 * kp, Cmid, Cq, act_out, st);
+  Rows2d r;
+  RPDE_TRY(spectral2d_rows("fnoblock2d_proj_eval_fwd", x, w1, w2, nullptr, B, Cin, Cout, M, N, m1, m2, 0, ws, ws_bytes, st, &r));
+  return conv_syn_proj(x, wc, bc, r.t1, r.pn->fs_t, pw1, pb1, pw2, pb2, out, B, Cout, M, N, 2 * r.pn->kp, Cmid, Cq, act_out, st);
 }
 
 // ---- evaluation-mode FNO2d: lifting + first block without the lifted field (reference models/fno.py:121-147:
@@ -699,7 +583,7 @@ size_t rpde_fno2d_lift_block_eval_ws_bytes(int B, int C, int Cout, int M, int N,
 int rpde_fno2d_lift_block_eval_ok(int Cu, int C, int Cout, int M, int N, int m1, int m2) {
   if (switch_off("RPDE_LIFT_FUSED")) return 0;
   const int kp = r4(m2);
-  return Cu == 1 && M <= 1024 && m2 <= N / 2 + 1 && m1 <= M && conv_syn_h2_ok(nullptr, nullptr, nullptr, C, Cout, M, N, 2 * kp) &&
+  return Cu == 1 && M <= 1024 && modes_fit(M, N, m1, m2) && conv_syn_h2_ok(nullptr, nullptr, nullptr, C, Cout, M, N, 2 * kp) &&
          col_stage_ok(M, m1, kp, nullptr, nullptr) ? 1 : 0;
 }
 
@@ -736,7 +620,7 @@ int rpde_spectral2d_bwd(const float* grad_out, const float* spec_in, const float
   RPDE_CHECK_ARG(grad_out && spec_in && w1 && w2 && B > 0 && Cin > 0 && Cout > 0 && M > 0 && N > 0 && m1 > 0 && m2 > 0,
                  "spectral2d_bwd: bad arguments");
   RPDE_CHECK_ARG(!act_in || x, "spectral2d_bwd: act_in needs x");
-  if (m2 > N / 2 + 1 || m1 > M) { set_error("SpectralConv2d: modes exceed the spectrum"); return RPDE_ERR_MODES; }
+  RPDE_TRY(check_modes2d(M, N, m1, m2));
   hipStream_t st = as_stream(stream);
   const rpde_plan *pn, *pm;
   RPDE_TRY(get_plan(&pn, N, m2, RPDE_NORM_BACKWARD, 1, PLAN_REAL, st));
@@ -759,270 +643,6 @@ int rpde_spectral2d_bwd(const float* grad_out, const float* spec_in, const float
     RPDE_TRY(cf_analysis_T(pn, ds1, grad_x, (long)B * Cin * M, N, act_in, x, st));
   }
   return RPDE_OK;
-}
-
-
-// ---- spectral resize (reference: utils/res_utils.py:29-50 `resize`, :93-125 `resize_1d`) ------------------
-// rfft -> keep the bins both sizes share -> irfft at the new size, times out/in: the same truncated-DFT
-// plans, analysis at the source size and synthesis at the target size.
-size_t rpde_resize1d_ws_bytes(int64_t rows, int n_in, int n_out) {
-  const int k = (n_in / 2 + 1) < (n_out / 2 + 1) ? (n_in / 2 + 1) : (n_out / 2 + 1);
-  return arena_bytes((size_t)rows * 2 * r4(k));
-}
-
-int rpde_resize1d(const float* x, float* out, int64_t rows, int n_in, int n_out, void* ws, size_t ws_bytes, void* stream) {
-  RPDE_CHECK_ARG(x && out && rows > 0 && n_in > 0 && n_out > 0 && rows < (1L << 31), "resize1d: bad arguments");
-  hipStream_t st = as_stream(stream);
-  const int k = (n_in / 2 + 1) < (n_out / 2 + 1) ? (n_in / 2 + 1) : (n_out / 2 + 1);
-  const rpde_plan *pa, *ps;
-  RPDE_TRY(get_plan(&pa, n_in, k, RPDE_NORM_BACKWARD, 1, PLAN_REAL, st));
-  RPDE_TRY(get_plan(&ps, n_out, k, RPDE_NORM_BACKWARD, 1, PLAN_REAL, st));
-  Arena ar(ws, ws_bytes);
-  float* spec = ar.take((size_t)rows * 2 * pa->kp);
-  if (!ar.ok()) { set_error("resize1d: workspace too small"); return RPDE_ERR_WORKSPACE; }
-  RPDE_TRY(cf_analysis(pa, x, spec, rows, n_in, 0, st));
-  return cf_synthesis(ps, spec, out, rows, n_out, st, (float)((double)n_out / (double)n_in));
-}
-
-size_t rpde_resize2d_ws_bytes(int64_t rows, int M, int N, int Mo, int No) {
-  const int k2 = (N / 2 + 1) < (No / 2 + 1) ? (N / 2 + 1) : (No / 2 + 1);
-  const int top = ((M + 1) / 2) < ((Mo + 1) / 2) ? (M + 1) / 2 : (Mo + 1) / 2;
-  const int bot = (M / 2) < (Mo / 2) ? M / 2 : Mo / 2;
-  const int mm = M > Mo ? M : Mo;
-  return 2 * arena_bytes((size_t)rows * mm * 2 * r4(k2)) + arena_bytes((size_t)rows * 2 * (top + bot) * r4(k2));
-}
-
-// x [rows, M, N] -> out [rows, Mo, No]  (rows = batch * channels)
-int rpde_resize2d(const float* x, float* out, int64_t rows, int M, int N, int Mo, int No, void* ws, size_t ws_bytes,
-                  void* stream) {
-  RPDE_CHECK_ARG(x && out && rows > 0 && M > 0 && N > 0 && Mo > 0 && No > 0 && rows * (long)(M > Mo ? M : Mo) < (1L << 31),
-                 "resize2d: bad arguments");
-  hipStream_t st = as_stream(stream);
-  const int k2 = (N / 2 + 1) < (No / 2 + 1) ? (N / 2 + 1) : (No / 2 + 1);
-  const int top = ((M + 1) / 2) < ((Mo + 1) / 2) ? (M + 1) / 2 : (Mo + 1) / 2;
-  const int bot = (M / 2) < (Mo / 2) ? M / 2 : Mo / 2;
-  const int R = top + bot;
-  const rpde_plan *pn, *pno, *pm, *pmo;
-  RPDE_TRY(get_plan(&pn, N, k2, RPDE_NORM_BACKWARD, 1, PLAN_REAL, st));
-  RPDE_TRY(get_plan(&pno, No, k2, RPDE_NORM_BACKWARD, 1, PLAN_REAL, st));
-  RPDE_TRY(get_plan(&pm, M, top, RPDE_NORM_BACKWARD, 0, PLAN_CPLX, st, bot));
-  RPDE_TRY(get_plan(&pmo, Mo, top, RPDE_NORM_BACKWARD, 0, PLAN_CPLX, st, bot));
-  const int kp = pn->kp;
-  const int mm = M > Mo ? M : Mo;
-  Arena ar(ws, ws_bytes);
-  float* s1 = ar.take((size_t)rows * mm * 2 * kp);
-  float* t1 = ar.take((size_t)rows * mm * 2 * kp);
-  float* s2 = ar.take((size_t)rows * 2 * R * kp);
-  if (!ar.ok()) { set_error("resize2d: workspace too small"); return RPDE_ERR_WORKSPACE; }
-  RPDE_TRY(cf_analysis(pn, x, s1, rows * M, N, 0, st));
-  RPDE_TRY(cf_rowdft(pm->fa, 2L * M, false, 2 * R, 2 * M, s1, s2, (int)rows, kp, st));
-  RPDE_TRY(cf_rowdft(pmo->fs, 2L * R, false, 2 * Mo, 2 * R, s2, t1, (int)rows, kp, st));
-  const double scale = ((double)Mo / M) * ((double)No / N);
-  return cf_synthesis(pno, t1, out, rows * Mo, No, st, (float)scale);
-}
-
-}  // extern "C"
-
-// ---- mode-weighted relative L2 loss (utils/loss.py SpectralRelativeL2Loss; no counterpart in the reference) ------
-//   E(z)[b] = sum_c sum_k  omega_k c_kx / (M N) |Z[b,c,k]|^2,   Z = rfft / rfft2 of z, unnormalised,
-//   rel[b]  = sqrt(E(x - y)[b]) / (sqrt(E(y)[b]) + 1e-8),        c_kx = 1 at kx = 0 and (even N) kx = N/2, else 2
-// on the full-spectrum plans of the resizers (equal input and output size): analysis along N, for M > 1 the complex
-// column DFT keeping every row in fft order.  A spectrum is [B*C][M][re|im][kp] (kp = N/2+1 rounded up to 4; the plan's
-// table rows past N/2 are zero).  The small kernels around the transforms:
-//   k_wl2_diff     d = x - y in fp32 BEFORE the transform (freq_energy.hip has the reason: for a decent model the
-//                  difference of two spectra loses the digits, the spectrum of the difference does not)
-//   k_wl2_energy   omega_k c_kx |Z|^2 summed per (field, sample, slot) in float64; k_wl2_final adds the slots in fixed
-//                  order -- the k_rel_l2_partial / k_rel_l2_final pattern, no atomics: identical calls, identical bits
-//   k_wl2_weight   backward: coef_b omega_k D, coef_b = g_b / (sqrt(E_d) (sqrt(E_y) + 1e-8)) formed from the saved
-//                  stats and the upstream gradient on the device (0 where E_d = 0, as k_rel_l2_bwd), then the inverse
-//                  half of the resizer: d rel[b] / d x = coef_b irfft(omega . rfft(x - y))
-namespace rpde {
-
-constexpr int WL2_SLOTS = 32;        // partial sums per (field, sample) at most
-constexpr int WL2_MAX_N = 4096;      // per axis: the full-spectrum tables are quadratic in it
-
-__global__ __launch_bounds__(256) void k_wl2_diff(const float* __restrict__ x, const float* __restrict__ y, float* __restrict__ d,
-                                                  long n, int vec) {
-  const long i0 = (long)blockIdx.x * 256 + threadIdx.x, step = (long)gridDim.x * 256;
-  if (vec) {
-    for (long i = i0; i < n / 4; i += step) {
-      const float4 a = reinterpret_cast<const float4*>(x)[i], b = reinterpret_cast<const float4*>(y)[i];
-      reinterpret_cast<float4*>(d)[i] = make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w);
-    }
-  } else {
-    for (long i = i0; i < n; i += step) d[i] = x[i] - y[i];
-  }
-}
-
-struct Wl2Geom { int B, C, M, N, K, kp, S; };
-
-__device__ __forceinline__ float wl2_mult(int kx, int N) { return (kx == 0 || (N % 2 == 0 && kx == N / 2)) ? 1.f : 2.f; }
-
-// grid (S, B, 2): field 0 = spectrum of x - y, field 1 = spectrum of y; part[(f B + b) S + slot]
-__global__ __launch_bounds__(256) void k_wl2_energy(const float* __restrict__ sd, const float* __restrict__ sy,
-                                                    const float* __restrict__ omega, double* __restrict__ part, Wl2Geom g) {
-  __shared__ double red[4];
-  const int b = blockIdx.y, f = blockIdx.z;
-  const long per = (long)g.C * g.M * 2 * g.kp;
-  const float* __restrict__ sp = (f ? sy : sd) + (long)b * per;
-  double acc = 0.0;
-  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < per; e += (long)gridDim.x * 256) {
-    const int kx = (int)(e % g.kp);
-    if (kx >= g.K) continue;
-    const int ky = (int)((e / (2L * g.kp)) % g.M);
-    const float v = sp[e];
-    acc += (double)(omega[(long)ky * g.K + kx] * wl2_mult(kx, g.N)) * ((double)v * (double)v);
-  }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) part[((long)f * g.B + b) * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// one workgroup: stats[b] = (sqrt E_d, sqrt E_y), rel[b], loss = mean / sum
-__global__ __launch_bounds__(256) void k_wl2_final(const double* __restrict__ part, float* __restrict__ rel, float* __restrict__ loss,
-                                                   float* __restrict__ stats, Wl2Geom g, int size_average) {
-  __shared__ double red[256];
-  const double inv = 1.0 / ((double)g.M * (double)g.N);
-  double acc = 0.0;
-  for (int b = threadIdx.x; b < g.B; b += 256) {
-    double ed = 0.0, ey = 0.0;
-    for (int j = 0; j < g.S; ++j) { ed += part[(long)b * g.S + j]; ey += part[((long)g.B + b) * g.S + j]; }
-    const float dn = (float)sqrt(ed * inv), yn = (float)sqrt(ey * inv);
-    const float r = dn / (yn + 1e-8f);
-    stats[2 * b] = dn; stats[2 * b + 1] = yn;
-    if (rel) rel[b] = r;
-    acc += (double)r;
-  }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && loss) *loss = (float)(size_average ? red[0] / g.B : red[0]);
-}
-
-// grid (blocks, B): w[b] = coef_b omega D[b]; the padded columns (kx >= K) are written as zeros
-__global__ __launch_bounds__(256) void k_wl2_weight(const float* __restrict__ sd, const float* __restrict__ omega,
-                                                    const float* __restrict__ stats, const float* __restrict__ grad_loss,
-                                                    const float* __restrict__ grad_rel, float* __restrict__ w, Wl2Geom g,
-                                                    int size_average) {
-  const int b = blockIdx.y;
-  const float dn = stats[2 * b], yn = stats[2 * b + 1];
-  const float gr = grad_rel ? grad_rel[b] : (size_average ? grad_loss[0] / g.B : grad_loss[0]);
-  const float coef = dn > 0.f ? gr / (dn * (yn + 1e-8f)) : 0.f;
-  const long per = (long)g.C * g.M * 2 * g.kp;
-  const float* __restrict__ sp = sd + (long)b * per;
-  float* __restrict__ wp = w + (long)b * per;
-  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < per; e += (long)gridDim.x * 256) {
-    const int kx = (int)(e % g.kp);
-    const int ky = (int)((e / (2L * g.kp)) % g.M);
-    wp[e] = kx < g.K ? (coef * omega[(long)ky * g.K + kx]) * sp[e] : 0.f;
-  }
-}
-
-static bool wl2_dims_ok(int B, int C, int M, int N) {
-  return B > 0 && C > 0 && M >= 1 && N >= 2 && M <= WL2_MAX_N && N <= WL2_MAX_N && (long)B * C * M < (1L << 31);
-}
-static Wl2Geom wl2_geom(int B, int C, int M, int N) {
-  Wl2Geom g{B, C, M, N, N / 2 + 1, r4(N / 2 + 1), 1};
-  const long per = (long)C * M * 2 * g.kp;
-  g.S = (int)((per + 2047) / 2048 < WL2_SLOTS ? (per + 2047) / 2048 : WL2_SLOTS);
-  return g;
-}
-// the plans of rpde_resize1d / rpde_resize2d at equal sizes; pm stays null for M = 1 (shared with ns_solver.hip)
-int wl2_plans(const rpde_plan** pn, const rpde_plan** pm, int M, int N, hipStream_t st) {
-  RPDE_TRY(get_plan(pn, N, N / 2 + 1, RPDE_NORM_BACKWARD, 1, PLAN_REAL, st));
-  *pm = nullptr;
-  if (M > 1) RPDE_TRY(get_plan(pm, M, (M + 1) / 2, RPDE_NORM_BACKWARD, 0, PLAN_CPLX, st, M / 2));
-  return RPDE_OK;
-}
-// z [rows, M, N] -> spec [rows][2M][kp]; s1: scratch of the same size (unused for M = 1)
-int wl2_forward_dft(const rpde_plan* pn, const rpde_plan* pm, const float* z, float* s1, float* spec, long rows, int M,
-                    int N, hipStream_t st) {
-  if (!pm) return cf_analysis(pn, z, spec, rows, N, 0, st);
-  RPDE_TRY(cf_analysis(pn, z, s1, rows * M, N, 0, st));
-  return cf_rowdft(pm->fa, 2L * M, false, 2 * M, 2 * M, s1, spec, (int)rows, pn->kp, st);
-}
-// spec [rows][2M][kp] -> z [rows, M, N], 1 / (M N) from the plans' tables; t1: scratch of the spectrum's size (unused for M = 1)
-int wl2_inverse_dft(const rpde_plan* pn, const rpde_plan* pm, const float* spec, float* t1, float* z, long rows, int M, int N,
-                    hipStream_t st) {
-  if (!pm) return cf_synthesis(pn, spec, z, rows, N, st);
-  RPDE_TRY(cf_rowdft(pm->fs, 2L * M, false, 2 * M, 2 * M, spec, t1, (int)rows, pn->kp, st));
-  return cf_synthesis(pn, t1, z, rows * M, N, st);
-}
-
-}  // namespace rpde
-
-extern "C" {
-
-size_t rpde_wrel_l2_spec_elems(int B, int C, int M, int N) {
-  if (!wl2_dims_ok(B, C, M, N)) return 0;
-  return (size_t)B * C * M * 2 * r4(N / 2 + 1);
-}
-
-size_t rpde_wrel_l2_ws_bytes(int B, int C, int M, int N) {
-  if (!wl2_dims_ok(B, C, M, N)) return 0;
-  const size_t spec = rpde_wrel_l2_spec_elems(B, C, M, N);
-  // forward: the difference, the target's spectrum, the row spectra, the partial sums (doubles); the backward needs less
-  return arena_bytes((size_t)B * C * M * N) + 2 * arena_bytes(spec) + arena_bytes((size_t)2 * 2 * B * WL2_SLOTS);
-}
-
-int rpde_wrel_l2_fwd(const float* x, const float* y, const float* omega, float* rel, float* loss, float* stats, float* spec_d,
-                     int B, int C, int M, int N, int size_average, void* ws, size_t ws_bytes, void* stream) {
-  RPDE_CHECK_ARG(x && y && omega && stats && spec_d && ws, "wrel_l2_fwd: null pointer");
-  RPDE_CHECK_ARG(wl2_dims_ok(B, C, M, N), "wrel_l2_fwd: bad B=%d C=%d M=%d N=%d (axes 2 .. %d; M = 1: one-dimensional)", B, C, M, N,
-                 WL2_MAX_N);
-  const Wl2Geom g = wl2_geom(B, C, M, N);
-  const long rows = (long)B * C;
-  const size_t spec = (size_t)rows * M * 2 * g.kp;
-  Arena ar(ws, ws_bytes);
-  float* d = ar.take((size_t)rows * M * N);
-  float* sy = ar.take(spec);
-  float* s1 = ar.take(spec);
-  double* part = reinterpret_cast<double*>(ar.take((size_t)2 * 2 * B * WL2_SLOTS));
-  if (!ar.ok()) { set_error("wrel_l2_fwd: workspace too small"); return RPDE_ERR_WORKSPACE; }
-  hipStream_t st = as_stream(stream);
-  const rpde_plan *pn, *pm;
-  RPDE_TRY(wl2_plans(&pn, &pm, M, N, st));
-  const long total = rows * M * N;
-  const int vec = total % 4 == 0 && al16(x) && al16(y) && al16(d);
-  long nb = ((vec ? total / 4 : total) + 255) / 256;
-  if (nb > 2048) nb = 2048;
-  hipLaunchKernelGGL(k_wl2_diff, dim3((unsigned)nb), dim3(256), 0, st, x, y, d, total, vec);
-  RPDE_LAUNCH_CHECK();
-  RPDE_TRY(wl2_forward_dft(pn, pm, d, s1, spec_d, rows, M, N, st));
-  RPDE_TRY(wl2_forward_dft(pn, pm, y, s1, sy, rows, M, N, st));
-  hipLaunchKernelGGL(k_wl2_energy, dim3(g.S, B, 2), dim3(256), 0, st, spec_d, sy, omega, part, g);
-  RPDE_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_wl2_final, dim3(1), dim3(256), 0, st, part, rel, loss, stats, g, size_average);
-  RPDE_LAUNCH_CHECK();
-  return RPDE_OK;
-}
-
-int rpde_wrel_l2_bwd(const float* spec_d, const float* omega, const float* stats, const float* grad_loss, const float* grad_rel,
-                     float* grad_x, int B, int C, int M, int N, int size_average, void* ws, size_t ws_bytes, void* stream) {
-  RPDE_CHECK_ARG(spec_d && omega && stats && grad_x && ws && (grad_loss || grad_rel), "wrel_l2_bwd: null pointer");
-  RPDE_CHECK_ARG(wl2_dims_ok(B, C, M, N), "wrel_l2_bwd: bad B=%d C=%d M=%d N=%d (axes 2 .. %d; M = 1: one-dimensional)", B, C, M, N,
-                 WL2_MAX_N);
-  const Wl2Geom g = wl2_geom(B, C, M, N);
-  const long rows = (long)B * C;
-  const size_t spec = (size_t)rows * M * 2 * g.kp;
-  Arena ar(ws, ws_bytes);
-  float* w = ar.take(spec);
-  float* t1 = ar.take(spec);
-  if (!ar.ok()) { set_error("wrel_l2_bwd: workspace too small"); return RPDE_ERR_WORKSPACE; }
-  hipStream_t st = as_stream(stream);
-  const rpde_plan *pn, *pm;
-  RPDE_TRY(wl2_plans(&pn, &pm, M, N, st));
-  const long per = (long)C * M * 2 * g.kp;
-  long nb = (per + 1023) / 1024;
-  if (nb > 256) nb = 256;
-  hipLaunchKernelGGL(k_wl2_weight, dim3((unsigned)nb, B), dim3(256), 0, st, spec_d, omega, stats, grad_loss, grad_rel, w, g,
-                     size_average);
-  RPDE_LAUNCH_CHECK();
-  return wl2_inverse_dft(pn, pm, w, t1, grad_x, rows, M, N, st);
 }
 
 }  // extern "C"

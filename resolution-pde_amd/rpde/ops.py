@@ -803,7 +803,7 @@ def relative_l2(x, y, size_average: bool = True, reduction: bool = True):
 
 
 # ----------------------------------------------------------------------------
-# mode-weighted relative L2 loss (csrc/spectral_cf.hip, rpde_wrel_l2_*; utils/loss.py SpectralRelativeL2Loss)
+# mode-weighted relative L2 loss (csrc/spectral_loss.hip, rpde_wrel_l2_*; utils/loss.py SpectralRelativeL2Loss)
 # ----------------------------------------------------------------------------
 class _WRelL2(torch.autograd.Function):
     @staticmethod
@@ -857,7 +857,7 @@ def weighted_relative_l2(x, y, omega, dims: int, size_average: bool = True, redu
 
 
 # ----------------------------------------------------------------------------
-# spectral resize (evaluation-time data path; no autograd)
+# spectral resize (csrc/resize.hip; evaluation-time data path, no autograd)
 # ----------------------------------------------------------------------------
 def resize1d(x: torch.Tensor, out_size: int) -> torch.Tensor:
     """x [..., n] -> [..., out_size]: rfft, keep the shared bins, irfft(out_size), times out/in"""

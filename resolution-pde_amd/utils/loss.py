@@ -4,7 +4,7 @@ prediction and target (wavefront-shuffle reductions, deterministic).
 
 SpectralRelativeL2Loss (no counterpart in the reference): the same ratio with a non-negative weight per Fourier
 mode -- the H^s / Sobolev relative loss of operator learning is the preset -- forward and backward on the device
-(rpde.ops.weighted_relative_l2, csrc/spectral_cf.hip)."""
+(rpde.ops.weighted_relative_l2, csrc/spectral_loss.hip)."""
 from __future__ import annotations
 
 import math

@@ -415,6 +415,20 @@ def test_last_block_and_projection_in_one_pass(gpu_device, shape, act):
     assert got.shape == (B, Cq, M, N)
     assert float((got.cpu().double() - ref).norm() / ref.norm()) < 2e-6
     assert float((got - two).norm() / two.norm()) < 2e-6
+    if shape == (2, 17, 5, 64, 2, 3, 24, 4):
+        # this entry point's three GEMM-shaped steps in place of the column stage; m2 = 3 -> kp = 4: the padded modes are zeroed
+        oldc = os.environ.get("RPDE_COL_FUSED")
+        os.environ["RPDE_COL_FUSED"] = "0"
+        try:
+            with torch.no_grad():
+                gemm_leg = ops.fnoblock2d_proj_eval(x, w1, w2, wc, bc, act, p1, q1, p2, q2)
+        finally:
+            if oldc is None:
+                os.environ.pop("RPDE_COL_FUSED")
+            else:
+                os.environ["RPDE_COL_FUSED"] = oldc
+        assert gemm_leg is not None
+        assert float((got - gemm_leg).norm() / gemm_leg.norm()) < 2e-6
 
 
 def test_fused_evaluation_fnoblock2d_narrow_grid_takes_the_two_step_path(gpu_device):

@@ -1,4 +1,4 @@
-"""GPU: the mode-weighted relative L2 loss (csrc/spectral_cf.hip rpde_wrel_l2_* -> rpde.ops.weighted_relative_l2 ->
+"""GPU: the mode-weighted relative L2 loss (csrc/spectral_loss.hip rpde_wrel_l2_* -> rpde.ops.weighted_relative_l2 ->
 utils.loss.SpectralRelativeL2Loss) against the float64 restatement of tests/spectral_loss_ref.py.
 
 Tolerances are the project's parity budgets: 1e-5 on the loss (rel-L2 over the per-sample vector), 2e-5 on the gradient
