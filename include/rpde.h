@@ -435,6 +435,41 @@ size_t rpde_grf2d_ws_bytes(int B, int M, int N);
 int rpde_grf2d(const float* noise, const float* sqrt_eig, float* out, int B, int M, int N,
                void* ws, size_t ws_bytes, void* stream);
 
+/* ---- 1-D exponential-time-differencing generator (csrc/etd1d.hip, on the 1-D transforms of csrc/cf_dft.h): every
+ * equation u_t = L u - (c/2) (u^2)_x on a periodic domain of length len -- Burgers (L = nu_eff d_xx) and
+ * Kuramoto-Sivashinsky (L = -d_xx - nu d_xxxx) -- and the 1-D Gaussian random field.
+ * Grid N even, 4 .. 4096.  A half spectrum is [images][re|im][kp] floats, k = 0 .. N/2 contiguous, kp = N/2+1 rounded
+ * up to 4, padded columns zero; the spec_elems query gives the floats of B images.  The rfft / irfft calls are
+ * torch.fft.rfft (unnormalised) and irfft (1 / N; Im of the mean and Nyquist bins ignored) between u [B, N] and that
+ * layout.  With kappa_n = 2 pi n / len, the symbol l_n = c2 kappa_n^2 + c4 kappa_n^4 and the step h, the caller forms
+ * seven tables [kp] (padded entries zero) in float64 and rounds them to fp32 once -- ETDRK4 in the Kassam-Trefethen
+ * form, z = h l_n, LR = z + r_m, r_m = exp(i pi (m - 1/2) / 32), m = 1 .. 32, <.> the mean over m:
+ *   E  = e^z,  E2 = e^(z/2),  Q = h Re<(e^(LR/2) - 1) / LR>,
+ *   f1 = h Re<(-4 - LR + e^LR (4 - 3 LR + LR^2)) / LR^3>,  f2 = h Re<(2 + LR + e^LR (-2 + LR)) / LR^3>,
+ *   f3 = h Re<(-4 - 3 LR - LR^2 + e^LR (4 - LR)) / LR^3>,
+ *   g  = -(c/2) kappa_n dealias_n,  dealias_n = [n <= (2/3)(N/2)] or 1,  g_{N/2} = 0.
+ * The steps call advances the spectrum v = U in place by nsteps steps of, with Nhat(w) = i g rfft(irfft(w)^2),
+ *   Nv = Nhat(v), a = E2 v + Q Nv;   Na = Nhat(a), b = E2 v + Q Na;   Nb = Nhat(b), c = E2 a + Q (2 Nb - Nv);
+ *   Nc = Nhat(c), v <- E v + f1 Nv + 2 f2 (Na + Nb) + f3 Nc.
+ * Sixteen launches per step on the caller's stream (per stage: the inverse transform, the square, the forward
+ * transform, the fused stage kernel), no host synchronisation, no atomics:
+ * identical calls give identical bits, and k calls of n steps equal one call of k n steps bit for bit.
+ * The grf1d call: noise [B, N, 2] (complex coefficients in fft order), sqrt_eig [N] -> out [B, N] =
+ * Re ifft(sqrt_eig . noise) with 1 / N, through the Hermitian-symmetrised half spectrum and the same inverse.
+ * State and tables 16-byte aligned (noise 8), the workspaces of the steps and grf1d calls 256-byte aligned (the
+ * transforms alone need none); the ws / spec queries return 0 for sizes the calls refuse (odd or out-of-range N, B outside 1 .. 65535).
+ * nsteps == 0 is a no-op.  The first use of a grid builds its plan: it allocates and synchronises once.
+ * Argument errors are reported before any device work. */
+size_t rpde_etd1d_ws_bytes(int B, int N);
+size_t rpde_etd1d_spec_elems(int B, int N);
+int rpde_etd1d_rfft(const float* u, float* U, int B, int N, void* stream);
+int rpde_etd1d_irfft(const float* U, float* u, int B, int N, void* stream);
+int rpde_etd1d_steps(float* U, const float* E, const float* E2, const float* Q, const float* f1, const float* f2,
+                     const float* f3, const float* g, int B, int N, int nsteps, void* ws, size_t ws_bytes, void* stream);
+size_t rpde_grf1d_ws_bytes(int B, int N);
+int rpde_grf1d(const float* noise, const float* sqrt_eig, float* out, int B, int N, void* ws, size_t ws_bytes,
+               void* stream);
+
 /* ---- optimizer step: torch.optim.AdamW as built at main_1d.py:144 / main_2d.py:173 (decoupled weight decay,
  * bias-corrected moments, no amsgrad), one streaming kernel over flat fp32 buffers of n (multiple of 4) elements.
  * The caller passes the step's scalars: 1 - lr*wd, 1 - b1, b2, 1 - b2, lr / (1 - b1^t), sqrt(1 - b2^t), eps. */

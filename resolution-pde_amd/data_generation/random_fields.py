@@ -5,7 +5,13 @@ built here.
     sqrt_eig[k] = size^2 sqrt(2) sigma (4 pi^2 |k|^2 + tau^2)^(-alpha/2),  0 at the mean mode,  sigma = tau^(alpha - 1)
     sample      = Re ifft2(sqrt_eig . (xi_re + i xi_im)),  xi standard normal,  torch's 1/size^2 in the inverse
 
-The noise comes from torch.randn on the device; the transform is rpde.ops.grf2d (csrc/ns_solver.hip)."""
+The noise comes from torch.randn on the device; the transform is rpde.ops.grf2d (csrc/ns_solver.hip).
+
+The periodic 1-D field -- the reference's dim = 1 formula -- is a class of its own, GaussianRF1d, on rpde.ops.grf1d
+(csrc/etd1d.hip); GaussianRF itself still refuses dim = 1:
+
+    sqrt_eig[k] = size sqrt(2) sigma (4 pi^2 k^2 + tau^2)^(-alpha/2),  0 at k = 0,  sigma = tau^((2 alpha - 1) / 2)
+    sample      = Re ifft(sqrt_eig . (xi_re + i xi_im))"""
 from __future__ import annotations
 
 import math
@@ -57,3 +63,48 @@ class GaussianRF(object):
         elif tuple(noise.shape) != (int(N), *self.size, 2):
             raise ValueError(f"GaussianRF.sample: noise {tuple(noise.shape)}, expected {(int(N), *self.size, 2)}")
         return ops.grf2d(noise.to(self.device), self.sqrt_eig)
+
+
+def sqrt_eig_1d(N: int, alpha: float, tau: float, sigma: float) -> torch.Tensor:
+    """float32 [N] host tensor, formed in float64 and rounded once; signed integer wavenumbers in fft order (Nyquist
+    -N/2), 0 at k = 0"""
+    k = (torch.fft.fftfreq(N, dtype=torch.float64) * N).round()
+    e = N * math.sqrt(2.0) * float(sigma) * (4.0 * math.pi ** 2 * k ** 2 + float(tau) ** 2) ** (-float(alpha) / 2.0)
+    e[0] = 0.0
+    return e.to(torch.float32)
+
+
+class GaussianRF1d(object):
+    """the reference's GaussianRF(dim=1, size, ...) with periodic boundary, sampled on the device"""
+
+    def __init__(self, size, alpha=2, tau=3, sigma=None, device=None):
+        size = int(size)
+        if size < 4 or size > 4096 or size % 2:
+            raise ValueError(f"GaussianRF1d: size must be even, 4 .. 4096 (got {size})")
+        if not tau > 0:
+            raise ValueError(f"GaussianRF1d: tau must be positive (got {tau})")
+        self.dim = 1
+        self.device = torch.device("cuda" if device is None else device)
+        if sigma is None:
+            sigma = tau ** (0.5 * (2 * alpha - self.dim))
+        self.alpha, self.tau, self.sigma = alpha, tau, sigma
+        self.size = size
+        self._sqrt_eig_host = sqrt_eig_1d(size, alpha, tau, sigma)
+        self._sqrt_eig = None
+
+    @property
+    def sqrt_eig(self) -> torch.Tensor:
+        """[size] fp32 on the device (moved there at first use)"""
+        if self._sqrt_eig is None:
+            self._sqrt_eig = self._sqrt_eig_host.to(self.device)
+        return self._sqrt_eig
+
+    def sample(self, N, generator: Optional[torch.Generator] = None, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """[N, size] samples.  The noise [N, size, 2] is drawn with torch.randn on the device (from `generator`, a
+        device generator, when given: equal seeds give equal samples) or passed in."""
+        from rpde import ops
+        if noise is None:
+            noise = torch.randn(int(N), self.size, 2, device=self.device, dtype=torch.float32, generator=generator)
+        elif tuple(noise.shape) != (int(N), self.size, 2):
+            raise ValueError(f"GaussianRF1d.sample: noise {tuple(noise.shape)}, expected {(int(N), self.size, 2)}")
+        return ops.grf1d(noise.to(self.device), self.sqrt_eig)

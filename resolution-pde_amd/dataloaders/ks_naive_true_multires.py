@@ -27,9 +27,14 @@ class KSTrajectoryDatasetFromExtracted(TrajectoryList):
     """whole test trajectories [T,X] for rollout evaluation"""
 
 
-def _ks_path(saved_folder, resolution, viscosity, L, lmax, et, nte, nt, train_s):
+def _ks_file(saved_folder, resolution, viscosity, L, lmax, et, nte, nt, train_s):
+    """where a resolution's training file lives, whether it exists or not (data_generation/ks_1d.py writes there)"""
     sub = f"visc_{viscosity}_L{L}_lmax{lmax}_et{et}_nte{nte}_nt{nt}"
-    return with_npz_fallback(os.path.join(saved_folder, f"res_{resolution}", sub, f"KS_train_{train_s}.h5"))
+    return os.path.join(saved_folder, f"res_{resolution}", sub, f"KS_train_{train_s}.h5")
+
+
+def _ks_path(saved_folder, resolution, viscosity, L, lmax, et, nte, nt, train_s):
+    return with_npz_fallback(_ks_file(saved_folder, resolution, viscosity, L, lmax, et, nte, nt, train_s))
 
 
 def _ks_read(path: str) -> np.ndarray:

@@ -148,6 +148,13 @@ _SIGNATURES = {
     "rpde_ns2d_steps": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
     "rpde_grf2d_ws_bytes": (_Z, [_I, _I, _I]),
     "rpde_grf2d": (_I, [_P, _P, _P, _I, _I, _I, _P, _Z, _P]),
+    "rpde_etd1d_ws_bytes": (_Z, [_I, _I]),
+    "rpde_etd1d_spec_elems": (_Z, [_I, _I]),
+    "rpde_etd1d_rfft": (_I, [_P, _P, _I, _I, _P]),
+    "rpde_etd1d_irfft": (_I, [_P, _P, _I, _I, _P]),
+    "rpde_etd1d_steps": (_I, [_P] * 8 + [_I, _I, _I, _P, _Z, _P]),
+    "rpde_grf1d_ws_bytes": (_Z, [_I, _I]),
+    "rpde_grf1d": (_I, [_P, _P, _P, _I, _I, _P, _Z, _P]),
     "rpde_adamw_step": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _F, _F, _P]),
     "rpde_adamw_step_dev": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _P, _P]),
     "rpde_adamw_set_hyper_dev": (_I, [_P, _F, _F, _P]),

@@ -1086,6 +1086,111 @@ def ns2d_solve(w0: torch.Tensor, f: torch.Tensor, visc: float, dt: float, steps:
     return snaps[:n_rec].permute(1, 2, 3, 0).contiguous()
 
 
+# ----------------------------------------------------------------------------
+# 1-D exponential-time-differencing generator and the 1-D Gaussian random field (csrc/etd1d.hip, rpde_etd1d_* /
+# rpde_grf1d; data_generation/burgers_1d.py, ks_1d.py and random_fields.py are the callers).  Data production: no
+# autograd, GPU tensors only, no CPU fallback.
+# ----------------------------------------------------------------------------
+def etd1d_tables(N: int, length: float, c2: float, c4: float, dt: float, advect: float = 1.0, dealias: bool = True):
+    """(E, E2, Q, f1, f2, f3, g): the ETDRK4 tables of u_t = L u - (advect/2) (u^2)_x with the symbol
+    l_n = c2 kappa_n^2 + c4 kappa_n^4, kappa_n = 2 pi n / length, as float32 [kp] host tensors (kp = N//2+1 rounded up to
+    4, padding zero), formed in float64 and rounded once.  Kassam-Trefethen: z = dt l_n, LR = z + r_m on the 32 contour
+    points r_m = exp(i pi (m - 1/2) / 32) -- the f coefficients cancel catastrophically in fp32 for small z, the contour
+    mean in float64 does not.  g_n = -(advect/2) kappa_n dealias_n, dealias_n = [n <= (2/3)(N/2)] (or 1), g_{N/2} = 0.
+    include/rpde.h has the formulas."""
+    import math
+    N = int(N)
+    if N < 4 or N % 2:
+        raise ValueError(f"etd1d_tables: N must be even and >= 4, got {N}")
+    if not (float(length) > 0 and float(dt) > 0):
+        raise ValueError(f"etd1d_tables: length and dt must be positive, got length={length} dt={dt}")
+    K, kp = N // 2 + 1, (N // 2 + 1 + 3) // 4 * 4
+    n = torch.arange(K, dtype=torch.float64)
+    kappa = (2.0 * math.pi / float(length)) * n
+    h = float(dt)
+    z = h * (float(c2) * kappa ** 2 + float(c4) * kappa ** 4)
+    m = torch.arange(1, 33, dtype=torch.float64)
+    r = torch.polar(torch.ones(32, dtype=torch.float64), math.pi * (m - 0.5) / 32.0)
+    LR = z.view(K, 1).to(torch.complex128) + r.view(1, 32)
+    eLR = torch.exp(LR)
+
+    def mean(t):
+        return t.mean(dim=1).real
+
+    keep = (n <= (2.0 / 3.0) * (N // 2)).to(torch.float64) if dealias else torch.ones(K, dtype=torch.float64)
+    g = -(float(advect) / 2.0) * kappa * keep
+    g[N // 2] = 0.0
+    out = []
+    for t in (torch.exp(z), torch.exp(z / 2.0),
+              h * mean((torch.exp(LR / 2.0) - 1.0) / LR),
+              h * mean((-4.0 - LR + eLR * (4.0 - 3.0 * LR + LR ** 2)) / LR ** 3),
+              h * mean((2.0 + LR + eLR * (-2.0 + LR)) / LR ** 3),
+              h * mean((-4.0 - 3.0 * LR - LR ** 2 + eLR * (4.0 - LR)) / LR ** 3),
+              g):
+        p = torch.zeros(kp, dtype=torch.float32)
+        p[:K] = t.to(torch.float32)
+        out.append(p)
+    return tuple(out)
+
+
+def _grid2(t: torch.Tensor, what: str):
+    if t.dim() != 2:
+        raise ValueError(f"{what}: expected [B, N], got {tuple(t.shape)}")
+    B, N = (int(v) for v in t.shape)
+    if load().rpde_etd1d_ws_bytes(B, N) == 0:
+        raise ValueError(f"{what}: unsupported grid B={B} N={N} (N even, 4 .. 4096, B <= 65535)")
+    return B, N
+
+
+def grf1d(noise: torch.Tensor, sqrt_eig: torch.Tensor) -> torch.Tensor:
+    """noise [B, N, 2] (real and imaginary part of the coefficients in fft order, standard normal), sqrt_eig [N] ->
+    [B, N] = Re ifft(sqrt_eig . noise), torch's 1/N included.  The HIP side is deterministic given the noise.
+    Contiguous fp32 tensors on the GPU; no autograd, no CPU fallback."""
+    lib = load()
+    if noise.dim() != 3 or noise.shape[-1] != 2 or tuple(sqrt_eig.shape) != tuple(noise.shape[1:2]):
+        raise ValueError(f"grf1d: noise {tuple(noise.shape)} / sqrt_eig {tuple(sqrt_eig.shape)}, expected [B, N, 2] and [N]")
+    noise, sqrt_eig = _f32c(noise.detach()), _f32c(sqrt_eig.detach())
+    pn, ps = ptr(noise), ptr(sqrt_eig)                     # raises for CPU tensors: there is no fallback
+    B, N = _grid2(noise[..., 0], "grf1d")
+    out = torch.empty(B, N, dtype=torch.float32, device=noise.device)
+    nws = lib.rpde_grf1d_ws_bytes(B, N)
+    ws = workspace(nws, noise.device)
+    check(lib.rpde_grf1d(pn, ps, ptr(out), B, N, ws.data_ptr(), nws, stream_ptr()), "grf1d")
+    return out
+
+
+def etd1d_solve(u0: torch.Tensor, tables, steps: int, record_every: int) -> torch.Tensor:
+    """`steps` ETDRK4 steps of u_t = L u - (c/2) (u^2)_x from u0 [B, N] with the seven tables of etd1d_tables (host or
+    device tensors, [kp]); a snapshot -- irfft of the state -- after every `record_every`-th step.  Returns
+    [B, steps // record_every, N], contiguous fp32.  Sixteen launches per step, no host synchronisation between them;
+    the recording loop calls the device `steps // record_every` times, which gives the bits of one long call.
+    Contiguous fp32 tensors on the GPU; no autograd, no CPU fallback."""
+    lib = load()
+    steps, record_every = int(steps), int(record_every)
+    if steps < 0 or record_every < 1:
+        raise ValueError(f"etd1d_solve: bad steps={steps} record_every={record_every}")
+    u0 = _f32c(u0.detach())
+    pu = ptr(u0)                                           # raises for CPU tensors: there is no fallback
+    B, N = _grid2(u0, "etd1d_solve")
+    kp = (N // 2 + 1 + 3) // 4 * 4
+    tables = tuple(tables)
+    if len(tables) != 7 or any(tuple(t.shape) != (kp,) for t in tables):
+        raise ValueError(f"etd1d_solve: expected the seven [{kp}] tables of etd1d_tables(N={N}, ...)")
+    dev = u0.device
+    tabs = [_f32c(t.detach().to(dev)) for t in tables]
+    nws = lib.rpde_etd1d_ws_bytes(B, N)
+    ws = workspace(nws, dev)
+    st = stream_ptr()
+    U = torch.empty(lib.rpde_etd1d_spec_elems(B, N), dtype=torch.float32, device=dev)
+    check(lib.rpde_etd1d_rfft(pu, ptr(U), B, N, st), "etd1d_rfft")
+    n_rec = steps // record_every
+    snaps = torch.empty(max(n_rec, 1), B, N, dtype=torch.float32, device=dev)
+    for c in range(n_rec):
+        check(lib.rpde_etd1d_steps(ptr(U), *(ptr(t) for t in tabs), B, N, record_every, ws.data_ptr(), nws, st), "etd1d_steps")
+        check(lib.rpde_etd1d_irfft(ptr(U), ptr(snaps[c]), B, N, st), "etd1d_irfft")
+    return snaps[:n_rec].permute(1, 0, 2).contiguous()
+
+
 def warm_plans(model, resolutions, dims: int, in_channels: int = 1, device="cuda") -> None:
     """Build every DFT plan (tables, adjoint tables, operand images: hipMalloc + one stream sync each,
     csrc/core.hip get_plan) and size the workspaces the model needs at the given grid resolutions, with one

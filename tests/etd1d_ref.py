@@ -1,0 +1,185 @@
+"""Restatement of the 1-D exponential-time-differencing generator and its Gaussian random field with torch.fft (test
+infrastructure only; the product tree does not import it), and the parity cases.
+
+Periodic domain of length L, grid N (even), u^ = rfft(u) unnormalised, kappa_n = 2 pi n / L, n = 0 .. N/2.  Every
+equation u_t = L u - (c/2) (u^2)_x with the symbol l_n = c2 kappa_n^2 + c4 kappa_n^4:
+
+    Burgers  u_t + u u_x = nu_eff u_xx              c2 = -nu_eff, c4 = 0
+    KS       u_t + u u_x + u_xx + nu u_xxxx = 0     c2 = +1,      c4 = -nu
+
+    Nhat(v) = i g_n rfft(irfft(v)^2),  g_n = -(c/2) kappa_n dealias_n,  dealias_n = [n <= (2/3)(N/2)] or 1,  g_{N/2} = 0
+
+ETDRK4 in the Kassam-Trefethen form, step h, z = h l_n, LR = z + r_m, r_m = exp(i pi (m - 1/2) / 32), m = 1 .. 32, <.>
+the mean over m:
+
+    E = e^z,  E2 = e^(z/2),  Q = h Re<(e^(LR/2) - 1) / LR>
+    f1 = h Re<(-4 - LR + e^LR (4 - 3 LR + LR^2)) / LR^3>
+    f2 = h Re<(2 + LR + e^LR (-2 + LR)) / LR^3>
+    f3 = h Re<(-4 - 3 LR - LR^2 + e^LR (4 - LR)) / LR^3>
+
+    Nv = Nhat(v), a = E2 v + Q Nv;  Na = Nhat(a), b = E2 v + Q Na;  Nb = Nhat(b), c = E2 a + Q (2 Nb - Nv);
+    Nc = Nhat(c), v <- E v + f1 Nv + 2 f2 (Na + Nb) + f3 Nc
+
+Everything in float64 by default: the yardstick.  ``dtype=torch.float32`` runs the same restatement entirely in single
+precision, tables included (contour in complex64): its distance from the float64 run on the same inputs is the floor
+(`floor32`) the device is measured against.  ``nonlinear=False`` drops Nhat: the tests use it to show that the inputs make
+that term matter."""
+from __future__ import annotations
+
+import math
+
+import torch
+
+# (B, N): kp padding of 3 columns each, a non-power-of-two grid, odd B
+CASES = [(3, 16), (2, 48), (2, 64), (1, 128), (2, 200), (2, 256)]
+STEPS, SNAPSHOTS = 80, 4
+KS_NU, KS_DT = 0.05, 0.01
+BURGERS_NU, BURGERS_DT, BURGERS_L = 0.1, 5e-3, 2.0
+BURGERS_GRF = (2.0, 5.0, 25.0)     # alpha, tau, sigma
+FLOOR_FACTOR = 4.0                 # the bound on the device: FLOOR_FACTOR x the restatement's own float32 error
+
+
+def case_id(c):
+    return "x".join(str(v) for v in c)
+
+
+def _cdtype(dtype):
+    return torch.complex128 if dtype == torch.float64 else torch.complex64
+
+
+def ks_symbol(nu):
+    """(c2, c4) of u_t + u u_x + u_xx + nu u_xxxx = 0"""
+    return 1.0, -float(nu)
+
+
+def burgers_symbol(nu_eff):
+    """(c2, c4) of u_t + u u_x = nu_eff u_xx"""
+    return -float(nu_eff), 0.0
+
+
+def tables(N, length, c2, c4, dt, advect=1.0, dealias=True, dtype=torch.float64):
+    """(E, E2, Q, f1, f2, f3, g), each [N/2 + 1] of `dtype`"""
+    K = N // 2 + 1
+    n = torch.arange(K, dtype=dtype)
+    kappa = (2.0 * math.pi / float(length)) * n
+    ell = float(c2) * kappa ** 2 + float(c4) * kappa ** 4
+    h = float(dt)
+    z = h * ell
+    m = torch.arange(1, 33, dtype=dtype)
+    r = torch.polar(torch.ones(32, dtype=dtype), math.pi * (m - 0.5) / 32.0)
+    LR = z.view(K, 1).to(_cdtype(dtype)) + r.view(1, 32)
+    eLR = torch.exp(LR)
+    mean = lambda t: t.mean(dim=1).real                                   # noqa: E731
+    E, E2 = torch.exp(z), torch.exp(z / 2.0)
+    Q = h * mean((torch.exp(LR / 2.0) - 1.0) / LR)
+    f1 = h * mean((-4.0 - LR + eLR * (4.0 - 3.0 * LR + LR ** 2)) / LR ** 3)
+    f2 = h * mean((2.0 + LR + eLR * (-2.0 + LR)) / LR ** 3)
+    f3 = h * mean((-4.0 - 3.0 * LR - LR ** 2 + eLR * (4.0 - LR)) / LR ** 3)
+    keep = (n <= (2.0 / 3.0) * (N // 2)).to(dtype) if dealias else torch.ones(K, dtype=dtype)
+    g = -(float(advect) / 2.0) * kappa * keep
+    g[N // 2] = 0.0
+    return E, E2, Q, f1, f2, f3, g
+
+
+def solve(u0, length, c2, c4, dt, steps, record_every, dtype=torch.float64, advect=1.0, dealias=True, nonlinear=True):
+    """u0 [B, N] -> [B, steps // record_every, N] of `dtype`: irfft of the state after every record_every-th step"""
+    u0 = u0.to(dtype)
+    B, N = u0.shape
+    E, E2, Q, f1, f2, f3, g = tables(N, length, c2, c4, dt, advect, dealias, dtype)
+    ig = torch.complex(torch.zeros_like(g), g)
+    inv = lambda w: torch.fft.irfft(w, n=N)                               # noqa: E731
+    if nonlinear:
+        nl = lambda w: ig * torch.fft.rfft(inv(w) ** 2)                   # noqa: E731
+    else:
+        nl = lambda w: torch.zeros_like(w)                                # noqa: E731
+    v = torch.fft.rfft(u0)
+    out = torch.zeros(B, steps // record_every, N, dtype=dtype)
+    for j in range(steps):
+        Nv = nl(v)
+        a = E2 * v + Q * Nv
+        Na = nl(a)
+        b = E2 * v + Q * Na
+        Nb = nl(b)
+        c = E2 * a + Q * (2.0 * Nb - Nv)
+        Nc = nl(c)
+        v = E * v + f1 * Nv + 2.0 * f2 * (Na + Nb) + f3 * Nc
+        if (j + 1) % record_every == 0 and (j + 1) // record_every <= out.shape[1]:
+            out[:, (j + 1) // record_every - 1] = inv(v)
+    return out
+
+
+def sqrt_eig(N, alpha, tau, sigma=None, dtype=torch.float64):
+    """N sqrt(2) sigma (4 pi^2 k^2 + tau^2)^(-alpha/2) over signed integer k in fft order, 0 at k = 0;
+    sigma = tau^((2 alpha - 1) / 2) by default"""
+    if sigma is None:
+        sigma = tau ** (0.5 * (2 * alpha - 1))
+    k = (torch.fft.fftfreq(N, dtype=torch.float64) * N).round()
+    e = N * math.sqrt(2.0) * sigma * (4 * math.pi ** 2 * k ** 2 + tau ** 2) ** (-alpha / 2.0)
+    e[0] = 0.0
+    return e.to(dtype)
+
+
+def grf(noise, se, dtype=torch.float64):
+    """noise [B, N, 2], se [N] -> Re ifft(se . (noise_re + i noise_im)) [B, N]"""
+    noise, se = noise.to(dtype), se.to(dtype)
+    return torch.fft.ifft(torch.complex(se * noise[..., 0], se * noise[..., 1])).real
+
+
+def noise64(B, N, seed):
+    return torch.randn(B, N, 2, generator=torch.Generator().manual_seed(seed), dtype=torch.float64)
+
+
+def ks_initial(B, N, length, lmax, seed):
+    """sum_{j<10} A_j sin(2 pi l_j x / L + phi_j) on x = i L / N, A in U(-1/2, 1/2), l in {1 .. lmax}, phi in U(0, 2 pi);
+    float64 [B, N]"""
+    gen = torch.Generator().manual_seed(seed)
+    A = torch.rand(B, 10, generator=gen, dtype=torch.float64) - 0.5
+    l = torch.randint(1, lmax + 1, (B, 10), generator=gen).to(torch.float64)
+    phi = 2.0 * math.pi * torch.rand(B, 10, generator=gen, dtype=torch.float64)
+    x = torch.arange(N, dtype=torch.float64) * (float(length) / N)
+    return (A[..., None] * torch.sin(2.0 * math.pi * l[..., None] * x / float(length) + phi[..., None])).sum(1)
+
+
+def burgers_initial(B, N, seed):
+    """GRF(alpha = 2, tau = 5, sigma = 25) from seeded float64 noise, float64 [B, N]"""
+    alpha, tau, sigma = BURGERS_GRF
+    return grf(noise64(B, N, seed), sqrt_eig(N, alpha, tau, sigma))
+
+
+def rel(x, y):
+    """relative L2 error of x against y, in float64"""
+    x, y = x.detach().double().cpu(), y.detach().double().cpu()
+    return float((x - y).norm() / y.norm())
+
+
+def setup(pde, case):
+    """(u0 float64 [B, N], length, (c2, c4), dt) of a parity case"""
+    B, N = case
+    if pde == "ks":
+        length = N / 4.0
+        return ks_initial(B, N, length, min(8, N // 5), seed=31 + N), length, ks_symbol(KS_NU), KS_DT
+    if pde == "burgers":
+        return burgers_initial(B, N, seed=47 + N), BURGERS_L, burgers_symbol(BURGERS_NU), BURGERS_DT
+    raise ValueError(pde)
+
+
+_PARITY: dict = {}
+
+
+def parity_reference(pde, case):
+    """{u0, length, c2, c4, dt, sol64 [B, SNAPSHOTS, N], floor32 [SNAPSHOTS], nonlinear_share}: computed once per case
+    and shared; read-only"""
+    hit = _PARITY.get((pde, case))
+    if hit is not None:
+        return hit
+    u0, length, (c2, c4), dt = setup(pde, case)
+    every = STEPS // SNAPSHOTS
+    sol64 = solve(u0, length, c2, c4, dt, STEPS, every)
+    # the floor sees what the device sees: float32 inputs
+    sol32 = solve(u0.float(), length, c2, c4, dt, STEPS, every, dtype=torch.float32)
+    lin = solve(u0, length, c2, c4, dt, STEPS, every, nonlinear=False)
+    out = dict(u0=u0, length=length, c2=c2, c4=c4, dt=dt, sol64=sol64,
+               floor32=[rel(sol32[:, c], sol64[:, c]) for c in range(SNAPSHOTS)],
+               nonlinear_share=rel(lin[:, -1], sol64[:, -1]))
+    _PARITY[(pde, case)] = out
+    return out
