@@ -392,7 +392,7 @@ int rpde_rel_l2_bwd(const float* x, const float* y, const float* stats,
  * E_d = 0, formed on the device; g_b = grad_rel[b], or grad_loss[0] (/ B when size_average) with grad_rel NULL.
  * No gradient for y.  In 2-D the columns kx = 0 and (even N) kx = N/2 of omega must be symmetric in ky
  * (omega[ky] == omega[(M - ky) % M]): the caller checks it.  Axes 2 .. 4096; the full-spectrum plans are those of the
- * resizers at equal sizes (cf_rfft2_plans, csrc/cf_dft.h; first use of a grid allocates and synchronises).  Argument errors are reported before any
+ * resizers at equal sizes (cf_rfft2_plans, csrc/cf_dft.h, through csrc/halfspec.h; first use of a grid allocates and synchronises).  Argument errors are reported before any
  * device work. */
 size_t rpde_wrel_l2_ws_bytes(int B, int C, int M, int N);
 size_t rpde_wrel_l2_spec_elems(int B, int C, int M, int N);
@@ -403,8 +403,9 @@ int rpde_wrel_l2_bwd(const float* spec_d, const float* omega, const float* stats
                      void* ws, size_t ws_bytes, void* stream);
 
 /* ---- NS vorticity generator (reference: data_generation/ns_2d.py, random_fields.py): 2-D Navier-Stokes in vorticity
- * form on the periodic unit square, pseudo-spectral, and the Gaussian random field that seeds it (csrc/ns_solver.hip, on the 2-D
- * transforms of csrc/cf_dft.h).
+ * form on the periodic unit square, pseudo-spectral (csrc/ns_solver.hip), and the Gaussian random field that seeds it
+ * and the rfft2 / irfft2 calls (csrc/halfspec.hip), on the half-spectrum layer of csrc/halfspec.h over the 2-D transforms of
+ * csrc/cf_dft.h.
  * Grids M x N, both axes even, 4 .. 4096.  A half spectrum is [images][M][re|im][kp] floats: rows ky in fft order
  * (signed k1 = ky < M/2 ? ky : ky - M), kx = k2 = 0 .. N/2 contiguous, kp = N/2+1 rounded up to 4, padded columns zero;
  * the spec_elems query gives the floats of B images.  The rfft2 / irfft2 calls are torch.fft.rfft2 (unnormalised) and
@@ -435,11 +436,12 @@ size_t rpde_grf2d_ws_bytes(int B, int M, int N);
 int rpde_grf2d(const float* noise, const float* sqrt_eig, float* out, int B, int M, int N,
                void* ws, size_t ws_bytes, void* stream);
 
-/* ---- 1-D exponential-time-differencing generator (csrc/etd1d.hip, on the 1-D transforms of csrc/cf_dft.h): every
+/* ---- 1-D exponential-time-differencing generator (csrc/etd1d.hip; the rfft / irfft and grf1d calls are the M = 1 case of
+ * the NS generator's in csrc/halfspec.hip, on the 1-D transforms of csrc/cf_dft.h): every
  * equation u_t = L u - (c/2) (u^2)_x on a periodic domain of length len -- Burgers (L = nu_eff d_xx) and
  * Kuramoto-Sivashinsky (L = -d_xx - nu d_xxxx) -- and the 1-D Gaussian random field.
  * Grid N even, 4 .. 4096.  A half spectrum is [images][re|im][kp] floats, k = 0 .. N/2 contiguous, kp = N/2+1 rounded
- * up to 4, padded columns zero; the spec_elems query gives the floats of B images.  The rfft / irfft calls are
+ * up to 4, padded columns zero -- the layout above with one row; the spec_elems query gives the floats of B images.  The rfft / irfft calls are
  * torch.fft.rfft (unnormalised) and irfft (1 / N; Im of the mean and Nyquist bins ignored) between u [B, N] and that
  * layout.  With kappa_n = 2 pi n / len, the symbol l_n = c2 kappa_n^2 + c4 kappa_n^4 and the step h, the caller forms
  * seven tables [kp] (padded entries zero) in float64 and rounds them to fp32 once -- ETDRK4 in the Kassam-Trefethen

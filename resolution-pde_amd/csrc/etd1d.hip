@@ -1,8 +1,8 @@
 // Exponential-time-differencing generator for u_t = L u - (c/2) (u^2)_x on a periodic 1-D domain (Burgers,
-// Kuramoto-Sivashinsky; data_generation/burgers_1d.py, ks_1d.py) and the 1-D Gaussian random field
-// (random_fields.py, GaussianRF1d).  ETDRK4 in the Kassam-Trefethen form, pseudo-spectral.  gfx950, wave64.
+// Kuramoto-Sivashinsky; data_generation/burgers_1d.py, ks_1d.py).  ETDRK4 in the Kassam-Trefethen form,
+// pseudo-spectral.  gfx950, wave64.
 //
-// The state is the half spectrum v = rfft(u), [B][re|im][kp] (etd1d.h).  With Nhat(w) = i g rfft(irfft(w)^2) one step is
+// The state is the half spectrum v = rfft(u), [B][re|im][kp] (halfspec.h, M = 1).  With Nhat(w) = i g rfft(irfft(w)^2) one step is
 //   Nv = Nhat(v), a = E2 v + Q Nv;   Na = Nhat(a), b = E2 v + Q Na;   Nb = Nhat(b), c = E2 a + Q (2 Nb - Nv);
 //   Nc = Nhat(c), v <- E v + f1 Nv + 2 f2 (Na + Nb) + f3 Nc
 // and sixteen launches on the caller's stream, four per stage, no host synchronisation:
@@ -12,25 +12,15 @@
 //   k_etd_stage<S>   i g F in registers (a swap and a sign) and the stage's update, fused multiply-adds only
 // The seven tables (E, E2, Q, f1, f2, f3, g) [kp] are formed by the caller in float64 and rounded to fp32 once
 // (include/rpde.h has the formulas): no division and no transcendental here.  The transforms are the one-dimensional
-// case of the full-spectrum real DFT of cf_dft.h (cf_rfft2 / cf_irfft2 without a column plan, GEMM form; 1 / N in the
-// synthesis table).  The stage kernels stream as ns_solver.hip does: a thread owns one 16-byte group of k for both re
+// case of the full-spectrum real DFT of cf_dft.h (hs_rfft / hs_irfft at M = 1: no column plan, GEMM form; 1 / N in the
+// synthesis table; the rfft / irfft entries and the random field are in halfspec.hip).  The stage kernels stream as ns_solver.hip does: a thread owns one 16-byte group of k for both re
 // and im, every load and store is a whole float4, grid (blocks, B).  The square is not folded into a transform: the
 // GEMMs carry no squaring prologue, and one more epilogue there would serve this file alone.
 // The stage sequence is a pure function of v: k calls of n steps give the bits of one call of k n steps.  No atomics
 // anywhere: identical calls give identical bits.
-#include "etd1d.h"
-#include "cf_dft.h"
-#include "pointwise.h"
+#include "halfspec.h"
 
 namespace rpde {
-
-__device__ __forceinline__ void etd_ld4(const float* p, float (&v)[4]) {
-  const float4 t = *reinterpret_cast<const float4*>(p);
-  v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-}
-__device__ __forceinline__ void etd_st4(float* p, const float (&v)[4]) {
-  *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-}
 
 struct EtdTables { const float *E, *E2, *Q, *f1, *f2, *f3, *g; };
 // v: the state; nv: Nv; a: stage a; sum: Na, then Na + Nb; bc: stage b, then stage c (each the next synthesis' input)
@@ -44,7 +34,7 @@ struct EtdBufs { float *v, *nv, *a, *sum, *bc; };
 // i g (Fr + i Fi) = -g Fi + i g Fr.  grid (blocks, B).  Padded columns (k > N/2) are written as zeros: the synthesis
 // reads them.
 template <int S>
-__global__ __launch_bounds__(256) void k_etd_stage(EtdBufs u, const float* __restrict__ F, EtdTables t, EtdGeom g) {
+__global__ __launch_bounds__(256) void k_etd_stage(EtdBufs u, const float* __restrict__ F, EtdTables t, HalfSpec g) {
   const long per = 2L * g.kp, base = (long)blockIdx.y * per;
   const float* __restrict__ Fb = F + base;
   const int c4n = g.kp / 4;
@@ -52,9 +42,9 @@ __global__ __launch_bounds__(256) void k_etd_stage(EtdBufs u, const float* __res
     const int k0 = q * 4;
     const long ore = base + k0, oim = ore + g.kp;
     float fr[4], fi[4], gg[4], nr[4], ni[4];
-    etd_ld4(Fb + k0, fr);
-    etd_ld4(Fb + g.kp + k0, fi);
-    etd_ld4(t.g + k0, gg);
+    ld4(Fb + k0, fr);
+    ld4(Fb + g.kp + k0, fi);
+    ld4(t.g + k0, gg);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       nr[j] = -gg[j] * fi[j];
@@ -62,8 +52,8 @@ __global__ __launch_bounds__(256) void k_etd_stage(EtdBufs u, const float* __res
     }
     if (S == 0 || S == 1) {
       float vr[4], vi[4], e2[4], qq[4], orr[4], oi[4];
-      etd_ld4(u.v + ore, vr); etd_ld4(u.v + oim, vi);
-      etd_ld4(t.E2 + k0, e2); etd_ld4(t.Q + k0, qq);
+      ld4(u.v + ore, vr); ld4(u.v + oim, vi);
+      ld4(t.E2 + k0, e2); ld4(t.Q + k0, qq);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const bool live = k0 + j < g.K;
@@ -74,14 +64,14 @@ __global__ __launch_bounds__(256) void k_etd_stage(EtdBufs u, const float* __res
       }
       float* __restrict__ nout = S == 0 ? u.nv : u.sum;
       float* __restrict__ sout = S == 0 ? u.a : u.bc;
-      etd_st4(nout + ore, nr); etd_st4(nout + oim, ni);
-      etd_st4(sout + ore, orr); etd_st4(sout + oim, oi);
+      st4(nout + ore, nr); st4(nout + oim, ni);
+      st4(sout + ore, orr); st4(sout + oim, oi);
     } else if (S == 2) {
       float ar[4], ai[4], pr[4], pi[4], sr[4], si[4], e2[4], qq[4], cr[4], ci[4];
-      etd_ld4(u.a + ore, ar);   etd_ld4(u.a + oim, ai);
-      etd_ld4(u.nv + ore, pr);  etd_ld4(u.nv + oim, pi);
-      etd_ld4(u.sum + ore, sr); etd_ld4(u.sum + oim, si);
-      etd_ld4(t.E2 + k0, e2);   etd_ld4(t.Q + k0, qq);
+      ld4(u.a + ore, ar);   ld4(u.a + oim, ai);
+      ld4(u.nv + ore, pr);  ld4(u.nv + oim, pi);
+      ld4(u.sum + ore, sr); ld4(u.sum + oim, si);
+      ld4(t.E2 + k0, e2);   ld4(t.Q + k0, qq);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const bool live = k0 + j < g.K;
@@ -90,15 +80,15 @@ __global__ __launch_bounds__(256) void k_etd_stage(EtdBufs u, const float* __res
         sr[j] = live ? sr[j] + nr[j] : 0.f;
         si[j] = live ? si[j] + ni[j] : 0.f;
       }
-      etd_st4(u.sum + ore, sr); etd_st4(u.sum + oim, si);
-      etd_st4(u.bc + ore, cr);  etd_st4(u.bc + oim, ci);
+      st4(u.sum + ore, sr); st4(u.sum + oim, si);
+      st4(u.bc + ore, cr);  st4(u.bc + oim, ci);
     } else {
       float vr[4], vi[4], pr[4], pi[4], sr[4], si[4], e[4], c1[4], c2[4], c3[4];
-      etd_ld4(u.v + ore, vr);   etd_ld4(u.v + oim, vi);
-      etd_ld4(u.nv + ore, pr);  etd_ld4(u.nv + oim, pi);
-      etd_ld4(u.sum + ore, sr); etd_ld4(u.sum + oim, si);
-      etd_ld4(t.E + k0, e);     etd_ld4(t.f1 + k0, c1);
-      etd_ld4(t.f2 + k0, c2);   etd_ld4(t.f3 + k0, c3);
+      ld4(u.v + ore, vr);   ld4(u.v + oim, vi);
+      ld4(u.nv + ore, pr);  ld4(u.nv + oim, pi);
+      ld4(u.sum + ore, sr); ld4(u.sum + oim, si);
+      ld4(t.E + k0, e);     ld4(t.f1 + k0, c1);
+      ld4(t.f2 + k0, c2);   ld4(t.f3 + k0, c3);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const bool live = k0 + j < g.K;
@@ -106,7 +96,7 @@ __global__ __launch_bounds__(256) void k_etd_stage(EtdBufs u, const float* __res
         vr[j] = live ? fmaf(e[j], vr[j], fmaf(c1[j], pr[j], fmaf(two_f2, sr[j], c3[j] * nr[j]))) : 0.f;
         vi[j] = live ? fmaf(e[j], vi[j], fmaf(c1[j], pi[j], fmaf(two_f2, si[j], c3[j] * ni[j]))) : 0.f;
       }
-      etd_st4(u.v + ore, vr); etd_st4(u.v + oim, vi);
+      st4(u.v + ore, vr); st4(u.v + oim, vi);
     }
   }
 }
@@ -121,94 +111,30 @@ __global__ __launch_bounds__(256) void k_etd_square(float* __restrict__ p, long 
   }
 }
 
-// noise [B][N][re|im] (coefficients c in fft order), se [N] = sqrt_eig -> the half spectrum
-// h[k] = (se[k] c[k] + conj(se[-k] c[-k])) / 2, k = 0 .. N/2, -k = (N - k) mod N: irfft(h) is the real part of
-// ifft(se . c).  grid (blocks, B); a thread per 16-byte group of k, padded columns zero
-__global__ __launch_bounds__(256) void k_grf1d_half(const float* __restrict__ noise, const float* __restrict__ se,
-                                                    float* __restrict__ h, EtdGeom g) {
-  const float2* __restrict__ nb = reinterpret_cast<const float2*>(noise) + (long)blockIdx.y * g.N;
-  float* __restrict__ hb = h + (long)blockIdx.y * 2 * g.kp;
-  const int c4n = g.kp / 4;
-  for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < c4n; q += gridDim.x * blockDim.x) {
-    const int k0 = q * 4;
-    float re[4], im[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int k = k0 + j;
-      re[j] = 0.f; im[j] = 0.f;
-      if (k < g.K) {
-        const int m = k ? g.N - k : 0;
-        const float2 c1 = nb[k], c2 = nb[m];
-        const float s1 = se[k], s2 = se[m];
-        re[j] = 0.5f * fmaf(s1, c1.x, s2 * c2.x);
-        im[j] = 0.5f * fmaf(s1, c1.y, -(s2 * c2.y));
-      }
-    }
-    etd_st4(hb + k0, re);
-    etd_st4(hb + g.kp + k0, im);
-  }
-}
-
-static bool etd_dims_ok(int B, int N) {
-  return B > 0 && B <= 65535 && N >= ETD_MIN_N && N <= ETD_MAX_N && N % 2 == 0;
-}
-static EtdGeom etd_geom(int B, int N) { return EtdGeom{B, N, N / 2 + 1, r4(N / 2 + 1)}; }
-static size_t etd_spec(int B, int N) { return (size_t)B * 2 * r4(N / 2 + 1); }
-// a block per 64 groups where an image has no more (N <= 510: a wave covers them), 256 threads otherwise
-static int etd_block(const EtdGeom& g) { return g.kp / 4 <= 64 ? 64 : 256; }
-static dim3 etd_grid(const EtdGeom& g) {
-  const int blk = etd_block(g);
-  return dim3((unsigned)((g.kp / 4 + blk - 1) / blk), g.B);
-}
-
-#define ETD_CHECK_WS(what, ws) \
-  RPDE_CHECK_ARG((reinterpret_cast<uintptr_t>(ws) & 255) == 0, what ": the workspace must be 256-byte aligned")
-#define ETD_CHECK_DIMS(what, B, N)                                                                                  \
-  RPDE_CHECK_ARG(etd_dims_ok(B, N), what ": bad B=%d N=%d (N even, %d .. %d, 1 <= B <= 65535)", B, N, ETD_MIN_N, \
-                 ETD_MAX_N)
-
 }  // namespace rpde
 
 using namespace rpde;
 
 extern "C" {
 
-size_t rpde_etd1d_spec_elems(int B, int N) { return etd_dims_ok(B, N) ? etd_spec(B, N) : 0; }
+size_t rpde_etd1d_spec_elems(int B, int N) { return hs_dims_ok(B, 1, N) ? hs_elems(hs_geom(B, 1, N)) : 0; }
 
 size_t rpde_etd1d_ws_bytes(int B, int N) {
-  if (!etd_dims_ok(B, N)) return 0;
+  if (!hs_dims_ok(B, 1, N)) return 0;
   // rpde_etd1d_steps: Nv, a, the running sum, b / c and the product spectrum, and the field (the rfft / irfft calls need none)
-  return 5 * arena_bytes(etd_spec(B, N)) + arena_bytes((size_t)B * N);
-}
-
-int rpde_etd1d_rfft(const float* u, float* U, int B, int N, void* stream) {
-  RPDE_CHECK_ARG(u && U, "etd1d_rfft: null pointer");
-  ETD_CHECK_DIMS("etd1d_rfft", B, N);
-  hipStream_t st = as_stream(stream);
-  const rpde_plan *pn, *pm;
-  RPDE_TRY(cf_rfft2_plans(&pn, &pm, 1, N, st));
-  return cf_rfft2(pn, pm, u, nullptr, U, B, st);
-}
-
-int rpde_etd1d_irfft(const float* U, float* u, int B, int N, void* stream) {
-  RPDE_CHECK_ARG(u && U, "etd1d_irfft: null pointer");
-  ETD_CHECK_DIMS("etd1d_irfft", B, N);
-  hipStream_t st = as_stream(stream);
-  const rpde_plan *pn, *pm;
-  RPDE_TRY(cf_rfft2_plans(&pn, &pm, 1, N, st));
-  return cf_irfft2(pn, pm, U, nullptr, u, B, st);
+  return 5 * arena_bytes(hs_elems(hs_geom(B, 1, N))) + arena_bytes((size_t)B * N);
 }
 
 int rpde_etd1d_steps(float* U, const float* E, const float* E2, const float* Q, const float* f1, const float* f2,
                      const float* f3, const float* g, int B, int N, int nsteps, void* ws, size_t ws_bytes, void* stream) {
   RPDE_CHECK_ARG(U && E && E2 && Q && f1 && f2 && f3 && g && ws, "etd1d_steps: null pointer");
-  ETD_CHECK_DIMS("etd1d_steps", B, N);
-  ETD_CHECK_WS("etd1d_steps", ws);
+  HS_CHECK_DIMS_1D("etd1d_steps", B, N);
+  HS_CHECK_WS("etd1d_steps", ws);
   RPDE_CHECK_ARG(nsteps >= 0, "etd1d_steps: nsteps %d < 0", nsteps);
   RPDE_CHECK_ARG(al16(U) && al16(E) && al16(E2) && al16(Q) && al16(f1) && al16(f2) && al16(f3) && al16(g),
                  "etd1d_steps: state and tables must be 16-byte aligned");
-  const EtdGeom geo = etd_geom(B, N);
-  const size_t spec = etd_spec(B, N), phys = (size_t)B * N;
+  const HalfSpec geo = hs_geom(B, 1, N);
+  const size_t spec = hs_elems(geo), phys = (size_t)B * N;
   Arena ar(ws, ws_bytes);
   EtdBufs u;
   u.v = U;
@@ -221,19 +147,16 @@ int rpde_etd1d_steps(float* U, const float* E, const float* E2, const float* Q, 
   if (!ar.ok()) { set_error("etd1d_steps: workspace too small"); return RPDE_ERR_WORKSPACE; }
   if (nsteps == 0) return RPDE_OK;
   hipStream_t st = as_stream(stream);
-  const rpde_plan *pn, *pm;
-  RPDE_TRY(cf_rfft2_plans(&pn, &pm, 1, N, st));
   const EtdTables t{E, E2, Q, f1, f2, f3, g};
-  const dim3 sg = etd_grid(geo), sb(etd_block(geo));
+  // a wave per image of at most 64 groups (N <= 510), 256 threads otherwise
+  const dim3 sb(hs_block(geo.kp / 4)), sg = hs_grid(geo.kp / 4, B, sb.x);
   const long n4 = ((long)phys + 3) / 4;
-  long qb = (n4 + 255) / 256;
-  if (qb > 2048) qb = 2048;
   // F = rfft(irfft(w)^2)
   auto product = [&](const float* w) -> int {
-    RPDE_TRY(cf_irfft2(pn, pm, w, nullptr, P, B, st));
-    hipLaunchKernelGGL(k_etd_square, dim3((unsigned)qb), dim3(256), 0, st, P, n4);
+    RPDE_TRY(hs_irfft(geo, w, nullptr, P, st));
+    hipLaunchKernelGGL(k_etd_square, dim3(hs_blocks(n4, 2048)), dim3(256), 0, st, P, n4);
     RPDE_LAUNCH_CHECK();
-    return cf_rfft2(pn, pm, P, nullptr, F, B, st);
+    return hs_rfft(geo, P, nullptr, F, st);
   };
   for (int j = 0; j < nsteps; ++j) {
     RPDE_TRY(product(u.v));
@@ -250,26 +173,6 @@ int rpde_etd1d_steps(float* U, const float* E, const float* E2, const float* Q, 
     RPDE_LAUNCH_CHECK();
   }
   return RPDE_OK;
-}
-
-size_t rpde_grf1d_ws_bytes(int B, int N) { return etd_dims_ok(B, N) ? arena_bytes(etd_spec(B, N)) : 0; }
-
-int rpde_grf1d(const float* noise, const float* sqrt_eig, float* out, int B, int N, void* ws, size_t ws_bytes,
-               void* stream) {
-  RPDE_CHECK_ARG(noise && sqrt_eig && out && ws, "grf1d: null pointer");
-  ETD_CHECK_DIMS("grf1d", B, N);
-  ETD_CHECK_WS("grf1d", ws);
-  RPDE_CHECK_ARG(((uintptr_t)noise & 7) == 0, "grf1d: noise must be 8-byte aligned");
-  const EtdGeom geo = etd_geom(B, N);
-  Arena ar(ws, ws_bytes);
-  float* h = ar.take(etd_spec(B, N));
-  if (!ar.ok()) { set_error("grf1d: workspace too small"); return RPDE_ERR_WORKSPACE; }
-  hipStream_t st = as_stream(stream);
-  const rpde_plan *pn, *pm;
-  RPDE_TRY(cf_rfft2_plans(&pn, &pm, 1, N, st));
-  hipLaunchKernelGGL(k_grf1d_half, etd_grid(geo), dim3(etd_block(geo)), 0, st, noise, sqrt_eig, h, geo);
-  RPDE_LAUNCH_CHECK();
-  return cf_irfft2(pn, pm, h, nullptr, out, B, st);
 }
 
 }  // extern "C"

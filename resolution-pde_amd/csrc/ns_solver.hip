@@ -1,8 +1,7 @@
-// Navier-Stokes vorticity generator on the unit periodic square (reference: data_generation/ns_2d.py) and the Gaussian
-// random field that seeds it (random_fields.py, dim = 2): pseudo-spectral, Crank-Nicolson on the diffusion, explicit
-// advection and forcing, 2/3 de-aliasing.  gfx950, wave64.
+// Navier-Stokes vorticity generator on the unit periodic square (reference: data_generation/ns_2d.py): pseudo-spectral,
+// Crank-Nicolson on the diffusion, explicit advection and forcing, 2/3 de-aliasing.  gfx950, wave64.
 //
-// The state is the half spectrum W = rfft2(w), [B][M][re|im][kp] (ns_solver.h).  One step is six launches on the
+// The state is the half spectrum W = rfft2(w), [B][M][re|im][kp] (halfspec.h).  One step is six launches on the
 // caller's stream, no host synchronisation:
 //   rowdft + synthesis   one batched inverse 2-D transform of the 4B derivative spectra (q^, v^, w_x^, w_y^)
 //   k_ns_advect          F_phys = q w_x + v w_y
@@ -10,24 +9,15 @@
 //   k_ns_update_fanout   W <- c_w W - c_f F + g_h, and from the NEW W the four derivative spectra of the next step
 // with the coefficient tables formed by the caller in float64 and rounded to fp32 once:
 //   a = dt visc lap / 2,  c_w = (1 - a) / (1 + a),  c_f = dt dealias / (1 + a),  g_h = dt / (1 + a) f_h,  inv_lap = 1 / lap.
-// The transforms are the full-spectrum real 2-D DFT of cf_dft.h (cf_rfft2 / cf_irfft2, GEMM form); everything else here
-// streams: a thread owns one 16-byte group of kx for both re and im, so a wave covers whole 128-byte lines of every
-// array it reads or writes.  No atomics anywhere: identical calls give identical bits.
-#include "ns_solver.h"
-#include "cf_dft.h"
-#include "pointwise.h"
+// The transforms are the full-spectrum real 2-D DFT of cf_dft.h (hs_rfft / hs_irfft, GEMM form); the rfft2 / irfft2
+// entries and the random field that seeds the solver are in halfspec.hip.  Everything else here streams: a thread owns
+// one 16-byte group of kx for both re and im, so a wave covers whole 128-byte lines of every array it reads or writes.
+// No atomics anywhere: identical calls give identical bits.
+#include "halfspec.h"
 
 namespace rpde {
 
 constexpr float NS_TWO_PI = 6.28318530717958647692f;
-
-__device__ __forceinline__ void ns_ld4(const float* p, float (&v)[4]) {
-  const float4 t = *reinterpret_cast<const float4*>(p);
-  v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-}
-__device__ __forceinline__ void ns_st4(float* p, const float (&v)[4]) {
-  *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-}
 
 // MODE 0: fan-out only (the first step of a call: W is read, not written)
 //      1: update, then fan-out of the new W
@@ -39,10 +29,10 @@ template <int MODE>
 __global__ __launch_bounds__(256) void k_ns_update_fanout(float* __restrict__ W, const float* __restrict__ F,
                                                           const float* __restrict__ gh, long gstride,
                                                           const float* __restrict__ cw, const float* __restrict__ cf,
-                                                          const float* __restrict__ il, float* __restrict__ D, NsGeom g) {
+                                                          const float* __restrict__ il, float* __restrict__ D, HalfSpec g) {
   const int b = blockIdx.y;
   const int c4n = g.kp / 4, per4 = g.M * c4n;
-  const long per = (long)g.M * 2 * g.kp, dstride = (long)g.B * per;
+  const long per = (long)g.M * 2 * g.kp, dstride = (long)g.images * per;
   float* __restrict__ Wb = W + (long)b * per;
   const float* __restrict__ Fb = F + (long)b * per;
   const float* __restrict__ gb = gh + (long)b * gstride;
@@ -51,25 +41,25 @@ __global__ __launch_bounds__(256) void k_ns_update_fanout(float* __restrict__ W,
     const int ky = v / c4n, kx0 = (v - ky * c4n) * 4;
     const long ore = (long)ky * 2 * g.kp + kx0, oim = ore + g.kp, ot = (long)ky * g.kp + kx0;
     float wr[4], wi[4];
-    ns_ld4(Wb + ore, wr);
-    ns_ld4(Wb + oim, wi);
+    ld4(Wb + ore, wr);
+    ld4(Wb + oim, wi);
     if (MODE != 0) {
       float fr[4], fi[4], gr[4], gi[4], a[4], c[4];
-      ns_ld4(Fb + ore, fr); ns_ld4(Fb + oim, fi);
-      ns_ld4(gb + ore, gr); ns_ld4(gb + oim, gi);
-      ns_ld4(cw + ot, a);   ns_ld4(cf + ot, c);
+      ld4(Fb + ore, fr); ld4(Fb + oim, fi);
+      ld4(gb + ore, gr); ld4(gb + oim, gi);
+      ld4(cw + ot, a);   ld4(cf + ot, c);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const bool live = kx0 + j < g.K;
         wr[j] = live ? fmaf(a[j], wr[j], fmaf(-c[j], fr[j], gr[j])) : 0.f;
         wi[j] = live ? fmaf(a[j], wi[j], fmaf(-c[j], fi[j], gi[j])) : 0.f;
       }
-      ns_st4(Wb + ore, wr);
-      ns_st4(Wb + oim, wi);
+      st4(Wb + ore, wr);
+      st4(Wb + oim, wi);
     }
     if (MODE != 2) {
       float li[4], qr[4], qi[4], vr[4], vi[4], xr[4], xi[4], yr[4], yi[4];
-      ns_ld4(il + ot, li);
+      ld4(il + ot, li);
       const float k1 = NS_TWO_PI * (float)(ky < g.M / 2 ? ky : ky - g.M);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -81,10 +71,10 @@ __global__ __launch_bounds__(256) void k_ns_update_fanout(float* __restrict__ W,
         xr[j] = live ? -k1 * wi[j] : 0.f;  xi[j] = live ? k1 * wr[j] : 0.f;
         yr[j] = live ? -k2 * wi[j] : 0.f;  yi[j] = live ? k2 * wr[j] : 0.f;
       }
-      ns_st4(Db + ore, qr);               ns_st4(Db + oim, qi);
-      ns_st4(Db + dstride + ore, vr);     ns_st4(Db + dstride + oim, vi);
-      ns_st4(Db + 2 * dstride + ore, xr); ns_st4(Db + 2 * dstride + oim, xi);
-      ns_st4(Db + 3 * dstride + ore, yr); ns_st4(Db + 3 * dstride + oim, yi);
+      st4(Db + ore, qr);               st4(Db + oim, qi);
+      st4(Db + dstride + ore, vr);     st4(Db + dstride + oim, vi);
+      st4(Db + 2 * dstride + ore, xr); st4(Db + 2 * dstride + oim, xi);
+      st4(Db + 3 * dstride + ore, yr); st4(Db + 3 * dstride + oim, yi);
     }
   }
 }
@@ -103,7 +93,7 @@ __global__ __launch_bounds__(256) void k_ns_advect(const float* __restrict__ P, 
 
 // out = table . spec over `images` spectra, table [M][kp] (g_h = dt / (1 + a) f_h, once per solve); grid (blocks, images)
 __global__ __launch_bounds__(256) void k_ns_scale(const float* __restrict__ spec, const float* __restrict__ table,
-                                                  float* __restrict__ out, NsGeom g) {
+                                                  float* __restrict__ out, HalfSpec g) {
   const int c4n = g.kp / 4, per4 = g.M * 2 * c4n;
   const long per = (long)g.M * 2 * g.kp;
   const float* __restrict__ sb = spec + (long)blockIdx.y * per;
@@ -111,56 +101,13 @@ __global__ __launch_bounds__(256) void k_ns_scale(const float* __restrict__ spec
   for (int v = blockIdx.x * 256 + threadIdx.x; v < per4; v += gridDim.x * 256) {
     const int row = v / c4n, kx0 = (v - row * c4n) * 4;          // row = 2 ky + (re | im)
     float s[4], t[4];
-    ns_ld4(sb + (long)row * g.kp + kx0, s);
-    ns_ld4(table + (long)(row >> 1) * g.kp + kx0, t);
+    ld4(sb + (long)row * g.kp + kx0, s);
+    ld4(table + (long)(row >> 1) * g.kp + kx0, t);
 #pragma unroll
     for (int j = 0; j < 4; ++j) s[j] = kx0 + j < g.K ? s[j] * t[j] : 0.f;
-    ns_st4(ob + (long)row * g.kp + kx0, s);
+    st4(ob + (long)row * g.kp + kx0, s);
   }
 }
-
-// noise [B][M][N][re|im] (coefficients c of the full M x N grid), se [M][N] = sqrt_eig -> the half spectrum
-// h[k] = (se[k] c[k] + conj(se[-k] c[-k])) / 2, kx = 0 .. N/2: irfft2(h) is the real part of ifft2(se . c).
-// grid (blocks, B); a thread per (ky, kx < kp), padded columns zero
-__global__ __launch_bounds__(256) void k_grf_half(const float* __restrict__ noise, const float* __restrict__ se,
-                                                  float* __restrict__ h, NsGeom g) {
-  const long per = (long)g.M * 2 * g.kp;
-  const float2* __restrict__ nb = reinterpret_cast<const float2*>(noise) + (long)blockIdx.y * g.M * g.N;
-  float* __restrict__ hb = h + (long)blockIdx.y * per;
-  const int tot = g.M * g.kp;
-  for (int e = blockIdx.x * 256 + threadIdx.x; e < tot; e += gridDim.x * 256) {
-    const int ky = e / g.kp, kx = e - ky * g.kp;
-    float re = 0.f, im = 0.f;
-    if (kx < g.K) {
-      const int my = ky ? g.M - ky : 0, mx = kx ? g.N - kx : 0;
-      const long i1 = (long)ky * g.N + kx, i2 = (long)my * g.N + mx;
-      const float2 c1 = nb[i1], c2 = nb[i2];
-      const float s1 = se[i1], s2 = se[i2];
-      re = 0.5f * fmaf(s1, c1.x, s2 * c2.x);
-      im = 0.5f * fmaf(s1, c1.y, -(s2 * c2.y));
-    }
-    hb[(long)ky * 2 * g.kp + kx] = re;
-    hb[(long)ky * 2 * g.kp + g.kp + kx] = im;
-  }
-}
-
-static bool ns_axis_ok(int n) { return n >= NS_MIN_N && n <= NS_MAX_N && n % 2 == 0; }
-static bool ns_dims_ok(int B, int M, int N) {
-  return B > 0 && B <= 65535 && ns_axis_ok(M) && ns_axis_ok(N) && 4L * B * (M > N ? M : N) < (1L << 31);
-}
-static NsGeom ns_geom(int B, int M, int N) { return NsGeom{B, M, N, N / 2 + 1, r4(N / 2 + 1)}; }
-static size_t ns_spec(int B, int M, int N) { return (size_t)B * M * 2 * r4(N / 2 + 1); }
-static unsigned ns_blocks(long items, long cap) {
-  long nb = (items + 255) / 256;
-  if (nb > cap) nb = cap;
-  return (unsigned)(nb < 1 ? 1 : nb);
-}
-
-#define NS_CHECK_WS(what, ws) \
-  RPDE_CHECK_ARG((reinterpret_cast<uintptr_t>(ws) & 255) == 0, what ": the workspace must be 256-byte aligned")
-#define NS_CHECK_DIMS(what, B, M, N)                                                                                   \
-  RPDE_CHECK_ARG(ns_dims_ok(B, M, N), what ": bad B=%d M=%d N=%d (even axes %d .. %d, 4 B max(M, N) < 2^31, B <= 65535)", \
-                 B, M, N, NS_MIN_N, NS_MAX_N)
 
 }  // namespace rpde
 
@@ -168,49 +115,22 @@ using namespace rpde;
 
 extern "C" {
 
-size_t rpde_ns2d_spec_elems(int B, int M, int N) { return ns_dims_ok(B, M, N) ? ns_spec(B, M, N) : 0; }
+size_t rpde_ns2d_spec_elems(int B, int M, int N) { return hs_dims2_ok(B, M, N) ? hs_elems(hs_geom(B, M, N)) : 0; }
 
 size_t rpde_ns2d_ws_bytes(int B, int M, int N) {
-  if (!ns_dims_ok(B, M, N)) return 0;
-  const size_t spec = ns_spec(B, M, N), phys = (size_t)B * M * N;
+  if (!hs_dims2_ok(B, M, N)) return 0;
+  const size_t spec = hs_elems(hs_geom(B, M, N)), phys = (size_t)B * M * N;
   // rpde_ns2d_steps: derivative spectra and their column stage (4B each), the four fields, their product, the
   // product's row spectra and spectrum; the transforms alone need one spectrum
   return 2 * arena_bytes(4 * spec) + arena_bytes(4 * phys) + arena_bytes(phys) + 2 * arena_bytes(spec);
 }
 
-int rpde_ns2d_rfft2(const float* w, float* W, int B, int M, int N, void* ws, size_t ws_bytes, void* stream) {
-  RPDE_CHECK_ARG(w && W && ws, "ns2d_rfft2: null pointer");
-  NS_CHECK_DIMS("ns2d_rfft2", B, M, N);
-  NS_CHECK_WS("ns2d_rfft2", ws);
-  Arena ar(ws, ws_bytes);
-  float* s1 = ar.take(ns_spec(B, M, N));
-  if (!ar.ok()) { set_error("ns2d_rfft2: workspace too small"); return RPDE_ERR_WORKSPACE; }
-  hipStream_t st = as_stream(stream);
-  const rpde_plan *pn, *pm;
-  RPDE_TRY(cf_rfft2_plans(&pn, &pm, M, N, st));
-  return cf_rfft2(pn, pm, w, s1, W, B, st);
-}
-
-int rpde_ns2d_irfft2(const float* W, float* w, int B, int M, int N, void* ws, size_t ws_bytes, void* stream) {
-  RPDE_CHECK_ARG(w && W && ws, "ns2d_irfft2: null pointer");
-  NS_CHECK_DIMS("ns2d_irfft2", B, M, N);
-  NS_CHECK_WS("ns2d_irfft2", ws);
-  Arena ar(ws, ws_bytes);
-  float* t1 = ar.take(ns_spec(B, M, N));
-  if (!ar.ok()) { set_error("ns2d_irfft2: workspace too small"); return RPDE_ERR_WORKSPACE; }
-  hipStream_t st = as_stream(stream);
-  const rpde_plan *pn, *pm;
-  RPDE_TRY(cf_rfft2_plans(&pn, &pm, M, N, st));
-  return cf_irfft2(pn, pm, W, t1, w, B, st);
-}
-
 int rpde_ns2d_scale(const float* spec, const float* table, float* out, int B, int M, int N, void* stream) {
   RPDE_CHECK_ARG(spec && table && out, "ns2d_scale: null pointer");
-  NS_CHECK_DIMS("ns2d_scale", B, M, N);
+  HS_CHECK_DIMS_2D("ns2d_scale", B, M, N);
   RPDE_CHECK_ARG(al16(spec) && al16(table) && al16(out), "ns2d_scale: pointers must be 16-byte aligned");
-  const NsGeom g = ns_geom(B, M, N);
-  hipLaunchKernelGGL(k_ns_scale, dim3(ns_blocks((long)M * 2 * (g.kp / 4), 256), B), dim3(256), 0, as_stream(stream), spec,
-                     table, out, g);
+  const HalfSpec g = hs_geom(B, M, N);
+  hipLaunchKernelGGL(k_ns_scale, hs_grid((long)M * 2 * (g.kp / 4), B), dim3(256), 0, as_stream(stream), spec, table, out, g);
   RPDE_LAUNCH_CHECK();
   return RPDE_OK;
 }
@@ -218,13 +138,13 @@ int rpde_ns2d_scale(const float* spec, const float* table, float* out, int B, in
 int rpde_ns2d_steps(float* W, const float* g_h, int g_batched, const float* c_w, const float* c_f, const float* inv_lap,
                     int B, int M, int N, int nsteps, void* ws, size_t ws_bytes, void* stream) {
   RPDE_CHECK_ARG(W && g_h && c_w && c_f && inv_lap && ws, "ns2d_steps: null pointer");
-  NS_CHECK_DIMS("ns2d_steps", B, M, N);
-  NS_CHECK_WS("ns2d_steps", ws);
+  HS_CHECK_DIMS_2D("ns2d_steps", B, M, N);
+  HS_CHECK_WS("ns2d_steps", ws);
   RPDE_CHECK_ARG(nsteps >= 0, "ns2d_steps: nsteps %d < 0", nsteps);
   RPDE_CHECK_ARG(al16(W) && al16(g_h) && al16(c_w) && al16(c_f) && al16(inv_lap),
                  "ns2d_steps: state, forcing and tables must be 16-byte aligned");
-  const NsGeom g = ns_geom(B, M, N);
-  const size_t spec = ns_spec(B, M, N), phys = (size_t)B * M * N;
+  const HalfSpec g = hs_geom(B, M, N), g4 = hs_geom(4 * B, M, N);      // the state; the four derivative fields
+  const size_t spec = hs_elems(g), phys = (size_t)B * M * N;
   Arena ar(ws, ws_bytes);
   float* D = ar.take(4 * spec);
   float* T1 = ar.take(4 * spec);
@@ -235,46 +155,21 @@ int rpde_ns2d_steps(float* W, const float* g_h, int g_batched, const float* c_w,
   if (!ar.ok()) { set_error("ns2d_steps: workspace too small"); return RPDE_ERR_WORKSPACE; }
   if (nsteps == 0) return RPDE_OK;
   hipStream_t st = as_stream(stream);
-  const rpde_plan *pn, *pm;
-  RPDE_TRY(cf_rfft2_plans(&pn, &pm, M, N, st));
-  const dim3 ug(ns_blocks((long)M * (g.kp / 4), 256), B);
-  const long gstride = g_batched ? (long)M * 2 * g.kp : 0;
+  const dim3 ug = hs_grid((long)M * (g.kp / 4), B);
+  const long gstride = g_batched ? (long)hs_per(g) : 0;
   const long n4 = (long)phys / 4;
   hipLaunchKernelGGL(k_ns_update_fanout<0>, ug, dim3(256), 0, st, W, F, g_h, gstride, c_w, c_f, inv_lap, D, g);
   RPDE_LAUNCH_CHECK();
   for (int j = 0; j < nsteps; ++j) {
-    RPDE_TRY(cf_irfft2(pn, pm, D, T1, P, 4L * B, st));
-    hipLaunchKernelGGL(k_ns_advect, dim3(ns_blocks(n4, 2048)), dim3(256), 0, st, P, Fp, n4);
+    RPDE_TRY(hs_irfft(g4, D, T1, P, st));
+    hipLaunchKernelGGL(k_ns_advect, dim3(hs_blocks(n4, 2048)), dim3(256), 0, st, P, Fp, n4);
     RPDE_LAUNCH_CHECK();
-    RPDE_TRY(cf_rfft2(pn, pm, Fp, S1, F, B, st));
+    RPDE_TRY(hs_rfft(g, Fp, S1, F, st));
     if (j + 1 < nsteps) hipLaunchKernelGGL(k_ns_update_fanout<1>, ug, dim3(256), 0, st, W, F, g_h, gstride, c_w, c_f, inv_lap, D, g);
     else hipLaunchKernelGGL(k_ns_update_fanout<2>, ug, dim3(256), 0, st, W, F, g_h, gstride, c_w, c_f, inv_lap, D, g);
     RPDE_LAUNCH_CHECK();
   }
   return RPDE_OK;
-}
-
-size_t rpde_grf2d_ws_bytes(int B, int M, int N) {
-  return ns_dims_ok(B, M, N) ? 2 * arena_bytes(ns_spec(B, M, N)) : 0;
-}
-
-int rpde_grf2d(const float* noise, const float* sqrt_eig, float* out, int B, int M, int N, void* ws, size_t ws_bytes,
-               void* stream) {
-  RPDE_CHECK_ARG(noise && sqrt_eig && out && ws, "grf2d: null pointer");
-  NS_CHECK_DIMS("grf2d", B, M, N);
-  NS_CHECK_WS("grf2d", ws);
-  RPDE_CHECK_ARG(((uintptr_t)noise & 7) == 0, "grf2d: noise must be 8-byte aligned");
-  const NsGeom g = ns_geom(B, M, N);
-  Arena ar(ws, ws_bytes);
-  float* h = ar.take(ns_spec(B, M, N));
-  float* t1 = ar.take(ns_spec(B, M, N));
-  if (!ar.ok()) { set_error("grf2d: workspace too small"); return RPDE_ERR_WORKSPACE; }
-  hipStream_t st = as_stream(stream);
-  const rpde_plan *pn, *pm;
-  RPDE_TRY(cf_rfft2_plans(&pn, &pm, M, N, st));
-  hipLaunchKernelGGL(k_grf_half, dim3(ns_blocks((long)M * g.kp, 256), B), dim3(256), 0, st, noise, sqrt_eig, h, g);
-  RPDE_LAUNCH_CHECK();
-  return cf_irfft2(pn, pm, h, t1, out, B, st);
 }
 
 }  // extern "C"

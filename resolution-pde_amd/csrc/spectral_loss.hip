@@ -2,8 +2,8 @@
 //   E(z)[b] = sum_c sum_k  omega_k c_kx / (M N) |Z[b,c,k]|^2,   Z = rfft / rfft2 of z, unnormalised,
 //   rel[b]  = sqrt(E(x - y)[b]) / (sqrt(E(y)[b]) + 1e-8),        c_kx = 1 at kx = 0 and (even N) kx = N/2, else 2
 // on the full-spectrum real 2-D DFT of cf_dft.h (cf_rfft2_plans): analysis along N, for M > 1 the complex column DFT
-// keeping every row in fft order.  A spectrum is [B*C][M][re|im][kp] (kp = N/2+1 rounded up to 4; the plan's
-// table rows past N/2 are zero).  The small kernels around the transforms:
+// keeping every row in fft order.  A spectrum is the half spectrum of halfspec.h over B*C images (the plan's table rows
+// past N/2 are zero).  The small kernels around the transforms:
 //   k_wl2_diff     d = x - y in fp32 BEFORE the transform (freq_energy.hip has the reason: for a decent model the
 //                  difference of two spectra loses the digits, the spectrum of the difference does not)
 //   k_wl2_energy   omega_k c_kx |Z|^2 summed per (field, sample, slot) in float64; k_wl2_final adds the slots in fixed
@@ -11,14 +11,12 @@
 //   k_wl2_weight   backward: coef_b omega_k D, coef_b = g_b / (sqrt(E_d) (sqrt(E_y) + 1e-8)) formed from the saved
 //                  stats and the upstream gradient on the device (0 where E_d = 0, as k_rel_l2_bwd), then the inverse
 //                  transform: d rel[b] / d x = coef_b irfft(omega . rfft(x - y))
-#include "pointwise.h"
-#include "cf_dft.h"
+#include "halfspec.h"
 #include "wave.h"
 
 namespace rpde {
 
 constexpr int WL2_SLOTS = 32;        // partial sums per (field, sample) at most
-constexpr int WL2_MAX_N = 4096;      // per axis: the full-spectrum tables are quadratic in it
 
 __global__ __launch_bounds__(256) void k_wl2_diff(const float* __restrict__ x, const float* __restrict__ y, float* __restrict__ d,
                                                   long n, int vec) {
@@ -33,7 +31,7 @@ __global__ __launch_bounds__(256) void k_wl2_diff(const float* __restrict__ x, c
   }
 }
 
-struct Wl2Geom { int B, C, M, N, K, kp, S; };
+struct Wl2Geom : HalfSpec { int B, C, S; };     // B C images; S partial sums per (field, sample)
 
 __device__ __forceinline__ float wl2_mult(int kx, int N) { return (kx == 0 || (N % 2 == 0 && kx == N / 2)) ? 1.f : 2.f; }
 
@@ -102,11 +100,11 @@ __global__ __launch_bounds__(256) void k_wl2_weight(const float* __restrict__ sd
 }
 
 static bool wl2_dims_ok(int B, int C, int M, int N) {
-  return B > 0 && C > 0 && M >= 1 && N >= 2 && M <= WL2_MAX_N && N <= WL2_MAX_N && (long)B * C * M < (1L << 31);
+  return B > 0 && C > 0 && M >= 1 && N >= 2 && M <= HS_MAX_N && N <= HS_MAX_N && (long)B * C * M < (1L << 31);
 }
 static Wl2Geom wl2_geom(int B, int C, int M, int N) {
-  Wl2Geom g{B, C, M, N, N / 2 + 1, r4(N / 2 + 1), 1};
-  const long per = (long)C * M * 2 * g.kp;
+  Wl2Geom g{hs_geom(B * C, M, N), B, C, 1};
+  const long per = (long)C * hs_per(g);
   g.S = (int)((per + 2047) / 2048 < WL2_SLOTS ? (per + 2047) / 2048 : WL2_SLOTS);
   return g;
 }
@@ -118,8 +116,7 @@ using namespace rpde;
 extern "C" {
 
 size_t rpde_wrel_l2_spec_elems(int B, int C, int M, int N) {
-  if (!wl2_dims_ok(B, C, M, N)) return 0;
-  return (size_t)B * C * M * 2 * r4(N / 2 + 1);
+  return wl2_dims_ok(B, C, M, N) ? hs_elems(hs_geom(B * C, M, N)) : 0;
 }
 
 size_t rpde_wrel_l2_ws_bytes(int B, int C, int M, int N) {
@@ -133,27 +130,24 @@ int rpde_wrel_l2_fwd(const float* x, const float* y, const float* omega, float* 
                      int B, int C, int M, int N, int size_average, void* ws, size_t ws_bytes, void* stream) {
   RPDE_CHECK_ARG(x && y && omega && stats && spec_d && ws, "wrel_l2_fwd: null pointer");
   RPDE_CHECK_ARG(wl2_dims_ok(B, C, M, N), "wrel_l2_fwd: bad B=%d C=%d M=%d N=%d (axes 2 .. %d; M = 1: one-dimensional)", B, C, M, N,
-                 WL2_MAX_N);
+                 HS_MAX_N);
   const Wl2Geom g = wl2_geom(B, C, M, N);
-  const long rows = (long)B * C;
-  const size_t spec = (size_t)rows * M * 2 * g.kp;
+  const size_t spec = hs_elems(g);
   Arena ar(ws, ws_bytes);
-  float* d = ar.take((size_t)rows * M * N);
+  float* d = ar.take((size_t)g.images * M * N);
   float* sy = ar.take(spec);
   float* s1 = ar.take(spec);
   double* part = reinterpret_cast<double*>(ar.take((size_t)2 * 2 * B * WL2_SLOTS));
   if (!ar.ok()) { set_error("wrel_l2_fwd: workspace too small"); return RPDE_ERR_WORKSPACE; }
   hipStream_t st = as_stream(stream);
-  const rpde_plan *pn, *pm;
-  RPDE_TRY(cf_rfft2_plans(&pn, &pm, M, N, st));
-  const long total = rows * M * N;
+  const long total = (long)g.images * M * N;
   const int vec = total % 4 == 0 && al16(x) && al16(y) && al16(d);
   long nb = ((vec ? total / 4 : total) + 255) / 256;
   if (nb > 2048) nb = 2048;
   hipLaunchKernelGGL(k_wl2_diff, dim3((unsigned)nb), dim3(256), 0, st, x, y, d, total, vec);
   RPDE_LAUNCH_CHECK();
-  RPDE_TRY(cf_rfft2(pn, pm, d, s1, spec_d, rows, st));
-  RPDE_TRY(cf_rfft2(pn, pm, y, s1, sy, rows, st));
+  RPDE_TRY(hs_rfft(g, d, s1, spec_d, st));
+  RPDE_TRY(hs_rfft(g, y, s1, sy, st));
   hipLaunchKernelGGL(k_wl2_energy, dim3(g.S, B, 2), dim3(256), 0, st, spec_d, sy, omega, part, g);
   RPDE_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_wl2_final, dim3(1), dim3(256), 0, st, part, rel, loss, stats, g, size_average);
@@ -165,24 +159,21 @@ int rpde_wrel_l2_bwd(const float* spec_d, const float* omega, const float* stats
                      float* grad_x, int B, int C, int M, int N, int size_average, void* ws, size_t ws_bytes, void* stream) {
   RPDE_CHECK_ARG(spec_d && omega && stats && grad_x && ws && (grad_loss || grad_rel), "wrel_l2_bwd: null pointer");
   RPDE_CHECK_ARG(wl2_dims_ok(B, C, M, N), "wrel_l2_bwd: bad B=%d C=%d M=%d N=%d (axes 2 .. %d; M = 1: one-dimensional)", B, C, M, N,
-                 WL2_MAX_N);
+                 HS_MAX_N);
   const Wl2Geom g = wl2_geom(B, C, M, N);
-  const long rows = (long)B * C;
-  const size_t spec = (size_t)rows * M * 2 * g.kp;
+  const size_t spec = hs_elems(g);
   Arena ar(ws, ws_bytes);
   float* w = ar.take(spec);
   float* t1 = ar.take(spec);
   if (!ar.ok()) { set_error("wrel_l2_bwd: workspace too small"); return RPDE_ERR_WORKSPACE; }
   hipStream_t st = as_stream(stream);
-  const rpde_plan *pn, *pm;
-  RPDE_TRY(cf_rfft2_plans(&pn, &pm, M, N, st));
-  const long per = (long)C * M * 2 * g.kp;
+  const long per = (long)C * hs_per(g);
   long nb = (per + 1023) / 1024;
   if (nb > 256) nb = 256;
   hipLaunchKernelGGL(k_wl2_weight, dim3((unsigned)nb, B), dim3(256), 0, st, spec_d, omega, stats, grad_loss, grad_rel, w, g,
                      size_average);
   RPDE_LAUNCH_CHECK();
-  return cf_irfft2(pn, pm, w, t1, grad_x, rows, st);
+  return hs_irfft(g, w, t1, grad_x, st);
 }
 
 }  // extern "C"

@@ -995,6 +995,39 @@ def freq_energy2d(pred: torch.Tensor, target: torch.Tensor, num_radial_bins: int
 # data_generation/ns_2d.py and random_fields.py are the callers).  Data production: no autograd, GPU tensors only,
 # no CPU fallback.
 # ----------------------------------------------------------------------------
+def _kp(N: int) -> int:
+    """padded length of a half spectrum's contiguous axis: N//2+1 rounded up to 4 (csrc/halfspec.h)"""
+    return (N // 2 + 1 + 3) // 4 * 4
+
+
+def _grid(t: torch.Tensor, what: str, d: int):
+    """the dims of a batch of d-dimensional fields, [B, N] or [B, M, N], refused as the C side refuses them"""
+    names = ("B", "N") if d == 1 else ("B", "M", "N")
+    if t.dim() != d + 1:
+        raise ValueError(f"{what}: expected [{', '.join(names)}], got {tuple(t.shape)}")
+    dims = tuple(int(v) for v in t.shape)
+    if (load().rpde_etd1d_ws_bytes if d == 1 else load().rpde_ns2d_ws_bytes)(*dims) == 0:
+        raise ValueError(f"{what}: unsupported grid {' '.join(f'{n}={v}' for n, v in zip(names, dims))} "
+                         + ("(N even, 4 .. 4096, B <= 65535)" if d == 1 else "(even axes 4 .. 4096)"))
+    return dims
+
+
+def _grf(what: str, d: int, noise: torch.Tensor, sqrt_eig: torch.Tensor) -> torch.Tensor:
+    """noise [B, *grid, 2], sqrt_eig [*grid] of d dimensions -> [B, *grid] through rpde_grf1d / rpde_grf2d"""
+    lib = load()
+    if noise.dim() != d + 2 or noise.shape[-1] != 2 or tuple(sqrt_eig.shape) != tuple(noise.shape[1:-1]):
+        raise ValueError(f"{what}: noise {tuple(noise.shape)} / sqrt_eig {tuple(sqrt_eig.shape)}, expected "
+                         + ("[B, N, 2] and [N]" if d == 1 else "[B, M, N, 2] and [M, N]"))
+    noise, sqrt_eig = _f32c(noise.detach()), _f32c(sqrt_eig.detach())
+    pn, ps = ptr(noise), ptr(sqrt_eig)                     # raises for CPU tensors: there is no fallback
+    dims = _grid(noise[..., 0], what, d)
+    out = torch.empty(dims, dtype=torch.float32, device=noise.device)
+    nws = getattr(lib, f"rpde_{what}_ws_bytes")(*dims)
+    ws = workspace(nws, noise.device)
+    check(getattr(lib, f"rpde_{what}")(pn, ps, ptr(out), *dims, ws.data_ptr(), nws, stream_ptr()), what)
+    return out
+
+
 def ns2d_tables(M: int, N: int, visc: float, dt: float):
     """(c_w, c_f, c_g, inv_lap): the step's coefficient tables, float32 [M, kp] host tensors (kp = N//2+1 rounded up to
     4, padded columns zero), formed in float64 and rounded once.  k1 = fftfreq(M) M (signed, Nyquist -M/2),
@@ -1003,7 +1036,7 @@ def ns2d_tables(M: int, N: int, visc: float, dt: float):
     1 for this division only."""
     import math
     M, N = int(M), int(N)
-    K, kp = N // 2 + 1, (N // 2 + 1 + 3) // 4 * 4
+    K, kp = N // 2 + 1, _kp(N)
     k1 = (torch.fft.fftfreq(M, dtype=torch.float64) * M).round().view(M, 1)
     k2 = torch.arange(K, dtype=torch.float64).view(1, K)
     lap = 4.0 * math.pi ** 2 * (k1 ** 2 + k2 ** 2)
@@ -1019,30 +1052,11 @@ def ns2d_tables(M: int, N: int, visc: float, dt: float):
     return tuple(out)
 
 
-def _grid3(t: torch.Tensor, what: str):
-    if t.dim() != 3:
-        raise ValueError(f"{what}: expected [B, M, N], got {tuple(t.shape)}")
-    B, M, N = (int(v) for v in t.shape)
-    if load().rpde_ns2d_ws_bytes(B, M, N) == 0:
-        raise ValueError(f"{what}: unsupported grid B={B} M={M} N={N} (even axes 4 .. 4096)")
-    return B, M, N
-
-
 def grf2d(noise: torch.Tensor, sqrt_eig: torch.Tensor) -> torch.Tensor:
     """noise [B, M, N, 2] (real and imaginary part of the coefficients of the full M x N grid, standard normal),
     sqrt_eig [M, N] -> [B, M, N] = Re ifft2(sqrt_eig . noise), torch's 1/(M N) included.  The HIP side is deterministic
     given the noise.  Contiguous fp32 tensors on the GPU; no autograd, no CPU fallback."""
-    lib = load()
-    if noise.dim() != 4 or noise.shape[-1] != 2 or tuple(sqrt_eig.shape) != tuple(noise.shape[1:3]):
-        raise ValueError(f"grf2d: noise {tuple(noise.shape)} / sqrt_eig {tuple(sqrt_eig.shape)}, expected [B, M, N, 2] and [M, N]")
-    noise, sqrt_eig = _f32c(noise.detach()), _f32c(sqrt_eig.detach())
-    pn, ps = ptr(noise), ptr(sqrt_eig)                     # raises for CPU tensors: there is no fallback
-    B, M, N = _grid3(noise[..., 0], "grf2d")
-    out = torch.empty(B, M, N, dtype=torch.float32, device=noise.device)
-    nws = lib.rpde_grf2d_ws_bytes(B, M, N)
-    ws = workspace(nws, noise.device)
-    check(lib.rpde_grf2d(pn, ps, ptr(out), B, M, N, ws.data_ptr(), nws, stream_ptr()), "grf2d")
-    return out
+    return _grf("grf2d", 2, noise, sqrt_eig)
 
 
 def ns2d_solve(w0: torch.Tensor, f: torch.Tensor, visc: float, dt: float, steps: int, record_every: int) -> torch.Tensor:
@@ -1057,7 +1071,7 @@ def ns2d_solve(w0: torch.Tensor, f: torch.Tensor, visc: float, dt: float, steps:
         raise ValueError(f"ns2d_solve: bad steps={steps} record_every={record_every}")
     w0, f = _f32c(w0.detach()), _f32c(f.detach())
     pw, _ = ptr(w0), ptr(f)                                # raises for CPU tensors: there is no fallback
-    B, M, N = _grid3(w0, "ns2d_solve")
+    B, M, N = _grid(w0, "ns2d_solve", 2)
     if tuple(f.shape) not in ((M, N), (B, M, N)):
         raise ValueError(f"ns2d_solve: forcing {tuple(f.shape)}, expected {(M, N)} or {(B, M, N)}")
     fb = 1 if f.dim() == 2 else B
@@ -1104,7 +1118,7 @@ def etd1d_tables(N: int, length: float, c2: float, c4: float, dt: float, advect:
         raise ValueError(f"etd1d_tables: N must be even and >= 4, got {N}")
     if not (float(length) > 0 and float(dt) > 0):
         raise ValueError(f"etd1d_tables: length and dt must be positive, got length={length} dt={dt}")
-    K, kp = N // 2 + 1, (N // 2 + 1 + 3) // 4 * 4
+    K, kp = N // 2 + 1, _kp(N)
     n = torch.arange(K, dtype=torch.float64)
     kappa = (2.0 * math.pi / float(length)) * n
     h = float(dt)
@@ -1133,30 +1147,11 @@ def etd1d_tables(N: int, length: float, c2: float, c4: float, dt: float, advect:
     return tuple(out)
 
 
-def _grid2(t: torch.Tensor, what: str):
-    if t.dim() != 2:
-        raise ValueError(f"{what}: expected [B, N], got {tuple(t.shape)}")
-    B, N = (int(v) for v in t.shape)
-    if load().rpde_etd1d_ws_bytes(B, N) == 0:
-        raise ValueError(f"{what}: unsupported grid B={B} N={N} (N even, 4 .. 4096, B <= 65535)")
-    return B, N
-
-
 def grf1d(noise: torch.Tensor, sqrt_eig: torch.Tensor) -> torch.Tensor:
     """noise [B, N, 2] (real and imaginary part of the coefficients in fft order, standard normal), sqrt_eig [N] ->
     [B, N] = Re ifft(sqrt_eig . noise), torch's 1/N included.  The HIP side is deterministic given the noise.
     Contiguous fp32 tensors on the GPU; no autograd, no CPU fallback."""
-    lib = load()
-    if noise.dim() != 3 or noise.shape[-1] != 2 or tuple(sqrt_eig.shape) != tuple(noise.shape[1:2]):
-        raise ValueError(f"grf1d: noise {tuple(noise.shape)} / sqrt_eig {tuple(sqrt_eig.shape)}, expected [B, N, 2] and [N]")
-    noise, sqrt_eig = _f32c(noise.detach()), _f32c(sqrt_eig.detach())
-    pn, ps = ptr(noise), ptr(sqrt_eig)                     # raises for CPU tensors: there is no fallback
-    B, N = _grid2(noise[..., 0], "grf1d")
-    out = torch.empty(B, N, dtype=torch.float32, device=noise.device)
-    nws = lib.rpde_grf1d_ws_bytes(B, N)
-    ws = workspace(nws, noise.device)
-    check(lib.rpde_grf1d(pn, ps, ptr(out), B, N, ws.data_ptr(), nws, stream_ptr()), "grf1d")
-    return out
+    return _grf("grf1d", 1, noise, sqrt_eig)
 
 
 def etd1d_solve(u0: torch.Tensor, tables, steps: int, record_every: int) -> torch.Tensor:
@@ -1171,8 +1166,8 @@ def etd1d_solve(u0: torch.Tensor, tables, steps: int, record_every: int) -> torc
         raise ValueError(f"etd1d_solve: bad steps={steps} record_every={record_every}")
     u0 = _f32c(u0.detach())
     pu = ptr(u0)                                           # raises for CPU tensors: there is no fallback
-    B, N = _grid2(u0, "etd1d_solve")
-    kp = (N // 2 + 1 + 3) // 4 * 4
+    B, N = _grid(u0, "etd1d_solve", 1)
+    kp = _kp(N)
     tables = tuple(tables)
     if len(tables) != 7 or any(tuple(t.shape) != (kp,) for t in tables):
         raise ValueError(f"etd1d_solve: expected the seven [{kp}] tables of etd1d_tables(N={N}, ...)")

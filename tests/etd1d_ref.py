@@ -30,8 +30,9 @@ import math
 
 import torch
 
-# (B, N): kp padding of 3 columns each, a non-power-of-two grid, odd B
-CASES = [(3, 16), (2, 48), (2, 64), (1, 128), (2, 200), (2, 256)]
+# (B, N): kp padding of 3 columns each, a non-power-of-two grid, odd B; N = 512 is the first grid with more than 64
+# 16-byte groups per image, where the stage kernels launch 256 threads instead of 64
+CASES = [(3, 16), (2, 48), (2, 64), (1, 128), (2, 200), (2, 256), (1, 512)]
 STEPS, SNAPSHOTS = 80, 4
 KS_NU, KS_DT = 0.05, 0.01
 BURGERS_NU, BURGERS_DT, BURGERS_L = 0.1, 5e-3, 2.0

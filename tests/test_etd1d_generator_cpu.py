@@ -146,6 +146,19 @@ def test_gaussian_rf_1d_table_and_errors():
         GaussianRF(1, 64)
 
 
+@pytest.mark.parametrize("N", [4, 64, 200, 4096])
+@pytest.mark.parametrize("alpha,tau,sigma", [(2, 3, None), (2, 5, 25)])
+def test_sqrt_eig_1d_is_row_zero_of_the_2d_table(N, alpha, tau, sigma):
+    """M = 1: k1 = 0 adds an exact zero and the factor M N is N, so the 2-D function is the 1-D one bit for bit"""
+    from data_generation.random_fields import sqrt_eig_1d, sqrt_eig_2d
+    if sigma is None:
+        sigma = tau ** (0.5 * (2 * alpha - 1))
+    one, two = sqrt_eig_1d(N, alpha, tau, sigma), sqrt_eig_2d(1, N, alpha, tau, sigma)
+    assert tuple(one.shape) == (N,) and tuple(two.shape) == (1, N)
+    assert torch.equal(one, two[0])
+    assert torch.equal(one, R.sqrt_eig(N, alpha, tau, sigma).float())
+
+
 def test_schedule_arithmetic():
     from data_generation.etd1d import snapshot_schedule
     from data_generation.ks_1d import ks_schedule

@@ -3,7 +3,12 @@ grf2d, data_generation/ns_2d.py / random_fields.py) against the float64 restatem
 
 The bound everywhere is FLOOR_FACTOR = 4 times the restatement's own float32 error on the same inputs (`floor32`): a
 margin over what the reference's fp32 arithmetic loses, not a measured device number.  Measured on the MI355X
-(device error / floor32, worst snapshot per case) -- see DESIGN.md "NS vorticity generator"."""
+(device error / floor32, worst snapshot per case) -- see DESIGN.md "NS vorticity generator".  The random field there
+(device error / floor32):
+
+    GaussianRF 32, 64 and ops.grf2d 16x24           see DESIGN.md
+    ops.grf2d (M, N), the edges of the group layout
+    (4, 6)    1.16      (4, 8)    1.07      (6, 10)   1.36      (4, 12)   1.00      (12, 6)   1.30"""
 import math
 
 import numpy as np
@@ -114,6 +119,16 @@ def test_grf_rectangular_through_ops(gpu_device):
     noise = R.noise64(3, M, N, seed=6)
     se64 = R.sqrt_eig(M, N, 2.5, 7)
     _grf_check("ops.grf2d 16x24", ops.grf2d(_dev(noise, gpu_device), _dev(se64, gpu_device)), noise, se64)
+
+
+@pytest.mark.parametrize("M,N", [(4, 6), (4, 8), (6, 10), (4, 12), (12, 6)])
+def test_grf_group_edges_through_ops(gpu_device, M, N):
+    """K = N/2 + 1 = 4, 5, 6, 7, 4: every remainder of the last 16-byte group of a row, on rectangles both ways and
+    with an M that is no power of two -- the last group's padding and the partner index (M - ky) % M, (N - kx) % N"""
+    from rpde import ops
+    noise = R.noise64(3, M, N, seed=8)
+    se64 = R.sqrt_eig(M, N, 2.5, 7)
+    _grf_check(f"ops.grf2d {M}x{N}", ops.grf2d(_dev(noise, gpu_device), _dev(se64, gpu_device)), noise, se64)
 
 
 def test_grf_sampling_is_reproducible(gpu_device):
