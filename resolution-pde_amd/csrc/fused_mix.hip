@@ -269,9 +269,16 @@ __global__ __launch_bounds__(256, 2) void k_mix_h2(const MixP P) {
 // channels of each tensor is staged in LDS as f16 pieces in memory order and read back with transposing reads
 // (ds_read_b64_tr_b16) -- the same register image serves as A operand (rows = channels i) and as B operand (columns =
 // channels o).  Wave w owns the output rows i = 16w .. 16w + 15 of both gWr and gWi (8 accumulator tiles); one
-// workgroup per (axis, mode, slab of lines); slabs are folded in fixed order by k_mix_wgrad_fold.  One power-of-two
-// scale per tensor and axis, from the line maxima the analysis kernels leave (a product's error scales with the OTHER
-// operand's magnitude, so modes far below the maximum keep their relative accuracy).
+// workgroup per (axis, mode, slab of lines); slabs are folded in fixed order by k_mix_wgrad_fold.  Scales: the reduction
+// index is the line, so the two scales of a line must multiply to ONE constant for the whole axis -- but each line may
+// split that constant its own way.  With Es, Eg the exponents of a line's maxima (left by the analysis kernels) and
+// P = max over the lines of Es + Eg, the line's spectrum is scaled by 2^(141 - Es) -- its own maximum in [2^14, 2^15),
+// like every other h2 block -- and its gradient spectrum by 2^(141 - P + Es), which puts it Es + Eg - P binary places
+// below that: a line keeps full resolution unless its PRODUCT is small against the largest product, and then it
+// contributes as little to the sum.  (One scale per tensor lost a sample that is 2^20 smaller than its neighbour in x and
+// as much larger in the cotangent: 2^-19 per element, 16 times the float32 error in the worst mode of the gradient.)
+// Within a line a product's error scales with the OTHER operand's magnitude, so modes far below the line's maximum
+// keep their relative accuracy.
 // Replaces the 128 x 128 real-block GEMM + unpack per axis of round 2 (2 x (52 + 26) us at B = 32).
 // ------------------------------------------------------------------------------------------------------------
 struct MixWgP {
@@ -284,31 +291,30 @@ struct MixWgP {
 
 __global__ __launch_bounds__(256, 2) void k_mix_wgrad_h2(const MixWgP P) {
   __shared__ __attribute__((aligned(16))) char smem[4 * 8192];      // pieces spec re, spec im, g re, g im: [hi 4 KB | lo 4 KB]
-  __shared__ float red[2][4];
+  __shared__ float red[4];
   const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, g = l >> 4, li = l & 15;
   const int k = blockIdx.x, s = blockIdx.y, a = blockIdx.z;
   const long lines = P.lines[a];
   const long tiles = lines / 32, tps = (tiles + P.S - 1) / P.S;
   const long t0 = s * tps, t1 = min(t0 + tps, tiles);
   float* const slab = P.slabs + (((long)s * 2 + a) * P.kp + k) * (64 * 64 * 2);
-  // ---- scales: max over the axis' line maxima ----
-  float ms = 0.f, mg = 0.f;
-  for (long i = tid; i < lines; i += 256) { ms = fmaxf(ms, P.amax_s[a][i]); mg = fmaxf(mg, P.amax_g[a][i]); }
-  ms = wave_max(ms); mg = wave_max(mg);
-  if (l == 0) { red[0][w] = ms; red[1][w] = mg; }
+  // ---- P: the largest sum of the exponent fields of a line's two maxima (each clamped like h2_scale's) ----
+  auto expo = [](float m) { return max((int)(__float_as_uint(m) >> 23) & 0xff, 15); };
+  float pm = 0.f;                                       // (small integers: exact in a float, so wave_max serves)
+  for (long i = tid; i < lines; i += 256) pm = fmaxf(pm, (float)(expo(P.amax_s[a][i]) + expo(P.amax_g[a][i])));
+  pm = wave_max(pm);
+  if (l == 0) red[w] = pm;
   __syncthreads();
-  ms = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
-  mg = fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3]));
-  float sc_s, iv_s, sc_g, iv_g;
-  h2_scale(ms, 0, sc_s, iv_s);
-  h2_scale(mg, 0, sc_g, iv_g);
+  const int Psum = (int)fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));      // 30 .. 508
 
   // staging: thread -> line tid >> 3 of the tile, 16 consecutive floats (tid & 7) of the line's 128 (re 64 | im 64)
   const int sl = tid >> 3, ch = tid & 7, part = ch >> 2, c80 = 4 * (ch & 3);
   const long lstride = (long)P.R * 64;
   float4 rs[4], rg[4];
+  float am_s = 0.f;                                     // maximum of this thread's line of the saved spectra
   auto issue = [&](long t) {
     const long off = (t * 32 + sl) * lstride + k * 128 + ch * 16;
+    am_s = P.amax_s[a][t * 32 + sl];
     const float4* ps = reinterpret_cast<const float4*>(P.spec[a] + off);
     const float4* pg = reinterpret_cast<const float4*>(P.gspec[a] + off);
 #pragma unroll
@@ -342,8 +348,13 @@ __global__ __launch_bounds__(256, 2) void k_mix_wgrad_h2(const MixWgP P) {
   for (int ot = 0; ot < 4; ++ot) { cr[ot] = (f32x4v){0.f, 0.f, 0.f, 0.f}; ci[ot] = (f32x4v){0.f, 0.f, 0.f, 0.f}; }
   if (t0 < t1) issue(t0);
   for (long t = t0; t < t1; ++t) {
-    put(rs, part, sc_s);              // pieces 0 / 1: spectra re / im
-    put(rg, 2 + part, sc_g);          // pieces 2 / 3: gradient spectra re / im
+    {
+      const int Es = expo(am_s), fg = 268 - Psum + Es;                 // fg <= 253; below 1 the line's products vanish
+      const float sc_s = __uint_as_float((unsigned)(268 - Es) << 23);
+      const float sc_g = fg >= 1 ? __uint_as_float((unsigned)fg << 23) : 0.f;
+      put(rs, part, sc_s);            // pieces 0 / 1: spectra re / im
+      put(rg, 2 + part, sc_g);        // pieces 2 / 3: gradient spectra re / im
+    }
     if (t + 1 < t1) issue(t + 1);
     lds_barrier();
     // A operands: this wave's 16 channels i of the saved spectra
@@ -367,13 +378,15 @@ __global__ __launch_bounds__(256, 2) void k_mix_wgrad_h2(const MixWgP P) {
     lds_barrier();
   }
   // rows i = 16 w + 4 g + jj, column o = 16 ot + li: (gWr, gWi) pairs
-  const float inv = iv_s * iv_g;
+  // the product of a line's scales is 2^(282 - Psum) on every line; undone in two exact steps, each a normal number
+  const int ea = (Psum - 282) >> 1, eb = (Psum - 282) - ea;             // -126 .. 113
+  const float inv_a = __uint_as_float((unsigned)(127 + ea) << 23), inv_b = __uint_as_float((unsigned)(127 + eb) << 23);
 #pragma unroll
   for (int ot = 0; ot < 4; ++ot)
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) {
       const int i = 16 * w + 4 * g + jj, o = 16 * ot + li;
-      *reinterpret_cast<float2*>(slab + (i * 64 + o) * 2) = make_float2(cr[ot][jj] * inv, ci[ot][jj] * inv);
+      *reinterpret_cast<float2*>(slab + (i * 64 + o) * 2) = make_float2(cr[ot][jj] * inv_a * inv_b, ci[ot][jj] * inv_a * inv_b);
     }
 }
 
