@@ -402,6 +402,37 @@ int rpde_wrel_l2_bwd(const float* spec_d, const float* omega, const float* stats
                      const float* grad_rel, float* grad_x, int B, int C, int M, int N, int size_average,
                      void* ws, size_t ws_bytes, void* stream);
 
+/* ---- per-sample, per-band spectral energies, forward and backward (csrc/band_energy.hip, rpde.ops.band_energy;
+ * utils/loss.py BandRelativeL2Loss and SpectrumMatchingLoss; an interface addition, the reference has none).
+ * x, y [B, C, M, N] fp32 channels-first, M = 1 for one-dimensional fields.  The field z is x, or x - y formed in fp32
+ * before the transform when y is not NULL.  With Z = rfft / rfft2 (unnormalised), c_kx = 1 at kx = 0 and (even N)
+ * kx = N/2, else 2, and a band in {-1, 0 .. J-1} for every entry (ky, kx) of the half spectrum, rows in fft order:
+ *   E[b, j] = sum_c sum_{(ky,kx): band = j} c_kx / (M N) |Z[b,c,ky,kx]|^2          E [B, J] floats
+ * Entries of band -1 belong to no band; if every entry has one, sum_j E[b, j] = sum |z[b]|^2 (Parseval).
+ * Backward, for gE [B, J]:  grad_x[b, c] = 2 irfft2(gE[b, band(ky,kx)] Z[b,c,ky,kx]), weight 0 where band = -1, irfft2
+ * with 1 / (M N) and Im of the self-conjugate bins of the last axis ignored.  No gradient for y.  It is the gradient
+ * only if, in 2-D, the columns kx = 0 and (even N) kx = N/2 of the band table are symmetric in ky
+ * (band[ky] == band[(M - ky) % M]): the caller checks it (rpde.ops.check_band_table).
+ * Device tables, int32, built once per (grid, table) by the caller (rpde.ops.band_tables):
+ *   forward   entries [n_entries], start [J+1]: band j owns entries[start[j] .. start[j+1]), each entry
+ *             (offset << 1) | (c_kx == 2), offset = ky 2 kp + kx: where Re of (ky, kx) sits in ONE image's half spectrum
+ *             (Im is kp further), kp = N/2+1 rounded up to 4; entries of band -1 are not listed
+ *   backward  band [M][kp]: the band of every entry, the padded columns -1; 16-byte aligned
+ * The kernels skip an offset outside the image, a start[] outside entries[] and a band outside 0 .. J-1.
+ * spec (the spec_elems query's count of floats, or NULL: not kept) receives the half spectrum of z,
+ * [B C][M][re|im][kp] with the padded columns zero, and is what the backward call takes.
+ * Grids as rpde_wrel_l2_* (axes 2 .. 4096) with 1 <= J <= 4096: otherwise the two queries return 0.  The transforms
+ * and plans are those of rpde_wrel_l2_* (first use of a grid allocates and synchronises).  The sums are float64 in two
+ * fixed-order stages without atomics: identical calls give identical bits, and a sample's energies do not depend on
+ * the batch around it.  The workspace is 256-byte aligned.  Argument errors are reported before any device work. */
+size_t rpde_band_energy_ws_bytes(int B, int C, int M, int N, int J);
+size_t rpde_band_energy_spec_elems(int B, int C, int M, int N);
+int rpde_band_energy_fwd(const float* x, const float* y, const int32_t* entries, const int32_t* start, int n_entries,
+                         float* E, float* spec, int B, int C, int M, int N, int J, void* ws, size_t ws_bytes,
+                         void* stream);
+int rpde_band_energy_bwd(const float* spec, const int32_t* band, const float* gE, float* grad_x, int B, int C, int M,
+                         int N, int J, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- NS vorticity generator (reference: data_generation/ns_2d.py, random_fields.py): 2-D Navier-Stokes in vorticity
  * form on the periodic unit square, pseudo-spectral (csrc/ns_solver.hip), and the Gaussian random field that seeds it
  * and the rfft2 / irfft2 calls (csrc/halfspec.hip), on the half-spectrum layer of csrc/halfspec.h over the 2-D transforms of

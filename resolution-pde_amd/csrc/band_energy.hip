@@ -1,0 +1,191 @@
+// Per-sample, per-band spectral energies of a field, forward and backward (rpde.ops.band_energy; utils/loss.py
+// BandRelativeL2Loss and SpectrumMatchingLoss are built on it; no counterpart in the reference)
+//   E[b, j] = sum_c sum_{(ky,kx): band = j}  c_kx / (M N) |Z[b,c,ky,kx]|^2,   Z = rfft / rfft2 of z, unnormalised,
+//   c_kx = 1 at kx = 0 and (even N) kx = N/2, else 2;  band in {-1, 0 .. J-1}, -1: the entry belongs to no band
+//   grad_z[b, c] = 2 irfft2(gE[b, band(ky,kx)] Z[b,c,ky,kx]),  weight 0 where band = -1
+// on the half-spectrum layer of halfspec.h (hs_rfft / hs_irfft: the plans of the loss, the resizers, the generators).
+// The field is x, or x - y formed in fp32 BEFORE the transform (k_be_diff; freq_energy.hip has the reason).
+//
+// The band table reaches the kernels in two forms, both built once per (grid, table) by rpde.ops:
+//   entries [n_entries], start [J+1]   the entries of band j are entries[start[j] .. start[j+1]), each
+//                                      (offset << 1) | (c_kx == 2) with offset = ky 2 kp + kx the position of Re in ONE
+//                                      image's spectrum (Im sits kp further); forward only
+//   band [M][kp]                       the band of every entry, padded columns -1; backward only
+// so that a (sample, band) sum reads exactly the entries of its band, not the whole table:
+//   k_be_partial   a wave per (sample, band, slot): |Z|^2 c_kx over its share of the band's entries and the C channels in
+//                  float64, lanes in a fixed order; k_be_final adds the slots in order and scales by 1 / (M N) -- the
+//                  k_wl2_energy / k_wl2_final pattern, no atomics: identical calls, identical bits, and a sample's
+//                  energies do not depend on the batch it sits in
+//   k_be_scale     backward: a thread per 16-byte group of kx gathers gE[b, band] for its four entries and writes
+//                  2 gE Z (zeros where band = -1 and in the padded columns), the spectrum the inverse transform reads
+// An offset outside the image, a start[] outside entries[] and a band outside 0 .. J-1 are skipped, not trusted.
+#include "halfspec.h"
+#include "wave.h"
+
+namespace rpde {
+
+constexpr int BE_SLOTS = 32;         // partial sums per (sample, band) at most
+constexpr int BE_MAX_BANDS = 4096;
+
+__global__ __launch_bounds__(256) void k_be_diff(const float* __restrict__ x, const float* __restrict__ y, float* __restrict__ d,
+                                                 long n, int vec) {
+  const long i0 = (long)blockIdx.x * 256 + threadIdx.x, step = (long)gridDim.x * 256;
+  if (vec) {
+    for (long i = i0; i < n / 4; i += step) {
+      const float4 a = reinterpret_cast<const float4*>(x)[i], b = reinterpret_cast<const float4*>(y)[i];
+      reinterpret_cast<float4*>(d)[i] = make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w);
+    }
+  } else {
+    for (long i = i0; i < n; i += step) d[i] = x[i] - y[i];
+  }
+}
+
+struct BeGeom : HalfSpec { int B, C, J, S; };     // B C images; S partial sums per (sample, band)
+
+// grid (ceil(J / 4), S, samples): wave w of a workgroup takes band 4 blockIdx.x + w; part[(b J + j) S + slot]
+__global__ __launch_bounds__(256) void k_be_partial(const float* __restrict__ spec, const int* __restrict__ entries,
+                                                    const int* __restrict__ start, int n_entries,
+                                                    double* __restrict__ part, BeGeom g) {
+  const int lane = threadIdx.x & 63, j = (int)blockIdx.x * 4 + (threadIdx.x >> 6), slot = blockIdx.y;
+  if (j >= g.J) return;
+  const long per = (long)g.M * 2 * g.kp;
+  int e0 = start[j], e1 = start[j + 1];
+  if (e0 < 0) e0 = 0;
+  if (e1 > n_entries) e1 = n_entries;
+  for (int b = blockIdx.z; b < g.B; b += gridDim.z) {
+    double acc = 0.0;
+    for (int c = 0; c < g.C; ++c) {
+      const float* __restrict__ sp = spec + ((long)b * g.C + c) * per;
+      for (long e = (long)e0 + slot * 64 + lane; e < e1; e += (long)g.S * 64) {
+        const int en = entries[e], off = en >> 1;
+        if (off < 0 || off + g.kp >= per) continue;
+        const double re = (double)sp[off], im = (double)sp[off + g.kp];
+        acc += ((en & 1) ? 2.0 : 1.0) * (re * re + im * im);
+      }
+    }
+    acc = wave_sum(acc);
+    if (lane == 0) part[((long)b * g.J + j) * g.S + slot] = acc;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_be_final(const double* __restrict__ part, float* __restrict__ E, BeGeom g) {
+  const double inv = 1.0 / ((double)g.M * (double)g.N);
+  const long n = (long)g.B * g.J;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    double s = 0.0;
+    for (int q = 0; q < g.S; ++q) s += part[i * g.S + q];
+    E[i] = (float)(s * inv);
+  }
+}
+
+// grid hs_grid(groups of an image, images): w = 2 gE[b, band] Z
+__global__ __launch_bounds__(256) void k_be_scale(const float* __restrict__ spec, const int* __restrict__ band,
+                                                  const float* __restrict__ gE, float* __restrict__ w, BeGeom g) {
+  const long per = (long)g.M * 2 * g.kp;
+  const int groups = (int)(per / 4);
+  for (int img = blockIdx.y; img < g.images; img += gridDim.y) {
+    const float* __restrict__ ge = gE + (long)(img / g.C) * g.J;
+    for (int gi = blockIdx.x * blockDim.x + threadIdx.x; gi < groups; gi += gridDim.x * blockDim.x) {
+      const int e = gi * 4, row = e / g.kp, kx0 = e - row * g.kp;
+      const int4 bd = *reinterpret_cast<const int4*>(band + (long)(row >> 1) * g.kp + kx0);
+      const int bj[4] = {bd.x, bd.y, bd.z, bd.w};
+      float v[4];
+      ld4(spec + (long)img * per + e, v);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[i] = (bj[i] >= 0 && bj[i] < g.J) ? (2.f * ge[bj[i]]) * v[i] : 0.f;
+      st4(w + (long)img * per + e, v);
+    }
+  }
+}
+
+// the grids of rpde_wrel_l2_*, and a band count in range
+static bool be_dims_ok(int B, int C, int M, int N, int J) {
+  return B > 0 && C > 0 && M >= 1 && N >= 2 && M <= HS_MAX_N && N <= HS_MAX_N && (long)B * C * M < (1L << 31) && J >= 1 &&
+         J <= BE_MAX_BANDS;
+}
+static BeGeom be_geom(int B, int C, int M, int N, int J) {
+  BeGeom g{hs_geom(B * C, M, N), B, C, J, 1};
+  const long most = (long)C * M * g.K;            // no band owns more terms than a sample has
+  g.S = (int)((most + 2047) / 2048 < BE_SLOTS ? (most + 2047) / 2048 : BE_SLOTS);
+  return g;
+}
+
+}  // namespace rpde
+
+using namespace rpde;
+
+extern "C" {
+
+size_t rpde_band_energy_spec_elems(int B, int C, int M, int N) {
+  return be_dims_ok(B, C, M, N, 1) ? hs_elems(hs_geom(B * C, M, N)) : 0;
+}
+
+size_t rpde_band_energy_ws_bytes(int B, int C, int M, int N, int J) {
+  if (!be_dims_ok(B, C, M, N, J)) return 0;
+  const BeGeom g = be_geom(B, C, M, N, J);
+  // forward: the difference, the spectrum when it is not kept, the row spectra, the partial sums (doubles); the backward
+  // needs the two spectra only
+  return arena_bytes((size_t)B * C * M * N) + 2 * arena_bytes(hs_elems(g)) + arena_bytes((size_t)2 * B * J * g.S);
+}
+
+int rpde_band_energy_fwd(const float* x, const float* y, const int32_t* entries, const int32_t* start, int n_entries,
+                         float* E, float* spec, int B, int C, int M, int N, int J, void* ws, size_t ws_bytes,
+                         void* stream) {
+  RPDE_CHECK_ARG(x && entries && start && E && ws, "band_energy_fwd: null pointer");
+  RPDE_CHECK_ARG(be_dims_ok(B, C, M, N, J),
+                 "band_energy_fwd: bad B=%d C=%d M=%d N=%d J=%d (axes 2 .. %d; M = 1: one-dimensional; 1 <= J <= %d)", B, C, M, N,
+                 J, HS_MAX_N, BE_MAX_BANDS);
+  RPDE_CHECK_ARG(n_entries >= 0 && n_entries <= (long)M * (N / 2 + 1), "band_energy_fwd: n_entries=%d for a %d x %d spectrum",
+                 n_entries, M, N / 2 + 1);
+  HS_CHECK_WS("band_energy_fwd", ws);
+  const BeGeom g = be_geom(B, C, M, N, J);
+  const size_t ns = hs_elems(g);
+  Arena ar(ws, ws_bytes);
+  float* d = ar.take((size_t)g.images * M * N);
+  float* s0 = ar.take(ns);
+  float* s1 = ar.take(ns);
+  double* part = reinterpret_cast<double*>(ar.take((size_t)2 * B * J * g.S));
+  if (!ar.ok()) { set_error("band_energy_fwd: workspace too small"); return RPDE_ERR_WORKSPACE; }
+  hipStream_t st = as_stream(stream);
+  float* sp = spec ? spec : s0;
+  const float* z = x;
+  if (y) {
+    const long total = (long)g.images * M * N;
+    const int vec = total % 4 == 0 && al16(x) && al16(y);
+    hipLaunchKernelGGL(k_be_diff, dim3(hs_blocks(vec ? total / 4 : total, 2048)), dim3(256), 0, st, x, y, d, total, vec);
+    RPDE_LAUNCH_CHECK();
+    z = d;
+  }
+  RPDE_TRY(hs_rfft(g, z, s1, sp, st));
+  const unsigned nb = (unsigned)(B < 65535 ? B : 65535);
+  hipLaunchKernelGGL(k_be_partial, dim3((J + 3) / 4, g.S, nb), dim3(256), 0, st, sp, entries, start, n_entries, part, g);
+  RPDE_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_be_final, dim3(hs_blocks((long)B * J, 1024)), dim3(256), 0, st, part, E, g);
+  RPDE_LAUNCH_CHECK();
+  return RPDE_OK;
+}
+
+int rpde_band_energy_bwd(const float* spec, const int32_t* band, const float* gE, float* grad_x, int B, int C, int M, int N,
+                         int J, void* ws, size_t ws_bytes, void* stream) {
+  RPDE_CHECK_ARG(spec && band && gE && grad_x && ws, "band_energy_bwd: null pointer");
+  RPDE_CHECK_ARG(be_dims_ok(B, C, M, N, J),
+                 "band_energy_bwd: bad B=%d C=%d M=%d N=%d J=%d (axes 2 .. %d; M = 1: one-dimensional; 1 <= J <= %d)", B, C, M, N,
+                 J, HS_MAX_N, BE_MAX_BANDS);
+  RPDE_CHECK_ARG(al16(spec) && al16(band), "band_energy_bwd: the spectrum and the band table must be 16-byte aligned");
+  HS_CHECK_WS("band_energy_bwd", ws);
+  const BeGeom g = be_geom(B, C, M, N, J);
+  const size_t ns = hs_elems(g);
+  Arena ar(ws, ws_bytes);
+  float* w = ar.take(ns);
+  float* t1 = ar.take(ns);
+  if (!ar.ok()) { set_error("band_energy_bwd: workspace too small"); return RPDE_ERR_WORKSPACE; }
+  hipStream_t st = as_stream(stream);
+  const long groups = (long)hs_per(g) / 4;
+  const int blk = hs_block(groups);
+  hipLaunchKernelGGL(k_be_scale, hs_grid(groups, g.images < 65535 ? g.images : 65535, blk), dim3(blk), 0, st, spec, band, gE, w,
+                     g);
+  RPDE_LAUNCH_CHECK();
+  return hs_irfft(g, w, t1, grad_x, st);
+}
+
+}  // extern "C"

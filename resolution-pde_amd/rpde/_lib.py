@@ -140,6 +140,10 @@ _SIGNATURES = {
     "rpde_wrel_l2_spec_elems": (_Z, [_I, _I, _I, _I]),
     "rpde_wrel_l2_fwd": (_I, [_P] * 7 + [_I] * 5 + [_P, _Z, _P]),
     "rpde_wrel_l2_bwd": (_I, [_P] * 6 + [_I] * 5 + [_P, _Z, _P]),
+    "rpde_band_energy_ws_bytes": (_Z, [_I, _I, _I, _I, _I]),
+    "rpde_band_energy_spec_elems": (_Z, [_I, _I, _I, _I]),
+    "rpde_band_energy_fwd": (_I, [_P] * 4 + [_I] + [_P] * 2 + [_I] * 5 + [_P, _Z, _P]),
+    "rpde_band_energy_bwd": (_I, [_P] * 4 + [_I] * 5 + [_P, _Z, _P]),
     "rpde_ns2d_ws_bytes": (_Z, [_I, _I, _I]),
     "rpde_ns2d_spec_elems": (_Z, [_I, _I, _I]),
     "rpde_ns2d_rfft2": (_I, [_P, _P, _I, _I, _I, _P, _Z, _P]),

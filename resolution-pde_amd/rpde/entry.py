@@ -64,6 +64,40 @@ def _sweep_fields(args, test_set, x_normalizer, y_normalizer, min_model, max_mod
     return tx, ty_phys, dec, how, top_res
 
 
+def training_loss(training, dims: int):
+    """(name, loss_fn or None) of the optional training objective, from the overrides under `training` (a mapping; no
+    device work here).  Absent or "l2": (l2, None), train() then takes RelativeL2Loss.
+      training.loss=sobolev   the H^s relative loss (utils.loss.SpectralRelativeL2Loss) with training.loss_s (default
+                              1.0) and training.loss_length (a float or one per axis, default 1.0)
+      training.loss=band      the relative error band by band (BandRelativeL2Loss) with training.loss_band_floor (1e-3)
+      training.loss=spectrum  relative L2 + training.loss_lambda (0.1) x the mismatch of the energy per band
+                              (SpectrumMatchingLoss) with training.loss_spectrum_floor (1e-6)
+    band and spectrum take training.loss_bands (octave; radial in 2-D, modes in 1-D) and training.loss_num_bands, and
+    the 1-D rollout record then also carries the octave band energies along the rollout.  Anything else: SystemExit.
+    Validation, the test score and the sweeps stay relative L2."""
+    name = str(training.get("loss", "l2"))
+    if name == "l2":
+        return name, None
+    if name == "sobolev":
+        from utils.loss import SpectralRelativeL2Loss
+        length = training.get("loss_length", 1.0)
+        length = [float(v) for v in length] if isinstance(length, (list, tuple)) else float(length)
+        return name, SpectralRelativeL2Loss(dims, "sobolev", s=float(training.get("loss_s", 1.0)), length=length)
+    if name not in ("band", "spectrum"):
+        raise SystemExit(f"training.loss={name}: expected l2, sobolev, band or spectrum")
+    from utils.loss import BandRelativeL2Loss, RelativeL2Loss, SpectrumMatchingLoss, SumLoss
+    bands = str(training.get("loss_bands", "octave"))
+    nb = training.get("loss_num_bands", None)
+    nb = None if nb is None else int(nb)
+    try:
+        if name == "band":
+            return name, BandRelativeL2Loss(dims, bands, nb, band_floor=float(training.get("loss_band_floor", 1e-3)))
+        match = SpectrumMatchingLoss(dims, bands, nb, spectrum_floor=float(training.get("loss_spectrum_floor", 1e-6)))
+        return name, SumLoss([(1.0, RelativeL2Loss()), (float(training.get("loss_lambda", 0.1)), match)])
+    except ValueError as e:
+        raise SystemExit(f"training.loss={name}: {e}")
+
+
 def run(dims: int, argv=None):
     here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     args = compose(os.path.join(here, "conf"), "config", list(sys.argv[1:] if argv is None else argv))
@@ -142,20 +176,11 @@ def run(dims: int, argv=None):
         optimizer = FlatAdamW(model.parameters(), lr=lr, weight_decay=1e-4, **guard)
         scheduler = optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=100, eta_min=1e-5)
 
-    # optional training objective (no yaml carries it): training.loss=sobolev trains on the H^s relative loss
-    # (utils.loss.SpectralRelativeL2Loss) with training.loss_s (default 1.0) and training.loss_length (a float or one
-    # per axis, default 1.0); absent or "l2": RelativeL2Loss.  Validation, the test score and the sweeps stay relative L2.
-    loss_fn = None
-    loss_name = str(args.training.get("loss", "l2"))
-    if loss_name == "sobolev":
-        from utils.loss import SpectralRelativeL2Loss
-        length = args.training.get("loss_length", 1.0)
-        length = [float(v) for v in length] if isinstance(length, (list, tuple)) else float(length)
-        loss_fn = SpectralRelativeL2Loss(dims, "sobolev", s=float(args.training.get("loss_s", 1.0)), length=length)
+    # optional training objective (no yaml carries it): training_loss() below
+    loss_name, loss_fn = training_loss(args.training, dims)
+    if loss_fn is not None:
         for r in train_loader.resolution_groups:
             loss_fn.warm((int(r),) * dims, device)
-    elif loss_name != "l2":
-        raise SystemExit(f"training.loss={loss_name}: expected l2 or sobolev")
 
     n_params = sum(p.numel() for p in model.parameters())
     if rank == 0:
@@ -180,7 +205,7 @@ def run(dims: int, argv=None):
     tx, ty_phys, dec, how, top_res = _sweep_fields(args, test_set, x_normalizer, y_normalizer, min_model, max_model, device)
     resolution_results = evaluate_all_resolutions(model, tx, ty_phys, max_resolution=top_res, min_resolution=min(32, top_res),
                                                   how=how, batch_size=bs, y_decode=dec, device=device)
-    rollout_results = None
+    rollout_results = rollout_bands = None
     if dims == 1:
         from utils.autoregressive_step import perform_rollout_1d, rollout_loss
         steps = int(args.dataset.get("rollout_steps", 4))
@@ -211,22 +236,49 @@ def run(dims: int, argv=None):
             xn = yn = None
             enc = decode_pred = lambda t: t                                      # noqa: E731
         acc = torch.zeros(len(resolution_results), 2, dtype=torch.float64, device=device)
+        # with a banded objective: sums over this rank's trajectories of (E_pred [J], E_true [J], log-ratio mean square)
+        # per step, by resolution
+        band_acc = {} if loss_name in ("band", "spectrum") else None
         for k, res in enumerate(resolution_results):
             tr = to_resolution(traj, res, "naive_downsample")
             if tr.shape[0]:
                 pred = perform_rollout_1d(model.eval(), enc(tr[:, 0]), steps, device=device, x_normalizer=xn, y_normalizer=yn)
-                acc[k, 0] += rollout_loss(decode_pred(pred), tr) * tr.shape[0]
+                pred = decode_pred(pred)
+                acc[k, 0] += rollout_loss(pred, tr) * tr.shape[0]
                 acc[k, 1] += tr.shape[0]
+            if band_acc is not None:
+                from rpde.ops import band_table
+                from utils.autoregressive_step import rollout_band_energy
+                J = band_table((int(res),), "octave")[1]
+                band_acc[res] = torch.zeros(steps, 2 * J + 1, dtype=torch.float64, device=device)
+                if tr.shape[0]:
+                    st = rollout_band_energy(pred, tr, "octave")
+                    band_acc[res] += tr.shape[0] * torch.cat([st["energy_pred"], st["energy_true"],
+                                                              st["log_ratio_rms"].view(-1, 1) ** 2], dim=1).to(device)
         if world > 1:
             dist.all_reduce(acc)
+            for t in (band_acc or {}).values():
+                dist.all_reduce(t)
         rollout_results = {res: (float(acc[k, 0] / acc[k, 1]) if float(acc[k, 1]) > 0 else float("nan"))
                            for k, res in enumerate(resolution_results)}
+        if band_acc is not None:
+            rollout_bands = {}
+            for k, res in enumerate(resolution_results):
+                n, t = float(acc[k, 1]), band_acc[res].cpu()
+                if n > 0:
+                    J = (t.shape[1] - 1) // 2
+                    rollout_bands[res] = {"energy_pred": (t[:, :J] / n).tolist(), "energy_true": (t[:, J:2 * J] / n).tolist(),
+                                          "log_ratio_rms": (t[:, 2 * J] / n).sqrt().tolist()}
     if rank == 0:
         print(json.dumps({"evaluation_type": how, "resolution_rel_l2": {str(k): v for k, v in resolution_results.items()}}),
               flush=True)
         if rollout_results is not None:
             print(json.dumps({"rollout_rel_l2": {str(k): v for k, v in rollout_results.items()}}), flush=True)
+        if rollout_bands is not None:
+            print(json.dumps({"rollout_band_energy": {str(k): v for k, v in rollout_bands.items()}}), flush=True)
     run.last = {"test_rel_l2": test_l2, "resolution_rel_l2": resolution_results, "rollout_rel_l2": rollout_results}
+    if rollout_bands is not None:
+        run.last["rollout_band_energy"] = rollout_bands
     if rank == 0:
         os.makedirs(args.checkpoint_dir, exist_ok=True)
         path = os.path.join(args.checkpoint_dir, f"{args.project_name}_{dims}d.pt")

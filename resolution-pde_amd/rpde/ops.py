@@ -991,6 +991,219 @@ def freq_energy2d(pred: torch.Tensor, target: torch.Tensor, num_radial_bins: int
 
 
 # ----------------------------------------------------------------------------
+# per-sample, per-band spectral energies with autograd (csrc/band_energy.hip, rpde_band_energy_*): the primitive under
+# utils.loss.BandRelativeL2Loss / SpectrumMatchingLoss and utils.autoregressive_step.rollout_band_energy.  GPU tensors
+# only, no CPU fallback.
+# ----------------------------------------------------------------------------
+_BAND_TABLES: dict = {}
+_BAND_TABLES_DEV: dict = {}
+BAND_KINDS = ("octave", "radial", "modes")
+MAX_BANDS = 4096
+
+
+def _band_grid(spatial_shape, what: str):
+    """(grid, M, N) of a 1-D (n,) or 2-D (H, W) grid; M = 1 in 1-D"""
+    grid = tuple(int(n) for n in spatial_shape)
+    if len(grid) not in (1, 2) or min(grid) < 2:
+        raise ValueError(f"{what}: spatial_shape {tuple(spatial_shape)}, expected (n,) or (H, W) with every axis >= 2")
+    return grid, (1 if len(grid) == 1 else grid[0]), grid[-1]
+
+
+def band_table(spatial_shape, kind: str, num_bands: Optional[int] = None):
+    """(table, J): table int32 [M, N//2+1] (M = 1 for a 1-D grid), the band in -1 .. J-1 of every rfft / rfft2 entry,
+    rows in fft order.  Host tensors, cached.
+      "octave"  band 0 for k = 0, else 1 + floor(log2 |k|), |k|^2 = k1^2 + k2^2 with signed integer wavenumbers (k1 = 0
+                in 1-D), in integer arithmetic (1 + (bit_length(|k|^2) - 1) // 2: exact on the band edges).  Every entry
+                has a band and a band means the same physical scales at every resolution; J follows from the grid.
+      "radial"  (2-D) radial_bins(H, W, num_bands)[0] unchanged, num_bands = 64 by default: the evaluator's bins, entries
+                with r >= 0.5 stay -1.
+      "modes"   (1-D) band = mode index for k < num_bands, -1 above."""
+    grid, M, N = _band_grid(spatial_shape, "band_table")
+    key = (grid, str(kind), None if num_bands is None else int(num_bands))
+    hit = _BAND_TABLES.get(key)
+    if hit is not None:
+        return hit
+    K = N // 2 + 1
+    if kind == "octave":
+        if num_bands is not None:
+            raise ValueError("band_table: the octave bands follow from the grid, num_bands must be None")
+        k1 = torch.arange(M, dtype=torch.int64)
+        k1 = torch.where(k1 <= (M - 1) // 2, k1, k1 - M)
+        k2 = torch.arange(K, dtype=torch.int64)
+        q = k1.view(-1, 1) ** 2 + k2.view(1, -1) ** 2
+        bits, v = torch.zeros_like(q), q.clone()
+        while bool(v.any()):                                   # bit_length, entry by entry
+            bits += (v > 0).to(torch.int64)
+            v >>= 1
+        table = torch.where(q == 0, torch.zeros_like(q), 1 + (bits - 1) // 2)
+        J = int(table.max()) + 1
+    elif kind == "radial":
+        if len(grid) != 2:
+            raise ValueError("band_table: radial bands are for 2-D grids")
+        J = 64 if num_bands is None else int(num_bands)
+        table = radial_bins(M, N, J)[0]
+    elif kind == "modes":
+        if len(grid) != 1 or num_bands is None or int(num_bands) < 1:
+            raise ValueError("band_table: 'modes' is for 1-D grids and needs num_bands >= 1")
+        J = int(num_bands)
+        k2 = torch.arange(K, dtype=torch.int64).view(1, K)
+        table = torch.where(k2 < J, k2, torch.full_like(k2, -1))
+    else:
+        raise ValueError(f"band_table: unknown kind {kind!r} (kinds: {', '.join(BAND_KINDS)})")
+    if not 1 <= J <= MAX_BANDS:
+        raise ValueError(f"band_table: {J} bands, expected 1 .. {MAX_BANDS}")
+    _BAND_TABLES[key] = (table.to(torch.int32).reshape(M, K).contiguous(), J)
+    return _BAND_TABLES[key]
+
+
+def check_band_table(table: torch.Tensor, spatial_shape, J: int) -> None:
+    """ValueError unless table is an integer table of the half spectrum of this grid ([M, N//2+1]; [N//2+1] also for a
+    1-D grid) with values in -1 .. J-1 whose self-conjugate columns (kx = 0 and, for even W, kx = W/2) are symmetric
+    in ky: otherwise gE[band] * rfft2(z) is not the spectrum of a real field and the inverse transform is not the
+    gradient"""
+    grid, M, N = _band_grid(spatial_shape, "check_band_table")
+    K = N // 2 + 1
+    if not torch.is_tensor(table) or table.is_floating_point() or table.is_complex() or table.dtype == torch.bool:
+        raise ValueError(f"band table: expected an integer tensor, got {getattr(table, 'dtype', type(table))}")
+    ok = ((M, K),) + (((K,),) if M == 1 else ())
+    if tuple(table.shape) not in ok:
+        raise ValueError(f"band table of shape {tuple(table.shape)}: the grid {grid} needs {(M, K)}")
+    if not 1 <= int(J) <= MAX_BANDS:
+        raise ValueError(f"band table: {J} bands, expected 1 .. {MAX_BANDS}")
+    t = table.detach().cpu().to(torch.int64).reshape(M, K)
+    if int(t.min()) < -1 or int(t.max()) >= int(J):
+        raise ValueError(f"band table: values {int(t.min())} .. {int(t.max())}, expected -1 .. {int(J) - 1}")
+    if M > 1:
+        flip = (M - torch.arange(M)) % M
+        for kx in [0] + ([N // 2] if N % 2 == 0 else []):
+            if not torch.equal(t[:, kx], t[flip, kx]):
+                raise ValueError(f"band table: column kx={kx} is not symmetric in ky (band[ky] != band[(H - ky) % H])")
+
+
+class BandTables:
+    """the device tables of one (grid, band table): what rpde_band_energy_* take (include/rpde.h)"""
+    __slots__ = ("grid", "J", "J_e", "n_entries", "band", "entries", "start")
+
+    def __init__(self, grid, J, J_e, n_entries, band, entries, start):
+        self.grid, self.J, self.J_e, self.n_entries = grid, J, J_e, n_entries
+        self.band, self.entries, self.start = band, entries, start
+
+
+def band_tables(table: torch.Tensor, J: int, spatial_shape, device) -> BandTables:
+    """Validate a host band table and build its device forms: the padded band-of-every-entry table [M, kp] and the
+    entries of each band listed band by band (ky-major inside a band) with start [J+1].  J_e: bands that own at least
+    one entry.  One host pass and three copies: callers keep the result per (grid, device)."""
+    check_band_table(table, spatial_shape, J)
+    grid, M, N = _band_grid(spatial_shape, "band_tables")
+    J, K, kp = int(J), N // 2 + 1, _kp(N)
+    t = table.detach().cpu().to(torch.int64).reshape(M, K)
+    band = torch.full((M, kp), -1, dtype=torch.int32)
+    band[:, :K] = t.to(torch.int32)
+    ky = torch.arange(M, dtype=torch.int64).view(M, 1)
+    kx = torch.arange(K, dtype=torch.int64).view(1, K)
+    twice = ~((kx == 0) | ((kx == N // 2) & (N % 2 == 0)))
+    packed = (((ky * (2 * kp) + kx) << 1) | twice.to(torch.int64)).reshape(-1)
+    flat = t.reshape(-1)
+    keep = flat >= 0
+    order = torch.argsort(flat[keep], stable=True)
+    entries = packed[keep][order].to(torch.int32)
+    counts = torch.bincount(flat[keep], minlength=J)
+    start = torch.zeros(J + 1, dtype=torch.int32)
+    start[1:] = torch.cumsum(counts, 0).to(torch.int32)
+    n = int(entries.numel())
+    if n == 0:
+        entries = torch.zeros(1, dtype=torch.int32)              # a pointer to pass; no entry is read
+    return BandTables(grid, J, int((counts > 0).sum()), n, band.to(device), entries.to(device), start.to(device))
+
+
+def _band_tables_on(device, grid, kind: str, num_bands) -> BandTables:
+    key = (torch.device(device), tuple(grid), str(kind), None if num_bands is None else int(num_bands))
+    t = _BAND_TABLES_DEV.get(key)
+    if t is None:
+        table, J = band_table(grid, kind, num_bands)
+        t = _BAND_TABLES_DEV[key] = band_tables(table, J, grid, device)
+    return t
+
+
+def resolve_bands(bands, spatial_shape, device) -> BandTables:
+    """the device tables of what band_energy accepts as `bands`, for this grid: a kind and (kind, num_bands) come from
+    the cache, an integer table is validated and copied, BandTables pass through"""
+    grid = tuple(int(n) for n in spatial_shape)
+    if isinstance(bands, BandTables):
+        T = bands
+    elif isinstance(bands, str):
+        T = _band_tables_on(device, grid, bands, None)
+    elif isinstance(bands, (tuple, list)) and len(bands) == 2 and isinstance(bands[0], str):
+        T = _band_tables_on(device, grid, bands[0], bands[1])
+    elif torch.is_tensor(bands):
+        T = band_tables(bands, max(int(bands.max()), 0) + 1 if bands.numel() else 1, grid, device)
+    else:
+        raise ValueError("bands must be a kind, (kind, num_bands), an integer table or BandTables")
+    if T.grid != grid:
+        raise ValueError(f"band tables of the grid {T.grid} for a field on {grid}")
+    return T
+
+
+class _BandEnergy(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, T: BandTables, dims: int):
+        lib = load()
+        x = _f32c(x)
+        px = ptr(x)                                            # raises for CPU tensors: there is no fallback
+        py = None
+        if y is not None:
+            if y.shape != x.shape:
+                raise ValueError(f"band_energy: x {tuple(x.shape)} / y {tuple(y.shape)} differ")
+            y = _f32c(y)
+            py = ptr(y)
+        B, Cc = x.shape[0], x.shape[1]
+        M, N = (1, x.shape[2]) if dims == 1 else (x.shape[2], x.shape[3])
+        if T.band.device != x.device:
+            raise ValueError(f"band_energy: band tables on {T.band.device}, x on {x.device}")
+        nws = lib.rpde_band_energy_ws_bytes(B, Cc, M, N, T.J)
+        if nws == 0:
+            raise ValueError(f"band_energy: unsupported B={B} C={Cc} grid {tuple(x.shape[2:])} J={T.J}")
+        keep = ctx.needs_input_grad[0]
+        E = torch.empty(B, T.J, dtype=torch.float32, device=x.device)
+        spec = torch.empty(lib.rpde_band_energy_spec_elems(B, Cc, M, N), dtype=torch.float32, device=x.device) if keep else None
+        ws = workspace(nws, x.device)
+        check(lib.rpde_band_energy_fwd(px, py, T.entries.data_ptr(), T.start.data_ptr(), T.n_entries, ptr(E), ptr(spec),
+                                       B, Cc, M, N, T.J, ws.data_ptr(), nws, stream_ptr()), "band_energy_fwd")
+        if keep:
+            ctx.save_for_backward(spec)
+        ctx.meta = (tuple(x.shape), B, Cc, M, N, T)
+        return E
+
+    @staticmethod
+    def backward(ctx, gE):
+        lib = load()
+        spec, = ctx.saved_tensors
+        shape, B, Cc, M, N, T = ctx.meta
+        gE = _f32c(gE)
+        gx = torch.empty(shape, dtype=torch.float32, device=spec.device)
+        nws = lib.rpde_band_energy_ws_bytes(B, Cc, M, N, T.J)
+        ws = workspace(nws, spec.device)
+        check(lib.rpde_band_energy_bwd(ptr(spec), T.band.data_ptr(), ptr(gE), ptr(gx), B, Cc, M, N, T.J, ws.data_ptr(), nws,
+                                       stream_ptr()), "band_energy_bwd")
+        return gx, None, None, None
+
+
+def band_energy(x, bands, dims: int, y=None):
+    """E [B, J] fp32: E[b, j] = sum_c sum_{(ky,kx) in band j} c_kx / (M N) |rfft(z)[b,c,ky,kx]|^2 (rfft2 for dims=2) of
+    z = x, or z = x - y formed in fp32 before the transform; c_kx the Hermitian multiplicity of the half axis.  x, y:
+    channels-first [B, C, n] / [B, C, H, W] fp32 tensors on the GPU.  bands: a kind of band_table ("octave"), a pair
+    (kind, num_bands), an integer table for this grid (its J is max + 1; validated and copied on every call), or the
+    BandTables that band_tables() prepared.  Gradient for x only; the spectrum is kept only when x needs one."""
+    if dims not in (1, 2):
+        raise ValueError(f"band_energy: dims must be 1 or 2, got {dims}")
+    if x.dim() != dims + 2:
+        raise ValueError(f"band_energy: x {tuple(x.shape)}, expected a {dims + 2}-D channels-first tensor")
+    if not x.is_cuda:
+        ptr(x)                                                 # the CPU refusal of every op
+    return _BandEnergy.apply(x, y, resolve_bands(bands, x.shape[2:], x.device), int(dims))
+
+
+# ----------------------------------------------------------------------------
 # Navier-Stokes vorticity generator and its Gaussian random field (csrc/ns_solver.hip, rpde_ns2d_* / rpde_grf2d;
 # data_generation/ns_2d.py and random_fields.py are the callers).  Data production: no autograd, GPU tensors only,
 # no CPU fallback.

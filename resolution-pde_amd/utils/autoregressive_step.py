@@ -9,6 +9,7 @@ from typing import Optional
 
 import torch
 
+from rpde import ops
 from rpde.ops import frozen_weights
 from utils.loss import RelativeL2Loss
 
@@ -76,3 +77,27 @@ def rollout_loss(predictions: torch.Tensor, trajectory: torch.Tensor) -> float:
     pred = predictions.reshape(B * steps, -1)
     tgt = trajectory[:, 1:steps + 1].reshape(B * steps, -1)
     return float(RelativeL2Loss(size_average=True)(pred, tgt))
+
+
+@torch.no_grad()
+def rollout_band_energy(predictions: torch.Tensor, trajectory: torch.Tensor, bands="octave", spectrum_floor: float = 1e-6) -> dict:
+    """Energy per wavenumber band along a rollout: what stays comparable past the Lyapunov time, where rollout_loss
+    saturates.  predictions [B, T, *grid], trajectory [B, >= T+1, *grid] (target_t = trajectory[:, t+1]); bands as
+    rpde.ops.band_energy takes them.  Returns host float64 tensors
+        energy_pred [T, J], energy_true [T, J]   batch means of the band energies E_j per step
+        log_ratio_rms [T]                        sqrt(mean_b mean_j (log(E_j(pred) + d) - log(E_j(true) + d))^2) over the
+                                                 bands that own an entry, d = spectrum_floor E_tot(true) + 1e-30
+    from one primitive call per field over the B T (sample, step) pairs and one host read."""
+    B, T = predictions.shape[0], predictions.shape[1]
+    grid = tuple(predictions.shape[2:])
+    pred = predictions.reshape(B * T, 1, *grid)
+    true = trajectory[:, 1:T + 1].reshape(B * T, 1, *grid)
+    tables = ops.resolve_bands(bands, grid, pred.device)
+    e_p = ops.band_energy(pred, tables, len(grid)).double()
+    e_t = ops.band_energy(true, tables, len(grid)).double()
+    d = spectrum_floor * e_t.sum(1, keepdim=True) + 1e-30
+    # a band without entries has E = 0 in both fields and adds 0: divide by the number of the others
+    msq = ((torch.log(e_p + d) - torch.log(e_t + d)) ** 2).sum(1) / max(tables.J_e, 1)
+    J = e_p.shape[1]
+    out = torch.cat([e_p.view(B, T, J).mean(0), e_t.view(B, T, J).mean(0), msq.view(B, T).mean(0).sqrt().view(T, 1)], dim=1).cpu()
+    return {"energy_pred": out[:, :J], "energy_true": out[:, J:2 * J], "log_ratio_rms": out[:, 2 * J]}

@@ -4,7 +4,12 @@ prediction and target (wavefront-shuffle reductions, deterministic).
 
 SpectralRelativeL2Loss (no counterpart in the reference): the same ratio with a non-negative weight per Fourier
 mode -- the H^s / Sobolev relative loss of operator learning is the preset -- forward and backward on the device
-(rpde.ops.weighted_relative_l2, csrc/spectral_loss.hip)."""
+(rpde.ops.weighted_relative_l2, csrc/spectral_loss.hip).
+
+BandRelativeL2Loss, SpectrumMatchingLoss (no counterpart in the reference): objectives whose weights depend on the
+sample -- the relative error band by band, and the mismatch of the energy per wavenumber band -- as a few operations
+on the [B, J] per-sample band energies of rpde.ops.band_energy (csrc/band_energy.hip, forward and backward on the
+device).  SumLoss adds weighted losses into one callable."""
 from __future__ import annotations
 
 import math
@@ -126,3 +131,147 @@ class SpectralRelativeL2Loss(nn.Module):
             raise ValueError(f"SpectralRelativeL2Loss(dims={self.dims}): expected [B, C, *grid], got {tuple(x.shape)}")
         omega = self._table(tuple(x.shape[2:]), x.device)
         return ops.weighted_relative_l2(x, y, omega, self.dims, self.size_average, self.reduction)
+
+
+def _safe_sqrt(e: torch.Tensor) -> torch.Tensor:
+    """sqrt with the value 0 and the gradient 0 (not inf) at 0"""
+    pos = e > 0
+    return torch.where(pos, torch.sqrt(torch.where(pos, e, torch.ones_like(e))), torch.zeros_like(e))
+
+
+class _BandedLoss(nn.Module):
+    """What the two band losses share: the band table (a kind of rpde.ops.band_table built per grid, or one explicit
+    integer table [n//2+1] / [H, W//2+1] with values -1 .. J-1 for ONE grid), its device forms cached per
+    (grid, device), warm() for graph capture and the reduction of the per-sample vector."""
+
+    def __init__(self, dims, bands="octave", num_bands=None, size_average=True, reduction=True):
+        super().__init__()
+        name = type(self).__name__
+        if int(dims) not in (1, 2):
+            raise ValueError(f"{name}: dims must be 1 or 2, got {dims}")
+        self.dims = int(dims)
+        if isinstance(bands, str):
+            ops.band_table((8,) * self.dims, bands, num_bands)        # validates kind / num_bands / dims now
+            self._explicit = None
+        elif torch.is_tensor(bands):
+            if bands.dim() != self.dims or bands.is_floating_point():
+                raise ValueError(f"{name}: an explicit band table is an integer tensor with {self.dims} dimension(s)")
+            self._explicit = bands.detach().cpu()
+            self._explicit_grid = None
+            num_bands = int(num_bands) if num_bands is not None else max(int(self._explicit.max()), 0) + 1
+        else:
+            raise ValueError(f"{name}: bands must be one of {ops.BAND_KINDS} or an integer tensor")
+        self.bands, self.num_bands = bands if isinstance(bands, str) else "explicit", num_bands
+        self.size_average = size_average
+        self.reduction = reduction
+        self._tables: dict = {}
+
+    def _table(self, grid, device) -> "ops.BandTables":
+        key = (grid, torch.device(device))
+        t = self._tables.get(key)
+        if t is None:
+            if self._explicit is None:
+                table, J = ops.band_table(grid, self.bands, self.num_bands)
+            else:
+                if self._explicit_grid not in (None, grid):
+                    raise ValueError(f"{type(self).__name__}: the explicit band table serves the grid "
+                                     f"{self._explicit_grid}, got {grid}")
+                table, J = self._explicit.reshape(1 if self.dims == 1 else grid[0], -1), self.num_bands
+            t = ops.band_tables(table, J, grid, device)
+            if self._explicit is not None:
+                self._explicit_grid = grid
+            self._tables[key] = t
+        return t
+
+    def warm(self, spatial_shape, device="cuda") -> None:
+        """plans, workspaces and the band tables of one grid, outside any capture"""
+        grid = tuple(int(n) for n in spatial_shape)
+        if len(grid) != self.dims:
+            raise ValueError(f"{type(self).__name__}.warm: grid {grid} for dims={self.dims}")
+        z = torch.zeros((1, 1) + grid, dtype=torch.float32, device=device, requires_grad=True)
+        self(z, torch.ones_like(z.detach())).sum().backward()
+        torch.cuda.synchronize(z.device)
+
+    def _tables_for(self, x, y):
+        if x.dim() != self.dims + 2 or x.shape != y.shape:
+            raise ValueError(f"{type(self).__name__}(dims={self.dims}): expected equal [B, C, *grid] shapes, got "
+                             f"{tuple(x.shape)} / {tuple(y.shape)}")
+        return self._table(tuple(int(n) for n in x.shape[2:]), x.device)
+
+    def _reduce(self, v):
+        if not self.reduction:
+            return v
+        return v.mean() if self.size_average else v.sum()
+
+
+class BandRelativeL2Loss(_BandedLoss):
+    """Relative error band by band, so that a weak high-wavenumber band counts as much as the energetic low ones:
+
+        rel[b] = (1/J_e) sum_j sqrt(E_j(x - y)[b]) / (sqrt(E_j(y)[b]) + band_floor sqrt(E_tot(y)[b]) + 1e-8)
+
+    with E_j the per-sample band energies of rpde.ops.band_energy (x - y formed in fp32 before the transform), E_tot the
+    sum over the bands and J_e the number of bands that own an entry on the grid; then mean / sum / per-sample vector as
+    RelativeL2Loss.  One band that owns every entry and band_floor = 0 is RelativeL2Loss.  band_floor keeps a band the
+    target leaves empty from dominating.  x, y: channels-first fp32 tensors on the GPU; gradient for x only."""
+
+    def __init__(self, dims, bands="octave", num_bands=None, band_floor=1e-3, size_average=True, reduction=True):
+        super().__init__(dims, bands, num_bands, size_average, reduction)
+        if not (math.isfinite(float(band_floor)) and float(band_floor) >= 0):
+            raise ValueError(f"BandRelativeL2Loss: band_floor {band_floor}")
+        self.band_floor = float(band_floor)
+
+    def forward(self, x, y):
+        T = self._tables_for(x, y)
+        y = y.detach()
+        e_d = ops.band_energy(x, T, self.dims, y=y)
+        e_y = ops.band_energy(y, T, self.dims)
+        denom = torch.sqrt(e_y) + (self.band_floor * torch.sqrt(e_y.sum(1, keepdim=True)) + 1e-8)
+        return self._reduce((_safe_sqrt(e_d) / denom).sum(1) / T.J_e)
+
+
+class SpectrumMatchingLoss(_BandedLoss):
+    """The prediction has the wrong amount of energy in band j (spectral blur), whatever the phases:
+
+        val[b] = (1/J_e) sum_j (log(E_j(x)[b] + delta_b) - log(E_j(y)[b] + delta_b))^2,
+        delta_b = spectrum_floor E_tot(y)[b] + 1e-30
+
+    with the band energies of rpde.ops.band_energy; then mean / sum / per-sample vector.  It does not see a phase error:
+    add it to a pointwise loss (SumLoss).  x, y: channels-first fp32 tensors on the GPU; gradient for x only."""
+
+    def __init__(self, dims, bands="octave", num_bands=None, spectrum_floor=1e-6, size_average=True, reduction=True):
+        super().__init__(dims, bands, num_bands, size_average, reduction)
+        if not (math.isfinite(float(spectrum_floor)) and float(spectrum_floor) >= 0):
+            raise ValueError(f"SpectrumMatchingLoss: spectrum_floor {spectrum_floor}")
+        self.spectrum_floor = float(spectrum_floor)
+
+    def forward(self, x, y):
+        T = self._tables_for(x, y)
+        e_x = ops.band_energy(x, T, self.dims)
+        e_y = ops.band_energy(y.detach(), T, self.dims)
+        delta = self.spectrum_floor * e_y.sum(1, keepdim=True) + 1e-30
+        return self._reduce(((torch.log(e_x + delta) - torch.log(e_y + delta)) ** 2).sum(1) / T.J_e)
+
+
+class SumLoss(nn.Module):
+    """sum_i weight_i loss_i(x, y) as one callable: SumLoss([(1.0, RelativeL2Loss()), (0.1, SpectrumMatchingLoss(1))]).
+    warm() goes to the terms that have one."""
+
+    def __init__(self, terms):
+        super().__init__()
+        terms = [(float(w), fn) for w, fn in terms]
+        if not terms:
+            raise ValueError("SumLoss: no terms")
+        self.weights = [w for w, _ in terms]
+        self.terms = nn.ModuleList([fn for _, fn in terms])
+
+    def warm(self, spatial_shape, device="cuda") -> None:
+        for fn in self.terms:
+            if hasattr(fn, "warm"):
+                fn.warm(spatial_shape, device)
+
+    def forward(self, x, y):
+        out = None
+        for w, fn in zip(self.weights, self.terms):
+            v = fn(x, y) * w
+            out = v if out is None else out + v
+        return out
