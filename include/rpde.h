@@ -492,13 +492,27 @@ int rpde_grf2d(const float* noise, const float* sqrt_eig, float* out, int B, int
  * State and tables 16-byte aligned (noise 8), the workspaces of the steps and grf1d calls 256-byte aligned (the
  * transforms alone need none); the ws / spec queries return 0 for sizes the calls refuse (odd or out-of-range N, B outside 1 .. 65535).
  * nsteps == 0 is a no-op.  The first use of a grid builds its plan: it allocates and synchronises once.
- * Argument errors are reported before any device work. */
+ * Argument errors are reported before any device work.
+ * The steps_cx call is the same step for a symbol with odd derivatives (advection, dispersion: Korteweg-de Vries),
+ *   l_n = c2 kappa_n^2 + c4 kappa_n^4 + i (c1 kappa_n + c3 kappa_n^3),  Im l_{N/2} = 0
+ * (an odd derivative of the Nyquist mode vanishes on the grid; its bin of a real field stays real).  E, E2, Q, f1, f2, f3
+ * are then complex, each [re|im][kp] floats -- the plane layout of a spectrum, padded columns zero -- and g stays real
+ * [kp].  z = h l_n is complex, so the contour is the full circle and the mean is the complex mean, no Re:
+ *   LR = z + r_m,  r_m = exp(2 pi i (m - 1/2) / 64),  m = 1 .. 64;   E = e^z,  E2 = e^(z/2),  Q = h <(e^(LR/2) - 1) / LR>,
+ *   f1 = h <(-4 - LR + e^LR (4 - 3 LR + LR^2)) / LR^3>,  f2 = h <(2 + LR + e^LR (-2 + LR)) / LR^3>,
+ *   f3 = h <(-4 - 3 LR - LR^2 + e^LR (4 - LR)) / LR^3>
+ * (the upper half circle with Re<.> above is this mean for real z only; where z is real the imaginary parts are zero).  Same state, workspace (the ws query), launch
+ * sequence, alignment and error rules as the steps call; every coefficient product is a complex one in fused
+ * multiply-adds.  The steps call itself, its tables and its bits are unchanged. */
 size_t rpde_etd1d_ws_bytes(int B, int N);
 size_t rpde_etd1d_spec_elems(int B, int N);
 int rpde_etd1d_rfft(const float* u, float* U, int B, int N, void* stream);
 int rpde_etd1d_irfft(const float* U, float* u, int B, int N, void* stream);
 int rpde_etd1d_steps(float* U, const float* E, const float* E2, const float* Q, const float* f1, const float* f2,
                      const float* f3, const float* g, int B, int N, int nsteps, void* ws, size_t ws_bytes, void* stream);
+int rpde_etd1d_steps_cx(float* U, const float* E, const float* E2, const float* Q, const float* f1, const float* f2,
+                        const float* f3, const float* g, int B, int N, int nsteps, void* ws, size_t ws_bytes,
+                        void* stream);
 size_t rpde_grf1d_ws_bytes(int B, int N);
 int rpde_grf1d(const float* noise, const float* sqrt_eig, float* out, int B, int N, void* ws, size_t ws_bytes,
                void* stream);

@@ -18,6 +18,10 @@
 // GEMMs carry no squaring prologue, and one more epilogue there would serve this file alone.
 // The stage sequence is a pure function of v: k calls of n steps give the bits of one call of k n steps.  No atomics
 // anywhere: identical calls give identical bits.
+// rpde_etd1d_steps_cx is the same step for a symbol with odd derivatives, l_n += i (c1 kappa_n + c3 kappa_n^3) (advection,
+// dispersion: Korteweg-de Vries, data_generation/kdv_1d.py): E, E2, Q, f1, f2, f3 are complex [re|im][kp], g stays real,
+// and the stage kernels are k_etd_stage_cx<S>.  The same workspace, launches and transforms; k_etd_stage<S> and the
+// real call are as they were.
 #include "halfspec.h"
 
 namespace rpde {
@@ -101,6 +105,107 @@ __global__ __launch_bounds__(256) void k_etd_stage(EtdBufs u, const float* __res
   }
 }
 
+// k_etd_stage for complex tables (rpde_etd1d_steps_cx: a symbol with odd derivatives): E, E2, Q, f1, f2, f3 are
+// [re|im][kp], the plane layout of the spectra, g stays real.  Every coefficient product of k_etd_stage becomes a complex
+// one -- the real plane's multiply or fma, then two more fmas with the imaginary plane -- in the same order of terms.
+// Same geometry, same streaming: the imaginary planes are further whole float4 loads, all of them unconditional.  The
+// masked values are formed before the selects: a select whose arm holds the only use of a load becomes a branch with
+// that element's load inside it, which splits the float4 and waits per element.
+
+// p = c x
+__device__ __forceinline__ void etd_cmul(float cr, float ci, float xr, float xi, float& pr, float& pi) {
+  pr = fmaf(-ci, xi, cr * xr);
+  pi = fmaf(ci, xr, cr * xi);
+}
+// p += c x
+__device__ __forceinline__ void etd_cfma(float cr, float ci, float xr, float xi, float& pr, float& pi) {
+  pr = fmaf(-ci, xi, fmaf(cr, xr, pr));
+  pi = fmaf(ci, xr, fmaf(cr, xi, pi));
+}
+
+template <int S>
+__global__ __launch_bounds__(256) void k_etd_stage_cx(EtdBufs u, const float* __restrict__ F, EtdTables t, HalfSpec g) {
+  const long per = 2L * g.kp, base = (long)blockIdx.y * per;
+  const float* __restrict__ Fb = F + base;
+  const int c4n = g.kp / 4;
+  for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < c4n; q += gridDim.x * blockDim.x) {
+    const int k0 = q * 4, k1 = k0 + g.kp;                     // a table's real and imaginary group
+    const long ore = base + k0, oim = ore + g.kp;
+    float fr[4], fi[4], gg[4], nr[4], ni[4];
+    ld4(Fb + k0, fr);
+    ld4(Fb + k1, fi);
+    ld4(t.g + k0, gg);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      nr[j] = -gg[j] * fi[j];
+      ni[j] = gg[j] * fr[j];
+    }
+    if (S == 0 || S == 1) {
+      float vr[4], vi[4], e2r[4], e2i[4], qr[4], qi[4], orr[4], oi[4];
+      ld4(u.v + ore, vr);   ld4(u.v + oim, vi);
+      ld4(t.E2 + k0, e2r);  ld4(t.E2 + k1, e2i);
+      ld4(t.Q + k0, qr);    ld4(t.Q + k1, qi);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const bool live = k0 + j < g.K;
+        float xr, xi;
+        etd_cmul(qr[j], qi[j], nr[j], ni[j], xr, xi);
+        etd_cfma(e2r[j], e2i[j], vr[j], vi[j], xr, xi);
+        orr[j] = live ? xr : 0.f;
+        oi[j] = live ? xi : 0.f;
+        nr[j] = live ? nr[j] : 0.f;
+        ni[j] = live ? ni[j] : 0.f;
+      }
+      float* __restrict__ nout = S == 0 ? u.nv : u.sum;
+      float* __restrict__ sout = S == 0 ? u.a : u.bc;
+      st4(nout + ore, nr); st4(nout + oim, ni);
+      st4(sout + ore, orr); st4(sout + oim, oi);
+    } else if (S == 2) {
+      float ar[4], ai[4], pr[4], pi[4], sr[4], si[4], e2r[4], e2i[4], qr[4], qi[4], cr[4], ci[4];
+      ld4(u.a + ore, ar);   ld4(u.a + oim, ai);
+      ld4(u.nv + ore, pr);  ld4(u.nv + oim, pi);
+      ld4(u.sum + ore, sr); ld4(u.sum + oim, si);
+      ld4(t.E2 + k0, e2r);  ld4(t.E2 + k1, e2i);
+      ld4(t.Q + k0, qr);    ld4(t.Q + k1, qi);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const bool live = k0 + j < g.K;
+        float xr, xi;
+        etd_cmul(qr[j], qi[j], fmaf(2.f, nr[j], -pr[j]), fmaf(2.f, ni[j], -pi[j]), xr, xi);
+        etd_cfma(e2r[j], e2i[j], ar[j], ai[j], xr, xi);
+        const float tr = sr[j] + nr[j], ti = si[j] + ni[j];
+        cr[j] = live ? xr : 0.f;
+        ci[j] = live ? xi : 0.f;
+        sr[j] = live ? tr : 0.f;
+        si[j] = live ? ti : 0.f;
+      }
+      st4(u.sum + ore, sr); st4(u.sum + oim, si);
+      st4(u.bc + ore, cr);  st4(u.bc + oim, ci);
+    } else {
+      float vr[4], vi[4], pr[4], pi[4], sr[4], si[4], er[4], ei[4], c1r[4], c1i[4], c2r[4], c2i[4], c3r[4], c3i[4];
+      ld4(u.v + ore, vr);   ld4(u.v + oim, vi);
+      ld4(u.nv + ore, pr);  ld4(u.nv + oim, pi);
+      ld4(u.sum + ore, sr); ld4(u.sum + oim, si);
+      ld4(t.E + k0, er);    ld4(t.E + k1, ei);
+      ld4(t.f1 + k0, c1r);  ld4(t.f1 + k1, c1i);
+      ld4(t.f2 + k0, c2r);  ld4(t.f2 + k1, c2i);
+      ld4(t.f3 + k0, c3r);  ld4(t.f3 + k1, c3i);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const bool live = k0 + j < g.K;
+        float xr, xi;
+        etd_cmul(c3r[j], c3i[j], nr[j], ni[j], xr, xi);
+        etd_cfma(2.f * c2r[j], 2.f * c2i[j], sr[j], si[j], xr, xi);
+        etd_cfma(c1r[j], c1i[j], pr[j], pi[j], xr, xi);
+        etd_cfma(er[j], ei[j], vr[j], vi[j], xr, xi);
+        vr[j] = live ? xr : 0.f;
+        vi[j] = live ? xi : 0.f;
+      }
+      st4(u.v + ore, vr); st4(u.v + oim, vi);
+    }
+  }
+}
+
 // p <- p^2 over n4 float4 groups.  The field is a workspace piece, 256-byte aligned and padded to 256 bytes: the last
 // group is whole also when B N is not a multiple of 4 (what it squares past the field is never read).
 __global__ __launch_bounds__(256) void k_etd_square(float* __restrict__ p, long n4) {
@@ -109,6 +214,59 @@ __global__ __launch_bounds__(256) void k_etd_square(float* __restrict__ p, long 
     const float4 a = q[i];
     q[i] = make_float4(a.x * a.x, a.y * a.y, a.z * a.z, a.w * a.w);
   }
+}
+
+// rpde_etd1d_steps (CX = false: seven real tables [kp]) and rpde_etd1d_steps_cx (six complex tables [re|im][kp] and
+// the real g): the same checks, workspace and sixteen launches per step, the stage kernels of the table kind
+template <bool CX>
+static int etd1d_steps(float* U, const EtdTables& t, int B, int N, int nsteps, void* ws, size_t ws_bytes, void* stream) {
+  const char* what = CX ? "etd1d_steps_cx" : "etd1d_steps";
+  RPDE_CHECK_ARG(U && t.E && t.E2 && t.Q && t.f1 && t.f2 && t.f3 && t.g && ws, "%s: null pointer", what);
+  if (CX) HS_CHECK_DIMS_1D("etd1d_steps_cx", B, N);
+  else HS_CHECK_DIMS_1D("etd1d_steps", B, N);
+  HS_CHECK_WS(what, ws);
+  RPDE_CHECK_ARG(nsteps >= 0, "%s: nsteps %d < 0", what, nsteps);
+  RPDE_CHECK_ARG(al16(U) && al16(t.E) && al16(t.E2) && al16(t.Q) && al16(t.f1) && al16(t.f2) && al16(t.f3) && al16(t.g),
+                 "%s: state and tables must be 16-byte aligned", what);
+  const HalfSpec geo = hs_geom(B, 1, N);
+  const size_t spec = hs_elems(geo), phys = (size_t)B * N;
+  Arena ar(ws, ws_bytes);
+  EtdBufs u;
+  u.v = U;
+  u.nv = ar.take(spec);
+  u.a = ar.take(spec);
+  u.sum = ar.take(spec);
+  u.bc = ar.take(spec);
+  float* F = ar.take(spec);
+  float* P = ar.take(phys);
+  if (!ar.ok()) { set_error("%s: workspace too small", what); return RPDE_ERR_WORKSPACE; }
+  if (nsteps == 0) return RPDE_OK;
+  hipStream_t st = as_stream(stream);
+  // a wave per image of at most 64 groups (N <= 510), 256 threads otherwise
+  const dim3 sb(hs_block(geo.kp / 4)), sg = hs_grid(geo.kp / 4, B, sb.x);
+  const long n4 = ((long)phys + 3) / 4;
+  // F = rfft(irfft(w)^2)
+  auto product = [&](const float* w) -> int {
+    RPDE_TRY(hs_irfft(geo, w, nullptr, P, st));
+    hipLaunchKernelGGL(k_etd_square, dim3(hs_blocks(n4, 2048)), dim3(256), 0, st, P, n4);
+    RPDE_LAUNCH_CHECK();
+    return hs_rfft(geo, P, nullptr, F, st);
+  };
+  for (int j = 0; j < nsteps; ++j) {
+    RPDE_TRY(product(u.v));
+    hipLaunchKernelGGL(CX ? k_etd_stage_cx<0> : k_etd_stage<0>, sg, sb, 0, st, u, F, t, geo);
+    RPDE_LAUNCH_CHECK();
+    RPDE_TRY(product(u.a));
+    hipLaunchKernelGGL(CX ? k_etd_stage_cx<1> : k_etd_stage<1>, sg, sb, 0, st, u, F, t, geo);
+    RPDE_LAUNCH_CHECK();
+    RPDE_TRY(product(u.bc));
+    hipLaunchKernelGGL(CX ? k_etd_stage_cx<2> : k_etd_stage<2>, sg, sb, 0, st, u, F, t, geo);
+    RPDE_LAUNCH_CHECK();
+    RPDE_TRY(product(u.bc));
+    hipLaunchKernelGGL(CX ? k_etd_stage_cx<3> : k_etd_stage<3>, sg, sb, 0, st, u, F, t, geo);
+    RPDE_LAUNCH_CHECK();
+  }
+  return RPDE_OK;
 }
 
 }  // namespace rpde
@@ -127,52 +285,13 @@ size_t rpde_etd1d_ws_bytes(int B, int N) {
 
 int rpde_etd1d_steps(float* U, const float* E, const float* E2, const float* Q, const float* f1, const float* f2,
                      const float* f3, const float* g, int B, int N, int nsteps, void* ws, size_t ws_bytes, void* stream) {
-  RPDE_CHECK_ARG(U && E && E2 && Q && f1 && f2 && f3 && g && ws, "etd1d_steps: null pointer");
-  HS_CHECK_DIMS_1D("etd1d_steps", B, N);
-  HS_CHECK_WS("etd1d_steps", ws);
-  RPDE_CHECK_ARG(nsteps >= 0, "etd1d_steps: nsteps %d < 0", nsteps);
-  RPDE_CHECK_ARG(al16(U) && al16(E) && al16(E2) && al16(Q) && al16(f1) && al16(f2) && al16(f3) && al16(g),
-                 "etd1d_steps: state and tables must be 16-byte aligned");
-  const HalfSpec geo = hs_geom(B, 1, N);
-  const size_t spec = hs_elems(geo), phys = (size_t)B * N;
-  Arena ar(ws, ws_bytes);
-  EtdBufs u;
-  u.v = U;
-  u.nv = ar.take(spec);
-  u.a = ar.take(spec);
-  u.sum = ar.take(spec);
-  u.bc = ar.take(spec);
-  float* F = ar.take(spec);
-  float* P = ar.take(phys);
-  if (!ar.ok()) { set_error("etd1d_steps: workspace too small"); return RPDE_ERR_WORKSPACE; }
-  if (nsteps == 0) return RPDE_OK;
-  hipStream_t st = as_stream(stream);
-  const EtdTables t{E, E2, Q, f1, f2, f3, g};
-  // a wave per image of at most 64 groups (N <= 510), 256 threads otherwise
-  const dim3 sb(hs_block(geo.kp / 4)), sg = hs_grid(geo.kp / 4, B, sb.x);
-  const long n4 = ((long)phys + 3) / 4;
-  // F = rfft(irfft(w)^2)
-  auto product = [&](const float* w) -> int {
-    RPDE_TRY(hs_irfft(geo, w, nullptr, P, st));
-    hipLaunchKernelGGL(k_etd_square, dim3(hs_blocks(n4, 2048)), dim3(256), 0, st, P, n4);
-    RPDE_LAUNCH_CHECK();
-    return hs_rfft(geo, P, nullptr, F, st);
-  };
-  for (int j = 0; j < nsteps; ++j) {
-    RPDE_TRY(product(u.v));
-    hipLaunchKernelGGL(k_etd_stage<0>, sg, sb, 0, st, u, F, t, geo);
-    RPDE_LAUNCH_CHECK();
-    RPDE_TRY(product(u.a));
-    hipLaunchKernelGGL(k_etd_stage<1>, sg, sb, 0, st, u, F, t, geo);
-    RPDE_LAUNCH_CHECK();
-    RPDE_TRY(product(u.bc));
-    hipLaunchKernelGGL(k_etd_stage<2>, sg, sb, 0, st, u, F, t, geo);
-    RPDE_LAUNCH_CHECK();
-    RPDE_TRY(product(u.bc));
-    hipLaunchKernelGGL(k_etd_stage<3>, sg, sb, 0, st, u, F, t, geo);
-    RPDE_LAUNCH_CHECK();
-  }
-  return RPDE_OK;
+  return etd1d_steps<false>(U, EtdTables{E, E2, Q, f1, f2, f3, g}, B, N, nsteps, ws, ws_bytes, stream);
+}
+
+int rpde_etd1d_steps_cx(float* U, const float* E, const float* E2, const float* Q, const float* f1, const float* f2,
+                        const float* f3, const float* g, int B, int N, int nsteps, void* ws, size_t ws_bytes,
+                        void* stream) {
+  return etd1d_steps<true>(U, EtdTables{E, E2, Q, f1, f2, f3, g}, B, N, nsteps, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

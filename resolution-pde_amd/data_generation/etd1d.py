@@ -1,6 +1,7 @@
-"""What the two 1-D generator scripts (burgers_1d.py, ks_1d.py) share: the snapshot arithmetic, the call into the
-device integrator rpde.ops.etd1d_solve (csrc/etd1d.hip: ETDRK4 for u_t = L u - (1/2) (u^2)_x, pseudo-spectral, 2/3
-de-aliasing) and the handling of --resolution / --resolutions.  Host arithmetic apart from `integrate`."""
+"""What the three 1-D generator scripts (burgers_1d.py, ks_1d.py, kdv_1d.py) share: the snapshot arithmetic, the call
+into the device integrator rpde.ops.etd1d_solve (csrc/etd1d.hip: ETDRK4 for u_t = L u - (1/2) (u^2)_x, pseudo-spectral,
+2/3 de-aliasing; real tables for even symbols, complex ones when an odd derivative is present) and the handling of
+--resolution / --resolutions.  Host arithmetic apart from `integrate`."""
 from __future__ import annotations
 
 from typing import List, Tuple
@@ -25,14 +26,19 @@ def snapshot_schedule(T: float, dt: float, record_steps: int) -> Tuple[int, int,
     return every * record_steps, every, [(c + 1) * every * float(dt) for c in range(record_steps)]
 
 
-def integrate(u0: torch.Tensor, length: float, c2: float, c4: float, T: float, dt: float, record_steps: int):
-    """u0 [B, N] on the GPU -> (sol [B, record_steps, N], sol_t [record_steps]) for the symbol c2 kappa^2 + c4 kappa^4.
-    The schedule is checked before any device work."""
+def integrate(u0: torch.Tensor, length: float, c2: float, c4: float, T: float, dt: float, record_steps: int,
+              c1: float = 0.0, c3: float = 0.0):
+    """u0 [B, N] on the GPU -> (sol [B, record_steps, N], sol_t [record_steps]) for the symbol c2 kappa^2 + c4 kappa^4
+    + i (c1 kappa + c3 kappa^3).  With c1 = c3 = 0 the real tables and the real call, as before; otherwise the complex
+    ones (rpde.ops.etd1d_tables_cx).  The schedule is checked before any device work."""
     steps, every, times = snapshot_schedule(T, dt, record_steps)
     if u0.dim() != 2:
         raise ValueError(f"expected u0 [B, N], got {tuple(u0.shape)}")
     from rpde import ops
-    tables = ops.etd1d_tables(int(u0.shape[1]), length, c2, c4, dt)
+    if c1 == 0.0 and c3 == 0.0:
+        tables = ops.etd1d_tables(int(u0.shape[1]), length, c2, c4, dt)
+    else:
+        tables = ops.etd1d_tables_cx(int(u0.shape[1]), length, c1, c2, c3, c4, dt)
     sol = ops.etd1d_solve(u0, tables, steps, every)
     return sol, torch.tensor(times, dtype=torch.float32, device=sol.device)
 

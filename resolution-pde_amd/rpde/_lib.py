@@ -157,6 +157,7 @@ _SIGNATURES = {
     "rpde_etd1d_rfft": (_I, [_P, _P, _I, _I, _P]),
     "rpde_etd1d_irfft": (_I, [_P, _P, _I, _I, _P]),
     "rpde_etd1d_steps": (_I, [_P] * 8 + [_I, _I, _I, _P, _Z, _P]),
+    "rpde_etd1d_steps_cx": (_I, [_P] * 8 + [_I, _I, _I, _P, _Z, _P]),
     "rpde_grf1d_ws_bytes": (_Z, [_I, _I]),
     "rpde_grf1d": (_I, [_P, _P, _P, _I, _I, _P, _Z, _P]),
     "rpde_adamw_step": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _F, _F, _P]),

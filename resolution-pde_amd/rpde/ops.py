@@ -1360,6 +1360,59 @@ def etd1d_tables(N: int, length: float, c2: float, c4: float, dt: float, advect:
     return tuple(out)
 
 
+def etd1d_tables_cx(N: int, length: float, c1: float, c2: float, c3: float, c4: float, dt: float, advect: float = 1.0,
+                    dealias: bool = True):
+    """(E, E2, Q, f1, f2, f3, g): the ETDRK4 tables of u_t = L u - (advect/2) (u^2)_x for a symbol with odd derivatives,
+    l_n = c2 kappa_n^2 + c4 kappa_n^4 + i (c1 kappa_n + c3 kappa_n^3), kappa_n = 2 pi n / length -- the sign convention
+    of etd1d_tables continued: KdV u_t + u u_x + u_xxx = 0 is c3 = +1, advection u_t + a u_x = ... is c1 = -a.  The six
+    coefficient tables are complex, float32 [2, kp] host tensors (real plane, imaginary plane; padding zero), g is
+    float32 [kp] as in etd1d_tables; formed in float64 / complex128 and rounded once.  Im l_{N/2} = 0: an odd derivative
+    of the Nyquist mode vanishes on the grid, and with it the Nyquist bin of a real field stays real.  z = dt l_n is
+    complex, so the contour is the full circle, LR = z + r_m, r_m = exp(2 pi i (m - 1/2) / 64), m = 1 .. 64, and the mean is
+    the complex mean (the upper half circle with Re<.> of etd1d_tables is that mean for real z only); where z is real the
+    mean is real and its imaginary part is stored as zero.  include/rpde.h has the formulas."""
+    import math
+    N = int(N)
+    if N < 4 or N % 2:
+        raise ValueError(f"etd1d_tables_cx: N must be even and >= 4, got {N}")
+    if not (float(length) > 0 and float(dt) > 0):
+        raise ValueError(f"etd1d_tables_cx: length and dt must be positive, got length={length} dt={dt}")
+    K, kp = N // 2 + 1, _kp(N)
+    n = torch.arange(K, dtype=torch.float64)
+    kappa = (2.0 * math.pi / float(length)) * n
+    h = float(dt)
+    odd = float(c1) * kappa + float(c3) * kappa ** 3
+    odd[N // 2] = 0.0
+    z = h * torch.complex(float(c2) * kappa ** 2 + float(c4) * kappa ** 4, odd)
+    m = torch.arange(1, 65, dtype=torch.float64)
+    r = torch.polar(torch.ones(64, dtype=torch.float64), 2.0 * math.pi * (m - 0.5) / 64.0)
+    LR = z.view(K, 1) + r.view(1, 64)
+    eLR = torch.exp(LR)
+
+    def mean(t):
+        return t.mean(dim=1)
+
+    keep = (n <= (2.0 / 3.0) * (N // 2)).to(torch.float64) if dealias else torch.ones(K, dtype=torch.float64)
+    g = -(float(advect) / 2.0) * kappa * keep
+    g[N // 2] = 0.0
+    out = []
+    for t in (torch.exp(z), torch.exp(z / 2.0),
+              h * mean((torch.exp(LR / 2.0) - 1.0) / LR),
+              h * mean((-4.0 - LR + eLR * (4.0 - 3.0 * LR + LR ** 2)) / LR ** 3),
+              h * mean((2.0 + LR + eLR * (-2.0 + LR)) / LR ** 3),
+              h * mean((-4.0 - 3.0 * LR - LR ** 2 + eLR * (4.0 - LR)) / LR ** 3)):
+        p = torch.zeros(2, kp, dtype=torch.float32)
+        p[0, :K] = t.real.to(torch.float32)
+        # real z (the mean and Nyquist modes, an even symbol): the circle's points pair up as conjugates and the mean is
+        # real; what its imaginary part holds then is the sum's rounding (1e-20), dropped
+        p[1, :K] = torch.where(z.imag == 0, torch.zeros(K, dtype=torch.float64), t.imag).to(torch.float32)
+        out.append(p)
+    p = torch.zeros(kp, dtype=torch.float32)
+    p[:K] = g.to(torch.float32)
+    out.append(p)
+    return tuple(out)
+
+
 def grf1d(noise: torch.Tensor, sqrt_eig: torch.Tensor) -> torch.Tensor:
     """noise [B, N, 2] (real and imaginary part of the coefficients in fft order, standard normal), sqrt_eig [N] ->
     [B, N] = Re ifft(sqrt_eig . noise), torch's 1/N included.  The HIP side is deterministic given the noise.
@@ -1368,8 +1421,9 @@ def grf1d(noise: torch.Tensor, sqrt_eig: torch.Tensor) -> torch.Tensor:
 
 
 def etd1d_solve(u0: torch.Tensor, tables, steps: int, record_every: int) -> torch.Tensor:
-    """`steps` ETDRK4 steps of u_t = L u - (c/2) (u^2)_x from u0 [B, N] with the seven tables of etd1d_tables (host or
-    device tensors, [kp]); a snapshot -- irfft of the state -- after every `record_every`-th step.  Returns
+    """`steps` ETDRK4 steps of u_t = L u - (c/2) (u^2)_x from u0 [B, N] with the seven tables of etd1d_tables ([kp]) or
+    of etd1d_tables_cx (six [2, kp] and g [kp]: a symbol with odd derivatives, rpde_etd1d_steps_cx), host or device
+    tensors; a snapshot -- irfft of the state -- after every `record_every`-th step.  Returns
     [B, steps // record_every, N], contiguous fp32.  Sixteen launches per step, no host synchronisation between them;
     the recording loop calls the device `steps // record_every` times, which gives the bits of one long call.
     Contiguous fp32 tensors on the GPU; no autograd, no CPU fallback."""
@@ -1378,12 +1432,18 @@ def etd1d_solve(u0: torch.Tensor, tables, steps: int, record_every: int) -> torc
     if steps < 0 or record_every < 1:
         raise ValueError(f"etd1d_solve: bad steps={steps} record_every={record_every}")
     u0 = _f32c(u0.detach())
-    pu = ptr(u0)                                           # raises for CPU tensors: there is no fallback
     B, N = _grid(u0, "etd1d_solve", 1)
     kp = _kp(N)
     tables = tuple(tables)
-    if len(tables) != 7 or any(tuple(t.shape) != (kp,) for t in tables):
-        raise ValueError(f"etd1d_solve: expected the seven [{kp}] tables of etd1d_tables(N={N}, ...)")
+    shapes = [tuple(t.shape) for t in tables]
+    if shapes == [(kp,)] * 7:
+        steps_call, name = lib.rpde_etd1d_steps, "etd1d_steps"
+    elif shapes == [(2, kp)] * 6 + [(kp,)]:
+        steps_call, name = lib.rpde_etd1d_steps_cx, "etd1d_steps_cx"
+    else:
+        raise ValueError(f"etd1d_solve: expected the seven [{kp}] tables of etd1d_tables(N={N}, ...) or the six [2, {kp}] "
+                         f"tables and g [{kp}] of etd1d_tables_cx(N={N}, ...)")
+    pu = ptr(u0)                                           # raises for CPU tensors: there is no fallback
     dev = u0.device
     tabs = [_f32c(t.detach().to(dev)) for t in tables]
     nws = lib.rpde_etd1d_ws_bytes(B, N)
@@ -1394,7 +1454,7 @@ def etd1d_solve(u0: torch.Tensor, tables, steps: int, record_every: int) -> torc
     n_rec = steps // record_every
     snaps = torch.empty(max(n_rec, 1), B, N, dtype=torch.float32, device=dev)
     for c in range(n_rec):
-        check(lib.rpde_etd1d_steps(ptr(U), *(ptr(t) for t in tabs), B, N, record_every, ws.data_ptr(), nws, st), "etd1d_steps")
+        check(steps_call(ptr(U), *(ptr(t) for t in tabs), B, N, record_every, ws.data_ptr(), nws, st), name)
         check(lib.rpde_etd1d_irfft(ptr(U), ptr(snaps[c]), B, N, st), "etd1d_irfft")
     return snaps[:n_rec].permute(1, 0, 2).contiguous()
 
