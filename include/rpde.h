@@ -517,6 +517,41 @@ size_t rpde_grf1d_ws_bytes(int B, int N);
 int rpde_grf1d(const float* noise, const float* sqrt_eig, float* out, int B, int N, void* ws, size_t ws_bytes,
                void* stream);
 
+/* ---- Darcy flow generator (csrc/darcy.hip; reference: dataloaders/darcy_loader.py and the piececonst_* files of
+ * load_darcy_data_from_mat): -div(a grad u) = f on the unit square, u = 0 on the boundary, s x s cells with centres
+ * x_i = (i + 1/2) / s, a and u [B, s, s] at the centres.  Finite volumes: an interior face between cells c and n weighs
+ * w = 2 a_c a_n / (a_c + a_n), a boundary face of cell c weighs 2 a_c (the wall is half a cell away, u = 0 there), and
+ *   (A u)_c = s^2 sum_faces w_face (u_c - u_n),  u_n = 0 across a boundary face,
+ * evaluated in this difference form.  The apply call is Au = A u.
+ * The solve call runs `iterations` iterations of conjugate gradients from u = 0, preconditioned with the same operator at
+ * a = 1 inverted exactly, P^-1 r = S^T (inv_lambda . (S r S^T)) S.  The caller forms both tables [s, s] in float64 and rounds
+ * them to fp32 once (rpde.ops.darcy2d_tables):
+ *   S[k, i] = sqrt(2 / s) sin(pi (k + 1) (i + 1/2) / s), row k = s - 1 divided by sqrt 2      (DST-II, orthogonal)
+ *   inv_lambda[k1, k2] = 1 / (l_k1 + l_k2),  l_k = s^2 (2 - 2 cos(pi (k + 1) / s)).
+ * f is one right-hand side [s, s] (f_batched = 0) or B of them.  Nine launches per iteration on the caller's stream, no
+ * host synchronisation and no device-to-host read; every scalar (alpha, beta, r.z, the norms, the per-sample state) stays
+ * in device memory; no atomics: identical calls give identical bits, and a sample never reads another sample's scalars.
+ * A sample freezes -- its alpha and beta are 0 and its u fixed for the rest of the loop -- once its recurrence residual
+ * satisfies |r| <= tol |f|, or its p.Ap or r.z is not a positive finite number.  After the loop one more apply gives
+ * rel_residual[b] = |f - A u| / |f| (0 for f = 0), the true residual, and frozen_at[b] is the number of iterations the
+ * sample took before it froze; `iterations` means it never did.  The iterate is advanced as a two-float sum (its low part
+ * lives in the workspace) and u is that sum rounded once: the true residual is the one of the correctly rounded
+ * solution, which in fp32 grows like s^2 (7e-6 at s = 32, 1e-4 at 128 for a of order 10, f = 1).
+ * The sep2d call: out_b = L in_b R^T for B images [s, s] and two tables [s, s] -- the product form of a separable
+ * transform (one batched GEMM with the shared table on the left, one GEMM over [B s, s] on the right); the solver's
+ * sine transforms and the cosine-series random field (data_generation/random_fields.py GaussianRFNeumann) go through it.
+ * Grids 8 <= s <= 512, s a multiple of 4, 1 <= B <= 65535: the ws query returns 0 otherwise and the calls refuse.
+ * Fields and tables 16-byte aligned, workspaces 256-byte aligned (sep2d: B s s floats rounded up to 256 bytes).
+ * a must be positive and finite: the caller's contract, not checked here.  Argument errors are reported before any
+ * device work. */
+size_t rpde_darcy2d_ws_bytes(int B, int s);
+int rpde_darcy2d_apply(const float* a, const float* u, float* Au, int B, int s, void* stream);
+int rpde_darcy2d_solve(const float* a, const float* f, int f_batched, const float* S, const float* inv_lambda,
+                       float* u, float* rel_residual /*[B]*/, int* frozen_at /*[B]*/,
+                       int B, int s, int iterations, float tol, void* ws, size_t ws_bytes, void* stream);
+int rpde_sep2d(const float* in, const float* L, const float* R, float* out, int B, int s, void* ws, size_t ws_bytes,
+               void* stream);
+
 /* ---- optimizer step: torch.optim.AdamW as built at main_1d.py:144 / main_2d.py:173 (decoupled weight decay,
  * bias-corrected moments, no amsgrad), one streaming kernel over flat fp32 buffers of n (multiple of 4) elements.
  * The caller passes the step's scalars: 1 - lr*wd, 1 - b1, b2, 1 - b2, lr / (1 - b1^t), sqrt(1 - b2^t), eps. */

@@ -11,7 +11,11 @@ The periodic 1-D field -- the reference's dim = 1 formula -- is a class of its o
 (the same kernel at one row); GaussianRF itself still refuses dim = 1:
 
     sqrt_eig[k] = size sqrt(2) sigma (4 pi^2 k^2 + tau^2)^(-alpha/2),  0 at k = 0,  sigma = tau^((2 alpha - 1) / 2)
-    sample      = Re ifft(sqrt_eig . (xi_re + i xi_im))"""
+    sample      = Re ifft(sqrt_eig . (xi_re + i xi_im))
+
+GaussianRFNeumann is the 2-D field with zero-flux boundary on cell centres, a cosine series through rpde.ops.sep2d
+(csrc/darcy.hip); the reference's GaussianRF has no such boundary, and GaussianRF here still refuses anything but
+'periodic'."""
 from __future__ import annotations
 
 import math
@@ -91,3 +95,59 @@ class GaussianRF1d(_DeviceRF):
             raise ValueError(f"GaussianRF1d: tau must be positive (got {tau})")
         self.size = size
         self._setup((size,), alpha, tau, sigma, device)
+
+
+def neumann_tables(size: int, alpha: float, tau: float, sigma: float):
+    """(C, coef) float32 [size, size] host tensors, formed in float64 and rounded once: the cosine table
+    C[i, k] = cos(pi k (i + 1/2) / size) on the cell centres and coef[k1, k2] = sigma (pi^2 (k1^2 + k2^2) + tau^2)^(-alpha/2),
+    0 at the mean mode"""
+    i = (torch.arange(size, dtype=torch.float64) + 0.5).view(size, 1)
+    k = torch.arange(size, dtype=torch.float64).view(1, size)
+    C = torch.cos(math.pi * k * i / size)
+    coef = float(sigma) * (math.pi ** 2 * (k.view(size, 1) ** 2 + k ** 2) + float(tau) ** 2) ** (-float(alpha) / 2.0)
+    coef[0, 0] = 0.0
+    return C.to(torch.float32), coef.to(torch.float32)
+
+
+class GaussianRFNeumann(object):
+    """N(0, sigma^2 (-Laplacian + tau^2)^-alpha) on the unit square with zero-flux boundary, on the cell centres
+    (i + 1/2) / size: the cosine series
+
+        sample = C (coef . xi) C^T,  C[i, k] = cos(pi k (i + 1/2) / size),  xi standard normal [size, size],
+        coef[k1, k2] = sigma (pi^2 (k1^2 + k2^2) + tau^2)^(-alpha/2),  coef[0, 0] = 0,  sigma = tau^(alpha - 1) by default
+
+    (the coefficient fields of the Darcy benchmark are thresholds of it, data_generation/darcy_2d.py).  The two
+    products are rpde.ops.sep2d (csrc/darcy.hip); sizes are the Darcy generator's, multiples of 4 in 8 .. 512."""
+
+    def __init__(self, size, alpha=2, tau=3, sigma=None, device=None):
+        size = int(size)
+        if size < 8 or size > 512 or size % 4:
+            raise ValueError(f"GaussianRFNeumann: size must be a multiple of 4, 8 .. 512 (got {size})")
+        if not tau > 0:
+            raise ValueError(f"GaussianRFNeumann: tau must be positive (got {tau})")
+        self.dim, self.size = 2, (size, size)
+        self.device = torch.device("cuda" if device is None else device)
+        if sigma is None:
+            sigma = tau ** (0.5 * (2 * alpha - self.dim))
+        self.alpha, self.tau, self.sigma = alpha, tau, sigma
+        self._host = neumann_tables(size, alpha, tau, sigma)
+        self._dev = None
+
+    @property
+    def tables(self):
+        """(C, coef) fp32 [size, size] on the device (moved there at first use)"""
+        if self._dev is None:
+            self._dev = tuple(t.to(self.device) for t in self._host)
+        return self._dev
+
+    def sample(self, N, generator: Optional[torch.Generator] = None, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """[N, size, size] samples.  The noise [N, size, size] is drawn with torch.randn on the device (from `generator`,
+        a device generator, when given: equal seeds give equal samples) or passed in."""
+        from rpde import ops
+        shape = (int(N), *self.size)
+        if noise is None:
+            noise = torch.randn(shape, device=self.device, dtype=torch.float32, generator=generator)
+        elif tuple(noise.shape) != shape:
+            raise ValueError(f"GaussianRFNeumann.sample: noise {tuple(noise.shape)}, expected {shape}")
+        C, coef = self.tables
+        return ops.sep2d(noise.to(self.device).to(torch.float32) * coef, C, C)

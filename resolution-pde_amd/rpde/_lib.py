@@ -160,6 +160,10 @@ _SIGNATURES = {
     "rpde_etd1d_steps_cx": (_I, [_P] * 8 + [_I, _I, _I, _P, _Z, _P]),
     "rpde_grf1d_ws_bytes": (_Z, [_I, _I]),
     "rpde_grf1d": (_I, [_P, _P, _P, _I, _I, _P, _Z, _P]),
+    "rpde_darcy2d_ws_bytes": (_Z, [_I, _I]),
+    "rpde_darcy2d_apply": (_I, [_P, _P, _P, _I, _I, _P]),
+    "rpde_darcy2d_solve": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _Z, _P]),
+    "rpde_sep2d": (_I, [_P, _P, _P, _P, _I, _I, _P, _Z, _P]),
     "rpde_adamw_step": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _F, _F, _P]),
     "rpde_adamw_step_dev": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _P, _P]),
     "rpde_adamw_set_hyper_dev": (_I, [_P, _F, _F, _P]),

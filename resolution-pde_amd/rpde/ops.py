@@ -1459,6 +1459,99 @@ def etd1d_solve(u0: torch.Tensor, tables, steps: int, record_every: int) -> torc
     return snaps[:n_rec].permute(1, 0, 2).contiguous()
 
 
+# ----------------------------------------------------------------------------
+# Darcy flow generator (csrc/darcy.hip, rpde_darcy2d_* / rpde_sep2d; data_generation/darcy_2d.py and
+# random_fields.py GaussianRFNeumann are the callers).  Data production: no autograd, GPU tensors only, no CPU fallback.
+# ----------------------------------------------------------------------------
+def _darcy_grid(t: torch.Tensor, what: str):
+    """(B, s) of a batch of square fields [B, s, s], refused as the C side refuses them"""
+    if t.dim() != 3 or t.shape[1] != t.shape[2]:
+        raise ValueError(f"{what}: expected [B, s, s], got {tuple(t.shape)}")
+    B, s = int(t.shape[0]), int(t.shape[1])
+    if load().rpde_darcy2d_ws_bytes(B, s) == 0:
+        raise ValueError(f"{what}: unsupported grid B={B} s={s} (s a multiple of 4, 8 .. 512, 1 <= B <= 65535)")
+    return B, s
+
+
+def darcy2d_tables(s: int):
+    """(S, inv_lambda): float32 [s, s] host tensors, formed in float64 and rounded once.
+    S[k, i] = sqrt(2/s) sin(pi (k+1) (i+1/2) / s) with row s-1 divided by sqrt 2 (DST-II, orthogonal);
+    inv_lambda[k1, k2] = 1 / (l_k1 + l_k2), l_k = s^2 (2 - 2 cos(pi (k+1) / s)): the eigenvalues of the finite-volume
+    Dirichlet Laplacian on cell centres, whose eigenvectors are the rows of S."""
+    import math
+    s = int(s)
+    if s < 8 or s > 512 or s % 4:
+        raise ValueError(f"darcy2d_tables: s must be a multiple of 4, 8 .. 512, got {s}")
+    k = torch.arange(1, s + 1, dtype=torch.float64).view(s, 1)
+    x = (torch.arange(s, dtype=torch.float64) + 0.5).view(1, s)
+    S = math.sqrt(2.0 / s) * torch.sin(math.pi * k * x / s)
+    S[s - 1] /= math.sqrt(2.0)
+    lam = float(s) ** 2 * (2.0 - 2.0 * torch.cos(math.pi * k.view(-1) / s))
+    return S.to(torch.float32), (1.0 / (lam.view(s, 1) + lam.view(1, s))).to(torch.float32)
+
+
+def sep2d(x: torch.Tensor, L: torch.Tensor, R: torch.Tensor) -> torch.Tensor:
+    """out[b] = L x[b] R^T for x [B, s, s] and two tables [s, s]: a separable transform as two matrix products.
+    Contiguous fp32 tensors on the GPU; no autograd, no CPU fallback."""
+    lib = load()
+    x, L, R = _f32c(x.detach()), _f32c(L.detach()), _f32c(R.detach())
+    px, pl, pr = ptr(x), ptr(L), ptr(R)                    # raises for CPU tensors: there is no fallback
+    B, s = _darcy_grid(x, "sep2d")
+    if tuple(L.shape) != (s, s) or tuple(R.shape) != (s, s):
+        raise ValueError(f"sep2d: tables {tuple(L.shape)} and {tuple(R.shape)}, expected {(s, s)}")
+    out = torch.empty_like(x)
+    nws = B * s * s * 4 + 256
+    ws = workspace(nws, x.device)
+    check(lib.rpde_sep2d(px, pl, pr, ptr(out), B, s, ws.data_ptr(), nws, stream_ptr()), "sep2d")
+    return out
+
+
+def darcy2d_apply(a: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
+    """A u for the finite-volume operator of -div(a grad .) with u = 0 on the boundary (include/rpde.h has the
+    formulas): a, u [B, s, s] at the cell centres.  Contiguous fp32 tensors on the GPU; no autograd, no CPU fallback."""
+    lib = load()
+    a, u = _f32c(a.detach()), _f32c(u.detach())
+    pa, pu = ptr(a), ptr(u)                                # raises for CPU tensors: there is no fallback
+    B, s = _darcy_grid(a, "darcy2d_apply")
+    if tuple(u.shape) != (B, s, s):
+        raise ValueError(f"darcy2d_apply: u {tuple(u.shape)}, expected {(B, s, s)}")
+    out = torch.empty_like(u)
+    check(lib.rpde_darcy2d_apply(pa, pu, ptr(out), B, s, stream_ptr()), "darcy2d_apply")
+    return out
+
+
+def darcy2d_solve(a: torch.Tensor, f: torch.Tensor, iterations: int = 24, tol: float = 1e-6):
+    """-div(a grad u) = f on the unit square with u = 0 on the boundary, finite volumes on the s x s cell centres:
+    `iterations` iterations of conjugate gradients preconditioned with the constant-coefficient operator (two sine
+    transforms as matrix products).  a [B, s, s] positive and finite (checked here: one device-to-host read before the
+    solve, none inside it), f [s, s] for the whole batch or [B, s, s].  Returns (u [B, s, s], rel_residual [B] =
+    |f - A u| / |f| recomputed after the loop, frozen_at [B] int32 = the iterations a sample took until |r| <= tol |f|,
+    `iterations` if it never got there).  Nine launches per iteration; identical calls give identical bits.  Contiguous
+    fp32 tensors on the GPU; no autograd, no CPU fallback."""
+    import math
+    lib = load()
+    iterations, tol = int(iterations), float(tol)
+    if iterations < 0 or not (tol >= 0.0 and math.isfinite(tol)):
+        raise ValueError(f"darcy2d_solve: bad iterations={iterations} tol={tol}")
+    a, f = _f32c(a.detach()), _f32c(f.detach())
+    pa, pf = ptr(a), ptr(f)                                # raises for CPU tensors: there is no fallback
+    B, s = _darcy_grid(a, "darcy2d_solve")
+    if tuple(f.shape) not in ((s, s), (B, s, s)):
+        raise ValueError(f"darcy2d_solve: right-hand side {tuple(f.shape)}, expected {(s, s)} or {(B, s, s)}")
+    if not bool((torch.isfinite(a) & (a > 0)).all()):
+        raise ValueError("darcy2d_solve: the coefficient a must be positive and finite everywhere")
+    dev = a.device
+    S, inv_lambda = (t.to(dev) for t in darcy2d_tables(s))
+    u = torch.empty_like(a)
+    rel = torch.empty(B, dtype=torch.float32, device=dev)
+    frozen_at = torch.empty(B, dtype=torch.int32, device=dev)
+    nws = lib.rpde_darcy2d_ws_bytes(B, s)
+    ws = workspace(nws, dev)
+    check(lib.rpde_darcy2d_solve(pa, pf, int(f.dim() == 3), ptr(S), ptr(inv_lambda), ptr(u), ptr(rel), frozen_at.data_ptr(),
+                                 B, s, iterations, tol, ws.data_ptr(), nws, stream_ptr()), "darcy2d_solve")
+    return u, rel, frozen_at
+
+
 def warm_plans(model, resolutions, dims: int, in_channels: int = 1, device="cuda") -> None:
     """Build every DFT plan (tables, adjoint tables, operand images: hipMalloc + one stream sync each,
     csrc/core.hip get_plan) and size the workspaces the model needs at the given grid resolutions, with one
