@@ -467,6 +467,37 @@ size_t rpde_grf2d_ws_bytes(int B, int M, int N);
 int rpde_grf2d(const float* noise, const float* sqrt_eig, float* out, int B, int M, int N,
                void* ws, size_t ws_bytes, void* stream);
 
+/* ---- active-scalar Navier-Stokes generator (csrc/ns_scalar.hip; an interface addition, the reference has no
+ * generator for its active-matter files): the vorticity equation above with a scalar c that the flow advects and that
+ * drives the flow back through buoyancy along axis 2 (Boussinesq; the curl of the force is beta dc/dx1), on the same
+ * half-spectrum layer and grids.  The state is two half spectra per sample in the layout above,
+ * S = [W_0 .. W_{B-1}, C_0 .. C_{B-1}], 2 B images.  With psi, k1, k2, lap and dealias as above, the steps call advances S
+ * in place by nsteps steps of
+ *   q = irfft2(2 pi i k2 psi),  v = irfft2(-2 pi i k1 psi),  w_1, w_2 = irfft2(2 pi i k1 W), irfft2(2 pi i k2 W),
+ *   c_1, c_2 = irfft2(2 pi i k1 C), irfft2(2 pi i k2 C),
+ *   F_w = rfft2(q w_1 + v w_2) - beta 2 pi i k1 C  (C of the old time level),   F_c = rfft2(q c_1 + v c_2),
+ *   W <- c_w W - c_f F_w + g_h,   C <- d_w C - d_f F_c
+ * with the tables c_w, c_f, d_w, d_f, inv_lap [M][kp] (padded columns zero) formed by the caller in float64 and rounded
+ * once (rpde.ops.nsc2d_tables): c_w, c_f, inv_lap as above, and with b = dt kappa lap / 2:
+ *   d_w = (1 - b) / (1 + b),  d_f = dt dealias / (1 + b);
+ * g_h as above, from rpde_ns2d_scale: one spectrum (g_batched = 0) or B (g_batched = 1); beta a scalar.  Six launches
+ * per step on the caller's stream (a fused update + fan-out of the six derivative spectra, the inverse transform of the
+ * 6 B images in two launches, the two products, the forward transform of the 2 B products in two launches), no host
+ * synchronisation, no atomics: identical calls give identical bits, and k calls of n steps equal one call of k n steps
+ * bit for bit.  nsteps == 0 is a no-op.
+ * The fields call: out [B, 3, M, N] = (c, q, v) of S, the concentration and the velocity u = (q, v) -- one fan-out and
+ * one inverse transform of 3 B images.
+ * State, forcing, tables and out 16-byte aligned, the workspace (the ws query covers both calls) 256-byte aligned; the
+ * ws query returns 0 for sizes the calls refuse: odd or out-of-range axes, and a B whose 6 B derivative images are
+ * no generator grid (6 B > 65535 or 24 B max(M, N) >= 2^31).  The plans are those of the NS generator: the first use
+ * of a grid allocates and synchronises.  Argument errors are reported before any device work. */
+size_t rpde_nsc2d_ws_bytes(int B, int M, int N);
+int rpde_nsc2d_steps(float* S, const float* g_h, int g_batched, const float* c_w, const float* c_f, const float* d_w,
+                     const float* d_f, const float* inv_lap, float beta, int B, int M, int N, int nsteps, void* ws,
+                     size_t ws_bytes, void* stream);
+int rpde_nsc2d_fields(const float* S, const float* inv_lap, float* out, int B, int M, int N, void* ws, size_t ws_bytes,
+                      void* stream);
+
 /* ---- 1-D exponential-time-differencing generator (csrc/etd1d.hip; the rfft / irfft and grf1d calls are the M = 1 case of
  * the NS generator's in csrc/halfspec.hip, on the 1-D transforms of csrc/cf_dft.h): every
  * equation u_t = L u - (c/2) (u^2)_x on a periodic domain of length len -- Burgers (L = nu_eff d_xx) and

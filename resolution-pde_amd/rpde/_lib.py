@@ -152,6 +152,9 @@ _SIGNATURES = {
     "rpde_ns2d_steps": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
     "rpde_grf2d_ws_bytes": (_Z, [_I, _I, _I]),
     "rpde_grf2d": (_I, [_P, _P, _P, _I, _I, _I, _P, _Z, _P]),
+    "rpde_nsc2d_ws_bytes": (_Z, [_I, _I, _I]),
+    "rpde_nsc2d_steps": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _P, _Z, _P]),
+    "rpde_nsc2d_fields": (_I, [_P, _P, _P, _I, _I, _I, _P, _Z, _P]),
     "rpde_etd1d_ws_bytes": (_Z, [_I, _I]),
     "rpde_etd1d_spec_elems": (_Z, [_I, _I]),
     "rpde_etd1d_rfft": (_I, [_P, _P, _I, _I, _P]),

@@ -1314,6 +1314,88 @@ def ns2d_solve(w0: torch.Tensor, f: torch.Tensor, visc: float, dt: float, steps:
 
 
 # ----------------------------------------------------------------------------
+# Active-scalar Navier-Stokes generator (csrc/ns_scalar.hip, rpde_nsc2d_*; data_generation/active_scalar_2d.py is the
+# caller).  Data production: no autograd, GPU tensors only, no CPU fallback.
+# ----------------------------------------------------------------------------
+def nsc2d_tables(M: int, N: int, visc: float, kappa: float, dt: float):
+    """(c_w, c_f, d_w, d_f, c_g, inv_lap): the coupled step's coefficient tables, float32 [M, kp] host tensors with the
+    padded columns zero -- ns2d_tables' arithmetic, once with the viscosity (c_w, c_f, c_g, inv_lap) and once with the
+    scalar's diffusivity, b = dt kappa lap / 2: d_w = (1 - b)/(1 + b), d_f = dt dealias/(1 + b)."""
+    c_w, c_f, c_g, inv_lap = ns2d_tables(M, N, visc, dt)
+    d_w, d_f, _, _ = ns2d_tables(M, N, kappa, dt)
+    return c_w, c_f, d_w, d_f, c_g, inv_lap
+
+
+def _nsc2d_state(what: str, w: torch.Tensor, c: torch.Tensor):
+    """w, c [B, M, N] -> (lib, B, M, N, ws, nws, S): S = [rfft2(w), rfft2(c)], the solver's state of 2 B half spectra"""
+    lib = load()
+    w, c = _f32c(w.detach()), _f32c(c.detach())
+    ptr(w), ptr(c)                                         # raises for CPU tensors: there is no fallback
+    B, M, N = _grid(w, what, 2)
+    if tuple(c.shape) != (B, M, N) or c.device != w.device:
+        raise ValueError(f"{what}: scalar {tuple(c.shape)} on {c.device}, expected {(B, M, N)} on {w.device}")
+    nws = lib.rpde_nsc2d_ws_bytes(B, M, N)
+    if nws == 0:
+        raise ValueError(f"{what}: unsupported batch B={B} for the grid {M} x {N} (6 B <= 65535, 24 B max(M, N) < 2^31)")
+    ws = workspace(nws, w.device)
+    S = torch.empty(lib.rpde_ns2d_spec_elems(2 * B, M, N), dtype=torch.float32, device=w.device)
+    wc = torch.cat([w, c], dim=0)
+    check(lib.rpde_ns2d_rfft2(ptr(wc), ptr(S), 2 * B, M, N, ws.data_ptr(), nws, stream_ptr()), "ns2d_rfft2")
+    return lib, B, M, N, ws, nws, S
+
+
+def nsc2d_fields(w: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
+    """w (vorticity), c (scalar) [B, M, N] -> [B, 3, M, N] = (c, q, v): the scalar and the velocity u = (q, v) of w,
+    q = d psi/dx2, v = -d psi/dx1, lap psi = -w, through rpde_nsc2d_fields (c itself goes through the transform pair).
+    Contiguous fp32 tensors on the GPU; no autograd, no CPU fallback."""
+    lib, B, M, N, ws, nws, S = _nsc2d_state("nsc2d_fields", w, c)
+    inv_lap = ns2d_tables(M, N, 0.0, 0.0)[3].to(S.device)
+    out = torch.empty(B, 3, M, N, dtype=torch.float32, device=S.device)
+    check(lib.rpde_nsc2d_fields(ptr(S), ptr(inv_lap), ptr(out), B, M, N, ws.data_ptr(), nws, stream_ptr()), "nsc2d_fields")
+    return out
+
+
+def nsc2d_solve(w0: torch.Tensor, c0: torch.Tensor, f: torch.Tensor, visc: float, kappa: float, beta: float, dt: float,
+                steps: int, record_every: int):
+    """2-D Navier-Stokes in vorticity form with an active scalar on the periodic unit square: from w0, c0 [B, M, N] with
+    forcing f ([M, N] or [B, M, N]) on the vorticity, `steps` pseudo-spectral steps of size dt of
+        w_t + u . grad w = visc lap w + beta dc/dx1 + f,    c_t + u . grad c = kappa lap c
+    (Crank-Nicolson on both diffusions, explicit advection, buoyancy and forcing, 2/3 de-aliasing; include/rpde.h has the
+    formulas), a snapshot after every `record_every`-th.  Returns (fields [B, steps // record_every, 3, M, N] = (c, q, v)
+    with u = (q, v), vorticity [B, steps // record_every, M, N]).  Six launches per step, one device call per snapshot's
+    steps, no host synchronisation.  Contiguous fp32 tensors on the GPU; no autograd, no CPU fallback."""
+    steps, record_every = int(steps), int(record_every)
+    if steps < 0 or record_every < 1:
+        raise ValueError(f"nsc2d_solve: bad steps={steps} record_every={record_every}")
+    f = _f32c(f.detach())
+    ptr(f)
+    lib, B, M, N, ws, nws, S = _nsc2d_state("nsc2d_solve", w0, c0)
+    if tuple(f.shape) not in ((M, N), (B, M, N)):
+        raise ValueError(f"nsc2d_solve: forcing {tuple(f.shape)}, expected {(M, N)} or {(B, M, N)}")
+    fb = 1 if f.dim() == 2 else B
+    dev = S.device
+    c_w, c_f, d_w, d_f, c_g, inv_lap = (t.to(dev) for t in nsc2d_tables(M, N, visc, kappa, dt))
+    st = stream_ptr()
+    # g_h as in ns2d_solve: one image at a time, so that a sample's forcing spectrum does not depend on the batch
+    per = lib.rpde_ns2d_spec_elems(1, M, N)
+    f_h = torch.empty(fb * per, dtype=torch.float32, device=dev)
+    g_h = torch.empty_like(f_h)
+    f3 = f.view(fb, M, N)
+    for i in range(fb):
+        check(lib.rpde_ns2d_rfft2(ptr(f3[i]), ptr(f_h[i * per:(i + 1) * per]), 1, M, N, ws.data_ptr(), nws, st), "ns2d_rfft2")
+    check(lib.rpde_ns2d_scale(ptr(f_h), ptr(c_g), ptr(g_h), fb, M, N, st), "ns2d_scale")
+    n_rec = steps // record_every
+    fields = torch.empty(max(n_rec, 1), B, 3, M, N, dtype=torch.float32, device=dev)
+    vort = torch.empty(max(n_rec, 1), B, M, N, dtype=torch.float32, device=dev)
+    for c in range(n_rec):
+        check(lib.rpde_nsc2d_steps(ptr(S), ptr(g_h), int(f.dim() == 3), ptr(c_w), ptr(c_f), ptr(d_w), ptr(d_f),
+                                   ptr(inv_lap), float(beta), B, M, N, record_every, ws.data_ptr(), nws, st), "nsc2d_steps")
+        check(lib.rpde_nsc2d_fields(ptr(S), ptr(inv_lap), ptr(fields[c]), B, M, N, ws.data_ptr(), nws, st), "nsc2d_fields")
+        check(lib.rpde_ns2d_irfft2(ptr(S), ptr(vort[c]), B, M, N, ws.data_ptr(), nws, st), "ns2d_irfft2")
+    return fields[:n_rec].transpose(0, 1).contiguous(), vort[:n_rec].transpose(0, 1).contiguous()
+
+
+# ----------------------------------------------------------------------------
 # 1-D exponential-time-differencing generator and the 1-D Gaussian random field (csrc/etd1d.hip, rpde_etd1d_* /
 # rpde_grf1d; data_generation/burgers_1d.py, ks_1d.py and random_fields.py are the callers).  Data production: no
 # autograd, GPU tensors only, no CPU fallback.
