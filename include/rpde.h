@@ -467,7 +467,7 @@ size_t rpde_grf2d_ws_bytes(int B, int M, int N);
 int rpde_grf2d(const float* noise, const float* sqrt_eig, float* out, int B, int M, int N,
                void* ws, size_t ws_bytes, void* stream);
 
-/* ---- active-scalar Navier-Stokes generator (csrc/ns_scalar.hip; an interface addition, the reference has no
+/* ---- active-scalar Navier-Stokes generator (csrc/ns_solver.hip, SCALAR; an interface addition, the reference has no
  * generator for its active-matter files): the vorticity equation above with a scalar c that the flow advects and that
  * drives the flow back through buoyancy along axis 2 (Boussinesq; the curl of the force is beta dc/dx1), on the same
  * half-spectrum layer and grids.  The state is two half spectra per sample in the layout above,

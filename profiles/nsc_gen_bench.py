@@ -1,4 +1,4 @@
-"""Time one step of the active-scalar Navier-Stokes generator (csrc/ns_scalar.hip, rpde_nsc2d_steps) against one step of
+"""Time one step of the active-scalar Navier-Stokes generator (csrc/ns_solver.hip, rpde_nsc2d_steps) against one step of
 the vorticity generator (csrc/ns_solver.hip, rpde_ns2d_steps) on the same GPU in the same run.  Does not touch bench.py.
 
     python profiles/nsc_gen_bench.py [--steps 50] [--repeats 7] [--sizes 256x50,64x50] [--out profiles/nsc_gen_bench.json]
@@ -8,7 +8,7 @@ events, alternating the two solvers; reported are the median, minimum and maximu
 ratio of the medians.  The coupled step transforms 6B + 2B images where the vorticity step transforms 4B + B, and its
 streaming kernels move bytes in about that proportion: the ratio to expect is 8/5 = 1.6.  The parts of the coupled step
 are timed the same way through the C ABI: the inverse transform of 6B spectra, the forward transform of 2B products, and
-the rest (k_nsc_advect + k_nsc_update_fanout) as the difference.  Needs the GPU: there is no fallback."""
+the rest (k_ns_advect<true> + k_ns_update_fanout<MODE, true>) as the difference.  Needs the GPU: there is no fallback."""
 from __future__ import annotations
 
 import argparse

@@ -18,13 +18,16 @@ struct HalfSpec { int images, M, N, K, kp; };
 inline HalfSpec hs_geom(int images, int M, int N) { return HalfSpec{images, M, N, N / 2 + 1, r4(N / 2 + 1)}; }
 inline size_t hs_per(const HalfSpec& g) { return (size_t)g.M * 2 * g.kp; }      // floats of one image
 inline size_t hs_elems(const HalfSpec& g) { return (size_t)g.images * hs_per(g); }
-// a generator grid: N even in range, M = 1 or even in range, images within gridDim.y, and the 4 x images derivative
-// fields of the Navier-Stokes step within the transforms' int rows (always so for M = 1)
-inline bool hs_dims_ok(int images, int M, int N) {
+// a generator grid: N even in range, M = 1 or even in range, and fan x images -- the largest batch the caller makes of
+// them -- within gridDim.y, four times that within the transforms' int rows (always so for M = 1).  fan = 1 is the
+// batch as it stands: with the factor four, the 4 x images derivative fields of the plain Navier-Stokes step.  The
+// active-scalar step passes 6, so that its 6 x images derivative spectra are held to both limits as a batch of their own
+inline bool hs_dims_ok(int images, int M, int N, int fan = 1) {
   const auto axis = [](int n) { return n >= HS_MIN_N && n <= HS_MAX_N && n % 2 == 0; };
-  return images > 0 && images <= 65535 && axis(N) && (M == 1 || axis(M)) && 4L * images * (M > N ? M : N) < (1L << 31);
+  return images > 0 && images <= 65535 / fan && axis(N) && (M == 1 || axis(M)) &&
+         4L * fan * images * (M > N ? M : N) < (1L << 31);
 }
-inline bool hs_dims2_ok(int images, int M, int N) { return M > 1 && hs_dims_ok(images, M, N); }     // two-dimensional only
+inline bool hs_dims2_ok(int images, int M, int N, int fan = 1) { return M > 1 && hs_dims_ok(images, M, N, fan); }   // 2-D only
 
 // `what`: the entry's name, a literal or a variable
 #define HS_CHECK_WS(what, ws) \
@@ -33,6 +36,10 @@ inline bool hs_dims2_ok(int images, int M, int N) { return M > 1 && hs_dims_ok(i
   RPDE_CHECK_ARG(hs_dims2_ok(B, M, N),                                                                            \
                  what ": bad B=%d M=%d N=%d (even axes %d .. %d, 4 B max(M, N) < 2^31, B <= 65535)", B, M, N, HS_MIN_N, \
                  HS_MAX_N)
+// the same with a fan-out factor, and `what` a variable
+#define HS_CHECK_DIMS_2D_FAN(what, B, M, N, fan)                                                                  \
+  RPDE_CHECK_ARG(hs_dims2_ok(B, M, N, fan), "%s: bad B=%d M=%d N=%d (even axes %d .. %d, %d B max(M, N) < 2^31, %d B <= 65535)", \
+                 what, B, M, N, HS_MIN_N, HS_MAX_N, 4 * (fan), fan)
 #define HS_CHECK_DIMS_1D(what, B, N)                                                                              \
   RPDE_CHECK_ARG(hs_dims_ok(B, 1, N), what ": bad B=%d N=%d (N even, %d .. %d, 1 <= B <= 65535)", B, N, HS_MIN_N, \
                  HS_MAX_N)

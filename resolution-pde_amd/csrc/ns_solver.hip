@@ -1,14 +1,21 @@
-// Navier-Stokes vorticity generator on the unit periodic square (reference: data_generation/ns_2d.py): pseudo-spectral,
-// Crank-Nicolson on the diffusion, explicit advection and forcing, 2/3 de-aliasing.  gfx950, wave64.
+// Navier-Stokes vorticity generator on the unit periodic square (reference: data_generation/ns_2d.py), plain or with an
+// active scalar c that the flow advects and that drives the flow back through buoyancy along axis 2 (Boussinesq: the
+// curl of the force is beta dc/dx1; data_generation/active_scalar_2d.py).  Pseudo-spectral, Crank-Nicolson on the
+// diffusions, explicit advection, buoyancy and forcing, 2/3 de-aliasing.  gfx950, wave64.
 //
-// The state is the half spectrum W = rfft2(w), [B][M][re|im][kp] (halfspec.h).  One step is six launches on the
-// caller's stream, no host synchronisation:
-//   rowdft + synthesis   one batched inverse 2-D transform of the 4B derivative spectra (q^, v^, w_x^, w_y^)
-//   k_ns_advect          F_phys = q w_x + v w_y
-//   analysis + rowdft    one forward 2-D transform of the B products
-//   k_ns_update_fanout   W <- c_w W - c_f F + g_h, and from the NEW W the four derivative spectra of the next step
-// with the coefficient tables formed by the caller in float64 and rounded to fp32 once:
-//   a = dt visc lap / 2,  c_w = (1 - a) / (1 + a),  c_f = dt dealias / (1 + a),  g_h = dt / (1 + a) f_h,  inv_lap = 1 / lap.
+// The state is the half spectrum W = rfft2(w), [B][M][re|im][kp] (halfspec.h); with the scalar, two per sample:
+// S = [W_0 .. W_{B-1}, C_0 .. C_{B-1}].  One step is six launches on the caller's stream, no host synchronisation:
+//   rowdft + synthesis   one batched inverse 2-D transform of the derivative spectra, 4B (q^, v^, w_1^, w_2^) or with
+//                        the scalar 6B (.. c_1^, c_2^)
+//   k_ns_advect          F_phys = q w_1 + v w_2, and with the scalar q c_1 + v c_2
+//   analysis + rowdft    one forward 2-D transform of the B (2B) products
+//   k_ns_update_fanout   W <- c_w W - c_f F + g_h, and from the NEW W the derivative spectra of the next step.  With the
+//                        scalar: W <- c_w W - c_f (F_w - beta 2 pi i k1 C) + g_h with the OLD C, C <- d_w C - d_f F_c,
+//                        and the fan-out from the new W and C
+// One code path serves both (SCALAR of the kernels and of ns_steps): the scalar's parts are additions to the plain step.
+// The coefficient tables are formed by the caller in float64 and rounded to fp32 once (rpde.ops.ns2d_tables, nsc2d_tables):
+//   a = dt visc lap / 2,  c_w = (1 - a) / (1 + a),  c_f = dt dealias / (1 + a),  g_h = dt / (1 + a) f_h,  inv_lap = 1 / lap,
+//   d_w and d_f as c_w and c_f with the scalar's diffusivity.
 // The transforms are the full-spectrum real 2-D DFT of cf_dft.h (hs_rfft / hs_irfft, GEMM form); the rfft2 / irfft2
 // entries and the random field that seeds the solver are in halfspec.hip.  Everything else here streams: a thread owns
 // one 16-byte group of kx for both re and im, so a wave covers whole 128-byte lines of every array it reads or writes.
@@ -19,48 +26,69 @@ namespace rpde {
 
 constexpr float NS_TWO_PI = 6.28318530717958647692f;
 
-// MODE 0: fan-out only (the first step of a call: W is read, not written)
-//      1: update, then fan-out of the new W
+// the step's tables; the plain step has, and so passes, only the first three
+template <bool SCALAR> struct NsTables { const float *cw, *cf, *il; };
+template <> struct NsTables<true> { const float *cw, *cf, *il, *dw, *df; float beta; };
+
+// MODE 0: fan-out only (the first step of a call: the state is read, not written)
+//      1: update, then fan-out of the new state
 //      2: update only (the last step of a call)
-// grid (blocks, B).  D is [4][B] spectra: q^ = 2 pi i k2 psi, v^ = -2 pi i k1 psi, w_x^ = 2 pi i k1 W, w_y^ = 2 pi i k2 W,
-// psi = W inv_lap.  g_h has gstride floats between samples (0: one forcing for the batch).  Padded columns
-// (kx > N/2) are written as zeros in W and in D: the synthesis reads them.
-template <int MODE>
-__global__ __launch_bounds__(256) void k_ns_update_fanout(float* __restrict__ W, const float* __restrict__ F,
-                                                          const float* __restrict__ gh, long gstride,
-                                                          const float* __restrict__ cw, const float* __restrict__ cf,
-                                                          const float* __restrict__ il, float* __restrict__ D, HalfSpec g) {
+// grid (blocks, B), g.images = B.  F is [1 | 2][B] spectra (F_w, F_c), D is [4 | 6][B]: q^ = 2 pi i k2 psi,
+// v^ = -2 pi i k1 psi, w_1^ = 2 pi i k1 W, w_2^ = 2 pi i k2 W, c_1^ = 2 pi i k1 C, c_2^ = 2 pi i k2 C, psi = W inv_lap.
+// g_h has gstride floats between samples (0: one forcing for the batch).  Padded columns (kx > N/2) are written as
+// zeros in the state and in D: the synthesis reads them.
+template <int MODE, bool SCALAR>
+__global__ __launch_bounds__(256) void k_ns_update_fanout(float* __restrict__ S, const float* __restrict__ F,
+                                                          const float* __restrict__ gh, long gstride, NsTables<SCALAR> t,
+                                                          float* __restrict__ D, HalfSpec g) {
   const int b = blockIdx.y;
   const int c4n = g.kp / 4, per4 = g.M * c4n;
-  const long per = (long)g.M * 2 * g.kp, dstride = (long)g.images * per;
-  float* __restrict__ Wb = W + (long)b * per;
-  const float* __restrict__ Fb = F + (long)b * per;
+  const long per = (long)g.M * 2 * g.kp, half = (long)g.images * per;
+  float* __restrict__ Wb = S + (long)b * per;
+  float* __restrict__ Cb = Wb + half;                   // the scalar's spectra and products: SCALAR only
+  const float* __restrict__ Fw = F + (long)b * per;
+  const float* __restrict__ Fc = Fw + half;
   const float* __restrict__ gb = gh + (long)b * gstride;
   float* __restrict__ Db = D + (long)b * per;
   for (int v = blockIdx.x * 256 + threadIdx.x; v < per4; v += gridDim.x * 256) {
     const int ky = v / c4n, kx0 = (v - ky * c4n) * 4;
     const long ore = (long)ky * 2 * g.kp + kx0, oim = ore + g.kp, ot = (long)ky * g.kp + kx0;
-    float wr[4], wi[4];
-    ld4(Wb + ore, wr);
-    ld4(Wb + oim, wi);
+    const float k1 = NS_TWO_PI * (float)(ky < g.M / 2 ? ky : ky - g.M);
+    float wr[4], wi[4], cr[4], ci[4];
+    ld4(Wb + ore, wr); ld4(Wb + oim, wi);
+    if constexpr (SCALAR) { ld4(Cb + ore, cr); ld4(Cb + oim, ci); }
     if (MODE != 0) {
       float fr[4], fi[4], gr[4], gi[4], a[4], c[4];
-      ld4(Fb + ore, fr); ld4(Fb + oim, fi);
+      ld4(Fw + ore, fr); ld4(Fw + oim, fi);
       ld4(gb + ore, gr); ld4(gb + oim, gi);
-      ld4(cw + ot, a);   ld4(cf + ot, c);
+      ld4(t.cw + ot, a); ld4(t.cf + ot, c);
+      if constexpr (SCALAR) {
+        float er[4], ei[4], p[4], q[4];
+        ld4(Fc + ore, er); ld4(Fc + oim, ei);
+        ld4(t.dw + ot, p); ld4(t.df + ot, q);
+        const float bk = t.beta * k1;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const bool live = kx0 + j < g.K;
+          // F_w - beta 2 pi i k1 C = (F_re + bk C_im) + i (F_im - bk C_re), C of the old time level
+          fr[j] = fmaf(bk, ci[j], fr[j]);
+          fi[j] = fmaf(-bk, cr[j], fi[j]);
+          cr[j] = live ? fmaf(p[j], cr[j], -(q[j] * er[j])) : 0.f;
+          ci[j] = live ? fmaf(p[j], ci[j], -(q[j] * ei[j])) : 0.f;
+        }
+        st4(Cb + ore, cr); st4(Cb + oim, ci);
+      }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const bool live = kx0 + j < g.K;
         wr[j] = live ? fmaf(a[j], wr[j], fmaf(-c[j], fr[j], gr[j])) : 0.f;
         wi[j] = live ? fmaf(a[j], wi[j], fmaf(-c[j], fi[j], gi[j])) : 0.f;
       }
-      st4(Wb + ore, wr);
-      st4(Wb + oim, wi);
+      st4(Wb + ore, wr); st4(Wb + oim, wi);
     }
     if (MODE != 2) {
       float li[4], qr[4], qi[4], vr[4], vi[4], xr[4], xi[4], yr[4], yi[4];
-      ld4(il + ot, li);
-      const float k1 = NS_TWO_PI * (float)(ky < g.M / 2 ? ky : ky - g.M);
+      ld4(t.il + ot, li);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const bool live = kx0 + j < g.K;
@@ -71,23 +99,73 @@ __global__ __launch_bounds__(256) void k_ns_update_fanout(float* __restrict__ W,
         xr[j] = live ? -k1 * wi[j] : 0.f;  xi[j] = live ? k1 * wr[j] : 0.f;
         yr[j] = live ? -k2 * wi[j] : 0.f;  yi[j] = live ? k2 * wr[j] : 0.f;
       }
-      st4(Db + ore, qr);               st4(Db + oim, qi);
-      st4(Db + dstride + ore, vr);     st4(Db + dstride + oim, vi);
-      st4(Db + 2 * dstride + ore, xr); st4(Db + 2 * dstride + oim, xi);
-      st4(Db + 3 * dstride + ore, yr); st4(Db + 3 * dstride + oim, yi);
+      st4(Db + ore, qr);            st4(Db + oim, qi);
+      st4(Db + half + ore, vr);     st4(Db + half + oim, vi);
+      st4(Db + 2 * half + ore, xr); st4(Db + 2 * half + oim, xi);
+      st4(Db + 3 * half + ore, yr); st4(Db + 3 * half + oim, yi);
+      if constexpr (SCALAR) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const bool live = kx0 + j < g.K;
+          const float k2 = NS_TWO_PI * (float)(kx0 + j);
+          xr[j] = live ? -k1 * ci[j] : 0.f;  xi[j] = live ? k1 * cr[j] : 0.f;
+          yr[j] = live ? -k2 * ci[j] : 0.f;  yi[j] = live ? k2 * cr[j] : 0.f;
+        }
+        st4(Db + 4 * half + ore, xr); st4(Db + 4 * half + oim, xi);
+        st4(Db + 5 * half + ore, yr); st4(Db + 5 * half + oim, yi);
+      }
     }
   }
 }
 
-// P [4][B M N] = (q, v, w_x, w_y) -> out = q w_x + v w_y; n4 float4 groups per field (M, N even and the workspace pieces
-// 256-byte aligned: always whole, aligned groups)
+// S -> D [B][3] spectra (C, q^, v^), sample-major: their inverse transform is out [B, 3, M, N] = (c, q, v) as it stands.
+// grid (blocks, B), g.images = B; padded columns zero
+__global__ __launch_bounds__(256) void k_nsc_fields_fanout(const float* __restrict__ S, const float* __restrict__ il,
+                                                           float* __restrict__ D, HalfSpec g) {
+  const int b = blockIdx.y;
+  const int c4n = g.kp / 4, per4 = g.M * c4n;
+  const long per = (long)g.M * 2 * g.kp, half = (long)g.images * per;
+  const float* __restrict__ Wb = S + (long)b * per;
+  const float* __restrict__ Cb = Wb + half;
+  float* __restrict__ Db = D + (long)b * 3 * per;
+  for (int v = blockIdx.x * 256 + threadIdx.x; v < per4; v += gridDim.x * 256) {
+    const int ky = v / c4n, kx0 = (v - ky * c4n) * 4;
+    const long ore = (long)ky * 2 * g.kp + kx0, oim = ore + g.kp, ot = (long)ky * g.kp + kx0;
+    const float k1 = NS_TWO_PI * (float)(ky < g.M / 2 ? ky : ky - g.M);
+    float wr[4], wi[4], cr[4], ci[4], li[4], qr[4], qi[4], vr[4], vi[4];
+    ld4(Wb + ore, wr); ld4(Wb + oim, wi);
+    ld4(Cb + ore, cr); ld4(Cb + oim, ci);
+    ld4(il + ot, li);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const bool live = kx0 + j < g.K;
+      const float k2 = NS_TWO_PI * (float)(kx0 + j);
+      const float pr = wr[j] * li[j], pi = wi[j] * li[j];
+      cr[j] = live ? cr[j] : 0.f;      ci[j] = live ? ci[j] : 0.f;
+      qr[j] = live ? -k2 * pi : 0.f;   qi[j] = live ? k2 * pr : 0.f;
+      vr[j] = live ? k1 * pi : 0.f;    vi[j] = live ? -k1 * pr : 0.f;
+    }
+    st4(Db + ore, cr);           st4(Db + oim, ci);
+    st4(Db + per + ore, qr);     st4(Db + per + oim, qi);
+    st4(Db + 2 * per + ore, vr); st4(Db + 2 * per + oim, vi);
+  }
+}
+
+// P [4 | 6][B M N] = (q, v, w_1, w_2, c_1, c_2) -> out [1 | 2][B M N] = (q w_1 + v w_2, q c_1 + v c_2); n4 float4 groups
+// per field (M, N even and the workspace pieces 256-byte aligned: always whole, aligned groups)
+template <bool SCALAR>
 __global__ __launch_bounds__(256) void k_ns_advect(const float* __restrict__ P, float* __restrict__ out, long n4) {
   const float4* __restrict__ q = reinterpret_cast<const float4*>(P);
-  const float4 *__restrict__ v = q + n4, *__restrict__ wx = q + 2 * n4, *__restrict__ wy = q + 3 * n4;
+  const float4 *__restrict__ v = q + n4, *__restrict__ w1 = q + 2 * n4, *__restrict__ w2 = q + 3 * n4;
+  const float4 *__restrict__ c1 = q + 4 * n4, *__restrict__ c2 = q + 5 * n4;
+  float4* __restrict__ o = reinterpret_cast<float4*>(out);
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-    const float4 a = q[i], b = v[i], c = wx[i], d = wy[i];
-    reinterpret_cast<float4*>(out)[i] =
-        make_float4(fmaf(a.x, c.x, b.x * d.x), fmaf(a.y, c.y, b.y * d.y), fmaf(a.z, c.z, b.z * d.z), fmaf(a.w, c.w, b.w * d.w));
+    const float4 a = q[i], b = v[i], c = w1[i], d = w2[i];
+    o[i] = make_float4(fmaf(a.x, c.x, b.x * d.x), fmaf(a.y, c.y, b.y * d.y), fmaf(a.z, c.z, b.z * d.z), fmaf(a.w, c.w, b.w * d.w));
+    if constexpr (SCALAR) {
+      const float4 e = c1[i], f = c2[i];
+      o[n4 + i] = make_float4(fmaf(a.x, e.x, b.x * f.x), fmaf(a.y, e.y, b.y * f.y), fmaf(a.z, e.z, b.z * f.z), fmaf(a.w, e.w, b.w * f.w));
+    }
   }
 }
 
@@ -109,6 +187,80 @@ __global__ __launch_bounds__(256) void k_ns_scale(const float* __restrict__ spec
   }
 }
 
+// Per sample, the derivative spectra of a step and its products.  The plain step's 4B derivative spectra are what the
+// limits of a generator grid already count; the 6B of the scalar step are held to them as a batch of their own
+// (hs_dims_ok's fan)
+constexpr int ns_derivs(bool scalar) { return scalar ? 6 : 4; }
+constexpr int ns_products(bool scalar) { return scalar ? 2 : 1; }
+inline bool ns_dims_ok(bool scalar, int B, int M, int N) { return hs_dims2_ok(B, M, N, scalar ? ns_derivs(true) : 1); }
+
+// The workspace of a step: the derivative spectra and their column stage, the fields, their products, the products' row
+// spectra and spectra.  ws null: only `bytes` counts.  The transforms alone need one spectrum, rpde_nsc2d_fields the
+// first two pieces with 3B spectra each
+struct NsWork {
+  float *D, *T1, *P, *Fp, *S1, *F;
+  size_t bytes = 0;
+  NsWork(bool scalar, size_t spec, size_t phys, void* ws) {
+    const auto take = [&](size_t floats) {
+      float* p = ws ? reinterpret_cast<float*>(static_cast<char*>(ws) + bytes) : nullptr;
+      bytes += arena_bytes(floats);
+      return p;
+    };
+    const size_t nd = ns_derivs(scalar), np = ns_products(scalar);
+    D = take(nd * spec);
+    T1 = take(nd * spec);
+    P = take(nd * phys);
+    Fp = take(np * phys);
+    S1 = take(np * spec);
+    F = take(np * spec);
+  }
+};
+
+static size_t ns_ws_bytes(bool scalar, int B, int M, int N) {
+  if (!ns_dims_ok(scalar, B, M, N)) return 0;
+  return NsWork(scalar, hs_elems(hs_geom(B, M, N)), (size_t)B * M * N, nullptr).bytes;
+}
+
+// rpde_ns2d_steps and rpde_nsc2d_steps: the checks, the workspace, the first fan-out and nsteps times six launches
+template <bool SCALAR>
+static int ns_steps(float* S, const float* g_h, int g_batched, const NsTables<SCALAR>& t, int B, int M, int N, int nsteps,
+                    void* ws, size_t ws_bytes, void* stream) {
+  const char* what = SCALAR ? "nsc2d_steps" : "ns2d_steps";
+  bool tables = t.cw && t.cf && t.il, aligned = al16(S) && al16(g_h) && al16(t.cw) && al16(t.cf) && al16(t.il);
+  if constexpr (SCALAR) {
+    tables = tables && t.dw && t.df;
+    aligned = aligned && al16(t.dw) && al16(t.df);
+  }
+  RPDE_CHECK_ARG(S && g_h && tables && ws, "%s: null pointer", what);
+  if (SCALAR) HS_CHECK_DIMS_2D_FAN(what, B, M, N, ns_derivs(true));
+  else HS_CHECK_DIMS_2D("ns2d_steps", B, M, N);
+  HS_CHECK_WS(what, ws);
+  RPDE_CHECK_ARG(nsteps >= 0, "%s: nsteps %d < 0", what, nsteps);
+  RPDE_CHECK_ARG(aligned, "%s: state, forcing and tables must be 16-byte aligned", what);
+  // the state; the products; the derivative fields
+  const HalfSpec g = hs_geom(B, M, N), gp = hs_geom(ns_products(SCALAR) * B, M, N), gd = hs_geom(ns_derivs(SCALAR) * B, M, N);
+  const size_t phys = (size_t)B * M * N;
+  const NsWork w(SCALAR, hs_elems(g), phys, ws);
+  if (w.bytes > ws_bytes) { set_error("%s: workspace too small", what); return RPDE_ERR_WORKSPACE; }
+  if (nsteps == 0) return RPDE_OK;
+  hipStream_t st = as_stream(stream);
+  const dim3 ug = hs_grid((long)M * (g.kp / 4), B);
+  const long gstride = g_batched ? (long)hs_per(g) : 0;
+  const long n4 = (long)phys / 4;
+  hipLaunchKernelGGL((k_ns_update_fanout<0, SCALAR>), ug, dim3(256), 0, st, S, w.F, g_h, gstride, t, w.D, g);
+  RPDE_LAUNCH_CHECK();
+  for (int j = 0; j < nsteps; ++j) {
+    RPDE_TRY(hs_irfft(gd, w.D, w.T1, w.P, st));
+    hipLaunchKernelGGL(k_ns_advect<SCALAR>, dim3(hs_blocks(n4, 2048)), dim3(256), 0, st, w.P, w.Fp, n4);
+    RPDE_LAUNCH_CHECK();
+    RPDE_TRY(hs_rfft(gp, w.Fp, w.S1, w.F, st));
+    if (j + 1 < nsteps) hipLaunchKernelGGL((k_ns_update_fanout<1, SCALAR>), ug, dim3(256), 0, st, S, w.F, g_h, gstride, t, w.D, g);
+    else hipLaunchKernelGGL((k_ns_update_fanout<2, SCALAR>), ug, dim3(256), 0, st, S, w.F, g_h, gstride, t, w.D, g);
+    RPDE_LAUNCH_CHECK();
+  }
+  return RPDE_OK;
+}
+
 }  // namespace rpde
 
 using namespace rpde;
@@ -117,13 +269,9 @@ extern "C" {
 
 size_t rpde_ns2d_spec_elems(int B, int M, int N) { return hs_dims2_ok(B, M, N) ? hs_elems(hs_geom(B, M, N)) : 0; }
 
-size_t rpde_ns2d_ws_bytes(int B, int M, int N) {
-  if (!hs_dims2_ok(B, M, N)) return 0;
-  const size_t spec = hs_elems(hs_geom(B, M, N)), phys = (size_t)B * M * N;
-  // rpde_ns2d_steps: derivative spectra and their column stage (4B each), the four fields, their product, the
-  // product's row spectra and spectrum; the transforms alone need one spectrum
-  return 2 * arena_bytes(4 * spec) + arena_bytes(4 * phys) + arena_bytes(phys) + 2 * arena_bytes(spec);
-}
+size_t rpde_ns2d_ws_bytes(int B, int M, int N) { return ns_ws_bytes(false, B, M, N); }
+
+size_t rpde_nsc2d_ws_bytes(int B, int M, int N) { return ns_ws_bytes(true, B, M, N); }
 
 int rpde_ns2d_scale(const float* spec, const float* table, float* out, int B, int M, int N, void* stream) {
   RPDE_CHECK_ARG(spec && table && out, "ns2d_scale: null pointer");
@@ -137,39 +285,32 @@ int rpde_ns2d_scale(const float* spec, const float* table, float* out, int B, in
 
 int rpde_ns2d_steps(float* W, const float* g_h, int g_batched, const float* c_w, const float* c_f, const float* inv_lap,
                     int B, int M, int N, int nsteps, void* ws, size_t ws_bytes, void* stream) {
-  RPDE_CHECK_ARG(W && g_h && c_w && c_f && inv_lap && ws, "ns2d_steps: null pointer");
-  HS_CHECK_DIMS_2D("ns2d_steps", B, M, N);
-  HS_CHECK_WS("ns2d_steps", ws);
-  RPDE_CHECK_ARG(nsteps >= 0, "ns2d_steps: nsteps %d < 0", nsteps);
-  RPDE_CHECK_ARG(al16(W) && al16(g_h) && al16(c_w) && al16(c_f) && al16(inv_lap),
-                 "ns2d_steps: state, forcing and tables must be 16-byte aligned");
-  const HalfSpec g = hs_geom(B, M, N), g4 = hs_geom(4 * B, M, N);      // the state; the four derivative fields
-  const size_t spec = hs_elems(g), phys = (size_t)B * M * N;
+  return ns_steps<false>(W, g_h, g_batched, NsTables<false>{c_w, c_f, inv_lap}, B, M, N, nsteps, ws, ws_bytes, stream);
+}
+
+int rpde_nsc2d_steps(float* S, const float* g_h, int g_batched, const float* c_w, const float* c_f, const float* d_w,
+                     const float* d_f, const float* inv_lap, float beta, int B, int M, int N, int nsteps, void* ws,
+                     size_t ws_bytes, void* stream) {
+  return ns_steps<true>(S, g_h, g_batched, NsTables<true>{c_w, c_f, inv_lap, d_w, d_f, beta}, B, M, N, nsteps, ws, ws_bytes,
+                        stream);
+}
+
+int rpde_nsc2d_fields(const float* S, const float* inv_lap, float* out, int B, int M, int N, void* ws, size_t ws_bytes,
+                      void* stream) {
+  RPDE_CHECK_ARG(S && inv_lap && out && ws, "nsc2d_fields: null pointer");
+  HS_CHECK_DIMS_2D_FAN("nsc2d_fields", B, M, N, ns_derivs(true));
+  HS_CHECK_WS("nsc2d_fields", ws);
+  RPDE_CHECK_ARG(al16(S) && al16(inv_lap) && al16(out), "nsc2d_fields: state, table and output must be 16-byte aligned");
+  const HalfSpec g = hs_geom(B, M, N), g3 = hs_geom(3 * B, M, N);
+  const size_t spec = hs_elems(g);
   Arena ar(ws, ws_bytes);
-  float* D = ar.take(4 * spec);
-  float* T1 = ar.take(4 * spec);
-  float* P = ar.take(4 * phys);
-  float* Fp = ar.take(phys);
-  float* S1 = ar.take(spec);
-  float* F = ar.take(spec);
-  if (!ar.ok()) { set_error("ns2d_steps: workspace too small"); return RPDE_ERR_WORKSPACE; }
-  if (nsteps == 0) return RPDE_OK;
+  float* D = ar.take(3 * spec);
+  float* T1 = ar.take(3 * spec);
+  if (!ar.ok()) { set_error("nsc2d_fields: workspace too small"); return RPDE_ERR_WORKSPACE; }
   hipStream_t st = as_stream(stream);
-  const dim3 ug = hs_grid((long)M * (g.kp / 4), B);
-  const long gstride = g_batched ? (long)hs_per(g) : 0;
-  const long n4 = (long)phys / 4;
-  hipLaunchKernelGGL(k_ns_update_fanout<0>, ug, dim3(256), 0, st, W, F, g_h, gstride, c_w, c_f, inv_lap, D, g);
+  hipLaunchKernelGGL(k_nsc_fields_fanout, hs_grid((long)M * (g.kp / 4), B), dim3(256), 0, st, S, inv_lap, D, g);
   RPDE_LAUNCH_CHECK();
-  for (int j = 0; j < nsteps; ++j) {
-    RPDE_TRY(hs_irfft(g4, D, T1, P, st));
-    hipLaunchKernelGGL(k_ns_advect, dim3(hs_blocks(n4, 2048)), dim3(256), 0, st, P, Fp, n4);
-    RPDE_LAUNCH_CHECK();
-    RPDE_TRY(hs_rfft(g, Fp, S1, F, st));
-    if (j + 1 < nsteps) hipLaunchKernelGGL(k_ns_update_fanout<1>, ug, dim3(256), 0, st, W, F, g_h, gstride, c_w, c_f, inv_lap, D, g);
-    else hipLaunchKernelGGL(k_ns_update_fanout<2>, ug, dim3(256), 0, st, W, F, g_h, gstride, c_w, c_f, inv_lap, D, g);
-    RPDE_LAUNCH_CHECK();
-  }
-  return RPDE_OK;
+  return hs_irfft(g3, D, T1, out, st);
 }
 
 }  // extern "C"

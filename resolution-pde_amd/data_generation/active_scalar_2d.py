@@ -6,7 +6,7 @@ read, which cannot be regenerated (the reference has no generator for them).
     active_scalar_2d(w0, c0, f, visc, kappa, beta, T, delta_t, record_steps)
         -> fields [B, record_steps, 3, M, N] = (c, q, v), vorticity [B, record_steps, M, N], sol_t [record_steps]
 
-with the schedule of data_generation/ns_2d.py; the solver is rpde.ops.nsc2d_solve (csrc/ns_scalar.hip).  As a script it
+with the schedule of data_generation/ns_2d.py; the solver is rpde.ops.nsc2d_solve (csrc/ns_solver.hip).  As a script it
 writes --files .npz archives active_scalar_visc_<v>_kappa_<k>_beta_<b>_<i>.npz whose members carry the names of the HDF5
 files' datasets ('/' separates groups; dataloaders/_store.py reads them as such), T = --record-steps:
 

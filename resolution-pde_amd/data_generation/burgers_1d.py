@@ -41,7 +41,7 @@ _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if _ROOT not in sys.path:
     sys.path.insert(0, _ROOT)
 
-from data_generation.etd1d import integrate, resolutions_of, snapshot_schedule  # noqa: E402
+from data_generation.etd1d import check_samples, integrate, resolutions_of, snapshot_schedule  # noqa: E402
 from data_generation.random_fields import GaussianRF1d  # noqa: E402
 
 IC_ALPHA, IC_TAU, IC_SIGMA = 2.0, 5.0, 25.0
@@ -74,8 +74,7 @@ def main(argv: Optional[List[str]] = None) -> List[str]:
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", required=True, help="output folder")
     args = ap.parse_args(argv)
-    if args.samples < 1 or args.batch < 1 or args.batch > 65535:
-        ap.error("--samples and --batch must be positive, --batch at most 65535")
+    check_samples(args, ap)
     if args.snapshots < 2:
         ap.error("--snapshots counts the initial condition: at least 2")
     if not (args.viscosity > 0 and args.length > 0):

@@ -41,15 +41,15 @@ import os
 import sys
 from typing import List, Optional
 
-import numpy as np
 import torch
 
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if _ROOT not in sys.path:
     sys.path.insert(0, _ROOT)
 
-from data_generation.etd1d import integrate, resolutions_of  # noqa: E402
-from data_generation.ks_1d import _SPLIT_STREAM, SPLITS, ks_initial_condition, ks_schedule  # noqa: E402
+from data_generation.etd1d import (add_trajectory_arguments, check_samples, integrate, trajectory_resolutions,  # noqa: E402
+                                   write_trajectories)
+from data_generation.ks_1d import ks_initial_condition  # noqa: E402
 
 
 def kdv_1d(u0, length, T, dt=0.01, record_steps=1, dispersion=1.0, viscosity=0.0):
@@ -74,64 +74,27 @@ def main(argv: Optional[List[str]] = None) -> List[str]:
     ap.add_argument("--dispersion", type=float, default=1.0, help="coefficient of u_xxx")
     ap.add_argument("--viscosity", type=float, default=0.0, help="coefficient of u_xx on the right (KdV-Burgers when > 0)")
     ap.add_argument("--amplitude", type=float, default=2.0, help="factor on the KS initial condition")
-    ap.add_argument("--L", type=float, default=64.0)
-    ap.add_argument("--lmax", type=int, default=8)
-    ap.add_argument("--et", type=float, default=5.0, help="end time")
-    ap.add_argument("--nte", type=int, default=51, help="snapshots kept (the last nte of nt)")
-    ap.add_argument("--nt", type=int, default=51, help="snapshots over [0, et], the initial condition first")
-    ap.add_argument("--resolution", type=int, default=256)
-    ap.add_argument("--resolutions", default="", help="comma-separated: one solve per entry, each at its own resolution")
-    ap.add_argument("--dt", type=float, default=0.01)
-    ap.add_argument("--samples", type=int, default=2048)
-    ap.add_argument("--batch", type=int, default=512)
-    ap.add_argument("--split", choices=SPLITS, default="train")
-    ap.add_argument("--flat", action="store_true", help="write straight into --out (one resolution)")
-    ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--out", required=True, help="output folder")
+    add_trajectory_arguments(ap)
     args = ap.parse_args(argv)
-    if args.samples < 1 or args.batch < 1 or args.batch > 65535:
-        ap.error("--samples and --batch must be positive, --batch at most 65535")
+    check_samples(args, ap)
     if not (args.L > 0 and args.lmax >= 1 and args.amplitude > 0):
         ap.error("--L and --amplitude must be positive, --lmax at least 1")
     if args.dispersion == 0 or not args.viscosity >= 0:
         ap.error("--dispersion must not be zero, --viscosity not negative")
-    resolutions = resolutions_of(args, ap)
-    if args.flat and len(resolutions) != 1:
-        ap.error("--flat holds one resolution")
-    try:                                                               # argument errors before any device work
-        steps, every, times = ks_schedule(args.et, args.nt, args.nte, args.dt)
-    except ValueError as e:
-        ap.error(str(e))
-    if not torch.cuda.is_available():
-        raise RuntimeError("kdv_1d.py generates on the GPU; there is no CPU path")
-    dev = torch.device("cuda")
-    nt, nte = args.nt, args.nte
-    t = np.asarray(times[nt - nte:], dtype=np.float32)
-    written = []
-    for X in resolutions:
-        gen = torch.Generator().manual_seed(args.seed + X + _SPLIT_STREAM[args.split])
-        u = np.empty((args.samples, nte, X), dtype=np.float32)
-        for c in range(0, args.samples, args.batch):
-            b = min(args.batch, args.samples - c)
-            u0 = (args.amplitude * ks_initial_condition(b, X, args.L, args.lmax, gen).double()).float()
-            sol, _ = kdv_1d(u0.to(dev), args.L, args.et, args.dt, nt - 1, args.dispersion, args.viscosity)
-            sol = sol.cpu()
-            if not bool(torch.isfinite(sol).all()):
-                raise RuntimeError(f"kdv_1d: non-finite values at resolution {X} with dt = {args.dt:g} (amplitude "
-                                   f"{args.amplitude:g}, dispersion {args.dispersion:g}): the step is too long for this "
-                                   "amplitude -- lower --dt")
-            full = torch.cat([u0[:, None, :], sol], dim=1)             # [b, nt, X]
-            u[c:c + b] = full[:, nt - nte:].numpy()
-            print(f"[kdv_1d] {args.split} resolution {X}: {c + b}/{args.samples} samples", flush=True)
-        path = kdv_path(args.out, args.split, X, args.samples, args.flat)
-        os.makedirs(os.path.dirname(path), exist_ok=True)
-        s = args.split
-        np.savez(path, **{f"{s}/pde_{nte}-{X}": u, f"{s}/t": t,
-                          f"{s}/x": (np.arange(X, dtype=np.float64) * (args.L / X)).astype(np.float32),
-                          f"{s}/dx": np.float32(args.L / X), f"{s}/dt": np.float32(every * args.dt)})
-        print(f"[kdv_1d] wrote {path}: {s}/pde_{nte}-{X} {u.shape}", flush=True)
-        written.append(path)
-    return written
+    resolutions = trajectory_resolutions(args, ap)
+
+    def solve(u0, X):
+        sol = kdv_1d(u0, args.L, args.et, args.dt, args.nt - 1, args.dispersion, args.viscosity)[0].cpu()
+        if not bool(torch.isfinite(sol).all()):
+            raise RuntimeError(f"kdv_1d: non-finite values at resolution {X} with dt = {args.dt:g} (amplitude "
+                               f"{args.amplitude:g}, dispersion {args.dispersion:g}): the step is too long for this "
+                               "amplitude -- lower --dt")
+        return sol
+
+    return write_trajectories(
+        "kdv_1d", args, ap, resolutions,
+        lambda b, X, gen: (args.amplitude * ks_initial_condition(b, X, args.L, args.lmax, gen).double()).float(),
+        solve, lambda X: kdv_path(args.out, args.split, X, args.samples, args.flat))
 
 
 if __name__ == "__main__":

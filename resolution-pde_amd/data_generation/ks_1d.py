@@ -33,17 +33,14 @@ import os
 import sys
 from typing import List, Optional
 
-import numpy as np
 import torch
 
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if _ROOT not in sys.path:
     sys.path.insert(0, _ROOT)
 
-from data_generation.etd1d import integrate, resolutions_of, snapshot_schedule  # noqa: E402
-
-SPLITS = ("train", "valid", "test")
-_SPLIT_STREAM = {"train": 0, "valid": 100003, "test": 200003}
+from data_generation.etd1d import (add_trajectory_arguments, check_samples, integrate, ks_schedule,  # noqa: E402,F401
+                                   trajectory_resolutions, write_trajectories)
 
 
 def ks_1d(u0, viscosity, length, T, dt=0.01, record_steps=1):
@@ -63,17 +60,6 @@ def ks_initial_condition(samples: int, X: int, length: float, lmax: int, generat
     x = torch.arange(X, dtype=torch.float64) * (float(length) / X)
     u = (A[..., None] * torch.sin(2.0 * math.pi * l[..., None] * x / float(length) + phi[..., None])).sum(1)
     return u.to(torch.float32)
-
-
-def ks_schedule(et: float, nt: int, nte: int, dt: float):
-    """(steps, record_every, times [nt]) of nt snapshots over [0, et] with the first at 0; nte <= nt of them are kept"""
-    nt, nte = int(nt), int(nte)
-    if nt < 2:
-        raise ValueError(f"nt counts the initial condition: at least 2, got {nt}")
-    if nte < 2 or nte > nt:
-        raise ValueError(f"nte must be 2 .. nt = {nt}, got {nte}")
-    steps, every, times = snapshot_schedule(et, dt, nt - 1)
-    return steps, every, [0.0] + times
 
 
 def damped_modes(X: int, length: float, viscosity: float) -> int:
@@ -96,67 +82,34 @@ def ks_path(out: str, split: str, resolution: int, viscosity: float, L: float, l
 def main(argv: Optional[List[str]] = None) -> List[str]:
     ap = argparse.ArgumentParser(description="Generate 1-D Kuramoto-Sivashinsky trajectories on the GPU")
     ap.add_argument("--viscosity", type=float, default=0.05)
-    ap.add_argument("--L", type=float, default=64.0)
-    ap.add_argument("--lmax", type=int, default=8)
-    ap.add_argument("--et", type=float, default=5.0, help="end time")
-    ap.add_argument("--nte", type=int, default=51, help="snapshots kept (the last nte of nt)")
-    ap.add_argument("--nt", type=int, default=51, help="snapshots over [0, et], the initial condition first")
-    ap.add_argument("--resolution", type=int, default=256)
-    ap.add_argument("--resolutions", default="", help="comma-separated: one solve per entry, each at its own resolution")
-    ap.add_argument("--dt", type=float, default=0.01)
-    ap.add_argument("--samples", type=int, default=2048)
-    ap.add_argument("--batch", type=int, default=512)
-    ap.add_argument("--split", choices=SPLITS, default="train")
-    ap.add_argument("--flat", action="store_true", help="write straight into --out (one resolution)")
-    ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--out", required=True, help="output folder")
+    add_trajectory_arguments(ap)
     args = ap.parse_args(argv)
-    if args.samples < 1 or args.batch < 1 or args.batch > 65535:
-        ap.error("--samples and --batch must be positive, --batch at most 65535")
+    check_samples(args, ap)
     if not (args.viscosity > 0 and args.L > 0 and args.lmax >= 1):
         ap.error("--viscosity and --L must be positive, --lmax at least 1")
-    resolutions = resolutions_of(args, ap)
-    if args.flat and len(resolutions) != 1:
-        ap.error("--flat holds one resolution")
+    resolutions = trajectory_resolutions(args, ap)
     for X in resolutions:
         if damped_modes(X, args.L, args.viscosity) < 1:
             ap.error(f"resolution {X} is too coarse for viscosity {args.viscosity:g} on L = {args.L:g}: every mode the "
                      f"2/3 rule keeps is linearly unstable (kappa^2 < 1/nu), so nothing dissipates and the run blows up")
-    try:                                                               # argument errors before any device work
-        steps, every, times = ks_schedule(args.et, args.nt, args.nte, args.dt)
-    except ValueError as e:
-        ap.error(str(e))
-    if not torch.cuda.is_available():
-        raise RuntimeError("ks_1d.py generates on the GPU; there is no CPU path")
-    dev = torch.device("cuda")
-    nt, nte = args.nt, args.nte
-    t = np.asarray(times[nt - nte:], dtype=np.float32)
-    written = []
-    for X in resolutions:
-        gen = torch.Generator().manual_seed(args.seed + X + _SPLIT_STREAM[args.split])
-        u = np.empty((args.samples, nte, X), dtype=np.float32)
-        for c in range(0, args.samples, args.batch):
-            b = min(args.batch, args.samples - c)
-            u0 = ks_initial_condition(b, X, args.L, args.lmax, gen)
-            sol, _ = ks_1d(u0.to(dev), args.viscosity, args.L, args.et, args.dt, nt - 1)
-            full = torch.cat([u0[:, None, :], sol.cpu()], dim=1)       # [b, nt, X]
-            u[c:c + b] = full[:, nt - nte:].numpy()
-            print(f"[ks_1d] {args.split} resolution {X}: {c + b}/{args.samples} samples", flush=True)
-        path = ks_path(args.out, args.split, X, args.viscosity, args.L, args.lmax, args.et, nte, nt, args.samples, args.flat)
-        os.makedirs(os.path.dirname(path), exist_ok=True)
-        s = args.split
-        np.savez(path, **{f"{s}/pde_{nte}-{X}": u, f"{s}/t": t,
-                          f"{s}/x": (np.arange(X, dtype=np.float64) * (args.L / X)).astype(np.float32),
-                          f"{s}/dx": np.float32(args.L / X), f"{s}/dt": np.float32(every * args.dt)})
-        if s == "train" and not args.flat:                             # the loader's own lookup finds what was written
+
+    def path_of(X):
+        return ks_path(args.out, args.split, X, args.viscosity, args.L, args.lmax, args.et, args.nte, args.nt, args.samples,
+                       args.flat)
+
+    def found_by_loader(X, path):
+        if args.split == "train" and not args.flat:                    # the loader's own lookup finds what was written
             from dataloaders.ks_naive_true_multires import _ks_path
-            found = _ks_path(args.out, X, args.viscosity, args.L, args.lmax, args.et, nte, nt, args.samples)
+            found = _ks_path(args.out, X, args.viscosity, args.L, args.lmax, args.et, args.nte, args.nt, args.samples)
             if found != path:
                 raise RuntimeError(f"ks_naive_true_multires reads {found} for resolution {X}, not {path} "
                                    "(an .h5 file of the same stem takes precedence over the .npz archive)")
-        print(f"[ks_1d] wrote {path}: {s}/pde_{nte}-{X} {u.shape}", flush=True)
-        written.append(path)
-    return written
+
+    return write_trajectories(
+        "ks_1d", args, ap, resolutions,
+        lambda b, X, gen: ks_initial_condition(b, X, args.L, args.lmax, gen),
+        lambda u0, X: ks_1d(u0, args.viscosity, args.L, args.et, args.dt, args.nt - 1)[0].cpu(),
+        path_of, found_by_loader)
 
 
 if __name__ == "__main__":

@@ -1225,6 +1225,22 @@ def _grid(t: torch.Tensor, what: str, d: int):
     return dims
 
 
+def _padded(t: torch.Tensor) -> torch.Tensor:
+    """a float64 table [..., K] of a half spectrum's K = N//2+1 columns -> float32 [..., kp], rounded once, padding zero"""
+    K = t.shape[-1]
+    p = torch.zeros(*t.shape[:-1], _kp(2 * (K - 1)), dtype=torch.float32)
+    p[..., :K] = t.to(torch.float32)
+    return p
+
+
+def _schedule(what: str, steps, record_every):
+    """(steps, record_every) as ints, refused unless steps >= 0 and record_every >= 1"""
+    steps, record_every = int(steps), int(record_every)
+    if steps < 0 or record_every < 1:
+        raise ValueError(f"{what}: bad steps={steps} record_every={record_every}")
+    return steps, record_every
+
+
 def _grf(what: str, d: int, noise: torch.Tensor, sqrt_eig: torch.Tensor) -> torch.Tensor:
     """noise [B, *grid, 2], sqrt_eig [*grid] of d dimensions -> [B, *grid] through rpde_grf1d / rpde_grf2d"""
     lib = load()
@@ -1249,7 +1265,7 @@ def ns2d_tables(M: int, N: int, visc: float, dt: float):
     1 for this division only."""
     import math
     M, N = int(M), int(N)
-    K, kp = N // 2 + 1, _kp(N)
+    K = N // 2 + 1
     k1 = (torch.fft.fftfreq(M, dtype=torch.float64) * M).round().view(M, 1)
     k2 = torch.arange(K, dtype=torch.float64).view(1, K)
     lap = 4.0 * math.pi ** 2 * (k1 ** 2 + k2 ** 2)
@@ -1257,12 +1273,8 @@ def ns2d_tables(M: int, N: int, visc: float, dt: float):
     dealias = ((k1.abs() <= (2.0 / 3.0) * (M // 2)) & (k2.abs() <= (2.0 / 3.0) * (N // 2))).to(torch.float64)
     poisson = lap.clone()
     poisson[0, 0] = 1.0
-    out = []
-    for t in ((1.0 - a) / (1.0 + a), float(dt) * dealias / (1.0 + a), float(dt) / (1.0 + a), 1.0 / poisson):
-        p = torch.zeros(M, kp, dtype=torch.float32)
-        p[:, :K] = t.to(torch.float32)
-        out.append(p)
-    return tuple(out)
+    return tuple(_padded(t) for t in ((1.0 - a) / (1.0 + a), float(dt) * dealias / (1.0 + a), float(dt) / (1.0 + a),
+                                      1.0 / poisson))
 
 
 def grf2d(noise: torch.Tensor, sqrt_eig: torch.Tensor) -> torch.Tensor:
@@ -1272,6 +1284,26 @@ def grf2d(noise: torch.Tensor, sqrt_eig: torch.Tensor) -> torch.Tensor:
     return _grf("grf2d", 2, noise, sqrt_eig)
 
 
+def _ns2d_forcing(what: str, f: torch.Tensor, c_g: torch.Tensor, B: int, M: int, N: int, ws: torch.Tensor, nws: int):
+    """(g_h, batched): g_h = dt / (1 + a) rfft2(f) for the forcing f [M, N] (one for the batch) or [B, M, N], once per
+    solve, and whether it holds a spectrum per sample"""
+    lib = load()
+    if tuple(f.shape) not in ((M, N), (B, M, N)):
+        raise ValueError(f"{what}: forcing {tuple(f.shape)}, expected {(M, N)} or {(B, M, N)}")
+    fb = 1 if f.dim() == 2 else B
+    st = stream_ptr()
+    # The forcing is transformed one image at a time, so that a sample's forcing spectrum does not depend on the batch
+    # around it: f [M, N] and the same f repeated B times give the same bits
+    per = lib.rpde_ns2d_spec_elems(1, M, N)
+    f_h = torch.empty(fb * per, dtype=torch.float32, device=c_g.device)
+    g_h = torch.empty_like(f_h)
+    f3 = f.view(fb, M, N)
+    for i in range(fb):
+        check(lib.rpde_ns2d_rfft2(ptr(f3[i]), ptr(f_h[i * per:(i + 1) * per]), 1, M, N, ws.data_ptr(), nws, st), "ns2d_rfft2")
+    check(lib.rpde_ns2d_scale(ptr(f_h), ptr(c_g), ptr(g_h), fb, M, N, st), "ns2d_scale")
+    return g_h, int(f.dim() == 3)
+
+
 def ns2d_solve(w0: torch.Tensor, f: torch.Tensor, visc: float, dt: float, steps: int, record_every: int) -> torch.Tensor:
     """2-D Navier-Stokes in vorticity form on the periodic unit square from w0 [B, M, N] with forcing f ([M, N] for the
     whole batch or [B, M, N]): `steps` pseudo-spectral steps of size dt (Crank-Nicolson diffusion, explicit advection and
@@ -1279,42 +1311,29 @@ def ns2d_solve(w0: torch.Tensor, f: torch.Tensor, visc: float, dt: float, steps:
     [B, M, N, steps // record_every].  Six launches per step, no host synchronisation between them.  Contiguous fp32
     tensors on the GPU; no autograd, no CPU fallback."""
     lib = load()
-    steps, record_every = int(steps), int(record_every)
-    if steps < 0 or record_every < 1:
-        raise ValueError(f"ns2d_solve: bad steps={steps} record_every={record_every}")
+    steps, record_every = _schedule("ns2d_solve", steps, record_every)
     w0, f = _f32c(w0.detach()), _f32c(f.detach())
     pw, _ = ptr(w0), ptr(f)                                # raises for CPU tensors: there is no fallback
     B, M, N = _grid(w0, "ns2d_solve", 2)
-    if tuple(f.shape) not in ((M, N), (B, M, N)):
-        raise ValueError(f"ns2d_solve: forcing {tuple(f.shape)}, expected {(M, N)} or {(B, M, N)}")
-    fb = 1 if f.dim() == 2 else B
     dev = w0.device
     c_w, c_f, c_g, inv_lap = (t.to(dev) for t in ns2d_tables(M, N, visc, dt))
     nws = lib.rpde_ns2d_ws_bytes(B, M, N)
     ws = workspace(nws, dev)
     st = stream_ptr()
+    g_h, batched = _ns2d_forcing("ns2d_solve", f, c_g, B, M, N, ws, nws)
     W = torch.empty(lib.rpde_ns2d_spec_elems(B, M, N), dtype=torch.float32, device=dev)
     check(lib.rpde_ns2d_rfft2(pw, ptr(W), B, M, N, ws.data_ptr(), nws, st), "ns2d_rfft2")
-    # g_h = dt / (1 + a) rfft2(f), once per solve.  The forcing is transformed one image at a time, so that a sample's
-    # forcing spectrum does not depend on the batch around it: f [M, N] and the same f repeated B times give the same bits
-    per = lib.rpde_ns2d_spec_elems(1, M, N)
-    f_h = torch.empty(fb * per, dtype=torch.float32, device=dev)
-    g_h = torch.empty_like(f_h)
-    f3 = f.view(fb, M, N)
-    for i in range(fb):
-        check(lib.rpde_ns2d_rfft2(ptr(f3[i]), ptr(f_h[i * per:(i + 1) * per]), 1, M, N, ws.data_ptr(), nws, st), "ns2d_rfft2")
-    check(lib.rpde_ns2d_scale(ptr(f_h), ptr(c_g), ptr(g_h), fb, M, N, st), "ns2d_scale")
     n_rec = steps // record_every
     snaps = torch.empty(max(n_rec, 1), B, M, N, dtype=torch.float32, device=dev)
     for c in range(n_rec):
-        check(lib.rpde_ns2d_steps(ptr(W), ptr(g_h), int(f.dim() == 3), ptr(c_w), ptr(c_f), ptr(inv_lap), B, M, N,
+        check(lib.rpde_ns2d_steps(ptr(W), ptr(g_h), batched, ptr(c_w), ptr(c_f), ptr(inv_lap), B, M, N,
                                   record_every, ws.data_ptr(), nws, st), "ns2d_steps")
         check(lib.rpde_ns2d_irfft2(ptr(W), ptr(snaps[c]), B, M, N, ws.data_ptr(), nws, st), "ns2d_irfft2")
     return snaps[:n_rec].permute(1, 2, 3, 0).contiguous()
 
 
 # ----------------------------------------------------------------------------
-# Active-scalar Navier-Stokes generator (csrc/ns_scalar.hip, rpde_nsc2d_*; data_generation/active_scalar_2d.py is the
+# Active-scalar Navier-Stokes generator (csrc/ns_solver.hip, rpde_nsc2d_*; data_generation/active_scalar_2d.py is the
 # caller).  Data production: no autograd, GPU tensors only, no CPU fallback.
 # ----------------------------------------------------------------------------
 def nsc2d_tables(M: int, N: int, visc: float, kappa: float, dt: float):
@@ -1364,31 +1383,19 @@ def nsc2d_solve(w0: torch.Tensor, c0: torch.Tensor, f: torch.Tensor, visc: float
     formulas), a snapshot after every `record_every`-th.  Returns (fields [B, steps // record_every, 3, M, N] = (c, q, v)
     with u = (q, v), vorticity [B, steps // record_every, M, N]).  Six launches per step, one device call per snapshot's
     steps, no host synchronisation.  Contiguous fp32 tensors on the GPU; no autograd, no CPU fallback."""
-    steps, record_every = int(steps), int(record_every)
-    if steps < 0 or record_every < 1:
-        raise ValueError(f"nsc2d_solve: bad steps={steps} record_every={record_every}")
+    steps, record_every = _schedule("nsc2d_solve", steps, record_every)
     f = _f32c(f.detach())
     ptr(f)
     lib, B, M, N, ws, nws, S = _nsc2d_state("nsc2d_solve", w0, c0)
-    if tuple(f.shape) not in ((M, N), (B, M, N)):
-        raise ValueError(f"nsc2d_solve: forcing {tuple(f.shape)}, expected {(M, N)} or {(B, M, N)}")
-    fb = 1 if f.dim() == 2 else B
     dev = S.device
     c_w, c_f, d_w, d_f, c_g, inv_lap = (t.to(dev) for t in nsc2d_tables(M, N, visc, kappa, dt))
     st = stream_ptr()
-    # g_h as in ns2d_solve: one image at a time, so that a sample's forcing spectrum does not depend on the batch
-    per = lib.rpde_ns2d_spec_elems(1, M, N)
-    f_h = torch.empty(fb * per, dtype=torch.float32, device=dev)
-    g_h = torch.empty_like(f_h)
-    f3 = f.view(fb, M, N)
-    for i in range(fb):
-        check(lib.rpde_ns2d_rfft2(ptr(f3[i]), ptr(f_h[i * per:(i + 1) * per]), 1, M, N, ws.data_ptr(), nws, st), "ns2d_rfft2")
-    check(lib.rpde_ns2d_scale(ptr(f_h), ptr(c_g), ptr(g_h), fb, M, N, st), "ns2d_scale")
+    g_h, batched = _ns2d_forcing("nsc2d_solve", f, c_g, B, M, N, ws, nws)
     n_rec = steps // record_every
     fields = torch.empty(max(n_rec, 1), B, 3, M, N, dtype=torch.float32, device=dev)
     vort = torch.empty(max(n_rec, 1), B, M, N, dtype=torch.float32, device=dev)
     for c in range(n_rec):
-        check(lib.rpde_nsc2d_steps(ptr(S), ptr(g_h), int(f.dim() == 3), ptr(c_w), ptr(c_f), ptr(d_w), ptr(d_f),
+        check(lib.rpde_nsc2d_steps(ptr(S), ptr(g_h), batched, ptr(c_w), ptr(c_f), ptr(d_w), ptr(d_f),
                                    ptr(inv_lap), float(beta), B, M, N, record_every, ws.data_ptr(), nws, st), "nsc2d_steps")
         check(lib.rpde_nsc2d_fields(ptr(S), ptr(inv_lap), ptr(fields[c]), B, M, N, ws.data_ptr(), nws, st), "nsc2d_fields")
         check(lib.rpde_ns2d_irfft2(ptr(S), ptr(vort[c]), B, M, N, ws.data_ptr(), nws, st), "ns2d_irfft2")
@@ -1400,6 +1407,43 @@ def nsc2d_solve(w0: torch.Tensor, c0: torch.Tensor, f: torch.Tensor, visc: float
 # rpde_grf1d; data_generation/burgers_1d.py, ks_1d.py and random_fields.py are the callers).  Data production: no
 # autograd, GPU tensors only, no CPU fallback.
 # ----------------------------------------------------------------------------
+def _etd1d_tables(what: str, N, length, dt, symbol, advect, dealias, full_circle: bool):
+    """The tables under etd1d_tables (full_circle False) and etd1d_tables_cx (True): six float64 / complex128
+    coefficients [K] of z = dt symbol(kappa) and the float32 [kp] table g.  Kassam-Trefethen: LR = z + r_m over the
+    contour points r_m.  For real z the 32 points of the upper half circle, exp(i pi (m - 1/2) / 32), with Re<.> of the
+    mean; for complex z that is wrong, and it is the full circle's 64 points, exp(2 pi i (m - 1/2) / 64), with the complex
+    mean."""
+    import math
+    N = int(N)
+    if N < 4 or N % 2:
+        raise ValueError(f"{what}: N must be even and >= 4, got {N}")
+    if not (float(length) > 0 and float(dt) > 0):
+        raise ValueError(f"{what}: length and dt must be positive, got length={length} dt={dt}")
+    K = N // 2 + 1
+    n = torch.arange(K, dtype=torch.float64)
+    kappa = (2.0 * math.pi / float(length)) * n
+    h = float(dt)
+    z = h * symbol(kappa)
+    points = 64 if full_circle else 32
+    m = torch.arange(1, points + 1, dtype=torch.float64)
+    r = torch.polar(torch.ones(points, dtype=torch.float64), (2.0 if full_circle else 1.0) * math.pi * (m - 0.5) / points)
+    LR = z.view(K, 1).to(torch.complex128) + r.view(1, points)
+    eLR = torch.exp(LR)
+
+    def mean(t):
+        return t.mean(dim=1) if full_circle else t.mean(dim=1).real
+
+    keep = (n <= (2.0 / 3.0) * (N // 2)).to(torch.float64) if dealias else torch.ones(K, dtype=torch.float64)
+    g = -(float(advect) / 2.0) * kappa * keep
+    g[N // 2] = 0.0
+    coefficients = (torch.exp(z), torch.exp(z / 2.0),
+                    h * mean((torch.exp(LR / 2.0) - 1.0) / LR),
+                    h * mean((-4.0 - LR + eLR * (4.0 - 3.0 * LR + LR ** 2)) / LR ** 3),
+                    h * mean((2.0 + LR + eLR * (-2.0 + LR)) / LR ** 3),
+                    h * mean((-4.0 - 3.0 * LR - LR ** 2 + eLR * (4.0 - LR)) / LR ** 3))
+    return z, coefficients, _padded(g)
+
+
 def etd1d_tables(N: int, length: float, c2: float, c4: float, dt: float, advect: float = 1.0, dealias: bool = True):
     """(E, E2, Q, f1, f2, f3, g): the ETDRK4 tables of u_t = L u - (advect/2) (u^2)_x with the symbol
     l_n = c2 kappa_n^2 + c4 kappa_n^4, kappa_n = 2 pi n / length, as float32 [kp] host tensors (kp = N//2+1 rounded up to
@@ -1407,39 +1451,9 @@ def etd1d_tables(N: int, length: float, c2: float, c4: float, dt: float, advect:
     points r_m = exp(i pi (m - 1/2) / 32) -- the f coefficients cancel catastrophically in fp32 for small z, the contour
     mean in float64 does not.  g_n = -(advect/2) kappa_n dealias_n, dealias_n = [n <= (2/3)(N/2)] (or 1), g_{N/2} = 0.
     include/rpde.h has the formulas."""
-    import math
-    N = int(N)
-    if N < 4 or N % 2:
-        raise ValueError(f"etd1d_tables: N must be even and >= 4, got {N}")
-    if not (float(length) > 0 and float(dt) > 0):
-        raise ValueError(f"etd1d_tables: length and dt must be positive, got length={length} dt={dt}")
-    K, kp = N // 2 + 1, _kp(N)
-    n = torch.arange(K, dtype=torch.float64)
-    kappa = (2.0 * math.pi / float(length)) * n
-    h = float(dt)
-    z = h * (float(c2) * kappa ** 2 + float(c4) * kappa ** 4)
-    m = torch.arange(1, 33, dtype=torch.float64)
-    r = torch.polar(torch.ones(32, dtype=torch.float64), math.pi * (m - 0.5) / 32.0)
-    LR = z.view(K, 1).to(torch.complex128) + r.view(1, 32)
-    eLR = torch.exp(LR)
-
-    def mean(t):
-        return t.mean(dim=1).real
-
-    keep = (n <= (2.0 / 3.0) * (N // 2)).to(torch.float64) if dealias else torch.ones(K, dtype=torch.float64)
-    g = -(float(advect) / 2.0) * kappa * keep
-    g[N // 2] = 0.0
-    out = []
-    for t in (torch.exp(z), torch.exp(z / 2.0),
-              h * mean((torch.exp(LR / 2.0) - 1.0) / LR),
-              h * mean((-4.0 - LR + eLR * (4.0 - 3.0 * LR + LR ** 2)) / LR ** 3),
-              h * mean((2.0 + LR + eLR * (-2.0 + LR)) / LR ** 3),
-              h * mean((-4.0 - 3.0 * LR - LR ** 2 + eLR * (4.0 - LR)) / LR ** 3),
-              g):
-        p = torch.zeros(kp, dtype=torch.float32)
-        p[:K] = t.to(torch.float32)
-        out.append(p)
-    return tuple(out)
+    _, coefficients, g = _etd1d_tables("etd1d_tables", N, length, dt,
+                                       lambda kappa: float(c2) * kappa ** 2 + float(c4) * kappa ** 4, advect, dealias, False)
+    return tuple(_padded(t) for t in coefficients) + (g,)
 
 
 def etd1d_tables_cx(N: int, length: float, c1: float, c2: float, c3: float, c4: float, dt: float, advect: float = 1.0,
@@ -1453,46 +1467,16 @@ def etd1d_tables_cx(N: int, length: float, c1: float, c2: float, c3: float, c4: 
     complex, so the contour is the full circle, LR = z + r_m, r_m = exp(2 pi i (m - 1/2) / 64), m = 1 .. 64, and the mean is
     the complex mean (the upper half circle with Re<.> of etd1d_tables is that mean for real z only); where z is real the
     mean is real and its imaginary part is stored as zero.  include/rpde.h has the formulas."""
-    import math
-    N = int(N)
-    if N < 4 or N % 2:
-        raise ValueError(f"etd1d_tables_cx: N must be even and >= 4, got {N}")
-    if not (float(length) > 0 and float(dt) > 0):
-        raise ValueError(f"etd1d_tables_cx: length and dt must be positive, got length={length} dt={dt}")
-    K, kp = N // 2 + 1, _kp(N)
-    n = torch.arange(K, dtype=torch.float64)
-    kappa = (2.0 * math.pi / float(length)) * n
-    h = float(dt)
-    odd = float(c1) * kappa + float(c3) * kappa ** 3
-    odd[N // 2] = 0.0
-    z = h * torch.complex(float(c2) * kappa ** 2 + float(c4) * kappa ** 4, odd)
-    m = torch.arange(1, 65, dtype=torch.float64)
-    r = torch.polar(torch.ones(64, dtype=torch.float64), 2.0 * math.pi * (m - 0.5) / 64.0)
-    LR = z.view(K, 1) + r.view(1, 64)
-    eLR = torch.exp(LR)
+    def symbol(kappa):
+        odd = float(c1) * kappa + float(c3) * kappa ** 3
+        odd[-1] = 0.0
+        return torch.complex(float(c2) * kappa ** 2 + float(c4) * kappa ** 4, odd)
 
-    def mean(t):
-        return t.mean(dim=1)
-
-    keep = (n <= (2.0 / 3.0) * (N // 2)).to(torch.float64) if dealias else torch.ones(K, dtype=torch.float64)
-    g = -(float(advect) / 2.0) * kappa * keep
-    g[N // 2] = 0.0
-    out = []
-    for t in (torch.exp(z), torch.exp(z / 2.0),
-              h * mean((torch.exp(LR / 2.0) - 1.0) / LR),
-              h * mean((-4.0 - LR + eLR * (4.0 - 3.0 * LR + LR ** 2)) / LR ** 3),
-              h * mean((2.0 + LR + eLR * (-2.0 + LR)) / LR ** 3),
-              h * mean((-4.0 - 3.0 * LR - LR ** 2 + eLR * (4.0 - LR)) / LR ** 3)):
-        p = torch.zeros(2, kp, dtype=torch.float32)
-        p[0, :K] = t.real.to(torch.float32)
-        # real z (the mean and Nyquist modes, an even symbol): the circle's points pair up as conjugates and the mean is
-        # real; what its imaginary part holds then is the sum's rounding (1e-20), dropped
-        p[1, :K] = torch.where(z.imag == 0, torch.zeros(K, dtype=torch.float64), t.imag).to(torch.float32)
-        out.append(p)
-    p = torch.zeros(kp, dtype=torch.float32)
-    p[:K] = g.to(torch.float32)
-    out.append(p)
-    return tuple(out)
+    z, coefficients, g = _etd1d_tables("etd1d_tables_cx", N, length, dt, symbol, advect, dealias, True)
+    # real z (the mean and Nyquist modes, an even symbol): the circle's points pair up as conjugates and the mean is
+    # real; what its imaginary part holds then is the sum's rounding (1e-20), dropped
+    return tuple(_padded(torch.stack([t.real, torch.where(z.imag == 0, torch.zeros_like(t.imag), t.imag)]))
+                 for t in coefficients) + (g,)
 
 
 def grf1d(noise: torch.Tensor, sqrt_eig: torch.Tensor) -> torch.Tensor:
@@ -1510,9 +1494,7 @@ def etd1d_solve(u0: torch.Tensor, tables, steps: int, record_every: int) -> torc
     the recording loop calls the device `steps // record_every` times, which gives the bits of one long call.
     Contiguous fp32 tensors on the GPU; no autograd, no CPU fallback."""
     lib = load()
-    steps, record_every = int(steps), int(record_every)
-    if steps < 0 or record_every < 1:
-        raise ValueError(f"etd1d_solve: bad steps={steps} record_every={record_every}")
+    steps, record_every = _schedule("etd1d_solve", steps, record_every)
     u0 = _f32c(u0.detach())
     B, N = _grid(u0, "etd1d_solve", 1)
     kp = _kp(N)

@@ -33,6 +33,9 @@ import torch
 # (B, N): kp padding of 3 columns each, a non-power-of-two grid, odd B; N = 512 is the first grid with more than 64
 # 16-byte groups per image, where the stage kernels launch 256 threads instead of 64
 CASES = [(3, 16), (2, 48), (2, 64), (1, 128), (2, 200), (2, 256), (1, 512)]
+# every N of CASES has K = N/2+1 = 1 (mod 4), three padded columns in the last 16-byte group; these have K = 4, 6, 7: none,
+# two and one
+EDGE_CASES = [(2, 6), (2, 10), (2, 12)]
 STEPS, SNAPSHOTS = 80, 4
 KS_NU, KS_DT = 0.05, 0.01
 BURGERS_NU, BURGERS_DT, BURGERS_L = 0.1, 5e-3, 2.0

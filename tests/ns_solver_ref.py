@@ -23,6 +23,8 @@ import torch
 
 # (B, M, N)
 CASES = [(3, 8, 8), (2, 16, 24), (2, 32, 48), (1, 48, 32), (2, 64, 64)]
+# the edges of the group layout, K = N/2+1 = 4, 5, 6, 7, 4: 0 .. 3 padded columns in the last 16-byte group, M above N
+EDGE_CASES = [(2, 4, 6), (2, 4, 8), (2, 6, 10), (2, 4, 12), (2, 12, 6)]
 VISC, DT, STEPS, RECORD_STEPS = 1e-3, 2e-3, 100, 4
 T_FINAL = 0.2                      # STEPS * DT: ceil(0.2 / 2e-3) = 100
 W0_SCALE, W0_ALPHA, W0_TAU = 8.0, 2.5, 7.0

@@ -21,8 +21,8 @@ import torch
 
 from tests import ns_solver_ref as R
 
-# (B, M, N): the NS generator's cases, then the edges of the group layout, K = N/2+1 = 4, 5, 6, 7, 4
-CASES = list(R.CASES) + [(2, 4, 6), (2, 4, 8), (2, 6, 10), (2, 4, 12), (2, 12, 6)]
+# (B, M, N): the NS generator's cases, then its edges of the group layout, K = N/2+1 = 4, 5, 6, 7, 4
+CASES = list(R.CASES) + list(R.EDGE_CASES)
 VISC, KAPPA, BETA = 1e-3, 2e-3, 5.0          # visc != kappa on purpose: swapped tables show
 DT, T_FINAL, RECORD_STEPS = 2e-3, 0.2, 4
 FLOOR_FACTOR = R.FLOOR_FACTOR

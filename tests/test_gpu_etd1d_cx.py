@@ -36,6 +36,10 @@ from tests import etd1d_ref as R
 pytestmark = pytest.mark.gpu
 
 FAMILY_IDS = list(C.FAMILIES)
+# every family on CASES; advburg also where K = N/2+1 is not 1 (mod 4) (kdv fails its own input conditions at these sizes:
+# the nonlinear share is 0.08 at N = 12, the imaginary share is undefined at N = 6 and 12)
+FAMILY_CASES = [pytest.param(f, c, id=f"{f}-{C.case_id(c)}") for f in FAMILY_IDS for c in C.CASES] + \
+               [pytest.param("advburg", c, id=f"advburg-{C.case_id(c)}") for c in R.EDGE_CASES]
 
 
 def _dev(t, gpu_device):
@@ -53,8 +57,7 @@ def _solve(family, ref, u0, steps=C.STEPS, snapshots=C.SNAPSHOTS):
 
 
 # ---- 1. solver parity ------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", C.CASES, ids=C.case_id)
-@pytest.mark.parametrize("family", FAMILY_IDS)
+@pytest.mark.parametrize("family,case", FAMILY_CASES)
 def test_solver_matches_float64(gpu_device, family, case):
     ref = C.parity_reference(family, case)
     # conditions on the inputs: the nonlinear term and the imaginary part of the symbol both shape the answer
@@ -111,8 +114,7 @@ def test_linear_modes_advect_and_decay_in_closed_form(gpu_device):
 
 
 # ---- 4. bookkeeping --------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", C.CASES, ids=C.case_id)
-@pytest.mark.parametrize("family", FAMILY_IDS)
+@pytest.mark.parametrize("family,case", FAMILY_CASES)
 def test_mean_is_conserved(gpu_device, family, case):
     """g_0 = 0, E_0 = 1 and Im of every table is 0 at the mean mode: it is carried through every stage unchanged, so
     mean(u_T) - mean(u_0) is what the two transforms round.  The bound is that of the real path's test, 64 eps times

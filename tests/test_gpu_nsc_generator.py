@@ -1,4 +1,4 @@
-"""The on-device active-scalar Navier-Stokes generator (csrc/ns_scalar.hip, rpde.ops.nsc2d_solve / nsc2d_fields,
+"""The on-device active-scalar Navier-Stokes generator (csrc/ns_solver.hip, rpde.ops.nsc2d_solve / nsc2d_fields,
 data_generation/active_scalar_2d.py) against the float64 restatement tests/nsc_solver_ref.py, and the active-matter data
 path from the generator's files to a training run.
 
