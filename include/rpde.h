@@ -548,6 +548,48 @@ size_t rpde_grf1d_ws_bytes(int B, int N);
 int rpde_grf1d(const float* noise, const float* sqrt_eig, float* out, int B, int N, void* ws, size_t ws_bytes,
                void* stream);
 
+/* ---- equation-residual loss of the 1-D ETD family, forward and backward (csrc/etd_residual.hip, rpde.ops.etd1d_residual;
+ * utils/loss.py EquationResidualLoss; an interface addition, the reference has none).  It asks a one-step map x = u(t) ->
+ * p ~ u(t + D) to satisfy u_t = L u - (c/2) (u^2)_x itself.  p, x [B, N] fp32, grid, length, kappa_n, the symbol l_n
+ * (complex in general, Im l_{N/2} = 0) and g_n as in the generator block above; D is the time between the two fields (the
+ * snapshot interval of a data set, not a solver's step).  The exact solution obeys
+ *   u^(t + D) = e^(D l) u^(t) + int_0^D e^((D - s) l) Nhat(u(t + s)) ds,   Nhat(w) = i g rfft(w^2);
+ * interpolating Nhat linearly between the two ends (the exponential trapezoidal rule, ETD2: exact in the linear part
+ * however stiff) leaves the residual, with z = D l_n,
+ *   r^_n = p^_n - E_n x^_n - m0_n rfft(x^2)_n - m1_n rfft(p^2)_n,
+ *   E = e^z,   m0 = D (phi1(z) - phi2(z)) i g,   m1 = D phi2(z) i g,
+ *   phi1 = <(e^LR - 1) / LR>,  phi2 = <(e^LR - 1 - LR) / LR^2>,  LR = z + r_m,  r_m = exp(2 pi i (m - 1/2) / 64), m = 1 .. 64,
+ * <.> the complex mean.  The caller forms the three tables in float64 / complex128 and rounds them to fp32 once
+ * (rpde.ops.etd1d_residual_tables); they are always complex, each [re|im][kp] floats -- the plane layout of a spectrum,
+ * padded columns zero, Im E = 0 where z is real, m0 = m1 = 0 at n = 0 and N/2 -- with g (de-aliasing and c) folded in.
+ *   rel[b] = sqrt(E_r[b]) / (sqrt(E_x[b]) + 1e-8),   E(z)[b] = sum_n c_n |z^_n|^2 / N,  c_n = 1 at n = 0, N/2, else 2.
+ * The rule is second order: the residual of an exact pair falls as D^3 and is meaningful while |D N_tt| is small -- on
+ * KS (N = 64, len 16, nu 0.05) rel(exact pair) is 3.5e-4 .. 9.7e-4 at D = 0.05 and 4.8e-3 .. 1.2e-2 at D = 0.1 against
+ * 0.15 .. 0.24 and 0.36 .. 0.56 for p = x, and by D ~ 0.4 it is ~ 1 for both (DESIGN.md has the table).
+ * affine: four host floats (a_p, b_p, a_x, b_x), NULL = (1, 0, 1, 0).  The residual is formed on a_p p + b_p and
+ * a_x x + b_x (a model trained on encoded fields, penalised in physical units) and grad_p is with respect to the raw p.
+ * rel [B] or NULL; loss: device scalar = mean (size_average) or sum, NULL for reduction=False; stats: 2 B floats
+ * (sqrt E_r, sqrt E_x per sample) and spec_r (the spec_elems query's count of floats: r^, B images) are kept for backward.
+ * Forward: one pass decodes, squares, forms the four spectra of [x~ | p~ | x~^2 | p~^2] as float64 sums over the N
+ * points and from them r^ (rounded once) and the energies: for a good model r^ is a small remainder of terms of the
+ * size of the field, and an fp32 transform's error in x^ would be of that remainder's size
+ * (float64, two deterministic stages without atomics: identical calls give identical bits, and a sample's value does not
+ * depend on the batch around it).  Backward: one inverse transform of the 2 B spectra [r^ | conj(m1) r^], then
+ *   grad_p[b] = a_p coef_b (irfft(r^) - 2 p~ irfft(conj(m1) r^)),  coef_b = g_b / (sqrt(E_r) (sqrt(E_x) + 1e-8)), 0 where
+ * E_r = 0; g_b = grad_rel[b], or grad_loss[0] (/ B when size_average) with grad_rel NULL.  No gradient for x: the
+ * denominator is a constant of the sample.  N even, 4 .. 4096, 1 <= B <= 16383 (four fields of B images as one batch
+ * of the half-spectrum layer): the two queries return 0 otherwise.  Tables and spec_r 16-byte aligned, the workspace (the ws query
+ * serves both calls) 256-byte aligned.  On the caller's stream, no host synchronisation (the first use of a grid builds
+ * its plan: it allocates and synchronises once).  Argument errors are reported before any device work. */
+size_t rpde_etd_residual_ws_bytes(int B, int N);
+size_t rpde_etd_residual_spec_elems(int B, int N);
+int rpde_etd_residual_fwd(const float* p, const float* x, const float* E, const float* m0, const float* m1,
+                          const float* affine, float* rel, float* loss, float* stats, float* spec_r, int B, int N,
+                          int size_average, void* ws, size_t ws_bytes, void* stream);
+int rpde_etd_residual_bwd(const float* p, const float* spec_r, const float* m1, const float* affine, const float* stats,
+                          const float* grad_loss, const float* grad_rel, float* grad_p, int B, int N, int size_average,
+                          void* ws, size_t ws_bytes, void* stream);
+
 /* ---- Darcy flow generator (csrc/darcy.hip; reference: dataloaders/darcy_loader.py and the piececonst_* files of
  * load_darcy_data_from_mat): -div(a grad u) = f on the unit square, u = 0 on the boundary, s x s cells with centres
  * x_i = (i + 1/2) / s, a and u [B, s, s] at the centres.  Finite volumes: an interior face between cells c and n weighs

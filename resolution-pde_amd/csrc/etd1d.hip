@@ -22,6 +22,7 @@
 // dispersion: Korteweg-de Vries, data_generation/kdv_1d.py): E, E2, Q, f1, f2, f3 are complex [re|im][kp], g stays real,
 // and the stage kernels are k_etd_stage_cx<S>.  The same workspace, launches and transforms; k_etd_stage<S> and the
 // real call are as they were.
+#include "etd_cx.h"
 #include "halfspec.h"
 
 namespace rpde {
@@ -110,19 +111,7 @@ __global__ __launch_bounds__(256) void k_etd_stage(EtdBufs u, const float* __res
 // one -- the real plane's multiply or fma, then two more fmas with the imaginary plane -- in the same order of terms.
 // Same geometry, same streaming: the imaginary planes are further whole float4 loads, all of them unconditional.  The
 // masked values are formed before the selects: a select whose arm holds the only use of a load becomes a branch with
-// that element's load inside it, which splits the float4 and waits per element.
-
-// p = c x
-__device__ __forceinline__ void etd_cmul(float cr, float ci, float xr, float xi, float& pr, float& pi) {
-  pr = fmaf(-ci, xi, cr * xr);
-  pi = fmaf(ci, xr, cr * xi);
-}
-// p += c x
-__device__ __forceinline__ void etd_cfma(float cr, float ci, float xr, float xi, float& pr, float& pi) {
-  pr = fmaf(-ci, xi, fmaf(cr, xr, pr));
-  pi = fmaf(ci, xr, fmaf(cr, xi, pi));
-}
-
+// that element's load inside it, which splits the float4 and waits per element.  etd_cmul / etd_cfma: etd_cx.h.
 template <int S>
 __global__ __launch_bounds__(256) void k_etd_stage_cx(EtdBufs u, const float* __restrict__ F, EtdTables t, HalfSpec g) {
   const long per = 2L * g.kp, base = (long)blockIdx.y * per;

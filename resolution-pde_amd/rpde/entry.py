@@ -64,14 +64,18 @@ def _sweep_fields(args, test_set, x_normalizer, y_normalizer, min_model, max_mod
     return tx, ty_phys, dec, how, top_res
 
 
-def training_loss(training, dims: int):
+def training_loss(training, dims: int, dataset=None):
     """(name, loss_fn or None) of the optional training objective, from the overrides under `training` (a mapping; no
-    device work here).  Absent or "l2": (l2, None), train() then takes RelativeL2Loss.
+    device work here); `dataset`: the data set's config, read by training.loss=residual alone.  Absent or "l2": (l2, None), train() then takes RelativeL2Loss.
       training.loss=sobolev   the H^s relative loss (utils.loss.SpectralRelativeL2Loss) with training.loss_s (default
                               1.0) and training.loss_length (a float or one per axis, default 1.0)
       training.loss=band      the relative error band by band (BandRelativeL2Loss) with training.loss_band_floor (1e-3)
       training.loss=spectrum  relative L2 + training.loss_lambda (0.1) x the mismatch of the energy per band
                               (SpectrumMatchingLoss) with training.loss_spectrum_floor (1e-6)
+      training.loss=residual  relative L2 + training.loss_lambda (0.1) x the equation residual of the one-step map
+                              (EquationResidualLoss, 1-D only), built from the data set's `equation:` mapping
+                              {c1, c2, c3, c4, advect, length, interval} (length and interval required, the rest
+                              default to 0 and advect to 1); run() sets its decode maps (residual_affine below)
     band and spectrum take training.loss_bands (octave; radial in 2-D, modes in 1-D) and training.loss_num_bands, and
     the 1-D rollout record then also carries the octave band energies along the rollout.  Anything else: SystemExit.
     Validation, the test score and the sweeps stay relative L2."""
@@ -83,8 +87,26 @@ def training_loss(training, dims: int):
         length = training.get("loss_length", 1.0)
         length = [float(v) for v in length] if isinstance(length, (list, tuple)) else float(length)
         return name, SpectralRelativeL2Loss(dims, "sobolev", s=float(training.get("loss_s", 1.0)), length=length)
+    if name == "residual":
+        from utils.loss import EquationResidualLoss, RelativeL2Loss, SumLoss
+        if dims != 1:
+            raise SystemExit(f"training.loss=residual: the equation residual is one-dimensional, got dims={dims}")
+        eq = None if dataset is None else dataset.get("equation")
+        if not eq:
+            raise SystemExit("training.loss=residual: the dataset config has no `equation:` mapping "
+                             "({c1, c2, c3, c4, advect, length, interval})")
+        eq = dict(eq)
+        unknown = sorted(set(eq) - {"c1", "c2", "c3", "c4", "advect", "length", "interval"})
+        if unknown or "length" not in eq or "interval" not in eq:
+            raise SystemExit(f"training.loss=residual: equation needs length and interval and takes c1, c2, c3, c4, advect; "
+                             f"got {sorted(eq)}")
+        try:
+            res = EquationResidualLoss(**{k: float(v) for k, v in eq.items()})
+        except ValueError as e:
+            raise SystemExit(f"training.loss=residual: {e}")
+        return name, SumLoss([(1.0, RelativeL2Loss()), (float(training.get("loss_lambda", 0.1)), res)])
     if name not in ("band", "spectrum"):
-        raise SystemExit(f"training.loss={name}: expected l2, sobolev, band or spectrum")
+        raise SystemExit(f"training.loss={name}: expected l2, sobolev, band, spectrum or residual")
     from utils.loss import BandRelativeL2Loss, RelativeL2Loss, SpectrumMatchingLoss, SumLoss
     bands = str(training.get("loss_bands", "octave"))
     nb = training.get("loss_num_bands", None)
@@ -96,6 +118,30 @@ def training_loss(training, dims: int):
         return name, SumLoss([(1.0, RelativeL2Loss()), (float(training.get("loss_lambda", 0.1)), match)])
     except ValueError as e:
         raise SystemExit(f"training.loss={name}: {e}")
+
+
+def residual_affine(loss_fn, x_normalizer, y_normalizer, use_normalizer: bool, minmax: bool = False) -> None:
+    """The decode maps of a training.loss=residual objective from the data set's normalisers, so that the equation is
+    asked in physical units: the input is decoded with the x-statistics; the prediction with the y-statistics, unless
+    training.use_normalizer is true -- train() has decoded it by then and its map is the identity.  Only one global
+    affine map (SimpleNormalizer) folds into the loss: point-wise or min-max normalisers are a SystemExit."""
+    from utils.loss import EquationResidualLoss
+    from utils.normalizers import scalar_stats
+    terms = [t for t in getattr(loss_fn, "terms", [loss_fn]) if isinstance(t, EquationResidualLoss)]
+    if not terms:
+        return
+    if minmax:
+        raise SystemExit("training.loss=residual: min-max normalised data is not supported (normalization_type: simple, "
+                         "one global mean and std, is)")
+    maps = []
+    for norm in (x_normalizer, y_normalizer):
+        st = (0.0, 1.0) if norm is None else scalar_stats(norm)
+        if st is None:
+            raise SystemExit("training.loss=residual: a point-wise normaliser does not fold into the loss "
+                             "(normalization_type: simple, one global mean and std, does)")
+        maps.append((st[1], st[0]))                              # decode: field * (std + eps) + mean
+    for t in terms:
+        t.set_affine(pred=(1.0, 0.0) if use_normalizer and y_normalizer is not None else maps[1], inp=maps[0])
 
 
 def run(dims: int, argv=None):
@@ -177,8 +223,9 @@ def run(dims: int, argv=None):
         scheduler = optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=100, eta_min=1e-5)
 
     # optional training objective (no yaml carries it): training_loss() below
-    loss_name, loss_fn = training_loss(args.training, dims)
+    loss_name, loss_fn = training_loss(args.training, dims, args.dataset)
     if loss_fn is not None:
+        residual_affine(loss_fn, x_normalizer, y_normalizer, bool(args.training.use_normalizer), normalization_type == "minmax")
         for r in train_loader.resolution_groups:
             loss_fn.warm((int(r),) * dims, device)
 

@@ -42,7 +42,8 @@ class GraphedTrainStep:
 
     x / y of later calls must have the example's shape and dtype (one graph per shape; build one instance per
     resolution for multi-resolution training).  `after_backward` (e.g. FlatGradBucket.all_reduce_mean) runs
-    inside the captured region between backward and the optimizer step.
+    inside the captured region between backward and the optimizer step.  loss_takes_input: the objective is
+    loss_fn(prediction, target, input) (utils.loss.EquationResidualLoss and a SumLoss that holds one).
 
     warmup = 0: the caller has already run eager steps of this very shape (plans, allocator pools and optimizer state
     exist) -- the construction then applies NO optimizer step of its own, which is what a training loop needs
@@ -57,7 +58,7 @@ class GraphedTrainStep:
     whoever moved them.  Other optimizers bake the values into the graph, and the replay is refused once they change."""
 
     def __init__(self, model, loss_fn, optimizer, x: torch.Tensor, y: torch.Tensor, warmup: int = 3,
-                 after_backward: Optional[Callable[[], None]] = None):
+                 after_backward: Optional[Callable[[], None]] = None, loss_takes_input: bool = False):
         if not x.is_cuda:
             raise ValueError("GraphedTrainStep needs HIP tensors")
         if _has_torch_dropout(model):
@@ -68,6 +69,7 @@ class GraphedTrainStep:
                 raise ValueError("GraphedTrainStep: build the optimizer with capturable=True")
         self.model, self.loss_fn, self.optimizer = model, loss_fn, optimizer
         self.after_backward = after_backward
+        self.loss_takes_input = bool(loss_takes_input)
         self.x, self.y = x.clone(), y.clone()
         side = torch.cuda.Stream(device=x.device)
         side.wait_stream(torch.cuda.current_stream(x.device))
@@ -95,7 +97,10 @@ class GraphedTrainStep:
         from . import ops
         ops.drop_epoch(self.x.device).add_(1)        # new dropout masks at every replay (device-side counter)
         self.optimizer.zero_grad(set_to_none=False)
-        loss = self.loss_fn(self.model(self.x), self.y)
+        if self.loss_takes_input:
+            loss = self.loss_fn(self.model(self.x), self.y, self.x)
+        else:
+            loss = self.loss_fn(self.model(self.x), self.y)
         loss.backward()
         if self.after_backward is not None:
             self.after_backward()

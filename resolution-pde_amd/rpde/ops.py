@@ -1407,12 +1407,11 @@ def nsc2d_solve(w0: torch.Tensor, c0: torch.Tensor, f: torch.Tensor, visc: float
 # rpde_grf1d; data_generation/burgers_1d.py, ks_1d.py and random_fields.py are the callers).  Data production: no
 # autograd, GPU tensors only, no CPU fallback.
 # ----------------------------------------------------------------------------
-def _etd1d_tables(what: str, N, length, dt, symbol, advect, dealias, full_circle: bool):
-    """The tables under etd1d_tables (full_circle False) and etd1d_tables_cx (True): six float64 / complex128
-    coefficients [K] of z = dt symbol(kappa) and the float32 [kp] table g.  Kassam-Trefethen: LR = z + r_m over the
-    contour points r_m.  For real z the 32 points of the upper half circle, exp(i pi (m - 1/2) / 32), with Re<.> of the
-    mean; for complex z that is wrong, and it is the full circle's 64 points, exp(2 pi i (m - 1/2) / 64), with the complex
-    mean."""
+def _etd1d_contour(what: str, N, length, dt, symbol, advect, dealias, full_circle: bool):
+    """What every table of the 1-D ETD family starts from: z = dt symbol(kappa) [K], LR = z + r_m [K, points] over the
+    Kassam-Trefethen contour points r_m, the mean over them and the float64 g [K].  For real z the 32 points of the upper
+    half circle, exp(i pi (m - 1/2) / 32), with Re<.> of the mean; for complex z that is wrong, and it is the full
+    circle's 64 points, exp(2 pi i (m - 1/2) / 64), with the complex mean."""
     import math
     N = int(N)
     if N < 4 or N % 2:
@@ -1422,13 +1421,11 @@ def _etd1d_tables(what: str, N, length, dt, symbol, advect, dealias, full_circle
     K = N // 2 + 1
     n = torch.arange(K, dtype=torch.float64)
     kappa = (2.0 * math.pi / float(length)) * n
-    h = float(dt)
-    z = h * symbol(kappa)
+    z = float(dt) * symbol(kappa)
     points = 64 if full_circle else 32
     m = torch.arange(1, points + 1, dtype=torch.float64)
     r = torch.polar(torch.ones(points, dtype=torch.float64), (2.0 if full_circle else 1.0) * math.pi * (m - 0.5) / points)
     LR = z.view(K, 1).to(torch.complex128) + r.view(1, points)
-    eLR = torch.exp(LR)
 
     def mean(t):
         return t.mean(dim=1) if full_circle else t.mean(dim=1).real
@@ -1436,12 +1433,37 @@ def _etd1d_tables(what: str, N, length, dt, symbol, advect, dealias, full_circle
     keep = (n <= (2.0 / 3.0) * (N // 2)).to(torch.float64) if dealias else torch.ones(K, dtype=torch.float64)
     g = -(float(advect) / 2.0) * kappa * keep
     g[N // 2] = 0.0
+    return z, LR, mean, g
+
+
+def _etd1d_tables(what: str, N, length, dt, symbol, advect, dealias, full_circle: bool):
+    """The tables under etd1d_tables (full_circle False) and etd1d_tables_cx (True): six float64 / complex128
+    coefficients [K] of z = dt symbol(kappa) and the float32 [kp] table g, on the contour of _etd1d_contour."""
+    z, LR, mean, g = _etd1d_contour(what, N, length, dt, symbol, advect, dealias, full_circle)
+    h = float(dt)
+    eLR = torch.exp(LR)
     coefficients = (torch.exp(z), torch.exp(z / 2.0),
                     h * mean((torch.exp(LR / 2.0) - 1.0) / LR),
                     h * mean((-4.0 - LR + eLR * (4.0 - 3.0 * LR + LR ** 2)) / LR ** 3),
                     h * mean((2.0 + LR + eLR * (-2.0 + LR)) / LR ** 3),
                     h * mean((-4.0 - 3.0 * LR - LR ** 2 + eLR * (4.0 - LR)) / LR ** 3))
     return z, coefficients, _padded(g)
+
+
+def _cx_symbol(c1, c2, c3, c4):
+    """kappa [K] -> l = c2 kappa^2 + c4 kappa^4 + i (c1 kappa + c3 kappa^3) with Im l_{N/2} = 0"""
+    def symbol(kappa):
+        odd = float(c1) * kappa + float(c3) * kappa ** 3
+        odd[-1] = 0.0
+        return torch.complex(float(c2) * kappa ** 2 + float(c4) * kappa ** 4, odd)
+    return symbol
+
+
+def _cx_padded(z: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+    """a complex128 table [K] of z -> float32 [2, kp] (real plane, imaginary plane).  Real z (the mean and Nyquist modes,
+    an even symbol): the circle's points pair up as conjugates and the mean is real; what its imaginary part holds then
+    is the sum's rounding (1e-20), dropped"""
+    return _padded(torch.stack([t.real, torch.where(z.imag == 0, torch.zeros_like(t.imag), t.imag)]))
 
 
 def etd1d_tables(N: int, length: float, c2: float, c4: float, dt: float, advect: float = 1.0, dealias: bool = True):
@@ -1467,16 +1489,8 @@ def etd1d_tables_cx(N: int, length: float, c1: float, c2: float, c3: float, c4: 
     complex, so the contour is the full circle, LR = z + r_m, r_m = exp(2 pi i (m - 1/2) / 64), m = 1 .. 64, and the mean is
     the complex mean (the upper half circle with Re<.> of etd1d_tables is that mean for real z only); where z is real the
     mean is real and its imaginary part is stored as zero.  include/rpde.h has the formulas."""
-    def symbol(kappa):
-        odd = float(c1) * kappa + float(c3) * kappa ** 3
-        odd[-1] = 0.0
-        return torch.complex(float(c2) * kappa ** 2 + float(c4) * kappa ** 4, odd)
-
-    z, coefficients, g = _etd1d_tables("etd1d_tables_cx", N, length, dt, symbol, advect, dealias, True)
-    # real z (the mean and Nyquist modes, an even symbol): the circle's points pair up as conjugates and the mean is
-    # real; what its imaginary part holds then is the sum's rounding (1e-20), dropped
-    return tuple(_padded(torch.stack([t.real, torch.where(z.imag == 0, torch.zeros_like(t.imag), t.imag)]))
-                 for t in coefficients) + (g,)
+    z, coefficients, g = _etd1d_tables("etd1d_tables_cx", N, length, dt, _cx_symbol(c1, c2, c3, c4), advect, dealias, True)
+    return tuple(_cx_padded(z, t) for t in coefficients) + (g,)
 
 
 def grf1d(noise: torch.Tensor, sqrt_eig: torch.Tensor) -> torch.Tensor:
@@ -1521,6 +1535,116 @@ def etd1d_solve(u0: torch.Tensor, tables, steps: int, record_every: int) -> torc
         check(steps_call(ptr(U), *(ptr(t) for t in tabs), B, N, record_every, ws.data_ptr(), nws, st), name)
         check(lib.rpde_etd1d_irfft(ptr(U), ptr(snaps[c]), B, N, st), "etd1d_irfft")
     return snaps[:n_rec].permute(1, 0, 2).contiguous()
+
+
+# ----------------------------------------------------------------------------
+# equation-residual loss of the 1-D ETD family (csrc/etd_residual.hip, rpde_etd_residual_*; utils/loss.py
+# EquationResidualLoss).  Forward and backward on the device, GPU tensors only, no CPU fallback.
+# ----------------------------------------------------------------------------
+def etd1d_residual_tables(N: int, length: float, c1: float, c2: float, c3: float, c4: float, interval: float,
+                          advect: float = 1.0, dealias: bool = True):
+    """(E, m0, m1): the tables of the equation residual of u_t = L u - (advect/2) (u^2)_x over the time `interval` between
+    an input and a prediction, for the symbol and g of etd1d_tables_cx, as float32 [2, kp] host tensors (real plane,
+    imaginary plane; padding zero), formed in float64 / complex128 and rounded once.  With z = interval l_n, LR = z + r_m on
+    the full circle's 64 points and <.> the complex mean:
+        E = e^z,  m0 = interval (phi1 - phi2) i g,  m1 = interval phi2 i g,
+        phi1 = <(e^LR - 1) / LR>,  phi2 = <(e^LR - 1 - LR) / LR^2>
+    -- the exponential trapezoidal rule (ETD2).  The tables are always complex (i g is); where z is real the imaginary part
+    of E is stored as zero, and g_0 = g_{N/2} = 0 makes m0 = m1 = 0 there.  include/rpde.h has the formulas."""
+    z, LR, mean, g = _etd1d_contour("etd1d_residual_tables", N, length, interval, _cx_symbol(c1, c2, c3, c4), advect,
+                                    dealias, True)
+    h = float(interval)
+    eLR = torch.exp(LR)
+    phi1 = mean((eLR - 1.0) / LR)
+    phi2 = mean((eLR - 1.0 - LR) / LR ** 2)
+    # real z: the means are real, and what their imaginary parts hold is the sum's rounding, dropped before i g turns
+    # it into a real part
+    real = z.imag == 0
+    phi1 = torch.complex(phi1.real, torch.where(real, torch.zeros_like(phi1.imag), phi1.imag))
+    phi2 = torch.complex(phi2.real, torch.where(real, torch.zeros_like(phi2.imag), phi2.imag))
+    ig = torch.complex(torch.zeros_like(g), g)
+    m0, m1 = h * (phi1 - phi2) * ig + 0.0, h * phi2 * ig + 0.0                # + 0.0: no negative zeros where g = 0
+    return (_cx_padded(z, torch.exp(z)), _padded(torch.stack([m0.real, m0.imag])), _padded(torch.stack([m1.real, m1.imag])))
+
+
+def _residual_affine(affine):
+    """(a_p, b_p, a_x, b_x) as a ctypes float[4], or None for the identity"""
+    if affine is None:
+        return None
+    vals = tuple(float(v) for v in affine)
+    if len(vals) != 4 or not all(v == v and abs(v) != float("inf") for v in vals):
+        raise ValueError(f"etd1d_residual: affine must be four finite numbers (a_p, b_p, a_x, b_x), got {affine}")
+    return (C.c_float * 4)(*vals)
+
+
+class _EtdResidual(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, x, E, m0, m1, affine, size_average: bool, reduction: bool):
+        lib = load()
+        shape = tuple(pred.shape)
+        B, N = shape[0], shape[-1]
+        p2, x2 = _f32c(pred).reshape(B, N), _f32c(x.detach()).reshape(B, N)
+        pp, px = ptr(p2), ptr(x2)                             # raises for CPU tensors: there is no fallback
+        dev = p2.device
+        nws = lib.rpde_etd_residual_ws_bytes(B, N)
+        if nws == 0:
+            raise ValueError(f"etd1d_residual: unsupported B={B} N={N} (N even, 4 .. 4096; 1 <= B <= 16383: four "
+                             "fields of B images are one batch of the half-spectrum layer)")
+        aff = _residual_affine(affine)
+        stats = torch.empty(2 * B, dtype=torch.float32, device=dev)
+        rel = torch.empty(B, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev) if reduction else None
+        spec = torch.empty(lib.rpde_etd_residual_spec_elems(B, N), dtype=torch.float32, device=dev)
+        ws = workspace(nws, dev)
+        check(lib.rpde_etd_residual_fwd(pp, px, ptr(E), ptr(m0), ptr(m1), aff, ptr(rel), ptr(loss), ptr(stats), ptr(spec),
+                                        B, N, int(size_average), ws.data_ptr(), nws, stream_ptr()), "etd_residual_fwd")
+        ctx.save_for_backward(p2, spec, stats, m1)
+        ctx.meta = (shape, B, N, affine, size_average, reduction)
+        return loss if reduction else rel
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = load()
+        p2, spec, stats, m1 = ctx.saved_tensors
+        shape, B, N, affine, size_average, reduction = ctx.meta
+        g = _f32c(g)
+        gp = torch.empty(shape, dtype=torch.float32, device=p2.device)
+        nws = lib.rpde_etd_residual_ws_bytes(B, N)
+        ws = workspace(nws, p2.device)
+        check(lib.rpde_etd_residual_bwd(ptr(p2), ptr(spec), ptr(m1), _residual_affine(affine), ptr(stats),
+                                        ptr(g) if reduction else None, None if reduction else ptr(g), ptr(gp), B, N,
+                                        int(size_average), ws.data_ptr(), nws, stream_ptr()), "etd_residual_bwd")
+        return gp, None, None, None, None, None, None, None
+
+
+def etd1d_residual(pred, x, tables, affine=None, size_average: bool = True, reduction: bool = True):
+    """Does pred ~ u(t + interval) follow from x = u(t) under u_t = L u - (c/2) (u^2)_x?  With the tables (E, m0, m1) of
+    etd1d_residual_tables (host or device tensors, [2, kp] each),
+        r^ = rfft(p~) - E rfft(x~) - m0 rfft(x~^2) - m1 rfft(p~^2),   rel[b] = |r[b]|_2 / (|x~[b]|_2 + 1e-8),
+    then mean / sum / the per-sample vector as relative_l2.  affine = (a_p, b_p, a_x, b_x): p~ = a_p pred + b_p,
+    x~ = a_x x + b_x (None: the identity); the gradient is with respect to pred itself.  The rule is the exponential
+    trapezoidal one: exact in the linear part, second order in the nonlinear one, so the residual of an exact pair is
+    O(interval^3 N_tt) and the loss is for |interval N_tt| small (DESIGN.md has the table: on KS at N = 64 an exact
+    pair gives rel ~ 1e-3 at interval 0.05, ~ 1e-2 at 0.1 and ~ 1 by 0.4).  pred, x: [B, N] or [B, 1, N] (one channel:
+    the equation is scalar) contiguous fp32 tensors on the GPU; gradient for pred only, no CPU fallback."""
+    ok = pred.dim() in (2, 3) and pred.shape == x.shape and (pred.dim() == 2 or pred.shape[1] == 1)
+    if not ok:
+        raise ValueError(f"etd1d_residual: pred {tuple(pred.shape)} / x {tuple(x.shape)}, expected equal [B, N] or [B, 1, N] "
+                         "shapes (one channel)")
+    if pred.dtype != torch.float32 or x.dtype != torch.float32:
+        raise ValueError(f"etd1d_residual: expected float32 fields, got {pred.dtype} / {x.dtype}")
+    N = int(pred.shape[-1])
+    tables = tuple(tables)
+    want = (2, _kp(N))
+    if len(tables) != 3 or any(tuple(t.shape) != want for t in tables):
+        raise ValueError(f"etd1d_residual: expected the three [2, {want[1]}] tables of etd1d_residual_tables(N={N}, ...), got "
+                         f"{[tuple(t.shape) for t in tables]}")
+    _residual_affine(affine)                                  # validates
+    if not pred.is_cuda:
+        ptr(pred)                                             # the CPU refusal of every op
+    E, m0, m1 = (_f32c(t.detach().to(pred.device)) for t in tables)
+    return _EtdResidual.apply(pred, x, E, m0, m1, None if affine is None else tuple(float(v) for v in affine),
+                              bool(size_average), bool(reduction))
 
 
 # ----------------------------------------------------------------------------

@@ -52,7 +52,9 @@ def train(model, train_loader, val_loader, optimizer, scheduler, y_normalizer=No
           graph: Optional[bool] = None, loss_fn=None):
     """loss_fn (default: RelativeL2Loss(size_average=True)): the training objective, a callable (prediction, target) ->
     device scalar, e.g. utils.loss.SpectralRelativeL2Loss; validation and evaluate() stay plain relative L2 whatever
-    trains the model, so reported metrics compare across objectives.  For graph=True its plans and tables must exist
+    trains the model, so reported metrics compare across objectives.  A loss_fn whose `takes_input` attribute is true
+    (utils.loss.EquationResidualLoss, a SumLoss that holds one) is called as loss_fn(prediction, target, input) with the
+    batch's input as the loader gave it (not decoded: the loss carries its own affine map).  For graph=True its plans and tables must exist
     before the capture: the GRAPH_AFTER eager steps of a batch shape see to that.
 
     graph (default: environment RPDE_TRAIN_GRAPH=1): replay the step -- zero_grad, forward, loss, backward, gradient
@@ -88,11 +90,13 @@ def train(model, train_loader, val_loader, optimizer, scheduler, y_normalizer=No
                 setattr(resident, k, v.to(device))
         y_normalizer = resident
 
-    def step_loss(pred_y, batch_y):
+    takes_input = bool(getattr(loss_fn, "takes_input", False))
+
+    def step_loss(pred_y, batch_y, batch_x=None):
         if decode:
             pred_y = y_normalizer.decode(pred_y, device=device)
             batch_y = y_normalizer.decode(batch_y, device=device)
-        return loss_fn(pred_y, batch_y)
+        return loss_fn(pred_y, batch_y, batch_x) if takes_input else loss_fn(pred_y, batch_y)
     seen: dict = {}          # batch shape -> eager steps run so far, then its GraphedTrainStep
     loss_history, val_loss_history = [], []
     for epoch in range(epochs):
@@ -109,7 +113,7 @@ def train(model, train_loader, val_loader, optimizer, scheduler, y_normalizer=No
                     from rpde.graph import GraphedTrainStep
                     try:
                         state = GraphedTrainStep(model, step_loss, optimizer, batch_x, batch_y, warmup=0,
-                                                 after_backward=bucket.all_reduce_mean)
+                                                 after_backward=bucket.all_reduce_mean, loss_takes_input=takes_input)
                     except ValueError:             # a model the graph refuses (host-side randomness): this shape stays eager
                         state = -1
                     seen[key] = state
@@ -124,7 +128,7 @@ def train(model, train_loader, val_loader, optimizer, scheduler, y_normalizer=No
             if use_normalizer and y_normalizer is not None:
                 pred_y = y_normalizer.decode(pred_y, device=device)
                 batch_y = y_normalizer.decode(batch_y, device=device)
-            loss = loss_fn(pred_y, batch_y)
+            loss = loss_fn(pred_y, batch_y, batch_x) if takes_input else loss_fn(pred_y, batch_y)
             loss.backward()
             bucket.all_reduce_mean()
             bucket.detach_untouched()          # parameters outside the graph keep grad None, as after zero_grad()

@@ -12,17 +12,7 @@ import torch
 from rpde import ops
 from rpde.ops import frozen_weights
 from utils.loss import RelativeL2Loss
-
-
-def _scalar_stats(norm):
-    """(mean, std + eps) when the normaliser is one global affine map (SimpleNormalizer), else None"""
-    try:
-        m, s, e = norm.mean, norm.std, getattr(norm, "eps", 0.0)
-        if isinstance(m, (int, float)) and isinstance(s, (int, float)):
-            return float(m), float(s) + float(e)
-    except AttributeError:
-        pass
-    return None
+from utils.normalizers import scalar_stats as _scalar_stats
 
 
 @torch.no_grad()

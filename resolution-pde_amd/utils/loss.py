@@ -9,7 +9,12 @@ mode -- the H^s / Sobolev relative loss of operator learning is the preset -- fo
 BandRelativeL2Loss, SpectrumMatchingLoss (no counterpart in the reference): objectives whose weights depend on the
 sample -- the relative error band by band, and the mismatch of the energy per wavenumber band -- as a few operations
 on the [B, J] per-sample band energies of rpde.ops.band_energy (csrc/band_energy.hip, forward and backward on the
-device).  SumLoss adds weighted losses into one callable."""
+device).
+
+EquationResidualLoss (no counterpart in the reference): the physics-informed term for the 1-D ETD family
+u_t = L u - (c/2) (u^2)_x -- does the one-step map satisfy the equation itself? -- forward and backward on the device
+(rpde.ops.etd1d_residual, csrc/etd_residual.hip).  It reads the network's input next to its prediction
+(`takes_input`).  SumLoss adds weighted losses into one callable."""
 from __future__ import annotations
 
 import math
@@ -252,9 +257,96 @@ class SpectrumMatchingLoss(_BandedLoss):
         return self._reduce(((torch.log(e_x + delta) - torch.log(e_y + delta)) ** 2).sum(1) / T.J_e)
 
 
+class EquationResidualLoss(nn.Module):
+    """Does the prediction p ~ u(t + interval) follow from the input x = u(t) under
+
+        u_t = L u - (advect/2) (u^2)_x,   l_n = c2 kappa_n^2 + c4 kappa_n^4 + i (c1 kappa_n + c3 kappa_n^3),  kappa_n = 2 pi n / length
+
+    (the family and sign conventions of rpde.ops.etd1d_tables_cx and the generators)?  With the exponential trapezoidal
+    rule -- exact in the linear part however stiff, the nonlinear term interpolated linearly between the two ends --
+
+        r^ = rfft(p) - E rfft(x) - m0 rfft(x^2) - m1 rfft(p^2),   rel[b] = |r[b]|_2 / (|x[b]|_2 + 1e-8)
+
+    then mean / sum / per-sample vector as RelativeL2Loss (rpde.ops.etd1d_residual_tables has E, m0, m1).  `interval` is
+    the time between input and prediction: the snapshot interval of the data set, not the solver's step.  The rule is
+    second order, so an exact pair leaves rel ~ interval^3 |N_tt|: the loss is for |interval N_tt| small.  Float64
+    figures, exact pair against the trivial predictor p = x (DESIGN.md has the table): KS N = 64, length 16, nu 0.05:
+    3.5e-4 .. 9.7e-4 against 0.15 .. 0.24 at interval 0.05, 4.8e-3 .. 1.2e-2 against 0.36 .. 0.56 at 0.1, and by
+    interval ~ 0.4 the rule has lost its meaning (rel ~ 1 for both).
+
+    forward(pred, target, inp): the target is unused and may be None; pred, inp [B, N] or [B, 1, N] fp32 tensors on the
+    GPU, gradient for pred only.  set_affine(pred=(a, b), inp=(a, b)): the residual is formed on a pred + b and a inp + b
+    (fields a SimpleNormalizer encoded, penalised in physical units); the gradient is still with respect to pred.
+    Device tables are cached per (N, device), so one object serves mixed-resolution batches; warm((N,), device) builds
+    them, the plans and the workspaces ahead of a hipGraph capture."""
+
+    takes_input = True
+
+    def __init__(self, length, interval, c1=0.0, c2=0.0, c3=0.0, c4=0.0, advect=1.0, dealias=True, size_average=True,
+                 reduction=True):
+        super().__init__()
+        vals = [float(v) for v in (length, interval, c1, c2, c3, c4, advect)]
+        if not all(math.isfinite(v) for v in vals) or not (vals[0] > 0 and vals[1] > 0):
+            raise ValueError(f"EquationResidualLoss: length {length} and interval {interval} must be positive and every "
+                             "coefficient finite")
+        self.length, self.interval, self.c1, self.c2, self.c3, self.c4, self.advect = vals
+        self.dealias = bool(dealias)
+        self.size_average = size_average
+        self.reduction = reduction
+        self._affine = None
+        self._tables: dict = {}
+
+    @classmethod
+    def burgers(cls, nu_eff, length, interval, **kw):
+        """u_t + u u_x = nu_eff u_xx (data_generation/burgers_1d.py: nu_eff = nu / pi)"""
+        return cls(length, interval, c2=-float(nu_eff), **kw)
+
+    @classmethod
+    def ks(cls, viscosity, length, interval, **kw):
+        """u_t + u u_x + u_xx + viscosity u_xxxx = 0 (data_generation/ks_1d.py)"""
+        return cls(length, interval, c2=1.0, c4=-float(viscosity), **kw)
+
+    @classmethod
+    def kdv(cls, dispersion, viscosity, length, interval, **kw):
+        """u_t + u u_x + dispersion u_xxx = viscosity u_xx (data_generation/kdv_1d.py)"""
+        return cls(length, interval, c2=-float(viscosity), c3=float(dispersion), **kw)
+
+    def set_affine(self, pred=(1.0, 0.0), inp=(1.0, 0.0)) -> None:
+        """decode maps of the prediction and of the input, each (a, b) for a field + b; set before a capture"""
+        aff = (float(pred[0]), float(pred[1]), float(inp[0]), float(inp[1]))
+        if not all(math.isfinite(v) for v in aff):
+            raise ValueError(f"EquationResidualLoss.set_affine: {pred} / {inp}")
+        self._affine = None if aff == (1.0, 0.0, 1.0, 0.0) else aff
+
+    def _table(self, N, device):
+        key = (int(N), torch.device(device))
+        t = self._tables.get(key)
+        if t is None:
+            host = ops.etd1d_residual_tables(int(N), self.length, self.c1, self.c2, self.c3, self.c4, self.interval,
+                                             self.advect, self.dealias)
+            t = self._tables[key] = tuple(h.to(device).contiguous() for h in host)
+        return t
+
+    def warm(self, spatial_shape, device="cuda") -> None:
+        """plans, workspaces and the tables of one grid, outside any capture"""
+        grid = tuple(int(n) for n in spatial_shape)
+        if len(grid) != 1:
+            raise ValueError(f"EquationResidualLoss.warm: grid {grid}, the equation is one-dimensional")
+        z = torch.zeros((1, 1) + grid, dtype=torch.float32, device=device, requires_grad=True)
+        self(z, None, torch.ones_like(z.detach())).sum().backward()
+        torch.cuda.synchronize(z.device)
+
+    def forward(self, pred, target, inp):
+        if inp is None:
+            raise ValueError("EquationResidualLoss: the network's input is needed next to its prediction")
+        return ops.etd1d_residual(pred, inp, self._table(pred.shape[-1], pred.device), self._affine, self.size_average,
+                                  self.reduction)
+
+
 class SumLoss(nn.Module):
     """sum_i weight_i loss_i(x, y) as one callable: SumLoss([(1.0, RelativeL2Loss()), (0.1, SpectrumMatchingLoss(1))]).
-    warm() goes to the terms that have one."""
+    warm() goes to the terms that have one.  A term whose `takes_input` is true (EquationResidualLoss) is called as
+    loss_i(x, y, inp) with the network's input; `takes_input` of the sum is true when any term's is."""
 
     def __init__(self, terms):
         super().__init__()
@@ -263,15 +355,18 @@ class SumLoss(nn.Module):
             raise ValueError("SumLoss: no terms")
         self.weights = [w for w, _ in terms]
         self.terms = nn.ModuleList([fn for _, fn in terms])
+        self.takes_input = any(getattr(fn, "takes_input", False) for fn in self.terms)
 
     def warm(self, spatial_shape, device="cuda") -> None:
         for fn in self.terms:
             if hasattr(fn, "warm"):
                 fn.warm(spatial_shape, device)
 
-    def forward(self, x, y):
+    def forward(self, x, y, inp=None):
+        if self.takes_input and inp is None:
+            raise ValueError("SumLoss: a term needs the network's input (call it as loss(pred, target, inp))")
         out = None
         for w, fn in zip(self.weights, self.terms):
-            v = fn(x, y) * w
+            v = (fn(x, y, inp) if getattr(fn, "takes_input", False) else fn(x, y)) * w
             out = v if out is None else out + v
         return out
