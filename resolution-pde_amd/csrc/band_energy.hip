@@ -4,7 +4,7 @@
 //   c_kx = 1 at kx = 0 and (even N) kx = N/2, else 2;  band in {-1, 0 .. J-1}, -1: the entry belongs to no band
 //   grad_z[b, c] = 2 irfft2(gE[b, band(ky,kx)] Z[b,c,ky,kx]),  weight 0 where band = -1
 // on the half-spectrum layer of halfspec.h (hs_rfft / hs_irfft: the plans of the loss, the resizers, the generators).
-// The field is x, or x - y formed in fp32 BEFORE the transform (k_be_diff; freq_energy.hip has the reason).
+// The field is x, or x - y formed in fp32 BEFORE the transform (rel_diff of rel_loss.h).
 //
 // The band table reaches the kernels in two forms, both built once per (grid, table) by rpde.ops:
 //   entries [n_entries], start [J+1]   the entries of band j are entries[start[j] .. start[j+1]), each
@@ -13,32 +13,18 @@
 //   band [M][kp]                       the band of every entry, padded columns -1; backward only
 // so that a (sample, band) sum reads exactly the entries of its band, not the whole table:
 //   k_be_partial   a wave per (sample, band, slot): |Z|^2 c_kx over its share of the band's entries and the C channels in
-//                  float64, lanes in a fixed order; k_be_final adds the slots in order and scales by 1 / (M N) -- the
-//                  k_wl2_energy / k_wl2_final pattern, no atomics: identical calls, identical bits, and a sample's
-//                  energies do not depend on the batch it sits in
+//                  float64, lanes in a fixed order; k_be_final adds the slots in order and scales by 1 / (M N): no
+//                  atomics, identical calls give identical bits, and a sample's energies do not depend on its batch
 //   k_be_scale     backward: a thread per 16-byte group of kx gathers gE[b, band] for its four entries and writes
 //                  2 gE Z (zeros where band = -1 and in the padded columns), the spectrum the inverse transform reads
 // An offset outside the image, a start[] outside entries[] and a band outside 0 .. J-1 are skipped, not trusted.
 #include "halfspec.h"
+#include "rel_loss.h"
 #include "wave.h"
 
 namespace rpde {
 
-constexpr int BE_SLOTS = 32;         // partial sums per (sample, band) at most
 constexpr int BE_MAX_BANDS = 4096;
-
-__global__ __launch_bounds__(256) void k_be_diff(const float* __restrict__ x, const float* __restrict__ y, float* __restrict__ d,
-                                                 long n, int vec) {
-  const long i0 = (long)blockIdx.x * 256 + threadIdx.x, step = (long)gridDim.x * 256;
-  if (vec) {
-    for (long i = i0; i < n / 4; i += step) {
-      const float4 a = reinterpret_cast<const float4*>(x)[i], b = reinterpret_cast<const float4*>(y)[i];
-      reinterpret_cast<float4*>(d)[i] = make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w);
-    }
-  } else {
-    for (long i = i0; i < n; i += step) d[i] = x[i] - y[i];
-  }
-}
 
 struct BeGeom : HalfSpec { int B, C, J, S; };     // B C images; S partial sums per (sample, band)
 
@@ -98,15 +84,10 @@ __global__ __launch_bounds__(256) void k_be_scale(const float* __restrict__ spec
   }
 }
 
-// the grids of rpde_wrel_l2_*, and a band count in range
-static bool be_dims_ok(int B, int C, int M, int N, int J) {
-  return B > 0 && C > 0 && M >= 1 && N >= 2 && M <= HS_MAX_N && N <= HS_MAX_N && (long)B * C * M < (1L << 31) && J >= 1 &&
-         J <= BE_MAX_BANDS;
-}
+static bool be_dims_ok(int B, int C, int M, int N, int J) { return hs_loss_dims_ok(B, C, M, N) && J >= 1 && J <= BE_MAX_BANDS; }
 static BeGeom be_geom(int B, int C, int M, int N, int J) {
   BeGeom g{hs_geom(B * C, M, N), B, C, J, 1};
-  const long most = (long)C * M * g.K;            // no band owns more terms than a sample has
-  g.S = (int)((most + 2047) / 2048 < BE_SLOTS ? (most + 2047) / 2048 : BE_SLOTS);
+  g.S = rel_slots((long)C * M * g.K);             // no band owns more terms than a sample has
   return g;
 }
 
@@ -150,10 +131,7 @@ int rpde_band_energy_fwd(const float* x, const float* y, const int32_t* entries,
   float* sp = spec ? spec : s0;
   const float* z = x;
   if (y) {
-    const long total = (long)g.images * M * N;
-    const int vec = total % 4 == 0 && al16(x) && al16(y);
-    hipLaunchKernelGGL(k_be_diff, dim3(hs_blocks(vec ? total / 4 : total, 2048)), dim3(256), 0, st, x, y, d, total, vec);
-    RPDE_LAUNCH_CHECK();
+    RPDE_TRY(rel_diff(x, y, d, (long)g.images * M * N, st));
     z = d;
   }
   RPDE_TRY(hs_rfft(g, z, s1, sp, st));

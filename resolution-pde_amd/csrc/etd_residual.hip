@@ -2,7 +2,7 @@
 // counterpart in the reference): does the one-step map x = u(t) -> p ~ u(t + D) satisfy the equation?  With the exponential
 // trapezoidal rule (ETD2: the linear part exact, Nhat(w) = i g rfft(w^2) interpolated linearly between the two ends)
 //   r^_n   = p^_n - E_n x^_n - m0_n rfft(x^2)_n - m1_n rfft(p^2)_n,      E = e^z, m0 = D (phi1 - phi2) i g, m1 = D phi2 i g
-//   rel[b] = sqrt(E_r[b]) / (sqrt(E_x[b]) + 1e-8),   E(z)[b] = sum_n c_n |z^_n|^2 / N,   c_n = 1 at n = 0, N/2, else 2
+//   rel[b] = sqrt(E_r[b]) / (sqrt(E_x[b]) + REL_EPS),   E(z)[b] = sum_n c_n |z^_n|^2 / N,   c_n = 1 at n = 0, N/2, else 2
 // on the half-spectrum layer of halfspec.h at M = 1.  The three tables are complex, [re|im][kp], formed by the caller in
 // float64 and rounded once (include/rpde.h has the formulas): no division and no transcendental here but the final
 // sqrt and the per-sample coefficient.  An affine decode (a_p p + b_p, a_x x + b_x) is folded into the first pass.
@@ -13,19 +13,18 @@
 //                   fp32 transforms of halfspec.h leave an error of that size in it (see the kernel).  r^ is rounded once
 //                   and stored for backward (padded columns zero); c_n |r^_n|^2 and c_n |x^_n|^2 per (field, sample,
 //                   slot) in float64
-//   k_res_final     adds the slots in fixed order: stats, rel, loss -- the k_wl2_energy / k_wl2_final pattern of
-//                   spectral_loss.hip, no atomics: identical calls give identical bits, and the slots of a sample depend on
-//                   N alone, so its value does not depend on the batch around it
+//   rel_final       (rel_loss.h) adds the slots in fixed order: stats, rel, loss.  The slots of a sample depend on N
+//                   alone, so its value does not depend on the batch around it
 // Backward:  d rel[b] / d p = a_p coef_b (irfft(r^) - 2 p~ irfft(conj(m1) r^))
 //   k_res_fan       [r^ | conj(m1) r^], 2 B spectra
 //   synthesis       of the 2 B images
-//   k_res_grad      p~ recomputed from p; coef_b = g_b / (sqrt(E_r) (sqrt(E_x) + 1e-8)) formed from the saved stats and the
-//                   upstream gradient on the device, 0 where E_r = 0, as k_wl2_weight
+//   k_res_grad      p~ recomputed from p; coef_b is rel_coef of rel_loss.h
 // The backward's spectral kernel streams as k_etd_stage_cx does: a thread owns one 16-byte group of k for both planes,
 // whole float4 loads and stores, grid (blocks, images).  Its transform is that of halfspec.h: the gradient is no
 // remainder, and holds its bound with it.
 #include "etd_cx.h"
 #include "halfspec.h"
+#include "rel_loss.h"
 
 namespace rpde {
 
@@ -103,30 +102,6 @@ __global__ __launch_bounds__(RES_BLOCK) void k_res_spectrum(const float* __restr
   }
 }
 
-// one workgroup: stats[b] = (sqrt E_r, sqrt E_x), rel[b], loss = mean / sum
-__global__ __launch_bounds__(256) void k_res_final(const double* __restrict__ part, float* __restrict__ rel, float* __restrict__ loss,
-                                                   float* __restrict__ stats, ResGeom g, int S, int size_average) {
-  __shared__ double red[256];
-  const double inv = 1.0 / (double)g.N;
-  double acc = 0.0;
-  for (int b = threadIdx.x; b < g.B; b += 256) {
-    double er = 0.0, ex = 0.0;
-    for (int j = 0; j < S; ++j) { er += part[(long)b * S + j]; ex += part[((long)g.B + b) * S + j]; }
-    const float rn = (float)sqrt(er * inv), xn = (float)sqrt(ex * inv);
-    const float r = rn / (xn + 1e-8f);
-    stats[2 * b] = rn; stats[2 * b + 1] = xn;
-    if (rel) rel[b] = r;
-    acc += (double)r;
-  }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && loss) *loss = (float)(size_average ? red[0] / g.B : red[0]);
-}
-
 // grid (blocks, B): out [2 B] spectra, out[b] = r^[b], out[B + b] = conj(m1) r^[b].  The padded columns of spec_r and of
 // m1 are zero, and so are those of both outputs
 __global__ __launch_bounds__(256) void k_res_fan(const float* __restrict__ spec_r, const float* __restrict__ m1,
@@ -151,10 +126,7 @@ __global__ __launch_bounds__(256) void k_res_grad(const float* __restrict__ p, c
                                                   const float* __restrict__ grad_rel, float* __restrict__ grad_p, int B, int N,
                                                   int vec, int size_average, ResAffine a) {
   const int b = blockIdx.y;
-  const float rn = stats[2 * b], xn = stats[2 * b + 1];
-  const float gr = grad_rel ? grad_rel[b] : (size_average ? grad_loss[0] / B : grad_loss[0]);
-  const float coef = rn > 0.f ? gr / (rn * (xn + 1e-8f)) : 0.f;
-  const float scale = a.ap * coef;
+  const float scale = a.ap * rel_coef(stats, grad_loss, grad_rel, b, B, size_average);
   const long row = (long)b * N;
   const float* __restrict__ pb = p + row;
   const float* __restrict__ rb = rs + row;
@@ -221,9 +193,7 @@ int rpde_etd_residual_fwd(const float* p, const float* x, const float* E, const 
   RPDE_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_res_spectrum, sg, sb, 0, st, p, x, tw, E, m0, m1, spec_r, part, g, res_affine(affine));
   RPDE_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_res_final, dim3(1), dim3(256), 0, st, part, rel, loss, stats, g, (int)sg.x, size_average);
-  RPDE_LAUNCH_CHECK();
-  return RPDE_OK;
+  return rel_final(part, rel, loss, stats, B, (int)sg.x, 1.0 / (double)N, size_average, st);
 }
 
 int rpde_etd_residual_bwd(const float* p, const float* spec_r, const float* m1, const float* affine, const float* stats,

@@ -1,6 +1,6 @@
 // The half-spectrum layer under the generators (ns_solver.hip, etd1d.hip), the random fields and transform entries
-// (halfspec.hip) and the mode-weighted loss (spectral_loss.hip): one geometry, its limits, the 16-byte group helpers and
-// the transforms of a geometry on the full-spectrum real DFT of cf_dft.h.
+// (halfspec.hip) and the spectral losses (spectral_loss.hip, band_energy.hip, etd_residual.hip): one geometry, its
+// limits, the 16-byte group helpers and the transforms of a geometry on the full-spectrum real DFT of cf_dft.h.
 #pragma once
 #include "cf_dft.h"
 #include "pointwise.h"
@@ -28,6 +28,10 @@ inline bool hs_dims_ok(int images, int M, int N, int fan = 1) {
          4L * fan * images * (M > N ? M : N) < (1L << 31);
 }
 inline bool hs_dims2_ok(int images, int M, int N, int fan = 1) { return M > 1 && hs_dims_ok(images, M, N, fan); }   // 2-D only
+// a loss grid (spectral_loss.hip, band_energy.hip): B C images whose axes may be odd, M = 1: one-dimensional
+inline bool hs_loss_dims_ok(int B, int C, int M, int N) {
+  return B > 0 && C > 0 && M >= 1 && N >= 2 && M <= HS_MAX_N && N <= HS_MAX_N && (long)B * C * M < (1L << 31);
+}
 
 // `what`: the entry's name, a literal or a variable
 #define HS_CHECK_WS(what, ws) \

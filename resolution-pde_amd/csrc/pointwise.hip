@@ -612,83 +612,6 @@ __global__ __launch_bounds__(256) void k_weight_norm_bwd(const float* __restrict
     for (int i = lane; i < in_f; i += 64) gv[(long)o * in_f + i] = scale * (gr[i] - vr[i] * back);
 }
 
-// ---------------------------------------------------------------------------
-// relative L2 loss
-// ---------------------------------------------------------------------------
-constexpr int L2_BLOCKS = 64;   // partial blocks per sample
-
-__global__ __launch_bounds__(256) void k_rel_l2_partial(const float* __restrict__ x, const float* __restrict__ y,
-                                                        float* __restrict__ part, long per) {
-  __shared__ float red[2][4];
-  const int b = blockIdx.y;
-  const float* xb = x + (long)b * per;
-  const float* yb = y + (long)b * per;
-  float sd = 0.f, sy = 0.f;
-  const bool vec = (per % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0) && ((reinterpret_cast<uintptr_t>(y) & 15) == 0);
-  if (vec) {
-    const long nv = per / 4;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nv; i += (long)gridDim.x * 256) {
-      const float4 a = reinterpret_cast<const float4*>(xb)[i];
-      const float4 c = reinterpret_cast<const float4*>(yb)[i];
-      const float d0 = a.x - c.x, d1 = a.y - c.y, d2 = a.z - c.z, d3 = a.w - c.w;
-      sd += d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
-      sy += c.x * c.x + c.y * c.y + c.z * c.z + c.w * c.w;
-    }
-  } else {
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < per; i += (long)gridDim.x * 256) {
-      const float d = xb[i] - yb[i];
-      sd += d * d;
-      sy += yb[i] * yb[i];
-    }
-  }
-  sd = wave_sum(sd);
-  sy = wave_sum(sy);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { red[0][w] = sd; red[1][w] = sy; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    part[((long)b * gridDim.x + blockIdx.x) * 2] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-    part[((long)b * gridDim.x + blockIdx.x) * 2 + 1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-  }
-}
-
-// one block: stats[b] = (|x-y|, |y|), rel[b], loss = mean/sum
-__global__ void k_rel_l2_final(const float* __restrict__ part, int nblk, float* __restrict__ rel, float* __restrict__ loss,
-                               float* __restrict__ stats, int B, int size_average) {
-  __shared__ float red[256];
-  float acc = 0.f;
-  for (int b = threadIdx.x; b < B; b += blockDim.x) {
-    float sd = 0.f, sy = 0.f;
-    for (int j = 0; j < nblk; ++j) { sd += part[((long)b * nblk + j) * 2]; sy += part[((long)b * nblk + j) * 2 + 1]; }
-    const float dn = sqrtf(sd), yn = sqrtf(sy);
-    const float r = dn / (yn + 1e-8f);
-    stats[2 * b] = dn; stats[2 * b + 1] = yn;
-    if (rel) rel[b] = r;
-    acc += r;
-  }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = blockDim.x / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && loss) *loss = size_average ? red[0] / B : red[0];
-}
-
-__global__ __launch_bounds__(256) void k_rel_l2_bwd(const float* __restrict__ x, const float* __restrict__ y,
-                                                    const float* __restrict__ stats, const float* __restrict__ grad_loss,
-                                                    const float* __restrict__ grad_rel, float* __restrict__ gx, int B, long per,
-                                                    int size_average) {
-  const int b = blockIdx.y;
-  const float dn = stats[2 * b], yn = stats[2 * b + 1];
-  float gr = grad_rel ? grad_rel[b] : (size_average ? grad_loss[0] / B : grad_loss[0]);
-  const float coef = dn > 0.f ? gr / (dn * (yn + 1e-8f)) : 0.f;
-  const float* xb = x + (long)b * per;
-  const float* yb = y + (long)b * per;
-  float* gb = gx + (long)b * per;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < per; i += (long)gridDim.x * 256) gb[i] = coef * (xb[i] - yb[i]);
-}
-
 }  // namespace rpde
 
 using namespace rpde;
@@ -706,33 +629,6 @@ int rpde_weight_norm_bwd(const float* v, const float* g, const float* grad_w, fl
                          void* stream) {
   RPDE_CHECK_ARG(v && g && grad_w && (grad_v || grad_g) && out_f > 0 && in_f > 0, "weight_norm_bwd: bad arguments");
   hipLaunchKernelGGL(k_weight_norm_bwd, dim3((out_f + 3) / 4), dim3(256), 0, as_stream(stream), v, g, grad_w, grad_v, grad_g, out_f, in_f);
-  RPDE_LAUNCH_CHECK();
-  return RPDE_OK;
-}
-
-
-int rpde_rel_l2_fwd(const float* x, const float* y, float* rel, float* loss, float* stats, int B, int64_t per,
-                    int size_average, void* stream) {
-  RPDE_CHECK_ARG(x && y && stats && B > 0 && per > 0, "rel_l2_fwd: bad arguments");
-  hipStream_t st = as_stream(stream);
-  // partial sums live behind the stats the caller keeps: stats has 2*B floats,
-  // the partials need 2*B*L2_BLOCKS more -> caller allocates stats with
-  // rpde_rel_l2_stats_elems(B) floats.
-  float* part = stats + 2L * B;
-  hipLaunchKernelGGL(k_rel_l2_partial, dim3(L2_BLOCKS, B), dim3(256), 0, st, x, y, part, (long)per);
-  RPDE_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_rel_l2_final, dim3(1), dim3(256), 0, st, part, L2_BLOCKS, rel, loss, stats, B, size_average);
-  RPDE_LAUNCH_CHECK();
-  return RPDE_OK;
-}
-
-int64_t rpde_rel_l2_stats_elems(int B) { return 2L * B * (1 + L2_BLOCKS); }
-
-int rpde_rel_l2_bwd(const float* x, const float* y, const float* stats, const float* grad_loss, const float* grad_rel,
-                    float* grad_x, int B, int64_t per, int size_average, void* stream) {
-  RPDE_CHECK_ARG(x && y && stats && grad_x && (grad_loss || grad_rel), "rel_l2_bwd: bad arguments");
-  long nb = (per + 1023) / 1024; if (nb > 256) nb = 256; if (nb < 1) nb = 1;
-  hipLaunchKernelGGL(k_rel_l2_bwd, dim3((unsigned)nb, B), dim3(256), 0, as_stream(stream), x, y, stats, grad_loss, grad_rel, grad_x, B, (long)per, size_average);
   RPDE_LAUNCH_CHECK();
   return RPDE_OK;
 }

@@ -764,8 +764,24 @@ def to_channels_last(x):
 
 
 # ----------------------------------------------------------------------------
-# relative L2 loss
+# relative L2 loss; the three helpers serve the whole family (csrc/rel_loss.hip)
 # ----------------------------------------------------------------------------
+def _rel_outputs(B: int, device, reduction: bool, stats_elems: Optional[int] = None):
+    """(stats, rel, loss or None) of a relative loss: stats [2 B] unless the entry asks for more"""
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=device)          # noqa: E731
+    return new(stats_elems or 2 * B), new(B), new() if reduction else None
+
+
+def _upstream(g: torch.Tensor, reduction: bool):
+    """(grad_loss, grad_rel) for an entry's backward: the scalar's gradient, or the per-sample vector's"""
+    return (ptr(g), None) if reduction else (None, ptr(g))
+
+
+def _bcmn(x: torch.Tensor, dims: int):
+    """(B, C, M, N) of a channels-first field, M = 1 for dims = 1"""
+    return (x.shape[0], x.shape[1], 1, x.shape[2]) if dims == 1 else tuple(x.shape[:4])
+
+
 class _RelL2(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, y, size_average: bool, reduction: bool):
@@ -776,9 +792,7 @@ class _RelL2(torch.autograd.Function):
         per = x.numel() // B
         if y.numel() != x.numel():
             raise RuntimeError(f"RelativeL2Loss: shapes {tuple(x.shape)} and {tuple(y.shape)} differ in size")
-        stats = torch.empty(lib.rpde_rel_l2_stats_elems(B), dtype=torch.float32, device=x.device)
-        rel = torch.empty(B, dtype=torch.float32, device=x.device)
-        loss = torch.empty((), dtype=torch.float32, device=x.device) if reduction else None
+        stats, rel, loss = _rel_outputs(B, x.device, reduction, lib.rpde_rel_l2_stats_elems(B))
         check(lib.rpde_rel_l2_fwd(ptr(x), ptr(y), ptr(rel), ptr(loss), ptr(stats), B, per, int(size_average),
                                   stream_ptr()), "rel_l2_fwd")
         ctx.save_for_backward(x, y, stats)
@@ -792,9 +806,8 @@ class _RelL2(torch.autograd.Function):
         B, per, size_average, reduction = ctx.meta
         g = _f32c(g)
         gx = torch.empty_like(x)
-        check(lib.rpde_rel_l2_bwd(ptr(x), ptr(y), ptr(stats), ptr(g) if reduction else None,
-                                  None if reduction else ptr(g), ptr(gx), B, per, int(size_average), stream_ptr()),
-              "rel_l2_bwd")
+        check(lib.rpde_rel_l2_bwd(ptr(x), ptr(y), ptr(stats), *_upstream(g, reduction), ptr(gx), B, per, int(size_average),
+                                  stream_ptr()), "rel_l2_bwd")
         return gx, None, None, None
 
 
@@ -812,16 +825,13 @@ class _WRelL2(torch.autograd.Function):
         if x.dim() != dims + 2 or x.shape != y.shape:
             raise ValueError(f"weighted_relative_l2: x {tuple(x.shape)} / y {tuple(y.shape)}, expected equal "
                              f"{dims + 2}-D channels-first shapes")
-        B, Cc = x.shape[0], x.shape[1]
-        M, N = (1, x.shape[2]) if dims == 1 else (x.shape[2], x.shape[3])
+        B, Cc, M, N = _bcmn(x, dims)
         want = (N // 2 + 1,) if dims == 1 else (M, N // 2 + 1)
         if tuple(omega.shape) != want:
             raise ValueError(f"weighted_relative_l2: omega {tuple(omega.shape)}, expected {want} for the grid {tuple(x.shape[2:])}")
         x, y = _f32c(x), _f32c(y)
         px, py, pw = ptr(x), ptr(y), ptr(omega)               # raises for CPU tensors: there is no fallback
-        stats = torch.empty(2 * B, dtype=torch.float32, device=x.device)
-        rel = torch.empty(B, dtype=torch.float32, device=x.device)
-        loss = torch.empty((), dtype=torch.float32, device=x.device) if reduction else None
+        stats, rel, loss = _rel_outputs(B, x.device, reduction)
         spec = torch.empty(lib.rpde_wrel_l2_spec_elems(B, Cc, M, N), dtype=torch.float32, device=x.device)
         nws = lib.rpde_wrel_l2_ws_bytes(B, Cc, M, N)
         ws = workspace(nws, x.device)
@@ -840,9 +850,8 @@ class _WRelL2(torch.autograd.Function):
         gx = torch.empty(shape, dtype=torch.float32, device=spec.device)
         nws = lib.rpde_wrel_l2_ws_bytes(B, Cc, M, N)
         ws = workspace(nws, spec.device)
-        check(lib.rpde_wrel_l2_bwd(ptr(spec), ptr(omega), ptr(stats), ptr(g) if reduction else None,
-                                   None if reduction else ptr(g), ptr(gx), B, Cc, M, N, int(size_average),
-                                   ws.data_ptr(), nws, stream_ptr()), "wrel_l2_bwd")
+        check(lib.rpde_wrel_l2_bwd(ptr(spec), ptr(omega), ptr(stats), *_upstream(g, reduction), ptr(gx), B, Cc, M, N,
+                                   int(size_average), ws.data_ptr(), nws, stream_ptr()), "wrel_l2_bwd")
         return gx, None, None, None, None, None
 
 
@@ -1156,8 +1165,7 @@ class _BandEnergy(torch.autograd.Function):
                 raise ValueError(f"band_energy: x {tuple(x.shape)} / y {tuple(y.shape)} differ")
             y = _f32c(y)
             py = ptr(y)
-        B, Cc = x.shape[0], x.shape[1]
-        M, N = (1, x.shape[2]) if dims == 1 else (x.shape[2], x.shape[3])
+        B, Cc, M, N = _bcmn(x, dims)
         if T.band.device != x.device:
             raise ValueError(f"band_energy: band tables on {T.band.device}, x on {x.device}")
         nws = lib.rpde_band_energy_ws_bytes(B, Cc, M, N, T.J)
@@ -1591,9 +1599,7 @@ class _EtdResidual(torch.autograd.Function):
             raise ValueError(f"etd1d_residual: unsupported B={B} N={N} (N even, 4 .. 4096; 1 <= B <= 16383: four "
                              "fields of B images are one batch of the half-spectrum layer)")
         aff = _residual_affine(affine)
-        stats = torch.empty(2 * B, dtype=torch.float32, device=dev)
-        rel = torch.empty(B, dtype=torch.float32, device=dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev) if reduction else None
+        stats, rel, loss = _rel_outputs(B, dev, reduction)
         spec = torch.empty(lib.rpde_etd_residual_spec_elems(B, N), dtype=torch.float32, device=dev)
         ws = workspace(nws, dev)
         check(lib.rpde_etd_residual_fwd(pp, px, ptr(E), ptr(m0), ptr(m1), aff, ptr(rel), ptr(loss), ptr(stats), ptr(spec),
@@ -1612,8 +1618,8 @@ class _EtdResidual(torch.autograd.Function):
         nws = lib.rpde_etd_residual_ws_bytes(B, N)
         ws = workspace(nws, p2.device)
         check(lib.rpde_etd_residual_bwd(ptr(p2), ptr(spec), ptr(m1), _residual_affine(affine), ptr(stats),
-                                        ptr(g) if reduction else None, None if reduction else ptr(g), ptr(gp), B, N,
-                                        int(size_average), ws.data_ptr(), nws, stream_ptr()), "etd_residual_bwd")
+                                        *_upstream(g, reduction), ptr(gp), B, N, int(size_average), ws.data_ptr(), nws,
+                                        stream_ptr()), "etd_residual_bwd")
         return gp, None, None, None, None, None, None, None
 
 

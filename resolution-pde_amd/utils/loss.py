@@ -1,6 +1,7 @@
 """RelativeL2Loss (reference: utils/loss.py:17-59): per-sample
 |x - y|_2 / (|y|_2 + 1e-8), then mean / sum / none -- one fused HIP pass over
-prediction and target (wavefront-shuffle reductions, deterministic).
+prediction and target (wavefront-shuffle reductions, deterministic; csrc/rel_loss.hip, which also holds what the
+relative losses below share).
 
 SpectralRelativeL2Loss (no counterpart in the reference): the same ratio with a non-negative weight per Fourier
 mode -- the H^s / Sobolev relative loss of operator learning is the preset -- forward and backward on the device
@@ -72,7 +73,53 @@ def check_mode_weights(omega: torch.Tensor, spatial_shape) -> None:
                 raise ValueError(f"mode weights: column kx={kx} is not symmetric in ky (omega[ky] != omega[(H - ky) % H])")
 
 
-class SpectralRelativeL2Loss(nn.Module):
+class _GridTableLoss(nn.Module):
+    """A loss with tables built on the host per grid: the cache of their device forms per (grid, device), the guard of
+    an explicit table (it serves ONE grid), warm() for graph capture and the reduction of a per-sample vector.  A
+    subclass supplies _build(grid, device) and forward; `dims` is the rank of its grids."""
+
+    _explicit = None                  # the table given for one grid, if any, and the grid that took it
+    _explicit_grid = None
+    _explicit_kind = ""               # "weight" / "band", for the guard's message
+
+    def __init__(self, size_average=True, reduction=True):
+        super().__init__()
+        self.size_average = size_average
+        self.reduction = reduction
+        self._tables: dict = {}
+
+    def _table(self, grid, device):
+        key = (grid, torch.device(device))
+        t = self._tables.get(key)
+        if t is None:
+            if self._explicit is not None and self._explicit_grid not in (None, grid):
+                raise ValueError(f"{type(self).__name__}: the explicit {self._explicit_kind} table serves the grid "
+                                 f"{self._explicit_grid}, got {grid}")
+            t = self._tables[key] = self._build(grid, device)
+            if self._explicit is not None:
+                self._explicit_grid = grid
+        return t
+
+    def _bad_rank(self, grid) -> str:
+        return f"{type(self).__name__}.warm: grid {grid} for dims={self.dims}"
+
+    def warm(self, spatial_shape, device="cuda") -> None:
+        """plans, workspaces and the tables of one grid, outside any capture"""
+        grid = tuple(int(n) for n in spatial_shape)
+        if len(grid) != self.dims:
+            raise ValueError(self._bad_rank(grid))
+        z = torch.zeros((1, 1) + grid, dtype=torch.float32, device=device, requires_grad=True)
+        ones = torch.ones_like(z.detach())
+        (self(z, None, ones) if getattr(self, "takes_input", False) else self(z, ones)).sum().backward()
+        torch.cuda.synchronize(z.device)
+
+    def _reduce(self, v):
+        if not self.reduction:
+            return v
+        return v.mean() if self.size_average else v.sum()
+
+
+class SpectralRelativeL2Loss(_GridTableLoss):
     """rel[b] = sqrt(E(x - y)[b]) / (sqrt(E(y)[b]) + 1e-8) with E(z)[b] = sum_c sum_k omega_k c_kx / N |rfft(z)[b,c,k]|^2
     (rfft2 for dims=2; c_kx the Hermitian multiplicity of the half axis), then mean / sum / per-sample vector as
     RelativeL2Loss.  omega == 1 is RelativeL2Loss by Parseval.  x, y: channels-first fp32 tensors on the GPU.
@@ -84,8 +131,10 @@ class SpectralRelativeL2Loss(nn.Module):
     The first call at a grid builds the transform plans and the device table (allocation, one synchronisation);
     warm(spatial_shape, device) does that ahead of a hipGraph capture."""
 
+    _explicit_kind = "weight"
+
     def __init__(self, dims, weights="sobolev", s=1.0, length=1.0, size_average=True, reduction=True):
-        super().__init__()
+        super().__init__(size_average, reduction)
         if int(dims) not in (1, 2):
             raise ValueError(f"SpectralRelativeL2Loss: dims must be 1 or 2, got {dims}")
         self.dims = int(dims)
@@ -93,43 +142,21 @@ class SpectralRelativeL2Loss(nn.Module):
             if weights != "sobolev":
                 raise ValueError(f"SpectralRelativeL2Loss: unknown weights preset {weights!r} (presets: 'sobolev')")
             sobolev_weights((4,) * self.dims, s, length)          # validates s / length now
-            self._explicit = None
         elif torch.is_tensor(weights):
             if weights.dim() != self.dims:
                 raise ValueError(f"SpectralRelativeL2Loss: a {weights.dim()}-D weight table for dims={self.dims}")
             self._explicit = weights.detach()
-            self._explicit_grid = None
         else:
             raise ValueError("SpectralRelativeL2Loss: weights must be 'sobolev' or a tensor")
         self.s, self.length = float(s), length
-        self.size_average = size_average
-        self.reduction = reduction
-        self._tables: dict = {}
 
-    def _table(self, grid, device) -> torch.Tensor:
-        key = (grid, torch.device(device))
-        t = self._tables.get(key)
-        if t is None:
-            if self._explicit is None:
-                w = sobolev_weights(grid, self.s, self.length)
-            else:
-                w = self._explicit
-                if self._explicit_grid not in (None, grid):
-                    raise ValueError(f"SpectralRelativeL2Loss: the explicit weight table serves the grid "
-                                     f"{self._explicit_grid}, got {grid}")
-                check_mode_weights(w, grid)
-                self._explicit_grid = grid
-            t = self._tables[key] = w.to(device=device, dtype=torch.float32).contiguous()
-        return t
-
-    def warm(self, spatial_shape, device="cuda") -> None:
-        """plans, workspaces and the weight table of one grid, outside any capture"""
-        grid = tuple(int(n) for n in spatial_shape)
-        if len(grid) != self.dims:
-            raise ValueError(f"SpectralRelativeL2Loss.warm: grid {grid} for dims={self.dims}")
-        z = torch.zeros((1, 1) + grid, dtype=torch.float32, device=device, requires_grad=True)
-        ops.weighted_relative_l2(z, torch.ones_like(z), self._table(grid, z.device), self.dims, True, True).backward()
-        torch.cuda.synchronize(z.device)
+    def _build(self, grid, device) -> torch.Tensor:
+        if self._explicit is None:
+            w = sobolev_weights(grid, self.s, self.length)
+        else:
+            w = self._explicit
+            check_mode_weights(w, grid)
+        return w.to(device=device, dtype=torch.float32).contiguous()
 
     def forward(self, x, y):
         if x.dim() != self.dims + 2:
@@ -144,69 +171,41 @@ def _safe_sqrt(e: torch.Tensor) -> torch.Tensor:
     return torch.where(pos, torch.sqrt(torch.where(pos, e, torch.ones_like(e))), torch.zeros_like(e))
 
 
-class _BandedLoss(nn.Module):
+class _BandedLoss(_GridTableLoss):
     """What the two band losses share: the band table (a kind of rpde.ops.band_table built per grid, or one explicit
-    integer table [n//2+1] / [H, W//2+1] with values -1 .. J-1 for ONE grid), its device forms cached per
-    (grid, device), warm() for graph capture and the reduction of the per-sample vector."""
+    integer table [n//2+1] / [H, W//2+1] with values -1 .. J-1 for ONE grid) and the check of the fields' shapes."""
+
+    _explicit_kind = "band"
 
     def __init__(self, dims, bands="octave", num_bands=None, size_average=True, reduction=True):
-        super().__init__()
+        super().__init__(size_average, reduction)
         name = type(self).__name__
         if int(dims) not in (1, 2):
             raise ValueError(f"{name}: dims must be 1 or 2, got {dims}")
         self.dims = int(dims)
         if isinstance(bands, str):
             ops.band_table((8,) * self.dims, bands, num_bands)        # validates kind / num_bands / dims now
-            self._explicit = None
         elif torch.is_tensor(bands):
             if bands.dim() != self.dims or bands.is_floating_point():
                 raise ValueError(f"{name}: an explicit band table is an integer tensor with {self.dims} dimension(s)")
             self._explicit = bands.detach().cpu()
-            self._explicit_grid = None
             num_bands = int(num_bands) if num_bands is not None else max(int(self._explicit.max()), 0) + 1
         else:
             raise ValueError(f"{name}: bands must be one of {ops.BAND_KINDS} or an integer tensor")
         self.bands, self.num_bands = bands if isinstance(bands, str) else "explicit", num_bands
-        self.size_average = size_average
-        self.reduction = reduction
-        self._tables: dict = {}
 
-    def _table(self, grid, device) -> "ops.BandTables":
-        key = (grid, torch.device(device))
-        t = self._tables.get(key)
-        if t is None:
-            if self._explicit is None:
-                table, J = ops.band_table(grid, self.bands, self.num_bands)
-            else:
-                if self._explicit_grid not in (None, grid):
-                    raise ValueError(f"{type(self).__name__}: the explicit band table serves the grid "
-                                     f"{self._explicit_grid}, got {grid}")
-                table, J = self._explicit.reshape(1 if self.dims == 1 else grid[0], -1), self.num_bands
-            t = ops.band_tables(table, J, grid, device)
-            if self._explicit is not None:
-                self._explicit_grid = grid
-            self._tables[key] = t
-        return t
-
-    def warm(self, spatial_shape, device="cuda") -> None:
-        """plans, workspaces and the band tables of one grid, outside any capture"""
-        grid = tuple(int(n) for n in spatial_shape)
-        if len(grid) != self.dims:
-            raise ValueError(f"{type(self).__name__}.warm: grid {grid} for dims={self.dims}")
-        z = torch.zeros((1, 1) + grid, dtype=torch.float32, device=device, requires_grad=True)
-        self(z, torch.ones_like(z.detach())).sum().backward()
-        torch.cuda.synchronize(z.device)
+    def _build(self, grid, device) -> "ops.BandTables":
+        if self._explicit is None:
+            table, J = ops.band_table(grid, self.bands, self.num_bands)
+        else:
+            table, J = self._explicit.reshape(1 if self.dims == 1 else grid[0], -1), self.num_bands
+        return ops.band_tables(table, J, grid, device)
 
     def _tables_for(self, x, y):
         if x.dim() != self.dims + 2 or x.shape != y.shape:
             raise ValueError(f"{type(self).__name__}(dims={self.dims}): expected equal [B, C, *grid] shapes, got "
                              f"{tuple(x.shape)} / {tuple(y.shape)}")
         return self._table(tuple(int(n) for n in x.shape[2:]), x.device)
-
-    def _reduce(self, v):
-        if not self.reduction:
-            return v
-        return v.mean() if self.size_average else v.sum()
 
 
 class BandRelativeL2Loss(_BandedLoss):
@@ -257,7 +256,7 @@ class SpectrumMatchingLoss(_BandedLoss):
         return self._reduce(((torch.log(e_x + delta) - torch.log(e_y + delta)) ** 2).sum(1) / T.J_e)
 
 
-class EquationResidualLoss(nn.Module):
+class EquationResidualLoss(_GridTableLoss):
     """Does the prediction p ~ u(t + interval) follow from the input x = u(t) under
 
         u_t = L u - (advect/2) (u^2)_x,   l_n = c2 kappa_n^2 + c4 kappa_n^4 + i (c1 kappa_n + c3 kappa_n^3),  kappa_n = 2 pi n / length
@@ -277,24 +276,22 @@ class EquationResidualLoss(nn.Module):
     forward(pred, target, inp): the target is unused and may be None; pred, inp [B, N] or [B, 1, N] fp32 tensors on the
     GPU, gradient for pred only.  set_affine(pred=(a, b), inp=(a, b)): the residual is formed on a pred + b and a inp + b
     (fields a SimpleNormalizer encoded, penalised in physical units); the gradient is still with respect to pred.
-    Device tables are cached per (N, device), so one object serves mixed-resolution batches; warm((N,), device) builds
+    Device tables are cached per (grid, device), so one object serves mixed-resolution batches; warm((N,), device) builds
     them, the plans and the workspaces ahead of a hipGraph capture."""
 
     takes_input = True
+    dims = 1
 
     def __init__(self, length, interval, c1=0.0, c2=0.0, c3=0.0, c4=0.0, advect=1.0, dealias=True, size_average=True,
                  reduction=True):
-        super().__init__()
+        super().__init__(size_average, reduction)
         vals = [float(v) for v in (length, interval, c1, c2, c3, c4, advect)]
         if not all(math.isfinite(v) for v in vals) or not (vals[0] > 0 and vals[1] > 0):
             raise ValueError(f"EquationResidualLoss: length {length} and interval {interval} must be positive and every "
                              "coefficient finite")
         self.length, self.interval, self.c1, self.c2, self.c3, self.c4, self.advect = vals
         self.dealias = bool(dealias)
-        self.size_average = size_average
-        self.reduction = reduction
         self._affine = None
-        self._tables: dict = {}
 
     @classmethod
     def burgers(cls, nu_eff, length, interval, **kw):
@@ -318,29 +315,19 @@ class EquationResidualLoss(nn.Module):
             raise ValueError(f"EquationResidualLoss.set_affine: {pred} / {inp}")
         self._affine = None if aff == (1.0, 0.0, 1.0, 0.0) else aff
 
-    def _table(self, N, device):
-        key = (int(N), torch.device(device))
-        t = self._tables.get(key)
-        if t is None:
-            host = ops.etd1d_residual_tables(int(N), self.length, self.c1, self.c2, self.c3, self.c4, self.interval,
-                                             self.advect, self.dealias)
-            t = self._tables[key] = tuple(h.to(device).contiguous() for h in host)
-        return t
+    def _build(self, grid, device):
+        host = ops.etd1d_residual_tables(grid[0], self.length, self.c1, self.c2, self.c3, self.c4, self.interval,
+                                         self.advect, self.dealias)
+        return tuple(h.to(device).contiguous() for h in host)
 
-    def warm(self, spatial_shape, device="cuda") -> None:
-        """plans, workspaces and the tables of one grid, outside any capture"""
-        grid = tuple(int(n) for n in spatial_shape)
-        if len(grid) != 1:
-            raise ValueError(f"EquationResidualLoss.warm: grid {grid}, the equation is one-dimensional")
-        z = torch.zeros((1, 1) + grid, dtype=torch.float32, device=device, requires_grad=True)
-        self(z, None, torch.ones_like(z.detach())).sum().backward()
-        torch.cuda.synchronize(z.device)
+    def _bad_rank(self, grid) -> str:
+        return f"EquationResidualLoss.warm: grid {grid}, the equation is one-dimensional"
 
     def forward(self, pred, target, inp):
         if inp is None:
             raise ValueError("EquationResidualLoss: the network's input is needed next to its prediction")
-        return ops.etd1d_residual(pred, inp, self._table(pred.shape[-1], pred.device), self._affine, self.size_average,
-                                  self.reduction)
+        return ops.etd1d_residual(pred, inp, self._table((int(pred.shape[-1]),), pred.device), self._affine,
+                                  self.size_average, self.reduction)
 
 
 class SumLoss(nn.Module):

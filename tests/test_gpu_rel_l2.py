@@ -1,4 +1,4 @@
-"""RelativeL2Loss / ops.relative_l2 (csrc/pointwise.hip: k_rel_l2_partial, k_rel_l2_final, k_rel_l2_bwd) against float64
+"""RelativeL2Loss / ops.relative_l2 (csrc/rel_loss.hip: k_rel_l2_partial, k_rel_l2_final, k_rel_l2_bwd) against float64
 on the same fp32 inputs:
 
     rel_b = |x - y| / (|y| + 1e-8),    d loss / d x_b = g_b (x - y) / (|x - y| (|y| + 1e-8)),  0 where x == y,
