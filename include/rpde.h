@@ -153,7 +153,8 @@ int rpde_fspectral2d_bwd(const float* grad_out, const float* spec_y, const float
                          void* ws, size_t ws_bytes, void* stream);
 /* The same for FSpectralConv2d.forward_fourier in evaluation: rpde_fspectral2d_prep_bytes (0: nothing to prepare for
  * this shape, use rpde_fspectral2d_fwd) bytes hold the mode-mix weight fragments of both axes; the forward then needs
- * rpde_fspectral2d_eval_ws_bytes of workspace (the spectra live there: nothing is saved for a backward). */
+ * rpde_fspectral2d_eval_ws_bytes of workspace (the spectra live there: nothing is saved for a backward; 0 where
+ * rpde_fspectral2d_prep_bytes is 0). */
 size_t rpde_fspectral2d_prep_bytes(int M, int N, int C, int K);
 size_t rpde_fspectral2d_eval_ws_bytes(int B, int M, int N, int C, int K);
 int rpde_fspectral2d_prepare(const float* w_y, const float* w_x, int M, int N, int C, int K,

@@ -101,12 +101,23 @@ size_t rpde_band_energy_spec_elems(int B, int C, int M, int N) {
   return be_dims_ok(B, C, M, N, 1) ? hs_elems(hs_geom(B * C, M, N)) : 0;
 }
 
+// forward: the difference, the spectrum when it is not kept, the row spectra, the partial sums (doubles)
+struct BeFwdWork {
+  float *d, *s0, *s1; double* part;
+  BeFwdWork(Arena& ar, const BeGeom& g)
+      : d(ar.take((size_t)g.images * g.M * g.N)), s0(ar.take(hs_elems(g))), s1(ar.take(hs_elems(g))),
+        part(reinterpret_cast<double*>(ar.take((size_t)2 * g.B * g.J * g.S))) {}
+};
+// backward: the scaled spectrum and the row spectra
+struct BeBwdWork {
+  float *w, *t1;
+  BeBwdWork(Arena& ar, const BeGeom& g) : w(ar.take(hs_elems(g))), t1(ar.take(hs_elems(g))) {}
+};
+
 size_t rpde_band_energy_ws_bytes(int B, int C, int M, int N, int J) {
   if (!be_dims_ok(B, C, M, N, J)) return 0;
   const BeGeom g = be_geom(B, C, M, N, J);
-  // forward: the difference, the spectrum when it is not kept, the row spectra, the partial sums (doubles); the backward
-  // needs the two spectra only
-  return arena_bytes((size_t)B * C * M * N) + 2 * arena_bytes(hs_elems(g)) + arena_bytes((size_t)2 * B * J * g.S);
+  return ws_max(ws_measure<BeFwdWork>(g), ws_measure<BeBwdWork>(g));
 }
 
 int rpde_band_energy_fwd(const float* x, const float* y, const int32_t* entries, const int32_t* start, int n_entries,
@@ -120,25 +131,19 @@ int rpde_band_energy_fwd(const float* x, const float* y, const int32_t* entries,
                  n_entries, M, N / 2 + 1);
   HS_CHECK_WS("band_energy_fwd", ws);
   const BeGeom g = be_geom(B, C, M, N, J);
-  const size_t ns = hs_elems(g);
-  Arena ar(ws, ws_bytes);
-  float* d = ar.take((size_t)g.images * M * N);
-  float* s0 = ar.take(ns);
-  float* s1 = ar.take(ns);
-  double* part = reinterpret_cast<double*>(ar.take((size_t)2 * B * J * g.S));
-  if (!ar.ok()) { set_error("band_energy_fwd: workspace too small"); return RPDE_ERR_WORKSPACE; }
+  RPDE_CARVE("band_energy_fwd", BeFwdWork, w, ws, ws_bytes, g);
   hipStream_t st = as_stream(stream);
-  float* sp = spec ? spec : s0;
+  float* sp = spec ? spec : w.s0;
   const float* z = x;
   if (y) {
-    RPDE_TRY(rel_diff(x, y, d, (long)g.images * M * N, st));
-    z = d;
+    RPDE_TRY(rel_diff(x, y, w.d, (long)g.images * M * N, st));
+    z = w.d;
   }
-  RPDE_TRY(hs_rfft(g, z, s1, sp, st));
+  RPDE_TRY(hs_rfft(g, z, w.s1, sp, st));
   const unsigned nb = (unsigned)(B < 65535 ? B : 65535);
-  hipLaunchKernelGGL(k_be_partial, dim3((J + 3) / 4, g.S, nb), dim3(256), 0, st, sp, entries, start, n_entries, part, g);
+  hipLaunchKernelGGL(k_be_partial, dim3((J + 3) / 4, g.S, nb), dim3(256), 0, st, sp, entries, start, n_entries, w.part, g);
   RPDE_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_be_final, dim3(hs_blocks((long)B * J, 1024)), dim3(256), 0, st, part, E, g);
+  hipLaunchKernelGGL(k_be_final, dim3(hs_blocks((long)B * J, 1024)), dim3(256), 0, st, w.part, E, g);
   RPDE_LAUNCH_CHECK();
   return RPDE_OK;
 }
@@ -152,18 +157,14 @@ int rpde_band_energy_bwd(const float* spec, const int32_t* band, const float* gE
   RPDE_CHECK_ARG(al16(spec) && al16(band), "band_energy_bwd: the spectrum and the band table must be 16-byte aligned");
   HS_CHECK_WS("band_energy_bwd", ws);
   const BeGeom g = be_geom(B, C, M, N, J);
-  const size_t ns = hs_elems(g);
-  Arena ar(ws, ws_bytes);
-  float* w = ar.take(ns);
-  float* t1 = ar.take(ns);
-  if (!ar.ok()) { set_error("band_energy_bwd: workspace too small"); return RPDE_ERR_WORKSPACE; }
+  RPDE_CARVE("band_energy_bwd", BeBwdWork, w, ws, ws_bytes, g);
   hipStream_t st = as_stream(stream);
   const long groups = (long)hs_per(g) / 4;
   const int blk = hs_block(groups);
-  hipLaunchKernelGGL(k_be_scale, hs_grid(groups, g.images < 65535 ? g.images : 65535, blk), dim3(blk), 0, st, spec, band, gE, w,
+  hipLaunchKernelGGL(k_be_scale, hs_grid(groups, g.images < 65535 ? g.images : 65535, blk), dim3(blk), 0, st, spec, band, gE, w.w,
                      g);
   RPDE_LAUNCH_CHECK();
-  return hs_irfft(g, w, t1, grad_x, st);
+  return hs_irfft(g, w.w, w.t1, grad_x, st);
 }
 
 }  // extern "C"

@@ -310,14 +310,22 @@ using namespace rpde;
 
 extern "C" {
 
-size_t rpde_darcy2d_ws_bytes(int B, int s) {
-  if (!darcy_dims_ok(B, s)) return 0;
-  const size_t phys = (size_t)B * s * s, nblk = hs_grid((long)s * (s / 4), B).x;
-  // r, p, Ap, z, the low part of u, the transform's intermediate and the spectrum; three sets of per-block partials
-  // (doubles); two state records
-  return 7 * arena_bytes(phys) + 3 * arena_bytes(2 * (size_t)B * nblk) +
-         2 * arena_bytes((size_t)B * sizeof(DarcyState) / sizeof(float));
-}
+// rpde_darcy2d_solve: r, p, Ap, z, the low part of u, the transform's intermediate and the spectrum; three sets of
+// per-block partials (doubles); two state records.  rpde_sep2d needs one field, which fits the first
+struct DarcyWork {
+  float *r, *p, *Ap, *z, *ul, *tmp, *rh; double *pap, *rr, *rz; DarcyState *s0, *s1;
+  DarcyWork(Arena& ar, int B, int s) {
+    const size_t phys = (size_t)B * s * s, nblk = hs_grid((long)s * (s / 4), B).x;
+    const auto state = [&] { return reinterpret_cast<DarcyState*>(ar.take((size_t)B * sizeof(DarcyState) / sizeof(float))); };
+    const auto partials = [&] { return reinterpret_cast<double*>(ar.take(2 * B * nblk)); };
+    r = ar.take(phys); p = ar.take(phys); Ap = ar.take(phys); z = ar.take(phys);
+    ul = ar.take(phys); tmp = ar.take(phys); rh = ar.take(phys);
+    pap = partials(); rr = partials(); rz = partials();
+    s0 = state(); s1 = state();
+  }
+};
+
+size_t rpde_darcy2d_ws_bytes(int B, int s) { return darcy_dims_ok(B, s) ? ws_measure<DarcyWork>(B, s) : 0; }
 
 int rpde_darcy2d_apply(const float* a, const float* u, float* Au, int B, int s, void* stream) {
   RPDE_CHECK_ARG(a && u && Au, "darcy2d_apply: null pointer");
@@ -337,7 +345,7 @@ int rpde_sep2d(const float* in, const float* L, const float* R, float* out, int 
   RPDE_CHECK_ARG(al16(in) && al16(L) && al16(R) && al16(out), "sep2d: pointers must be 16-byte aligned");
   Arena ar(ws, ws_bytes);
   float* tmp = ar.take((size_t)B * s * s);
-  if (!ar.ok()) { set_error("sep2d: workspace too small (%zu bytes, needs %zu)", ws_bytes, arena_bytes((size_t)B * s * s)); return RPDE_ERR_WORKSPACE; }
+  RPDE_CLAIM_WS("sep2d", ar, ws_bytes);
   return sep2d(in, L, false, R, false, tmp, out, B, s, as_stream(stream));
 }
 
@@ -351,26 +359,12 @@ int rpde_darcy2d_solve(const float* a, const float* f, int f_batched, const floa
   RPDE_CHECK_ARG(tol >= 0.f && tol < INFINITY, "darcy2d_solve: tol must be finite and >= 0");
   RPDE_CHECK_ARG(al16(a) && al16(f) && al16(S) && al16(inv_lambda) && al16(u),
                  "darcy2d_solve: fields and tables must be 16-byte aligned");
-  const size_t phys = (size_t)B * s * s;
   const dim3 grid = hs_grid((long)s * (s / 4), B);
   const size_t nblk = grid.x;
-  Arena ar(ws, ws_bytes);
-  float* r = ar.take(phys);
-  float* p = ar.take(phys);
-  float* Ap = ar.take(phys);
-  float* z = ar.take(phys);
-  float* ul = ar.take(phys);
-  float* tmp = ar.take(phys);
-  float* rh = ar.take(phys);
-  double* pap = reinterpret_cast<double*>(ar.take(2 * B * nblk));
-  double* rr = reinterpret_cast<double*>(ar.take(2 * B * nblk));
-  double* rz = reinterpret_cast<double*>(ar.take(2 * B * nblk));
-  DarcyState* s0 = reinterpret_cast<DarcyState*>(ar.take((size_t)B * sizeof(DarcyState) / sizeof(float)));
-  DarcyState* s1 = reinterpret_cast<DarcyState*>(ar.take((size_t)B * sizeof(DarcyState) / sizeof(float)));
-  if (!ar.ok()) {
-    set_error("darcy2d_solve: workspace too small (%zu bytes, needs %zu)", ws_bytes, rpde_darcy2d_ws_bytes(B, s));
-    return RPDE_ERR_WORKSPACE;
-  }
+  RPDE_CARVE("darcy2d_solve", DarcyWork, w, ws, ws_bytes, B, s);
+  float *r = w.r, *p = w.p, *Ap = w.Ap, *z = w.z, *ul = w.ul, *tmp = w.tmp, *rh = w.rh;
+  double *pap = w.pap, *rr = w.rr, *rz = w.rz;
+  DarcyState *s0 = w.s0, *s1 = w.s1;
   hipStream_t st = as_stream(stream);
   const dim3 blk(256);
   const long fstride = f_batched ? (long)s * s : 0;

@@ -205,6 +205,14 @@ __global__ __launch_bounds__(256) void k_etd_square(float* __restrict__ p, long 
   }
 }
 
+// rpde_etd1d_steps: Nv, a, the running sum, b / c and the product spectrum, and the field (the rfft / irfft calls need
+// none)
+struct EtdWork {
+  float *nv, *a, *sum, *bc, *F, *P;
+  EtdWork(Arena& ar, size_t spec, size_t phys)
+      : nv(ar.take(spec)), a(ar.take(spec)), sum(ar.take(spec)), bc(ar.take(spec)), F(ar.take(spec)), P(ar.take(phys)) {}
+};
+
 // rpde_etd1d_steps (CX = false: seven real tables [kp]) and rpde_etd1d_steps_cx (six complex tables [re|im][kp] and
 // the real g): the same checks, workspace and sixteen launches per step, the stage kernels of the table kind
 template <bool CX>
@@ -218,17 +226,10 @@ static int etd1d_steps(float* U, const EtdTables& t, int B, int N, int nsteps, v
   RPDE_CHECK_ARG(al16(U) && al16(t.E) && al16(t.E2) && al16(t.Q) && al16(t.f1) && al16(t.f2) && al16(t.f3) && al16(t.g),
                  "%s: state and tables must be 16-byte aligned", what);
   const HalfSpec geo = hs_geom(B, 1, N);
-  const size_t spec = hs_elems(geo), phys = (size_t)B * N;
-  Arena ar(ws, ws_bytes);
-  EtdBufs u;
-  u.v = U;
-  u.nv = ar.take(spec);
-  u.a = ar.take(spec);
-  u.sum = ar.take(spec);
-  u.bc = ar.take(spec);
-  float* F = ar.take(spec);
-  float* P = ar.take(phys);
-  if (!ar.ok()) { set_error("%s: workspace too small", what); return RPDE_ERR_WORKSPACE; }
+  const size_t phys = (size_t)B * N;
+  RPDE_CARVE(what, EtdWork, w, ws, ws_bytes, hs_elems(geo), phys);
+  const EtdBufs u{U, w.nv, w.a, w.sum, w.bc};
+  float *F = w.F, *P = w.P;
   if (nsteps == 0) return RPDE_OK;
   hipStream_t st = as_stream(stream);
   // a wave per image of at most 64 groups (N <= 510), 256 threads otherwise
@@ -266,11 +267,7 @@ extern "C" {
 
 size_t rpde_etd1d_spec_elems(int B, int N) { return hs_dims_ok(B, 1, N) ? hs_elems(hs_geom(B, 1, N)) : 0; }
 
-size_t rpde_etd1d_ws_bytes(int B, int N) {
-  if (!hs_dims_ok(B, 1, N)) return 0;
-  // rpde_etd1d_steps: Nv, a, the running sum, b / c and the product spectrum, and the field (the rfft / irfft calls need none)
-  return 5 * arena_bytes(hs_elems(hs_geom(B, 1, N))) + arena_bytes((size_t)B * N);
-}
+size_t rpde_etd1d_ws_bytes(int B, int N) { return hs_dims_ok(B, 1, N) ? ws_measure<EtdWork>(hs_elems(hs_geom(B, 1, N)), (size_t)B * N) : 0; }
 
 int rpde_etd1d_steps(float* U, const float* E, const float* E2, const float* Q, const float* f1, const float* f2,
                      const float* f3, const float* g, int B, int N, int nsteps, void* ws, size_t ws_bytes, void* stream) {

@@ -165,13 +165,20 @@ extern "C" {
 
 size_t rpde_etd_residual_spec_elems(int B, int N) { return res_dims_ok(B, N) ? hs_elems(hs_geom(B, 1, N)) : 0; }
 
+// forward: the roots of unity and the partial sums (doubles both)
+struct ResFwdWork {
+  double2* tw; double* part;
+  ResFwdWork(Arena& ar, int B, int N)
+      : tw(reinterpret_cast<double2*>(ar.take((size_t)4 * N))), part(reinterpret_cast<double*>(ar.take((size_t)2 * 2 * B * RES_SLOTS))) {}
+};
+// backward: two spectra and two fields
+struct ResBwdWork {
+  float *s2, *rs;
+  ResBwdWork(Arena& ar, int B, int N) : s2(ar.take(hs_elems(hs_geom(2 * B, 1, N)))), rs(ar.take((size_t)2 * B * N)) {}
+};
+
 size_t rpde_etd_residual_ws_bytes(int B, int N) {
-  if (!res_dims_ok(B, N)) return 0;
-  const size_t spec = hs_elems(hs_geom(B, 1, N)), phys = (size_t)B * N;
-  // forward: the roots of unity and the partial sums (doubles both); backward: two spectra and two fields
-  const size_t fwd = arena_bytes((size_t)4 * N) + arena_bytes((size_t)2 * 2 * B * RES_SLOTS);
-  const size_t bwd = arena_bytes(2 * spec) + arena_bytes(2 * phys);
-  return fwd > bwd ? fwd : bwd;
+  return res_dims_ok(B, N) ? ws_max(ws_measure<ResFwdWork>(B, N), ws_measure<ResBwdWork>(B, N)) : 0;
 }
 
 int rpde_etd_residual_fwd(const float* p, const float* x, const float* E, const float* m0, const float* m1,
@@ -182,18 +189,15 @@ int rpde_etd_residual_fwd(const float* p, const float* x, const float* E, const 
   HS_CHECK_WS("etd_residual_fwd", ws);
   RPDE_CHECK_ARG(al16(E) && al16(m0) && al16(m1) && al16(spec_r), "etd_residual_fwd: tables and spec_r must be 16-byte aligned");
   const ResGeom g{hs_geom(B, 1, N), B};
-  Arena ar(ws, ws_bytes);
-  double2* tw = reinterpret_cast<double2*>(ar.take((size_t)4 * N));
-  double* part = reinterpret_cast<double*>(ar.take((size_t)2 * 2 * B * RES_SLOTS));
-  if (!ar.ok()) { set_error("etd_residual_fwd: workspace too small"); return RPDE_ERR_WORKSPACE; }
+  RPDE_CARVE("etd_residual_fwd", ResFwdWork, w, ws, ws_bytes, B, N);
   // a wave per image of at most 64 columns (N <= 120), RES_BLOCK threads otherwise; the blocks of an image are its slots
   const dim3 sb(g.kp <= 64 ? 64 : RES_BLOCK), sg((g.kp + sb.x - 1) / sb.x, B);
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(k_res_twiddle, dim3((N + 255) / 256), dim3(256), 0, st, tw, N);
+  hipLaunchKernelGGL(k_res_twiddle, dim3((N + 255) / 256), dim3(256), 0, st, w.tw, N);
   RPDE_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_res_spectrum, sg, sb, 0, st, p, x, tw, E, m0, m1, spec_r, part, g, res_affine(affine));
+  hipLaunchKernelGGL(k_res_spectrum, sg, sb, 0, st, p, x, w.tw, E, m0, m1, spec_r, w.part, g, res_affine(affine));
   RPDE_LAUNCH_CHECK();
-  return rel_final(part, rel, loss, stats, B, (int)sg.x, 1.0 / (double)N, size_average, st);
+  return rel_final(w.part, rel, loss, stats, B, (int)sg.x, 1.0 / (double)N, size_average, st);
 }
 
 int rpde_etd_residual_bwd(const float* p, const float* spec_r, const float* m1, const float* affine, const float* stats,
@@ -205,18 +209,14 @@ int rpde_etd_residual_bwd(const float* p, const float* spec_r, const float* m1, 
   RPDE_CHECK_ARG(al16(m1) && al16(spec_r), "etd_residual_bwd: tables and spec_r must be 16-byte aligned");
   const ResGeom g{hs_geom(B, 1, N), B};
   const HalfSpec g2 = hs_geom(2 * B, 1, N);
-  const size_t phys = (size_t)B * N;
-  Arena ar(ws, ws_bytes);
-  float* s2 = ar.take(hs_elems(g2));
-  float* rs = ar.take(2 * phys);
-  if (!ar.ok()) { set_error("etd_residual_bwd: workspace too small"); return RPDE_ERR_WORKSPACE; }
+  RPDE_CARVE("etd_residual_bwd", ResBwdWork, w, ws, ws_bytes, B, N);
   hipStream_t st = as_stream(stream);
   const dim3 sb(hs_block(g.kp / 4)), sg = hs_grid(g.kp / 4, B, sb.x);
-  hipLaunchKernelGGL(k_res_fan, sg, sb, 0, st, spec_r, m1, s2, g);
+  hipLaunchKernelGGL(k_res_fan, sg, sb, 0, st, spec_r, m1, w.s2, g);
   RPDE_LAUNCH_CHECK();
-  RPDE_TRY(hs_irfft(g2, s2, nullptr, rs, st));
+  RPDE_TRY(hs_irfft(g2, w.s2, nullptr, w.rs, st));
   const int vec = N % 4 == 0 && al16(p) && al16(grad_p);
-  hipLaunchKernelGGL(k_res_grad, hs_grid(vec ? N / 4 : N, B), dim3(256), 0, st, p, rs, stats, grad_loss, grad_rel, grad_p, B, N,
+  hipLaunchKernelGGL(k_res_grad, hs_grid(vec ? N / 4 : N, B), dim3(256), 0, st, p, w.rs, stats, grad_loss, grad_rel, grad_p, B, N,
                      vec, size_average, res_affine(affine));
   RPDE_LAUNCH_CHECK();
   return RPDE_OK;

@@ -140,6 +140,50 @@ static size_t wgrad_ws_floats(long P, int in_f, int out_f) {
   return a;
 }
 
+// the shape of a FeedForward alone, for the queries
+static rpde_ff_params ff_dims(int dim, int factor, int n_layers) {
+  rpde_ff_params q;
+  memset(&q, 0, sizeof(q));
+  q.dim = dim; q.factor = factor; q.n_layers = n_layers;
+  return q;
+}
+static int ff_hid(const rpde_ff_params& q) { return q.n_layers > 1 ? q.dim * q.factor : q.dim; }
+
+// The backward: two hidden-sized buffers; per layer its own weight-gradient slabs, column-sum slabs and weight image,
+// so that the folds and the splits of the whole pass are one launch each (FoldJobs, SplitJobs) -- the regions of layer 0
+// are followed by the others', so the fused path may use them as one region of the largest layer's size; the column-sum
+// and tail scratch; `fused`: + dz3, the per-workgroup sums and the weight fragments of the fused kernel
+struct FfBwdWork {
+  float *buf0, *buf1, *small, *tailws, *dz3 = nullptr, *part = nullptr;
+  void* fimg = nullptr;
+  std::vector<float*> slabs, csum, wt;
+  FfBwdWork(Arena& ar, const rpde_ff_params& q, long P, bool fused) {
+    const int L = q.n_layers > 0 ? q.n_layers : 0, hid = ff_hid(q);
+    slabs.resize(L); csum.resize(L); wt.resize(L);
+    buf0 = ar.take((size_t)P * hid);
+    buf1 = ar.take((size_t)P * hid);
+    for (int l = 0; l < L; ++l) slabs[l] = ar.take(wgrad_ws_floats(P, ff_in(&q, l), ff_out(&q, l)));
+    for (int l = 0; l < L; ++l) csum[l] = ar.take((size_t)(colsum_tiles(P) + REDUCE_CHUNKS) * hid);
+    for (int l = 0; l < L; ++l) wt[l] = ar.take(ff_wimg_floats(hid));
+    small = ar.take(colsum_ws_floats(P, hid));
+    tailws = ar.take(ff_tail_bwd_ws_floats(P, q.dim));
+    if (!fused) return;
+    dz3 = ar.take((size_t)P * q.dim);
+    part = ar.take(ff3_fused_bwd_part_floats());
+    fimg = ar.take(ff3_fused_ws_floats());
+  }
+};
+// the forward's optional scratch on the GEMM path: `n` split weight images
+struct FfFwdImgs {
+  std::vector<float*> wimg;
+  FfFwdImgs(Arena& ar, const rpde_ff_params& q, int n) : wimg(n > 0 ? n : 0) { for (float*& w : wimg) w = ar.take(ff_wimg_floats(ff_hid(q))); }
+};
+// the weight fragments of the fused kernel: the fused forward's scratch, and the whole of a prepared buffer
+struct FfFusedImg {
+  void* img;
+  explicit FfFusedImg(Arena& ar) : img(ar.take(ff3_fused_ws_floats())) {}
+};
+
 }  // namespace rpde
 
 using namespace rpde;
@@ -147,36 +191,19 @@ using namespace rpde;
 extern "C" {
 
 // ------------------------------ FeedForward --------------------------------
-// backward workspace of the GEMM path: every layer has its own weight-gradient slabs, column-sum slabs and weight
-// images, so that the folds and the splits of the whole pass are one launch each (FoldJobs, SplitJobs)
 size_t rpde_feedforward_ws_bytes(int64_t P, int dim, int factor, int n_layers) {
-  const int hid = n_layers > 1 ? dim * factor : dim;
-  size_t n = 2 * arena_bytes((size_t)P * hid);
-  for (int l = 0; l < n_layers; ++l) {
-    const int i = l == 0 ? dim : dim * factor, o = l == n_layers - 1 ? dim : dim * factor;
-    n += arena_bytes(wgrad_ws_floats(P, i, o));
-    n += arena_bytes((size_t)(colsum_tiles(P) + REDUCE_CHUNKS) * hid);
-    n += arena_bytes(ff_wimg_floats(hid));
-  }
-  n += arena_bytes(colsum_ws_floats(P, hid)) + arena_bytes(ff_tail_bwd_ws_floats(P, dim));
-  rpde_ff_params q;
-  memset(&q, 0, sizeof(q));
-  q.dim = dim; q.factor = factor; q.n_layers = n_layers;
-  if (ff3_fused_ok(&q, (long)P))           // + dz3, the per-workgroup sums, the weight fragments of the fused kernel
-    n += arena_bytes((size_t)P * dim) + arena_bytes(ff3_fused_bwd_part_floats()) + arena_bytes(ff3_fused_ws_floats());
-  return n;
+  const rpde_ff_params q = ff_dims(dim, factor, n_layers);
+  const size_t general = ws_measure<FfBwdWork>(q, (long)P, false);
+  return ff3_fused_ok(&q, (long)P) ? ws_max(general, ws_measure<FfBwdWork>(q, (long)P, true)) : general;
 }
 
 size_t rpde_feedforward_fwd_ws_bytes(int dim, int factor, int n_layers) {
-  const size_t a = (size_t)n_layers * arena_bytes(ff_wimg_floats(n_layers > 1 ? dim * factor : dim)), b = arena_bytes(ff3_fused_ws_floats());
-  return a > b ? a : b;
+  return ws_max(ws_measure<FfFwdImgs>(ff_dims(dim, factor, n_layers), n_layers), ws_measure<FfFusedImg>());
 }
 
 // 1 when rpde_feedforward_fwd runs this shape as one fused kernel that needs no hidden buffers in evaluation
 int rpde_feedforward_is_fused(int dim, int factor, int n_layers, int64_t P) {
-  rpde_ff_params q;
-  memset(&q, 0, sizeof(q));
-  q.dim = dim; q.factor = factor; q.n_layers = n_layers;
+  const rpde_ff_params q = ff_dims(dim, factor, n_layers);
   return ff3_fused_ok(&q, (long)P) ? 1 : 0;
 }
 
@@ -184,19 +211,23 @@ int rpde_feedforward_is_fused(int dim, int factor, int n_layers, int64_t P) {
 // and reused by every call until the weights change (rpde.ops.frozen_weights owns that promise) ----
 int rpde_feedforward_prepare(const rpde_ff_params* p, void* prep, size_t prep_bytes, void* stream) {
   RPDE_CHECK_ARG(p && prep, "feedforward_prepare: bad arguments");
-  RPDE_CHECK_ARG(ff3_fused_ok(p, 32) && prep_bytes >= arena_bytes(ff3_fused_ws_floats()), "feedforward_prepare: shape not fused or buffer too small");
+  Arena ar(prep, prep_bytes);
+  const FfFusedImg f(ar);
+  RPDE_CHECK_ARG(ff3_fused_ok(p, 32) && ar.ok(), "feedforward_prepare: shape not fused or buffer too small");
   RPDE_CHECK_ARG(p->weights && p->weights[0] && p->weights[1] && p->weights[2], "feedforward_prepare: null weights");
-  return ff3_fused_prepare(p, prep, as_stream(stream));
+  return ff3_fused_prepare(p, f.img, as_stream(stream));
 }
 
 int rpde_feedforward_fwd_prepared(const rpde_ff_params* p, const float* x, const float* residual, float* out, int64_t P,
                                   const void* prep, size_t prep_bytes, void* stream) {
   RPDE_CHECK_ARG(p && x && out && prep && P > 0 && P < (1L << 31), "feedforward_fwd_prepared: bad arguments");
-  RPDE_CHECK_ARG(ff3_fused_ok(p, P) && prep_bytes >= arena_bytes(ff3_fused_ws_floats()), "feedforward_fwd_prepared: shape not fused");
+  Arena ar(const_cast<void*>(prep), prep_bytes);
+  const FfFusedImg f(ar);
+  RPDE_CHECK_ARG(ff3_fused_ok(p, P) && ar.ok(), "feedforward_fwd_prepared: shape not fused");
   RPDE_CHECK_ARG(!p->layer_norm || (p->ln_gamma && p->ln_beta), "feedforward_fwd_prepared: layer_norm needs gamma/beta");
   RPDE_CHECK_ARG(p->dropout_p == 0.f, "feedforward_fwd_prepared: evaluation only");
   return ff3_fused_fwd(p, x, residual, nullptr, nullptr, out /* z_last is not written in evaluation */, out, P,
-                       const_cast<void*>(prep), as_stream(stream), true);
+                       f.img, as_stream(stream), true);
 }
 
 int rpde_feedforward_fwd(const rpde_ff_params* p, const float* x, const float* residual, float* const* hs,
@@ -206,25 +237,24 @@ int rpde_feedforward_fwd(const rpde_ff_params* p, const float* x, const float* r
   RPDE_CHECK_ARG(P < (1L << 31), "feedforward_fwd: too many points for one call");
   RPDE_CHECK_ARG(p->dropout_p >= 0.f && p->dropout_p < 1.f, "feedforward_fwd: dropout %f", p->dropout_p);
   hipStream_t st = as_stream(stream);
-  if (ff3_fused_ok(p, P) && ws && ws_bytes >= arena_bytes(ff3_fused_ws_floats())) {
+  Arena far(ws, ws_bytes);
+  const FfFusedImg fused(far);
+  if (ff3_fused_ok(p, P) && far.ok()) {
     RPDE_CHECK_ARG(p->weights[0] && p->weights[1] && p->weights[2], "feedforward_fwd: null weights");
     RPDE_CHECK_ARG(!p->layer_norm || (p->ln_gamma && p->ln_beta), "feedforward_fwd: layer_norm needs gamma/beta");
-    return ff3_fused_fwd(p, x, residual, hs, ds, z_last, out, P, ws, st);
+    return ff3_fused_fwd(p, x, residual, hs, ds, z_last, out, P, fused.img, st);
   }
   RPDE_CHECK_ARG(p->n_layers == 1 || hs, "feedforward_fwd: hidden buffers missing");
   const int L = p->n_layers;
   // optional scratch (rpde_feedforward_fwd_ws_bytes): weights are pre-split once per call; without it the
   // GEMMs split them per workgroup (slower, same bits)
   // (one image per layer, all of them split by ONE launch: with a single image the layers split theirs one by one)
+  // (a short or null workspace: the images that fit, the first one at least, or none)
   Arena ar(ws, ws_bytes);
-  const size_t img_floats = ff_wimg_floats(L > 1 ? p->dim * p->factor : p->dim);
-  float* wimg[SplitJobs::MAX] = {nullptr, nullptr, nullptr, nullptr};
   bool all_imgs = ws != nullptr && L <= SplitJobs::MAX;
-  for (int l = 0; l < (all_imgs ? L : 1) && ws; ++l) {
-    float* t = ar.take(img_floats);
-    if (!t) { all_imgs = false; break; }
-    wimg[l] = t;
-  }
+  const FfFwdImgs imgs(ar, *p, all_imgs ? L : 1);
+  all_imgs = all_imgs && ar.ok();
+  float* const* wimg = imgs.wimg.data();
   if (all_imgs) {
     SplitJobs sj;
     for (int l = 0; l < L; ++l) {
@@ -252,34 +282,24 @@ int rpde_feedforward_bwd(const rpde_ff_params* p, const float* x, const float* c
   RPDE_CHECK_ARG(p && x && z_last && grad_out && P > 0, "feedforward_bwd: bad arguments");
   RPDE_CHECK_ARG(p->n_layers == 1 || (hs && ds), "feedforward_bwd: saved hidden tensors missing");
   RPDE_CHECK_ARG(P < (1L << 31), "feedforward_bwd: too many points for one call");
-  hipStream_t st = as_stream(stream);
   const int L = p->n_layers;
-  const int hid = L > 1 ? p->dim * p->factor : p->dim;
-  Arena ar(ws, ws_bytes);
-  float* buf0 = ar.take((size_t)P * hid);
-  float* buf1 = ar.take((size_t)P * hid);
-  // per layer: weight-gradient slabs, column-sum slabs, weight image (rpde_feedforward_ws_bytes) -- the regions of layer
-  // 0 are followed by the others', so the fused path below may use them as one region of the largest layer's size
+  const int hid = ff_hid(*p);
   // (any depth: folds and splits beyond the one-launch capacities of FoldJobs / SplitJobs run per layer)
-  std::vector<float*> slabs_l(L), csum_l(L), wt_l(L);
-  for (int l = 0; l < L; ++l) slabs_l[l] = ar.take(wgrad_ws_floats(P, ff_in(p, l), ff_out(p, l)));
-  for (int l = 0; l < L; ++l) csum_l[l] = ar.take((size_t)(colsum_tiles(P) + REDUCE_CHUNKS) * hid);
-  for (int l = 0; l < L; ++l) wt_l[l] = ar.take(ff_wimg_floats(hid));
-  float* small = ar.take(colsum_ws_floats(P, hid));
-  float* tailws = ar.take(ff_tail_bwd_ws_floats(P, p->dim));
-  if (!ar.ok()) { set_error("feedforward_bwd: workspace too small (%zu bytes given)", ws_bytes); return RPDE_ERR_WORKSPACE; }
+  const bool fused = ff3_fused_ok(p, P) && hs && hs[0] && hs[1];
+  RPDE_CARVE("feedforward_bwd", FfBwdWork, wk, ws, ws_bytes, *p, P, fused);
+  hipStream_t st = as_stream(stream);
+  float *buf0 = wk.buf0, *buf1 = wk.buf1, *small = wk.small, *tailws = wk.tailws;
+  const std::vector<float*>&slabs_l = wk.slabs, &csum_l = wk.csum, &wt_l = wk.wt;
   void* wt = wt_l[0];
 
-  if (ff3_fused_ok(p, P) && hs && hs[0] && hs[1]) {
+  if (fused) {
     // ds given: they hold d = gelu'(u) * dropscale and hs hold h.  ds absent: recompute mode, hs hold u = dropout(z)
     const int recompute = !(ds && ds[0] && ds[1]);
     const int act_h = recompute ? RPDE_ACT_GELU : RPDE_ACT_IDENTITY;
     // one fused kernel for the LayerNorm / dropout adjoint and the whole data-gradient chain; then the three
     // weight-gradient GEMMs on what it stored
-    float* dz3 = ar.take((size_t)P * p->dim);
-    float* part = ar.take(ff3_fused_bwd_part_floats());
-    void* fimg = ar.take(ff3_fused_ws_floats());
-    if (!ar.ok()) { set_error("feedforward_bwd: workspace too small (%zu bytes given)", ws_bytes); return RPDE_ERR_WORKSPACE; }
+    float *dz3 = wk.dz3, *part = wk.part;
+    void* fimg = wk.fimg;
     int grid = 0;
     RPDE_TRY(ff3_fused_bwd_launch(p, recompute ? hs : ds, recompute, z_last, grad_out, dz3, buf0, buf1, nullptr, part, &grid, P,
                                   fimg, st));
@@ -353,9 +373,14 @@ int rpde_feedforward_bwd(const rpde_ff_params* p, const float* x, const float* c
 }
 
 // ------------------------------ nn.Linear ----------------------------------
-size_t rpde_linear_ws_bytes(int64_t P, int in_f, int out_f) {
-  return arena_bytes(wgrad_ws_floats(P, in_f, out_f)) + arena_bytes(colsum_ws_floats(P, out_f));
-}
+// the weight-gradient slabs and the column-sum scratch
+struct LinearBwdWork {
+  float *slabs, *small;
+  LinearBwdWork(Arena& ar, long P, int in_f, int out_f)
+      : slabs(ar.take(wgrad_ws_floats(P, in_f, out_f))), small(ar.take(colsum_ws_floats(P, out_f))) {}
+};
+
+size_t rpde_linear_ws_bytes(int64_t P, int in_f, int out_f) { return ws_measure<LinearBwdWork>((long)P, in_f, out_f); }
 
 int rpde_linear_fwd(const float* x, const float* w, const float* b, float* out, int64_t P, int in_f, int out_f, void* stream) {
   RPDE_CHECK_ARG(x && w && out && P > 0 && in_f > 0 && out_f > 0 && P < (1L << 31), "linear_fwd: bad arguments");
@@ -365,12 +390,9 @@ int rpde_linear_fwd(const float* x, const float* w, const float* b, float* out, 
 int rpde_linear_bwd(const float* x, const float* w, const float* grad_out, float* grad_x, float* grad_w, float* grad_b,
                     int64_t P, int in_f, int out_f, void* ws, size_t ws_bytes, void* stream) {
   RPDE_CHECK_ARG(x && w && grad_out && P > 0 && in_f > 0 && out_f > 0 && P < (1L << 31), "linear_bwd: bad arguments");
+  RPDE_CARVE("linear_bwd", LinearBwdWork, wk, ws, ws_bytes, P, in_f, out_f);
   hipStream_t st = as_stream(stream);
-  Arena ar(ws, ws_bytes);
-  float* slabs = ar.take(wgrad_ws_floats(P, in_f, out_f));
-  float* small = ar.take(colsum_ws_floats(P, out_f));
-  if (!ar.ok()) { set_error("linear_bwd: workspace too small"); return RPDE_ERR_WORKSPACE; }
-  RPDE_TRY(linear_wgrad_impl(x, grad_out, grad_w, grad_b, P, in_f, out_f, slabs, small, st));
+  RPDE_TRY(linear_wgrad_impl(x, grad_out, grad_w, grad_b, P, in_f, out_f, wk.slabs, wk.small, st));
   if (grad_x) RPDE_TRY(linear_dgrad_impl(grad_out, w, grad_x, P, in_f, out_f, nullptr, nullptr, st));
   return RPDE_OK;
 }
@@ -383,9 +405,14 @@ static int conv1x1_ksplit(int B, int64_t S) {
   while (ks < 8 && B * ks < 64 && S / (2 * ks) >= 128) ks *= 2;
   return ks;
 }
-size_t rpde_conv1x1_ws_bytes(int B, int Cin, int Cout, int64_t S) {
-  return arena_bytes((size_t)B * conv1x1_ksplit(B, S) * Cout * Cin) + arena_bytes((size_t)B * Cout * 64);
-}
+// the weight-gradient slabs and the bias gradient's row sums
+struct Conv1x1BwdWork {
+  float *slabs, *part;
+  Conv1x1BwdWork(Arena& ar, int B, int Cin, int Cout, int64_t S)
+      : slabs(ar.take((size_t)B * conv1x1_ksplit(B, S) * Cout * Cin)), part(ar.take((size_t)B * Cout * 64)) {}
+};
+
+size_t rpde_conv1x1_ws_bytes(int B, int Cin, int Cout, int64_t S) { return ws_measure<Conv1x1BwdWork>(B, Cin, Cout, S); }
 
 int rpde_conv1x1_fwd(const float* x, const float* w, const float* b, float* out, int B, int Cin, int Cout, int64_t S,
                      int act_in, int accumulate, void* stream) {
@@ -445,12 +472,10 @@ int rpde_conv1x1_bwd(const float* x, const float* w, const float* grad_out, floa
                      int B, int Cin, int Cout, int64_t S, int act_in, int accumulate_gx, void* ws, size_t ws_bytes,
                      void* stream) {
   RPDE_CHECK_ARG(x && w && grad_out && B > 0 && Cin > 0 && Cout > 0 && S > 0 && S < (1L << 31), "conv1x1_bwd: bad arguments");
+  RPDE_CARVE("conv1x1_bwd", Conv1x1BwdWork, wk, ws, ws_bytes, B, Cin, Cout, S);
   hipStream_t st = as_stream(stream);
-  Arena ar(ws, ws_bytes);
   const int ks = conv1x1_ksplit(B, S);
-  float* slabs = ar.take((size_t)B * ks * Cout * Cin);
-  float* part = ar.take((size_t)B * Cout * 64);
-  if (!ar.ok()) { set_error("conv1x1_bwd: workspace too small"); return RPDE_ERR_WORKSPACE; }
+  float *slabs = wk.slabs, *part = wk.part;
   if (grad_w) {
     // gw[o,i] = sum_b sum_s g[b][o][s] * act(x[b][i][s]): one slab per batch entry, reduced over b
     rpde_gemm_desc d = gemm_desc();

@@ -302,12 +302,19 @@ using namespace rpde;
 
 extern "C" {
 
+// the slots' partial energies of both fields
+struct Fe1dWork {
+  float* part;
+  Fe1dWork(Arena& ar, int64_t rows, int num_modes) {
+    const long tiles = (rows + 15) / 16;
+    const int S = (int)(tiles < FE_SLOTS_1D ? tiles : FE_SLOTS_1D), NT = (2 * r4(num_modes) + 15) / 16;
+    part = ar.take((size_t)S * 2 * NT * 16);
+  }
+};
+
 size_t rpde_freq_energy1d_ws_bytes(int64_t rows, int n, int num_modes) {
   if (rows < 1 || n < 2 || n > FE_MAX_N || num_modes < 1) return 0;
-  const long tiles = (rows + 15) / 16;
-  const int S = (int)(tiles < FE_SLOTS_1D ? tiles : FE_SLOTS_1D);
-  const int NT = (2 * r4(num_modes) + 15) / 16;
-  return arena_bytes((size_t)S * 2 * NT * 16);
+  return ws_measure<Fe1dWork>(rows, num_modes);
 }
 
 int rpde_freq_energy1d(const float* pred, const float* target, double* acc, int64_t rows, int n, int num_modes,
@@ -316,10 +323,7 @@ int rpde_freq_energy1d(const float* pred, const float* target, double* acc, int6
   RPDE_CHECK_ARG(rows >= 1 && rows < (1L << 31) && n >= 2 && n <= FE_MAX_N && num_modes >= 1,
                  "freq_energy1d: bad rows=%ld n=%d (2 .. %d) num_modes=%d", (long)rows, n, FE_MAX_N, num_modes);
   if (num_modes > n / 2 + 1) { set_error("freq_energy1d: num_modes %d exceed n/2+1 = %d", num_modes, n / 2 + 1); return RPDE_ERR_MODES; }
-  if (!ws || ws_bytes < rpde_freq_energy1d_ws_bytes(rows, n, num_modes)) {
-    set_error("freq_energy1d: workspace too small");
-    return RPDE_ERR_WORKSPACE;
-  }
+  RPDE_CARVE("freq_energy1d", Fe1dWork, w, ws, ws_bytes, rows, num_modes);
   RPDE_CHECK_ARG(al16(ws), "freq_energy1d: the workspace must be 16-byte aligned");
   hipStream_t st = as_stream(stream);
   const rpde_plan* pl;
@@ -327,7 +331,7 @@ int rpde_freq_energy1d(const float* pred, const float* target, double* acc, int6
   FeP P;
   memset(&P, 0, sizeof(P));
   RPDE_TRY(fe_fragments(&P.timg, pl->fa, pl->ldn, 2 * pl->kp, n, st));
-  P.a = pred; P.b = target; P.out0 = static_cast<float*>(ws);
+  P.a = pred; P.b = target; P.out0 = w.part;
   P.K = n; P.KS = (n + 31) / 32; P.NT = (2 * pl->kp + 15) / 16;
   P.rpg = (int)rows; P.tiles = (int)((rows + 15) / 16); P.S = P.tiles < FE_SLOTS_1D ? P.tiles : FE_SLOTS_1D;
   P.vec = n % 4 == 0 && al16(pred) && al16(target);
@@ -337,12 +341,21 @@ int rpde_freq_energy1d(const float* pred, const float* target, double* acc, int6
   return RPDE_OK;
 }
 
+// a chunk's half-spectra of both fields and the slots' partial energies
+struct Fe2dWork {
+  float *s0, *s1, *part;
+  Fe2dWork(Arena& ar, int64_t images, int H, int W) {
+    const int cs = fe_chunk_images(images, H, W), KW = W / 2 + 1;
+    const int tiles = (cs + 15) / 16, S = tiles < FE_SLOTS_2D ? tiles : FE_SLOTS_2D, NT = (2 * H + 15) / 16;
+    s0 = ar.take((size_t)KW * cs * 2 * H);
+    s1 = ar.take((size_t)KW * cs * 2 * H);
+    part = ar.take((size_t)KW * S * 2 * NT * 16);
+  }
+};
+
 size_t rpde_freq_energy2d_ws_bytes(int64_t images, int H, int W) {
   if (images < 1 || H < 2 || W < 2 || H > FE_MAX_N || W > FE_MAX_N) return 0;
-  const int cs = fe_chunk_images(images, H, W), KW = W / 2 + 1;
-  const int tiles = (cs + 15) / 16, S = tiles < FE_SLOTS_2D ? tiles : FE_SLOTS_2D;
-  const int NT = (2 * H + 15) / 16;
-  return 2 * arena_bytes((size_t)KW * cs * 2 * H) + arena_bytes((size_t)KW * S * 2 * NT * 16);
+  return ws_measure<Fe2dWork>(images, H, W);
 }
 
 int rpde_freq_energy2d(const float* pred, const float* target, const int32_t* bins, double* acc, int64_t images, int H,
@@ -351,10 +364,7 @@ int rpde_freq_energy2d(const float* pred, const float* target, const int32_t* bi
   RPDE_CHECK_ARG(images >= 1 && H >= 2 && W >= 2 && H <= FE_MAX_N && W <= FE_MAX_N && n_bins >= 1 && n_bins <= 65535 &&
                      images * H < (1L << 31),
                  "freq_energy2d: bad images=%ld H=%d W=%d (2 .. %d) n_bins=%d", (long)images, H, W, FE_MAX_N, n_bins);
-  if (!ws || ws_bytes < rpde_freq_energy2d_ws_bytes(images, H, W)) {
-    set_error("freq_energy2d: workspace too small");
-    return RPDE_ERR_WORKSPACE;
-  }
+  RPDE_CARVE("freq_energy2d", Fe2dWork, w, ws, ws_bytes, images, H, W);
   RPDE_CHECK_ARG(al16(ws), "freq_energy2d: the workspace must be 16-byte aligned");
   hipStream_t st = as_stream(stream);
   const int KW = W / 2 + 1, cs = fe_chunk_images(images, H, W);
@@ -364,18 +374,13 @@ int rpde_freq_energy2d(const float* pred, const float* target, const int32_t* bi
   const char *tw, *th;
   RPDE_TRY(fe_fragments(&tw, pw->fa, pw->ldn, 2 * pw->kp, W, st));
   RPDE_TRY(fe_fragments(&th, ph->fa, ph->ldn, 2 * H, 2 * H, st));
-  const int tiles2 = (cs + 15) / 16, S2 = tiles2 < FE_SLOTS_2D ? tiles2 : FE_SLOTS_2D, NT2 = (2 * H + 15) / 16;
-  Arena ar(ws, ws_bytes);
-  float* s0 = ar.take((size_t)KW * cs * 2 * H);
-  float* s1 = ar.take((size_t)KW * cs * 2 * H);
-  float* part = ar.take((size_t)KW * S2 * 2 * NT2 * 16);
-  if (!ar.ok()) { set_error("freq_energy2d: workspace too small"); return RPDE_ERR_WORKSPACE; }
+  const int NT2 = (2 * H + 15) / 16;
   for (int64_t i0 = 0; i0 < images; i0 += cs) {
     const int c = (int)(images - i0 < cs ? images - i0 : cs);
     // rows along W: [c * H, W] -> both half-spectra, [kx][image][2 h + ri]
     FeP P;
     memset(&P, 0, sizeof(P));
-    P.a = pred + i0 * H * W; P.b = target + i0 * H * W; P.timg = tw; P.out0 = s0; P.out1 = s1;
+    P.a = pred + i0 * H * W; P.b = target + i0 * H * W; P.timg = tw; P.out0 = w.s0; P.out1 = w.s1;
     P.K = W; P.KS = (W + 31) / 32; P.NT = (2 * pw->kp + 15) / 16;
     P.rpg = c * H; P.tiles = (c * H + 15) / 16; P.S = P.tiles;
     P.H = H; P.KW = KW; P.bcc = c;
@@ -384,12 +389,12 @@ int rpde_freq_energy2d(const float* pred, const float* target, const int32_t* bi
     // columns along H: group kx holds c rows of 2 H interleaved (re, im) -> |Z|^2 summed over the images
     FeP Q;
     memset(&Q, 0, sizeof(Q));
-    Q.a = s0; Q.b = s1; Q.timg = th; Q.out0 = part;
+    Q.a = w.s0; Q.b = w.s1; Q.timg = th; Q.out0 = w.part;
     Q.K = 2 * H; Q.KS = (2 * H + 31) / 32; Q.NT = NT2;
     Q.rpg = c; Q.tiles = (c + 15) / 16; Q.S = Q.tiles < FE_SLOTS_2D ? Q.tiles : FE_SLOTS_2D;
     Q.vec = (2 * H) % 4 == 0;
     RPDE_TRY((fe_launch<false, false>(Q, KW, st)));
-    hipLaunchKernelGGL(k_fe_fold2d, dim3(n_bins, 2), dim3(256), 0, st, part, bins, Q.S, NT2 * 16, H, KW, W, n_bins, acc);
+    hipLaunchKernelGGL(k_fe_fold2d, dim3(n_bins, 2), dim3(256), 0, st, w.part, bins, Q.S, NT2 * 16, H, KW, W, n_bins, acc);
     RPDE_LAUNCH_CHECK();
   }
   return RPDE_OK;

@@ -114,67 +114,75 @@ static void axis_dims(Axis& ax, int n, int K, int rows) {
   ax.zdiv = 1; ax.s1 = ax.s2 = ax.ld = 0; ax.plan = nullptr;
 }
 
+// One axis.  Forward: the packed weight blocks and the mixed spectrum.  Backward: the g-spectrum, the weight blocks, the
+// d-spectrum and the weight-gradient slabs.  LOWPASS mixes nothing; thin (mix1d_ok: the few rows of the 1-D layer) reads
+// the weights where they lie (mix1d.hip) and needs neither blocks nor slabs
+struct AxisFwdWork {
+  bool thin; float *wblk = nullptr, *mixed = nullptr;
+  AxisFwdWork(Arena& ar, const Axis& ax, int C, int mode, bool thin_) : thin(thin_) {
+    if (mode != RPDE_MODE_FULL) return;
+    if (!thin) wblk = ar.take((size_t)ax.keff * 4 * C * C);
+    mixed = ar.take(spec_floats(ax, C));
+  }
+};
+struct AxisBwdWork {
+  bool thin; int S; float *gspec, *wblk = nullptr, *dsp = nullptr, *slabs = nullptr;
+  AxisBwdWork(Arena& ar, const Axis& ax, int C, int mode, bool thin_)
+      : thin(thin_), S(split_for(ax.rows, wgrad_tiles(C) * ax.keff)), gspec(ar.take(spec_floats(ax, C))) {
+    if (mode != RPDE_MODE_FULL) return;
+    if (!thin) wblk = ar.take((size_t)ax.keff * 4 * C * C);
+    dsp = ar.take(spec_floats(ax, C));
+    if (!thin) slabs = ar.take((size_t)S * ax.keff * 4 * C * C);
+  }
+};
+
+// the larger of an axis' forward and backward over both modes and both mixes
 static size_t axis_ws_bytes(const Axis& ax, int C) {
-  // forward: Wblk + mixed spectrum;  backward: Wblk + g-spectrum + d-spectrum + weight-grad slabs
-  const size_t wblk = arena_bytes((size_t)ax.keff * 4 * C * C);
-  const size_t sp = arena_bytes(spec_floats(ax, C));
-  const int S = split_for(ax.rows, wgrad_tiles(C) * ax.keff);
-  const size_t slabs = arena_bytes((size_t)S * ax.keff * 4 * C * C);
-  return wblk + 2 * sp + slabs;
+  size_t n = 0;
+  for (const int mode : {RPDE_MODE_FULL, RPDE_MODE_LOWPASS})
+    for (const bool thin : {false, true})
+      n = ws_max(n, ws_max(ws_measure<AxisFwdWork>(ax, C, mode, thin), ws_measure<AxisBwdWork>(ax, C, mode, thin)));
+  return n;
 }
 
 // forward of one axis: field x -> out (+)=
 static int axis_fwd(const Axis& ax, const float* x, const float* w, int K, float* out, float* spec_in, int C, int mode,
-                    int accumulate, Arena& ar, hipStream_t st) {
+                    int accumulate, const AxisFwdWork& wk, hipStream_t st) {
   RPDE_TRY(dft_analysis(ax, x, spec_in, C, false, st));
   const float* syn_in = spec_in;
-  if (mode == RPDE_MODE_FULL && mix1d_ok(ax.rows, C)) {
-    // few rows (the 1-D layer): the mix reads the weights where they lie (mix1d.hip)
-    float* mixed = ar.take(spec_floats(ax, C));
-    if (!ar.ok()) { set_error("fspectral: workspace too small"); return RPDE_ERR_WORKSPACE; }
-    RPDE_TRY(mix1d(spec_in, w, mixed, ax.rows, C, K, ax.keff, ax.kp, false, st));
-    syn_in = mixed;
+  if (mode == RPDE_MODE_FULL && wk.thin) {
+    RPDE_TRY(mix1d(spec_in, w, wk.mixed, ax.rows, C, K, ax.keff, ax.kp, false, st));
+    syn_in = wk.mixed;
   } else if (mode == RPDE_MODE_FULL) {
-    float* wblk = ar.take((size_t)ax.keff * 4 * C * C);
-    float* mixed = ar.take(spec_floats(ax, C));
-    if (!ar.ok()) { set_error("fspectral: workspace too small"); return RPDE_ERR_WORKSPACE; }
-    RPDE_TRY(pack_mix_weights(w, wblk, C, C, K, ax.keff, st));
-    if (ax.kp != ax.keff) RPDE_HIP(hipMemsetAsync(mixed, 0, spec_floats(ax, C) * sizeof(float), st));
-    RPDE_TRY(mode_mix(ax, spec_in, wblk, mixed, C, false, st));
-    syn_in = mixed;
+    RPDE_TRY(pack_mix_weights(w, wk.wblk, C, C, K, ax.keff, st));
+    if (ax.kp != ax.keff) RPDE_HIP(hipMemsetAsync(wk.mixed, 0, spec_floats(ax, C) * sizeof(float), st));
+    RPDE_TRY(mode_mix(ax, spec_in, wk.wblk, wk.mixed, C, false, st));
+    syn_in = wk.mixed;
   }
   return dft_synthesis(ax, syn_in, out, C, false, accumulate, st);
 }
 
 // backward of one axis: g -> gx (+)=, gw
 static int axis_bwd(const Axis& ax, const float* g, const float* spec_in, const float* w, int K, float* gx, float* gw, int C,
-                    int mode, int accumulate, Arena& ar, hipStream_t st, const float* skip = nullptr) {
-  float* gspec = ar.take(spec_floats(ax, C));
-  if (!ar.ok()) { set_error("fspectral: workspace too small"); return RPDE_ERR_WORKSPACE; }
+                    int mode, int accumulate, const AxisBwdWork& wk, hipStream_t st, const float* skip = nullptr) {
+  float *gspec = wk.gspec, *dsp = wk.dsp;
   RPDE_TRY(dft_analysis(ax, g, gspec, C, true, st));
   const float* dspec = gspec;
-  if (mode == RPDE_MODE_FULL && mix1d_ok(ax.rows, C)) {
-    float* dsp = ar.take(spec_floats(ax, C));
-    if (!ar.ok()) { set_error("fspectral: workspace too small"); return RPDE_ERR_WORKSPACE; }
+  if (mode == RPDE_MODE_FULL && wk.thin) {
     if (gw) RPDE_TRY(mix1d_wgrad(spec_in, gspec, gw, ax.rows, C, K, ax.keff, ax.kp, st));
     if (gx) {
       RPDE_TRY(mix1d(gspec, w, dsp, ax.rows, C, K, ax.keff, ax.kp, true, st));
       dspec = dsp;
     }
   } else if (mode == RPDE_MODE_FULL) {
-    float* wblk = ar.take((size_t)ax.keff * 4 * C * C);
-    float* dsp = ar.take(spec_floats(ax, C));
-    const int S = split_for(ax.rows, wgrad_tiles(C) * ax.keff);
-    float* slabs = ar.take((size_t)S * ax.keff * 4 * C * C);
-    if (!ar.ok()) { set_error("fspectral: workspace too small"); return RPDE_ERR_WORKSPACE; }
     if (gw) {
-      RPDE_TRY(mode_mix_wgrad(ax, spec_in, gspec, slabs, C, S, st));
-      RPDE_TRY(unpack_mix_grad(slabs, gw, C, C, K, ax.keff, S, (long)ax.keff * 4 * C * C, st));
+      RPDE_TRY(mode_mix_wgrad(ax, spec_in, gspec, wk.slabs, C, wk.S, st));
+      RPDE_TRY(unpack_mix_grad(wk.slabs, gw, C, C, K, ax.keff, wk.S, (long)ax.keff * 4 * C * C, st));
     }
     if (gx) {
-      RPDE_TRY(pack_mix_weights(w, wblk, C, C, K, ax.keff, st));
+      RPDE_TRY(pack_mix_weights(w, wk.wblk, C, C, K, ax.keff, st));
       if (ax.kp != ax.keff) RPDE_HIP(hipMemsetAsync(dsp, 0, spec_floats(ax, C) * sizeof(float), st));
-      RPDE_TRY(mode_mix(ax, gspec, wblk, dsp, C, true, st));
+      RPDE_TRY(mode_mix(ax, gspec, wk.wblk, dsp, C, true, st));
       dspec = dsp;
     }
   } else if (gw) {
@@ -202,49 +210,62 @@ static int mixw_slabs(const Axis& ay, const Axis& ax) {
   return (int)S;
 }
 
-static size_t fused2d_ws(const Axis& ay, const Axis& ax, int C, bool backward) {
-  const size_t spy = arena_bytes(spec_floats(ay, C)), spx = arena_bytes(spec_floats(ax, C));
-  const size_t wblk = arena_bytes((size_t)ay.keff * 4 * C * C);
-  const size_t img = arena_bytes(fused2d_img_bytes(ay.rows, 2 * ay.kp) / 4) + arena_bytes(fused2d_img_bytes(ax.rows, 2 * ax.kp) / 4);
-  const size_t inv = arena_bytes(ay.rows) + arena_bytes(ax.rows);
-  // h2 mode mix: weight fragments + per-mode constants + max |spectrum| per line
-  const size_t mix = arena_bytes(mix_wimg_bytes(ay.kp) / 4) + arena_bytes(4 * (size_t)ay.kp) + arena_bytes(ay.rows) + arena_bytes(ax.rows);
-  size_t n = wblk + (spy > spx ? spy : spx) + img + inv + mix;
-  if (backward) {
-    const int Sy = split_for(ay.rows, wgrad_tiles(C) * ay.keff), Sx = split_for(ax.rows, wgrad_tiles(C) * ax.keff);
-    const size_t sl = arena_bytes((size_t)(Sy > Sx ? Sy : Sx) * ay.keff * 4 * C * C);
-    n += spy + spx + sl + arena_bytes(mix_wgrad_slab_floats(ay.kp, mixw_slabs(ay, ax)));
-  }
-  return n;
+static size_t spec_max(const Axis& ay, const Axis& ax, int C) {
+  const size_t sy = spec_floats(ay, C), sx = spec_floats(ax, C);
+  return sy > sx ? sy : sx;
 }
+
+// Layouts of the fused path; the members are taken in the order they are declared, every piece whatever the mode and the
+// RPDE_FUSED_MIX switch.
+// The h2 mode mix's weight fragments and per-mode constants: a piece of both workspaces, and the whole of the buffer that
+// rpde_fspectral2d_prepare fills
+struct MixPrep {
+  void* wimg; float* wc;
+  MixPrep(Arena& ar, int kp) : wimg(ar.take(mix_wimg_bytes(kp) / 4)), wc(ar.take(4 * (size_t)kp)) {}
+};
+// forward: weight blocks and mixed spectrum of the GEMM mix, both axes' operand blocks and line scales, the h2 mix
+struct Fused2dFwdWork {
+  float *wblk, *mixed; void *imgy, *imgx; float *invy, *invx; MixPrep mix;
+  Fused2dFwdWork(Arena& ar, const Axis& ay, const Axis& ax, int C)
+      : wblk(ar.take((size_t)ay.keff * 4 * C * C)), mixed(ar.take(spec_max(ay, ax, C))),
+        imgy(ar.take(fused2d_img_bytes(ay.rows, 2 * ay.kp) / 4)), imgx(ar.take(fused2d_img_bytes(ax.rows, 2 * ax.kp) / 4)),
+        invy(ar.take(ay.rows)), invx(ar.take(ax.rows)), mix(ar, ay.kp) {}
+};
+// backward: the g-spectra, then as the forward with the GEMM mix's weight-gradient slabs; the g-spectra's line maxima and
+// the slabs of the h2 weight gradient
+struct Fused2dBwdWork {
+  int Sy, Sx, Sw;
+  float *gsy, *gsx, *wblk, *dsp; void *imgy, *imgx; float *invy, *invx, *slabs; MixPrep mix; float *amy, *amx, *wslabs;
+  Fused2dBwdWork(Arena& ar, const Axis& ay, const Axis& ax, int C)
+      : Sy(split_for(ay.rows, wgrad_tiles(C) * ay.keff)), Sx(split_for(ax.rows, wgrad_tiles(C) * ax.keff)), Sw(mixw_slabs(ay, ax)),
+        gsy(ar.take(spec_floats(ay, C))), gsx(ar.take(spec_floats(ax, C))), wblk(ar.take((size_t)ay.keff * 4 * C * C)),
+        dsp(ar.take(spec_max(ay, ax, C))), imgy(ar.take(fused2d_img_bytes(ay.rows, 2 * ay.kp) / 4)),
+        imgx(ar.take(fused2d_img_bytes(ax.rows, 2 * ax.kp) / 4)), invy(ar.take(ay.rows)), invx(ar.take(ax.rows)),
+        slabs(ar.take((size_t)(Sy > Sx ? Sy : Sx) * ay.keff * 4 * C * C)), mix(ar, ay.kp), amy(ar.take(ay.rows)),
+        amx(ar.take(ax.rows)), wslabs(ar.take(mix_wgrad_slab_floats(ay.kp, Sw))) {}
+};
+// evaluation with prepared weights: the spectra, their line maxima behind them, live in the workspace too
+struct Fused2dEvalWork {
+  float *spec_y, *spec_x; Fused2dFwdWork f;
+  Fused2dEvalWork(Arena& ar, const Axis& ay, const Axis& ax, int C)
+      : spec_y(ar.take(spec_floats(ay, C) + ay.rows)), spec_x(ar.take(spec_floats(ax, C) + ax.rows)), f(ar, ay, ax, C) {}
+};
 
 // prep (optional): weight fragments + constants written by rpde_fspectral2d_prepare for these weights
 static int fused2d_fwd(const Axis& ay, const Axis& ax, const float* x, const float* w_y, const float* w_x, float* out,
-                       float* spec_y, float* spec_x, int B, int M, int N, int C, int K, int mode, Arena& ar, hipStream_t st,
-                       const void* prep = nullptr) {
-  float* wblk = ar.take((size_t)ay.keff * 4 * C * C);
-  const size_t sy = spec_floats(ay, C), sx = spec_floats(ax, C);
-  float* mixed = ar.take(sy > sx ? sy : sx);
-  void* imgy = ar.take(fused2d_img_bytes(ay.rows, 2 * ay.kp) / 4);
-  void* imgx = ar.take(fused2d_img_bytes(ax.rows, 2 * ax.kp) / 4);
-  float* invy = ar.take(ay.rows);
-  float* invx = ar.take(ax.rows);
-  void* wimg = ar.take(mix_wimg_bytes(ay.kp) / 4);
-  float* wc = ar.take(4 * (size_t)ay.kp);
+                       float* spec_y, float* spec_x, int B, int M, int N, int C, int K, int mode, const Fused2dFwdWork& wk,
+                       hipStream_t st, const MixPrep* prep = nullptr) {
+  float *wblk = wk.wblk, *mixed = wk.mixed, *invy = wk.invy, *invx = wk.invx;
+  void *imgy = wk.imgy, *imgx = wk.imgx;
   // max |spectrum| per line: kept behind the saved spectra (rpde_fspectral2d_spec_elems), the backward needs them too
   float* amy = spec_y + spec_floats(ay, C);
   float* amx = spec_x + spec_floats(ax, C);
-  if (!ar.ok()) { set_error("fspectral2d: workspace too small"); return RPDE_ERR_WORKSPACE; }
   if (mode == RPDE_MODE_FULL && fused_mix_on()) {
     // prep (weights -> fragments) | analysis (+ max per line) | mix (spectra -> operand blocks) | synthesis
-    if (prep) {
-      wimg = const_cast<void*>(prep);
-      wc = reinterpret_cast<float*>(static_cast<char*>(wimg) + arena_bytes(mix_wimg_bytes(ay.kp) / 4));
-    } else {
-      RPDE_TRY(mix_prep(w_y, w_x, K, ay.keff, ay.kp, 0, wimg, wc, st));
-    }
+    const MixPrep& mix = prep ? *prep : wk.mix;
+    if (!prep) RPDE_TRY(mix_prep(w_y, w_x, K, ay.keff, ay.kp, 0, mix.wimg, mix.wc, st));
     RPDE_TRY(fused2d_analysis(x, spec_y, spec_x, amy, amx, ay.plan, ax.plan, 0, B, M, N, st));
-    RPDE_TRY(mix_h2(spec_y, spec_x, amy, amx, imgy, imgx, invy, invx, ay.rows, ax.rows, ay.kp, wimg, wc, st));
+    RPDE_TRY(mix_h2(spec_y, spec_x, amy, amx, imgy, imgx, invy, invx, ay.rows, ax.rows, ay.kp, mix.wimg, mix.wc, st));
     return fused2d_synthesis(imgy, imgx, invy, invx, ay.plan, ax.plan, 0, out, nullptr, B, M, N, st);
   }
   RPDE_TRY(fused2d_analysis(x, spec_y, spec_x, nullptr, nullptr, ay.plan, ax.plan, 0, B, M, N, st));
@@ -269,25 +290,11 @@ static int fused2d_fwd(const Axis& ay, const Axis& ax, const float* x, const flo
 
 static int fused2d_bwd(const Axis& ay, const Axis& ax, const float* g, const float* spec_y, const float* spec_x,
                        const float* w_y, const float* w_x, float* gx, float* gwy, float* gwx, const float* skip, int B, int M,
-                       int N, int C, int K, int mode, Arena& ar, hipStream_t st) {
-  float* gsy = ar.take(spec_floats(ay, C));
-  float* gsx = ar.take(spec_floats(ax, C));
-  float* wblk = ar.take((size_t)ay.keff * 4 * C * C);
-  const size_t sy = spec_floats(ay, C), sx = spec_floats(ax, C);
-  float* dsp = ar.take(sy > sx ? sy : sx);
-  void* imgy = ar.take(fused2d_img_bytes(ay.rows, 2 * ay.kp) / 4);
-  void* imgx = ar.take(fused2d_img_bytes(ax.rows, 2 * ax.kp) / 4);
-  float* invy = ar.take(ay.rows);
-  float* invx = ar.take(ax.rows);
-  const int Sy = split_for(ay.rows, wgrad_tiles(C) * ay.keff), Sx = split_for(ax.rows, wgrad_tiles(C) * ax.keff);
-  float* slabs = ar.take((size_t)(Sy > Sx ? Sy : Sx) * ay.keff * 4 * C * C);
-  void* wimg = ar.take(mix_wimg_bytes(ay.kp) / 4);
-  float* wc = ar.take(4 * (size_t)ay.kp);
-  float* amy = ar.take(ay.rows);
-  float* amx = ar.take(ax.rows);
-  const int Sw = mixw_slabs(ay, ax);
-  float* wslabs = ar.take(mix_wgrad_slab_floats(ay.kp, Sw));
-  if (!ar.ok()) { set_error("fspectral2d: workspace too small"); return RPDE_ERR_WORKSPACE; }
+                       int N, int C, int K, int mode, const Fused2dBwdWork& wk, hipStream_t st) {
+  float *gsy = wk.gsy, *gsx = wk.gsx, *wblk = wk.wblk, *dsp = wk.dsp, *invy = wk.invy, *invx = wk.invx, *slabs = wk.slabs;
+  float *wc = wk.mix.wc, *amy = wk.amy, *amx = wk.amx, *wslabs = wk.wslabs;
+  void *imgy = wk.imgy, *imgx = wk.imgx, *wimg = wk.mix.wimg;
+  const int Sy = wk.Sy, Sx = wk.Sx, Sw = wk.Sw;
   const bool h2mix = mode == RPDE_MODE_FULL && fused_mix_on();
   const bool hmix = h2mix && gx, hwg = h2mix && (gwy || gwx);
   if (hmix) RPDE_TRY(mix_prep(w_y, w_x, K, ay.keff, ay.kp, 1, wimg, wc, st));
@@ -338,6 +345,18 @@ using namespace rpde;
 
 extern "C" {
 
+// the geometry of the 2-D layer's axes without touching the device: lines along y (the last spatial dim), one per (b, m),
+// and lines along x, one per (b, n)
+static void axes2d_dims(Axis& ay, Axis& ax, int B, int M, int N, int K) {
+  axis_dims(ay, N, K, B * M);
+  axis_dims(ax, M, K, B * N);
+}
+static int make_axes2d(Axis& ay, Axis& ax, int B, int M, int N, int C, int K, hipStream_t st) {
+  // along y: points C apart; along x: points N*C apart
+  RPDE_TRY(make_axis(ay, N, K, RPDE_NORM_ORTHO, B * M, 1, (long)N * C, 0, C, st));
+  return make_axis(ax, M, K, RPDE_NORM_ORTHO, B * N, N, (long)M * N * C, C, (long)N * C, st);
+}
+
 // ------------------------------- 1-D ---------------------------------------
 size_t rpde_fspectral1d_ws_bytes(int B, int n, int C, int K) {
   Axis ax; axis_dims(ax, n, K, B);
@@ -353,11 +372,11 @@ int rpde_fspectral1d_fwd(const float* x, const float* w, float* out, float* spec
   RPDE_CHECK_ARG(x && out && spec_in && B > 0 && n > 0 && C > 0 && K > 0, "fspectral1d_fwd: bad arguments");
   RPDE_CHECK_ARG(mode == RPDE_MODE_LOWPASS || w, "fspectral1d_fwd: null weight");
   RPDE_CHECK_ARG(mode == RPDE_MODE_FULL || mode == RPDE_MODE_LOWPASS, "Mode %d not recognized", mode);
+  Axis ax; axis_dims(ax, n, K, B);
+  RPDE_CARVE("fspectral1d_fwd", AxisFwdWork, wk, ws, ws_bytes, ax, C, mode, mix1d_ok(B, C));
   hipStream_t st = as_stream(stream);
-  Axis ax;
   RPDE_TRY(make_axis(ax, n, K, norm, B, 1, (long)n * C, 0, C, st));
-  Arena ar(ws, ws_bytes);
-  return axis_fwd(ax, x, w, K, out, spec_in, C, mode, 0, ar, st);
+  return axis_fwd(ax, x, w, K, out, spec_in, C, mode, 0, wk, st);
 }
 
 int rpde_fspectral1d_bwd(const float* grad_out, const float* spec_in, const float* w, float* grad_x, float* grad_w,
@@ -365,29 +384,27 @@ int rpde_fspectral1d_bwd(const float* grad_out, const float* spec_in, const floa
                          void* stream) {
   RPDE_CHECK_ARG(grad_out && spec_in && B > 0 && n > 0 && C > 0 && K > 0, "fspectral1d_bwd: bad arguments");
   RPDE_CHECK_ARG(mode == RPDE_MODE_LOWPASS || w, "fspectral1d_bwd: null weight");
+  Axis ax; axis_dims(ax, n, K, B);
+  RPDE_CARVE("fspectral1d_bwd", AxisBwdWork, wk, ws, ws_bytes, ax, C, mode, mix1d_ok(B, C));
   hipStream_t st = as_stream(stream);
-  Axis ax;
   RPDE_TRY(make_axis(ax, n, K, norm, B, 1, (long)n * C, 0, C, st));
-  Arena ar(ws, ws_bytes);
-  return axis_bwd(ax, grad_out, spec_in, w, K, grad_x, grad_w, C, mode, 0, ar, st, grad_skip);
+  return axis_bwd(ax, grad_out, spec_in, w, K, grad_x, grad_w, C, mode, 0, wk, st, grad_skip);
 }
 
 // ------------------------------- 2-D ---------------------------------------
 size_t rpde_fspectral2d_ws_bytes(int B, int M, int N, int C, int K) {
   Axis ay, ax;
-  axis_dims(ay, N, K, B * M);
-  axis_dims(ax, M, K, B * N);
-  const size_t a = axis_ws_bytes(ay, C), b = axis_ws_bytes(ax, C);
-  size_t n = a > b ? a : b;   // the two axes run back to back and reuse the arena
-  if (fused2d_ok(M, N, C, ay.keff, ax.keff)) { const size_t f = fused2d_ws(ay, ax, C, true); if (f > n) n = f; }
-  return n;
+  axes2d_dims(ay, ax, B, M, N, K);
+  const size_t n = ws_max(axis_ws_bytes(ay, C), axis_ws_bytes(ax, C));   // the two axes run back to back and reuse the arena
+  if (!fused2d_ok(M, N, C, ay.keff, ax.keff)) return n;
+  return ws_max(n, ws_max(ws_measure<Fused2dFwdWork>(ay, ax, C), ws_measure<Fused2dBwdWork>(ay, ax, C)));
 }
 size_t rpde_fspectral2d_spec_elems(int B, int M, int N, int C, int K, int axis) {
-  Axis a, o;
-  if (axis == 0) { axis_dims(a, N, K, B * M); axis_dims(o, M, K, B * N); } else { axis_dims(a, M, K, B * N); axis_dims(o, N, K, B * M); }
+  Axis ay, ax;
+  axes2d_dims(ay, ax, B, M, N, K);
   // fused path: the line maxima of the spectrum ride behind it (the backward's weight-gradient kernel scales by them)
-  const bool fused = axis == 0 ? fused2d_ok(M, N, C, a.keff, o.keff) : fused2d_ok(M, N, C, o.keff, a.keff);
-  return spec_floats(a, C) + (fused ? (size_t)a.rows : 0);
+  const Axis& a = axis == 0 ? ay : ax;
+  return spec_floats(a, C) + (fused2d_ok(M, N, C, ay.keff, ax.keff) ? (size_t)a.rows : 0);
 }
 
 int rpde_fspectral2d_fwd(const float* x, const float* w_y, const float* w_x, float* out, float* spec_y, float* spec_x, int B,
@@ -397,62 +414,66 @@ int rpde_fspectral2d_fwd(const float* x, const float* w_y, const float* w_x, flo
   RPDE_CHECK_ARG(mode == RPDE_MODE_FULL || mode == RPDE_MODE_LOWPASS, "fspectral2d_fwd: mode %d", mode);
   hipStream_t st = as_stream(stream);
   Axis ay, ax;
-  // lines along y (last spatial dim): one per (b,m), points C apart
-  RPDE_TRY(make_axis(ay, N, K, RPDE_NORM_ORTHO, B * M, 1, (long)N * C, 0, C, st));
-  // lines along x: one per (b,n), points N*C apart
-  RPDE_TRY(make_axis(ax, M, K, RPDE_NORM_ORTHO, B * N, N, (long)M * N * C, C, (long)N * C, st));
-  if (fused2d_ok(M, N, C, ay.keff, ax.keff)) {
-    Arena ar(ws, ws_bytes);
-    return fused2d_fwd(ay, ax, x, w_y, w_x, out, spec_y, spec_x, B, M, N, C, K, mode, ar, st);
-  }
-  {
-    Arena ar(ws, ws_bytes);
-    RPDE_TRY(axis_fwd(ax, x, w_x, K, out, spec_x, C, mode, 0, ar, st));
-  }
+  axes2d_dims(ay, ax, B, M, N, K);
   Arena ar(ws, ws_bytes);
-  return axis_fwd(ay, x, w_y, K, out, spec_y, C, mode, 1, ar, st);
+  if (fused2d_ok(M, N, C, ay.keff, ax.keff)) {
+    const Fused2dFwdWork wk(ar, ay, ax, C);
+    RPDE_CLAIM_WS("fspectral2d_fwd", ar, ws_bytes);
+    RPDE_TRY(make_axes2d(ay, ax, B, M, N, C, K, st));
+    return fused2d_fwd(ay, ax, x, w_y, w_x, out, spec_y, spec_x, B, M, N, C, K, mode, wk, st);
+  }
+  // x, then y on the same bytes
+  Arena ar_y(ws, ws_bytes);
+  const AxisFwdWork wx(ar, ax, C, mode, mix1d_ok(ax.rows, C)), wy(ar_y, ay, C, mode, mix1d_ok(ay.rows, C));
+  RPDE_CLAIM_WS("fspectral2d_fwd", ar, ws_bytes);
+  RPDE_CLAIM_WS("fspectral2d_fwd", ar_y, ws_bytes);
+  RPDE_TRY(make_axes2d(ay, ax, B, M, N, C, K, st));
+  RPDE_TRY(axis_fwd(ax, x, w_x, K, out, spec_x, C, mode, 0, wx, st));
+  return axis_fwd(ay, x, w_y, K, out, spec_y, C, mode, 1, wy, st);
 }
 
 // ---- evaluation with frozen weights: rpde_fspectral2d_prepare builds the mode-mix weight fragments once,
 // rpde_fspectral2d_fwd_prepared runs analysis | mix | synthesis with them; spectra live in the workspace ----
 size_t rpde_fspectral2d_prep_bytes(int M, int N, int C, int K) {
   Axis ay, ax;
-  axis_dims(ay, N, K, M);
-  axis_dims(ax, M, K, N);
+  axes2d_dims(ay, ax, 1, M, N, K);
   if (!fused2d_ok(M, N, C, ay.keff, ax.keff) || !fused_mix_on()) return 0;      // 0: this shape has nothing to prepare
-  return arena_bytes(mix_wimg_bytes(ay.kp) / 4) + arena_bytes(4 * (size_t)ay.kp);
+  return ws_measure<MixPrep>(ay.kp);
 }
 
 size_t rpde_fspectral2d_eval_ws_bytes(int B, int M, int N, int C, int K) {
-  return rpde_fspectral2d_ws_bytes(B, M, N, C, K) + arena_bytes(rpde_fspectral2d_spec_elems(B, M, N, C, K, 0)) +
-         arena_bytes(rpde_fspectral2d_spec_elems(B, M, N, C, K, 1));
+  Axis ay, ax;
+  axes2d_dims(ay, ax, B, M, N, K);
+  // 0, as rpde_fspectral2d_prep_bytes: rpde_fspectral2d_fwd_prepared refuses this shape
+  return rpde_fspectral2d_prep_bytes(M, N, C, K) ? ws_measure<Fused2dEvalWork>(ay, ax, C) : 0;
 }
 
 int rpde_fspectral2d_prepare(const float* w_y, const float* w_x, int M, int N, int C, int K, void* prep, size_t prep_bytes,
                              void* stream) {
   RPDE_CHECK_ARG(w_y && w_x && prep && M > 0 && N > 0 && K > 0, "fspectral2d_prepare: bad arguments");
-  const size_t need = rpde_fspectral2d_prep_bytes(M, N, C, K);
-  RPDE_CHECK_ARG(need > 0 && prep_bytes >= need, "fspectral2d_prepare: shape not on the fused path or buffer too small");
   Axis ay;
   axis_dims(ay, N, K, M);
-  float* wc = reinterpret_cast<float*>(static_cast<char*>(prep) + arena_bytes(mix_wimg_bytes(ay.kp) / 4));
-  return mix_prep(w_y, w_x, K, ay.keff, ay.kp, 0, prep, wc, as_stream(stream));
+  Arena ar(prep, prep_bytes);
+  const MixPrep mix(ar, ay.kp);
+  RPDE_CHECK_ARG(rpde_fspectral2d_prep_bytes(M, N, C, K) > 0 && ar.ok(),
+                 "fspectral2d_prepare: shape not on the fused path or buffer too small");
+  return mix_prep(w_y, w_x, K, ay.keff, ay.kp, 0, mix.wimg, mix.wc, as_stream(stream));
 }
 
 int rpde_fspectral2d_fwd_prepared(const float* x, const void* prep, float* out, int B, int M, int N, int C, int K, void* ws,
                                   size_t ws_bytes, void* stream) {
   RPDE_CHECK_ARG(x && prep && out && ws && B > 0 && M > 0 && N > 0 && C > 0 && K > 0, "fspectral2d_fwd_prepared: bad arguments");
-  RPDE_CHECK_ARG(rpde_fspectral2d_prep_bytes(M, N, C, K) > 0, "fspectral2d_fwd_prepared: shape not on the fused path");
-  hipStream_t st = as_stream(stream);
+  const size_t prep_bytes = rpde_fspectral2d_prep_bytes(M, N, C, K);      // what rpde_fspectral2d_prepare asked for
+  RPDE_CHECK_ARG(prep_bytes > 0, "fspectral2d_fwd_prepared: shape not on the fused path");
   Axis ay, ax;
-  RPDE_TRY(make_axis(ay, N, K, RPDE_NORM_ORTHO, B * M, 1, (long)N * C, 0, C, st));
-  RPDE_TRY(make_axis(ax, M, K, RPDE_NORM_ORTHO, B * N, N, (long)M * N * C, C, (long)N * C, st));
-  Arena ar(ws, ws_bytes);
-  float* spec_y = ar.take(rpde_fspectral2d_spec_elems(B, M, N, C, K, 0));
-  float* spec_x = ar.take(rpde_fspectral2d_spec_elems(B, M, N, C, K, 1));
-  if (!ar.ok()) { set_error("fspectral2d_fwd_prepared: workspace too small"); return RPDE_ERR_WORKSPACE; }
-  Arena rest(static_cast<char*>(ws) + ar.used, ws_bytes - ar.used);
-  return fused2d_fwd(ay, ax, x, nullptr, nullptr, out, spec_y, spec_x, B, M, N, C, K, RPDE_MODE_FULL, rest, st, prep);
+  axes2d_dims(ay, ax, B, M, N, K);
+  Arena ar(ws, ws_bytes), par(const_cast<void*>(prep), prep_bytes);
+  const Fused2dEvalWork wk(ar, ay, ax, C);
+  const MixPrep mix(par, ay.kp);
+  RPDE_CLAIM_WS("fspectral2d_fwd_prepared", ar, ws_bytes);
+  hipStream_t st = as_stream(stream);
+  RPDE_TRY(make_axes2d(ay, ax, B, M, N, C, K, st));
+  return fused2d_fwd(ay, ax, x, nullptr, nullptr, out, wk.spec_y, wk.spec_x, B, M, N, C, K, RPDE_MODE_FULL, wk.f, st, &mix);
 }
 
 int rpde_fspectral2d_bwd(const float* grad_out, const float* spec_y, const float* spec_x, const float* w_y, const float* w_x,
@@ -462,19 +483,23 @@ int rpde_fspectral2d_bwd(const float* grad_out, const float* spec_y, const float
   RPDE_CHECK_ARG(mode == RPDE_MODE_LOWPASS || (w_y && w_x), "fspectral2d_bwd: null weight");
   hipStream_t st = as_stream(stream);
   Axis ay, ax;
-  RPDE_TRY(make_axis(ay, N, K, RPDE_NORM_ORTHO, B * M, 1, (long)N * C, 0, C, st));
-  RPDE_TRY(make_axis(ax, M, K, RPDE_NORM_ORTHO, B * N, N, (long)M * N * C, C, (long)N * C, st));
-  if (fused2d_ok(M, N, C, ay.keff, ax.keff)) {
-    Arena ar(ws, ws_bytes);
-    return fused2d_bwd(ay, ax, grad_out, spec_y, spec_x, w_y, w_x, grad_x, grad_wy, grad_wx, grad_skip, B, M, N, C, K, mode,
-                       ar, st);
-  }
-  {
-    Arena ar(ws, ws_bytes);
-    RPDE_TRY(axis_bwd(ax, grad_out, spec_x, w_x, K, grad_x, grad_wx, C, mode, 0, ar, st, grad_skip));
-  }
+  axes2d_dims(ay, ax, B, M, N, K);
   Arena ar(ws, ws_bytes);
-  return axis_bwd(ay, grad_out, spec_y, w_y, K, grad_x, grad_wy, C, mode, 1, ar, st);
+  if (fused2d_ok(M, N, C, ay.keff, ax.keff)) {
+    const Fused2dBwdWork wk(ar, ay, ax, C);
+    RPDE_CLAIM_WS("fspectral2d_bwd", ar, ws_bytes);
+    RPDE_TRY(make_axes2d(ay, ax, B, M, N, C, K, st));
+    return fused2d_bwd(ay, ax, grad_out, spec_y, spec_x, w_y, w_x, grad_x, grad_wy, grad_wx, grad_skip, B, M, N, C, K, mode,
+                       wk, st);
+  }
+  // x, then y on the same bytes
+  Arena ar_y(ws, ws_bytes);
+  const AxisBwdWork wx(ar, ax, C, mode, mix1d_ok(ax.rows, C)), wy(ar_y, ay, C, mode, mix1d_ok(ay.rows, C));
+  RPDE_CLAIM_WS("fspectral2d_bwd", ar, ws_bytes);
+  RPDE_CLAIM_WS("fspectral2d_bwd", ar_y, ws_bytes);
+  RPDE_TRY(make_axes2d(ay, ax, B, M, N, C, K, st));
+  RPDE_TRY(axis_bwd(ax, grad_out, spec_x, w_x, K, grad_x, grad_wx, C, mode, 0, wx, st, grad_skip));
+  return axis_bwd(ay, grad_out, spec_y, w_y, K, grad_x, grad_wy, C, mode, 1, wy, st);
 }
 
 }  // extern "C"

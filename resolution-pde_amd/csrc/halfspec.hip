@@ -37,22 +37,22 @@ __global__ __launch_bounds__(256) void k_grf_half(const float* __restrict__ nois
 }
 
 // the workspace holds the half spectrum and, for M > 1, the inverse transform's row spectra
-static size_t grf_ws_bytes(const HalfSpec& g) { return (g.M > 1 ? 2 : 1) * arena_bytes(hs_elems(g)); }
+struct GrfWork {
+  float *h, *rows;
+  GrfWork(Arena& ar, const HalfSpec& g) : h(ar.take(hs_elems(g))), rows(g.M > 1 ? ar.take(hs_elems(g)) : nullptr) {}
+};
 
 static int grf(const char* what, const float* noise, const float* sqrt_eig, float* out, const HalfSpec& g, void* ws,
                size_t ws_bytes, void* stream) {
   HS_CHECK_WS(what, ws);
   RPDE_CHECK_ARG(((uintptr_t)noise & 7) == 0, "%s: noise must be 8-byte aligned", what);
-  Arena ar(ws, ws_bytes);
-  float* h = ar.take(hs_elems(g));
-  float* rows = g.M > 1 ? ar.take(hs_elems(g)) : nullptr;
-  if (!ar.ok()) { set_error("%s: workspace too small", what); return RPDE_ERR_WORKSPACE; }
+  RPDE_CARVE(what, GrfWork, w, ws, ws_bytes, g);
   hipStream_t st = as_stream(stream);
   const long groups = (long)g.M * (g.kp / 4);
   const int blk = hs_block(groups);
-  hipLaunchKernelGGL(k_grf_half, hs_grid(groups, g.images, blk), dim3(blk), 0, st, noise, sqrt_eig, h, g);
+  hipLaunchKernelGGL(k_grf_half, hs_grid(groups, g.images, blk), dim3(blk), 0, st, noise, sqrt_eig, w.h, g);
   RPDE_LAUNCH_CHECK();
-  return hs_irfft(g, h, rows, out, st);
+  return hs_irfft(g, w.h, w.rows, out, st);
 }
 
 // a transform entry: the row spectra of M > 1 come from the caller's workspace
@@ -63,7 +63,7 @@ static int dft_entry(const char* what, bool inverse, const float* in, float* out
     HS_CHECK_WS(what, ws);
     Arena ar(ws, ws_bytes);
     rows = ar.take(hs_elems(g));
-    if (!ar.ok()) { set_error("%s: workspace too small", what); return RPDE_ERR_WORKSPACE; }
+    RPDE_CLAIM_WS(what, ar, ws_bytes);
   }
   return inverse ? hs_irfft(g, in, rows, out, as_stream(stream)) : hs_rfft(g, in, rows, out, as_stream(stream));
 }
@@ -98,7 +98,7 @@ int rpde_etd1d_irfft(const float* U, float* u, int B, int N, void* stream) {
   return dft_entry("etd1d_irfft", true, U, u, hs_geom(B, 1, N), nullptr, 0, stream);
 }
 
-size_t rpde_grf2d_ws_bytes(int B, int M, int N) { return hs_dims2_ok(B, M, N) ? grf_ws_bytes(hs_geom(B, M, N)) : 0; }
+size_t rpde_grf2d_ws_bytes(int B, int M, int N) { return hs_dims2_ok(B, M, N) ? ws_measure<GrfWork>(hs_geom(B, M, N)) : 0; }
 
 int rpde_grf2d(const float* noise, const float* sqrt_eig, float* out, int B, int M, int N, void* ws, size_t ws_bytes,
                void* stream) {
@@ -107,7 +107,7 @@ int rpde_grf2d(const float* noise, const float* sqrt_eig, float* out, int B, int
   return grf("grf2d", noise, sqrt_eig, out, hs_geom(B, M, N), ws, ws_bytes, stream);
 }
 
-size_t rpde_grf1d_ws_bytes(int B, int N) { return hs_dims_ok(B, 1, N) ? grf_ws_bytes(hs_geom(B, 1, N)) : 0; }
+size_t rpde_grf1d_ws_bytes(int B, int N) { return hs_dims_ok(B, 1, N) ? ws_measure<GrfWork>(hs_geom(B, 1, N)) : 0; }
 
 int rpde_grf1d(const float* noise, const float* sqrt_eig, float* out, int B, int N, void* ws, size_t ws_bytes,
                void* stream) {

@@ -195,30 +195,23 @@ constexpr int ns_products(bool scalar) { return scalar ? 2 : 1; }
 inline bool ns_dims_ok(bool scalar, int B, int M, int N) { return hs_dims2_ok(B, M, N, scalar ? ns_derivs(true) : 1); }
 
 // The workspace of a step: the derivative spectra and their column stage, the fields, their products, the products' row
-// spectra and spectra.  ws null: only `bytes` counts.  The transforms alone need one spectrum, rpde_nsc2d_fields the
-// first two pieces with 3B spectra each
+// spectra and spectra.  The transforms alone need one spectrum
 struct NsWork {
   float *D, *T1, *P, *Fp, *S1, *F;
-  size_t bytes = 0;
-  NsWork(bool scalar, size_t spec, size_t phys, void* ws) {
-    const auto take = [&](size_t floats) {
-      float* p = ws ? reinterpret_cast<float*>(static_cast<char*>(ws) + bytes) : nullptr;
-      bytes += arena_bytes(floats);
-      return p;
-    };
-    const size_t nd = ns_derivs(scalar), np = ns_products(scalar);
-    D = take(nd * spec);
-    T1 = take(nd * spec);
-    P = take(nd * phys);
-    Fp = take(np * phys);
-    S1 = take(np * spec);
-    F = take(np * spec);
-  }
+  NsWork(Arena& ar, size_t nd, size_t np, size_t spec, size_t phys)
+      : D(ar.take(nd * spec)), T1(ar.take(nd * spec)), P(ar.take(nd * phys)), Fp(ar.take(np * phys)), S1(ar.take(np * spec)),
+        F(ar.take(np * spec)) {}
+};
+// rpde_nsc2d_fields: three derivative spectra per sample and their column stage
+struct NscFieldsWork {
+  float *D, *T1;
+  NscFieldsWork(Arena& ar, size_t spec) : D(ar.take(3 * spec)), T1(ar.take(3 * spec)) {}
 };
 
 static size_t ns_ws_bytes(bool scalar, int B, int M, int N) {
   if (!ns_dims_ok(scalar, B, M, N)) return 0;
-  return NsWork(scalar, hs_elems(hs_geom(B, M, N)), (size_t)B * M * N, nullptr).bytes;
+  const size_t spec = hs_elems(hs_geom(B, M, N)), steps = ws_measure<NsWork>((size_t)ns_derivs(scalar), (size_t)ns_products(scalar), spec, (size_t)B * M * N);
+  return scalar ? ws_max(steps, ws_measure<NscFieldsWork>(spec)) : steps;
 }
 
 // rpde_ns2d_steps and rpde_nsc2d_steps: the checks, the workspace, the first fan-out and nsteps times six launches
@@ -240,8 +233,7 @@ static int ns_steps(float* S, const float* g_h, int g_batched, const NsTables<SC
   // the state; the products; the derivative fields
   const HalfSpec g = hs_geom(B, M, N), gp = hs_geom(ns_products(SCALAR) * B, M, N), gd = hs_geom(ns_derivs(SCALAR) * B, M, N);
   const size_t phys = (size_t)B * M * N;
-  const NsWork w(SCALAR, hs_elems(g), phys, ws);
-  if (w.bytes > ws_bytes) { set_error("%s: workspace too small", what); return RPDE_ERR_WORKSPACE; }
+  RPDE_CARVE(what, NsWork, w, ws, ws_bytes, ns_derivs(SCALAR), ns_products(SCALAR), hs_elems(g), phys);
   if (nsteps == 0) return RPDE_OK;
   hipStream_t st = as_stream(stream);
   const dim3 ug = hs_grid((long)M * (g.kp / 4), B);
@@ -302,15 +294,11 @@ int rpde_nsc2d_fields(const float* S, const float* inv_lap, float* out, int B, i
   HS_CHECK_WS("nsc2d_fields", ws);
   RPDE_CHECK_ARG(al16(S) && al16(inv_lap) && al16(out), "nsc2d_fields: state, table and output must be 16-byte aligned");
   const HalfSpec g = hs_geom(B, M, N), g3 = hs_geom(3 * B, M, N);
-  const size_t spec = hs_elems(g);
-  Arena ar(ws, ws_bytes);
-  float* D = ar.take(3 * spec);
-  float* T1 = ar.take(3 * spec);
-  if (!ar.ok()) { set_error("nsc2d_fields: workspace too small"); return RPDE_ERR_WORKSPACE; }
+  RPDE_CARVE("nsc2d_fields", NscFieldsWork, w, ws, ws_bytes, hs_elems(g));
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(k_nsc_fields_fanout, hs_grid((long)M * (g.kp / 4), B), dim3(256), 0, st, S, inv_lap, D, g);
+  hipLaunchKernelGGL(k_nsc_fields_fanout, hs_grid((long)M * (g.kp / 4), B), dim3(256), 0, st, S, inv_lap, w.D, g);
   RPDE_LAUNCH_CHECK();
-  return hs_irfft(g3, D, T1, out, st);
+  return hs_irfft(g3, w.D, w.T1, out, st);
 }
 
 }  // extern "C"

@@ -407,26 +407,32 @@ using namespace rpde;
 extern "C" {
 
 // --------------------------------- 1-D --------------------------------------
+// the spectra on the output side (the forward's output, the backward's grad_out), the backward's spectra of grad_x, and
+// the slabs of a thin transform (the forward's analysis of x, the backward's transposed synthesis of grad_out)
+struct Spectral1dWork {
+  float *ospec, *dspec, *slabs;
+  Spectral1dWork(Arena& ar, int B, int Cin, int Cout, int n, int K, bool backward) {
+    ospec = ar.take((size_t)B * Cout * 2 * r4(K));
+    dspec = backward ? ar.take((size_t)B * Cin * 2 * r4(K)) : nullptr;
+    const size_t nslab = thin_slab_floats((long)B * (backward ? Cout : Cin), 2 * r4(K), n);
+    slabs = nslab ? ar.take(nslab) : nullptr;
+  }
+};
+
 size_t rpde_spectral1d_ws_bytes(int B, int Cin, int Cout, int n, int K) {
-  const int kp = r4(K);
-  const int cm = Cin > Cout ? Cin : Cout;
-  const size_t a = thin_slab_floats((long)B * Cin, 2 * kp, n), b = thin_slab_floats((long)B * Cout, 2 * kp, n);
-  return 2 * arena_bytes((size_t)B * cm * 2 * kp) + arena_bytes(a > b ? a : b);
+  return ws_max(ws_measure<Spectral1dWork>(B, Cin, Cout, n, K, false), ws_measure<Spectral1dWork>(B, Cin, Cout, n, K, true));
 }
 
 int rpde_spectral1d_fwd(const float* x, const float* w, float* out, float* spec_in, int B, int Cin, int Cout, int n, int K,
                         int act_in, void* ws, size_t ws_bytes, void* stream) {
   RPDE_CHECK_ARG(x && w && out && spec_in && B > 0 && Cin > 0 && Cout > 0 && n > 0 && K > 0, "spectral1d_fwd: bad arguments");
   if (K > n / 2 + 1) { set_error("SpectralConv1d: modes1=%d exceeds n//2+1=%d", K, n / 2 + 1); return RPDE_ERR_MODES; }
+  RPDE_CARVE("spectral1d_fwd", Spectral1dWork, wk, ws, ws_bytes, B, Cin, Cout, n, K, false);
+  float* ospec = wk.ospec;
   hipStream_t st = as_stream(stream);
   const rpde_plan* pl;
   RPDE_TRY(get_plan(&pl, n, K, RPDE_NORM_BACKWARD, 1, PLAN_REAL, st));
-  Arena ar(ws, ws_bytes);
-  float* ospec = ar.take((size_t)B * Cout * 2 * pl->kp);
-  const size_t nslab = thin_slab_floats((long)B * Cin, 2 * pl->kp, n);
-  float* slabs = nslab ? ar.take(nslab) : nullptr;
-  if (!ar.ok()) { set_error("spectral1d_fwd: workspace too small"); return RPDE_ERR_WORKSPACE; }
-  RPDE_TRY(cf_analysis(pl, x, spec_in, (long)B * Cin, n, act_in, st, slabs));
+  RPDE_TRY(cf_analysis(pl, x, spec_in, (long)B * Cin, n, act_in, st, wk.slabs));
   if (pl->kp != K) RPDE_HIP(hipMemsetAsync(ospec, 0, sizeof(float) * (size_t)B * Cout * 2 * pl->kp, st));
   MixGeom g{B, Cin, Cout, 1, 1, K, pl->kp};
   RPDE_TRY(launch_mix(0, spec_in, nullptr, w, w, ospec, nullptr, g, st));
@@ -439,16 +445,12 @@ int rpde_spectral1d_bwd(const float* grad_out, const float* spec_in, const float
   RPDE_CHECK_ARG(grad_out && spec_in && w && B > 0 && Cin > 0 && Cout > 0 && n > 0 && K > 0, "spectral1d_bwd: bad arguments");
   RPDE_CHECK_ARG(!act_in || x, "spectral1d_bwd: act_in needs x");
   if (K > n / 2 + 1) { set_error("SpectralConv1d: modes1=%d exceeds n//2+1=%d", K, n / 2 + 1); return RPDE_ERR_MODES; }
+  RPDE_CARVE("spectral1d_bwd", Spectral1dWork, wk, ws, ws_bytes, B, Cin, Cout, n, K, true);
+  float *gspec = wk.ospec, *dspec = wk.dspec;
   hipStream_t st = as_stream(stream);
   const rpde_plan* pl;
   RPDE_TRY(get_plan(&pl, n, K, RPDE_NORM_BACKWARD, 1, PLAN_REAL, st));
-  Arena ar(ws, ws_bytes);
-  float* gspec = ar.take((size_t)B * Cout * 2 * pl->kp);
-  float* dspec = ar.take((size_t)B * Cin * 2 * pl->kp);
-  const size_t nslab = thin_slab_floats((long)B * Cout, 2 * pl->kp, n);
-  float* slabs = nslab ? ar.take(nslab) : nullptr;
-  if (!ar.ok()) { set_error("spectral1d_bwd: workspace too small"); return RPDE_ERR_WORKSPACE; }
-  RPDE_TRY(cf_synthesis_T(pl, grad_out, gspec, (long)B * Cout, n, st, slabs));
+  RPDE_TRY(cf_synthesis_T(pl, grad_out, gspec, (long)B * Cout, n, st, wk.slabs));
   MixGeom g{B, Cin, Cout, 1, 1, K, pl->kp};
   if (grad_w) RPDE_TRY(launch_mix(2, spec_in, gspec, nullptr, nullptr, grad_w, grad_w, g, st));
   if (grad_x) {
@@ -465,12 +467,27 @@ size_t rpde_spectral2d_spec_elems(int B, int Cin, int M, int N, int m1, int m2) 
   return (size_t)B * Cin * 2 * (2 * m1) * r4(m2);
 }
 
+// floats of `images` spectra of `rows` rows: [re|im][kp] each
+static size_t rows2d(long images, int rows, int m2) { return (size_t)images * rows * 2 * r4(m2); }
+// The forward up to the row spectra (spectral2d_rows): the row spectra of x and of the output, the mixed retained modes
+// and, with own_s2, the retained modes of x, which the training forward keeps in the caller's spec_in instead
+struct Spectral2dRows {
+  float *s1, *t1, *o2, *s2;
+  Spectral2dRows(Arena& ar, int B, int Ci, int Co, int M, int m1, int m2, bool own_s2)
+      : s1(ar.take(rows2d(B * Ci, M, m2))), t1(ar.take(rows2d(B * Co, M, m2))), o2(ar.take(rows2d(B * Co, 2 * m1, m2))),
+        s2(own_s2 ? ar.take(rows2d(B * Ci, 2 * m1, m2)) : nullptr) {}
+};
+// the backward: the row spectra and retained modes of grad_out and of grad_x
+struct Spectral2dBwdWork {
+  float *gt1, *ds1, *go2, *ds2;
+  Spectral2dBwdWork(Arena& ar, int B, int Cin, int Cout, int M, int m1, int m2)
+      : gt1(ar.take(rows2d(B * Cout, M, m2))), ds1(ar.take(rows2d(B * Cin, M, m2))), go2(ar.take(rows2d(B * Cout, 2 * m1, m2))),
+        ds2(ar.take(rows2d(B * Cin, 2 * m1, m2))) {}
+};
+
 size_t rpde_spectral2d_ws_bytes(int B, int Cin, int Cout, int M, int N, int m1, int m2) {
   (void)N;
-  const int cm = Cin > Cout ? Cin : Cout;
-  const size_t stage1 = arena_bytes((size_t)B * cm * M * 2 * r4(m2));
-  const size_t small = arena_bytes((size_t)B * cm * 2 * (2 * m1) * r4(m2));
-  return 2 * stage1 + 2 * small;
+  return ws_max(ws_measure<Spectral2dRows>(B, Cin, Cout, M, m1, m2, false), ws_measure<Spectral2dBwdWork>(B, Cin, Cout, M, m1, m2));
 }
 
 static bool modes_fit(int M, int N, int m1, int m2) { return m2 <= N / 2 + 1 && m1 <= M; }
@@ -482,21 +499,17 @@ static int check_modes2d(int M, int N, int m1, int m2) {
 
 // SpectralConv2d up to the row spectra: x [B,Ci,M,N] -> t1 [B*Co][2M][kp], ready for the synthesis along N with *pn.
 // The retained-mode spectra [B*Ci][2R][kp] go to `s2` (the training forward: the caller's spec_in, kept for the backward)
-// or, when s2 is null, to the workspace: rpde_spectral2d_ws_bytes above covers s1, t1 and o2 (and the backward's
-// four buffers), rpde_fnoblock2d_eval_ws_bytes adds the spectra.
+// or, when s2 is null, to the workspace (Spectral2dRows with own_s2).
 struct Rows2d { const rpde_plan* pn; float* t1; };
 static int spectral2d_rows(const char* who, const float* x, const float* w1, const float* w2, float* s2, int B, int Ci, int Co,
                            int M, int N, int m1, int m2, int act_in, void* ws, size_t ws_bytes, hipStream_t st, Rows2d* out) {
+  RPDE_CARVE(who, Spectral2dRows, wk, ws, ws_bytes, B, Ci, Co, M, m1, m2, !s2);
+  float *s1 = wk.s1, *t1 = wk.t1, *o2 = wk.o2;
+  if (!s2) s2 = wk.s2;
   const rpde_plan *pn, *pm;
   RPDE_TRY(get_plan(&pn, N, m2, RPDE_NORM_BACKWARD, 1, PLAN_REAL, st));
   RPDE_TRY(get_plan(&pm, M, m1, RPDE_NORM_BACKWARD, 0, PLAN_CPLX, st));
   const int kp = pn->kp, R = 2 * m1;
-  Arena ar(ws, ws_bytes);
-  float* s1 = ar.take((size_t)B * Ci * M * 2 * kp);
-  float* t1 = ar.take((size_t)B * Co * M * 2 * kp);
-  float* o2 = ar.take((size_t)B * Co * 2 * R * kp);
-  if (!s2) s2 = ar.take((size_t)B * Ci * 2 * R * kp);
-  if (!ar.ok()) { set_error("%s: workspace too small", who); return RPDE_ERR_WORKSPACE; }
   RPDE_TRY(cf_analysis(pn, x, s1, (long)B * Ci * M, N, act_in, st));
   MixGeom g{B, Ci, Co, R, m1, m2, kp};
   if (col_stage_ok(M, m1, kp, s1, t1)) {
@@ -526,7 +539,8 @@ int rpde_spectral2d_fwd(const float* x, const float* w1, const float* w2, float*
 // models/fno_blocks.py:63-83.  The spectral branch stops at the row spectra; the streaming kernel of conv_small.hip forms
 // the inverse DFT along the last axis, the 1x1 bypass convolution, bias and activation in one pass over x.
 size_t rpde_fnoblock2d_eval_ws_bytes(int B, int Cin, int Cout, int M, int N, int m1, int m2) {
-  return rpde_spectral2d_ws_bytes(B, Cin, Cout, M, N, m1, m2) + arena_bytes(rpde_spectral2d_spec_elems(B, Cin, M, N, m1, m2));
+  (void)N;
+  return ws_measure<Spectral2dRows>(B, Cin, Cout, M, m1, m2, true);
 }
 
 int rpde_fnoblock2d_eval_ok(int Cin, int Cout, int M, int N, int m2) {
@@ -574,10 +588,17 @@ int rpde_fnoblock2d_proj_eval_fwd(const float* x, const float* w1, const float* 
 
 // ---- evaluation-mode FNO2d: lifting + first block without the lifted field (reference models/fno.py:121-147:
 // cat(x, gridx, gridy) -> lifting -> fno_blocks[0]); u [B,1,M,N], gx [M], gy [N], wl [C,3], bl [C] ----
+// the row spectra of u, of the two constant rows, the lifted field's retained modes and the output's row spectra
+struct LiftBlockWork {
+  float *su, *sc, *s2, *t1;
+  LiftBlockWork(Arena& ar, int B, int C, int Cout, int M, int m1, int m2)
+      : su(ar.take(rows2d(B, M, m2))), sc(ar.take(rows2d(1, 2, m2))), s2(ar.take(rows2d(B * C, 2 * m1, m2))),
+        t1(ar.take(rows2d(B * Cout, M, m2))) {}
+};
+
 size_t rpde_fno2d_lift_block_eval_ws_bytes(int B, int C, int Cout, int M, int N, int m1, int m2) {
-  const size_t kp = (size_t)r4(m2), R = 2 * (size_t)m1;
-  return arena_bytes((size_t)B * M * 2 * kp) + arena_bytes(4 * kp) +
-         arena_bytes((size_t)B * C * 2 * R * kp) + arena_bytes((size_t)B * Cout * M * 2 * kp) + 4096;
+  (void)N;
+  return ws_measure<LiftBlockWork>(B, C, Cout, M, m1, m2);
 }
 
 int rpde_fno2d_lift_block_eval_ok(int Cu, int C, int Cout, int M, int N, int m1, int m2) {
@@ -593,19 +614,15 @@ int rpde_fno2d_lift_block_eval_fwd(const float* u, const float* gx, const float*
   RPDE_CHECK_ARG(u && gx && gy && wl && w1 && w2 && wc && out && B > 0 && C > 0 && Cout > 0 && M > 0 && N > 0 && m1 > 0 && m2 > 0,
                  "fno2d_lift_block_eval_fwd: bad arguments");
   RPDE_CHECK_ARG(rpde_fno2d_lift_block_eval_ok(1, C, Cout, M, N, m1, m2), "fno2d_lift_block_eval_fwd: shape not covered");
+  RPDE_CHECK_ARG(((reinterpret_cast<uintptr_t>(u) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(gy)) & 15) == 0,
+                 "fno2d_lift_block_eval_fwd: u, gy and out must be 16-byte aligned");
+  RPDE_CARVE("fno2d_lift_block_eval_fwd", LiftBlockWork, wk, ws, ws_bytes, B, C, Cout, M, m1, m2);
+  float *su = wk.su, *sc = wk.sc, *s2 = wk.s2, *t1 = wk.t1;
   hipStream_t st = as_stream(stream);
   const rpde_plan *pn, *pm;
   RPDE_TRY(get_plan(&pn, N, m2, RPDE_NORM_BACKWARD, 1, PLAN_REAL, st));
   RPDE_TRY(get_plan(&pm, M, m1, RPDE_NORM_BACKWARD, 0, PLAN_CPLX, st));
   const int kp = pn->kp, R = 2 * m1;
-  Arena ar(ws, ws_bytes);
-  float* su = ar.take((size_t)B * M * 2 * kp);
-  float* sc = ar.take(4 * (size_t)kp);
-  float* s2 = ar.take((size_t)B * C * 2 * R * kp);
-  float* t1 = ar.take((size_t)B * Cout * M * 2 * kp);
-  if (!ar.ok()) { set_error("fno2d_lift_block_eval_fwd: workspace too small"); return RPDE_ERR_WORKSPACE; }
-  RPDE_CHECK_ARG(((reinterpret_cast<uintptr_t>(u) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(gy)) & 15) == 0,
-                 "fno2d_lift_block_eval_fwd: u, gy and out must be 16-byte aligned");
   hipLaunchKernelGGL(k_lift_const_spectra, dim3((2 * kp + 3) / 4), dim3(256), 0, st, pn->fa, pn->ldn, gy, sc, N, 2 * kp);
   RPDE_TRY(cf_analysis(pn, u, su, (long)B * M, N, 0, st));
   MixGeom g{B, C, Cout, R, m1, m2, kp};
@@ -621,17 +638,13 @@ int rpde_spectral2d_bwd(const float* grad_out, const float* spec_in, const float
                  "spectral2d_bwd: bad arguments");
   RPDE_CHECK_ARG(!act_in || x, "spectral2d_bwd: act_in needs x");
   RPDE_TRY(check_modes2d(M, N, m1, m2));
+  RPDE_CARVE("spectral2d_bwd", Spectral2dBwdWork, wk, ws, ws_bytes, B, Cin, Cout, M, m1, m2);
+  float *gt1 = wk.gt1, *ds1 = wk.ds1, *go2 = wk.go2, *ds2 = wk.ds2;
   hipStream_t st = as_stream(stream);
   const rpde_plan *pn, *pm;
   RPDE_TRY(get_plan(&pn, N, m2, RPDE_NORM_BACKWARD, 1, PLAN_REAL, st));
   RPDE_TRY(get_plan(&pm, M, m1, RPDE_NORM_BACKWARD, 0, PLAN_CPLX, st));
   const int kp = pn->kp, R = 2 * m1;
-  Arena ar(ws, ws_bytes);
-  float* gt1 = ar.take((size_t)B * Cout * M * 2 * kp);
-  float* ds1 = ar.take((size_t)B * Cin * M * 2 * kp);
-  float* go2 = ar.take((size_t)B * Cout * 2 * R * kp);
-  float* ds2 = ar.take((size_t)B * Cin * 2 * R * kp);
-  if (!ar.ok()) { set_error("spectral2d_bwd: workspace too small"); return RPDE_ERR_WORKSPACE; }
   RPDE_TRY(cf_synthesis_T(pn, grad_out, gt1, (long)B * Cout * M, N, st));
   RPDE_TRY(cf_rowdft(pm->fs, 2L * R, true, 2 * R, 2 * M, gt1, go2, B * Cout, kp, st));
   MixGeom g{B, Cin, Cout, R, m1, m2, kp};

@@ -72,11 +72,23 @@ size_t rpde_wrel_l2_spec_elems(int B, int C, int M, int N) {
   return hs_loss_dims_ok(B, C, M, N) ? hs_elems(hs_geom(B * C, M, N)) : 0;
 }
 
+// forward: the difference, the target's spectrum, the row spectra, the partial sums (doubles)
+struct Wl2FwdWork {
+  float *d, *sy, *s1; double* part;
+  Wl2FwdWork(Arena& ar, const HalfSpec& g, int B)
+      : d(ar.take((size_t)g.images * g.M * g.N)), sy(ar.take(hs_elems(g))), s1(ar.take(hs_elems(g))),
+        part(reinterpret_cast<double*>(ar.take((size_t)2 * 2 * B * REL_SLOTS))) {}
+};
+// backward: the weighted spectrum and the row spectra
+struct Wl2BwdWork {
+  float *w, *t1;
+  Wl2BwdWork(Arena& ar, const HalfSpec& g) : w(ar.take(hs_elems(g))), t1(ar.take(hs_elems(g))) {}
+};
+
 size_t rpde_wrel_l2_ws_bytes(int B, int C, int M, int N) {
   if (!hs_loss_dims_ok(B, C, M, N)) return 0;
-  const size_t spec = rpde_wrel_l2_spec_elems(B, C, M, N);
-  // forward: the difference, the target's spectrum, the row spectra, the partial sums (doubles); the backward needs less
-  return arena_bytes((size_t)B * C * M * N) + 2 * arena_bytes(spec) + arena_bytes((size_t)2 * 2 * B * REL_SLOTS);
+  const HalfSpec g = hs_geom(B * C, M, N);
+  return ws_max(ws_measure<Wl2FwdWork>(g, B), ws_measure<Wl2BwdWork>(g));
 }
 
 int rpde_wrel_l2_fwd(const float* x, const float* y, const float* omega, float* rel, float* loss, float* stats, float* spec_d,
@@ -85,20 +97,14 @@ int rpde_wrel_l2_fwd(const float* x, const float* y, const float* omega, float* 
   RPDE_CHECK_ARG(hs_loss_dims_ok(B, C, M, N), "wrel_l2_fwd: bad B=%d C=%d M=%d N=%d (axes 2 .. %d; M = 1: one-dimensional)", B, C,
                  M, N, HS_MAX_N);
   const Wl2Geom g = wl2_geom(B, C, M, N);
-  const size_t spec = hs_elems(g);
-  Arena ar(ws, ws_bytes);
-  float* d = ar.take((size_t)g.images * M * N);
-  float* sy = ar.take(spec);
-  float* s1 = ar.take(spec);
-  double* part = reinterpret_cast<double*>(ar.take((size_t)2 * 2 * B * REL_SLOTS));
-  if (!ar.ok()) { set_error("wrel_l2_fwd: workspace too small"); return RPDE_ERR_WORKSPACE; }
+  RPDE_CARVE("wrel_l2_fwd", Wl2FwdWork, w, ws, ws_bytes, g, B);
   hipStream_t st = as_stream(stream);
-  RPDE_TRY(rel_diff(x, y, d, (long)g.images * M * N, st));
-  RPDE_TRY(hs_rfft(g, d, s1, spec_d, st));
-  RPDE_TRY(hs_rfft(g, y, s1, sy, st));
-  hipLaunchKernelGGL(k_wl2_energy, dim3(g.S, B, 2), dim3(256), 0, st, spec_d, sy, omega, part, g);
+  RPDE_TRY(rel_diff(x, y, w.d, (long)g.images * M * N, st));
+  RPDE_TRY(hs_rfft(g, w.d, w.s1, spec_d, st));
+  RPDE_TRY(hs_rfft(g, y, w.s1, w.sy, st));
+  hipLaunchKernelGGL(k_wl2_energy, dim3(g.S, B, 2), dim3(256), 0, st, spec_d, w.sy, omega, w.part, g);
   RPDE_LAUNCH_CHECK();
-  return rel_final(part, rel, loss, stats, B, g.S, 1.0 / ((double)M * (double)N), size_average, st);
+  return rel_final(w.part, rel, loss, stats, B, g.S, 1.0 / ((double)M * (double)N), size_average, st);
 }
 
 int rpde_wrel_l2_bwd(const float* spec_d, const float* omega, const float* stats, const float* grad_loss, const float* grad_rel,
@@ -107,19 +113,15 @@ int rpde_wrel_l2_bwd(const float* spec_d, const float* omega, const float* stats
   RPDE_CHECK_ARG(hs_loss_dims_ok(B, C, M, N), "wrel_l2_bwd: bad B=%d C=%d M=%d N=%d (axes 2 .. %d; M = 1: one-dimensional)", B, C,
                  M, N, HS_MAX_N);
   const Wl2Geom g = wl2_geom(B, C, M, N);
-  const size_t spec = hs_elems(g);
-  Arena ar(ws, ws_bytes);
-  float* w = ar.take(spec);
-  float* t1 = ar.take(spec);
-  if (!ar.ok()) { set_error("wrel_l2_bwd: workspace too small"); return RPDE_ERR_WORKSPACE; }
+  RPDE_CARVE("wrel_l2_bwd", Wl2BwdWork, w, ws, ws_bytes, g);
   hipStream_t st = as_stream(stream);
   const long per = (long)C * hs_per(g);
   long nb = (per + 1023) / 1024;
   if (nb > 256) nb = 256;
-  hipLaunchKernelGGL(k_wl2_weight, dim3((unsigned)nb, B), dim3(256), 0, st, spec_d, omega, stats, grad_loss, grad_rel, w, g,
+  hipLaunchKernelGGL(k_wl2_weight, dim3((unsigned)nb, B), dim3(256), 0, st, spec_d, omega, stats, grad_loss, grad_rel, w.w, g,
                      size_average);
   RPDE_LAUNCH_CHECK();
-  return hs_irfft(g, w, t1, grad_x, st);
+  return hs_irfft(g, w.w, w.t1, grad_x, st);
 }
 
 }  // extern "C"

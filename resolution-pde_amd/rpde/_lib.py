@@ -234,6 +234,16 @@ def workspace(nbytes: int, device) -> torch.Tensor:
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
 
 
+def run(entry: str, nws: int, where, *args) -> None:
+    """rpde_<entry>(*args, ws, nws, stream), its status checked under that name: every entry with a workspace ends in
+    (ws, ws_bytes, stream).  `where`: the device to allocate the nws bytes on, or a workspace of that size which the
+    caller keeps over several calls"""
+    ws = where if isinstance(where, torch.Tensor) else workspace(nws, where)
+    status = getattr(_lib or load(), "rpde_" + entry)(*args, ws.data_ptr(), nws, stream_ptr())
+    if status:
+        check(status, entry)
+
+
 def ptr_array(ts: Sequence[Optional[torch.Tensor]]):
     arr = (C.c_void_p * len(ts))()
     for i, t in enumerate(ts):

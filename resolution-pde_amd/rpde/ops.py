@@ -16,7 +16,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._lib import ACT, MODE, NORM, check, load, ptr, ptr_array, stream_ptr, workspace
+from ._lib import ACT, MODE, NORM, check, load, ptr, ptr_array, run, stream_ptr, workspace
 
 
 def _f32c(t: torch.Tensor) -> torch.Tensor:
@@ -96,10 +96,8 @@ class _FSpectral1d(torch.autograd.Function):
         B, n, Cc = x.shape
         out = torch.empty_like(x)
         spec = torch.empty(lib.rpde_fspectral1d_spec_elems(B, n, Cc, modes), dtype=torch.float32, device=x.device)
-        nws = lib.rpde_fspectral1d_ws_bytes(B, n, Cc, modes)
-        ws = workspace(nws, x.device)
-        check(lib.rpde_fspectral1d_fwd(ptr(x), ptr(wf), ptr(out), ptr(spec), B, n, Cc, modes, mode, norm,
-                                       ws.data_ptr(), nws, stream_ptr()), "fspectral1d_fwd")
+        run("fspectral1d_fwd", lib.rpde_fspectral1d_ws_bytes(B, n, Cc, modes), x.device, ptr(x), ptr(wf), ptr(out),
+            ptr(spec), B, n, Cc, modes, mode, norm)
         ctx.save_for_backward(spec, wf if wf is not None else x.new_empty(0))
         ctx.dims = (B, n, Cc, modes, mode, norm, wf is not None)
         # with_skip: also hand x back (an alias) for the caller's skip connection, so that the gradient
@@ -118,11 +116,8 @@ class _FSpectral1d(torch.autograd.Function):
         need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and has_w
         gx = torch.empty_like(g) if need_x else None
         gw = torch.empty_like(wf) if need_w else None
-        nws = lib.rpde_fspectral1d_ws_bytes(B, n, Cc, modes)
-        ws = workspace(nws, g.device)
-        check(lib.rpde_fspectral1d_bwd(ptr(g), ptr(spec), ptr(wf) if has_w else None, ptr(gx), ptr(gw),
-                                       ptr(g_skip) if need_x else None, B, n, Cc, modes,
-                                       mode, norm, ws.data_ptr(), nws, stream_ptr()), "fspectral1d_bwd")
+        run("fspectral1d_bwd", lib.rpde_fspectral1d_ws_bytes(B, n, Cc, modes), g.device, ptr(g), ptr(spec),
+            ptr(wf) if has_w else None, ptr(gx), ptr(gw), ptr(g_skip) if need_x else None, B, n, Cc, modes, mode, norm)
         return gx, gw, None, None, None, None
 
 
@@ -138,10 +133,8 @@ class _FSpectral2d(torch.autograd.Function):
         out = torch.empty_like(x)
         spec_y = torch.empty(lib.rpde_fspectral2d_spec_elems(B, M, N, Cc, modes, 0), dtype=torch.float32, device=x.device)
         spec_x = torch.empty(lib.rpde_fspectral2d_spec_elems(B, M, N, Cc, modes, 1), dtype=torch.float32, device=x.device)
-        nws = lib.rpde_fspectral2d_ws_bytes(B, M, N, Cc, modes)
-        ws = workspace(nws, x.device)
-        check(lib.rpde_fspectral2d_fwd(ptr(x), ptr(wyf), ptr(wxf), ptr(out), ptr(spec_y), ptr(spec_x), B, M, N, Cc, modes,
-                                       mode, ws.data_ptr(), nws, stream_ptr()), "fspectral2d_fwd")
+        run("fspectral2d_fwd", lib.rpde_fspectral2d_ws_bytes(B, M, N, Cc, modes), x.device, ptr(x), ptr(wyf),
+            ptr(wxf), ptr(out), ptr(spec_y), ptr(spec_x), B, M, N, Cc, modes, mode)
         if has_w:
             ctx.save_for_backward(spec_y, spec_x, wyf, wxf)
         else:
@@ -166,11 +159,9 @@ class _FSpectral2d(torch.autograd.Function):
         gx = torch.empty_like(g) if need_x else None
         gwy = torch.empty_like(wyf) if need_w else None
         gwx = torch.empty_like(wxf) if need_w else None
-        nws = lib.rpde_fspectral2d_ws_bytes(B, M, N, Cc, modes)
-        ws = workspace(nws, g.device)
-        check(lib.rpde_fspectral2d_bwd(ptr(g), ptr(spec_y), ptr(spec_x), ptr(wyf), ptr(wxf), ptr(gx), ptr(gwy), ptr(gwx),
-                                       ptr(g_skip) if need_x else None,
-                                       B, M, N, Cc, modes, mode, ws.data_ptr(), nws, stream_ptr()), "fspectral2d_bwd")
+        run("fspectral2d_bwd", lib.rpde_fspectral2d_ws_bytes(B, M, N, Cc, modes), g.device, ptr(g), ptr(spec_y),
+            ptr(spec_x), ptr(wyf), ptr(wxf), ptr(gx), ptr(gwy), ptr(gwx), ptr(g_skip) if need_x else None, B, M, N,
+            Cc, modes, mode)
         return gx, gwy, gwx, None, None, None
 
 
@@ -190,10 +181,8 @@ def _fspectral2d_frozen(x, wy, wx, modes: int):
     if prep is None:
         return None
     out = torch.empty_like(x)
-    nws = lib.rpde_fspectral2d_eval_ws_bytes(B, M, N, Cc, modes)
-    ws = workspace(nws, x.device)
-    check(lib.rpde_fspectral2d_fwd_prepared(ptr(x), prep.data_ptr(), ptr(out), B, M, N, Cc, modes, ws.data_ptr(), nws,
-                                            stream_ptr()), "fspectral2d_fwd_prepared")
+    run("fspectral2d_fwd_prepared", lib.rpde_fspectral2d_eval_ws_bytes(B, M, N, Cc, modes), x.device, ptr(x),
+        prep.data_ptr(), ptr(out), B, M, N, Cc, modes)
     return out
 
 
@@ -291,10 +280,8 @@ class _FeedForward(torch.autograd.Function):
                 check(lib.rpde_feedforward_fwd_prepared(C.byref(fp), ptr(x2), ptr(res2), ptr(out), P, prep.data_ptr(), nws,
                                                         stream_ptr()), "feedforward_fwd_prepared")
                 return out.reshape(shape)
-        ws = workspace(nws, x.device)
-        check(lib.rpde_feedforward_fwd(C.byref(fp), ptr(x2), ptr(res2), C.cast(ha, C.POINTER(C.c_void_p)),
-                                       C.cast(da, C.POINTER(C.c_void_p)), ptr(z_last), ptr(out), P, ws.data_ptr(), nws,
-                                       stream_ptr()), "feedforward_fwd")
+        run("feedforward_fwd", nws, x.device, C.byref(fp), ptr(x2), ptr(res2), C.cast(ha, C.POINTER(C.c_void_p)),
+            C.cast(da, C.POINTER(C.c_void_p)), ptr(z_last), ptr(out), P)
         ctx.cfg = cfg
         ctx.has_res = residual is not None
         if need_grad:
@@ -324,12 +311,9 @@ class _FeedForward(torch.autograd.Function):
         epoch = drop_epoch(g.device).data_ptr() if p_drop > 0.0 else None
         fp = _lib.FFParams(L, dim, factor, int(layer_norm), eps, p_drop, seed, post_act,
                            C.cast(wa, C.POINTER(C.c_void_p)), C.cast(ba, C.POINTER(C.c_void_p)), ptr(gamma), ptr(beta), epoch)
-        nws = lib.rpde_feedforward_ws_bytes(P, dim, factor, L)
-        ws = workspace(nws, g.device)
-        check(lib.rpde_feedforward_bwd(C.byref(fp), ptr(x2), C.cast(ha, C.POINTER(C.c_void_p)),
-                                       C.cast(da, C.POINTER(C.c_void_p)), ptr(z_last), ptr(g2), ptr(gx),
-                                       C.cast(gwa, C.POINTER(C.c_void_p)), C.cast(gba, C.POINTER(C.c_void_p)),
-                                       ptr(ggamma), ptr(gbeta), P, ws.data_ptr(), nws, stream_ptr()), "feedforward_bwd")
+        run("feedforward_bwd", lib.rpde_feedforward_ws_bytes(P, dim, factor, L), g.device, C.byref(fp), ptr(x2),
+            C.cast(ha, C.POINTER(C.c_void_p)), C.cast(da, C.POINTER(C.c_void_p)), ptr(z_last), ptr(g2), ptr(gx),
+            C.cast(gwa, C.POINTER(C.c_void_p)), C.cast(gba, C.POINTER(C.c_void_p)), ptr(ggamma), ptr(gbeta), P)
         grads: List[Optional[torch.Tensor]] = []
         for l in range(L):
             grads += [gws[l], gbs[l]]
@@ -380,10 +364,8 @@ class _Linear(torch.autograd.Function):
         gx = torch.empty_like(x2) if ctx.needs_input_grad[0] else None
         gw = torch.empty_like(w) if ctx.needs_input_grad[1] else None
         gb = torch.empty(out_f, dtype=torch.float32, device=g.device) if (ctx.has_b and ctx.needs_input_grad[2]) else None
-        nws = lib.rpde_linear_ws_bytes(P, in_f, out_f)
-        ws = workspace(nws, g.device)
-        check(lib.rpde_linear_bwd(ptr(x2), ptr(w), ptr(g2), ptr(gx), ptr(gw), ptr(gb), P, in_f, out_f, ws.data_ptr(), nws,
-                                  stream_ptr()), "linear_bwd")
+        run("linear_bwd", lib.rpde_linear_ws_bytes(P, in_f, out_f), g.device, ptr(x2), ptr(w), ptr(g2), ptr(gx),
+            ptr(gw), ptr(gb), P, in_f, out_f)
         return (gx.reshape(*g.shape[:-1], in_f) if gx is not None else None), gw, gb
 
 
@@ -436,10 +418,8 @@ class _Spectral1d(torch.autograd.Function):
         out = torch.empty(B, Co, n, dtype=torch.float32, device=x.device)
         kp = (K + 3) // 4 * 4
         spec = torch.empty(B * Ci * 2 * kp, dtype=torch.float32, device=x.device)
-        nws = lib.rpde_spectral1d_ws_bytes(B, Ci, Co, n, K)
-        ws = workspace(nws, x.device)
-        check(lib.rpde_spectral1d_fwd(ptr(x), ptr(wf), ptr(out), ptr(spec), B, Ci, Co, n, K, act_in, ws.data_ptr(), nws,
-                                      stream_ptr()), "spectral1d_fwd")
+        run("spectral1d_fwd", lib.rpde_spectral1d_ws_bytes(B, Ci, Co, n, K), x.device, ptr(x), ptr(wf), ptr(out),
+            ptr(spec), B, Ci, Co, n, K, act_in)
         ctx.save_for_backward(spec, w, x if act_in else x.new_empty(0))
         ctx.dims = (B, Ci, Co, n, K, act_in)
         return out
@@ -453,11 +433,9 @@ class _Spectral1d(torch.autograd.Function):
         wf = _as_float_storage(w)
         gx = torch.empty(B, Ci, n, dtype=torch.float32, device=g.device) if ctx.needs_input_grad[0] else None
         gw = torch.empty_like(w) if ctx.needs_input_grad[1] else None
-        nws = lib.rpde_spectral1d_ws_bytes(B, Ci, Co, n, K)
-        ws = workspace(nws, g.device)
-        check(lib.rpde_spectral1d_bwd(ptr(g), ptr(spec), ptr(wf), ptr(x) if act_in else None, ptr(gx),
-                                      ptr(_as_float_storage(gw)) if gw is not None else None, B, Ci, Co, n, K, act_in,
-                                      ws.data_ptr(), nws, stream_ptr()), "spectral1d_bwd")
+        run("spectral1d_bwd", lib.rpde_spectral1d_ws_bytes(B, Ci, Co, n, K), g.device, ptr(g), ptr(spec), ptr(wf),
+            ptr(x) if act_in else None, ptr(gx), ptr(_as_float_storage(gw)) if gw is not None else None, B, Ci, Co, n,
+            K, act_in)
         return gx, gw, None
 
 
@@ -470,10 +448,9 @@ class _Spectral2d(torch.autograd.Function):
         Co, m1, m2 = w1.shape[1], w1.shape[2], w1.shape[3]
         out = torch.empty(B, Co, M, N, dtype=torch.float32, device=x.device)
         spec = torch.empty(lib.rpde_spectral2d_spec_elems(B, Ci, M, N, m1, m2), dtype=torch.float32, device=x.device)
-        nws = lib.rpde_spectral2d_ws_bytes(B, Ci, Co, M, N, m1, m2)
-        ws = workspace(nws, x.device)
-        check(lib.rpde_spectral2d_fwd(ptr(x), ptr(_as_float_storage(w1)), ptr(_as_float_storage(w2)), ptr(out), ptr(spec),
-                                      B, Ci, Co, M, N, m1, m2, act_in, ws.data_ptr(), nws, stream_ptr()), "spectral2d_fwd")
+        run("spectral2d_fwd", lib.rpde_spectral2d_ws_bytes(B, Ci, Co, M, N, m1, m2), x.device, ptr(x),
+            ptr(_as_float_storage(w1)), ptr(_as_float_storage(w2)), ptr(out), ptr(spec), B, Ci, Co, M, N, m1, m2,
+            act_in)
         ctx.save_for_backward(spec, w1, w2, x if act_in else x.new_empty(0))
         ctx.dims = (B, Ci, Co, M, N, m1, m2, act_in)
         return out
@@ -488,13 +465,10 @@ class _Spectral2d(torch.autograd.Function):
         need_w = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
         gw1 = torch.empty_like(w1) if need_w else None
         gw2 = torch.empty_like(w2) if need_w else None
-        nws = lib.rpde_spectral2d_ws_bytes(B, Ci, Co, M, N, m1, m2)
-        ws = workspace(nws, g.device)
-        check(lib.rpde_spectral2d_bwd(ptr(g), ptr(spec), ptr(_as_float_storage(w1)), ptr(_as_float_storage(w2)),
-                                      ptr(x) if act_in else None, ptr(gx),
-                                      ptr(_as_float_storage(gw1)) if need_w else None,
-                                      ptr(_as_float_storage(gw2)) if need_w else None,
-                                      B, Ci, Co, M, N, m1, m2, act_in, ws.data_ptr(), nws, stream_ptr()), "spectral2d_bwd")
+        run("spectral2d_bwd", lib.rpde_spectral2d_ws_bytes(B, Ci, Co, M, N, m1, m2), g.device, ptr(g), ptr(spec),
+            ptr(_as_float_storage(w1)), ptr(_as_float_storage(w2)), ptr(x) if act_in else None, ptr(gx),
+            ptr(_as_float_storage(gw1)) if need_w else None, ptr(_as_float_storage(gw2)) if need_w else None, B, Ci,
+            Co, M, N, m1, m2, act_in)
         return gx, gw1, gw2, None
 
 
@@ -546,10 +520,8 @@ class _Conv1x1(torch.autograd.Function):
         gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         gw = torch.empty_like(w2) if ctx.needs_input_grad[1] else None
         gb = torch.empty(Co, dtype=torch.float32, device=g.device) if (has_b and ctx.needs_input_grad[2]) else None
-        nws = lib.rpde_conv1x1_ws_bytes(B, Ci, Co, S)
-        ws = workspace(nws, g.device)
-        check(lib.rpde_conv1x1_bwd(ptr(x), ptr(w2), ptr(g), ptr(gx), ptr(gw), ptr(gb), B, Ci, Co, S, act_in, 0,
-                                   ws.data_ptr(), nws, stream_ptr()), "conv1x1_bwd")
+        run("conv1x1_bwd", lib.rpde_conv1x1_ws_bytes(B, Ci, Co, S), g.device, ptr(x), ptr(w2), ptr(g), ptr(gx),
+            ptr(gw), ptr(gb), B, Ci, Co, S, act_in, 0)
         return gx, (gw.reshape(wshape) if gw is not None else None), gb, None, (g if has_acc else None), None
 
 
@@ -586,11 +558,9 @@ def fnoblock2d_eval(x, w1, w2, wc, bc, act_out: str):
     wcf = _f32c(wc.detach()).reshape(Co, Ci)
     bcf = _f32c(bc.detach()) if bc is not None else None
     out = torch.empty(B, Co, M, N, dtype=torch.float32, device=x.device)
-    nws = lib.rpde_fnoblock2d_eval_ws_bytes(B, Ci, Co, M, N, m1, m2)
-    ws = workspace(nws, x.device)
-    check(lib.rpde_fnoblock2d_eval_fwd(ptr(x), ptr(_as_float_storage(w1.detach())), ptr(_as_float_storage(w2.detach())), ptr(wcf),
-                                       ptr(bcf), ptr(out), B, Ci, Co, M, N, m1, m2, ACT[act_out], ws.data_ptr(), nws,
-                                       stream_ptr()), "fnoblock2d_eval_fwd")
+    run("fnoblock2d_eval_fwd", lib.rpde_fnoblock2d_eval_ws_bytes(B, Ci, Co, M, N, m1, m2), x.device, ptr(x),
+        ptr(_as_float_storage(w1.detach())), ptr(_as_float_storage(w2.detach())), ptr(wcf), ptr(bcf), ptr(out), B, Ci,
+        Co, M, N, m1, m2, ACT[act_out])
     return out
 
 
@@ -613,12 +583,9 @@ def fnoblock2d_proj_eval(x, w1, w2, wc, bc, act_out: str, pw1, pb1, pw2, pb2):
     q1 = _f32c(pb1.detach()) if pb1 is not None else None
     q2 = _f32c(pb2.detach()) if pb2 is not None else None
     out = torch.empty(B, Cq, M, N, dtype=torch.float32, device=x.device)
-    nws = lib.rpde_fnoblock2d_eval_ws_bytes(B, Ci, Co, M, N, m1, m2)
-    ws = workspace(nws, x.device)
-    check(lib.rpde_fnoblock2d_proj_eval_fwd(ptr(x), ptr(_as_float_storage(w1.detach())), ptr(_as_float_storage(w2.detach())),
-                                            ptr(wcf), ptr(bcf), ptr(p1), ptr(q1), ptr(p2), ptr(q2), ptr(out), B, Ci, Co, M, N, m1,
-                                            m2, ACT[act_out], Cm, Cq, ws.data_ptr(), nws, stream_ptr()),
-          "fnoblock2d_proj_eval_fwd")
+    run("fnoblock2d_proj_eval_fwd", lib.rpde_fnoblock2d_eval_ws_bytes(B, Ci, Co, M, N, m1, m2), x.device, ptr(x),
+        ptr(_as_float_storage(w1.detach())), ptr(_as_float_storage(w2.detach())), ptr(wcf), ptr(bcf), ptr(p1),
+        ptr(q1), ptr(p2), ptr(q2), ptr(out), B, Ci, Co, M, N, m1, m2, ACT[act_out], Cm, Cq)
     return out
 
 
@@ -640,11 +607,9 @@ def fno2d_lift_block_eval(u, gx, gy, wl, bl, w1, w2, wc, bc, act_out: str):
     wcf = _f32c(wc.detach()).reshape(Co, C)
     bcf = _f32c(bc.detach()) if bc is not None else None
     out = torch.empty(B, Co, M, N, dtype=torch.float32, device=u.device)
-    nws = lib.rpde_fno2d_lift_block_eval_ws_bytes(B, C, Co, M, N, m1, m2)
-    ws = workspace(nws, u.device)
-    check(lib.rpde_fno2d_lift_block_eval_fwd(ptr(u), ptr(gx), ptr(gy), ptr(wlf), ptr(blf), ptr(_as_float_storage(w1.detach())),
-                                             ptr(_as_float_storage(w2.detach())), ptr(wcf), ptr(bcf), ptr(out), B, C, Co, M, N,
-                                             m1, m2, ACT[act_out], ws.data_ptr(), nws, stream_ptr()), "fno2d_lift_block_eval_fwd")
+    run("fno2d_lift_block_eval_fwd", lib.rpde_fno2d_lift_block_eval_ws_bytes(B, C, Co, M, N, m1, m2), u.device,
+        ptr(u), ptr(gx), ptr(gy), ptr(wlf), ptr(blf), ptr(_as_float_storage(w1.detach())),
+        ptr(_as_float_storage(w2.detach())), ptr(wcf), ptr(bcf), ptr(out), B, C, Co, M, N, m1, m2, ACT[act_out])
     return out
 
 
@@ -833,10 +798,8 @@ class _WRelL2(torch.autograd.Function):
         px, py, pw = ptr(x), ptr(y), ptr(omega)               # raises for CPU tensors: there is no fallback
         stats, rel, loss = _rel_outputs(B, x.device, reduction)
         spec = torch.empty(lib.rpde_wrel_l2_spec_elems(B, Cc, M, N), dtype=torch.float32, device=x.device)
-        nws = lib.rpde_wrel_l2_ws_bytes(B, Cc, M, N)
-        ws = workspace(nws, x.device)
-        check(lib.rpde_wrel_l2_fwd(px, py, pw, ptr(rel), ptr(loss), ptr(stats), ptr(spec), B, Cc, M, N, int(size_average),
-                                   ws.data_ptr(), nws, stream_ptr()), "wrel_l2_fwd")
+        run("wrel_l2_fwd", lib.rpde_wrel_l2_ws_bytes(B, Cc, M, N), x.device, px, py, pw, ptr(rel), ptr(loss),
+            ptr(stats), ptr(spec), B, Cc, M, N, int(size_average))
         ctx.save_for_backward(spec, omega, stats)
         ctx.meta = (tuple(x.shape), B, Cc, M, N, size_average, reduction)
         return loss if reduction else rel
@@ -848,10 +811,8 @@ class _WRelL2(torch.autograd.Function):
         shape, B, Cc, M, N, size_average, reduction = ctx.meta
         g = _f32c(g)
         gx = torch.empty(shape, dtype=torch.float32, device=spec.device)
-        nws = lib.rpde_wrel_l2_ws_bytes(B, Cc, M, N)
-        ws = workspace(nws, spec.device)
-        check(lib.rpde_wrel_l2_bwd(ptr(spec), ptr(omega), ptr(stats), *_upstream(g, reduction), ptr(gx), B, Cc, M, N,
-                                   int(size_average), ws.data_ptr(), nws, stream_ptr()), "wrel_l2_bwd")
+        run("wrel_l2_bwd", lib.rpde_wrel_l2_ws_bytes(B, Cc, M, N), spec.device, ptr(spec), ptr(omega), ptr(stats),
+            *_upstream(g, reduction), ptr(gx), B, Cc, M, N, int(size_average))
         return gx, None, None, None, None, None
 
 
@@ -875,9 +836,8 @@ def resize1d(x: torch.Tensor, out_size: int) -> torch.Tensor:
     n = x.shape[-1]
     rows = x.numel() // n
     out = torch.empty(*x.shape[:-1], int(out_size), dtype=torch.float32, device=x.device)
-    nws = lib.rpde_resize1d_ws_bytes(rows, n, int(out_size))
-    ws = workspace(nws, x.device)
-    check(lib.rpde_resize1d(ptr(x), ptr(out), rows, n, int(out_size), ws.data_ptr(), nws, stream_ptr()), "resize1d")
+    run("resize1d", lib.rpde_resize1d_ws_bytes(rows, n, int(out_size)), x.device, ptr(x), ptr(out), rows, n,
+        int(out_size))
     return out
 
 
@@ -889,9 +849,7 @@ def resize2d(x: torch.Tensor, out_size) -> torch.Tensor:
     Mo, No = int(out_size[0]), int(out_size[1])
     rows = x.numel() // (M * N)
     out = torch.empty(*x.shape[:-2], Mo, No, dtype=torch.float32, device=x.device)
-    nws = lib.rpde_resize2d_ws_bytes(rows, M, N, Mo, No)
-    ws = workspace(nws, x.device)
-    check(lib.rpde_resize2d(ptr(x), ptr(out), rows, M, N, Mo, No, ws.data_ptr(), nws, stream_ptr()), "resize2d")
+    run("resize2d", lib.rpde_resize2d_ws_bytes(rows, M, N, Mo, No), x.device, ptr(x), ptr(out), rows, M, N, Mo, No)
     return out
 
 
@@ -971,9 +929,8 @@ def freq_energy1d(pred: torch.Tensor, target: torch.Tensor, acc: Optional[torch.
     rows = p.numel() // n
     k = min(int(num_modes or n // 2 + 1), n // 2 + 1)             # None or 0: every mode, as the reference's `or`
     acc = _freq_acc(acc, k, p.device)
-    nws = lib.rpde_freq_energy1d_ws_bytes(rows, n, k)
-    ws = workspace(nws, p.device)
-    check(lib.rpde_freq_energy1d(ptr(p), ptr(t), acc.data_ptr(), rows, n, k, ws.data_ptr(), nws, stream_ptr()), "freq_energy1d")
+    run("freq_energy1d", lib.rpde_freq_energy1d_ws_bytes(rows, n, k), p.device, ptr(p), ptr(t), acc.data_ptr(), rows,
+        n, k)
     return acc
 
 
@@ -992,10 +949,8 @@ def freq_energy2d(pred: torch.Tensor, target: torch.Tensor, num_radial_bins: int
     nb = int(num_radial_bins)
     bins = _radial_bins_on(p.device, H, W, nb)
     acc = _freq_acc(acc, nb, p.device)
-    nws = lib.rpde_freq_energy2d_ws_bytes(images, H, W)
-    ws = workspace(nws, p.device)
-    check(lib.rpde_freq_energy2d(ptr(p), ptr(t), bins.data_ptr(), acc.data_ptr(), images, H, W, nb, ws.data_ptr(), nws,
-                                 stream_ptr()), "freq_energy2d")
+    run("freq_energy2d", lib.rpde_freq_energy2d_ws_bytes(images, H, W), p.device, ptr(p), ptr(t), bins.data_ptr(),
+        acc.data_ptr(), images, H, W, nb)
     return acc
 
 
@@ -1174,9 +1129,8 @@ class _BandEnergy(torch.autograd.Function):
         keep = ctx.needs_input_grad[0]
         E = torch.empty(B, T.J, dtype=torch.float32, device=x.device)
         spec = torch.empty(lib.rpde_band_energy_spec_elems(B, Cc, M, N), dtype=torch.float32, device=x.device) if keep else None
-        ws = workspace(nws, x.device)
-        check(lib.rpde_band_energy_fwd(px, py, T.entries.data_ptr(), T.start.data_ptr(), T.n_entries, ptr(E), ptr(spec),
-                                       B, Cc, M, N, T.J, ws.data_ptr(), nws, stream_ptr()), "band_energy_fwd")
+        run("band_energy_fwd", nws, x.device, px, py, T.entries.data_ptr(), T.start.data_ptr(), T.n_entries, ptr(E),
+            ptr(spec), B, Cc, M, N, T.J)
         if keep:
             ctx.save_for_backward(spec)
         ctx.meta = (tuple(x.shape), B, Cc, M, N, T)
@@ -1189,10 +1143,8 @@ class _BandEnergy(torch.autograd.Function):
         shape, B, Cc, M, N, T = ctx.meta
         gE = _f32c(gE)
         gx = torch.empty(shape, dtype=torch.float32, device=spec.device)
-        nws = lib.rpde_band_energy_ws_bytes(B, Cc, M, N, T.J)
-        ws = workspace(nws, spec.device)
-        check(lib.rpde_band_energy_bwd(ptr(spec), T.band.data_ptr(), ptr(gE), ptr(gx), B, Cc, M, N, T.J, ws.data_ptr(), nws,
-                                       stream_ptr()), "band_energy_bwd")
+        run("band_energy_bwd", lib.rpde_band_energy_ws_bytes(B, Cc, M, N, T.J), spec.device, ptr(spec),
+            T.band.data_ptr(), ptr(gE), ptr(gx), B, Cc, M, N, T.J)
         return gx, None, None, None
 
 
@@ -1259,9 +1211,7 @@ def _grf(what: str, d: int, noise: torch.Tensor, sqrt_eig: torch.Tensor) -> torc
     pn, ps = ptr(noise), ptr(sqrt_eig)                     # raises for CPU tensors: there is no fallback
     dims = _grid(noise[..., 0], what, d)
     out = torch.empty(dims, dtype=torch.float32, device=noise.device)
-    nws = getattr(lib, f"rpde_{what}_ws_bytes")(*dims)
-    ws = workspace(nws, noise.device)
-    check(getattr(lib, f"rpde_{what}")(pn, ps, ptr(out), *dims, ws.data_ptr(), nws, stream_ptr()), what)
+    run(what, getattr(lib, f"rpde_{what}_ws_bytes")(*dims), noise.device, pn, ps, ptr(out), *dims)
     return out
 
 
@@ -1307,7 +1257,7 @@ def _ns2d_forcing(what: str, f: torch.Tensor, c_g: torch.Tensor, B: int, M: int,
     g_h = torch.empty_like(f_h)
     f3 = f.view(fb, M, N)
     for i in range(fb):
-        check(lib.rpde_ns2d_rfft2(ptr(f3[i]), ptr(f_h[i * per:(i + 1) * per]), 1, M, N, ws.data_ptr(), nws, st), "ns2d_rfft2")
+        run("ns2d_rfft2", nws, ws, ptr(f3[i]), ptr(f_h[i * per:(i + 1) * per]), 1, M, N)
     check(lib.rpde_ns2d_scale(ptr(f_h), ptr(c_g), ptr(g_h), fb, M, N, st), "ns2d_scale")
     return g_h, int(f.dim() == 3)
 
@@ -1326,17 +1276,15 @@ def ns2d_solve(w0: torch.Tensor, f: torch.Tensor, visc: float, dt: float, steps:
     dev = w0.device
     c_w, c_f, c_g, inv_lap = (t.to(dev) for t in ns2d_tables(M, N, visc, dt))
     nws = lib.rpde_ns2d_ws_bytes(B, M, N)
-    ws = workspace(nws, dev)
-    st = stream_ptr()
+    ws = workspace(nws, dev)                               # one workspace for every call of the solve
     g_h, batched = _ns2d_forcing("ns2d_solve", f, c_g, B, M, N, ws, nws)
     W = torch.empty(lib.rpde_ns2d_spec_elems(B, M, N), dtype=torch.float32, device=dev)
-    check(lib.rpde_ns2d_rfft2(pw, ptr(W), B, M, N, ws.data_ptr(), nws, st), "ns2d_rfft2")
+    run("ns2d_rfft2", nws, ws, pw, ptr(W), B, M, N)
     n_rec = steps // record_every
     snaps = torch.empty(max(n_rec, 1), B, M, N, dtype=torch.float32, device=dev)
     for c in range(n_rec):
-        check(lib.rpde_ns2d_steps(ptr(W), ptr(g_h), batched, ptr(c_w), ptr(c_f), ptr(inv_lap), B, M, N,
-                                  record_every, ws.data_ptr(), nws, st), "ns2d_steps")
-        check(lib.rpde_ns2d_irfft2(ptr(W), ptr(snaps[c]), B, M, N, ws.data_ptr(), nws, st), "ns2d_irfft2")
+        run("ns2d_steps", nws, ws, ptr(W), ptr(g_h), batched, ptr(c_w), ptr(c_f), ptr(inv_lap), B, M, N, record_every)
+        run("ns2d_irfft2", nws, ws, ptr(W), ptr(snaps[c]), B, M, N)
     return snaps[:n_rec].permute(1, 2, 3, 0).contiguous()
 
 
@@ -1367,7 +1315,7 @@ def _nsc2d_state(what: str, w: torch.Tensor, c: torch.Tensor):
     ws = workspace(nws, w.device)
     S = torch.empty(lib.rpde_ns2d_spec_elems(2 * B, M, N), dtype=torch.float32, device=w.device)
     wc = torch.cat([w, c], dim=0)
-    check(lib.rpde_ns2d_rfft2(ptr(wc), ptr(S), 2 * B, M, N, ws.data_ptr(), nws, stream_ptr()), "ns2d_rfft2")
+    run("ns2d_rfft2", nws, ws, ptr(wc), ptr(S), 2 * B, M, N)
     return lib, B, M, N, ws, nws, S
 
 
@@ -1378,7 +1326,7 @@ def nsc2d_fields(w: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
     lib, B, M, N, ws, nws, S = _nsc2d_state("nsc2d_fields", w, c)
     inv_lap = ns2d_tables(M, N, 0.0, 0.0)[3].to(S.device)
     out = torch.empty(B, 3, M, N, dtype=torch.float32, device=S.device)
-    check(lib.rpde_nsc2d_fields(ptr(S), ptr(inv_lap), ptr(out), B, M, N, ws.data_ptr(), nws, stream_ptr()), "nsc2d_fields")
+    run("nsc2d_fields", nws, ws, ptr(S), ptr(inv_lap), ptr(out), B, M, N)
     return out
 
 
@@ -1397,16 +1345,15 @@ def nsc2d_solve(w0: torch.Tensor, c0: torch.Tensor, f: torch.Tensor, visc: float
     lib, B, M, N, ws, nws, S = _nsc2d_state("nsc2d_solve", w0, c0)
     dev = S.device
     c_w, c_f, d_w, d_f, c_g, inv_lap = (t.to(dev) for t in nsc2d_tables(M, N, visc, kappa, dt))
-    st = stream_ptr()
     g_h, batched = _ns2d_forcing("nsc2d_solve", f, c_g, B, M, N, ws, nws)
     n_rec = steps // record_every
     fields = torch.empty(max(n_rec, 1), B, 3, M, N, dtype=torch.float32, device=dev)
     vort = torch.empty(max(n_rec, 1), B, M, N, dtype=torch.float32, device=dev)
     for c in range(n_rec):
-        check(lib.rpde_nsc2d_steps(ptr(S), ptr(g_h), batched, ptr(c_w), ptr(c_f), ptr(d_w), ptr(d_f),
-                                   ptr(inv_lap), float(beta), B, M, N, record_every, ws.data_ptr(), nws, st), "nsc2d_steps")
-        check(lib.rpde_nsc2d_fields(ptr(S), ptr(inv_lap), ptr(fields[c]), B, M, N, ws.data_ptr(), nws, st), "nsc2d_fields")
-        check(lib.rpde_ns2d_irfft2(ptr(S), ptr(vort[c]), B, M, N, ws.data_ptr(), nws, st), "ns2d_irfft2")
+        run("nsc2d_steps", nws, ws, ptr(S), ptr(g_h), batched, ptr(c_w), ptr(c_f), ptr(d_w), ptr(d_f), ptr(inv_lap),
+            float(beta), B, M, N, record_every)
+        run("nsc2d_fields", nws, ws, ptr(S), ptr(inv_lap), ptr(fields[c]), B, M, N)
+        run("ns2d_irfft2", nws, ws, ptr(S), ptr(vort[c]), B, M, N)
     return fields[:n_rec].transpose(0, 1).contiguous(), vort[:n_rec].transpose(0, 1).contiguous()
 
 
@@ -1523,9 +1470,9 @@ def etd1d_solve(u0: torch.Tensor, tables, steps: int, record_every: int) -> torc
     tables = tuple(tables)
     shapes = [tuple(t.shape) for t in tables]
     if shapes == [(kp,)] * 7:
-        steps_call, name = lib.rpde_etd1d_steps, "etd1d_steps"
+        name = "etd1d_steps"
     elif shapes == [(2, kp)] * 6 + [(kp,)]:
-        steps_call, name = lib.rpde_etd1d_steps_cx, "etd1d_steps_cx"
+        name = "etd1d_steps_cx"
     else:
         raise ValueError(f"etd1d_solve: expected the seven [{kp}] tables of etd1d_tables(N={N}, ...) or the six [2, {kp}] "
                          f"tables and g [{kp}] of etd1d_tables_cx(N={N}, ...)")
@@ -1540,7 +1487,7 @@ def etd1d_solve(u0: torch.Tensor, tables, steps: int, record_every: int) -> torc
     n_rec = steps // record_every
     snaps = torch.empty(max(n_rec, 1), B, N, dtype=torch.float32, device=dev)
     for c in range(n_rec):
-        check(steps_call(ptr(U), *(ptr(t) for t in tabs), B, N, record_every, ws.data_ptr(), nws, st), name)
+        run(name, nws, ws, ptr(U), *(ptr(t) for t in tabs), B, N, record_every)
         check(lib.rpde_etd1d_irfft(ptr(U), ptr(snaps[c]), B, N, st), "etd1d_irfft")
     return snaps[:n_rec].permute(1, 0, 2).contiguous()
 
@@ -1601,9 +1548,8 @@ class _EtdResidual(torch.autograd.Function):
         aff = _residual_affine(affine)
         stats, rel, loss = _rel_outputs(B, dev, reduction)
         spec = torch.empty(lib.rpde_etd_residual_spec_elems(B, N), dtype=torch.float32, device=dev)
-        ws = workspace(nws, dev)
-        check(lib.rpde_etd_residual_fwd(pp, px, ptr(E), ptr(m0), ptr(m1), aff, ptr(rel), ptr(loss), ptr(stats), ptr(spec),
-                                        B, N, int(size_average), ws.data_ptr(), nws, stream_ptr()), "etd_residual_fwd")
+        run("etd_residual_fwd", nws, dev, pp, px, ptr(E), ptr(m0), ptr(m1), aff, ptr(rel), ptr(loss), ptr(stats), ptr(spec),
+            B, N, int(size_average))
         ctx.save_for_backward(p2, spec, stats, m1)
         ctx.meta = (shape, B, N, affine, size_average, reduction)
         return loss if reduction else rel
@@ -1615,11 +1561,8 @@ class _EtdResidual(torch.autograd.Function):
         shape, B, N, affine, size_average, reduction = ctx.meta
         g = _f32c(g)
         gp = torch.empty(shape, dtype=torch.float32, device=p2.device)
-        nws = lib.rpde_etd_residual_ws_bytes(B, N)
-        ws = workspace(nws, p2.device)
-        check(lib.rpde_etd_residual_bwd(ptr(p2), ptr(spec), ptr(m1), _residual_affine(affine), ptr(stats),
-                                        *_upstream(g, reduction), ptr(gp), B, N, int(size_average), ws.data_ptr(), nws,
-                                        stream_ptr()), "etd_residual_bwd")
+        run("etd_residual_bwd", lib.rpde_etd_residual_ws_bytes(B, N), p2.device, ptr(p2), ptr(spec), ptr(m1),
+            _residual_affine(affine), ptr(stats), *_upstream(g, reduction), ptr(gp), B, N, int(size_average))
         return gp, None, None, None, None, None, None, None
 
 
@@ -1694,9 +1637,7 @@ def sep2d(x: torch.Tensor, L: torch.Tensor, R: torch.Tensor) -> torch.Tensor:
     if tuple(L.shape) != (s, s) or tuple(R.shape) != (s, s):
         raise ValueError(f"sep2d: tables {tuple(L.shape)} and {tuple(R.shape)}, expected {(s, s)}")
     out = torch.empty_like(x)
-    nws = B * s * s * 4 + 256
-    ws = workspace(nws, x.device)
-    check(lib.rpde_sep2d(px, pl, pr, ptr(out), B, s, ws.data_ptr(), nws, stream_ptr()), "sep2d")
+    run("sep2d", B * s * s * 4 + 256, x.device, px, pl, pr, ptr(out), B, s)
     return out
 
 
@@ -1739,10 +1680,8 @@ def darcy2d_solve(a: torch.Tensor, f: torch.Tensor, iterations: int = 24, tol: f
     u = torch.empty_like(a)
     rel = torch.empty(B, dtype=torch.float32, device=dev)
     frozen_at = torch.empty(B, dtype=torch.int32, device=dev)
-    nws = lib.rpde_darcy2d_ws_bytes(B, s)
-    ws = workspace(nws, dev)
-    check(lib.rpde_darcy2d_solve(pa, pf, int(f.dim() == 3), ptr(S), ptr(inv_lambda), ptr(u), ptr(rel), frozen_at.data_ptr(),
-                                 B, s, iterations, tol, ws.data_ptr(), nws, stream_ptr()), "darcy2d_solve")
+    run("darcy2d_solve", lib.rpde_darcy2d_ws_bytes(B, s), dev, pa, pf, int(f.dim() == 3), ptr(S), ptr(inv_lambda),
+        ptr(u), ptr(rel), frozen_at.data_ptr(), B, s, iterations, tol)
     return u, rel, frozen_at
 
 
