@@ -280,12 +280,13 @@ int rpde_feedforward_bwd(const rpde_ff_params* p, const float* x, const float* c
                          float* const* grad_biases, float* grad_gamma, float* grad_beta, int64_t P, void* ws,
                          size_t ws_bytes, void* stream) {
   RPDE_CHECK_ARG(p && x && z_last && grad_out && P > 0, "feedforward_bwd: bad arguments");
-  RPDE_CHECK_ARG(p->n_layers == 1 || (hs && ds), "feedforward_bwd: saved hidden tensors missing");
   RPDE_CHECK_ARG(P < (1L << 31), "feedforward_bwd: too many points for one call");
   const int L = p->n_layers;
   const int hid = ff_hid(*p);
   // (any depth: folds and splits beyond the one-launch capacities of FoldJobs / SplitJobs run per layer)
   const bool fused = ff3_fused_ok(p, P) && hs && hs[0] && hs[1];
+  // (ds NULL is the fused path's recompute mode, as rpde.h states it; the per-GEMM path needs the stored derivatives)
+  RPDE_CHECK_ARG(p->n_layers == 1 || (hs && (ds || fused)), "feedforward_bwd: saved hidden tensors missing");
   RPDE_CARVE("feedforward_bwd", FfBwdWork, wk, ws, ws_bytes, *p, P, fused);
   hipStream_t st = as_stream(stream);
   float *buf0 = wk.buf0, *buf1 = wk.buf1, *small = wk.small, *tailws = wk.tailws;
