@@ -591,6 +591,46 @@ int rpde_etd_residual_bwd(const float* p, const float* spec_r, const float* m1, 
                           const float* grad_loss, const float* grad_rel, float* grad_p, int B, int N, int size_average,
                           void* ws, size_t ws_bytes, void* stream);
 
+/* ---- equation-residual loss of the 2-D vorticity equation (csrc/ns_residual.hip; utils/loss.py VorticityResidualLoss;
+ * no counterpart in the reference): does the one-step map x = w(t) -> p ~ w(t + D) satisfy the equation of the
+ * Navier-Stokes generator above, w_t = -visc lap w - A(w) + f?  Grid, W = rfft2(w), k1, k2, lap, dealias and psi as in
+ * the generator block, and A(w) = dealias rfft2(q w_x + v w_y) its discrete advection.  The exponential trapezoidal
+ * rule of the 1-D block above with z = -D visc lap (all real):
+ *   r^ = d^ - (E - 1) x^ - (m0 + m1) f^ + m0 A(x~) + m1 A(p~),   d = p~ - x~ formed in physical space,
+ *   E = e^z,  m0 = D (phi1 - phi2),  m1 = D phi2  (phi1, phi2 on the 64-point contour),
+ *   rel[b] = sqrt(E_r[b]) / (sqrt(E_x[b]) + 1e-8),  E(z)[b] = sum c |z^|^2 / (M N),  c = 1 on the columns kx = 0, N/2, else 2.
+ * The caller forms the tables in float64 and rounds them once (rpde.ops.ns2d_residual_tables): em1 = E - 1 (expm1),
+ * m0 = m0 dealias, m1 = m1 dealias, inv_lap = 1 / lap (lap[0,0] -> 1), each [M][kp] floats with the padded columns zero;
+ * forcing_spec: the spectrum (m0 + m1) rfft2(f) of one forcing field for the batch, [M][re|im][kp], not de-aliased (the
+ * generator does not), or NULL.  affine, rel, loss, stats and the upstream gradients as in the 1-D block; spec (the
+ * spec_elems query's count of floats: [r^ | P^], 2 B images) is kept for backward.
+ * Forward: x^ and d^ (d formed per point in float64, never rounded) as separable float64 analyses (rows, then columns)
+ * that stay in float64 for the residual -- r^ is a remainder of 1e-3 |x| and an fp32 transform's absolute error in x^
+ * would enter through (E - 1) x^ --; P^ = X^ + D^ rounded once, the generator's fan-out of [X^ | P^] to eight derivative
+ * spectra, one inverse transform of 8 B images, the two advection products, one forward transform of 2 B, the residual
+ * kernel (float64 partial sums per (sample, slot), slots a function of the grid alone) and the family's final kernel.
+ * Backward, the exact adjoint of the discrete operator: g = irfft2(m1 r^) and the four fields of p~ rebuilt from P^ in
+ * one inverse transform of 5 B images, the four products, one forward transform of 4 B,
+ *   G^ = r^ + conj(2 pi i k2 / lap) rfft2(g w_x) + conj(-2 pi i k1 / lap) rfft2(g w_y) + conj(2 pi i k1) rfft2(g q)
+ *           + conj(2 pi i k2) rfft2(g v),     grad_p = a_p coef_b irfft2(G^).
+ * rpde_ns2d_residual_spectrum is the float64 analysis alone: spec64 and spec32 [B][M][re|im][kp] (doubles, floats) of
+ * a x + b, affine = two host floats (a, b) or NULL.
+ * Even M, N in 4 .. 4096 and 8 B images within the half-spectrum layer's limits (8 B <= 65535, 32 B max(M, N) < 2^31):
+ * the two queries return 0 otherwise.  Fields, tables and spectra 16-byte aligned, the workspace (rpde_ns2d_residual_work_bytes
+ * serves the three calls: one layout per entry, the largest of them) 256-byte aligned.  No atomics, no host synchronisation, everything on the caller's stream (the first use
+ * of a grid builds its plans: it allocates and synchronises once).  Argument errors are reported before any device work. */
+size_t rpde_ns2d_residual_work_bytes(int B, int M, int N);
+size_t rpde_ns2d_residual_spec_elems(int B, int M, int N);
+int rpde_ns2d_residual_spectrum(const float* x, const float* affine, double* spec64, float* spec32, int B, int M, int N,
+                                void* ws, size_t ws_bytes, void* stream);
+int rpde_ns2d_residual_fwd(const float* p, const float* x, const float* em1, const float* m0, const float* m1,
+                           const float* inv_lap, const float* forcing_spec, const float* affine, float* rel, float* loss,
+                           float* stats, float* spec, int B, int M, int N, int size_average, void* ws, size_t ws_bytes,
+                           void* stream);
+int rpde_ns2d_residual_bwd(const float* spec, const float* m1, const float* inv_lap, const float* affine, const float* stats,
+                           const float* grad_loss, const float* grad_rel, float* grad_p, int B, int M, int N,
+                           int size_average, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- Darcy flow generator (csrc/darcy.hip; reference: dataloaders/darcy_loader.py and the piececonst_* files of
  * load_darcy_data_from_mat): -div(a grad u) = f on the unit square, u = 0 on the boundary, s x s cells with centres
  * x_i = (i + 1/2) / s, a and u [B, s, s] at the centres.  Finite volumes: an interior face between cells c and n weighs

@@ -73,9 +73,11 @@ def training_loss(training, dims: int, dataset=None):
       training.loss=spectrum  relative L2 + training.loss_lambda (0.1) x the mismatch of the energy per band
                               (SpectrumMatchingLoss) with training.loss_spectrum_floor (1e-6)
       training.loss=residual  relative L2 + training.loss_lambda (0.1) x the equation residual of the one-step map
-                              (EquationResidualLoss, 1-D only), built from the data set's `equation:` mapping
+                              (EquationResidualLoss in 1-D), built from the data set's `equation:` mapping
                               {c1, c2, c3, c4, advect, length, interval} (length and interval required, the rest
-                              default to 0 and advect to 1); run() sets its decode maps (residual_affine below)
+                              default to 0 and advect to 1); in 2-D the mapping {kind: ns_vorticity, viscosity,
+                              interval, forcing} (forcing: reference, or none) builds VorticityResidualLoss, and a
+                              2-D mapping without that kind is refused; run() sets the decode maps (residual_affine)
     band and spectrum take training.loss_bands (octave; radial in 2-D, modes in 1-D) and training.loss_num_bands, and
     the 1-D rollout record then also carries the octave band energies along the rollout.  Anything else: SystemExit.
     Validation, the test score and the sweeps stay relative L2."""
@@ -88,10 +90,24 @@ def training_loss(training, dims: int, dataset=None):
         length = [float(v) for v in length] if isinstance(length, (list, tuple)) else float(length)
         return name, SpectralRelativeL2Loss(dims, "sobolev", s=float(training.get("loss_s", 1.0)), length=length)
     if name == "residual":
-        from utils.loss import EquationResidualLoss, RelativeL2Loss, SumLoss
-        if dims != 1:
-            raise SystemExit(f"training.loss=residual: the equation residual is one-dimensional, got dims={dims}")
+        from utils.loss import EquationResidualLoss, RelativeL2Loss, SumLoss, VorticityResidualLoss
         eq = None if dataset is None else dataset.get("equation")
+        if dims == 2 and eq and dict(eq).get("kind") == "ns_vorticity":
+            eq = dict(eq)
+            unknown = sorted(set(eq) - {"kind", "viscosity", "interval", "forcing"})
+            if unknown or "viscosity" not in eq or "interval" not in eq:
+                raise SystemExit(f"training.loss=residual: a ns_vorticity equation needs viscosity and interval and takes "
+                                 f"forcing (reference, or none); got {sorted(eq)}")
+            forcing = eq.get("forcing")
+            forcing = None if forcing is None or str(forcing).lower() in ("none", "null") else str(forcing)
+            try:
+                res = VorticityResidualLoss(float(eq["viscosity"]), float(eq["interval"]), forcing=forcing)
+            except ValueError as e:
+                raise SystemExit(f"training.loss=residual: {e}")
+            return name, SumLoss([(1.0, RelativeL2Loss()), (float(training.get("loss_lambda", 0.1)), res)])
+        if dims != 1:
+            raise SystemExit(f"training.loss=residual: the equation residual is one-dimensional, got dims={dims} (a 2-D data "
+                             "set names the vorticity equation: `equation: {kind: ns_vorticity, viscosity, interval, forcing}`)")
         if not eq:
             raise SystemExit("training.loss=residual: the dataset config has no `equation:` mapping "
                              "({c1, c2, c3, c4, advect, length, interval})")
@@ -125,9 +141,9 @@ def residual_affine(loss_fn, x_normalizer, y_normalizer, use_normalizer: bool, m
     asked in physical units: the input is decoded with the x-statistics; the prediction with the y-statistics, unless
     training.use_normalizer is true -- train() has decoded it by then and its map is the identity.  Only one global
     affine map (SimpleNormalizer) folds into the loss: point-wise or min-max normalisers are a SystemExit."""
-    from utils.loss import EquationResidualLoss
+    from utils.loss import EquationResidualLoss, VorticityResidualLoss
     from utils.normalizers import scalar_stats
-    terms = [t for t in getattr(loss_fn, "terms", [loss_fn]) if isinstance(t, EquationResidualLoss)]
+    terms = [t for t in getattr(loss_fn, "terms", [loss_fn]) if isinstance(t, (EquationResidualLoss, VorticityResidualLoss))]
     if not terms:
         return
     if minmax:

@@ -1215,22 +1215,30 @@ def _grf(what: str, d: int, noise: torch.Tensor, sqrt_eig: torch.Tensor) -> torc
     return out
 
 
-def ns2d_tables(M: int, N: int, visc: float, dt: float):
-    """(c_w, c_f, c_g, inv_lap): the step's coefficient tables, float32 [M, kp] host tensors (kp = N//2+1 rounded up to
-    4, padded columns zero), formed in float64 and rounded once.  k1 = fftfreq(M) M (signed, Nyquist -M/2),
-    k2 = 0 .. N/2, lap = 4 pi^2 (k1^2 + k2^2), a = dt visc lap / 2, dealias = |k1| <= (2/3)(M/2) and |k2| <= (2/3)(N/2):
-    c_w = (1 - a)/(1 + a), c_f = dt dealias/(1 + a), c_g = dt/(1 + a), inv_lap = 1/lap with the mean mode's lap set to
-    1 for this division only."""
+def _ns2d_symbols(M: int, N: int):
+    """(lap, dealias, poisson): float64 [M, K] tables of the half spectrum of an M x N grid, K = N//2+1 -- k1 = fftfreq(M) M
+    (signed, Nyquist -M/2), k2 = 0 .. N/2, lap = 4 pi^2 (k1^2 + k2^2), dealias = |k1| <= (2/3)(M/2) and |k2| <= (2/3)(N/2),
+    poisson = lap with the mean mode's entry set to 1"""
     import math
     M, N = int(M), int(N)
     K = N // 2 + 1
     k1 = (torch.fft.fftfreq(M, dtype=torch.float64) * M).round().view(M, 1)
     k2 = torch.arange(K, dtype=torch.float64).view(1, K)
     lap = 4.0 * math.pi ** 2 * (k1 ** 2 + k2 ** 2)
-    a = 0.5 * float(dt) * float(visc) * lap
     dealias = ((k1.abs() <= (2.0 / 3.0) * (M // 2)) & (k2.abs() <= (2.0 / 3.0) * (N // 2))).to(torch.float64)
     poisson = lap.clone()
     poisson[0, 0] = 1.0
+    return lap, dealias, poisson
+
+
+def ns2d_tables(M: int, N: int, visc: float, dt: float):
+    """(c_w, c_f, c_g, inv_lap): the step's coefficient tables, float32 [M, kp] host tensors (kp = N//2+1 rounded up to
+    4, padded columns zero), formed in float64 and rounded once.  k1 = fftfreq(M) M (signed, Nyquist -M/2),
+    k2 = 0 .. N/2, lap = 4 pi^2 (k1^2 + k2^2), a = dt visc lap / 2, dealias = |k1| <= (2/3)(M/2) and |k2| <= (2/3)(N/2):
+    c_w = (1 - a)/(1 + a), c_f = dt dealias/(1 + a), c_g = dt/(1 + a), inv_lap = 1/lap with the mean mode's lap set to
+    1 for this division only."""
+    lap, dealias, poisson = _ns2d_symbols(M, N)
+    a = 0.5 * float(dt) * float(visc) * lap
     return tuple(_padded(t) for t in ((1.0 - a) / (1.0 + a), float(dt) * dealias / (1.0 + a), float(dt) / (1.0 + a),
                                       1.0 / poisson))
 
@@ -1362,6 +1370,22 @@ def nsc2d_solve(w0: torch.Tensor, c0: torch.Tensor, f: torch.Tensor, visc: float
 # rpde_grf1d; data_generation/burgers_1d.py, ks_1d.py and random_fields.py are the callers).  Data production: no
 # autograd, GPU tensors only, no CPU fallback.
 # ----------------------------------------------------------------------------
+def _contour(z: torch.Tensor, full_circle: bool):
+    """(LR, mean): LR = z[..., None] + r_m over the Kassam-Trefethen contour points r_m -- the 32 points of the upper half
+    circle with Re<.> of the mean for real z, the full circle's 64 points with the complex mean otherwise -- and the
+    mean over them, for z of any shape"""
+    import math
+    points = 64 if full_circle else 32
+    m = torch.arange(1, points + 1, dtype=torch.float64)
+    r = torch.polar(torch.ones(points, dtype=torch.float64), (2.0 if full_circle else 1.0) * math.pi * (m - 0.5) / points)
+    LR = z.unsqueeze(-1).to(torch.complex128) + r
+
+    def mean(t):
+        return t.mean(dim=-1) if full_circle else t.mean(dim=-1).real
+
+    return LR, mean
+
+
 def _etd1d_contour(what: str, N, length, dt, symbol, advect, dealias, full_circle: bool):
     """What every table of the 1-D ETD family starts from: z = dt symbol(kappa) [K], LR = z + r_m [K, points] over the
     Kassam-Trefethen contour points r_m, the mean over them and the float64 g [K].  For real z the 32 points of the upper
@@ -1377,14 +1401,7 @@ def _etd1d_contour(what: str, N, length, dt, symbol, advect, dealias, full_circl
     n = torch.arange(K, dtype=torch.float64)
     kappa = (2.0 * math.pi / float(length)) * n
     z = float(dt) * symbol(kappa)
-    points = 64 if full_circle else 32
-    m = torch.arange(1, points + 1, dtype=torch.float64)
-    r = torch.polar(torch.ones(points, dtype=torch.float64), (2.0 if full_circle else 1.0) * math.pi * (m - 0.5) / points)
-    LR = z.view(K, 1).to(torch.complex128) + r.view(1, points)
-
-    def mean(t):
-        return t.mean(dim=1) if full_circle else t.mean(dim=1).real
-
+    LR, mean = _contour(z, full_circle)
     keep = (n <= (2.0 / 3.0) * (N // 2)).to(torch.float64) if dealias else torch.ones(K, dtype=torch.float64)
     g = -(float(advect) / 2.0) * kappa * keep
     g[N // 2] = 0.0
@@ -1594,6 +1611,140 @@ def etd1d_residual(pred, x, tables, affine=None, size_average: bool = True, redu
     E, m0, m1 = (_f32c(t.detach().to(pred.device)) for t in tables)
     return _EtdResidual.apply(pred, x, E, m0, m1, None if affine is None else tuple(float(v) for v in affine),
                               bool(size_average), bool(reduction))
+
+
+# ----------------------------------------------------------------------------
+# equation-residual loss of the 2-D vorticity equation (csrc/ns_residual.hip, rpde_ns2d_residual_*; utils/loss.py
+# VorticityResidualLoss).  Forward and backward on the device, GPU tensors only, no CPU fallback.
+# ----------------------------------------------------------------------------
+def _ns2d_residual_phi(what: str, M, N, visc, interval):
+    """(z, phi1, phi2, dealias, poisson), float64 [M, K]: z = -interval visc lap on the grid of ns2d_tables and the two
+    phi functions of the exponential trapezoidal rule on the full circle's 64 contour points (z is real: so are they)"""
+    import math
+    M, N = int(M), int(N)
+    if M < 4 or N < 4 or M % 2 or N % 2:
+        raise ValueError(f"{what}: M and N must be even and >= 4, got {M} x {N}")
+    if not (math.isfinite(float(visc)) and float(visc) >= 0 and math.isfinite(float(interval)) and float(interval) > 0):
+        raise ValueError(f"{what}: visc must be >= 0 and interval positive, got visc={visc} interval={interval}")
+    lap, dealias, poisson = _ns2d_symbols(M, N)
+    z = -float(interval) * float(visc) * lap
+    LR, mean = _contour(z, True)
+    eLR = torch.exp(LR)
+    return z, mean((eLR - 1.0) / LR).real, mean((eLR - 1.0 - LR) / LR ** 2).real, dealias, poisson
+
+
+def ns2d_residual_tables(M: int, N: int, visc: float, interval: float, dealias: bool = True):
+    """(em1, m0, m1, inv_lap): the tables of the equation residual of w_t = -visc lap w - A(w) + f over the time `interval`
+    between an input and a prediction, on the grid and with the symbols of ns2d_tables, as float32 [M, kp] host tensors
+    (padded columns zero), formed in float64 and rounded once.  With z = -interval visc lap and phi1, phi2 as in
+    etd1d_residual_tables (real here):
+        em1 = e^z - 1 (expm1),  m0 = interval (phi1 - phi2) dealias,  m1 = interval phi2 dealias,  inv_lap = 1 / lap
+    (the mean mode's lap set to 1 for the division).  dealias=False drops the 2/3 mask.  include/rpde.h has the formulas."""
+    z, phi1, phi2, keep, poisson = _ns2d_residual_phi("ns2d_residual_tables", M, N, visc, interval)
+    if not dealias:
+        keep = torch.ones_like(keep)
+    h = float(interval)
+    return tuple(_padded(t) for t in (torch.expm1(z), h * (phi1 - phi2) * keep, h * phi2 * keep, 1.0 / poisson))
+
+
+def ns2d_residual_forcing(f: torch.Tensor, visc: float, interval: float) -> torch.Tensor:
+    """The forcing term of the residual, (m0 + m1) rfft2(f) = interval phi1 rfft2(f), for one forcing field f [M, N]: a
+    float32 [M, 2, kp] host tensor (real plane, imaginary plane; padded columns zero), formed in float64 and rounded once.
+    Not de-aliased: the generator adds its forcing as it stands."""
+    if f.dim() != 2:
+        raise ValueError(f"ns2d_residual_forcing: forcing {tuple(f.shape)}, expected [M, N] (one field for the batch)")
+    M, N = (int(v) for v in f.shape)
+    _, phi1, _, _, _ = _ns2d_residual_phi("ns2d_residual_forcing", M, N, visc, interval)
+    s = float(interval) * phi1 * torch.fft.rfft2(f.detach().double().cpu())
+    return _padded(torch.stack([s.real, s.imag], dim=1)).contiguous()
+
+
+def ns2d_residual_spectrum(x: torch.Tensor, affine=None):
+    """(spec64, spec32): rfft2 of a x + b for x [B, M, N] by the float64 analysis of the residual's forward (rows, then
+    columns, float64 sums), as [B, M, 2, kp] float64 and its fp32 rounding.  affine = (a, b) or None.  GPU tensors only."""
+    lib = load()
+    x = _f32c(x.detach())
+    px = ptr(x)
+    if x.dim() != 3:
+        raise ValueError(f"ns2d_residual_spectrum: expected [B, M, N], got {tuple(x.shape)}")
+    B, M, N = (int(v) for v in x.shape)
+    nws = lib.rpde_ns2d_residual_work_bytes(B, M, N)
+    if nws == 0:
+        raise ValueError(f"ns2d_residual_spectrum: unsupported B={B} M={M} N={N} (even axes 4 .. 4096, 8 B <= 65535)")
+    s64 = torch.empty(B, M, 2, _kp(N), dtype=torch.float64, device=x.device)
+    s32 = torch.empty(B, M, 2, _kp(N), dtype=torch.float32, device=x.device)
+    aff = None if affine is None else (C.c_float * 2)(float(affine[0]), float(affine[1]))
+    run("ns2d_residual_spectrum", nws, x.device, px, aff, s64.data_ptr(), ptr(s32), B, M, N)
+    return s64, s32
+
+
+class _Ns2dResidual(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, x, em1, m0, m1, il, fs, affine, size_average: bool, reduction: bool):
+        lib = load()
+        shape = tuple(pred.shape)
+        B, M, N = shape[0], shape[-2], shape[-1]
+        p3, x3 = _f32c(pred).reshape(B, M, N), _f32c(x.detach()).reshape(B, M, N)
+        pp, px = ptr(p3), ptr(x3)                             # raises for CPU tensors: there is no fallback
+        dev = p3.device
+        nws = lib.rpde_ns2d_residual_work_bytes(B, M, N)
+        if nws == 0:
+            raise ValueError(f"ns2d_residual: unsupported B={B} M={M} N={N} (even axes 4 .. 4096; 8 B <= 65535 and "
+                             "32 B max(M, N) < 2^31: eight derivative fields per sample are one batch of the half-spectrum layer)")
+        aff = _residual_affine(affine)
+        stats, rel, loss = _rel_outputs(B, dev, reduction)
+        spec = torch.empty(lib.rpde_ns2d_residual_spec_elems(B, M, N), dtype=torch.float32, device=dev)
+        run("ns2d_residual_fwd", nws, dev, pp, px, ptr(em1), ptr(m0), ptr(m1), ptr(il), ptr(fs), aff, ptr(rel), ptr(loss),
+            ptr(stats), ptr(spec), B, M, N, int(size_average))
+        ctx.save_for_backward(spec, stats, m1, il)
+        ctx.meta = (shape, B, M, N, affine, size_average, reduction)
+        return loss if reduction else rel
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = load()
+        spec, stats, m1, il = ctx.saved_tensors
+        shape, B, M, N, affine, size_average, reduction = ctx.meta
+        g = _f32c(g)
+        gp = torch.empty(shape, dtype=torch.float32, device=spec.device)
+        run("ns2d_residual_bwd", lib.rpde_ns2d_residual_work_bytes(B, M, N), spec.device, ptr(spec), ptr(m1), ptr(il),
+            _residual_affine(affine), ptr(stats), *_upstream(g, reduction), ptr(gp), B, M, N, int(size_average))
+        return (gp,) + (None,) * 9
+
+
+def ns2d_residual(pred, inp, tables, forcing_spec=None, affine=None, size_average: bool = True, reduction: bool = True):
+    """Does pred ~ w(t + interval) follow from inp = w(t) under the vorticity equation of the generator (ns2d_solve),
+    w_t = -visc lap w - A(w) + f?  With the tables (em1, m0, m1, inv_lap) of ns2d_residual_tables (host or device tensors,
+    [M, kp] each) and forcing_spec of ns2d_residual_forcing ([M, 2, kp], or None: no forcing),
+        r^ = rfft2(p~ - x~) - em1 rfft2(x~) - forcing_spec + m0 rfft2(N(x~)) + m1 rfft2(N(p~)),  N(w) = q w_x + v w_y,
+        rel[b] = |r[b]|_2 / (|x~[b]|_2 + 1e-8),
+    then mean / sum / the per-sample vector as relative_l2.  affine = (a_p, b_p, a_x, b_x): p~ = a_p pred + b_p,
+    x~ = a_x inp + b_x (None: the identity); the gradient is with respect to pred itself.  The rule is the exponential
+    trapezoidal one, second order in the nonlinear term: the loss is for |interval N_tt| small (DESIGN.md 10.12 has the
+    table).  pred, inp: [B, M, N] or [B, 1, M, N] (one channel: the vorticity is scalar) contiguous fp32 tensors on the
+    GPU; gradient for pred only, no CPU fallback."""
+    ok = pred.dim() in (3, 4) and pred.shape == inp.shape and (pred.dim() == 3 or pred.shape[1] == 1)
+    if not ok:
+        raise ValueError(f"ns2d_residual: pred {tuple(pred.shape)} / inp {tuple(inp.shape)}, expected equal [B, M, N] or "
+                         "[B, 1, M, N] shapes (one channel)")
+    if pred.dtype != torch.float32 or inp.dtype != torch.float32:
+        raise ValueError(f"ns2d_residual: expected float32 fields, got {pred.dtype} / {inp.dtype}")
+    M, N = int(pred.shape[-2]), int(pred.shape[-1])
+    tables = tuple(tables)
+    want = (M, _kp(N))
+    if len(tables) != 4 or any(tuple(t.shape) != want for t in tables):
+        raise ValueError(f"ns2d_residual: expected the four [{M}, {want[1]}] tables of ns2d_residual_tables(M={M}, N={N}, ...), "
+                         f"got {[tuple(t.shape) for t in tables]}")
+    if forcing_spec is not None and tuple(forcing_spec.shape) != (M, 2, want[1]):
+        raise ValueError(f"ns2d_residual: forcing_spec {tuple(forcing_spec.shape)}, expected the [{M}, 2, {want[1]}] spectrum of "
+                         "ns2d_residual_forcing")
+    _residual_affine(affine)                                  # validates
+    if not pred.is_cuda:
+        ptr(pred)                                             # the CPU refusal of every op
+    em1, m0, m1, il = (_f32c(t.detach().to(pred.device)) for t in tables)
+    fs = None if forcing_spec is None else _f32c(forcing_spec.detach().to(pred.device))
+    return _Ns2dResidual.apply(pred, inp, em1, m0, m1, il, fs, None if affine is None else tuple(float(v) for v in affine),
+                               bool(size_average), bool(reduction))
 
 
 # ----------------------------------------------------------------------------

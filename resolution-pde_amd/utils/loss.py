@@ -15,7 +15,9 @@ device).
 EquationResidualLoss (no counterpart in the reference): the physics-informed term for the 1-D ETD family
 u_t = L u - (c/2) (u^2)_x -- does the one-step map satisfy the equation itself? -- forward and backward on the device
 (rpde.ops.etd1d_residual, csrc/etd_residual.hip).  It reads the network's input next to its prediction
-(`takes_input`).  SumLoss adds weighted losses into one callable."""
+(`takes_input`).  VorticityResidualLoss (no counterpart in the reference): the same term for the 2-D vorticity equation
+of the Navier-Stokes generator (rpde.ops.ns2d_residual, csrc/ns_residual.hip).  SumLoss adds weighted losses into one
+callable."""
 from __future__ import annotations
 
 import math
@@ -328,6 +330,93 @@ class EquationResidualLoss(_GridTableLoss):
             raise ValueError("EquationResidualLoss: the network's input is needed next to its prediction")
         return ops.etd1d_residual(pred, inp, self._table((int(pred.shape[-1]),), pred.device), self._affine,
                                   self.size_average, self.reduction)
+
+
+def reference_forcing(M: int, N: int) -> torch.Tensor:
+    """0.1 (sin 2 pi (x + y) + cos 2 pi (x + y)) on the grid x = i / M, y = j / N: the forcing of
+    data_generation/ns_2d.py, float64 [M, N]"""
+    x = (torch.arange(int(M), dtype=torch.float64) / int(M)).view(-1, 1)
+    y = (torch.arange(int(N), dtype=torch.float64) / int(N)).view(1, -1)
+    return 0.1 * (torch.sin(2 * math.pi * (x + y)) + torch.cos(2 * math.pi * (x + y)))
+
+
+class VorticityResidualLoss(_GridTableLoss):
+    """Does the prediction p ~ w(t + interval) follow from the input x = w(t) under the 2-D vorticity equation of the
+    generator (rpde.ops.ns2d_solve, data_generation/ns_2d.py) on the unit periodic square,
+
+        w_t + u . grad w = viscosity lap w + f,   u = (psi_y, -psi_x),  lap psi = -w ?
+
+    The advection is the generator's discrete one, A(w) = dealias rfft2(q w_x + v w_y), and the rule the exponential
+    trapezoidal one of EquationResidualLoss with z = -interval viscosity lap:
+
+        r^ = rfft2(p - x) - (E - 1) rfft2(x) - m0 (f^ - A(x)) - m1 (f^ - A(p)),   rel[b] = |r[b]|_2 / (|x[b]|_2 + 1e-8)
+
+    then mean / sum / per-sample vector as RelativeL2Loss (rpde.ops.ns2d_residual_tables has E - 1, m0, m1).  `interval`
+    is the time between input and prediction: the snapshot interval of the data set, not the solver's step.  The rule is
+    second order, so an exact pair leaves rel ~ interval^3 |N_tt|.  Float64 figures at viscosity 1e-3, w0 = 8 x GRF(2.5, 7)
+    and the reference forcing, exact pair against the trivial predictor p = x (DESIGN.md 10.12 has the table): at
+    interval 0.05, 1.3e-3 .. 1.9e-3 against 0.06 .. 0.07 on 64 x 64; by interval 0.1 the exact pair reaches a tenth
+    of p = x on 16 x 24.
+
+    forcing: None, "reference" (the forcing of data_generation/ns_2d.py on each grid) or one [M, N] tensor for ONE grid.
+    forward(pred, target, inp): the target is unused and may be None; pred, inp [B, M, N] or [B, 1, M, N] fp32 tensors
+    on the GPU (more channels: ValueError), gradient for pred only.  set_affine, the per-(grid, device) table cache and
+    warm((M, N), device) as in EquationResidualLoss."""
+
+    takes_input = True
+    dims = 2
+    _explicit_kind = "forcing"
+
+    def __init__(self, viscosity, interval, forcing=None, dealias=True, size_average=True, reduction=True):
+        super().__init__(size_average, reduction)
+        vals = [float(viscosity), float(interval)]
+        if not all(math.isfinite(v) for v in vals) or vals[0] < 0 or not vals[1] > 0:
+            raise ValueError(f"VorticityResidualLoss: viscosity {viscosity} must be >= 0 and interval {interval} positive")
+        self.viscosity, self.interval = vals
+        if torch.is_tensor(forcing):
+            if forcing.dim() != 2:
+                raise ValueError(f"VorticityResidualLoss: a forcing tensor is one [M, N] field, got {tuple(forcing.shape)}")
+            self._explicit = forcing.detach().double().cpu()
+            self.forcing = "explicit"
+        elif forcing in (None, "reference"):
+            self.forcing = forcing
+        else:
+            raise ValueError(f"VorticityResidualLoss: forcing must be None, 'reference' or an [M, N] tensor, got {forcing!r}")
+        self.dealias = bool(dealias)
+        self._affine = None
+
+    def set_affine(self, pred=(1.0, 0.0), inp=(1.0, 0.0)) -> None:
+        """decode maps of the prediction and of the input, each (a, b) for a field + b; set before a capture"""
+        aff = (float(pred[0]), float(pred[1]), float(inp[0]), float(inp[1]))
+        if not all(math.isfinite(v) for v in aff):
+            raise ValueError(f"VorticityResidualLoss.set_affine: {pred} / {inp}")
+        self._affine = None if aff == (1.0, 0.0, 1.0, 0.0) else aff
+
+    def _build(self, grid, device):
+        tabs = ops.ns2d_residual_tables(grid[0], grid[1], self.viscosity, self.interval, self.dealias)
+        if self.forcing is None:
+            f = None
+        elif self._explicit is not None:
+            if tuple(self._explicit.shape) != tuple(grid):
+                raise ValueError(f"VorticityResidualLoss: the forcing of shape {tuple(self._explicit.shape)} does not serve "
+                                 f"the grid {grid}")
+            f = self._explicit
+        else:
+            f = reference_forcing(*grid)
+        fs = None if f is None else ops.ns2d_residual_forcing(f, self.viscosity, self.interval).to(device).contiguous()
+        return tuple(t.to(device).contiguous() for t in tabs), fs
+
+    def _bad_rank(self, grid) -> str:
+        return f"VorticityResidualLoss.warm: grid {grid}, the equation is two-dimensional"
+
+    def forward(self, pred, target, inp):
+        if inp is None:
+            raise ValueError("VorticityResidualLoss: the network's input is needed next to its prediction")
+        if pred.dim() not in (3, 4) or (pred.dim() == 4 and pred.shape[1] != 1):
+            raise ValueError(f"VorticityResidualLoss: expected [B, M, N] or [B, 1, M, N] (the vorticity is one channel), got "
+                             f"{tuple(pred.shape)}")
+        tabs, fs = self._table((int(pred.shape[-2]), int(pred.shape[-1])), pred.device)
+        return ops.ns2d_residual(pred, inp, tabs, fs, self._affine, self.size_average, self.reduction)
 
 
 class SumLoss(nn.Module):
