@@ -616,10 +616,10 @@ int rpde_etd_residual_bwd(const float* p, const float* spec_r, const float* m1, 
  * rpde_ns2d_residual_spectrum is the float64 analysis alone: spec64 and spec32 [B][M][re|im][kp] (doubles, floats) of
  * a x + b, affine = two host floats (a, b) or NULL.
  * Even M, N in 4 .. 4096 and 8 B images within the half-spectrum layer's limits (8 B <= 65535, 32 B max(M, N) < 2^31):
- * the two queries return 0 otherwise.  Fields, tables and spectra 16-byte aligned, the workspace (rpde_ns2d_residual_work_bytes
- * serves the three calls: one layout per entry, the largest of them) 256-byte aligned.  No atomics, no host synchronisation, everything on the caller's stream (the first use
+ * the two queries return 0 otherwise.  Fields, tables and spectra 16-byte aligned, the workspace (the ws query
+ * serves the three calls: one layout per entry, the largest of them, the forward's) 256-byte aligned.  No atomics, no host synchronisation, everything on the caller's stream (the first use
  * of a grid builds its plans: it allocates and synchronises once).  Argument errors are reported before any device work. */
-size_t rpde_ns2d_residual_work_bytes(int B, int M, int N);
+size_t rpde_ns2d_residual_ws_bytes(int B, int M, int N);
 size_t rpde_ns2d_residual_spec_elems(int B, int M, int N);
 int rpde_ns2d_residual_spectrum(const float* x, const float* affine, double* spec64, float* spec32, int B, int M, int N,
                                 void* ws, size_t ws_bytes, void* stream);

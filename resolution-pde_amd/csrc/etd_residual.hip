@@ -7,7 +7,7 @@
 // float64 and rounded once (include/rpde.h has the formulas): no division and no transcendental here but the final
 // sqrt and the per-sample coefficient.  An affine decode (a_p p + b_p, a_x x + b_x) is folded into the first pass.
 // Forward, three launches on the caller's stream:
-//   k_res_twiddle   the N float64 roots of unity, into the workspace
+//   rel_roots       (rel_loss.h) the N float64 roots of unity, into the workspace
 //   k_res_spectrum  decode, square, the four spectra of [x~ | p~ | x~^2 | p~^2] and r^ in one pass, all in float64: for a
 //                   good model r^ is a small remainder (1e-3 of p^ and less) of terms of the size of the field, and the
 //                   fp32 transforms of halfspec.h leave an error of that size in it (see the kernel).  r^ is rounded once
@@ -31,20 +31,9 @@ namespace rpde {
 constexpr int RES_BLOCK = 256;       // threads of a block of k_res_spectrum where an image has more than 64 columns
 constexpr int RES_SLOTS = (HS_MAX_N / 2 + 4 + RES_BLOCK - 1) / RES_BLOCK;   // partial sums per (field, sample) at most
 
-struct ResAffine { float ap, bp, ax, bx; };
 struct ResGeom : HalfSpec { int B; };
 
-// tw[j] = (cos, -sin)(2 pi j / N), j < N: the float64 analysis kernel of k_res_spectrum.  sincospi is exact at the
-// multiples of a quarter turn, so Im of the mean and Nyquist bins is exactly zero
-__global__ __launch_bounds__(256) void k_res_twiddle(double2* __restrict__ tw, int N) {
-  const int j = blockIdx.x * 256 + threadIdx.x;
-  if (j >= N) return;
-  double s, c;
-  sincospi(2.0 * (double)j / (double)N, &s, &c);
-  tw[j] = make_double2(c, -s);
-}
-
-// grid (S, B), S = the blocks over the kp columns of an image; a thread owns one k.  The spectra of x~, p~, x~^2 and p~^2
+// grid (S, B), S = the blocks over the kp columns of an image; a thread owns one k; tw: the N roots of rel_roots.  The spectra of x~, p~, x~^2 and p~^2
 // as float64 sums over the N points (the fields and their squares are formed in registers, the squares exact in
 // float64), then r^ = p^ - E x^ - m0 rfft(x~^2) - m1 rfft(p~^2) in float64, rounded once into spec_r (padded columns zero).
 // Why not the matrix-product transform of halfspec.h: its error in x^ is absolute, about 2e-7 |x| at every mode, and for
@@ -55,8 +44,7 @@ __global__ __launch_bounds__(RES_BLOCK) void k_res_spectrum(const float* __restr
                                                             const double2* __restrict__ tw, const float* __restrict__ E,
                                                             const float* __restrict__ m0, const float* __restrict__ m1,
                                                             float* __restrict__ spec_r, double* __restrict__ part, ResGeom g,
-                                                            ResAffine a) {
-  __shared__ double red[2][4];
+                                                            RelAffine a) {
   const int b = blockIdx.y, k = blockIdx.x * blockDim.x + threadIdx.x;
   const float* __restrict__ xb = x + (long)b * g.N;
   const float* __restrict__ pb = p + (long)b * g.N;
@@ -89,17 +77,7 @@ __global__ __launch_bounds__(RES_BLOCK) void k_res_spectrum(const float* __restr
     spec_r[(long)b * 2 * g.kp + k] = 0.f;
     spec_r[(long)b * 2 * g.kp + g.kp + k] = 0.f;
   }
-  er = wave_sum(er);
-  ex = wave_sum(ex);
-  const int waves = blockDim.x >> 6;
-  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = er; red[1][threadIdx.x >> 6] = ex; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double tr = red[0][0], tx = red[1][0];
-    if (waves == 4) { tr = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]); tx = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]); }
-    part[(long)b * gridDim.x + blockIdx.x] = tr;
-    part[((long)g.B + b) * gridDim.x + blockIdx.x] = tx;
-  }
+  rel_block_slots(er, ex, part, b, g.B, blockDim.x == RES_BLOCK);
 }
 
 // grid (blocks, B): out [2 B] spectra, out[b] = r^[b], out[B + b] = conj(m1) r^[b].  The padded columns of spec_r and of
@@ -124,7 +102,7 @@ __global__ __launch_bounds__(256) void k_res_fan(const float* __restrict__ spec_
 __global__ __launch_bounds__(256) void k_res_grad(const float* __restrict__ p, const float* __restrict__ rs,
                                                   const float* __restrict__ stats, const float* __restrict__ grad_loss,
                                                   const float* __restrict__ grad_rel, float* __restrict__ grad_p, int B, int N,
-                                                  int vec, int size_average, ResAffine a) {
+                                                  int vec, int size_average, RelAffine a) {
   const int b = blockIdx.y;
   const float scale = a.ap * rel_coef(stats, grad_loss, grad_rel, b, B, size_average);
   const long row = (long)b * N;
@@ -149,9 +127,6 @@ __global__ __launch_bounds__(256) void k_res_grad(const float* __restrict__ p, c
 // the batch limit of four fields of B images as one batch of the half-spectrum layer
 constexpr int RES_MAX_B = 65535 / 4;
 static bool res_dims_ok(int B, int N) { return B > 0 && B <= RES_MAX_B && hs_dims_ok(4 * B, 1, N); }
-static ResAffine res_affine(const float* affine) {
-  return affine ? ResAffine{affine[0], affine[1], affine[2], affine[3]} : ResAffine{1.f, 0.f, 1.f, 0.f};
-}
 
 #define RES_CHECK_DIMS(what, B, N)                                                                                        \
   RPDE_CHECK_ARG(res_dims_ok(B, N), what ": bad B=%d N=%d (N even, %d .. %d, 1 <= B <= %d: four fields of B images)", B, N, \
@@ -193,9 +168,8 @@ int rpde_etd_residual_fwd(const float* p, const float* x, const float* E, const 
   // a wave per image of at most 64 columns (N <= 120), RES_BLOCK threads otherwise; the blocks of an image are its slots
   const dim3 sb(g.kp <= 64 ? 64 : RES_BLOCK), sg((g.kp + sb.x - 1) / sb.x, B);
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(k_res_twiddle, dim3((N + 255) / 256), dim3(256), 0, st, w.tw, N);
-  RPDE_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_res_spectrum, sg, sb, 0, st, p, x, w.tw, E, m0, m1, spec_r, w.part, g, res_affine(affine));
+  RPDE_TRY(rel_roots(w.tw, N, 0, st));
+  hipLaunchKernelGGL(k_res_spectrum, sg, sb, 0, st, p, x, w.tw, E, m0, m1, spec_r, w.part, g, rel_affine(affine));
   RPDE_LAUNCH_CHECK();
   return rel_final(w.part, rel, loss, stats, B, (int)sg.x, 1.0 / (double)N, size_average, st);
 }
@@ -217,7 +191,7 @@ int rpde_etd_residual_bwd(const float* p, const float* spec_r, const float* m1, 
   RPDE_TRY(hs_irfft(g2, w.s2, nullptr, w.rs, st));
   const int vec = N % 4 == 0 && al16(p) && al16(grad_p);
   hipLaunchKernelGGL(k_res_grad, hs_grid(vec ? N / 4 : N, B), dim3(256), 0, st, p, w.rs, stats, grad_loss, grad_rel, grad_p, B, N,
-                     vec, size_average, res_affine(affine));
+                     vec, size_average, rel_affine(affine));
   RPDE_LAUNCH_CHECK();
   return RPDE_OK;
 }

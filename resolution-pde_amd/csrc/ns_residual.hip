@@ -11,7 +11,7 @@
 // m0 dealias, m1 dealias, 1 / lap, each [M][kp], and the forcing term (m0 + m1) f^ as one spectrum (or none).
 // An affine decode (a_p p + b_p, a_x x + b_x) is folded into the first pass.
 // Forward, on the caller's stream:
-//   k_nsr_twiddle, then k_nsr_rows and k_nsr_cols twice: x^ and d^ as separable float64 analyses (rows, then columns).
+//   rel_roots, then k_nsr_rows and k_nsr_cols twice:     x^ and d^ as separable float64 analyses (rows, then columns).
 //                         r^ is a remainder of 1e-3 |x| and less, and (E - 1) x^ carries an fp32 transform's absolute
 //                         error in x^ straight into it; d is formed in float64 in LDS and never rounded (DESIGN.md
 //                         10.12 has the figures with d^ on the layer's transform).  Both stay in float64 for the
@@ -31,19 +31,6 @@
 
 namespace rpde {
 
-struct NsrAffine { float ap, bp, ax, bx; };
-
-// tw[j] = (cos, -sin)(2 pi j / N), j < N, then the same for M: tw[N + j], j < M (k_res_twiddle of etd_residual.hip on
-// both axes).  sincospi is exact at the multiples of a quarter turn
-__global__ __launch_bounds__(256) void k_nsr_twiddle(double2* __restrict__ tw, int N, int M) {
-  const int j = blockIdx.x * 256 + threadIdx.x;
-  if (j >= N + M) return;
-  const int n = j < N ? N : M, i = j < N ? j : j - N;
-  double s, c;
-  sincospi(2.0 * (double)i / (double)n, &s, &c);
-  tw[j] = make_double2(c, -s);
-}
-
 // grid (blocks over K, blocks of RY rows, B): R[b][y][k] = sum_j z[b][y][j] tw_N[j k mod N], RY rows y of z = x~ (p null)
 // or of z = d = p~ - x~ decoded into LDS in float64 (d is never rounded to fp32); a thread owns one k for the RY rows, so a
 // root of unity gathered once serves 2 RY multiply-adds.  TW: the N roots sit in LDS as well (N <= NSR_TW_MAX).
@@ -52,7 +39,7 @@ constexpr int NSR_TW_MAX = 1024;
 template <int RY, bool TW>
 __global__ __launch_bounds__(256) void k_nsr_rows(const float* __restrict__ x, const float* __restrict__ p,
                                                   const double2* __restrict__ twN, double2* __restrict__ R, HalfSpec g,
-                                                  NsrAffine a) {
+                                                  RelAffine a) {
   extern __shared__ double nsr_lds[];
   double* __restrict__ row = nsr_lds;
   const double2* __restrict__ tw = twN;
@@ -164,7 +151,6 @@ __global__ __launch_bounds__(256) void k_nsr_residual(const double* __restrict__
                                                       const float* __restrict__ m0, const float* __restrict__ m1,
                                                       const float* __restrict__ fs, float* __restrict__ spec_r,
                                                       double* __restrict__ part, HalfSpec g) {
-  __shared__ double red[2][4];
   const int b = blockIdx.y;
   const int c4n = g.kp / 4, per4 = g.M * c4n;
   const long per = (long)g.M * 2 * g.kp, base = (long)b * per, half = (long)g.images * per;
@@ -195,14 +181,7 @@ __global__ __launch_bounds__(256) void k_nsr_residual(const double* __restrict__
     }
     st4(spec_r + base + ore, rr); st4(spec_r + base + oim, ri);
   }
-  er = wave_sum(er);
-  ex = wave_sum(ex);
-  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = er; red[1][threadIdx.x >> 6] = ex; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    part[(long)b * gridDim.x + blockIdx.x] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-    part[((long)g.images + b) * gridDim.x + blockIdx.x] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-  }
+  rel_block_slots(er, ex, part, b, g.images, true);
 }
 
 // P [5][B M N] = (g, q, v, w_x, w_y) -> out [4][B M N] = (g w_x, g w_y, g q, g v); n4 float4 groups per field
@@ -272,9 +251,6 @@ __global__ __launch_bounds__(256) void k_nsr_grad(const float* __restrict__ z, c
 // Per sample the forward fans out eight derivative spectra: held to the half-spectrum layer's limits as a batch of 8 B
 constexpr int NSR_FAN = 8;
 static bool nsr_dims_ok(int B, int M, int N) { return hs_dims2_ok(B, M, N, NSR_FAN); }
-static NsrAffine nsr_affine(const float* affine) {
-  return affine ? NsrAffine{affine[0], affine[1], affine[2], affine[3]} : NsrAffine{1.f, 0.f, 1.f, 0.f};
-}
 
 // the float64 analysis: the roots of unity of both axes and the row spectra (double2 both)
 struct NsrSpecWork {
@@ -302,14 +278,9 @@ struct NsrBwdWork {
         G(ar.take(spec)), z(ar.take(phys)) {}
 };
 
-static int nsr_twiddle(const NsrSpecWork& w, const HalfSpec& g, hipStream_t st) {
-  hipLaunchKernelGGL(k_nsr_twiddle, dim3((g.N + g.M + 255) / 256), dim3(256), 0, st, w.tw, g.N, g.M);
-  RPDE_LAUNCH_CHECK();
-  return RPDE_OK;
-}
-// the float64 spectrum of x~ (p null) or of p~ - x~, rows then columns, after nsr_twiddle on the same stream
+// the float64 spectrum of x~ (p null) or of p~ - x~, rows then columns, after rel_roots(w.tw, N, M) on the same stream
 static int nsr_spectrum(const float* x, const float* p, const NsrSpecWork& w, double* Xd, float* X32, const HalfSpec& g,
-                        NsrAffine a, hipStream_t st) {
+                        RelAffine a, hipStream_t st) {
   // the wider kernels where they still leave the card a few blocks per CU
   const int rb = g.K >= 256 ? 256 : (g.K + 63) / 64 * 64;
   const long xb = (g.K + rb - 1) / rb, cb = (g.kp + 63) / 64;
@@ -339,7 +310,7 @@ extern "C" {
 
 size_t rpde_ns2d_residual_spec_elems(int B, int M, int N) { return nsr_dims_ok(B, M, N) ? 2 * hs_elems(hs_geom(B, M, N)) : 0; }
 
-size_t rpde_ns2d_residual_work_bytes(int B, int M, int N) {
+size_t rpde_ns2d_residual_ws_bytes(int B, int M, int N) {
   if (!nsr_dims_ok(B, M, N)) return 0;
   const size_t spec = hs_elems(hs_geom(B, M, N)), phys = (size_t)B * M * N;
   return ws_max(ws_measure<NsrFwdWork>(B, M, N, spec, phys), ws_measure<NsrBwdWork>(spec, phys));
@@ -352,8 +323,8 @@ int rpde_ns2d_residual_spectrum(const float* x, const float* affine, double* spe
   HS_CHECK_WS("ns2d_residual_spectrum", ws);
   RPDE_CHECK_ARG(al16(spec64) && al16(spec32), "ns2d_residual_spectrum: the spectra must be 16-byte aligned");
   RPDE_CARVE("ns2d_residual_spectrum", NsrSpecWork, w, ws, ws_bytes, B, M, N);
-  const NsrAffine a{1.f, 0.f, affine ? affine[0] : 1.f, affine ? affine[1] : 0.f};
-  RPDE_TRY(nsr_twiddle(w, hs_geom(B, M, N), as_stream(stream)));
+  const RelAffine a{1.f, 0.f, affine ? affine[0] : 1.f, affine ? affine[1] : 0.f};
+  RPDE_TRY(rel_roots(w.tw, N, M, as_stream(stream)));
   return nsr_spectrum(x, nullptr, w, spec64, spec32, hs_geom(B, M, N), a, as_stream(stream));
 }
 
@@ -370,9 +341,9 @@ int rpde_ns2d_residual_fwd(const float* p, const float* x, const float* em1, con
   const size_t nspec = hs_elems(g), phys = (size_t)B * M * N;
   RPDE_CARVE("ns2d_residual_fwd", NsrFwdWork, w, ws, ws_bytes, B, M, N, nspec, phys);
   hipStream_t st = as_stream(stream);
-  const NsrAffine a = nsr_affine(affine);
+  const RelAffine a = rel_affine(affine);
   float* spec_p = spec + nspec;                                   // spec = [r^ | P^]
-  RPDE_TRY(nsr_twiddle(w.a, g, st));
+  RPDE_TRY(rel_roots(w.a.tw, N, M, st));
   RPDE_TRY(nsr_spectrum(x, nullptr, w.a, w.Xd, w.S, g, a, st));
   RPDE_TRY(nsr_spectrum(x, p, w.a, w.Dd, nullptr, g, a, st));
   hipLaunchKernelGGL(k_nsr_pred, dim3(hs_blocks((long)nspec / 4, 2048)), dim3(256), 0, st, w.Xd, w.Dd, w.S + nspec, spec_p,
@@ -422,7 +393,7 @@ int rpde_ns2d_residual_bwd(const float* spec, const float* m1, const float* inv_
   RPDE_TRY(hs_irfft(g, w.G, w.T1, w.z, st));
   const int n4 = M * N / 4;
   hipLaunchKernelGGL(k_nsr_grad, hs_grid(n4, B), dim3(256), 0, st, w.z, stats, grad_loss, grad_rel, grad_p, B, n4, size_average,
-                     nsr_affine(affine).ap);
+                     rel_affine(affine).ap);
   RPDE_LAUNCH_CHECK();
   return RPDE_OK;
 }

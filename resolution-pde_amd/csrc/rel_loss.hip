@@ -60,6 +60,21 @@ int rel_final(const double* part, float* rel, float* loss, float* stats, int B, 
   return RPDE_OK;
 }
 
+__global__ __launch_bounds__(256) void k_rel_roots(double2* __restrict__ tw, int N, int M) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= N + M) return;
+  const int n = j < N ? N : M, i = j < N ? j : j - N;
+  double s, c;
+  sincospi(2.0 * (double)i / (double)n, &s, &c);
+  tw[j] = make_double2(c, -s);
+}
+
+int rel_roots(double2* tw, int N, int M, hipStream_t st) {
+  hipLaunchKernelGGL(k_rel_roots, dim3((N + M + 255) / 256), dim3(256), 0, st, tw, N, M);
+  RPDE_LAUNCH_CHECK();
+  return RPDE_OK;
+}
+
 // ---------------------------------------------------------------------------
 // relative L2 loss
 // ---------------------------------------------------------------------------

@@ -165,7 +165,7 @@ _SIGNATURES = {
     "rpde_etd_residual_spec_elems": (_Z, [_I, _I]),
     "rpde_etd_residual_fwd": (_I, [_P] * 10 + [_I, _I, _I, _P, _Z, _P]),
     "rpde_etd_residual_bwd": (_I, [_P] * 8 + [_I, _I, _I, _P, _Z, _P]),
-    "rpde_ns2d_residual_work_bytes": (_Z, [_I, _I, _I]),
+    "rpde_ns2d_residual_ws_bytes": (_Z, [_I, _I, _I]),
     "rpde_ns2d_residual_spec_elems": (_Z, [_I, _I, _I]),
     "rpde_ns2d_residual_spectrum": (_I, [_P] * 4 + [_I, _I, _I, _P, _Z, _P]),
     "rpde_ns2d_residual_fwd": (_I, [_P] * 12 + [_I, _I, _I, _I, _P, _Z, _P]),

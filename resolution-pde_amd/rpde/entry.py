@@ -64,6 +64,28 @@ def _sweep_fields(args, test_set, x_normalizer, y_normalizer, min_model, max_mod
     return tx, ty_phys, dec, how, top_res
 
 
+def _etd_residual(eq):
+    from utils.loss import EquationResidualLoss
+    return EquationResidualLoss(**{k: float(v) for k, v in eq.items()})
+
+
+def _vorticity_residual(eq):
+    from utils.loss import VorticityResidualLoss
+    forcing = eq.get("forcing")
+    forcing = None if forcing is None or str(forcing).lower() in ("none", "null") else str(forcing)
+    return VorticityResidualLoss(float(eq["viscosity"]), float(eq["interval"]), forcing=forcing)
+
+
+# training.loss=residual, the `equation:` mapping of the 1-D ETD family (False) and of kind ns_vorticity (True): the keys
+# it may hold, those it must, the loss it builds and the refusal of any other mapping
+_RESIDUALS = {
+    False: ({"c1", "c2", "c3", "c4", "advect", "length", "interval"}, {"length", "interval"}, _etd_residual,
+            "equation needs length and interval and takes c1, c2, c3, c4, advect"),
+    True: ({"kind", "viscosity", "interval", "forcing"}, {"viscosity", "interval"}, _vorticity_residual,
+           "a ns_vorticity equation needs viscosity and interval and takes forcing (reference, or none)"),
+}
+
+
 def training_loss(training, dims: int, dataset=None):
     """(name, loss_fn or None) of the optional training objective, from the overrides under `training` (a mapping; no
     device work here); `dataset`: the data set's config, read by training.loss=residual alone.  Absent or "l2": (l2, None), train() then takes RelativeL2Loss.
@@ -90,34 +112,20 @@ def training_loss(training, dims: int, dataset=None):
         length = [float(v) for v in length] if isinstance(length, (list, tuple)) else float(length)
         return name, SpectralRelativeL2Loss(dims, "sobolev", s=float(training.get("loss_s", 1.0)), length=length)
     if name == "residual":
-        from utils.loss import EquationResidualLoss, RelativeL2Loss, SumLoss, VorticityResidualLoss
-        eq = None if dataset is None else dataset.get("equation")
-        if dims == 2 and eq and dict(eq).get("kind") == "ns_vorticity":
-            eq = dict(eq)
-            unknown = sorted(set(eq) - {"kind", "viscosity", "interval", "forcing"})
-            if unknown or "viscosity" not in eq or "interval" not in eq:
-                raise SystemExit(f"training.loss=residual: a ns_vorticity equation needs viscosity and interval and takes "
-                                 f"forcing (reference, or none); got {sorted(eq)}")
-            forcing = eq.get("forcing")
-            forcing = None if forcing is None or str(forcing).lower() in ("none", "null") else str(forcing)
-            try:
-                res = VorticityResidualLoss(float(eq["viscosity"]), float(eq["interval"]), forcing=forcing)
-            except ValueError as e:
-                raise SystemExit(f"training.loss=residual: {e}")
-            return name, SumLoss([(1.0, RelativeL2Loss()), (float(training.get("loss_lambda", 0.1)), res)])
-        if dims != 1:
+        from utils.loss import RelativeL2Loss, SumLoss
+        eq = dict((None if dataset is None else dataset.get("equation")) or {})
+        vorticity = dims == 2 and eq.get("kind") == "ns_vorticity"
+        if dims != 1 and not vorticity:
             raise SystemExit(f"training.loss=residual: the equation residual is one-dimensional, got dims={dims} (a 2-D data "
                              "set names the vorticity equation: `equation: {kind: ns_vorticity, viscosity, interval, forcing}`)")
         if not eq:
             raise SystemExit("training.loss=residual: the dataset config has no `equation:` mapping "
                              "({c1, c2, c3, c4, advect, length, interval})")
-        eq = dict(eq)
-        unknown = sorted(set(eq) - {"c1", "c2", "c3", "c4", "advect", "length", "interval"})
-        if unknown or "length" not in eq or "interval" not in eq:
-            raise SystemExit(f"training.loss=residual: equation needs length and interval and takes c1, c2, c3, c4, advect; "
-                             f"got {sorted(eq)}")
+        allowed, required, make, refusal = _RESIDUALS[vorticity]
+        if set(eq) - allowed or not required <= set(eq):
+            raise SystemExit(f"training.loss=residual: {refusal}; got {sorted(eq)}")
         try:
-            res = EquationResidualLoss(**{k: float(v) for k, v in eq.items()})
+            res = make(eq)
         except ValueError as e:
             raise SystemExit(f"training.loss=residual: {e}")
         return name, SumLoss([(1.0, RelativeL2Loss()), (float(training.get("loss_lambda", 0.1)), res)])
@@ -141,9 +149,9 @@ def residual_affine(loss_fn, x_normalizer, y_normalizer, use_normalizer: bool, m
     asked in physical units: the input is decoded with the x-statistics; the prediction with the y-statistics, unless
     training.use_normalizer is true -- train() has decoded it by then and its map is the identity.  Only one global
     affine map (SimpleNormalizer) folds into the loss: point-wise or min-max normalisers are a SystemExit."""
-    from utils.loss import EquationResidualLoss, VorticityResidualLoss
+    from utils.loss import _ResidualLoss
     from utils.normalizers import scalar_stats
-    terms = [t for t in getattr(loss_fn, "terms", [loss_fn]) if isinstance(t, (EquationResidualLoss, VorticityResidualLoss))]
+    terms = [t for t in getattr(loss_fn, "terms", [loss_fn]) if isinstance(t, _ResidualLoss)]
     if not terms:
         return
     if minmax:

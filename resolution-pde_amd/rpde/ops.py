@@ -11,7 +11,7 @@ import contextlib
 import os
 
 import ctypes as C
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -1511,7 +1511,8 @@ def etd1d_solve(u0: torch.Tensor, tables, steps: int, record_every: int) -> torc
 
 # ----------------------------------------------------------------------------
 # equation-residual loss of the 1-D ETD family (csrc/etd_residual.hip, rpde_etd_residual_*; utils/loss.py
-# EquationResidualLoss).  Forward and backward on the device, GPU tensors only, no CPU fallback.
+# EquationResidualLoss).  Forward and backward on the device, GPU tensors only, no CPU fallback.  The Function and the
+# checks of fields, tables and affine serve the 2-D vorticity residual below as well.
 # ----------------------------------------------------------------------------
 def etd1d_residual_tables(N: int, length: float, c1: float, c2: float, c3: float, c4: float, interval: float,
                           advect: float = 1.0, dealias: bool = True):
@@ -1549,38 +1550,84 @@ def _residual_affine(affine):
     return (C.c_float * 4)(*vals)
 
 
-class _EtdResidual(torch.autograd.Function):
+class _Equation(NamedTuple):
+    """What tells one equation residual from the other at the C ABI"""
+    op: str                           # the op's name, for messages
+    stem: str                         # the entries are rpde_<stem>_{ws_bytes, spec_elems, fwd, bwd}
+    nd: int                           # the rank of the grid: the entries' dims are (B, *grid)
+    bwd_tables: slice                 # which of the forward's tables the backward gets
+    bwd_pred: bool                    # whether the backward gets the prediction
+    limits: str                       # the sizes the entries serve, for the refusal of any other
+
+
+_ETD1D = _Equation("etd1d_residual", "etd_residual", 1, slice(2, 3), True,
+                   "N even, 4 .. 4096; 1 <= B <= 16383: four fields of B images are one batch of the half-spectrum layer")
+_NS2D = _Equation("ns2d_residual", "ns2d_residual", 2, slice(2, 4), False,
+                  "even axes 4 .. 4096; 8 B <= 65535 and 32 B max(M, N) < 2^31: eight derivative fields per sample are one "
+                  "batch of the half-spectrum layer")
+
+
+class _EquationResidual(torch.autograd.Function):
+    """rpde_<stem>_fwd(p, x, *tables, affine, rel, loss, stats, spec, *dims, size_average) and
+    rpde_<stem>_bwd([p,] spec, *bwd_tables, affine, stats, grad_loss, grad_rel, grad_p, *dims, size_average); `tables`
+    are device tensors or None (no forcing), checked by the caller"""
+
     @staticmethod
-    def forward(ctx, pred, x, E, m0, m1, affine, size_average: bool, reduction: bool):
+    def forward(ctx, eq: _Equation, pred, x, tables, aff, size_average: bool, reduction: bool):
+        op, stem, nd, bwd_tables, bwd_pred, limits = eq
         lib = load()
         shape = tuple(pred.shape)
-        B, N = shape[0], shape[-1]
-        p2, x2 = _f32c(pred).reshape(B, N), _f32c(x.detach()).reshape(B, N)
-        pp, px = ptr(p2), ptr(x2)                             # raises for CPU tensors: there is no fallback
-        dev = p2.device
-        nws = lib.rpde_etd_residual_ws_bytes(B, N)
+        dims = (shape[0], *shape[-nd:])
+        p, x = _f32c(pred).reshape(*dims), _f32c(x.detach()).reshape(*dims)
+        pp, px = ptr(p), ptr(x)                               # raises for CPU tensors: there is no fallback
+        dev = p.device
+        nws = getattr(lib, f"rpde_{stem}_ws_bytes")(*dims)
         if nws == 0:
-            raise ValueError(f"etd1d_residual: unsupported B={B} N={N} (N even, 4 .. 4096; 1 <= B <= 16383: four "
-                             "fields of B images are one batch of the half-spectrum layer)")
-        aff = _residual_affine(affine)
-        stats, rel, loss = _rel_outputs(B, dev, reduction)
-        spec = torch.empty(lib.rpde_etd_residual_spec_elems(B, N), dtype=torch.float32, device=dev)
-        run("etd_residual_fwd", nws, dev, pp, px, ptr(E), ptr(m0), ptr(m1), aff, ptr(rel), ptr(loss), ptr(stats), ptr(spec),
-            B, N, int(size_average))
-        ctx.save_for_backward(p2, spec, stats, m1)
-        ctx.meta = (shape, B, N, affine, size_average, reduction)
+            sizes = " ".join(f"{n}={v}" for n, v in zip("BMN" if nd == 2 else "BN", dims))
+            raise ValueError(f"{op}: unsupported {sizes} ({limits})")
+        stats, rel, loss = _rel_outputs(dims[0], dev, reduction)
+        spec = torch.empty(getattr(lib, f"rpde_{stem}_spec_elems")(*dims), dtype=torch.float32, device=dev)
+        # ptr() is for tensors that come from outside; what was allocated here needs no check
+        run(stem + "_fwd", nws, dev, pp, px, *[ptr(t) for t in tables], aff, rel.data_ptr(), ptr(loss), stats.data_ptr(),
+            spec.data_ptr(), *dims, int(size_average))
+        ctx.save_for_backward(*((p, spec) if bwd_pred else (spec,)), *tables[bwd_tables], stats)
+        ctx.meta = (stem + "_bwd", shape, dims, nws, aff, size_average, reduction)
         return loss if reduction else rel
 
     @staticmethod
     def backward(ctx, g):
-        lib = load()
-        p2, spec, stats, m1 = ctx.saved_tensors
-        shape, B, N, affine, size_average, reduction = ctx.meta
+        *lead, stats = ctx.saved_tensors                      # ([p,] spec, the backward's tables), stats
+        entry, shape, dims, nws, aff, size_average, reduction = ctx.meta
         g = _f32c(g)
-        gp = torch.empty(shape, dtype=torch.float32, device=p2.device)
-        run("etd_residual_bwd", lib.rpde_etd_residual_ws_bytes(B, N), p2.device, ptr(p2), ptr(spec), ptr(m1),
-            _residual_affine(affine), ptr(stats), *_upstream(g, reduction), ptr(gp), B, N, int(size_average))
-        return gp, None, None, None, None, None, None, None
+        gp = torch.empty(shape, dtype=torch.float32, device=stats.device)
+        run(entry, nws, stats.device, *[ptr(t) for t in lead], aff, ptr(stats), *_upstream(g, reduction), gp.data_ptr(),
+            *dims, int(size_average))
+        return None, gp, None, None, None, None, None
+
+
+def _residual_fields(eq: _Equation, pred, x, xname: str):
+    """ValueError unless pred and x are equal float32 [B, *grid] or [B, 1, *grid] fields; -> the grid.  A CPU tensor
+    gets as far as the Function's ptr(): the CPU refusal of every op"""
+    nd, shape, d = eq.nd, pred.shape, pred.dim()
+    if shape != x.shape or not (d == nd + 1 or (d == nd + 2 and shape[1] == 1)):
+        grid = "N" if nd == 1 else "M, N"
+        raise ValueError(f"{eq.op}: pred {tuple(shape)} / {xname} {tuple(x.shape)}, expected equal [B, {grid}] or "
+                         f"[B, 1, {grid}] shapes (one channel)")
+    if pred.dtype != torch.float32 or x.dtype != torch.float32:
+        raise ValueError(f"{eq.op}: expected float32 fields, got {pred.dtype} / {x.dtype}")
+    return shape[-nd:]
+
+
+def _residual_tables(eq: _Equation, tables, grid, device):
+    """ValueError unless `tables` are the three [2, kp] (1-D) or four [M, kp] (2-D) tables of <op>_tables for this grid;
+    -> the tables, detached, as contiguous fp32 tensors on the device"""
+    tables = tuple(tables)
+    count, shape = eq.nd + 2, (2 if eq.nd == 1 else grid[0], _kp(grid[-1]))
+    if len(tables) != count or any(tuple(t.shape) != shape for t in tables):
+        sizes = ", ".join(f"{n}={v}" for n, v in zip("MN"[-eq.nd:], grid))
+        raise ValueError(f"{eq.op}: expected the {('three', 'four')[count - 3]} {list(shape)} tables of "
+                         f"{eq.op}_tables({sizes}, ...), got {[tuple(t.shape) for t in tables]}")
+    return tuple(_f32c(t.detach().to(device)) for t in tables)
 
 
 def etd1d_residual(pred, x, tables, affine=None, size_average: bool = True, reduction: bool = True):
@@ -1593,24 +1640,8 @@ def etd1d_residual(pred, x, tables, affine=None, size_average: bool = True, redu
     O(interval^3 N_tt) and the loss is for |interval N_tt| small (DESIGN.md has the table: on KS at N = 64 an exact
     pair gives rel ~ 1e-3 at interval 0.05, ~ 1e-2 at 0.1 and ~ 1 by 0.4).  pred, x: [B, N] or [B, 1, N] (one channel:
     the equation is scalar) contiguous fp32 tensors on the GPU; gradient for pred only, no CPU fallback."""
-    ok = pred.dim() in (2, 3) and pred.shape == x.shape and (pred.dim() == 2 or pred.shape[1] == 1)
-    if not ok:
-        raise ValueError(f"etd1d_residual: pred {tuple(pred.shape)} / x {tuple(x.shape)}, expected equal [B, N] or [B, 1, N] "
-                         "shapes (one channel)")
-    if pred.dtype != torch.float32 or x.dtype != torch.float32:
-        raise ValueError(f"etd1d_residual: expected float32 fields, got {pred.dtype} / {x.dtype}")
-    N = int(pred.shape[-1])
-    tables = tuple(tables)
-    want = (2, _kp(N))
-    if len(tables) != 3 or any(tuple(t.shape) != want for t in tables):
-        raise ValueError(f"etd1d_residual: expected the three [2, {want[1]}] tables of etd1d_residual_tables(N={N}, ...), got "
-                         f"{[tuple(t.shape) for t in tables]}")
-    _residual_affine(affine)                                  # validates
-    if not pred.is_cuda:
-        ptr(pred)                                             # the CPU refusal of every op
-    E, m0, m1 = (_f32c(t.detach().to(pred.device)) for t in tables)
-    return _EtdResidual.apply(pred, x, E, m0, m1, None if affine is None else tuple(float(v) for v in affine),
-                              bool(size_average), bool(reduction))
+    tables = _residual_tables(_ETD1D, tables, _residual_fields(_ETD1D, pred, x, "x"), pred.device)
+    return _EquationResidual.apply(_ETD1D, pred, x, tables, _residual_affine(affine), bool(size_average), bool(reduction))
 
 
 # ----------------------------------------------------------------------------
@@ -1668,7 +1699,7 @@ def ns2d_residual_spectrum(x: torch.Tensor, affine=None):
     if x.dim() != 3:
         raise ValueError(f"ns2d_residual_spectrum: expected [B, M, N], got {tuple(x.shape)}")
     B, M, N = (int(v) for v in x.shape)
-    nws = lib.rpde_ns2d_residual_work_bytes(B, M, N)
+    nws = lib.rpde_ns2d_residual_ws_bytes(B, M, N)
     if nws == 0:
         raise ValueError(f"ns2d_residual_spectrum: unsupported B={B} M={M} N={N} (even axes 4 .. 4096, 8 B <= 65535)")
     s64 = torch.empty(B, M, 2, _kp(N), dtype=torch.float64, device=x.device)
@@ -1676,40 +1707,6 @@ def ns2d_residual_spectrum(x: torch.Tensor, affine=None):
     aff = None if affine is None else (C.c_float * 2)(float(affine[0]), float(affine[1]))
     run("ns2d_residual_spectrum", nws, x.device, px, aff, s64.data_ptr(), ptr(s32), B, M, N)
     return s64, s32
-
-
-class _Ns2dResidual(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, pred, x, em1, m0, m1, il, fs, affine, size_average: bool, reduction: bool):
-        lib = load()
-        shape = tuple(pred.shape)
-        B, M, N = shape[0], shape[-2], shape[-1]
-        p3, x3 = _f32c(pred).reshape(B, M, N), _f32c(x.detach()).reshape(B, M, N)
-        pp, px = ptr(p3), ptr(x3)                             # raises for CPU tensors: there is no fallback
-        dev = p3.device
-        nws = lib.rpde_ns2d_residual_work_bytes(B, M, N)
-        if nws == 0:
-            raise ValueError(f"ns2d_residual: unsupported B={B} M={M} N={N} (even axes 4 .. 4096; 8 B <= 65535 and "
-                             "32 B max(M, N) < 2^31: eight derivative fields per sample are one batch of the half-spectrum layer)")
-        aff = _residual_affine(affine)
-        stats, rel, loss = _rel_outputs(B, dev, reduction)
-        spec = torch.empty(lib.rpde_ns2d_residual_spec_elems(B, M, N), dtype=torch.float32, device=dev)
-        run("ns2d_residual_fwd", nws, dev, pp, px, ptr(em1), ptr(m0), ptr(m1), ptr(il), ptr(fs), aff, ptr(rel), ptr(loss),
-            ptr(stats), ptr(spec), B, M, N, int(size_average))
-        ctx.save_for_backward(spec, stats, m1, il)
-        ctx.meta = (shape, B, M, N, affine, size_average, reduction)
-        return loss if reduction else rel
-
-    @staticmethod
-    def backward(ctx, g):
-        lib = load()
-        spec, stats, m1, il = ctx.saved_tensors
-        shape, B, M, N, affine, size_average, reduction = ctx.meta
-        g = _f32c(g)
-        gp = torch.empty(shape, dtype=torch.float32, device=spec.device)
-        run("ns2d_residual_bwd", lib.rpde_ns2d_residual_work_bytes(B, M, N), spec.device, ptr(spec), ptr(m1), ptr(il),
-            _residual_affine(affine), ptr(stats), *_upstream(g, reduction), ptr(gp), B, M, N, int(size_average))
-        return (gp,) + (None,) * 9
 
 
 def ns2d_residual(pred, inp, tables, forcing_spec=None, affine=None, size_average: bool = True, reduction: bool = True):
@@ -1723,28 +1720,14 @@ def ns2d_residual(pred, inp, tables, forcing_spec=None, affine=None, size_averag
     trapezoidal one, second order in the nonlinear term: the loss is for |interval N_tt| small (DESIGN.md 10.12 has the
     table).  pred, inp: [B, M, N] or [B, 1, M, N] (one channel: the vorticity is scalar) contiguous fp32 tensors on the
     GPU; gradient for pred only, no CPU fallback."""
-    ok = pred.dim() in (3, 4) and pred.shape == inp.shape and (pred.dim() == 3 or pred.shape[1] == 1)
-    if not ok:
-        raise ValueError(f"ns2d_residual: pred {tuple(pred.shape)} / inp {tuple(inp.shape)}, expected equal [B, M, N] or "
-                         "[B, 1, M, N] shapes (one channel)")
-    if pred.dtype != torch.float32 or inp.dtype != torch.float32:
-        raise ValueError(f"ns2d_residual: expected float32 fields, got {pred.dtype} / {inp.dtype}")
-    M, N = int(pred.shape[-2]), int(pred.shape[-1])
-    tables = tuple(tables)
-    want = (M, _kp(N))
-    if len(tables) != 4 or any(tuple(t.shape) != want for t in tables):
-        raise ValueError(f"ns2d_residual: expected the four [{M}, {want[1]}] tables of ns2d_residual_tables(M={M}, N={N}, ...), "
-                         f"got {[tuple(t.shape) for t in tables]}")
-    if forcing_spec is not None and tuple(forcing_spec.shape) != (M, 2, want[1]):
-        raise ValueError(f"ns2d_residual: forcing_spec {tuple(forcing_spec.shape)}, expected the [{M}, 2, {want[1]}] spectrum of "
+    M, N = grid = _residual_fields(_NS2D, pred, inp, "inp")
+    tables = _residual_tables(_NS2D, tables, grid, pred.device)
+    if forcing_spec is not None and tuple(forcing_spec.shape) != (M, 2, _kp(N)):
+        raise ValueError(f"ns2d_residual: forcing_spec {tuple(forcing_spec.shape)}, expected the [{M}, 2, {_kp(N)}] spectrum of "
                          "ns2d_residual_forcing")
-    _residual_affine(affine)                                  # validates
-    if not pred.is_cuda:
-        ptr(pred)                                             # the CPU refusal of every op
-    em1, m0, m1, il = (_f32c(t.detach().to(pred.device)) for t in tables)
     fs = None if forcing_spec is None else _f32c(forcing_spec.detach().to(pred.device))
-    return _Ns2dResidual.apply(pred, inp, em1, m0, m1, il, fs, None if affine is None else tuple(float(v) for v in affine),
-                               bool(size_average), bool(reduction))
+    return _EquationResidual.apply(_NS2D, pred, inp, tables + (fs,), _residual_affine(affine), bool(size_average),
+                                   bool(reduction))
 
 
 # ----------------------------------------------------------------------------

@@ -23,7 +23,7 @@ import torch.distributed as dist
 
 from rpde.ops import frozen_weights
 from rpde.parallel import FlatGradBucket
-from utils.loss import RelativeL2Loss
+from utils.loss import RelativeL2Loss, call_loss
 
 
 def _dist_on() -> bool:
@@ -96,7 +96,7 @@ def train(model, train_loader, val_loader, optimizer, scheduler, y_normalizer=No
         if decode:
             pred_y = y_normalizer.decode(pred_y, device=device)
             batch_y = y_normalizer.decode(batch_y, device=device)
-        return loss_fn(pred_y, batch_y, batch_x) if takes_input else loss_fn(pred_y, batch_y)
+        return call_loss(loss_fn, pred_y, batch_y, batch_x)
     seen: dict = {}          # batch shape -> eager steps run so far, then its GraphedTrainStep
     loss_history, val_loss_history = [], []
     for epoch in range(epochs):
@@ -128,7 +128,7 @@ def train(model, train_loader, val_loader, optimizer, scheduler, y_normalizer=No
             if use_normalizer and y_normalizer is not None:
                 pred_y = y_normalizer.decode(pred_y, device=device)
                 batch_y = y_normalizer.decode(batch_y, device=device)
-            loss = loss_fn(pred_y, batch_y, batch_x) if takes_input else loss_fn(pred_y, batch_y)
+            loss = call_loss(loss_fn, pred_y, batch_y, batch_x)
             loss.backward()
             bucket.all_reduce_mean()
             bucket.detach_untouched()          # parameters outside the graph keep grad None, as after zero_grad()

@@ -112,7 +112,7 @@ class _GridTableLoss(nn.Module):
             raise ValueError(self._bad_rank(grid))
         z = torch.zeros((1, 1) + grid, dtype=torch.float32, device=device, requires_grad=True)
         ones = torch.ones_like(z.detach())
-        (self(z, None, ones) if getattr(self, "takes_input", False) else self(z, ones)).sum().backward()
+        call_loss(self, z, ones, ones).sum().backward()
         torch.cuda.synchronize(z.device)
 
     def _reduce(self, v):
@@ -258,7 +258,29 @@ class SpectrumMatchingLoss(_BandedLoss):
         return self._reduce(((torch.log(e_x + delta) - torch.log(e_y + delta)) ** 2).sum(1) / T.J_e)
 
 
-class EquationResidualLoss(_GridTableLoss):
+class _ResidualLoss(_GridTableLoss):
+    """What the equation residuals share: forward(pred, target, inp) with the network's input (`takes_input`), the
+    decode maps of set_affine and the refusals.  A subclass supplies `dims`, _build and forward, which raises
+    _no_input() where inp is None."""
+
+    takes_input = True
+    _affine = None                    # (a_p, b_p, a_x, b_x), or None for the identity
+
+    def set_affine(self, pred=(1.0, 0.0), inp=(1.0, 0.0)) -> None:
+        """decode maps of the prediction and of the input, each (a, b) for a field + b; set before a capture"""
+        aff = (float(pred[0]), float(pred[1]), float(inp[0]), float(inp[1]))
+        if not all(math.isfinite(v) for v in aff):
+            raise ValueError(f"{type(self).__name__}.set_affine: {pred} / {inp}")
+        self._affine = None if aff == (1.0, 0.0, 1.0, 0.0) else aff
+
+    def _bad_rank(self, grid) -> str:
+        return f"{type(self).__name__}.warm: grid {grid}, the equation is {('one', 'two')[self.dims - 1]}-dimensional"
+
+    def _no_input(self) -> ValueError:
+        return ValueError(f"{type(self).__name__}: the network's input is needed next to its prediction")
+
+
+class EquationResidualLoss(_ResidualLoss):
     """Does the prediction p ~ u(t + interval) follow from the input x = u(t) under
 
         u_t = L u - (advect/2) (u^2)_x,   l_n = c2 kappa_n^2 + c4 kappa_n^4 + i (c1 kappa_n + c3 kappa_n^3),  kappa_n = 2 pi n / length
@@ -281,7 +303,6 @@ class EquationResidualLoss(_GridTableLoss):
     Device tables are cached per (grid, device), so one object serves mixed-resolution batches; warm((N,), device) builds
     them, the plans and the workspaces ahead of a hipGraph capture."""
 
-    takes_input = True
     dims = 1
 
     def __init__(self, length, interval, c1=0.0, c2=0.0, c3=0.0, c4=0.0, advect=1.0, dealias=True, size_average=True,
@@ -293,7 +314,6 @@ class EquationResidualLoss(_GridTableLoss):
                              "coefficient finite")
         self.length, self.interval, self.c1, self.c2, self.c3, self.c4, self.advect = vals
         self.dealias = bool(dealias)
-        self._affine = None
 
     @classmethod
     def burgers(cls, nu_eff, length, interval, **kw):
@@ -310,24 +330,14 @@ class EquationResidualLoss(_GridTableLoss):
         """u_t + u u_x + dispersion u_xxx = viscosity u_xx (data_generation/kdv_1d.py)"""
         return cls(length, interval, c2=-float(viscosity), c3=float(dispersion), **kw)
 
-    def set_affine(self, pred=(1.0, 0.0), inp=(1.0, 0.0)) -> None:
-        """decode maps of the prediction and of the input, each (a, b) for a field + b; set before a capture"""
-        aff = (float(pred[0]), float(pred[1]), float(inp[0]), float(inp[1]))
-        if not all(math.isfinite(v) for v in aff):
-            raise ValueError(f"EquationResidualLoss.set_affine: {pred} / {inp}")
-        self._affine = None if aff == (1.0, 0.0, 1.0, 0.0) else aff
-
     def _build(self, grid, device):
         host = ops.etd1d_residual_tables(grid[0], self.length, self.c1, self.c2, self.c3, self.c4, self.interval,
                                          self.advect, self.dealias)
         return tuple(h.to(device).contiguous() for h in host)
 
-    def _bad_rank(self, grid) -> str:
-        return f"EquationResidualLoss.warm: grid {grid}, the equation is one-dimensional"
-
     def forward(self, pred, target, inp):
         if inp is None:
-            raise ValueError("EquationResidualLoss: the network's input is needed next to its prediction")
+            raise self._no_input()
         return ops.etd1d_residual(pred, inp, self._table((int(pred.shape[-1]),), pred.device), self._affine,
                                   self.size_average, self.reduction)
 
@@ -340,7 +350,7 @@ def reference_forcing(M: int, N: int) -> torch.Tensor:
     return 0.1 * (torch.sin(2 * math.pi * (x + y)) + torch.cos(2 * math.pi * (x + y)))
 
 
-class VorticityResidualLoss(_GridTableLoss):
+class VorticityResidualLoss(_ResidualLoss):
     """Does the prediction p ~ w(t + interval) follow from the input x = w(t) under the 2-D vorticity equation of the
     generator (rpde.ops.ns2d_solve, data_generation/ns_2d.py) on the unit periodic square,
 
@@ -363,7 +373,6 @@ class VorticityResidualLoss(_GridTableLoss):
     on the GPU (more channels: ValueError), gradient for pred only.  set_affine, the per-(grid, device) table cache and
     warm((M, N), device) as in EquationResidualLoss."""
 
-    takes_input = True
     dims = 2
     _explicit_kind = "forcing"
 
@@ -383,14 +392,6 @@ class VorticityResidualLoss(_GridTableLoss):
         else:
             raise ValueError(f"VorticityResidualLoss: forcing must be None, 'reference' or an [M, N] tensor, got {forcing!r}")
         self.dealias = bool(dealias)
-        self._affine = None
-
-    def set_affine(self, pred=(1.0, 0.0), inp=(1.0, 0.0)) -> None:
-        """decode maps of the prediction and of the input, each (a, b) for a field + b; set before a capture"""
-        aff = (float(pred[0]), float(pred[1]), float(inp[0]), float(inp[1]))
-        if not all(math.isfinite(v) for v in aff):
-            raise ValueError(f"VorticityResidualLoss.set_affine: {pred} / {inp}")
-        self._affine = None if aff == (1.0, 0.0, 1.0, 0.0) else aff
 
     def _build(self, grid, device):
         tabs = ops.ns2d_residual_tables(grid[0], grid[1], self.viscosity, self.interval, self.dealias)
@@ -406,17 +407,19 @@ class VorticityResidualLoss(_GridTableLoss):
         fs = None if f is None else ops.ns2d_residual_forcing(f, self.viscosity, self.interval).to(device).contiguous()
         return tuple(t.to(device).contiguous() for t in tabs), fs
 
-    def _bad_rank(self, grid) -> str:
-        return f"VorticityResidualLoss.warm: grid {grid}, the equation is two-dimensional"
-
     def forward(self, pred, target, inp):
         if inp is None:
-            raise ValueError("VorticityResidualLoss: the network's input is needed next to its prediction")
+            raise self._no_input()
         if pred.dim() not in (3, 4) or (pred.dim() == 4 and pred.shape[1] != 1):
             raise ValueError(f"VorticityResidualLoss: expected [B, M, N] or [B, 1, M, N] (the vorticity is one channel), got "
                              f"{tuple(pred.shape)}")
         tabs, fs = self._table((int(pred.shape[-2]), int(pred.shape[-1])), pred.device)
         return ops.ns2d_residual(pred, inp, tabs, fs, self._affine, self.size_average, self.reduction)
+
+
+def call_loss(fn, pred, target, inp):
+    """fn(pred, target, inp) for an objective whose `takes_input` is true, fn(pred, target) for every other"""
+    return fn(pred, target, inp) if getattr(fn, "takes_input", False) else fn(pred, target)
 
 
 class SumLoss(nn.Module):
@@ -443,6 +446,6 @@ class SumLoss(nn.Module):
             raise ValueError("SumLoss: a term needs the network's input (call it as loss(pred, target, inp))")
         out = None
         for w, fn in zip(self.weights, self.terms):
-            v = (fn(x, y, inp) if getattr(fn, "takes_input", False) else fn(x, y)) * w
+            v = call_loss(fn, x, y, inp) * w
             out = v if out is None else out + v
         return out

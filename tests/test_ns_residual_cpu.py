@@ -188,7 +188,7 @@ def _hs_elems(B, M, N):
 def test_workspace_and_spectrum_sizes_at_the_refusal_boundaries():
     from rpde import _lib as L
     lib = L.load()
-    ws, se = lib.rpde_ns2d_residual_work_bytes, lib.rpde_ns2d_residual_spec_elems
+    ws, se = lib.rpde_ns2d_residual_ws_bytes, lib.rpde_ns2d_residual_spec_elems
     assert se(2, 16, 24) == 2 * _hs_elems(2, 16, 24) and ws(2, 16, 24) > 0 and ws(2, 16, 24) % 256 == 0
     # at least the eight derivative spectra, their row stage and the eight fields
     assert ws(2, 16, 24) >= 4 * (16 * _hs_elems(2, 16, 24) + 8 * 2 * 16 * 24)
@@ -216,7 +216,7 @@ def test_query_and_entries_share_their_layouts(entry, dims):
     import re
     from rpde import _lib as L
     lib = L.load()
-    need = lib.rpde_ns2d_residual_work_bytes(*dims)
+    need = lib.rpde_ns2d_residual_ws_bytes(*dims)
     assert need > 0 and need % 256 == 0
 
     def call(n):
@@ -240,7 +240,7 @@ def test_query_and_entries_share_their_layouts(entry, dims):
 def test_argument_errors_are_reported_without_a_gpu():
     from rpde import _lib as L
     lib = L.load()
-    nws = lib.rpde_ns2d_residual_work_bytes(2, 16, 24)
+    nws = lib.rpde_ns2d_residual_ws_bytes(2, 16, 24)
 
     def fwd(B=2, M=16, N=24, p=FAKE, x=FAKE, em1=FAKE, m0=FAKE, m1=FAKE, il=FAKE, fs=None, stats=FAKE, spec=FAKE, ws=FAKE, n=nws):
         return lib.rpde_ns2d_residual_fwd(p, x, em1, m0, m1, il, fs, None, FAKE, FAKE, stats, spec, B, M, N, 1, ws, n, None)

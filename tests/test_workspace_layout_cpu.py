@@ -41,6 +41,7 @@ CASES = [
     ("grf1d", (2, 48), "grf1d", (2, 48)),
     ("etd1d", (2, 48), "etd1d_steps", (2, 48, 1)),
     ("etd_residual", (2, 1024), "etd_residual_bwd", (2, 1024, 1)),
+    ("ns2d_residual", (2, 16, 24), "ns2d_residual_fwd", (2, 16, 24, 1)),
     ("darcy2d", (2, 16), "darcy2d_solve", (0, 2, 16, 4, 1e-6)),
 ]
 
