@@ -666,6 +666,35 @@ int rpde_darcy2d_solve(const float* a, const float* f, int f_batched, const floa
 int rpde_sep2d(const float* in, const float* L, const float* R, float* out, int B, int s, void* ws, size_t ws_bytes,
                void* stream);
 
+/* ---- equation-residual loss of the Darcy generator (csrc/darcy_residual.hip; utils/loss.py DarcyResidualLoss; no
+ * counterpart in the reference): does the map a -> p ~ u satisfy the discrete equation of the generator above?  The
+ * equation is steady and the network's input is the coefficient.  With a~ = a_x a + b_x and u~ = a_p p + b_p (affine =
+ * four host floats (a_p, b_p, a_x, b_x) or NULL, as in the residual blocks above) and one right-hand side f [s][s],
+ *   r_b = f - A(a~_b) u~_b,   A the operator of the apply call, bit for bit,
+ *   S, inv_lambda given (the dual norm of the preconditioner P = A(1)):  E_b = sum_k inv_lambda_k (S r_b S^T)_k^2 = r_b . P^-1 r_b,
+ *   S = inv_lambda = NULL (L2):                                          E_b = |r_b|^2,
+ *   rel[b] = sqrt(E_b) / (D + 1e-8),  D the same norm of f, formed by the caller in float64 (rpde.ops.darcy2d_residual_tables),
+ * then mean / sum / the per-sample vector; rel, loss, stats [2 B] = (sqrt(E_b), D) and the upstream gradients as in
+ * the residual blocks above.  Every face weight lies in [a_min, a_max], hence a_min P <= A(a) <= a_max P and the dual
+ * norm is the energy-norm error of p to within sqrt of the contrast at every grid size; the L2 form grows like s^2
+ * (DESIGN.md 10.14).  spec (the spec_elems query's count of floats, B s s) is kept for backward: inv_lambda . (S r S^T),
+ * or r for L2.  Forward: one apply kernel (decode on load), then for the dual norm one sep2d and one streaming kernel,
+ * then the family's final kernel -- five launches, two for L2.  Backward, A being self-adjoint:
+ *   z_b = S^T spec_b S (L2: z = spec),   grad_p = -a_p coef_b A(a~_b) z_b,   coef_b = upstream_b / ((D + 1e-8) sqrt(E_b)),
+ * 0 where E_b = 0: one sep2d and one apply kernel -- three launches, one for L2.  It reads the coefficient a again.
+ * Limits, alignment and the workspace are the generator's: rpde_darcy2d_ws_bytes(B, s) serves both calls (each carves
+ * a layout of its own that fits the solve's), the spec query returns 0 for a grid the generator refuses.  No atomics,
+ * no host synchronisation, no device-to-host read: identical calls give identical bits and a batch equals its B = 1
+ * calls.  A decoded coefficient that is not positive makes the loss non-finite: the caller's contract, not checked.
+ * Argument errors are reported before any device work. */
+size_t rpde_darcy2d_residual_spec_elems(int B, int s);
+int rpde_darcy2d_residual_fwd(const float* p, const float* a, const float* f, const float* S, const float* inv_lambda,
+                              double D, const float* affine, float* rel, float* loss, float* stats, float* spec, int B,
+                              int s, int size_average, void* ws, size_t ws_bytes, void* stream);
+int rpde_darcy2d_residual_bwd(const float* a, const float* spec, const float* S, const float* affine, const float* stats,
+                              const float* grad_loss, const float* grad_rel, float* grad_p, int B, int s, int size_average,
+                              void* ws, size_t ws_bytes, void* stream);
+
 /* ---- optimizer step: torch.optim.AdamW as built at main_1d.py:144 / main_2d.py:173 (decoupled weight decay,
  * bias-corrected moments, no amsgrad), one streaming kernel over flat fp32 buffers of n (multiple of 4) elements.
  * The caller passes the step's scalars: 1 - lr*wd, 1 - b1, b2, 1 - b2, lr / (1 - b1^t), sqrt(1 - b2^t), eps. */

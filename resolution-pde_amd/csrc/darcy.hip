@@ -26,66 +26,11 @@
 // u is carried as an unevaluated sum u + ul (two-float arithmetic in the update kernel): a dozen plain fp32 updates would
 // each round u at its full size, and that high-frequency noise times s^2 is what the true residual then shows (at
 // s = 32: 2e-5 plain against 6e-6 for the correctly rounded exact solution).  u is always the rounded value of the pair.
-#include "halfspec.h"
+#include "darcy.h"
 
 namespace rpde {
 
-constexpr int DARCY_MIN_S = 8, DARCY_MAX_S = 512;
-
-inline bool darcy_dims_ok(int B, int s) {
-  return B >= 1 && B <= 65535 && s >= DARCY_MIN_S && s <= DARCY_MAX_S && s % 4 == 0;
-}
-#define DARCY_CHECK_DIMS(what, B, s)                                                                                  \
-  RPDE_CHECK_ARG(darcy_dims_ok(B, s), what ": bad B=%d s=%d (s a multiple of 4, %d .. %d, 1 <= B <= 65535)", B, s, \
-                 DARCY_MIN_S, DARCY_MAX_S)
-
 struct DarcyState { double rz, ff; int active, frozen_at; };
-
-// the sum of n partials, lane-strided then across the wave: every wave of every block of the sample computes the same bits
-__device__ __forceinline__ double darcy_fold(const double* __restrict__ part, int n) {
-  double acc = 0.0;
-  for (int i = threadIdx.x & 63; i < n; i += 64) acc += part[i];
-  return wave_sum(acc);
-}
-// the block's sum to part[blockIdx.x] (256 threads, four waves added in order)
-__device__ __forceinline__ void darcy_block_partial(float v, double* __restrict__ part) {
-  __shared__ double sh[4];
-  const double w = wave_sum((double)v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = w;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
-__device__ __forceinline__ bool darcy_pos_finite(double v) { return v > 0.0 && v < INFINITY; }
-__device__ __forceinline__ float darcy_hmean(float x, float y) { return (2.f * x * y) / (x + y); }
-
-// (A u) of the four cells (i, j0 .. j0+3) of one sample, difference form
-__device__ __forceinline__ void darcy_row4(const float* __restrict__ a, const float* __restrict__ u, int s, int i, int j0,
-                                           float s2, float (&out)[4]) {
-  const long o = (long)i * s + j0;
-  const bool hw = j0 > 0, he = j0 + 4 < s, hn = i > 0, hs = i + 1 < s;
-  float ac[4], uc[4], an[4] = {0.f, 0.f, 0.f, 0.f}, un[4] = {0.f, 0.f, 0.f, 0.f}, as[4] = {0.f, 0.f, 0.f, 0.f},
-                      us[4] = {0.f, 0.f, 0.f, 0.f};
-  ld4(a + o, ac);
-  ld4(u + o, uc);
-  if (hn) { ld4(a + o - s, an); ld4(u + o - s, un); }
-  if (hs) { ld4(a + o + s, as); ld4(u + o + s, us); }
-  const float aw = hw ? a[o - 1] : 0.f, uw = hw ? u[o - 1] : 0.f;
-  const float ae = he ? a[o + 4] : 0.f, ue = he ? u[o + 4] : 0.f;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const bool l = j > 0 || hw, r = j < 3 || he;
-    const float al = j > 0 ? ac[j - 1] : aw, ul = j > 0 ? uc[j - 1] : uw;
-    const float ar = j < 3 ? ac[j + 1] : ae, ur = j < 3 ? uc[j + 1] : ue;
-    const float c = ac[j], two_c = 2.f * c, v = uc[j];
-    const float wl = l ? darcy_hmean(c, al) : two_c, wr = r ? darcy_hmean(c, ar) : two_c;
-    const float wn = hn ? darcy_hmean(c, an[j]) : two_c, ws = hs ? darcy_hmean(c, as[j]) : two_c;
-    float acc = wl * (v - (l ? ul : 0.f));
-    acc = fmaf(wr, v - (r ? ur : 0.f), acc);
-    acc = fmaf(wn, v - (hn ? un[j] : 0.f), acc);
-    acc = fmaf(ws, v - (hs ? us[j] : 0.f), acc);
-    out[j] = s2 * acc;
-  }
-}
 
 // MODE 0: out = A u                                   (rpde_darcy2d_apply)
 //      1: out = A u and partials of u . out, frozen samples skipped     (u is the direction p)
@@ -289,19 +234,6 @@ __global__ __launch_bounds__(64) void k_darcy_finish(const double* __restrict__ 
     rel[b] = S.ff > 0.0 ? (float)sqrt(rr / S.ff) : (rr == 0.0 ? 0.f : INFINITY);
     frozen_at[b] = S.active ? iterations : S.frozen_at;
   }
-}
-
-// out_b = op(L) in_b op(R)^T over B images [s, s]: cf_rowdft with the shared table for the left factor (into tmp), one GEMM
-// over [B s, s] for the right one.  lt / rt: the table is stored transposed (op(X) = X^T)
-static int sep2d(const float* in, const float* L, bool lt, const float* R, bool rt, float* tmp, float* out, int B, int s,
-                 hipStream_t st) {
-  RPDE_TRY(cf_rowdft(L, s, lt, s, s, in, tmp, B, s, st));
-  rpde_gemm_desc d = gemm_desc();
-  d.A = tmp; d.a_kmajor = 1; d.lda = s;
-  d.B = R; d.b_kmajor = rt ? 0 : 1; d.ldb = s;
-  d.C = out; d.ldc = s;
-  d.M = B * s; d.N = s; d.K = s;
-  return launch_gemm(d, st);
 }
 
 }  // namespace rpde

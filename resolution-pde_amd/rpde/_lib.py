@@ -176,6 +176,9 @@ _SIGNATURES = {
     "rpde_darcy2d_apply": (_I, [_P, _P, _P, _I, _I, _P]),
     "rpde_darcy2d_solve": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _Z, _P]),
     "rpde_sep2d": (_I, [_P, _P, _P, _P, _I, _I, _P, _Z, _P]),
+    "rpde_darcy2d_residual_spec_elems": (_Z, [_I, _I]),
+    "rpde_darcy2d_residual_fwd": (_I, [_P] * 5 + [_D] + [_P] * 5 + [_I, _I, _I, _P, _Z, _P]),
+    "rpde_darcy2d_residual_bwd": (_I, [_P] * 8 + [_I, _I, _I, _P, _Z, _P]),
     "rpde_adamw_step": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _F, _F, _P]),
     "rpde_adamw_step_dev": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _P, _P]),
     "rpde_adamw_set_hyper_dev": (_I, [_P, _F, _F, _P]),

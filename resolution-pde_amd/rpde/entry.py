@@ -76,13 +76,20 @@ def _vorticity_residual(eq):
     return VorticityResidualLoss(float(eq["viscosity"]), float(eq["interval"]), forcing=forcing)
 
 
-# training.loss=residual, the `equation:` mapping of the 1-D ETD family (False) and of kind ns_vorticity (True): the keys
-# it may hold, those it must, the loss it builds and the refusal of any other mapping
+def _darcy_residual(eq):
+    from utils.loss import DarcyResidualLoss
+    return DarcyResidualLoss(forcing=float(eq.get("forcing", 1.0)), norm=str(eq.get("norm", "dual")))
+
+
+# training.loss=residual, the `equation:` mapping by kind -- None: the 1-D ETD family, which names none --: the rank of
+# its grids, the keys it may hold, those it must, the loss it builds and the refusal of any other mapping
 _RESIDUALS = {
-    False: ({"c1", "c2", "c3", "c4", "advect", "length", "interval"}, {"length", "interval"}, _etd_residual,
-            "equation needs length and interval and takes c1, c2, c3, c4, advect"),
-    True: ({"kind", "viscosity", "interval", "forcing"}, {"viscosity", "interval"}, _vorticity_residual,
-           "a ns_vorticity equation needs viscosity and interval and takes forcing (reference, or none)"),
+    None: (1, {"c1", "c2", "c3", "c4", "advect", "length", "interval"}, {"length", "interval"}, _etd_residual,
+           "equation needs length and interval and takes c1, c2, c3, c4, advect"),
+    "ns_vorticity": (2, {"kind", "viscosity", "interval", "forcing"}, {"viscosity", "interval"}, _vorticity_residual,
+                     "a ns_vorticity equation needs viscosity and interval and takes forcing (reference, or none)"),
+    "darcy": (2, {"kind", "forcing", "norm"}, {"kind"}, _darcy_residual,
+              "a darcy equation takes forcing (a number, default 1.0) and norm (dual, or l2)"),
 }
 
 
@@ -98,8 +105,10 @@ def training_loss(training, dims: int, dataset=None):
                               (EquationResidualLoss in 1-D), built from the data set's `equation:` mapping
                               {c1, c2, c3, c4, advect, length, interval} (length and interval required, the rest
                               default to 0 and advect to 1); in 2-D the mapping {kind: ns_vorticity, viscosity,
-                              interval, forcing} (forcing: reference, or none) builds VorticityResidualLoss, and a
-                              2-D mapping without that kind is refused; run() sets the decode maps (residual_affine)
+                              interval, forcing} (forcing: reference, or none) builds VorticityResidualLoss and
+                              {kind: darcy, forcing, norm} (forcing a number, default 1.0; norm dual or l2; only the
+                              kind is required; reduced_resolution must be 1) builds DarcyResidualLoss; a 2-D mapping
+                              without a known kind is refused; run() sets the decode maps (residual_affine)
     band and spectrum take training.loss_bands (octave; radial in 2-D, modes in 1-D) and training.loss_num_bands, and
     the 1-D rollout record then also carries the octave band energies along the rollout.  Anything else: SystemExit.
     Validation, the test score and the sweeps stay relative L2."""
@@ -114,16 +123,26 @@ def training_loss(training, dims: int, dataset=None):
     if name == "residual":
         from utils.loss import RelativeL2Loss, SumLoss
         eq = dict((None if dataset is None else dataset.get("equation")) or {})
-        vorticity = dims == 2 and eq.get("kind") == "ns_vorticity"
-        if dims != 1 and not vorticity:
+        kind = eq.get("kind") if dims != 1 else None             # a 1-D mapping names no kind: the key is refused below
+        row = _RESIDUALS.get(kind if kind is None else str(kind))
+        if dims != 1 and (row is None or row[0] != dims):
             raise SystemExit(f"training.loss=residual: the equation residual is one-dimensional, got dims={dims} (a 2-D data "
-                             "set names the vorticity equation: `equation: {kind: ns_vorticity, viscosity, interval, forcing}`)")
+                             "set names the vorticity equation: `equation: {kind: ns_vorticity, viscosity, interval, forcing}`"
+                             ", or the Darcy equation: `equation: {kind: darcy, forcing, norm}`)")
         if not eq:
             raise SystemExit("training.loss=residual: the dataset config has no `equation:` mapping "
                              "({c1, c2, c3, c4, advect, length, interval})")
-        allowed, required, make, refusal = _RESIDUALS[vorticity]
+        _, allowed, required, make, refusal = row
         if set(eq) - allowed or not required <= set(eq):
             raise SystemExit(f"training.loss=residual: {refusal}; got {sorted(eq)}")
+        if kind == "darcy":
+            # strided samples of the cell centres (i + 1/2) / s are not the cell centres of the coarse grid: the coarse
+            # discrete equation does not hold for them (DESIGN.md 10.14 has the figure)
+            params = dataset.get("dataset_params") or {}
+            if int(params.get("reduced_resolution", 1)) != 1:
+                raise SystemExit("training.loss=residual: the Darcy residual needs the generator's own grid, got "
+                                 f"dataset_params.reduced_resolution={params.get('reduced_resolution')} (strided cell centres "
+                                 "are not the cell centres of the coarse grid)")
         try:
             res = make(eq)
         except ValueError as e:

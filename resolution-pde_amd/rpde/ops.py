@@ -11,7 +11,7 @@ import contextlib
 import os
 
 import ctypes as C
-from typing import List, NamedTuple, Optional, Sequence, Tuple
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -1553,11 +1553,15 @@ def _residual_affine(affine):
 class _Equation(NamedTuple):
     """What tells one equation residual from the other at the C ABI"""
     op: str                           # the op's name, for messages
-    stem: str                         # the entries are rpde_<stem>_{ws_bytes, spec_elems, fwd, bwd}
-    nd: int                           # the rank of the grid: the entries' dims are (B, *grid)
+    stem: str                         # the entries are rpde_<stem>_{spec_elems, fwd, bwd}
+    nd: int                           # the rank of the grid
     bwd_tables: slice                 # which of the forward's tables the backward gets
     bwd_pred: bool                    # whether the backward gets the prediction
     limits: str                       # the sizes the entries serve, for the refusal of any other
+    bwd_input: bool = False           # whether the backward gets the network's input
+    query: str = ""                   # the size query rpde_<query>_ws_bytes, where it is not the stem's own
+    square: bool = False              # the entries' dims are (B, s) of a square grid, else (B, *grid)
+    table_shapes: Optional[Callable] = None       # grid -> the shape of each table; None: nd + 2 half-spectrum tables
 
 
 _ETD1D = _Equation("etd1d_residual", "etd_residual", 1, slice(2, 3), True,
@@ -1565,38 +1569,44 @@ _ETD1D = _Equation("etd1d_residual", "etd_residual", 1, slice(2, 3), True,
 _NS2D = _Equation("ns2d_residual", "ns2d_residual", 2, slice(2, 4), False,
                   "even axes 4 .. 4096; 8 B <= 65535 and 32 B max(M, N) < 2^31: eight derivative fields per sample are one "
                   "batch of the half-spectrum layer")
+# steady, and the input is the operator's coefficient: the backward applies the operator again and needs it
+_DARCY2D = _Equation("darcy2d_residual", "darcy2d_residual", 2, slice(1, 2), False,
+                     "a square grid, s a multiple of 4, 8 .. 512, 1 <= B <= 65535", bwd_input=True, query="darcy2d",
+                     square=True, table_shapes=lambda grid: [tuple(grid)] * 3)
 
 
 class _EquationResidual(torch.autograd.Function):
     """rpde_<stem>_fwd(p, x, *tables, affine, rel, loss, stats, spec, *dims, size_average) and
-    rpde_<stem>_bwd([p,] spec, *bwd_tables, affine, stats, grad_loss, grad_rel, grad_p, *dims, size_average); `tables`
-    are device tensors or None (no forcing), checked by the caller"""
+    rpde_<stem>_bwd([p,] [x,] spec, *bwd_tables, affine, stats, grad_loss, grad_rel, grad_p, *dims, size_average);
+    `tables` are device tensors, None (no forcing; the L2 norm) or host floats (passed by value), checked by the caller"""
 
     @staticmethod
     def forward(ctx, eq: _Equation, pred, x, tables, aff, size_average: bool, reduction: bool):
-        op, stem, nd, bwd_tables, bwd_pred, limits = eq
+        op, stem, nd, bwd_tables, bwd_pred, limits, bwd_input, query, square, _ = eq     # one unpack (DESIGN.md 10.13)
         lib = load()
         shape = tuple(pred.shape)
-        dims = (shape[0], *shape[-nd:])
-        p, x = _f32c(pred).reshape(*dims), _f32c(x.detach()).reshape(*dims)
+        field = (shape[0], *shape[-nd:])
+        dims = field[:2] if square else field
+        p, x = _f32c(pred).reshape(*field), _f32c(x.detach()).reshape(*field)
         pp, px = ptr(p), ptr(x)                               # raises for CPU tensors: there is no fallback
         dev = p.device
-        nws = getattr(lib, f"rpde_{stem}_ws_bytes")(*dims)
+        nws = getattr(lib, f"rpde_{query or stem}_ws_bytes")(*dims)
         if nws == 0:
-            sizes = " ".join(f"{n}={v}" for n, v in zip("BMN" if nd == 2 else "BN", dims))
+            sizes = " ".join(f"{n}={v}" for n, v in zip("Bs" if square else "BMN" if nd == 2 else "BN", dims))
             raise ValueError(f"{op}: unsupported {sizes} ({limits})")
         stats, rel, loss = _rel_outputs(dims[0], dev, reduction)
         spec = torch.empty(getattr(lib, f"rpde_{stem}_spec_elems")(*dims), dtype=torch.float32, device=dev)
         # ptr() is for tensors that come from outside; what was allocated here needs no check
-        run(stem + "_fwd", nws, dev, pp, px, *[ptr(t) for t in tables], aff, rel.data_ptr(), ptr(loss), stats.data_ptr(),
-            spec.data_ptr(), *dims, int(size_average))
-        ctx.save_for_backward(*((p, spec) if bwd_pred else (spec,)), *tables[bwd_tables], stats)
+        run(stem + "_fwd", nws, dev, pp, px, *[t if isinstance(t, float) else ptr(t) for t in tables], aff, rel.data_ptr(),
+            ptr(loss), stats.data_ptr(), spec.data_ptr(), *dims, int(size_average))
+        lead = ((p,) if bwd_pred else ()) + ((x,) if bwd_input else ()) + (spec,)
+        ctx.save_for_backward(*lead, *tables[bwd_tables], stats)
         ctx.meta = (stem + "_bwd", shape, dims, nws, aff, size_average, reduction)
         return loss if reduction else rel
 
     @staticmethod
     def backward(ctx, g):
-        *lead, stats = ctx.saved_tensors                      # ([p,] spec, the backward's tables), stats
+        *lead, stats = ctx.saved_tensors                      # ([p,] [x,] spec, the backward's tables), stats
         entry, shape, dims, nws, aff, size_average, reduction = ctx.meta
         g = _f32c(g)
         gp = torch.empty(shape, dtype=torch.float32, device=stats.device)
@@ -1622,6 +1632,16 @@ def _residual_tables(eq: _Equation, tables, grid, device):
     """ValueError unless `tables` are the three [2, kp] (1-D) or four [M, kp] (2-D) tables of <op>_tables for this grid;
     -> the tables, detached, as contiguous fp32 tensors on the device"""
     tables = tuple(tables)
+    if eq.table_shapes is not None:
+        # tables of shapes of the equation's own; None stands for a table the chosen variant does not take
+        shapes = eq.table_shapes(grid)
+        if len(tables) != len(shapes) or any(t is not None and (not torch.is_tensor(t) or tuple(t.shape) != sh)
+                                             for t, sh in zip(tables, shapes)):
+            sizes = ", ".join(f"{n}={v}" for n, v in zip("MN"[-eq.nd:], grid))
+            raise ValueError(f"{eq.op}: expected the {len(shapes)} tables {[list(sh) for sh in shapes]} of "
+                             f"{eq.op}_tables({sizes}, ...), got "
+                             f"{[tuple(t.shape) if torch.is_tensor(t) else t for t in tables]}")
+        return tuple(None if t is None else _f32c(t.detach().to(device)) for t in tables)
     count, shape = eq.nd + 2, (2 if eq.nd == 1 else grid[0], _kp(grid[-1]))
     if len(tables) != count or any(tuple(t.shape) != shape for t in tables):
         sizes = ", ".join(f"{n}={v}" for n, v in zip("MN"[-eq.nd:], grid))
@@ -1749,16 +1769,22 @@ def darcy2d_tables(s: int):
     S[k, i] = sqrt(2/s) sin(pi (k+1) (i+1/2) / s) with row s-1 divided by sqrt 2 (DST-II, orthogonal);
     inv_lambda[k1, k2] = 1 / (l_k1 + l_k2), l_k = s^2 (2 - 2 cos(pi (k+1) / s)): the eigenvalues of the finite-volume
     Dirichlet Laplacian on cell centres, whose eigenvectors are the rows of S."""
+    S, inv_lambda = _darcy2d_tables64("darcy2d_tables", s)
+    return S.to(torch.float32), inv_lambda.to(torch.float32)
+
+
+def _darcy2d_tables64(what: str, s):
+    """(S, inv_lambda) of darcy2d_tables in float64, before the rounding"""
     import math
     s = int(s)
     if s < 8 or s > 512 or s % 4:
-        raise ValueError(f"darcy2d_tables: s must be a multiple of 4, 8 .. 512, got {s}")
+        raise ValueError(f"{what}: s must be a multiple of 4, 8 .. 512, got {s}")
     k = torch.arange(1, s + 1, dtype=torch.float64).view(s, 1)
     x = (torch.arange(s, dtype=torch.float64) + 0.5).view(1, s)
     S = math.sqrt(2.0 / s) * torch.sin(math.pi * k * x / s)
     S[s - 1] /= math.sqrt(2.0)
     lam = float(s) ** 2 * (2.0 - 2.0 * torch.cos(math.pi * k.view(-1) / s))
-    return S.to(torch.float32), (1.0 / (lam.view(s, 1) + lam.view(1, s))).to(torch.float32)
+    return S, 1.0 / (lam.view(s, 1) + lam.view(1, s))
 
 
 def sep2d(x: torch.Tensor, L: torch.Tensor, R: torch.Tensor) -> torch.Tensor:
@@ -1817,6 +1843,72 @@ def darcy2d_solve(a: torch.Tensor, f: torch.Tensor, iterations: int = 24, tol: f
     run("darcy2d_solve", lib.rpde_darcy2d_ws_bytes(B, s), dev, pa, pf, int(f.dim() == 3), ptr(S), ptr(inv_lambda),
         ptr(u), ptr(rel), frozen_at.data_ptr(), B, s, iterations, tol)
     return u, rel, frozen_at
+
+
+# ----------------------------------------------------------------------------
+# equation-residual loss of the Darcy generator (csrc/darcy_residual.hip, rpde_darcy2d_residual_*; utils/loss.py
+# DarcyResidualLoss).  Forward and backward on the device, GPU tensors only, no CPU fallback.
+# ----------------------------------------------------------------------------
+DARCY_NORMS = ("dual", "l2")
+
+
+def darcy2d_residual_tables(s: int, forcing=1.0, norm: str = "dual"):
+    """(f, S, inv_lambda, D): what the Darcy equation residual needs on an s x s grid.  f: the right-hand side, float32
+    [s, s] on the host -- a constant (the generator's --forcing) or one [s, s] field, rounded once.  norm="dual": S and
+    inv_lambda of darcy2d_tables and D = sqrt(sum_k inv_lambda_k (S f S^T)_k^2), the norm of f that the preconditioner
+    P = A(1) induces (f . P^-1 f); norm="l2": S = inv_lambda = None and D = |f|_2.  D is a Python float, formed in
+    float64 from the rounded f and the unrounded tables.  f = 0 is a ValueError: the ratio has no denominator."""
+    import math
+    if norm not in DARCY_NORMS:
+        raise ValueError(f"darcy2d_residual_tables: norm must be one of {DARCY_NORMS}, got {norm!r}")
+    S, inv_lambda = _darcy2d_tables64("darcy2d_residual_tables", s)
+    s = int(s)
+    if torch.is_tensor(forcing):
+        if tuple(forcing.shape) != (s, s):
+            raise ValueError(f"darcy2d_residual_tables: forcing {tuple(forcing.shape)}, expected one [{s}, {s}] field for "
+                             "the batch")
+        f = forcing.detach().cpu().to(torch.float32).contiguous()
+    else:
+        f = torch.full((s, s), float(forcing), dtype=torch.float32)
+    f64 = f.double()
+    if not bool(torch.isfinite(f64).all()):
+        raise ValueError("darcy2d_residual_tables: the forcing must be finite")
+    if norm == "dual":
+        D = math.sqrt(float((inv_lambda * (S @ f64 @ S.T) ** 2).sum()))
+    else:
+        D = math.sqrt(float((f64 ** 2).sum()))
+    if not D > 0.0:
+        raise ValueError("darcy2d_residual_tables: the forcing is zero: the relative residual has no denominator")
+    if norm == "l2":
+        return f, None, None, D
+    return f, S.to(torch.float32), inv_lambda.to(torch.float32), D
+
+
+def darcy2d_residual(pred, a, tables, affine=None, size_average: bool = True, reduction: bool = True):
+    """Does pred ~ u solve -div(a grad u) = f, u = 0 on the boundary, in the discretisation of the generator
+    (darcy2d_solve)?  With the tables (f, S, inv_lambda, D) of darcy2d_residual_tables (host or device tensors) and
+    r = f - A(a~) p~, A the operator of darcy2d_apply,
+        norm="dual":  rel[b] = sqrt(sum_k inv_lambda_k (S r[b] S^T)_k^2) / (D + 1e-8)   (r . P^-1 r, P = A(1))
+        norm="l2":    rel[b] = |r[b]|_2 / (D + 1e-8)                                   (S = inv_lambda = None)
+    then mean / sum / the per-sample vector as relative_l2.  affine = (a_p, b_p, a_x, b_x): p~ = a_p pred + b_p,
+    a~ = a_x a + b_x (None: the identity); the gradient is with respect to pred itself.  The dual norm is the
+    energy-norm error of the prediction to within sqrt(a_max / a_min), whatever the grid; the L2 form grows like s^2
+    (DESIGN.md 10.14).  A decoded coefficient that is not positive makes the loss non-finite (not checked: the
+    optimizer's non-finite step skipping takes such a step).  pred, a: [B, s, s] or [B, 1, s, s] contiguous fp32
+    tensors on the GPU, s a multiple of 4 in 8 .. 512; gradient for pred only, no CPU fallback."""
+    eq = _DARCY2D
+    grid = tuple(int(n) for n in _residual_fields(eq, pred, a, "a"))
+    if grid[0] != grid[1] or grid[0] < 8 or grid[0] > 512 or grid[0] % 4:
+        raise ValueError(f"{eq.op}: unsupported grid {grid} ({eq.limits})")
+    tables = tuple(tables)
+    if len(tables) != 4 or isinstance(tables[3], bool) or not isinstance(tables[3], (int, float)) or \
+            (tables[1] is None) != (tables[2] is None) or tables[0] is None:
+        raise ValueError(f"{eq.op}: expected the tables (f, S, inv_lambda, D) of darcy2d_residual_tables(s={grid[0]}, ...)")
+    D = float(tables[3])
+    if not (D > 0.0 and D < float("inf")):
+        raise ValueError(f"{eq.op}: the norm D of the right-hand side must be positive and finite, got {D}")
+    fields = _residual_tables(eq, tables[:3], grid, pred.device)
+    return _EquationResidual.apply(eq, pred, a, fields + (D,), _residual_affine(affine), bool(size_average), bool(reduction))
 
 
 def warm_plans(model, resolutions, dims: int, in_channels: int = 1, device="cuda") -> None:

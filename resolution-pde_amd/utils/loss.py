@@ -16,8 +16,10 @@ EquationResidualLoss (no counterpart in the reference): the physics-informed ter
 u_t = L u - (c/2) (u^2)_x -- does the one-step map satisfy the equation itself? -- forward and backward on the device
 (rpde.ops.etd1d_residual, csrc/etd_residual.hip).  It reads the network's input next to its prediction
 (`takes_input`).  VorticityResidualLoss (no counterpart in the reference): the same term for the 2-D vorticity equation
-of the Navier-Stokes generator (rpde.ops.ns2d_residual, csrc/ns_residual.hip).  SumLoss adds weighted losses into one
-callable."""
+of the Navier-Stokes generator (rpde.ops.ns2d_residual, csrc/ns_residual.hip).  DarcyResidualLoss (no counterpart in
+the reference): the term for the steady Darcy generator, whose input is the operator's coefficient, in the dual norm of
+the solver's preconditioner or in L2 (rpde.ops.darcy2d_residual, csrc/darcy_residual.hip).  SumLoss adds weighted
+losses into one callable."""
 from __future__ import annotations
 
 import math
@@ -415,6 +417,78 @@ class VorticityResidualLoss(_ResidualLoss):
                              f"{tuple(pred.shape)}")
         tabs, fs = self._table((int(pred.shape[-2]), int(pred.shape[-1])), pred.device)
         return ops.ns2d_residual(pred, inp, tabs, fs, self._affine, self.size_average, self.reduction)
+
+
+class DarcyResidualLoss(_ResidualLoss):
+    """Does the prediction p ~ u solve the Darcy equation of the generator (rpde.ops.darcy2d_solve,
+    data_generation/darcy_2d.py) for the coefficient a the network was given,
+
+        -div(a grad u) = f on the unit square,  u = 0 on the boundary ?
+
+    The equation is steady: the network's input is the operator's coefficient, not an earlier state.  With r = f - A(a) p,
+    A the generator's finite-volume operator (harmonic face weights, wall faces 2 a_c, difference form),
+
+        norm="dual" (default):  rel[b] = sqrt(r[b] . P^-1 r[b]) / (sqrt(f . P^-1 f) + 1e-8),  P = A(1)
+        norm="l2":              rel[b] = |r[b]|_2 / (|f|_2 + 1e-8)
+
+    then mean / sum / per-sample vector as RelativeL2Loss.  P is the solver's preconditioner, inverted exactly by two
+    sine transforms.  Every face weight lies in [a_min, a_max], so a_min P <= A(a) <= a_max P and, with e = u* - p,
+    a_min e.A e <= r.P^-1 r <= a_max e.A e: the dual norm is the energy-norm error of the prediction to within
+    sqrt(a_max / a_min) at every grid size, without knowing u*.  The L2 form (the strong-form PINO term) multiplies
+    cell-scale error by about 8 s^2 a and grows with the grid: float64, coefficients 12 / 3, f = 1, a prediction 1 %
+    of white noise away from u*: 0.13 at s = 8 and 19 at s = 100 in L2, 0.041 and 0.46 in the dual norm; 5 % of a smooth
+    perturbation: 0.043 and 0.41 against 0.026 and 0.033 (DESIGN.md 10.14 has the table).  p = 0 is rel = 1 in both.
+
+    forcing: a constant (the generator's --forcing, default 1.0) or one [s, s] tensor for ONE grid; zero is refused.
+    forward(pred, target, inp): the target is unused and may be None; pred, inp = a: [B, s, s] or [B, 1, s, s] fp32
+    tensors on the GPU, s a multiple of 4 in 8 .. 512 (more channels: ValueError), gradient for pred only.  A decoded
+    coefficient that is not positive makes the loss non-finite; it is not checked, and the optimizer's non-finite step
+    skipping takes such a step.  set_affine matters here: an encoded coefficient is negative wherever a < mean, so the
+    decode map is what makes the operator meaningful.  The samples must be the generator's cell centres: strided
+    samples of a finer grid are not the cell centres of the coarse one.  set_affine, the per-(grid, device) table cache
+    and warm((s, s), device) as in EquationResidualLoss."""
+
+    dims = 2
+    _explicit_kind = "forcing"
+
+    def __init__(self, forcing=1.0, norm="dual", size_average=True, reduction=True):
+        super().__init__(size_average, reduction)
+        if norm not in ops.DARCY_NORMS:
+            raise ValueError(f"DarcyResidualLoss: norm must be one of {ops.DARCY_NORMS}, got {norm!r}")
+        self.norm = norm
+        if torch.is_tensor(forcing):
+            if forcing.dim() != 2 or forcing.shape[0] != forcing.shape[1]:
+                raise ValueError(f"DarcyResidualLoss: a forcing tensor is one [s, s] field, got {tuple(forcing.shape)}")
+            self._explicit = forcing.detach().double().cpu()
+            if not bool(torch.isfinite(self._explicit).all()) or not bool(self._explicit.any()):
+                raise ValueError("DarcyResidualLoss: the forcing must be finite and not zero")
+            self.forcing = "explicit"
+        else:
+            try:
+                self.forcing = float(forcing)
+            except (TypeError, ValueError):
+                raise ValueError(f"DarcyResidualLoss: forcing must be a number or an [s, s] tensor, got {forcing!r}")
+            if not math.isfinite(self.forcing) or self.forcing == 0.0:
+                raise ValueError(f"DarcyResidualLoss: the forcing must be finite and not zero, got {forcing}")
+
+    def _build(self, grid, device):
+        if grid[0] != grid[1]:
+            raise ValueError(f"DarcyResidualLoss: the grid {grid} is not square")
+        if self._explicit is not None and tuple(self._explicit.shape) != tuple(grid):
+            raise ValueError(f"DarcyResidualLoss: the forcing of shape {tuple(self._explicit.shape)} does not serve the "
+                             f"grid {grid}")
+        f, S, il, D = ops.darcy2d_residual_tables(grid[0], self.forcing if self._explicit is None else self._explicit,
+                                                  self.norm)
+        return tuple(None if t is None else t.to(device).contiguous() for t in (f, S, il)) + (D,)
+
+    def forward(self, pred, target, inp):
+        if inp is None:
+            raise self._no_input()
+        if pred.dim() not in (3, 4) or (pred.dim() == 4 and pred.shape[1] != 1):
+            raise ValueError(f"DarcyResidualLoss: expected [B, s, s] or [B, 1, s, s] (the pressure is one channel), got "
+                             f"{tuple(pred.shape)}")
+        tabs = self._table((int(pred.shape[-2]), int(pred.shape[-1])), pred.device)
+        return ops.darcy2d_residual(pred, inp, tabs, self._affine, self.size_average, self.reduction)
 
 
 def call_loss(fn, pred, target, inp):
