@@ -86,6 +86,8 @@ typedef struct {
   /* epilogue: C = acc * act'(drop(aux)) * dropscale   (backward through act), or with
    * RPDE_EPI_MULAUX: C = acc * aux (aux holds a stored derivative)                */
   int epi_dact;            /* RPDE_ACT_*, RPDE_EPI_MULAUX or 0                      */
+  /* aux (row stride ldaux) and aux_out (row stride ldc) follow C's batch offsets: entry z is read / written at
+   * z1*sC1 + z2*sC2 from their base pointers */
   const float* aux; int64_t ldaux;
   /* dropout shared by prologue / epilogue: element id = point*drop_ld + feature;
    * drop_where: bit 0 mask the A operand, bit 1 the B operand, bit 2 the epilogue's aux */

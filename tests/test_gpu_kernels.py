@@ -339,7 +339,8 @@ def test_native_fp32_mfma_path_stays_green(gpu_device):
     env = dict(os.environ, RPDE_SPLIT_BF16="0")
     here = os.path.dirname(os.path.abspath(__file__))
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(here, "test_gpu_kernels.py"),
-                        os.path.join(here, "test_gpu_golden.py"), "-q", "-m", "gpu", "-p", "no:cacheprovider", "-x"],
+                        os.path.join(here, "test_gpu_golden.py"), os.path.join(here, "test_gpu_gemm_descriptor.py"),
+                        "-q", "-m", "gpu", "-p", "no:cacheprovider", "-x"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-3000:]
 
