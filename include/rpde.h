@@ -633,6 +633,63 @@ int rpde_ns2d_residual_bwd(const float* spec, const float* m1, const float* inv_
                            const float* grad_loss, const float* grad_rel, float* grad_p, int B, int M, int N,
                            int size_average, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- equation-residual loss of the active-scalar system (csrc/nsc_residual.hip; utils/loss.py
+ * ActiveScalarResidualLoss; no counterpart in the reference): does the one-step map x = (c, q, v)(t) -> p ~ (c, q, v)(t + D),
+ * both [B, 3, M, N], satisfy the equations of the active-scalar generator above (rpde_nsc2d_steps)?  The data are
+ * concentration and velocity; the equations evolve (w, c) with w = curl u.  Conventions of the vorticity block above;
+ * with the channel spectra x^ and d^ (d = p~ - x~ formed in physical space, ONE affine map for the three channels):
+ *   X_c = x^_c,  X_w = 2 pi i k1 x^_v - 2 pi i k2 x^_q   (likewise D_c, D_w;  P = X + D),
+ *   N_w(W, C) = dealias (rfft2(q w_1 + v w_2) - beta 2 pi i k1 C),  N_c(W, C) = dealias rfft2(q c_1 + v c_2): the
+ *               generator's F_w and F_c; q, v from psi = W / lap, so only the solenoidal part of a velocity advects,
+ *   r^_w = D_w - em1_nu X_w + m0_nu N_w(X) + m1_nu N_w(P) - forcing_spec,       z = -D visc lap,
+ *   r^_c = D_c - em1_kappa X_c + m0_kappa N_c(X) + m1_kappa N_c(P),             z = -D kappa lap,
+ *   delta^ = 2 pi i k1 P_q + 2 pi i k2 P_v  (the divergence of the predicted velocity),
+ *   mu = (d^_q[0,0], d^_v[0,0])             (the change of the mean velocity, which the equations conserve),
+ *   E_ru = sum_{k != 0} c (|r^_w|^2 + |delta^|^2) / lap / (M N) + |mu|^2 / (M N),   E_rc = sum c |r^_c|^2 / (M N),
+ *   rel[b] = sqrt(scalar_weight E_rc + E_ru) / (sqrt(scalar_weight E(x^_c) + E(x^_q) + E(x^_v)) + 1e-8):
+ * the vorticity's residual measured as the velocity it induces (energy |r^|^2 / lap), in the norm of the data's channels.
+ * The buoyancy is not stiff and sits in N_w, as in the generator.  The tables are those of the vorticity block, once
+ * per diffusivity (rpde.ops.nsc2d_residual_tables), m0 and m1 with the mask; forcing_spec as there, at the viscosity.
+ * affine, rel, loss, stats and the upstream gradients as in the 1-D block; spec (the spec_elems query's count of
+ * floats, 5 B images: [r^_w / lap | scalar_weight r^_c | delta^ / lap, its mean mode holding mu | P_w | P_c]) is kept
+ * for backward.
+ * Forward: the float64 analysis of the vorticity block over the 3 B images of x~ and over the 3 B images of d; X_w,
+ * X_c, P_w, P_c from the float64 channel spectra, rounded once; the generator's fan-out (scalar part on) of the 2 B
+ * states [X | P] to twelve derivative spectra per sample, one inverse transform of 12 B images, the four products, one
+ * forward transform of 4 B, the residual kernel (everything in float64 from the float64 channel spectra, the buoyancy
+ * terms included; partial sums per (sample, slot)) and the family's final kernel.
+ * Backward, the exact adjoint of the discrete operator.  With rho_w = r^_w / lap (0 at the mean mode), rho_c =
+ * scalar_weight r^_c, rho_d = delta^ / lap, g_w = irfft2(m1_nu rho_w), g_c = irfft2(m1_kappa rho_c) and the six fields of p~
+ * rebuilt from (P_w, P_c) in one inverse transform of 8 B images, the six products, one forward transform of 6 B,
+ *   G_w = rho_w + conj(2 pi i k2 / lap) rfft2(g_w w_1 + g_c c_1) + conj(-2 pi i k1 / lap) rfft2(g_w w_2 + g_c c_2)
+ *               + conj(2 pi i k1) rfft2(g_w q) + conj(2 pi i k2) rfft2(g_w v),
+ *   G_c = rho_c + conj(2 pi i k1) rfft2(g_c q) + conj(2 pi i k2) rfft2(g_c v) + conj(-beta 2 pi i k1) m1_nu rho_w,
+ *   grad p_c = irfft2(G_c),  grad p_q = irfft2(conj(-2 pi i k2) G_w + conj(2 pi i k1) rho_d + [k = 0] mu_q),
+ *   grad p_v = irfft2(conj(2 pi i k1) G_w + conj(2 pi i k2) rho_d + [k = 0] mu_v),   all times a_p coef_b
+ * (one inverse transform of 3 B images).
+ * rpde_nsc2d_residual_state is the forward up to the fan-out's state alone: state [4][B][M][re|im][kp] floats =
+ * (X_w, P_w, X_c, P_c).
+ * Even M, N in 4 .. 4096 and 12 B images within the half-spectrum layer's limits (12 B <= 65535, 48 B max(M, N) <
+ * 2^31): the two queries return 0 otherwise.  Fields, tables and spectra 16-byte aligned, the workspace 256-byte
+ * aligned.  The size query serves the three calls (one layout per entry, the query returns the largest); it is called
+ * *_arena_bytes and not *_ws_bytes because the set of *_ws_bytes names is closed: tests/test_workspace_layout_cpu.py
+ * pins it, and this query has the same query-against-entry check in tests/test_nsc_residual_cpu.py.  No atomics, no
+ * host synchronisation, everything on the caller's stream (the first use of a grid builds its plans: it allocates and
+ * synchronises once).  Argument errors are reported before any device work; the finiteness of the affine map is the
+ * last of them, behind the verdict on the workspace. */
+size_t rpde_nsc2d_residual_arena_bytes(int B, int M, int N);
+size_t rpde_nsc2d_residual_spec_elems(int B, int M, int N);
+int rpde_nsc2d_residual_state(const float* p, const float* x, const float* affine, float* state, int B, int M, int N,
+                              void* ws, size_t ws_bytes, void* stream);
+int rpde_nsc2d_residual_fwd(const float* p, const float* x, const float* em1_nu, const float* m0_nu, const float* em1_kappa,
+                            const float* m0_kappa, const float* forcing_spec, float scalar_weight, const float* m1_nu,
+                            const float* m1_kappa, const float* inv_lap, float beta, const float* affine, float* rel,
+                            float* loss, float* stats, float* spec, int B, int M, int N, int size_average, void* ws,
+                            size_t ws_bytes, void* stream);
+int rpde_nsc2d_residual_bwd(const float* spec, const float* m1_nu, const float* m1_kappa, const float* inv_lap, float beta,
+                            const float* affine, const float* stats, const float* grad_loss, const float* grad_rel,
+                            float* grad_p, int B, int M, int N, int size_average, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- Darcy flow generator (csrc/darcy.hip; reference: dataloaders/darcy_loader.py and the piececonst_* files of
  * load_darcy_data_from_mat): -div(a grad u) = f on the unit square, u = 0 on the boundary, s x s cells with centres
  * x_i = (i + 1/2) / s, a and u [B, s, s] at the centres.  Finite volumes: an interior face between cells c and n weighs

@@ -170,6 +170,11 @@ _SIGNATURES = {
     "rpde_ns2d_residual_spectrum": (_I, [_P] * 4 + [_I, _I, _I, _P, _Z, _P]),
     "rpde_ns2d_residual_fwd": (_I, [_P] * 12 + [_I, _I, _I, _I, _P, _Z, _P]),
     "rpde_ns2d_residual_bwd": (_I, [_P] * 8 + [_I, _I, _I, _I, _P, _Z, _P]),
+    "rpde_nsc2d_residual_arena_bytes": (_Z, [_I, _I, _I]),
+    "rpde_nsc2d_residual_spec_elems": (_Z, [_I, _I, _I]),
+    "rpde_nsc2d_residual_state": (_I, [_P] * 4 + [_I, _I, _I, _P, _Z, _P]),
+    "rpde_nsc2d_residual_fwd": (_I, [_P] * 7 + [_F] + [_P] * 3 + [_F] + [_P] * 5 + [_I, _I, _I, _I, _P, _Z, _P]),
+    "rpde_nsc2d_residual_bwd": (_I, [_P] * 4 + [_F] + [_P] * 5 + [_I, _I, _I, _I, _P, _Z, _P]),
     "rpde_grf1d_ws_bytes": (_Z, [_I, _I]),
     "rpde_grf1d": (_I, [_P, _P, _P, _I, _I, _P, _Z, _P]),
     "rpde_darcy2d_ws_bytes": (_Z, [_I, _I]),

@@ -81,6 +81,14 @@ def _darcy_residual(eq):
     return DarcyResidualLoss(forcing=float(eq.get("forcing", 1.0)), norm=str(eq.get("norm", "dual")))
 
 
+def _active_scalar_residual(eq):
+    from utils.loss import ActiveScalarResidualLoss
+    forcing = eq.get("forcing")
+    forcing = None if forcing is None or str(forcing).lower() in ("none", "null") else str(forcing)
+    return ActiveScalarResidualLoss(float(eq["viscosity"]), float(eq["diffusivity"]), float(eq["buoyancy"]),
+                                    float(eq["interval"]), forcing=forcing)
+
+
 # training.loss=residual, the `equation:` mapping by kind -- None: the 1-D ETD family, which names none --: the rank of
 # its grids, the keys it may hold, those it must, the loss it builds and the refusal of any other mapping
 _RESIDUALS = {
@@ -90,6 +98,10 @@ _RESIDUALS = {
                      "a ns_vorticity equation needs viscosity and interval and takes forcing (reference, or none)"),
     "darcy": (2, {"kind", "forcing", "norm"}, {"kind"}, _darcy_residual,
               "a darcy equation takes forcing (a number, default 1.0) and norm (dual, or l2)"),
+    "active_scalar": (2, {"kind", "viscosity", "diffusivity", "buoyancy", "interval", "forcing"},
+                      {"kind", "viscosity", "diffusivity", "buoyancy", "interval"}, _active_scalar_residual,
+                      "an active_scalar equation needs viscosity, diffusivity, buoyancy and interval and takes forcing "
+                      "(reference, or none)"),
 }
 
 
@@ -107,8 +119,11 @@ def training_loss(training, dims: int, dataset=None):
                               default to 0 and advect to 1); in 2-D the mapping {kind: ns_vorticity, viscosity,
                               interval, forcing} (forcing: reference, or none) builds VorticityResidualLoss and
                               {kind: darcy, forcing, norm} (forcing a number, default 1.0; norm dual or l2; only the
-                              kind is required; reduced_resolution must be 1) builds DarcyResidualLoss; a 2-D mapping
-                              without a known kind is refused; run() sets the decode maps (residual_affine)
+                              kind is required; reduced_resolution must be 1) builds DarcyResidualLoss and
+                              {kind: active_scalar, viscosity, diffusivity, buoyancy, interval, forcing} (forcing:
+                              reference, or none; the rest required) builds ActiveScalarResidualLoss for the
+                              three-channel (c, q, v) data; a 2-D mapping without a known kind is refused; run() sets
+                              the decode maps (residual_affine)
     band and spectrum take training.loss_bands (octave; radial in 2-D, modes in 1-D) and training.loss_num_bands, and
     the 1-D rollout record then also carries the octave band energies along the rollout.  Anything else: SystemExit.
     Validation, the test score and the sweeps stay relative L2."""
@@ -128,7 +143,8 @@ def training_loss(training, dims: int, dataset=None):
         if dims != 1 and (row is None or row[0] != dims):
             raise SystemExit(f"training.loss=residual: the equation residual is one-dimensional, got dims={dims} (a 2-D data "
                              "set names the vorticity equation: `equation: {kind: ns_vorticity, viscosity, interval, forcing}`"
-                             ", or the Darcy equation: `equation: {kind: darcy, forcing, norm}`)")
+                             ", the Darcy equation: `equation: {kind: darcy, forcing, norm}`, or the active-scalar system: "
+                             "`equation: {kind: active_scalar, viscosity, diffusivity, buoyancy, interval, forcing}`)")
         if not eq:
             raise SystemExit("training.loss=residual: the dataset config has no `equation:` mapping "
                              "({c1, c2, c3, c4, advect, length, interval})")
@@ -163,15 +179,26 @@ def training_loss(training, dims: int, dataset=None):
         raise SystemExit(f"training.loss={name}: {e}")
 
 
-def residual_affine(loss_fn, x_normalizer, y_normalizer, use_normalizer: bool, minmax: bool = False) -> None:
+def residual_affine(loss_fn, x_normalizer, y_normalizer, use_normalizer: bool, minmax: bool = False, ranges=None) -> None:
     """The decode maps of a training.loss=residual objective from the data set's normalisers, so that the equation is
     asked in physical units: the input is decoded with the x-statistics; the prediction with the y-statistics, unless
     training.use_normalizer is true -- train() has decoded it by then and its map is the identity.  Only one global
-    affine map (SimpleNormalizer) folds into the loss: point-wise or min-max normalisers are a SystemExit."""
+    affine map folds into the loss: SimpleNormalizer, or min-max normalisation with the loader's four scalar extrema
+    `ranges` = (min_data, max_data, min_model, max_model), field * (max - min) + min (four None: the loader did not
+    normalise, the identity).  Point-wise normalisers, and min-max without scalar ranges, are a SystemExit."""
     from utils.loss import _ResidualLoss
     from utils.normalizers import scalar_stats
     terms = [t for t in getattr(loss_fn, "terms", [loss_fn]) if isinstance(t, _ResidualLoss)]
     if not terms:
+        return
+    if minmax and ranges is not None and all(r is None for r in ranges):
+        for t in terms:
+            t.set_affine()
+        return
+    if minmax and ranges is not None and len(ranges) == 4 and all(isinstance(r, (int, float)) for r in ranges):
+        lo_x, hi_x, lo_y, hi_y = (float(r) for r in ranges)
+        for t in terms:
+            t.set_affine(pred=(hi_y - lo_y, lo_y), inp=(hi_x - lo_x, lo_x))
         return
     if minmax:
         raise SystemExit("training.loss=residual: min-max normalised data is not supported (normalization_type: simple, "
@@ -268,7 +295,8 @@ def run(dims: int, argv=None):
     # optional training objective (no yaml carries it): training_loss() below
     loss_name, loss_fn = training_loss(args.training, dims, args.dataset)
     if loss_fn is not None:
-        residual_affine(loss_fn, x_normalizer, y_normalizer, bool(args.training.use_normalizer), normalization_type == "minmax")
+        residual_affine(loss_fn, x_normalizer, y_normalizer, bool(args.training.use_normalizer), normalization_type == "minmax",
+                        ranges=(min_data, max_data, min_model, max_model))
         for r in train_loader.resolution_groups:
             loss_fn.warm((int(r),) * dims, device)
 

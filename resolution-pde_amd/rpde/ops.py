@@ -1559,9 +1559,11 @@ class _Equation(NamedTuple):
     bwd_pred: bool                    # whether the backward gets the prediction
     limits: str                       # the sizes the entries serve, for the refusal of any other
     bwd_input: bool = False           # whether the backward gets the network's input
-    query: str = ""                   # the size query rpde_<query>_ws_bytes, where it is not the stem's own
+    query: str = ""                   # the size query rpde_<query>_ws_bytes, where it is not the stem's own; a name
+                                      # that ends in _bytes is the whole query rpde_<query>
     square: bool = False              # the entries' dims are (B, s) of a square grid, else (B, *grid)
     table_shapes: Optional[Callable] = None       # grid -> the shape of each table; None: nd + 2 half-spectrum tables
+    channels: int = 1                 # the fields are [B, channels, *grid]; one channel may be left out of the shape
 
 
 _ETD1D = _Equation("etd1d_residual", "etd_residual", 1, slice(2, 3), True,
@@ -1573,24 +1575,31 @@ _NS2D = _Equation("ns2d_residual", "ns2d_residual", 2, slice(2, 4), False,
 _DARCY2D = _Equation("darcy2d_residual", "darcy2d_residual", 2, slice(1, 2), False,
                      "a square grid, s a multiple of 4, 8 .. 512, 1 <= B <= 65535", bwd_input=True, query="darcy2d",
                      square=True, table_shapes=lambda grid: [tuple(grid)] * 3)
+# the data are (c, q, v), the equation evolves (curl u, c): three channels, seven tables (four of one diffusivity, three
+# of the other).  The size query is not called *_ws_bytes (include/rpde.h has the reason)
+_NSC2D = _Equation("nsc2d_residual", "nsc2d_residual", 2, slice(6, 10), False,
+                   "even axes 4 .. 4096; 12 B <= 65535 and 48 B max(M, N) < 2^31: twelve derivative fields per sample are "
+                   "one batch of the half-spectrum layer", query="nsc2d_residual_arena_bytes",
+                   table_shapes=lambda grid: [(grid[0], _kp(grid[1]))] * 7, channels=3)
 
 
 class _EquationResidual(torch.autograd.Function):
     """rpde_<stem>_fwd(p, x, *tables, affine, rel, loss, stats, spec, *dims, size_average) and
     rpde_<stem>_bwd([p,] [x,] spec, *bwd_tables, affine, stats, grad_loss, grad_rel, grad_p, *dims, size_average);
-    `tables` are device tensors, None (no forcing; the L2 norm) or host floats (passed by value), checked by the caller"""
+    `tables` are device tensors, None (no forcing; the L2 norm) or host floats (passed by value), checked by the caller;
+    of the backward's tables the tensors come first, then the floats"""
 
     @staticmethod
     def forward(ctx, eq: _Equation, pred, x, tables, aff, size_average: bool, reduction: bool):
-        op, stem, nd, bwd_tables, bwd_pred, limits, bwd_input, query, square, _ = eq     # one unpack (DESIGN.md 10.13)
+        op, stem, nd, bwd_tables, bwd_pred, limits, bwd_input, query, square, _, channels = eq   # one unpack (DESIGN.md 10.13)
         lib = load()
         shape = tuple(pred.shape)
-        field = (shape[0], *shape[-nd:])
-        dims = field[:2] if square else field
+        dims = (shape[0], shape[-1]) if square else (shape[0], *shape[-nd:])
+        field = (shape[0], *((channels,) if channels > 1 else ()), *shape[-nd:])
         p, x = _f32c(pred).reshape(*field), _f32c(x.detach()).reshape(*field)
         pp, px = ptr(p), ptr(x)                               # raises for CPU tensors: there is no fallback
         dev = p.device
-        nws = getattr(lib, f"rpde_{query or stem}_ws_bytes")(*dims)
+        nws = getattr(lib, f"rpde_{query}" if query.endswith("_bytes") else f"rpde_{query or stem}_ws_bytes")(*dims)
         if nws == 0:
             sizes = " ".join(f"{n}={v}" for n, v in zip("Bs" if square else "BMN" if nd == 2 else "BN", dims))
             raise ValueError(f"{op}: unsupported {sizes} ({limits})")
@@ -1600,17 +1609,18 @@ class _EquationResidual(torch.autograd.Function):
         run(stem + "_fwd", nws, dev, pp, px, *[t if isinstance(t, float) else ptr(t) for t in tables], aff, rel.data_ptr(),
             ptr(loss), stats.data_ptr(), spec.data_ptr(), *dims, int(size_average))
         lead = ((p,) if bwd_pred else ()) + ((x,) if bwd_input else ()) + (spec,)
-        ctx.save_for_backward(*lead, *tables[bwd_tables], stats)
-        ctx.meta = (stem + "_bwd", shape, dims, nws, aff, size_average, reduction)
+        kept = tables[bwd_tables]
+        ctx.save_for_backward(*lead, *[t for t in kept if not isinstance(t, float)], stats)
+        ctx.meta = (stem + "_bwd", shape, dims, nws, aff, size_average, reduction, [t for t in kept if isinstance(t, float)])
         return loss if reduction else rel
 
     @staticmethod
     def backward(ctx, g):
         *lead, stats = ctx.saved_tensors                      # ([p,] [x,] spec, the backward's tables), stats
-        entry, shape, dims, nws, aff, size_average, reduction = ctx.meta
+        entry, shape, dims, nws, aff, size_average, reduction, floats = ctx.meta
         g = _f32c(g)
         gp = torch.empty(shape, dtype=torch.float32, device=stats.device)
-        run(entry, nws, stats.device, *[ptr(t) for t in lead], aff, ptr(stats), *_upstream(g, reduction), gp.data_ptr(),
+        run(entry, nws, stats.device, *[ptr(t) for t in lead], *floats, aff, ptr(stats), *_upstream(g, reduction), gp.data_ptr(),
             *dims, int(size_average))
         return None, gp, None, None, None, None, None
 
@@ -1748,6 +1758,71 @@ def ns2d_residual(pred, inp, tables, forcing_spec=None, affine=None, size_averag
     fs = None if forcing_spec is None else _f32c(forcing_spec.detach().to(pred.device))
     return _EquationResidual.apply(_NS2D, pred, inp, tables + (fs,), _residual_affine(affine), bool(size_average),
                                    bool(reduction))
+
+
+# ----------------------------------------------------------------------------
+# equation-residual loss of the active-scalar system (csrc/nsc_residual.hip, rpde_nsc2d_residual_*; utils/loss.py
+# ActiveScalarResidualLoss).  Forward and backward on the device, GPU tensors only, no CPU fallback.
+# ----------------------------------------------------------------------------
+def nsc2d_residual_tables(M: int, N: int, visc: float, kappa: float, interval: float):
+    """(em1_nu, m0_nu, m1_nu, inv_lap, em1_kappa, m0_kappa, m1_kappa): ns2d_residual_tables once with the viscosity and
+    once with the scalar's diffusivity (z = -interval kappa lap), float32 [M, kp] host tensors, padded columns zero."""
+    return ns2d_residual_tables(M, N, visc, interval) + ns2d_residual_tables(M, N, kappa, interval)[:3]
+
+
+def nsc2d_residual(pred, inp, tables, beta: float, forcing_spec=None, scalar_weight: float = 1.0, affine=None,
+                   size_average: bool = True, reduction: bool = True):
+    """Does pred ~ (c, q, v)(t + interval) follow from inp = (c, q, v)(t) under the active-scalar system of the generator
+    (nsc2d_solve): w_t + u . grad w = visc lap w + beta dc/dx1 + f, c_t + u . grad c = kappa lap c, w = curl u?  With the
+    seven tables of nsc2d_residual_tables (host or device tensors, [M, kp] each), forcing_spec of ns2d_residual_forcing at
+    the viscosity ([M, 2, kp], or None: no forcing), X_w = 2 pi i k1 x^_v - 2 pi i k2 x^_q, X_c = x^_c, likewise D from
+    d = p~ - x~, P = X + D, and the generator's N_w (advection and buoyancy) and N_c,
+        r^_w = D_w - em1_nu X_w + m0_nu N_w(X) + m1_nu N_w(P) - forcing_spec,   r^_c = D_c - em1_kappa X_c + m0_kappa N_c(X)
+        + m1_kappa N_c(P),   delta^ = 2 pi i (k1 P_q + k2 P_v),   mu = the change of the mean of (q, v),
+        E_ru = sum_{k != 0} c (|r^_w|^2 + |delta^|^2) / lap / (M N) + |mu|^2 / (M N),   E_rc = sum c |r^_c|^2 / (M N),
+        rel[b] = sqrt(scalar_weight E_rc + E_ru) / (sqrt(scalar_weight |x~_c|^2 + |x~_q|^2 + |x~_v|^2) + 1e-8),
+    then mean / sum / the per-sample vector as relative_l2: the vorticity's residual measured as a velocity, next to
+    what the predicted velocity owes to incompressibility and to its mean.  affine = (a_p, b_p, a_x, b_x), one map for
+    the three channels: p~ = a_p pred + b_p, x~ = a_x inp + b_x (None: the identity); the gradient is with respect to
+    pred itself.  The rule is the exponential trapezoidal one (DESIGN.md 10.15 has the range of validity).  pred, inp:
+    [B, 3, M, N] = (c, q, v) contiguous fp32 tensors on the GPU; gradient for pred only, no CPU fallback."""
+    import math
+    eq = _NSC2D
+    if pred.shape != inp.shape or pred.dim() != 4 or pred.shape[1] != 3:
+        raise ValueError(f"{eq.op}: pred {tuple(pred.shape)} / inp {tuple(inp.shape)}, expected equal [B, 3, M, N] shapes: "
+                         "the three channels (c, q, v), concentration and velocity")
+    if pred.dtype != torch.float32 or inp.dtype != torch.float32:
+        raise ValueError(f"{eq.op}: expected float32 fields, got {pred.dtype} / {inp.dtype}")
+    M, N = grid = tuple(int(n) for n in pred.shape[-2:])
+    beta, lam = float(beta), float(scalar_weight)
+    if not (math.isfinite(beta) and math.isfinite(lam) and lam >= 0.0):
+        raise ValueError(f"{eq.op}: beta {beta} must be finite and scalar_weight {scalar_weight} finite and >= 0")
+    em1n, m0n, m1n, il, em1k, m0k, m1k = _residual_tables(eq, tables, grid, pred.device)
+    if forcing_spec is not None and tuple(forcing_spec.shape) != (M, 2, _kp(N)):
+        raise ValueError(f"{eq.op}: forcing_spec {tuple(forcing_spec.shape)}, expected the [{M}, 2, {_kp(N)}] spectrum of "
+                         "ns2d_residual_forcing")
+    fs = None if forcing_spec is None else _f32c(forcing_spec.detach().to(pred.device))
+    # the forward's own tables, then what the backward takes as well (m1_nu, m1_kappa, inv_lap, beta)
+    return _EquationResidual.apply(eq, pred, inp, (em1n, m0n, em1k, m0k, fs, lam, m1n, m1k, il, beta),
+                                   _residual_affine(affine), bool(size_average), bool(reduction))
+
+
+def nsc2d_residual_state(pred, inp, affine=None):
+    """[4, B, M, 2, kp] = (X_w, P_w, X_c, P_c): the state the residual's forward hands to the generator's fan-out -- the
+    curl of the velocity channels and the scalar, of x~ and of p~ = x~ + d -- from the float64 analysis, rounded once.
+    pred, inp [B, 3, M, N]; affine as nsc2d_residual.  GPU tensors only."""
+    lib = load()
+    p, x = _f32c(pred.detach()), _f32c(inp.detach())
+    pp, px = ptr(p), ptr(x)
+    if p.shape != x.shape or p.dim() != 4 or p.shape[1] != 3:
+        raise ValueError(f"nsc2d_residual_state: expected equal [B, 3, M, N] fields (c, q, v), got {tuple(p.shape)} / {tuple(x.shape)}")
+    B, _, M, N = (int(v) for v in p.shape)
+    nws = lib.rpde_nsc2d_residual_arena_bytes(B, M, N)
+    if nws == 0:
+        raise ValueError(f"nsc2d_residual_state: unsupported B={B} M={M} N={N} ({_NSC2D.limits})")
+    out = torch.empty(4, B, M, 2, _kp(N), dtype=torch.float32, device=p.device)
+    run("nsc2d_residual_state", nws, p.device, pp, px, _residual_affine(affine), ptr(out), B, M, N)
+    return out
 
 
 # ----------------------------------------------------------------------------

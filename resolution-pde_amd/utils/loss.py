@@ -18,8 +18,9 @@ u_t = L u - (c/2) (u^2)_x -- does the one-step map satisfy the equation itself? 
 (`takes_input`).  VorticityResidualLoss (no counterpart in the reference): the same term for the 2-D vorticity equation
 of the Navier-Stokes generator (rpde.ops.ns2d_residual, csrc/ns_residual.hip).  DarcyResidualLoss (no counterpart in
 the reference): the term for the steady Darcy generator, whose input is the operator's coefficient, in the dual norm of
-the solver's preconditioner or in L2 (rpde.ops.darcy2d_residual, csrc/darcy_residual.hip).  SumLoss adds weighted
-losses into one callable."""
+the solver's preconditioner or in L2 (rpde.ops.darcy2d_residual, csrc/darcy_residual.hip).  ActiveScalarResidualLoss (no
+counterpart in the reference): the term for the active-scalar generator, whose data (c, q, v) are not the evolved
+variable (rpde.ops.nsc2d_residual, csrc/nsc_residual.hip).  SumLoss adds weighted losses into one callable."""
 from __future__ import annotations
 
 import math
@@ -85,6 +86,7 @@ class _GridTableLoss(nn.Module):
     _explicit = None                  # the table given for one grid, if any, and the grid that took it
     _explicit_grid = None
     _explicit_kind = ""               # "weight" / "band", for the guard's message
+    channels = 1                      # of the throw-away fields of warm()
 
     def __init__(self, size_average=True, reduction=True):
         super().__init__()
@@ -112,7 +114,7 @@ class _GridTableLoss(nn.Module):
         grid = tuple(int(n) for n in spatial_shape)
         if len(grid) != self.dims:
             raise ValueError(self._bad_rank(grid))
-        z = torch.zeros((1, 1) + grid, dtype=torch.float32, device=device, requires_grad=True)
+        z = torch.zeros((1, self.channels) + grid, dtype=torch.float32, device=device, requires_grad=True)
         ones = torch.ones_like(z.detach())
         call_loss(self, z, ones, ones).sum().backward()
         torch.cuda.synchronize(z.device)
@@ -489,6 +491,82 @@ class DarcyResidualLoss(_ResidualLoss):
                              f"{tuple(pred.shape)}")
         tabs = self._table((int(pred.shape[-2]), int(pred.shape[-1])), pred.device)
         return ops.darcy2d_residual(pred, inp, tabs, self._affine, self.size_average, self.reduction)
+
+
+class ActiveScalarResidualLoss(_ResidualLoss):
+    """Does the prediction p ~ (c, q, v)(t + interval) follow from the input x = (c, q, v)(t) under the active-scalar
+    system of the generator (rpde.ops.nsc2d_solve, data_generation/active_scalar_2d.py) on the unit periodic square,
+
+        w_t + u . grad w = viscosity lap w + buoyancy dc/dx1 + f,   c_t + u . grad c = diffusivity lap c,   w = curl u ?
+
+    The data are concentration and velocity, channels (c, q, v) with u = (q, v); the equation evolves (w, c).  The
+    vorticity of a field is the curl of its velocity channels, only the solenoidal part of a predicted velocity advects,
+    and the loss also charges what the equation cannot see: the divergence delta of the predicted velocity and the change
+    mu of its mean (the equation conserves the mean velocity).  With the exponential trapezoidal rule of
+    VorticityResidualLoss per evolved variable (z = -interval viscosity lap for w, -interval diffusivity lap for c; the
+    buoyancy is not stiff and sits with the advection, as in the generator) giving r_w and r_c,
+
+        E_ru = sum_{k != 0} c (|r^_w|^2 + |delta^|^2) / lap / (M N) + |mu|^2 / (M N),    E_rc = sum c |r^_c|^2 / (M N)
+        rel[b] = sqrt(scalar_weight E_rc + E_ru) / (sqrt(scalar_weight |x_c|^2 + |x_q|^2 + |x_v|^2) + 1e-8)
+
+    -- the vorticity's residual measured as the velocity it induces, in the norm of the data's channels -- then mean /
+    sum / per-sample vector as RelativeL2Loss.  `interval` is the time between input and prediction: the snapshot
+    interval of the data set, not the solver's step.  Float64 figures at viscosity 1e-3, diffusivity 2e-3, buoyancy 5,
+    interval 0.05 (DESIGN.md 10.15 has the table): an exact pair gives 1.0e-3 .. 8.6e-3 against 0.074 .. 0.18 for the
+    trivial predictor p = x; without the buoyancy term the exact pair is 7.6 .. 46 times worse.
+
+    forcing: None, "reference" (the forcing of data_generation/ns_2d.py on each grid) or one [M, N] tensor for ONE grid.
+    forward(pred, target, inp): the target is unused and may be None; pred, inp [B, 3, M, N] fp32 tensors on the GPU in
+    the channel order (c, q, v) (anything else: ValueError), gradient for pred only.  set_affine takes one map for the
+    three channels (the loaders' statistics are scalar); the per-(grid, device) table cache and warm((M, N), device) as
+    in EquationResidualLoss."""
+
+    dims = 2
+    channels = 3
+    _explicit_kind = "forcing"
+
+    def __init__(self, viscosity, diffusivity, buoyancy, interval, forcing=None, scalar_weight=1.0, size_average=True,
+                 reduction=True):
+        super().__init__(size_average, reduction)
+        vals = [float(viscosity), float(diffusivity), float(buoyancy), float(interval), float(scalar_weight)]
+        if not all(math.isfinite(v) for v in vals) or vals[0] < 0 or vals[1] < 0 or not vals[3] > 0 or vals[4] < 0:
+            raise ValueError(f"ActiveScalarResidualLoss: viscosity {viscosity}, diffusivity {diffusivity} and scalar_weight "
+                             f"{scalar_weight} must be >= 0, interval {interval} positive and buoyancy {buoyancy} finite")
+        self.viscosity, self.diffusivity, self.buoyancy, self.interval, self.scalar_weight = vals
+        if torch.is_tensor(forcing):
+            if forcing.dim() != 2:
+                raise ValueError(f"ActiveScalarResidualLoss: a forcing tensor is one [M, N] field, got {tuple(forcing.shape)}")
+            self._explicit = forcing.detach().double().cpu()
+            self.forcing = "explicit"
+        elif forcing in (None, "reference"):
+            self.forcing = forcing
+        else:
+            raise ValueError(f"ActiveScalarResidualLoss: forcing must be None, 'reference' or an [M, N] tensor, got {forcing!r}")
+
+    def _build(self, grid, device):
+        tabs = ops.nsc2d_residual_tables(grid[0], grid[1], self.viscosity, self.diffusivity, self.interval)
+        if self.forcing is None:
+            f = None
+        elif self._explicit is not None:
+            if tuple(self._explicit.shape) != tuple(grid):
+                raise ValueError(f"ActiveScalarResidualLoss: the forcing of shape {tuple(self._explicit.shape)} does not "
+                                 f"serve the grid {grid}")
+            f = self._explicit
+        else:
+            f = reference_forcing(*grid)
+        fs = None if f is None else ops.ns2d_residual_forcing(f, self.viscosity, self.interval).to(device).contiguous()
+        return tuple(t.to(device).contiguous() for t in tabs), fs
+
+    def forward(self, pred, target, inp):
+        if inp is None:
+            raise self._no_input()
+        for name, t in (("prediction", pred), ("input", inp)):
+            if t.dim() != 4 or t.shape[1] != 3:
+                raise ValueError(f"ActiveScalarResidualLoss: the {name} must be [B, 3, M, N] with the channels in the order "
+                                 f"(c, q, v) -- concentration, then the velocity (q, v) -- got {tuple(t.shape)}")
+        tabs, fs = self._table((int(pred.shape[-2]), int(pred.shape[-1])), pred.device)
+        return ops.nsc2d_residual(pred, inp, tabs, self.buoyancy, fs, self.scalar_weight, self._affine, self.size_average,
+                                  self.reduction)
 
 
 def call_loss(fn, pred, target, inp):
