@@ -801,6 +801,53 @@ int rpde_adamw_apply_dev_clip(float* p, const float* g, float* m, float* v, int6
                               float lr, float b1, float b2, float eps, float weight_decay,
                               const float* step_dev, const float* clip_dev, void* stream);
 
+/* ---- CNO: the alias-free activation (csrc/cno.hip; reference models/CNO1d.py:30-45 `CNO_LReLu`, built at
+ * main_1d.py:100-104 from conf/model/cno_1d/cno_1d.yaml).  The reference resamples x [B, C, n_in] (channels first) to
+ * n_mid = 2 in_size points with F.interpolate(mode="bicubic", antialias=True), applies LeakyReLU and resamples to n_out
+ * points: three ATen ops and two round trips of the n_mid-long tensor.  Both resamplings are fixed banded linear maps,
+ * so each call below is one kernel whose mid signal lives in LDS only:
+ *   fwd:  y = scale[c] * x + shift[c] (scale, shift [C] or both null: y = x; a BatchNorm's apply step),
+ *         u = U y,  v = u > 0 ? u : slope * u,  out = D v                                        out [B, C, n_out]
+ *   bwd:  gy = U^T ((u > 0 ? 1 : slope) * D^T g)   with u recomputed from x; the gradient with respect to y (the caller
+ *         owns the chain rule of its affine); at u == 0 the derivative is slope, torch's convention.   gy [B, C, n_in]
+ * n_in, n_mid and n_out are independent.  A band is given as  span [rows][2] int32 (first source, tap count; 8-byte
+ * aligned) and weights [rows][taps] fp32 (taps a multiple of 4, zero padded, 16-byte aligned): row i is
+ * sum_t weights[i][t] * src[span[i][0] + t].  U: n_mid rows over n_in sources; D: n_out rows over n_mid; U^T: n_in rows
+ * over n_mid (for each input, the contiguous run of mid points that read it); D^T: n_mid rows over n_out.  The tables
+ * must be those of rpde.ops.cno_tables (torch's antialiased bicubic rule): the workgroup tiling is sized from that
+ * filter's support.  Rows that fit a workgroup are packed several to one, longer rows are tiled along x (1024 written
+ * points per tile, halved while the mid span of a tile exceeds its LDS); a size ratio at which 32 written points no
+ * longer fit is refused with RPDE_ERR_ARG.  No workspace, no atomics: the same inputs give the same bits. */
+int rpde_cno_act1d_fwd(const float* x, const float* scale, const float* shift, float* out, int B, int C, int n_in,
+                       int n_mid, int n_out, float slope, const int32_t* u_span, const float* u_w, int u_taps,
+                       const int32_t* d_span, const float* d_w, int d_taps, void* stream);
+int rpde_cno_act1d_bwd(const float* x, const float* scale, const float* shift, const float* g, float* gy, int B, int C,
+                       int n_in, int n_mid, int n_out, float slope, const int32_t* u_span, const float* u_w, int u_taps,
+                       const int32_t* ut_span, const float* ut_w, int ut_taps, const int32_t* dt_span, const float* dt_w,
+                       int dt_taps, void* stream);
+
+/* ---- CNO: the rest of a block (reference models/CNO1d.py:51-164: Conv1d(k=3, padding=1) -> BatchNorm1d -> CNO_LReLu,
+ * and the residual block's second BatchNorm plus skip add).  Channels first, contiguous [B, C, n].
+ * conv1d_k3: the three taps as accumulating rpde_gemm_f32 products on shifted views -- the centre tap over the whole
+ *   range with the bias, tap 0 onto [1, n), tap 2 onto [0, n - 1) (n = 1: the centre tap alone).  wt is the weight
+ *   repacked tap-major, [3][Cout][Cin].  _bwd_data: gx from g with the transposed taps and mirrored shifts.
+ *   _bwd_weight: gw [Cout][Cin][3] (torch's layout) and gb [Cout] (or null) by one deterministic reduction over
+ *   (batch, x), fp32, fixed order, no atomics.
+ * moments: sums [C][4] doubles = (sum a, sum b, sum a b, sum b^2) per channel over (batch, x).  BatchNorm's forward
+ *   reads mean and variance of z from (z, z); its backward reads sum gy and sum gy z from (gy, z).
+ * affine: out = p0[c] a + p1[c] b + p2[c] (+ residual); b and p1 both null: no b term.  A BatchNorm's apply step (with the
+ *   residual block's skip add), its backward dz = p0 gy + p1 z + p2, and a plain skip add (p0 = 1, p2 = 0).  The
+ *   coefficients [C] are doubles and the sum is formed in double and rounded once: the backward's terms cancel to
+ *   eps / (var + eps) of their size when a channel has few values. */
+int rpde_cno_conv1d_k3_fwd(const float* x, const float* wt, const float* bias, float* out, int B, int Cin, int Cout, int n,
+                           void* stream);
+int rpde_cno_conv1d_k3_bwd_data(const float* g, const float* wt, float* gx, int B, int Cin, int Cout, int n, void* stream);
+int rpde_cno_conv1d_k3_bwd_weight(const float* x, const float* g, float* gw, float* gb, int B, int Cin, int Cout, int n,
+                                  void* stream);
+int rpde_cno_moments(const float* a, const float* b, double* sums, int B, int C, int n, void* stream);
+int rpde_cno_affine(const float* a, const float* b, const double* p0, const double* p1, const double* p2, const float* residual,
+                    float* out, int B, int C, int n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

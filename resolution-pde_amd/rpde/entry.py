@@ -34,6 +34,32 @@ def _init_distributed():
     return world, rank, local
 
 
+def build_model(args):
+    """instantiate(args.model); a CNO1d is built for size = dataset.cno_train_size, the resolution it is trained at
+    (reference main_1d.py:100-104): its levels are sized from it"""
+    if str(args.model["_target_"]).endswith("CNO1d"):
+        size = args.dataset.get("cno_train_size")
+        if size is None:
+            raise SystemExit("model CNO1d: the dataset config has no `cno_train_size` (the training resolution, "
+                             "which the model's `size` is set to)")
+        return instantiate(args.model, size=int(size))
+    return instantiate(args.model)
+
+
+def _model_resolution(args):
+    """the resolution the all-resolution sweep resizes to before the model and back after it: CNO's evaluation
+    (reference utils/resize_utils.py:527-539); None for the models that run at the test resolution"""
+    return int(args.dataset["cno_train_size"]) if str(args.model["_target_"]).endswith("CNO1d") else None
+
+
+def _at_own_resolution(args, model):
+    """the model as the rollout and the error-by-frequency sweep call it at every resolution: itself, or a CNO1d behind
+    utils.resize_utils.AtResolution (resized in and out)"""
+    from utils.resize_utils import AtResolution
+    res = _model_resolution(args)
+    return model if res is None else AtResolution(model, res)
+
+
 def _sweep_fields(args, test_set, x_normalizer, y_normalizer, min_model, max_model, device):
     """What the post-training sweeps (every resolution, error by frequency) evaluate on: (test inputs as the model takes
     them, test targets in physical units, decoder of the model's output or None, evaluation_type, top resolution)."""
@@ -257,7 +283,7 @@ def run(dims: int, argv=None):
     train_loader, val_loader, test_loader = mk(train_set, True), mk(val_set, False), mk(test_set, False)
 
     torch.manual_seed(seed)                                   # same initial weights on every rank
-    model = instantiate(args.model).to(device)
+    model = build_model(args).to(device)
     torch.manual_seed(seed + 1 + rank)                        # dropout seeds are drawn from this stream: one per rank
     ckpt = args.dataset.get("saved_checkpoint_path")
     if ckpt:
@@ -322,7 +348,8 @@ def run(dims: int, argv=None):
     from utils.resize_utils import evaluate_all_resolutions, to_resolution
     tx, ty_phys, dec, how, top_res = _sweep_fields(args, test_set, x_normalizer, y_normalizer, min_model, max_model, device)
     resolution_results = evaluate_all_resolutions(model, tx, ty_phys, max_resolution=top_res, min_resolution=min(32, top_res),
-                                                  how=how, batch_size=bs, y_decode=dec, device=device)
+                                                  how=how, batch_size=bs, y_decode=dec, device=device,
+                                                  model_resolution=_model_resolution(args))
     rollout_results = rollout_bands = None
     if dims == 1:
         from utils.autoregressive_step import perform_rollout_1d, rollout_loss
@@ -353,6 +380,7 @@ def run(dims: int, argv=None):
             traj = torch.stack(frames, dim=1).to(device)                       # [n, steps+1, res]
             xn = yn = None
             enc = decode_pred = lambda t: t                                      # noqa: E731
+        roller = _at_own_resolution(args, model.eval())
         acc = torch.zeros(len(resolution_results), 2, dtype=torch.float64, device=device)
         # with a banded objective: sums over this rank's trajectories of (E_pred [J], E_true [J], log-ratio mean square)
         # per step, by resolution
@@ -360,7 +388,7 @@ def run(dims: int, argv=None):
         for k, res in enumerate(resolution_results):
             tr = to_resolution(traj, res, "naive_downsample")
             if tr.shape[0]:
-                pred = perform_rollout_1d(model.eval(), enc(tr[:, 0]), steps, device=device, x_normalizer=xn, y_normalizer=yn)
+                pred = perform_rollout_1d(roller, enc(tr[:, 0]), steps, device=device, x_normalizer=xn, y_normalizer=yn)
                 pred = decode_pred(pred)
                 acc[k, 0] += rollout_loss(pred, tr) * tr.shape[0]
                 acc[k, 1] += tr.shape[0]
@@ -453,10 +481,10 @@ def run_frequency(argv=None):
     doc = {"dims": dims, "evaluation_type": how,
            "n_test": int(tx.shape[0]), "resolutions": resolutions, "models": {}}
     for name, path in ckpts.items():
-        model = instantiate(args.model).to(device)
+        model = build_model(args).to(device)
         state = torch.load(path, map_location=device, weights_only=True)
         model.load_state_dict(state["model_state_dict"])
-        res = evaluate_frequency_error(model, tx, ty_phys, resolutions=resolutions, how=doc["evaluation_type"],
+        res = evaluate_frequency_error(_at_own_resolution(args, model), tx, ty_phys, resolutions=resolutions, how=doc["evaluation_type"],
                                        batch_size=int(args.training.batch_size), num_modes=args.get("num_modes"),
                                        num_radial_bins=int(args.get("num_radial_bins", 64)), y_decode=dec, device=device)
         doc["models"][name] = {str(r): {"error": e.tolist(), "solution": s.tolist(), "frequencies": f.tolist()}

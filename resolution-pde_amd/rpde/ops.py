@@ -1986,6 +1986,13 @@ def darcy2d_residual(pred, a, tables, affine=None, size_average: bool = True, re
     return _EquationResidual.apply(eq, pred, a, fields + (D,), _residual_affine(affine), bool(size_average), bool(reduction))
 
 
+# ----------------------------------------------------------------------------
+# CNO: resampling tables and the fused alias-free activation (rpde/cno.py)
+# ----------------------------------------------------------------------------
+from .cno import (CnoBand, CnoTables, batchnorm1d, cno_act1d, cno_dense, cno_resample_table,  # noqa: E402,F401
+                  cno_tables, cno_transpose_band, conv1d_k3, skip_add)
+
+
 def warm_plans(model, resolutions, dims: int, in_channels: int = 1, device="cuda") -> None:
     """Build every DFT plan (tables, adjoint tables, operand images: hipMalloc + one stream sync each,
     csrc/core.hip get_plan) and size the workspaces the model needs at the given grid resolutions, with one

@@ -38,18 +38,38 @@ def to_resolution(fields: torch.Tensor, target: int, how: str = "naive_downsampl
     raise ValueError(f"unknown evaluation_type {how}")
 
 
+class AtResolution(torch.nn.Module):
+    """`model` run at `resolution` whatever it is fed (1-D): a field of another length is spectrally resized to it and
+    the prediction resized back -- how a CNO1d, whose levels are sized for one resolution, joins a rollout or a sweep
+    at the others (reference utils/resize_utils.py:527-539)"""
+
+    def __init__(self, model, resolution: int):
+        super().__init__()
+        self.model, self.resolution = model, int(resolution)
+
+    def forward(self, x):
+        n = x.shape[-1]
+        if n == self.resolution:
+            return self.model(x)
+        return resize_1d(self.model(resize_1d(x, self.resolution)), n)
+
+
 @torch.no_grad()
 def evaluate_all_resolutions(model, test_x: torch.Tensor, test_y: torch.Tensor, max_resolution: Optional[int] = None,
                              min_resolution: int = 32, how: str = "naive_downsample", batch_size: int = 16,
                              x_encode: Optional[Callable] = None, y_decode: Optional[Callable] = None,
-                             device="cuda") -> Dict[int, float]:
-    """{resolution: mean relative L2 over the test samples}; encode/decode are the x / y normalisers.  With
+                             device="cuda", model_resolution: Optional[int] = None) -> Dict[int, float]:
+    """{resolution: mean relative L2 over the test samples}; encode/decode are the x / y normalisers.
+    model_resolution (1-D): the model runs at that resolution whatever the test resolution -- inputs are spectrally
+    resized to it and predictions resized back (the reference's CNO evaluation, utils/resize_utils.py:527-539); a
+    field already at that resolution is passed as it is.  With
     torch.distributed initialised every rank evaluates samples rank, rank + world, ... and the sample-weighted sums
     are reduced (NaN for a resolution without samples)."""
     import torch.distributed as dist
     on = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
     rank, world = (dist.get_rank(), dist.get_world_size()) if on else (0, 1)
     model.eval()
+    run = model if model_resolution is None else AtResolution(model, model_resolution)
     loss_fn = RelativeL2Loss(size_average=True)
     full = test_x.shape[-1]
     mine_x, mine_y = test_x[rank::world], test_y[rank::world]
@@ -61,7 +81,7 @@ def evaluate_all_resolutions(model, test_x: torch.Tensor, test_y: torch.Tensor, 
             for i in range(0, mine_x.shape[0], batch_size):
                 x = to_resolution(mine_x[i:i + batch_size].to(device), res, how)
                 y = to_resolution(mine_y[i:i + batch_size].to(device), res, how)
-                pred = model(x_encode(x) if x_encode else x)
+                pred = run(x_encode(x) if x_encode else x)
                 if y_decode:
                     pred = y_decode(pred)
                 acc[k, 0] += loss_fn(pred, y).double() * x.shape[0]
