@@ -848,6 +848,53 @@ int rpde_cno_moments(const float* a, const float* b, double* sums, int B, int C,
 int rpde_cno_affine(const float* a, const float* b, const double* p0, const double* p1, const double* p2, const float* residual,
                     float* out, int B, int C, int n, void* stream);
 
+/* ---- CNO in 2-D (csrc/cno2d.hip; reference models/CNO2d.py, built at main_2d.py:119-124 from
+ * conf/model/cno_2d/cno_2d.yaml).  CNO_LReLu resamples a plane x [B, C, h_in, w_in] (channels first, contiguous fp32) to
+ * h_mid x w_mid with F.interpolate(mode="bicubic", antialias=True), applies LeakyReLU and resamples to h_out x w_out.
+ * The 2-D resampling is the tensor product of the 1-D banded maps above, one table per axis and direction:
+ *   fwd:  y = scale[c] * x + shift[c] (or y = x),  u = U_y y U_x^T,  out = D_y lrelu(u) D_x^T       out [B, C, h_out, w_out]
+ *   bwd:  gy = U_y^T ((u > 0 ? 1 : slope) * (D_y^T g D_x)) U_x  with u recomputed from x; the gradient with respect to y;
+ *         at u == 0 the derivative is slope.                                                        gy [B, C, h_in, w_in]
+ * Bands as in 1-D (span [rows][2] int32, weights [rows][taps] fp32, taps a multiple of 4), those of
+ * rpde.ops.cno_tables(device, n_in, n_out): U_y h_in -> h_mid, U_x w_in -> w_mid, D_y h_mid -> h_out, D_x w_mid -> w_out,
+ * and for the backward their transposed forms (`bwd` of the same tables).  Planes may be rectangular and the ratios
+ * non-integer.  A workgroup owns a tile of the written plane (the output in fwd, the input in bwd), 32 x 32 points or
+ * the largest power-of-two rectangle below it whose spans fit its LDS; planes that fit whole are packed several to a
+ * workgroup; a ratio at which one row of 4 written points does not fit is refused with RPDE_ERR_ARG.  The mid plane
+ * lives in LDS only.  No workspace, no atomics: the same inputs give the same bits.
+ * rpde_cno_act2d_plan reports the tile (th, tw) and the planes per workgroup the kernels use for a shape (backward: 0
+ * or 1); it launches nothing. */
+int rpde_cno_act2d_plan(int backward, int B, int C, int h_in, int w_in, int h_mid, int w_mid, int h_out, int w_out, int* th,
+                        int* tw, int* pack);
+int rpde_cno_act2d_fwd(const float* x, const float* scale, const float* shift, float* out, int B, int C, int h_in, int w_in,
+                       int h_mid, int w_mid, int h_out, int w_out, float slope, const int32_t* uy_span, const float* uy_w,
+                       int uy_taps, const int32_t* ux_span, const float* ux_w, int ux_taps, const int32_t* dy_span,
+                       const float* dy_w, int dy_taps, const int32_t* dx_span, const float* dx_w, int dx_taps, void* stream);
+int rpde_cno_act2d_bwd(const float* x, const float* scale, const float* shift, const float* g, float* gy, int B, int C,
+                       int h_in, int w_in, int h_mid, int w_mid, int h_out, int w_out, float slope, const int32_t* uy_span,
+                       const float* uy_w, int uy_taps, const int32_t* ux_span, const float* ux_w, int ux_taps,
+                       const int32_t* uyt_span, const float* uyt_w, int uyt_taps, const int32_t* uxt_span, const float* uxt_w,
+                       int uxt_taps, const int32_t* dyt_span, const float* dyt_w, int dyt_taps, const int32_t* dxt_span,
+                       const float* dxt_w, int dxt_taps, void* stream);
+
+/* conv2d_k3: Conv2d(k = 3, padding = 1) on [B, C, H, W] as nine accumulating rpde_gemm_f32 products on shifted views --
+ *   the centre tap over the flat H W axis with the bias, the two dx = 0 taps flat over (H - 1) W points, the six dx != 0
+ *   taps row by row through the descriptor's two-level batch so that no row wraps; taps without a valid range (H = 1 or
+ *   W = 1) are skipped.  wt is the weight repacked tap-major, [9][Cout][Cin], tap = 3 ty + tx.  _bwd_data: gx from g with
+ *   the transposed taps and mirrored shifts.
+ *   _bwd_weight: gw [Cout][Cin][3][3] (torch's layout) and gb [Cout] (or null), fp32, fixed order, no atomics: the image
+ *   rows (b, y) are split into slices over enough workgroups to fill the device when Cout Cin is small, the slices'
+ *   partial sums go to the caller's `partial` [slices][9 Cout Cin + Cout] floats (rpde_cno_conv2d_k3_bwd_weight_slices
+ *   gives the count; with one slice the buffer is not used and may be null) and a second kernel adds them in slice
+ *   order. */
+int rpde_cno_conv2d_k3_fwd(const float* x, const float* wt, const float* bias, float* out, int B, int Cin, int Cout, int H,
+                           int W, void* stream);
+int rpde_cno_conv2d_k3_bwd_data(const float* g, const float* wt, float* gx, int B, int Cin, int Cout, int H, int W,
+                                void* stream);
+int rpde_cno_conv2d_k3_bwd_weight_slices(int B, int Cin, int Cout, int H, int W);
+int rpde_cno_conv2d_k3_bwd_weight(const float* x, const float* g, float* gw, float* gb, int B, int Cin, int Cout, int H, int W,
+                                  float* partial, int partial_slices, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,7 @@
 // forms the mid signal there, and writes only the result: x is read once and out written once.
 // Below it, the rest of a CNO block: Conv1d(k = 3) as three shifted GEMMs with its own weight-gradient kernel, and the
 // two kernels of BatchNorm1d (per-channel moments, per-channel affine combine).  gfx950 (CDNA4, wave64) only.
-#include "rpde_internal.h"
+#include "cno.h"
 #include "wave.h"
 
 #include <algorithm>
@@ -19,42 +19,12 @@ constexpr int CNO_MID_CAP = 2304;     // ... for the mid signal
 constexpr int CNO_G_CAP = 1280;       // ... for the staged upstream gradient (backward)
 constexpr int CNO_PACK_WORK = 2048;   // mid points per workgroup up to which short rows are packed together
 
-// one band on the device: row i reads  weights[i * taps + t] * src[span[i].x + t],  t < span[i].y  (taps: row stride,
-// a multiple of 4, zero padded)
-struct CnoBand {
-  const int2* span;
-  const float* w;
-  int taps;
-};
-
 struct CnoShape {
   int rows, C, n_in, n_mid, n_out;
   int tile, ntiles, pack;             // points per tile, tiles per row, rows per workgroup
   int vec_x, vec_o;                   // 16-byte accesses to the n_in-long / n_out-long tensors
   float slope;
 };
-
-// sum_t w[t] * src[t], t < cnt, in tap order; the weights come as 16-byte loads (rows are padded to whole float4s), the
-// padding taps are never multiplied: what lies behind a staged segment is not ours to read into a sum
-__device__ __forceinline__ float band_dot(const float* __restrict__ w, const float* src, int cnt) {
-  float acc = 0.f;
-  for (int t = 0; t < cnt; t += 4) {
-    const float4 wv = *reinterpret_cast<const float4*>(w + t);
-    acc = fmaf(wv.x, src[t], acc);
-    if (t + 1 < cnt) acc = fmaf(wv.y, src[t + 1], acc);
-    if (t + 2 < cnt) acc = fmaf(wv.z, src[t + 2], acc);
-    if (t + 3 < cnt) acc = fmaf(wv.w, src[t + 3], acc);
-  }
-  return acc;
-}
-
-// [lo, hi) read by rows [r_lo, r_hi) of a band (starts and ends are monotone in the row), clipped to [0, n)
-__device__ __forceinline__ void band_range(const CnoBand& b, int r_lo, int r_hi, int n, int& lo, int& hi) {
-  if (r_hi <= r_lo) { lo = hi = 0; return; }
-  const int2 first = b.span[r_lo], last = b.span[r_hi - 1];
-  lo = min(max(first.x, 0), n);
-  hi = min(max(last.x + last.y, lo), n);
-}
 
 // rows [r0, r0 + nr) x points [lo, lo + len) of t [rows, n] -> dst [nr][len], scale[c] * v + shift[c] on the way when
 // scale is given.  VEC: lo, len and n are multiples of 4 and t is 16-byte aligned
@@ -181,19 +151,6 @@ k_cno_act_bwd(const float* __restrict__ x, const float* __restrict__ scale, cons
 }
 
 // ---- host: tile and packing -------------------------------------------------------------------------------------
-// Bounds from the filter of an na -> nb resampling (scale = na / nb, support = 2 max(scale, 1), centres scale (i + 1/2),
-// indices truncated): the sources that L consecutive outputs read, and the outputs that read L consecutive sources
-static int cno_sources(int L, int na, int nb) {
-  const double sc = (double)na / nb, sup = 2.0 * (sc >= 1.0 ? sc : 1.0);
-  const double v = floor(sc * (L - 1) + 2.0 * sup) + 3.0;
-  return v < na ? (int)v : na;
-}
-static int cno_readers(int L, int na, int nb) {
-  const double sc = (double)na / nb, sup = 2.0 * (sc >= 1.0 ? sc : 1.0);
-  const double v = floor((L + 2.0 * sup) / sc) + 3.0;
-  return v < nb ? (int)v : nb;
-}
-
 // fills tile / ntiles / pack of s for a kernel that writes the n_w-long axis; spans(T, sm, sx, sg) bounds what a tile
 // of T written points stages (mid points, inputs, upstream gradients).  Rows that fit whole are packed, several to a
 // workgroup; longer rows are tiled with the largest tile whose spans fit
@@ -215,26 +172,6 @@ static bool cno_plan(CnoShape& s, int n_w, const Spans& spans) {
     }
   }
   return false;
-}
-
-static int cno_check(const char* what, const void* x, const void* scale, const void* shift, int B, int C, int n_in,
-                     int n_mid, int n_out, float slope) {
-  RPDE_CHECK_ARG(x, "%s: null tensor", what);
-  RPDE_CHECK_ARG(B > 0 && C > 0 && n_in > 0 && n_mid > 0 && n_out > 0, "%s: bad sizes B=%d C=%d n_in=%d n_mid=%d n_out=%d",
-                 what, B, C, n_in, n_mid, n_out);
-  RPDE_CHECK_ARG((scale == nullptr) == (shift == nullptr), "%s: scale and shift come together", what);
-  RPDE_CHECK_ARG((long)B * C < (1L << 24) && n_in < (1 << 24) && n_mid < (1 << 24) && n_out < (1 << 24),
-                 "%s: tensor too large (B*C, n_in, n_mid, n_out must stay below 2^24)", what);
-  RPDE_CHECK_ARG(slope == slope, "%s: slope is NaN", what);
-  return RPDE_OK;
-}
-
-static int cno_band(const char* what, const char* name, const void* span, const float* w, int taps) {
-  RPDE_CHECK_ARG(span && w, "%s: null %s table", what, name);
-  RPDE_CHECK_ARG(taps >= 4 && taps % 4 == 0 && al16(w) && (reinterpret_cast<uintptr_t>(span) & 7) == 0,
-                 "%s: %s table: taps %d must be a positive multiple of 4, weights 16-byte and spans 8-byte aligned", what,
-                 name, taps);
-  return RPDE_OK;
 }
 
 // ---- Conv1d(k = 3, padding = 1): weight and bias gradient ---------------------------------------------------------

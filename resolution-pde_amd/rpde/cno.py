@@ -1,10 +1,12 @@
 """The CNO side of rpde.ops (re-exported there): the banded tables of torch's antialiased bicubic resampling, the
-autograd Function over the fused alias-free activation kernel, and the rest of a CNO block -- Conv1d(k = 3), BatchNorm1d,
-the skip add -- over their kernels (csrc/cno.hip, the CNO groups of include/rpde.h).
+autograd Functions over the fused alias-free activation kernels in 1-D and 2-D, and the rest of a CNO block -- Conv1d /
+Conv2d (k = 3), BatchNorm, the skip add -- over their kernels (csrc/cno.hip, csrc/cno2d.hip, the CNO groups of
+include/rpde.h).
 
 CNO_LReLu (reference models/CNO1d.py:30-45) is  resample to 2 in_size -> LeakyReLU -> resample to out_size, both
 resamplings being F.interpolate(mode="bicubic", antialias=True, align_corners=False) on a (1, n) image: the identity
-along the height axis and a fixed banded linear map along the width.  The tables below are those maps.
+along the height axis and a fixed banded linear map along the width.  The tables below are those maps.  In 2-D
+(reference models/CNO2d.py:31-46) the resampling of a plane is the tensor product of two of them, one per axis.
 """
 from __future__ import annotations
 
@@ -184,13 +186,74 @@ def cno_act1d(x: torch.Tensor, in_size: int, out_size: int, scale: Optional[torc
     return _CnoAct1d.apply(x, scale, shift, 2 * int(in_size), int(out_size), float(slope))
 
 
+def _bands(t: CnoBand):
+    return t.span.data_ptr(), ptr(t.weights), t.taps
+
+
+class _CnoAct2d(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, scale, shift, n_mid: int, n_out: int, slope: float):
+        lib = load()
+        x = _f32c(x)
+        B, Cc, h_in, w_in = x.shape
+        if scale is not None:
+            scale, shift = _f32c(scale.detach()), _f32c(shift.detach())
+        dev = x.device
+        Uy, Ux, D = cno_tables(dev, h_in, n_mid), cno_tables(dev, w_in, n_mid), cno_tables(dev, n_mid, n_out)
+        out = torch.empty(B, Cc, n_out, n_out, dtype=torch.float32, device=dev)
+        check(lib.rpde_cno_act2d_fwd(ptr(x), ptr(scale), ptr(shift), ptr(out), B, Cc, h_in, w_in, n_mid, n_mid, n_out, n_out,
+                                     slope, *_bands(Uy.fwd), *_bands(Ux.fwd), *_bands(D.fwd), *_bands(D.fwd), stream_ptr()),
+              "cno_act2d_fwd")
+        ctx.save_for_backward(x, scale, shift)
+        ctx.meta = (n_mid, n_out, slope)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = load()
+        x, scale, shift = ctx.saved_tensors
+        n_mid, n_out, slope = ctx.meta
+        B, Cc, h_in, w_in = x.shape
+        g = _f32c(g)
+        dev = x.device
+        Uy, Ux, D = cno_tables(dev, h_in, n_mid), cno_tables(dev, w_in, n_mid), cno_tables(dev, n_mid, n_out)
+        gy = torch.empty_like(x)
+        check(lib.rpde_cno_act2d_bwd(ptr(x), ptr(scale), ptr(shift), ptr(g), ptr(gy), B, Cc, h_in, w_in, n_mid, n_mid, n_out,
+                                     n_out, slope, *_bands(Uy.fwd), *_bands(Ux.fwd), *_bands(Uy.bwd), *_bands(Ux.bwd),
+                                     *_bands(D.bwd), *_bands(D.bwd), stream_ptr()), "cno_act2d_bwd")
+        return gy, None, None, None, None, None
+
+
+def cno_act2d(x: torch.Tensor, in_size: int, out_size: int, scale: Optional[torch.Tensor] = None,
+              shift: Optional[torch.Tensor] = None, slope: float = LEAKY_SLOPE) -> torch.Tensor:
+    """CNO_LReLu(in_size, out_size) on x [B, C, H, W] in one kernel: resample the plane to (2 in_size)^2, LeakyReLU,
+    resample to out_size^2, whatever (H, W) is; the (2 in_size)^2 plane never reaches memory.  scale / shift [C] and the
+    gradient as in cno_act1d."""
+    if x.dim() != 4:
+        raise ValueError(f"cno_act2d: expected [B, C, H, W], got {tuple(x.shape)}")
+    if (scale is None) != (shift is None):
+        raise ValueError("cno_act2d: scale and shift come together")
+    return _CnoAct2d.apply(x, scale, shift, 2 * int(in_size), int(out_size), float(slope))
+
+
 # ----------------------------------------------------------------------------
-# Conv1d(k = 3, padding = 1), BatchNorm1d and the skip add of a CNO block (the CNO group of include/rpde.h)
+# Conv1d / Conv2d (k = 3, padding = 1), BatchNorm and the skip add of a CNO block (the CNO groups of include/rpde.h)
 # ----------------------------------------------------------------------------
 def _bcn(x: torch.Tensor, what: str):
     if x.dim() != 3:
         raise ValueError(f"{what}: expected [B, C, n], got {tuple(x.shape)}")
     return int(x.shape[0]), int(x.shape[1]), int(x.shape[2])
+
+
+def _bchw(x: torch.Tensor, what: str):
+    if x.dim() != 4:
+        raise ValueError(f"{what}: expected [B, C, H, W], got {tuple(x.shape)}")
+    return tuple(int(v) for v in x.shape)
+
+
+def _points(x: torch.Tensor) -> int:
+    """values per (sample, channel): n of [B, C, n], H W of [B, C, H, W] -- what the per-channel kernels run over"""
+    return int(x.shape[2]) if x.dim() == 3 else int(x.shape[2]) * int(x.shape[3])
 
 
 class _Conv1dK3(torch.autograd.Function):
@@ -235,9 +298,53 @@ def conv1d_k3(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor
     return _Conv1dK3.apply(x, weight, bias)
 
 
+class _Conv2dK3(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, b):
+        lib = load()
+        x = _f32c(x)
+        B, Cin, H, W = x.shape
+        Cout = w.shape[0]
+        wt = _f32c(w.detach()).permute(2, 3, 0, 1).reshape(9, Cout, Cin).contiguous()    # tap-major: a layout copy
+        bias = None if b is None else _f32c(b.detach())
+        out = torch.empty(B, Cout, H, W, dtype=torch.float32, device=x.device)
+        check(lib.rpde_cno_conv2d_k3_fwd(ptr(x), ptr(wt), ptr(bias), ptr(out), B, Cin, Cout, H, W, stream_ptr()), "cno_conv2d_k3_fwd")
+        ctx.save_for_backward(x, wt)
+        ctx.has_bias = b is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = load()
+        x, wt = ctx.saved_tensors
+        B, Cin, H, W = x.shape
+        Cout = wt.shape[1]
+        g = _f32c(g)
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(x)
+            check(lib.rpde_cno_conv2d_k3_bwd_data(ptr(g), ptr(wt), ptr(gx), B, Cin, Cout, H, W, stream_ptr()), "cno_conv2d_k3_bwd_data")
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            gw = torch.empty(Cout, Cin, 3, 3, dtype=torch.float32, device=x.device)
+            gb = torch.empty(Cout, dtype=torch.float32, device=x.device) if ctx.has_bias else None
+            slices = lib.rpde_cno_conv2d_k3_bwd_weight_slices(B, Cin, Cout, H, W)      # > 1: partial sums per slice
+            part = torch.empty(slices, 9 * Cout * Cin + Cout, dtype=torch.float32, device=x.device) if slices > 1 else None
+            check(lib.rpde_cno_conv2d_k3_bwd_weight(ptr(x), ptr(g), ptr(gw), ptr(gb), B, Cin, Cout, H, W, ptr(part), slices,
+                                                    stream_ptr()), "cno_conv2d_k3_bwd_weight")
+        return gx, gw, gb
+
+
+def conv2d_k3(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """nn.Conv2d(kernel_size=3, padding=1) on x [B, Cin, H, W] with weight [Cout, Cin, 3, 3]"""
+    Cin = _bchw(x, "conv2d_k3")[1]
+    if weight.dim() != 4 or weight.shape[1] != Cin or tuple(weight.shape[2:]) != (3, 3):
+        raise ValueError(f"conv2d_k3: weight {tuple(weight.shape)} does not fit {Cin} input channels and 3 x 3 taps")
+    return _Conv2dK3.apply(x, weight, bias)
+
+
 def _moments(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """[C, 4] float64: (sum a, sum b, sum a b, sum b^2) per channel"""
-    B, Cc, n = a.shape
+    B, Cc, n = a.shape[0], a.shape[1], _points(a)
     sums = torch.empty(Cc, 4, dtype=torch.float64, device=a.device)
     check(load().rpde_cno_moments(ptr(a), ptr(b), sums.data_ptr(), B, Cc, n, stream_ptr()), "cno_moments")
     return sums
@@ -245,7 +352,7 @@ def _moments(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
 
 def _affine(a, b, p0, p1, p2, residual=None) -> torch.Tensor:
     """p0 a + p1 b + p2 (+ residual), coefficients [C] taken in float64"""
-    B, Cc, n = a.shape
+    B, Cc, n = a.shape[0], a.shape[1], _points(a)
     out = torch.empty_like(a)
     p0, p1, p2 = (None if p is None else p.to(torch.float64).contiguous() for p in (p0, p1, p2))
     check(load().rpde_cno_affine(ptr(a), ptr(b), p0.data_ptr(), None if p1 is None else p1.data_ptr(), p2.data_ptr(),
@@ -253,10 +360,11 @@ def _affine(a, b, p0, p1, p2, residual=None) -> torch.Tensor:
     return out
 
 
-class _BatchNorm1d(torch.autograd.Function):
-    """BatchNorm1d on z [B, C, n], followed by the CNO activation (act = (n_mid, n_out, slope): the normalised tensor is
-    never written, its apply step is the activation kernel's prologue) or by an optional skip add.  The per-channel
-    coefficients -- C numbers each -- are formed in float64 by torch from the moments kernel's sums."""
+class _BatchNorm(torch.autograd.Function):
+    """BatchNorm on z [B, C, n] or [B, C, H, W] (the moments and affine kernels see the plane as n = H W points),
+    followed by the CNO activation of z's rank (act = (n_mid, n_out, slope): the normalised tensor is never written, its
+    apply step is the activation kernel's prologue) or by an optional skip add.  The per-channel coefficients -- C
+    numbers each -- are formed in float64 by torch from the moments kernel's sums."""
 
     @staticmethod
     def forward(ctx, z, gamma, beta, mean, invstd, residual, act, batch_stats: bool):
@@ -265,8 +373,9 @@ class _BatchNorm1d(torch.autograd.Function):
         scale64 = g64 * invstd
         shift64 = beta.detach().double() - mean * scale64
         scale, shift = scale64.float(), shift64.float()
+        ctx.act_fn = _CnoAct1d if z.dim() == 3 else _CnoAct2d
         if act is not None:
-            out = _CnoAct1d.forward(ctx, z, scale, shift, *act)          # saves (z, scale, shift) and meta on ctx
+            out = ctx.act_fn.forward(ctx, z, scale, shift, *act)         # saves (z, scale, shift) and meta on ctx
         else:
             out = _affine(z, None, scale64, None, shift64, None if residual is None else _f32c(residual))
             ctx.save_for_backward(z, scale, shift)
@@ -281,9 +390,8 @@ class _BatchNorm1d(torch.autograd.Function):
         z, scale, shift = ctx.saved_tensors
         g64, mean, invstd, scale64 = ctx.stats
         g = _f32c(g)
-        gy = _CnoAct1d.backward(ctx, g)[0] if ctx.act is not None else g
-        B, Cc, n = z.shape
-        N = float(B * n)
+        gy = ctx.act_fn.backward(ctx, g)[0] if ctx.act is not None else g
+        N = float(z.shape[0] * _points(z))
         s = _moments(gy, z)
         sum_gy, sum_gyz = s[:, 0], s[:, 2]
         dbeta = sum_gy
@@ -307,9 +415,27 @@ def batchnorm1d(z: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, runni
     (unbiased running variance, num_batches_tracked + 1) in training mode, the running statistics in eval mode, a
     ValueError for training on one value per channel.  residual: added to the result (the residual block's skip).
     act = (in_size, out_size): CNO_LReLu(in_size, out_size) applied to the result in the same kernel."""
-    B, Cc, n = _bcn(z, "batchnorm1d")
+    _bcn(z, "batchnorm1d")
+    return _batchnorm("batchnorm1d", z, weight, bias, running_mean, running_var, num_batches_tracked, training, momentum, eps,
+                      residual, act, slope)
+
+
+def batchnorm2d(z: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, running_mean: Optional[torch.Tensor],
+                running_var: Optional[torch.Tensor], num_batches_tracked: Optional[torch.Tensor] = None,
+                training: bool = True, momentum: float = 0.1, eps: float = 1e-5, residual: Optional[torch.Tensor] = None,
+                act: Optional[Tuple[int, int]] = None, slope: float = LEAKY_SLOPE) -> torch.Tensor:
+    """nn.BatchNorm2d's forward on z [B, C, H, W]: torch's semantics exactly as batchnorm1d states them, the statistics
+    taken over (B, H, W).  act = (in_size, out_size): the 2-D CNO_LReLu(in_size, out_size) in the same kernel."""
+    _bchw(z, "batchnorm2d")
+    return _batchnorm("batchnorm2d", z, weight, bias, running_mean, running_var, num_batches_tracked, training, momentum, eps,
+                      residual, act, slope)
+
+
+def _batchnorm(what, z, weight, bias, running_mean, running_var, num_batches_tracked, training, momentum, eps, residual, act,
+               slope):
+    B, n = int(z.shape[0]), _points(z)
     if residual is not None and act is not None:
-        raise ValueError("batchnorm1d: residual and act exclude each other")
+        raise ValueError(f"{what}: residual and act exclude each other")
     use_batch = training or running_mean is None
     if use_batch:
         if B * n <= 1:
@@ -329,7 +455,7 @@ def batchnorm1d(z: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, runni
         mean, var = running_mean.detach().double(), running_var.detach().double()
     invstd = torch.rsqrt(var + eps)
     fn_act = None if act is None else (2 * int(act[0]), int(act[1]), float(slope))
-    return _BatchNorm1d.apply(z, weight, bias, mean, invstd, residual, fn_act, use_batch)
+    return _BatchNorm.apply(z, weight, bias, mean, invstd, residual, fn_act, use_batch)
 
 
 class _SkipAdd(torch.autograd.Function):
@@ -345,6 +471,7 @@ class _SkipAdd(torch.autograd.Function):
 
 
 def skip_add(a: torch.Tensor, residual: torch.Tensor) -> torch.Tensor:
-    """a + residual on [B, C, n] (a residual block without BatchNorm)"""
-    _bcn(a, "skip_add")
+    """a + residual on [B, C, n] or [B, C, H, W] (a residual block without BatchNorm)"""
+    if a.dim() not in (3, 4):
+        raise ValueError(f"skip_add: expected [B, C, n] or [B, C, H, W], got {tuple(a.shape)}")
     return _SkipAdd.apply(a, residual)

@@ -34,13 +34,20 @@ def _init_distributed():
     return world, rank, local
 
 
+def _cno_name(args):
+    """CNO1d / CNO2d when the model is one of them, else None"""
+    target = str(args.model["_target_"])
+    return next((name for name in ("CNO1d", "CNO2d") if target.endswith(name)), None)
+
+
 def build_model(args):
-    """instantiate(args.model); a CNO1d is built for size = dataset.cno_train_size, the resolution it is trained at
-    (reference main_1d.py:100-104): its levels are sized from it"""
-    if str(args.model["_target_"]).endswith("CNO1d"):
+    """instantiate(args.model); a CNO1d / CNO2d is built for size = dataset.cno_train_size, the resolution it is trained
+    at (reference main_1d.py:100-104, main_2d.py:119-124): its levels are sized from it"""
+    cno = _cno_name(args)
+    if cno is not None:
         size = args.dataset.get("cno_train_size")
         if size is None:
-            raise SystemExit("model CNO1d: the dataset config has no `cno_train_size` (the training resolution, "
+            raise SystemExit(f"model {cno}: the dataset config has no `cno_train_size` (the training resolution, "
                              "which the model's `size` is set to)")
         return instantiate(args.model, size=int(size))
     return instantiate(args.model)
@@ -48,12 +55,13 @@ def build_model(args):
 
 def _model_resolution(args):
     """the resolution the all-resolution sweep resizes to before the model and back after it: CNO's evaluation
-    (reference utils/resize_utils.py:527-539); None for the models that run at the test resolution"""
-    return int(args.dataset["cno_train_size"]) if str(args.model["_target_"]).endswith("CNO1d") else None
+    (reference utils/resize_utils.py:527-539 in 1-D, :218-230 in 2-D); None for the models that run at the test
+    resolution"""
+    return int(args.dataset["cno_train_size"]) if _cno_name(args) is not None else None
 
 
 def _at_own_resolution(args, model):
-    """the model as the rollout and the error-by-frequency sweep call it at every resolution: itself, or a CNO1d behind
+    """the model as the rollout and the error-by-frequency sweep call it at every resolution: itself, or a CNO behind
     utils.resize_utils.AtResolution (resized in and out)"""
     from utils.resize_utils import AtResolution
     res = _model_resolution(args)

@@ -1989,8 +1989,8 @@ def darcy2d_residual(pred, a, tables, affine=None, size_average: bool = True, re
 # ----------------------------------------------------------------------------
 # CNO: resampling tables and the fused alias-free activation (rpde/cno.py)
 # ----------------------------------------------------------------------------
-from .cno import (CnoBand, CnoTables, batchnorm1d, cno_act1d, cno_dense, cno_resample_table,  # noqa: E402,F401
-                  cno_tables, cno_transpose_band, conv1d_k3, skip_add)
+from .cno import (CnoBand, CnoTables, batchnorm1d, batchnorm2d, cno_act1d, cno_act2d, cno_dense,  # noqa: E402,F401
+                  cno_resample_table, cno_tables, cno_transpose_band, conv1d_k3, conv2d_k3, skip_add)
 
 
 def warm_plans(model, resolutions, dims: int, in_channels: int = 1, device="cuda") -> None:

@@ -39,9 +39,10 @@ def to_resolution(fields: torch.Tensor, target: int, how: str = "naive_downsampl
 
 
 class AtResolution(torch.nn.Module):
-    """`model` run at `resolution` whatever it is fed (1-D): a field of another length is spectrally resized to it and
-    the prediction resized back -- how a CNO1d, whose levels are sized for one resolution, joins a rollout or a sweep
-    at the others (reference utils/resize_utils.py:527-539)"""
+    """`model` run at `resolution` whatever it is fed: a field [B, C, n] of another length, or [B, C, M, N] of another
+    size, is spectrally resized to it (to resolution x resolution in 2-D) and the prediction resized back -- how a
+    CNO1d / CNO2d, whose levels are sized for one resolution, joins a rollout or a sweep at the others (reference
+    utils/resize_utils.py:527-539 and :218-230)"""
 
     def __init__(self, model, resolution: int):
         super().__init__()
@@ -49,6 +50,11 @@ class AtResolution(torch.nn.Module):
 
     def forward(self, x):
         n = x.shape[-1]
+        if x.dim() == 4:
+            m = x.shape[-2]
+            if (m, n) == (self.resolution, self.resolution):
+                return self.model(x)
+            return resize(self.model(resize(x, (self.resolution, self.resolution))), (m, n))
         if n == self.resolution:
             return self.model(x)
         return resize_1d(self.model(resize_1d(x, self.resolution)), n)
@@ -60,9 +66,9 @@ def evaluate_all_resolutions(model, test_x: torch.Tensor, test_y: torch.Tensor, 
                              x_encode: Optional[Callable] = None, y_decode: Optional[Callable] = None,
                              device="cuda", model_resolution: Optional[int] = None) -> Dict[int, float]:
     """{resolution: mean relative L2 over the test samples}; encode/decode are the x / y normalisers.
-    model_resolution (1-D): the model runs at that resolution whatever the test resolution -- inputs are spectrally
-    resized to it and predictions resized back (the reference's CNO evaluation, utils/resize_utils.py:527-539); a
-    field already at that resolution is passed as it is.  With
+    model_resolution: the model runs at that resolution whatever the test resolution -- inputs are spectrally
+    resized to it and predictions resized back (the reference's CNO evaluation, utils/resize_utils.py:527-539 in 1-D,
+    :218-230 in 2-D); a field already at that resolution is passed as it is.  With
     torch.distributed initialised every rank evaluates samples rank, rank + world, ... and the sample-weighted sums
     are reduced (NaN for a resolution without samples)."""
     import torch.distributed as dist
