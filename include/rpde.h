@@ -826,13 +826,15 @@ int rpde_cno_act1d_bwd(const float* x, const float* scale, const float* shift, c
                        const int32_t* ut_span, const float* ut_w, int ut_taps, const int32_t* dt_span, const float* dt_w,
                        int dt_taps, void* stream);
 
-/* ---- CNO: the rest of a block (reference models/CNO1d.py:51-164: Conv1d(k=3, padding=1) -> BatchNorm1d -> CNO_LReLu,
- * and the residual block's second BatchNorm plus skip add).  Channels first, contiguous [B, C, n].
+/* ---- CNO: the rest of a block (csrc/cno_layers.hip, both ranks; reference models/CNO1d.py:51-164: Conv1d(k=3,
+ * padding=1) -> BatchNorm1d -> CNO_LReLu, and the residual block's second BatchNorm plus skip add).  Channels first,
+ * contiguous [B, C, n].
  * conv1d_k3: the three taps as accumulating rpde_gemm_f32 products on shifted views -- the centre tap over the whole
- *   range with the bias, tap 0 onto [1, n), tap 2 onto [0, n - 1) (n = 1: the centre tap alone).  wt is the weight
+ *   range with the bias, tap 0 onto [1, n), tap 2 onto [0, n - 1) (n = 1: the centre tap alone): conv2d_k3's tap loop
+ *   on a plane of one row with one row of taps.  wt is the weight
  *   repacked tap-major, [3][Cout][Cin].  _bwd_data: gx from g with the transposed taps and mirrored shifts.
  *   _bwd_weight: gw [Cout][Cin][3] (torch's layout) and gb [Cout] (or null) by one deterministic reduction over
- *   (batch, x), fp32, fixed order, no atomics.
+ *   (batch, x), fp32, fixed order, no atomics: conv2d_k3's kernel with one row of taps, always in one slice.
  * moments: sums [C][4] doubles = (sum a, sum b, sum a b, sum b^2) per channel over (batch, x).  BatchNorm's forward
  *   reads mean and variance of z from (z, z); its backward reads sum gy and sum gy z from (gy, z).
  * affine: out = p0[c] a + p1[c] b + p2[c] (+ residual); b and p1 both null: no b term.  A BatchNorm's apply step (with the
@@ -877,8 +879,8 @@ int rpde_cno_act2d_bwd(const float* x, const float* scale, const float* shift, c
                        int uxt_taps, const int32_t* dyt_span, const float* dyt_w, int dyt_taps, const int32_t* dxt_span,
                        const float* dxt_w, int dxt_taps, void* stream);
 
-/* conv2d_k3: Conv2d(k = 3, padding = 1) on [B, C, H, W] as nine accumulating rpde_gemm_f32 products on shifted views --
- *   the centre tap over the flat H W axis with the bias, the two dx = 0 taps flat over (H - 1) W points, the six dx != 0
+/* conv2d_k3 (csrc/cno_layers.hip): Conv2d(k = 3, padding = 1) on [B, C, H, W] as nine accumulating rpde_gemm_f32 products
+ *   on shifted views -- the centre tap over the flat H W axis with the bias, the two dx = 0 taps flat over (H - 1) W points, the six dx != 0
  *   taps row by row through the descriptor's two-level batch so that no row wraps; taps without a valid range (H = 1 or
  *   W = 1) are skipped.  wt is the weight repacked tap-major, [9][Cout][Cin], tap = 3 ty + tx.  _bwd_data: gx from g with
  *   the transposed taps and mirrored shifts.

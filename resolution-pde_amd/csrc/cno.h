@@ -1,10 +1,11 @@
 // What the 1-D and 2-D CNO activation kernels (cno.hip, cno2d.hip) share: the banded table as the device sees it, the
 // dot product over one of its rows, the range a run of rows reads, the host's bounds on those ranges from the filter's
-// support, and the argument checks of the entry points.
+// support, the argument checks of the entry points and the choice of a kernel's 16-byte variants.
 #pragma once
 #include "rpde_internal.h"
 
 #include <cmath>
+#include <type_traits>
 
 namespace rpde {
 
@@ -65,12 +66,24 @@ inline int cno_check(const char* what, const void* x, const void* scale, const v
   return RPDE_OK;
 }
 
-inline int cno_band(const char* what, const char* name, const void* span, const float* w, int taps) {
+// the checks of one table an entry point was handed, and the band the device sees
+inline int cno_band(const char* what, const char* name, const int32_t* span, const float* w, int taps, CnoBand& band) {
   RPDE_CHECK_ARG(span && w, "%s: null %s table", what, name);
   RPDE_CHECK_ARG(taps >= 4 && taps % 4 == 0 && al16(w) && (reinterpret_cast<uintptr_t>(span) & 7) == 0,
                  "%s: %s table: taps %d must be a positive multiple of 4, weights 16-byte and spans 8-byte aligned", what,
                  name, taps);
+  band = CnoBand{reinterpret_cast<const int2*>(span), w, taps};
   return RPDE_OK;
+}
+
+// launch(VX, VO) with the two run-time flags as compile-time constants (std::true_type / std::false_type): the
+// activation kernels are templates on whether the n_in-long and the n_out-long tensors take 16-byte accesses
+template <class Launch>
+inline void cno_vec_dispatch(bool vx, bool vo, const Launch& launch) {
+  if (vx && vo) launch(std::true_type{}, std::true_type{});
+  else if (vx) launch(std::true_type{}, std::false_type{});
+  else if (vo) launch(std::false_type{}, std::true_type{});
+  else launch(std::false_type{}, std::false_type{});
 }
 
 }  // namespace rpde

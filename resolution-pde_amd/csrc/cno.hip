@@ -2,10 +2,8 @@
 // n_mid points, LeakyReLU, antialiased bicubic resampling to n_out points.  Both resamplings are fixed banded linear
 // maps (rpde/cno.py builds their tables from torch's rule), so a workgroup stages a row segment with its halo in LDS,
 // forms the mid signal there, and writes only the result: x is read once and out written once.
-// Below it, the rest of a CNO block: Conv1d(k = 3) as three shifted GEMMs with its own weight-gradient kernel, and the
-// two kernels of BatchNorm1d (per-channel moments, per-channel affine combine).  gfx950 (CDNA4, wave64) only.
+// The rest of a CNO block -- Conv(k = 3), BatchNorm -- is in cno_layers.hip.  gfx950 (CDNA4, wave64) only.
 #include "cno.h"
-#include "wave.h"
 
 #include <algorithm>
 
@@ -174,224 +172,20 @@ static bool cno_plan(CnoShape& s, int n_w, const Spans& spans) {
   return false;
 }
 
-// ---- Conv1d(k = 3, padding = 1): weight and bias gradient ---------------------------------------------------------
-// gw[co][ci][t] = sum_{b,x} g[b][co][x] * x[b][ci][x + t - 1],  gb[co] = sum_{b,x} g[b][co][x].  One workgroup per
-// 4 x 4 tile of (co, ci): every thread walks the (b, x) points tid, tid + 256, ... with 48 + 4 accumulators, then the
-// workgroup adds them up in a fixed order (DPP sum inside a wave, the four waves in sequence): no atomics
-constexpr int CNO_WG = 4;
-__global__ void __launch_bounds__(256)
-k_cno_conv_wgrad(const float* __restrict__ x, const float* __restrict__ g, float* __restrict__ gw, float* __restrict__ gb,
-                 int B, int Cin, int Cout, int n) {
-  __shared__ float red[4][CNO_WG * CNO_WG * 3 + CNO_WG];
-  const int ci0 = blockIdx.x * CNO_WG, co0 = blockIdx.y * CNO_WG;
-  float acc[CNO_WG][CNO_WG][3], accb[CNO_WG];
-#pragma unroll
-  for (int j = 0; j < CNO_WG; ++j) {
-    accb[j] = 0.f;
-#pragma unroll
-    for (int i = 0; i < CNO_WG; ++i) acc[j][i][0] = acc[j][i][1] = acc[j][i][2] = 0.f;
-  }
-  const long total = (long)B * n;
-  for (long p = threadIdx.x; p < total; p += 256) {
-    const long b = p / n;
-    const int xx = (int)(p - b * n);
-    float gv[CNO_WG], xv[CNO_WG][3];
-#pragma unroll
-    for (int j = 0; j < CNO_WG; ++j) gv[j] = co0 + j < Cout ? g[(b * Cout + co0 + j) * n + xx] : 0.f;
-#pragma unroll
-    for (int i = 0; i < CNO_WG; ++i) {
-      const bool live = ci0 + i < Cin;
-      const float* row = x + (b * Cin + (live ? ci0 + i : 0)) * n;
-      xv[i][0] = live && xx > 0 ? row[xx - 1] : 0.f;
-      xv[i][1] = live ? row[xx] : 0.f;
-      xv[i][2] = live && xx + 1 < n ? row[xx + 1] : 0.f;
-    }
-#pragma unroll
-    for (int j = 0; j < CNO_WG; ++j) {
-      accb[j] += gv[j];
-#pragma unroll
-      for (int i = 0; i < CNO_WG; ++i)
-#pragma unroll
-        for (int t = 0; t < 3; ++t) acc[j][i][t] = fmaf(gv[j], xv[i][t], acc[j][i][t]);
-    }
-  }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int j = 0; j < CNO_WG; ++j) {
-#pragma unroll
-    for (int i = 0; i < CNO_WG; ++i)
-#pragma unroll
-      for (int t = 0; t < 3; ++t) {
-        const float v = wave_sum_dpp(acc[j][i][t]);
-        if (lane == 0) red[wave][(j * CNO_WG + i) * 3 + t] = v;
-      }
-    const float v = wave_sum_dpp(accb[j]);
-    if (lane == 0) red[wave][CNO_WG * CNO_WG * 3 + j] = v;
-  }
-  __syncthreads();
-  const int k = threadIdx.x;
-  if (k < CNO_WG * CNO_WG * 3 + CNO_WG) {
-    const float v = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
-    if (k < CNO_WG * CNO_WG * 3) {
-      const int j = k / (CNO_WG * 3), i = (k / 3) % CNO_WG, t = k % 3;
-      if (co0 + j < Cout && ci0 + i < Cin) gw[((long)(co0 + j) * Cin + ci0 + i) * 3 + t] = v;
-    } else if (gb && blockIdx.x == 0 && co0 + (k - CNO_WG * CNO_WG * 3) < Cout) {
-      gb[co0 + k - CNO_WG * CNO_WG * 3] = v;
-    }
-  }
-}
-
-// ---- BatchNorm1d pieces -------------------------------------------------------------------------------------------
-// sums[c] = (sum a, sum b, sum a b, sum b^2) over (batch, x) of channel c of two [B, C, n] tensors, in double; one
-// workgroup per channel, fixed order.  The forward takes mean and variance of z from (z, z), the backward sum gy and
-// sum gy z from (gy, z)
-__global__ void __launch_bounds__(256)
-k_cno_moments(const float* __restrict__ a, const float* __restrict__ b, double* __restrict__ sums, int B, int C, int n) {
-  __shared__ double red[4][4];
-  const int c = blockIdx.x;
-  double s[4] = {0.0, 0.0, 0.0, 0.0};
-  const long total = (long)B * n;
-  for (long p = threadIdx.x; p < total; p += 256) {
-    const long bb = p / n;
-    const long at = (bb * C + c) * n + (p - bb * n);
-    const double va = a[at], vb = b[at];
-    s[0] += va; s[1] += vb; s[2] += va * vb; s[3] += vb * vb;
-  }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const double v = wave_sum(s[k]);
-    if (lane == 0) red[wave][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    const int k = threadIdx.x;
-    sums[c * 4 + k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
-  }
-}
-
-// out = p0[c] a + p1[c] b + p2[c] (+ residual): a BatchNorm's apply step (p1 null: no b term), its backward
-// dz = p0 gy + p1 z + p2, and the residual block's skip add.  The coefficients are doubles and so is the arithmetic,
-// rounded once: with few values per channel the backward's three terms cancel to eps / (var + eps) of their size, and
-// fp32 coefficients would leave nothing of the result; the kernel stays bound by its bytes
-template <bool VEC>
-__global__ void __launch_bounds__(256)
-k_cno_affine(const float* __restrict__ a, const float* __restrict__ b, const double* __restrict__ p0,
-             const double* __restrict__ p1, const double* __restrict__ p2, const float* __restrict__ res,
-             float* __restrict__ out, long total, int C, int n) {
-  constexpr int W = VEC ? 4 : 1;
-  const long i = ((long)blockIdx.x * 256 + threadIdx.x) * W;
-  if (i >= total) return;
-  const int c = (int)((i / n) % C);
-  const double k0 = p0[c], k1 = p1 ? p1[c] : 0.0, k2 = p2[c];
-  alignas(16) float va[W], vb[W], vr[W], o[W];
-  if (VEC) {
-    *reinterpret_cast<float4*>(va) = *reinterpret_cast<const float4*>(a + i);
-    if (p1) *reinterpret_cast<float4*>(vb) = *reinterpret_cast<const float4*>(b + i);
-    if (res) *reinterpret_cast<float4*>(vr) = *reinterpret_cast<const float4*>(res + i);
-  } else {
-    va[0] = a[i];
-    if (p1) vb[0] = b[i];
-    if (res) vr[0] = res[i];
-  }
-#pragma unroll
-  for (int k = 0; k < W; ++k) {
-    double v = fma(k0, (double)va[k], k2);
-    if (p1) v = fma(k1, (double)vb[k], v);
-    if (res) v += (double)vr[k];
-    o[k] = (float)v;
-  }
-  if (VEC) *reinterpret_cast<float4*>(out + i) = *reinterpret_cast<float4*>(o);
-  else out[i] = o[0];
-}
-
 }  // namespace rpde
 
 using namespace rpde;
 
 extern "C" {
 
-// the three taps of Conv1d(k = 3, padding = 1) as accumulating GEMMs on shifted views: the centre
-// tap over the whole range (it carries the bias and initialises C), then tap 0 onto [1, n) and tap 2 onto [0, n - 1).
-// transposed: the data gradient, the same three products with W_t^T and the shifts mirrored
-static int cno_conv_taps(const float* src, const float* wt, const float* bias, float* dst, int B, int Csrc, int Cdst, int n,
-                         bool transposed, hipStream_t st) {
-  const int Cin = transposed ? Cdst : Csrc, Cout = transposed ? Csrc : Cdst;
-  for (int pass = 0; pass < 3; ++pass) {
-    const int t = pass == 0 ? 1 : (pass == 1 ? 0 : 2);          // tap of this pass
-    if (t != 1 && n < 2) break;
-    rpde_gemm_desc d = gemm_desc();
-    d.A = wt + (long)t * Cout * Cin; d.a_kmajor = transposed ? 0 : 1; d.lda = Cin;
-    d.b_kmajor = 0; d.ldb = n; d.ldc = n;
-    d.M = Cdst; d.K = Csrc; d.N = t == 1 ? n : n - 1;
-    d.batch = B; d.sB1 = (long)Csrc * n; d.sC1 = (long)Cdst * n;
-    // forward: out[x] += W_t in[x + t - 1]; data gradient: gx[x] += W_t^T g[x - (t - 1)]
-    const int read_first = (t == 1) ? 0 : ((t == 0) != transposed ? 0 : 1);
-    const int write_first = (t == 1) ? 0 : 1 - read_first;
-    d.B = src + read_first; d.C = dst + write_first;
-    d.accumulate = pass > 0;
-    if (pass == 0 && bias) { d.bias = bias; d.bias_mode = 2; }
-    RPDE_TRY(launch_gemm(d, st));
-  }
-  return RPDE_OK;
-}
-
-int rpde_cno_conv1d_k3_fwd(const float* x, const float* wt, const float* bias, float* out, int B, int Cin, int Cout, int n,
-                           void* stream) {
-  RPDE_CHECK_ARG(x && wt && out, "cno_conv1d_k3_fwd: null tensor");
-  RPDE_CHECK_ARG(B > 0 && Cin > 0 && Cout > 0 && n > 0, "cno_conv1d_k3_fwd: bad sizes B=%d Cin=%d Cout=%d n=%d", B, Cin, Cout, n);
-  return cno_conv_taps(x, wt, bias, out, B, Cin, Cout, n, false, as_stream(stream));
-}
-
-int rpde_cno_conv1d_k3_bwd_data(const float* g, const float* wt, float* gx, int B, int Cin, int Cout, int n, void* stream) {
-  RPDE_CHECK_ARG(g && wt && gx, "cno_conv1d_k3_bwd_data: null tensor");
-  RPDE_CHECK_ARG(B > 0 && Cin > 0 && Cout > 0 && n > 0, "cno_conv1d_k3_bwd_data: bad sizes B=%d Cin=%d Cout=%d n=%d", B, Cin, Cout, n);
-  return cno_conv_taps(g, wt, nullptr, gx, B, Cout, Cin, n, true, as_stream(stream));
-}
-
-int rpde_cno_conv1d_k3_bwd_weight(const float* x, const float* g, float* gw, float* gb, int B, int Cin, int Cout, int n,
-                                  void* stream) {
-  RPDE_CHECK_ARG(x && g && gw, "cno_conv1d_k3_bwd_weight: null tensor");
-  RPDE_CHECK_ARG(B > 0 && Cin > 0 && Cout > 0 && n > 0, "cno_conv1d_k3_bwd_weight: bad sizes B=%d Cin=%d Cout=%d n=%d", B, Cin, Cout, n);
-  const dim3 grid((unsigned)((Cin + CNO_WG - 1) / CNO_WG), (unsigned)((Cout + CNO_WG - 1) / CNO_WG));
-  RPDE_CHECK_ARG(grid.y <= 65535, "cno_conv1d_k3_bwd_weight: too many output channels (%d)", Cout);
-  hipLaunchKernelGGL(k_cno_conv_wgrad, grid, dim3(256), 0, as_stream(stream), x, g, gw, gb, B, Cin, Cout, n);
-  RPDE_LAUNCH_CHECK();
-  return RPDE_OK;
-}
-
-int rpde_cno_moments(const float* a, const float* b, double* sums, int B, int C, int n, void* stream) {
-  RPDE_CHECK_ARG(a && b && sums, "cno_moments: null tensor");
-  RPDE_CHECK_ARG(B > 0 && C > 0 && n > 0, "cno_moments: bad sizes B=%d C=%d n=%d", B, C, n);
-  RPDE_CHECK_ARG((reinterpret_cast<uintptr_t>(sums) & 7) == 0, "cno_moments: sums must be 8-byte aligned");
-  hipLaunchKernelGGL(k_cno_moments, dim3((unsigned)C), dim3(256), 0, as_stream(stream), a, b, sums, B, C, n);
-  RPDE_LAUNCH_CHECK();
-  return RPDE_OK;
-}
-
-int rpde_cno_affine(const float* a, const float* b, const double* p0, const double* p1, const double* p2, const float* residual,
-                    float* out, int B, int C, int n, void* stream) {
-  RPDE_CHECK_ARG(a && p0 && p2 && out, "cno_affine: null tensor");
-  RPDE_CHECK_ARG((b == nullptr) == (p1 == nullptr), "cno_affine: b and p1 come together");
-  RPDE_CHECK_ARG(B > 0 && C > 0 && n > 0, "cno_affine: bad sizes B=%d C=%d n=%d", B, C, n);
-  const long total = (long)B * C * n;
-  const bool vec = n % 4 == 0 && al16(a) && al16(out) && (!b || al16(b)) && (!residual || al16(residual));
-  const long threads = vec ? total / 4 : total;
-  RPDE_CHECK_ARG((threads + 255) / 256 < (1L << 31), "cno_affine: tensor too large for one launch");
-  const dim3 grid((unsigned)((threads + 255) / 256));
-  if (vec) hipLaunchKernelGGL((k_cno_affine<true>), grid, dim3(256), 0, as_stream(stream), a, b, p0, p1, p2, residual, out, total, C, n);
-  else hipLaunchKernelGGL((k_cno_affine<false>), grid, dim3(256), 0, as_stream(stream), a, b, p0, p1, p2, residual, out, total, C, n);
-  RPDE_LAUNCH_CHECK();
-  return RPDE_OK;
-}
-
 int rpde_cno_act1d_fwd(const float* x, const float* scale, const float* shift, float* out, int B, int C, int n_in, int n_mid,
                        int n_out, float slope, const int32_t* u_span, const float* u_w, int u_taps, const int32_t* d_span,
                        const float* d_w, int d_taps, void* stream) {
   RPDE_TRY(cno_check("cno_act1d_fwd", x, scale, shift, B, C, n_in, n_mid, n_out, slope));
   RPDE_CHECK_ARG(out, "cno_act1d_fwd: null tensor");
-  RPDE_TRY(cno_band("cno_act1d_fwd", "U", u_span, u_w, u_taps));
-  RPDE_TRY(cno_band("cno_act1d_fwd", "D", d_span, d_w, d_taps));
+  CnoBand U, D;
+  RPDE_TRY(cno_band("cno_act1d_fwd", "U", u_span, u_w, u_taps, U));
+  RPDE_TRY(cno_band("cno_act1d_fwd", "D", d_span, d_w, d_taps, D));
   CnoShape s{B * C, C, n_in, n_mid, n_out, 0, 0, 0, 0, 0, slope};
   const bool fits = cno_plan(s, n_out, [&](int T, int& sm, int& sx, int& sg) {
     sm = cno_sources(T, n_mid, n_out); sx = cno_sources(sm, n_in, n_mid); sg = 0;
@@ -403,12 +197,10 @@ int rpde_cno_act1d_fwd(const float* x, const float* scale, const float* shift, f
   const long groups = ((long)s.rows + s.pack - 1) / s.pack;
   RPDE_CHECK_ARG(groups * s.ntiles < (1L << 31), "cno_act1d_fwd: too many workgroups");
   const dim3 grid((unsigned)(groups * s.ntiles)), block(CNO_THREADS);
-  const CnoBand U{reinterpret_cast<const int2*>(u_span), u_w, u_taps}, D{reinterpret_cast<const int2*>(d_span), d_w, d_taps};
   hipStream_t st = as_stream(stream);
-  if (s.vec_x && s.vec_o) hipLaunchKernelGGL((k_cno_act_fwd<true, true>), grid, block, 0, st, x, scale, shift, out, s, U, D);
-  else if (s.vec_x) hipLaunchKernelGGL((k_cno_act_fwd<true, false>), grid, block, 0, st, x, scale, shift, out, s, U, D);
-  else if (s.vec_o) hipLaunchKernelGGL((k_cno_act_fwd<false, true>), grid, block, 0, st, x, scale, shift, out, s, U, D);
-  else hipLaunchKernelGGL((k_cno_act_fwd<false, false>), grid, block, 0, st, x, scale, shift, out, s, U, D);
+  cno_vec_dispatch(s.vec_x, s.vec_o, [&](auto VX, auto VO) {
+    hipLaunchKernelGGL((k_cno_act_fwd<decltype(VX)::value, decltype(VO)::value>), grid, block, 0, st, x, scale, shift, out, s, U, D);
+  });
   RPDE_LAUNCH_CHECK();
   return RPDE_OK;
 }
@@ -419,9 +211,10 @@ int rpde_cno_act1d_bwd(const float* x, const float* scale, const float* shift, c
                        int dt_taps, void* stream) {
   RPDE_TRY(cno_check("cno_act1d_bwd", x, scale, shift, B, C, n_in, n_mid, n_out, slope));
   RPDE_CHECK_ARG(g && gy, "cno_act1d_bwd: null tensor");
-  RPDE_TRY(cno_band("cno_act1d_bwd", "U", u_span, u_w, u_taps));
-  RPDE_TRY(cno_band("cno_act1d_bwd", "U^T", ut_span, ut_w, ut_taps));
-  RPDE_TRY(cno_band("cno_act1d_bwd", "D^T", dt_span, dt_w, dt_taps));
+  CnoBand U, UT, DT;
+  RPDE_TRY(cno_band("cno_act1d_bwd", "U", u_span, u_w, u_taps, U));
+  RPDE_TRY(cno_band("cno_act1d_bwd", "U^T", ut_span, ut_w, ut_taps, UT));
+  RPDE_TRY(cno_band("cno_act1d_bwd", "D^T", dt_span, dt_w, dt_taps, DT));
   CnoShape s{B * C, C, n_in, n_mid, n_out, 0, 0, 0, 0, 0, slope};
   const bool fits = cno_plan(s, n_in, [&](int T, int& sm, int& sx, int& sg) {
     sm = cno_readers(T, n_in, n_mid); sx = cno_sources(sm, n_in, n_mid); sg = cno_readers(sm, n_mid, n_out);
@@ -433,13 +226,10 @@ int rpde_cno_act1d_bwd(const float* x, const float* scale, const float* shift, c
   const long groups = ((long)s.rows + s.pack - 1) / s.pack;
   RPDE_CHECK_ARG(groups * s.ntiles < (1L << 31), "cno_act1d_bwd: too many workgroups");
   const dim3 grid((unsigned)(groups * s.ntiles)), block(CNO_THREADS);
-  const CnoBand U{reinterpret_cast<const int2*>(u_span), u_w, u_taps}, UT{reinterpret_cast<const int2*>(ut_span), ut_w, ut_taps},
-      DT{reinterpret_cast<const int2*>(dt_span), dt_w, dt_taps};
   hipStream_t st = as_stream(stream);
-  if (s.vec_x && s.vec_o) hipLaunchKernelGGL((k_cno_act_bwd<true, true>), grid, block, 0, st, x, scale, shift, g, gy, s, U, UT, DT);
-  else if (s.vec_x) hipLaunchKernelGGL((k_cno_act_bwd<true, false>), grid, block, 0, st, x, scale, shift, g, gy, s, U, UT, DT);
-  else if (s.vec_o) hipLaunchKernelGGL((k_cno_act_bwd<false, true>), grid, block, 0, st, x, scale, shift, g, gy, s, U, UT, DT);
-  else hipLaunchKernelGGL((k_cno_act_bwd<false, false>), grid, block, 0, st, x, scale, shift, g, gy, s, U, UT, DT);
+  cno_vec_dispatch(s.vec_x, s.vec_o, [&](auto VX, auto VO) {
+    hipLaunchKernelGGL((k_cno_act_bwd<decltype(VX)::value, decltype(VO)::value>), grid, block, 0, st, x, scale, shift, g, gy, s, U, UT, DT);
+  });
   RPDE_LAUNCH_CHECK();
   return RPDE_OK;
 }

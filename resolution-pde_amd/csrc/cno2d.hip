@@ -2,10 +2,9 @@
 // resampling of a plane to h_mid x w_mid, LeakyReLU, antialiased bicubic resampling to h_out x w_out.  The 2-D
 // resampling is the tensor product of the 1-D banded maps of rpde/cno.py, so a workgroup stages a rectangular tile of
 // the plane with its halo in LDS and runs four separable passes LDS to LDS; the four-times-larger mid plane never
-// reaches memory.  Below it Conv2d(k = 3, padding = 1): nine shifted GEMMs and a split, deterministic
-// weight-gradient reduction.  gfx950 (CDNA4, wave64) only.
+// reaches memory.  The rest of a CNO block -- Conv(k = 3), BatchNorm -- is in cno_layers.hip.
+// gfx950 (CDNA4, wave64) only.
 #include "cno.h"
-#include "wave.h"
 
 #include <algorithm>
 
@@ -336,113 +335,6 @@ static int c2_shape(const char* what, Cno2Shape& s, bool backward, const void* x
   return RPDE_OK;
 }
 
-static CnoBand c2_band(const int32_t* span, const float* w, int taps) { return CnoBand{reinterpret_cast<const int2*>(span), w, taps}; }
-
-// ---- Conv2d(k = 3, padding = 1): weight and bias gradient ---------------------------------------------------------
-// gw[co][ci][ty][tx] = sum_{b,y,x} g[b][co][y][x] * x[b][ci][y + ty - 1][x + tx - 1],  gb[co] = sum g[b][co][y][x].
-// A workgroup owns a 4 x 4 tile of (co, ci) and one slice of the image rows (b, y): every thread walks the slice's
-// points tid, tid + 256, ... with 144 + 4 accumulators, then the workgroup adds them up in a fixed order (DPP sum inside
-// a wave, the four waves in sequence).  With one slice the sums are the result; with more they are partial sums
-// [slice][Cout Cin 9 + Cout], added slice by slice by k_cno_conv2d_wsum.  No atomics
-constexpr int C2W = 4;
-constexpr int C2W_N = C2W * C2W * 9 + C2W;
-constexpr int C2W_TARGET = 512;       // workgroups wanted: two per CU
-constexpr int C2W_MIN_POINTS = 256;   // a slice holds at least one point per thread
-
-__global__ void __launch_bounds__(256)
-k_cno_conv2d_wgrad(const float* __restrict__ x, const float* __restrict__ g, float* __restrict__ gw, float* __restrict__ gb,
-                   long slice_stride, int BH, int Cin, int Cout, int H, int W, int rows_per_slice) {
-  __shared__ float red[4][C2W_N];
-  const int ci0 = blockIdx.x * C2W, co0 = blockIdx.y * C2W;
-  const int r_lo = blockIdx.z * rows_per_slice, r_hi = min(BH, r_lo + rows_per_slice);
-  float acc[C2W][C2W][9], accb[C2W];
-#pragma unroll
-  for (int j = 0; j < C2W; ++j) {
-    accb[j] = 0.f;
-#pragma unroll
-    for (int i = 0; i < C2W; ++i)
-#pragma unroll
-      for (int t = 0; t < 9; ++t) acc[j][i][t] = 0.f;
-  }
-  const long plane = (long)H * W;
-  const long total = (long)(r_hi - r_lo) * W;
-  for (long p = threadIdx.x; p < total; p += 256) {
-    const int r = r_lo + (int)(p / W), xx = (int)(p % W);
-    const int b = r / H, y = r - b * H;
-    float gv[C2W];
-#pragma unroll
-    for (int j = 0; j < C2W; ++j) {
-      gv[j] = co0 + j < Cout ? g[((long)b * Cout + co0 + j) * plane + (long)y * W + xx] : 0.f;
-      accb[j] += gv[j];
-    }
-#pragma unroll
-    for (int i = 0; i < C2W; ++i) {
-      const bool live = ci0 + i < Cin;
-      const float* img = x + ((long)b * Cin + (live ? ci0 + i : 0)) * plane;
-      float xv[9];
-#pragma unroll
-      for (int ty = 0; ty < 3; ++ty) {
-        const int yy = y + ty - 1;
-        const bool row_ok = live && yy >= 0 && yy < H;
-#pragma unroll
-        for (int tx = 0; tx < 3; ++tx) {
-          const int xs = xx + tx - 1;
-          xv[ty * 3 + tx] = row_ok && xs >= 0 && xs < W ? img[(long)yy * W + xs] : 0.f;
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < C2W; ++j)
-#pragma unroll
-        for (int t = 0; t < 9; ++t) acc[j][i][t] = fmaf(gv[j], xv[t], acc[j][i][t]);
-    }
-  }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int j = 0; j < C2W; ++j) {
-#pragma unroll
-    for (int i = 0; i < C2W; ++i)
-#pragma unroll
-      for (int t = 0; t < 9; ++t) {
-        const float v = wave_sum_dpp(acc[j][i][t]);
-        if (lane == 0) red[wave][(j * C2W + i) * 9 + t] = v;
-      }
-    const float v = wave_sum_dpp(accb[j]);
-    if (lane == 0) red[wave][C2W * C2W * 9 + j] = v;
-  }
-  __syncthreads();
-  const int k = threadIdx.x;
-  if (k < C2W_N) {
-    const float v = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
-    float* gw_s = gw + blockIdx.z * slice_stride;
-    if (k < C2W * C2W * 9) {
-      const int j = k / (C2W * 9), i = (k / 9) % C2W, t = k % 9;
-      if (co0 + j < Cout && ci0 + i < Cin) gw_s[((long)(co0 + j) * Cin + ci0 + i) * 9 + t] = v;
-    } else if (gb && blockIdx.x == 0 && co0 + (k - C2W * C2W * 9) < Cout) {
-      gb[blockIdx.z * slice_stride + co0 + k - C2W * C2W * 9] = v;
-    }
-  }
-}
-
-// gw / gb = the slices' partial sums added in slice order
-__global__ void __launch_bounds__(256)
-k_cno_conv2d_wsum(const float* __restrict__ part, float* __restrict__ gw, float* __restrict__ gb, long n_gw, long n_gb,
-                  int slices) {
-  const long e = (long)blockIdx.x * 256 + threadIdx.x;
-  if (e >= n_gw + n_gb) return;
-  float v = 0.f;
-  for (int s = 0; s < slices; ++s) v += part[s * (n_gw + n_gb) + e];
-  if (e < n_gw) gw[e] = v;
-  else if (gb) gb[e - n_gw] = v;
-}
-
-// slices of the (b, y) rows the weight gradient is split over
-static int c2w_slices(int B, int Cin, int Cout, int H, int W) {
-  const long tiles = (long)((Cin + C2W - 1) / C2W) * ((Cout + C2W - 1) / C2W);
-  const long rows = (long)B * H;
-  long n = std::min<long>(C2W_TARGET / tiles, std::min<long>(rows, rows * W / C2W_MIN_POINTS));
-  return (int)std::max<long>(1, std::min<long>(n, 65535));
-}
-
 }  // namespace rpde
 
 using namespace rpde;
@@ -466,20 +358,18 @@ int rpde_cno_act2d_fwd(const float* x, const float* scale, const float* shift, f
   Cno2Shape s;
   RPDE_TRY(c2_shape(what, s, false, x, scale, shift, B, C, h_in, w_in, h_mid, w_mid, h_out, w_out, slope));
   RPDE_CHECK_ARG(out, "%s: null tensor", what);
-  RPDE_TRY(cno_band(what, "U_y", uy_span, uy_w, uy_taps));
-  RPDE_TRY(cno_band(what, "U_x", ux_span, ux_w, ux_taps));
-  RPDE_TRY(cno_band(what, "D_y", dy_span, dy_w, dy_taps));
-  RPDE_TRY(cno_band(what, "D_x", dx_span, dx_w, dx_taps));
+  CnoBand Uy, Ux, Dy, Dx;
+  RPDE_TRY(cno_band(what, "U_y", uy_span, uy_w, uy_taps, Uy));
+  RPDE_TRY(cno_band(what, "U_x", ux_span, ux_w, ux_taps, Ux));
+  RPDE_TRY(cno_band(what, "D_y", dy_span, dy_w, dy_taps, Dy));
+  RPDE_TRY(cno_band(what, "D_x", dx_span, dx_w, dx_taps, Dx));
   const bool vx = w_in % 4 == 0 && al16(x), vo = w_out % 4 == 0 && al16(out);
   const long groups = ((long)s.planes + s.pack - 1) / s.pack;
   const dim3 grid((unsigned)(groups * s.nty * s.ntx)), block(C2_THREADS);
-  const CnoBand Uy = c2_band(uy_span, uy_w, uy_taps), Ux = c2_band(ux_span, ux_w, ux_taps);
-  const CnoBand Dy = c2_band(dy_span, dy_w, dy_taps), Dx = c2_band(dx_span, dx_w, dx_taps);
   hipStream_t st = as_stream(stream);
-  if (vx && vo) hipLaunchKernelGGL((k_cno2d_act_fwd<true, true>), grid, block, 0, st, x, scale, shift, out, s, Uy, Ux, Dy, Dx);
-  else if (vx) hipLaunchKernelGGL((k_cno2d_act_fwd<true, false>), grid, block, 0, st, x, scale, shift, out, s, Uy, Ux, Dy, Dx);
-  else if (vo) hipLaunchKernelGGL((k_cno2d_act_fwd<false, true>), grid, block, 0, st, x, scale, shift, out, s, Uy, Ux, Dy, Dx);
-  else hipLaunchKernelGGL((k_cno2d_act_fwd<false, false>), grid, block, 0, st, x, scale, shift, out, s, Uy, Ux, Dy, Dx);
+  cno_vec_dispatch(vx, vo, [&](auto VX, auto VO) {
+    hipLaunchKernelGGL((k_cno2d_act_fwd<decltype(VX)::value, decltype(VO)::value>), grid, block, 0, st, x, scale, shift, out, s, Uy, Ux, Dy, Dx);
+  });
   RPDE_LAUNCH_CHECK();
   return RPDE_OK;
 }
@@ -494,114 +384,21 @@ int rpde_cno_act2d_bwd(const float* x, const float* scale, const float* shift, c
   Cno2Shape s;
   RPDE_TRY(c2_shape(what, s, true, x, scale, shift, B, C, h_in, w_in, h_mid, w_mid, h_out, w_out, slope));
   RPDE_CHECK_ARG(g && gy, "%s: null tensor", what);
-  RPDE_TRY(cno_band(what, "U_y", uy_span, uy_w, uy_taps));
-  RPDE_TRY(cno_band(what, "U_x", ux_span, ux_w, ux_taps));
-  RPDE_TRY(cno_band(what, "U_y^T", uyt_span, uyt_w, uyt_taps));
-  RPDE_TRY(cno_band(what, "U_x^T", uxt_span, uxt_w, uxt_taps));
-  RPDE_TRY(cno_band(what, "D_y^T", dyt_span, dyt_w, dyt_taps));
-  RPDE_TRY(cno_band(what, "D_x^T", dxt_span, dxt_w, dxt_taps));
+  CnoBand Uy, Ux, UyT, UxT, DyT, DxT;
+  RPDE_TRY(cno_band(what, "U_y", uy_span, uy_w, uy_taps, Uy));
+  RPDE_TRY(cno_band(what, "U_x", ux_span, ux_w, ux_taps, Ux));
+  RPDE_TRY(cno_band(what, "U_y^T", uyt_span, uyt_w, uyt_taps, UyT));
+  RPDE_TRY(cno_band(what, "U_x^T", uxt_span, uxt_w, uxt_taps, UxT));
+  RPDE_TRY(cno_band(what, "D_y^T", dyt_span, dyt_w, dyt_taps, DyT));
+  RPDE_TRY(cno_band(what, "D_x^T", dxt_span, dxt_w, dxt_taps, DxT));
   const bool vx = w_in % 4 == 0 && al16(x) && al16(gy), vo = w_out % 4 == 0 && al16(g);
   const long groups = ((long)s.planes + s.pack - 1) / s.pack;
   const dim3 grid((unsigned)(groups * s.nty * s.ntx)), block(C2_THREADS);
-  const CnoBand Uy = c2_band(uy_span, uy_w, uy_taps), Ux = c2_band(ux_span, ux_w, ux_taps);
-  const CnoBand UyT = c2_band(uyt_span, uyt_w, uyt_taps), UxT = c2_band(uxt_span, uxt_w, uxt_taps);
-  const CnoBand DyT = c2_band(dyt_span, dyt_w, dyt_taps), DxT = c2_band(dxt_span, dxt_w, dxt_taps);
   hipStream_t st = as_stream(stream);
-  if (vx && vo) hipLaunchKernelGGL((k_cno2d_act_bwd<true, true>), grid, block, 0, st, x, scale, shift, g, gy, s, Uy, Ux, UyT, UxT, DyT, DxT);
-  else if (vx) hipLaunchKernelGGL((k_cno2d_act_bwd<true, false>), grid, block, 0, st, x, scale, shift, g, gy, s, Uy, Ux, UyT, UxT, DyT, DxT);
-  else if (vo) hipLaunchKernelGGL((k_cno2d_act_bwd<false, true>), grid, block, 0, st, x, scale, shift, g, gy, s, Uy, Ux, UyT, UxT, DyT, DxT);
-  else hipLaunchKernelGGL((k_cno2d_act_bwd<false, false>), grid, block, 0, st, x, scale, shift, g, gy, s, Uy, Ux, UyT, UxT, DyT, DxT);
-  RPDE_LAUNCH_CHECK();
-  return RPDE_OK;
-}
-
-// the nine taps of Conv2d(k = 3, padding = 1) as accumulating GEMMs on shifted views.  Tap (dy, dx)
-// adds W_t src[y + dy][x + dx] to dst[y][x] wherever both lie in the plane.  The centre tap goes first, over the flat
-// H W axis (it carries the bias and initialises dst); a dx = 0 tap is flat too, (H - 1) W points from a row further
-// on; a dx != 0 tap must not wrap across row ends, so it runs row by row through the descriptor's two-level batch
-// (z1: sample, z2: image row) on W - 1 points.  transposed: the data gradient, the same products with W_t^T and the
-// shifts mirrored
-static int cno_conv2d_taps(const float* src, const float* wt, const float* bias, float* dst, int B, int Csrc, int Cdst, int H,
-                           int W, bool transposed, hipStream_t st) {
-  const int Cin = transposed ? Cdst : Csrc, Cout = transposed ? Csrc : Cdst;
-  const long plane = (long)H * W;
-  static const int order[9] = {4, 1, 7, 0, 2, 3, 5, 6, 8};
-  for (int pass = 0; pass < 9; ++pass) {
-    const int t = order[pass];
-    int dy = t / 3 - 1, dx = t % 3 - 1;
-    if ((dy != 0 && H < 2) || (dx != 0 && W < 2)) continue;
-    if (transposed) { dy = -dy; dx = -dx; }
-    const int ady = dy < 0 ? -dy : dy;
-    // dst[y][x] += src[y + dy][x + dx]: first row / column read and written
-    const long read_at = (long)std::max(dy, 0) * W + std::max(dx, 0), write_at = (long)std::max(-dy, 0) * W + std::max(-dx, 0);
-    rpde_gemm_desc d = gemm_desc();
-    d.A = wt + (long)t * Cout * Cin; d.a_kmajor = transposed ? 0 : 1; d.lda = Cin;
-    d.b_kmajor = 0; d.ldb = plane; d.ldc = plane;
-    d.M = Cdst; d.K = Csrc;
-    d.B = src + read_at; d.C = dst + write_at;
-    if (dx == 0) {
-      d.N = (int)((H - ady) * (long)W);
-      d.batch = B; d.sB1 = Csrc * plane; d.sC1 = Cdst * plane;
-    } else {
-      d.N = W - 1;
-      d.batch = B * (H - ady); d.zdiv = H - ady;
-      d.sB1 = Csrc * plane; d.sC1 = Cdst * plane; d.sB2 = W; d.sC2 = W;
-    }
-    d.accumulate = pass > 0;
-    if (pass == 0 && bias) { d.bias = bias; d.bias_mode = 2; }
-    RPDE_TRY(launch_gemm(d, st));
-  }
-  return RPDE_OK;
-}
-
-static int cno_conv2d_check(const char* what, const void* a, const void* b, const void* c, int B, int Cin, int Cout, int H, int W) {
-  RPDE_CHECK_ARG(a && b && c, "%s: null tensor", what);
-  RPDE_CHECK_ARG(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: bad sizes B=%d Cin=%d Cout=%d H=%d W=%d", what, B, Cin,
-                 Cout, H, W);
-  RPDE_CHECK_ARG((long)H * W < (1L << 31) && (long)B * H < (1L << 31), "%s: plane too large (H W and B H must stay below 2^31)", what);
-  return RPDE_OK;
-}
-
-int rpde_cno_conv2d_k3_fwd(const float* x, const float* wt, const float* bias, float* out, int B, int Cin, int Cout, int H,
-                           int W, void* stream) {
-  RPDE_TRY(cno_conv2d_check("cno_conv2d_k3_fwd", x, wt, out, B, Cin, Cout, H, W));
-  return cno_conv2d_taps(x, wt, bias, out, B, Cin, Cout, H, W, false, as_stream(stream));
-}
-
-int rpde_cno_conv2d_k3_bwd_data(const float* g, const float* wt, float* gx, int B, int Cin, int Cout, int H, int W,
-                                void* stream) {
-  RPDE_TRY(cno_conv2d_check("cno_conv2d_k3_bwd_data", g, wt, gx, B, Cin, Cout, H, W));
-  return cno_conv2d_taps(g, wt, nullptr, gx, B, Cout, Cin, H, W, true, as_stream(stream));
-}
-
-int rpde_cno_conv2d_k3_bwd_weight_slices(int B, int Cin, int Cout, int H, int W) {
-  if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return 0;
-  return c2w_slices(B, Cin, Cout, H, W);
-}
-
-int rpde_cno_conv2d_k3_bwd_weight(const float* x, const float* g, float* gw, float* gb, int B, int Cin, int Cout, int H, int W,
-                                  float* partial, int partial_slices, void* stream) {
-  const char* what = "cno_conv2d_k3_bwd_weight";
-  RPDE_TRY(cno_conv2d_check(what, x, g, gw, B, Cin, Cout, H, W));
-  const int slices = c2w_slices(B, Cin, Cout, H, W);
-  RPDE_CHECK_ARG(slices == 1 || (partial && partial_slices >= slices),
-                 "%s: partial sums of %d slices needed, the buffer holds %d", what, slices, partial ? partial_slices : 0);
-  const dim3 grid((unsigned)((Cin + C2W - 1) / C2W), (unsigned)((Cout + C2W - 1) / C2W), (unsigned)slices);
-  RPDE_CHECK_ARG(grid.y <= 65535, "%s: too many output channels (%d)", what, Cout);
-  const int BH = B * H, rows_per_slice = (BH + slices - 1) / slices;
-  const long n_gw = (long)Cout * Cin * 9, n_gb = Cout;
-  hipStream_t st = as_stream(stream);
-  if (slices == 1) {
-    hipLaunchKernelGGL(k_cno_conv2d_wgrad, grid, dim3(256), 0, st, x, g, gw, gb, 0L, BH, Cin, Cout, H, W, rows_per_slice);
-    RPDE_LAUNCH_CHECK();
-    return RPDE_OK;
-  }
-  float* part = partial;
-  hipLaunchKernelGGL(k_cno_conv2d_wgrad, grid, dim3(256), 0, st, x, g, part, part + n_gw, n_gw + n_gb, BH, Cin, Cout, H, W,
-                     rows_per_slice);
-  RPDE_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_cno_conv2d_wsum, dim3((unsigned)((n_gw + n_gb + 255) / 256)), dim3(256), 0, st, part, gw, gb, n_gw, n_gb,
-                     slices);
+  cno_vec_dispatch(vx, vo, [&](auto VX, auto VO) {
+    hipLaunchKernelGGL((k_cno2d_act_bwd<decltype(VX)::value, decltype(VO)::value>), grid, block, 0, st, x, scale, shift, g, gy, s, Uy, Ux,
+                       UyT, UxT, DyT, DxT);
+  });
   RPDE_LAUNCH_CHECK();
   return RPDE_OK;
 }

@@ -1,0 +1,334 @@
+// The rest of a CNO block, both ranks (the activation itself: cno.hip in 1-D, cno2d.hip in 2-D): Conv(k = 3,
+// padding = 1) as accumulating GEMMs on shifted views with its own deterministic weight-gradient kernel, and the two
+// kernels of BatchNorm (per-channel moments, per-channel affine combine).  Conv1d is Conv2d on a plane of one row with
+// one row of taps: one tap loop and one weight-gradient kernel serve both.  gfx950 (CDNA4,
+// wave64) only.
+#include "rpde_internal.h"
+#include "wave.h"
+
+#include <algorithm>
+
+namespace rpde {
+
+// ---- Conv(k = 3, padding = 1): weight and bias gradient -----------------------------------------------------------
+// gw[co][ci][ty][tx] = sum_{b,y,x} g[b][co][y][x] * x[b][ci][y + ty - KY / 2][x + tx - 1],  gb[co] = sum g[b][co][y][x],
+// KY rows of taps: 3 for Conv2d, 1 for Conv1d (H = 1, gw [Cout][Cin][3]).  A workgroup owns a 4 x 4 tile of (co, ci)
+// and one slice of the image rows (b, y): every thread walks the slice's points tid, tid + 256, ... with 48 KY + 4
+// accumulators, then the workgroup adds them up in a fixed order (DPP sum inside a wave, the four waves in sequence).
+// With one slice the sums are the result; with more they are partial sums [slice][Cout Cin 9 + Cout], added slice by
+// slice by k_cno_conv2d_wsum.  No atomics.  Conv1d always runs one slice
+constexpr int CNO_WG = 4;
+constexpr int C2W_TARGET = 512;       // workgroups wanted: two per CU
+constexpr int C2W_MIN_POINTS = 256;   // a slice holds at least one point per thread
+
+template <int KY>
+__global__ void __launch_bounds__(256)
+k_cno_conv_wgrad(const float* __restrict__ x, const float* __restrict__ g, float* __restrict__ gw, float* __restrict__ gb,
+                 long slice_stride, int BH, int Cin, int Cout, int H_, int W, int rows_per_slice) {
+  constexpr int T = 3 * KY, N_GW = CNO_WG * CNO_WG * T;
+  __shared__ float red[4][N_GW + CNO_WG];
+  const int H = KY == 1 ? 1 : H_;
+  const int ci0 = blockIdx.x * CNO_WG, co0 = blockIdx.y * CNO_WG;
+  const int r_lo = blockIdx.z * rows_per_slice, r_hi = min(BH, r_lo + rows_per_slice);
+  float acc[CNO_WG][CNO_WG][T], accb[CNO_WG];
+#pragma unroll
+  for (int j = 0; j < CNO_WG; ++j) {
+    accb[j] = 0.f;
+#pragma unroll
+    for (int i = 0; i < CNO_WG; ++i)
+#pragma unroll
+      for (int t = 0; t < T; ++t) acc[j][i][t] = 0.f;
+  }
+  const long plane = (long)H * W;
+  const long total = (long)(r_hi - r_lo) * W;
+  for (long p = threadIdx.x; p < total; p += 256) {
+    const int r = r_lo + (int)(p / W), xx = (int)(p % W);
+    const int b = r / H, y = r - b * H;
+    float gv[CNO_WG];
+#pragma unroll
+    for (int j = 0; j < CNO_WG; ++j) {
+      gv[j] = co0 + j < Cout ? g[((long)b * Cout + co0 + j) * plane + (long)y * W + xx] : 0.f;
+      accb[j] += gv[j];
+    }
+#pragma unroll
+    for (int i = 0; i < CNO_WG; ++i) {
+      const bool live = ci0 + i < Cin;
+      const float* img = x + ((long)b * Cin + (live ? ci0 + i : 0)) * plane;
+      float xv[T];
+#pragma unroll
+      for (int ty = 0; ty < KY; ++ty) {
+        const int yy = y + ty - KY / 2;
+        const bool row_ok = live && yy >= 0 && yy < H;
+#pragma unroll
+        for (int tx = 0; tx < 3; ++tx) {
+          const int xs = xx + tx - 1;
+          xv[ty * 3 + tx] = row_ok && xs >= 0 && xs < W ? img[(long)yy * W + xs] : 0.f;
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < CNO_WG; ++j)
+#pragma unroll
+        for (int t = 0; t < T; ++t) acc[j][i][t] = fmaf(gv[j], xv[t], acc[j][i][t]);
+    }
+  }
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+  for (int j = 0; j < CNO_WG; ++j) {
+#pragma unroll
+    for (int i = 0; i < CNO_WG; ++i)
+#pragma unroll
+      for (int t = 0; t < T; ++t) {
+        const float v = wave_sum_dpp(acc[j][i][t]);
+        if (lane == 0) red[wave][(j * CNO_WG + i) * T + t] = v;
+      }
+    const float v = wave_sum_dpp(accb[j]);
+    if (lane == 0) red[wave][N_GW + j] = v;
+  }
+  __syncthreads();
+  const int k = threadIdx.x;
+  if (k < N_GW + CNO_WG) {
+    const float v = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+    float* gw_s = gw + blockIdx.z * slice_stride;
+    if (k < N_GW) {
+      const int j = k / (CNO_WG * T), i = (k / T) % CNO_WG, t = k % T;
+      if (co0 + j < Cout && ci0 + i < Cin) gw_s[((long)(co0 + j) * Cin + ci0 + i) * T + t] = v;
+    } else if (gb && blockIdx.x == 0 && co0 + (k - N_GW) < Cout) {
+      gb[blockIdx.z * slice_stride + co0 + k - N_GW] = v;
+    }
+  }
+}
+
+// gw / gb = the slices' partial sums added in slice order
+__global__ void __launch_bounds__(256)
+k_cno_conv2d_wsum(const float* __restrict__ part, float* __restrict__ gw, float* __restrict__ gb, long n_gw, long n_gb,
+                  int slices) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n_gw + n_gb) return;
+  float v = 0.f;
+  for (int s = 0; s < slices; ++s) v += part[s * (n_gw + n_gb) + e];
+  if (e < n_gw) gw[e] = v;
+  else if (gb) gb[e - n_gw] = v;
+}
+
+// slices of the (b, y) rows the Conv2d weight gradient is split over
+static int c2w_slices(int B, int Cin, int Cout, int H, int W) {
+  const long tiles = (long)((Cin + CNO_WG - 1) / CNO_WG) * ((Cout + CNO_WG - 1) / CNO_WG);
+  const long rows = (long)B * H;
+  long n = std::min<long>(C2W_TARGET / tiles, std::min<long>(rows, rows * W / C2W_MIN_POINTS));
+  return (int)std::max<long>(1, std::min<long>(n, 65535));
+}
+
+// ---- BatchNorm pieces ---------------------------------------------------------------------------------------------
+// sums[c] = (sum a, sum b, sum a b, sum b^2) over (batch, x) of channel c of two [B, C, n] tensors, in double; one
+// workgroup per channel, fixed order.  The forward takes mean and variance of z from (z, z), the backward sum gy and
+// sum gy z from (gy, z)
+__global__ void __launch_bounds__(256)
+k_cno_moments(const float* __restrict__ a, const float* __restrict__ b, double* __restrict__ sums, int B, int C, int n) {
+  __shared__ double red[4][4];
+  const int c = blockIdx.x;
+  double s[4] = {0.0, 0.0, 0.0, 0.0};
+  const long total = (long)B * n;
+  for (long p = threadIdx.x; p < total; p += 256) {
+    const long bb = p / n;
+    const long at = (bb * C + c) * n + (p - bb * n);
+    const double va = a[at], vb = b[at];
+    s[0] += va; s[1] += vb; s[2] += va * vb; s[3] += vb * vb;
+  }
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const double v = wave_sum(s[k]);
+    if (lane == 0) red[wave][k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    const int k = threadIdx.x;
+    sums[c * 4 + k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+  }
+}
+
+// out = p0[c] a + p1[c] b + p2[c] (+ residual): a BatchNorm's apply step (p1 null: no b term), its backward
+// dz = p0 gy + p1 z + p2, and the residual block's skip add.  The coefficients are doubles and so is the arithmetic,
+// rounded once: with few values per channel the backward's three terms cancel to eps / (var + eps) of their size, and
+// fp32 coefficients would leave nothing of the result; the kernel stays bound by its bytes
+template <bool VEC>
+__global__ void __launch_bounds__(256)
+k_cno_affine(const float* __restrict__ a, const float* __restrict__ b, const double* __restrict__ p0,
+             const double* __restrict__ p1, const double* __restrict__ p2, const float* __restrict__ res,
+             float* __restrict__ out, long total, int C, int n) {
+  constexpr int W = VEC ? 4 : 1;
+  const long i = ((long)blockIdx.x * 256 + threadIdx.x) * W;
+  if (i >= total) return;
+  const int c = (int)((i / n) % C);
+  const double k0 = p0[c], k1 = p1 ? p1[c] : 0.0, k2 = p2[c];
+  alignas(16) float va[W], vb[W], vr[W], o[W];
+  if (VEC) {
+    *reinterpret_cast<float4*>(va) = *reinterpret_cast<const float4*>(a + i);
+    if (p1) *reinterpret_cast<float4*>(vb) = *reinterpret_cast<const float4*>(b + i);
+    if (res) *reinterpret_cast<float4*>(vr) = *reinterpret_cast<const float4*>(res + i);
+  } else {
+    va[0] = a[i];
+    if (p1) vb[0] = b[i];
+    if (res) vr[0] = res[i];
+  }
+#pragma unroll
+  for (int k = 0; k < W; ++k) {
+    double v = fma(k0, (double)va[k], k2);
+    if (p1) v = fma(k1, (double)vb[k], v);
+    if (res) v += (double)vr[k];
+    o[k] = (float)v;
+  }
+  if (VEC) *reinterpret_cast<float4*>(out + i) = *reinterpret_cast<float4*>(o);
+  else out[i] = o[0];
+}
+
+}  // namespace rpde
+
+using namespace rpde;
+
+extern "C" {
+
+// The taps of Conv(k = 3, padding = 1) as accumulating GEMMs on shifted views; wt holds KY
+// rows of three taps, [3 KY][Cout][Cin]: KY = 3 for Conv2d, KY = 1 for Conv1d, whose row of taps is the dy = 0 one of
+// a plane with H = 1.  Tap (dy, dx) adds W_t src[y + dy][x + dx] to dst[y][x] wherever both lie in the plane; taps
+// without a valid range (H = 1 or W = 1) are skipped.  The centre tap goes first, over the flat H W axis (it carries
+// the bias and initialises dst); a dx = 0 tap is flat too, (H - 1) W points from a row further on; a dx != 0 tap must
+// not wrap across row ends, so it runs row by row through the descriptor's two-level batch (z1: sample, z2: image row)
+// on W - 1 points.  (With one image row, H = 1, the second level is idle -- z2 = 0 -- and its stride W cannot move
+// launch_gemm's choice of kernel either: the vector path already needs N = W - 1 and ldb = W to be multiples of 4
+// together.  Conv1d's three GEMMs are therefore the ones it always ran: centre, left, right.)  transposed: the data
+// gradient, the same products with W_t^T and the shifts mirrored
+static int cno_conv_taps(const float* src, const float* wt, const float* bias, float* dst, int B, int Csrc, int Cdst, int KY,
+                         int H, int W, bool transposed, hipStream_t st) {
+  const int Cin = transposed ? Cdst : Csrc, Cout = transposed ? Csrc : Cdst;
+  const long plane = (long)H * W;
+  static const int order[9] = {4, 1, 7, 0, 2, 3, 5, 6, 8};
+  for (int pass = 0; pass < 9; ++pass) {
+    int dy = order[pass] / 3 - 1, dx = order[pass] % 3 - 1;
+    if ((dy != 0 && H < 2) || (dx != 0 && W < 2)) continue;
+    const int t = (dy + KY / 2) * 3 + dx + 1;                   // this tap in wt
+    if (transposed) { dy = -dy; dx = -dx; }
+    const int ady = dy < 0 ? -dy : dy;
+    // dst[y][x] += src[y + dy][x + dx]: first row / column read and written
+    const long read_at = (long)std::max(dy, 0) * W + std::max(dx, 0), write_at = (long)std::max(-dy, 0) * W + std::max(-dx, 0);
+    rpde_gemm_desc d = gemm_desc();
+    d.A = wt + (long)t * Cout * Cin; d.a_kmajor = transposed ? 0 : 1; d.lda = Cin;
+    d.b_kmajor = 0; d.ldb = plane; d.ldc = plane;
+    d.M = Cdst; d.K = Csrc;
+    d.B = src + read_at; d.C = dst + write_at;
+    if (dx == 0) {
+      d.N = (int)((H - ady) * (long)W);
+      d.batch = B; d.sB1 = Csrc * plane; d.sC1 = Cdst * plane;
+    } else {
+      d.N = W - 1;
+      d.batch = B * (H - ady); d.zdiv = H - ady;
+      d.sB1 = Csrc * plane; d.sC1 = Cdst * plane; d.sB2 = W; d.sC2 = W;
+    }
+    d.accumulate = pass > 0;
+    if (pass == 0 && bias) { d.bias = bias; d.bias_mode = 2; }
+    RPDE_TRY(launch_gemm(d, st));
+  }
+  return RPDE_OK;
+}
+
+static int cno_conv_wgrad(const char* what, const float* x, const float* g, float* gw, float* gb, int B, int Cin, int Cout,
+                          int KY, int H, int W, int slices, float* partial, hipStream_t st) {
+  const dim3 grid((unsigned)((Cin + CNO_WG - 1) / CNO_WG), (unsigned)((Cout + CNO_WG - 1) / CNO_WG), (unsigned)slices);
+  RPDE_CHECK_ARG(grid.y <= 65535, "%s: too many output channels (%d)", what, Cout);
+  const int BH = B * H, rows_per_slice = (BH + slices - 1) / slices;
+  const long n_gw = (long)Cout * Cin * 3 * KY, n_gb = Cout;
+  // one slice: the sums are the result; more: partial sums, then their sum
+  float* to_w = slices == 1 ? gw : partial;
+  float* to_b = slices == 1 ? gb : partial + n_gw;
+  const long stride = slices == 1 ? 0L : n_gw + n_gb;
+  if (KY == 1) hipLaunchKernelGGL(k_cno_conv_wgrad<1>, grid, dim3(256), 0, st, x, g, to_w, to_b, stride, BH, Cin, Cout, H, W, rows_per_slice);
+  else hipLaunchKernelGGL(k_cno_conv_wgrad<3>, grid, dim3(256), 0, st, x, g, to_w, to_b, stride, BH, Cin, Cout, H, W, rows_per_slice);
+  RPDE_LAUNCH_CHECK();
+  if (slices == 1) return RPDE_OK;
+  hipLaunchKernelGGL(k_cno_conv2d_wsum, dim3((unsigned)((n_gw + n_gb + 255) / 256)), dim3(256), 0, st, partial, gw, gb, n_gw,
+                     n_gb, slices);
+  RPDE_LAUNCH_CHECK();
+  return RPDE_OK;
+}
+
+int rpde_cno_conv1d_k3_fwd(const float* x, const float* wt, const float* bias, float* out, int B, int Cin, int Cout, int n,
+                           void* stream) {
+  RPDE_CHECK_ARG(x && wt && out, "cno_conv1d_k3_fwd: null tensor");
+  RPDE_CHECK_ARG(B > 0 && Cin > 0 && Cout > 0 && n > 0, "cno_conv1d_k3_fwd: bad sizes B=%d Cin=%d Cout=%d n=%d", B, Cin, Cout, n);
+  return cno_conv_taps(x, wt, bias, out, B, Cin, Cout, 1, 1, n, false, as_stream(stream));
+}
+
+int rpde_cno_conv1d_k3_bwd_data(const float* g, const float* wt, float* gx, int B, int Cin, int Cout, int n, void* stream) {
+  RPDE_CHECK_ARG(g && wt && gx, "cno_conv1d_k3_bwd_data: null tensor");
+  RPDE_CHECK_ARG(B > 0 && Cin > 0 && Cout > 0 && n > 0, "cno_conv1d_k3_bwd_data: bad sizes B=%d Cin=%d Cout=%d n=%d", B, Cin, Cout, n);
+  return cno_conv_taps(g, wt, nullptr, gx, B, Cout, Cin, 1, 1, n, true, as_stream(stream));
+}
+
+int rpde_cno_conv1d_k3_bwd_weight(const float* x, const float* g, float* gw, float* gb, int B, int Cin, int Cout, int n,
+                                  void* stream) {
+  RPDE_CHECK_ARG(x && g && gw, "cno_conv1d_k3_bwd_weight: null tensor");
+  RPDE_CHECK_ARG(B > 0 && Cin > 0 && Cout > 0 && n > 0, "cno_conv1d_k3_bwd_weight: bad sizes B=%d Cin=%d Cout=%d n=%d", B, Cin, Cout, n);
+  return cno_conv_wgrad("cno_conv1d_k3_bwd_weight", x, g, gw, gb, B, Cin, Cout, 1, 1, n, 1, nullptr, as_stream(stream));
+}
+
+static int cno_conv2d_check(const char* what, const void* a, const void* b, const void* c, int B, int Cin, int Cout, int H, int W) {
+  RPDE_CHECK_ARG(a && b && c, "%s: null tensor", what);
+  RPDE_CHECK_ARG(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: bad sizes B=%d Cin=%d Cout=%d H=%d W=%d", what, B, Cin,
+                 Cout, H, W);
+  RPDE_CHECK_ARG((long)H * W < (1L << 31) && (long)B * H < (1L << 31), "%s: plane too large (H W and B H must stay below 2^31)", what);
+  return RPDE_OK;
+}
+
+int rpde_cno_conv2d_k3_fwd(const float* x, const float* wt, const float* bias, float* out, int B, int Cin, int Cout, int H,
+                           int W, void* stream) {
+  RPDE_TRY(cno_conv2d_check("cno_conv2d_k3_fwd", x, wt, out, B, Cin, Cout, H, W));
+  return cno_conv_taps(x, wt, bias, out, B, Cin, Cout, 3, H, W, false, as_stream(stream));
+}
+
+int rpde_cno_conv2d_k3_bwd_data(const float* g, const float* wt, float* gx, int B, int Cin, int Cout, int H, int W,
+                                void* stream) {
+  RPDE_TRY(cno_conv2d_check("cno_conv2d_k3_bwd_data", g, wt, gx, B, Cin, Cout, H, W));
+  return cno_conv_taps(g, wt, nullptr, gx, B, Cout, Cin, 3, H, W, true, as_stream(stream));
+}
+
+int rpde_cno_conv2d_k3_bwd_weight_slices(int B, int Cin, int Cout, int H, int W) {
+  if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return 0;
+  return c2w_slices(B, Cin, Cout, H, W);
+}
+
+int rpde_cno_conv2d_k3_bwd_weight(const float* x, const float* g, float* gw, float* gb, int B, int Cin, int Cout, int H, int W,
+                                  float* partial, int partial_slices, void* stream) {
+  const char* what = "cno_conv2d_k3_bwd_weight";
+  RPDE_TRY(cno_conv2d_check(what, x, g, gw, B, Cin, Cout, H, W));
+  const int slices = c2w_slices(B, Cin, Cout, H, W);
+  RPDE_CHECK_ARG(slices == 1 || (partial && partial_slices >= slices),
+                 "%s: partial sums of %d slices needed, the buffer holds %d", what, slices, partial ? partial_slices : 0);
+  return cno_conv_wgrad(what, x, g, gw, gb, B, Cin, Cout, 3, H, W, slices, partial, as_stream(stream));
+}
+
+int rpde_cno_moments(const float* a, const float* b, double* sums, int B, int C, int n, void* stream) {
+  RPDE_CHECK_ARG(a && b && sums, "cno_moments: null tensor");
+  RPDE_CHECK_ARG(B > 0 && C > 0 && n > 0, "cno_moments: bad sizes B=%d C=%d n=%d", B, C, n);
+  RPDE_CHECK_ARG((reinterpret_cast<uintptr_t>(sums) & 7) == 0, "cno_moments: sums must be 8-byte aligned");
+  hipLaunchKernelGGL(k_cno_moments, dim3((unsigned)C), dim3(256), 0, as_stream(stream), a, b, sums, B, C, n);
+  RPDE_LAUNCH_CHECK();
+  return RPDE_OK;
+}
+
+int rpde_cno_affine(const float* a, const float* b, const double* p0, const double* p1, const double* p2, const float* residual,
+                    float* out, int B, int C, int n, void* stream) {
+  RPDE_CHECK_ARG(a && p0 && p2 && out, "cno_affine: null tensor");
+  RPDE_CHECK_ARG((b == nullptr) == (p1 == nullptr), "cno_affine: b and p1 come together");
+  RPDE_CHECK_ARG(B > 0 && C > 0 && n > 0, "cno_affine: bad sizes B=%d C=%d n=%d", B, C, n);
+  const long total = (long)B * C * n;
+  const bool vec = n % 4 == 0 && al16(a) && al16(out) && (!b || al16(b)) && (!residual || al16(residual));
+  const long threads = vec ? total / 4 : total;
+  RPDE_CHECK_ARG((threads + 255) / 256 < (1L << 31), "cno_affine: tensor too large for one launch");
+  const dim3 grid((unsigned)((threads + 255) / 256));
+  if (vec) hipLaunchKernelGGL((k_cno_affine<true>), grid, dim3(256), 0, as_stream(stream), a, b, p0, p1, p2, residual, out, total, C, n);
+  else hipLaunchKernelGGL((k_cno_affine<false>), grid, dim3(256), 0, as_stream(stream), a, b, p0, p1, p2, residual, out, total, C, n);
+  RPDE_LAUNCH_CHECK();
+  return RPDE_OK;
+}
+
+}  // extern "C"

@@ -1,149 +1,33 @@
-"""Convolutional Neural Operator in 2-D (reference models/CNO2d.py; Raonic et al., "Convolutional Neural Operators for
-robust and accurate learning of PDEs", NeurIPS 2023): an operator U-Net whose every activation is applied at twice the
-sampling rate between two antialiased resamplings, so that the nonlinearity does not alias.
+"""Convolutional Neural Operator in 2-D (reference models/CNO2d.py): the module tree of models/cno_nd.py bound to
+nn.Conv2d, nn.BatchNorm2d and rpde.ops conv2d_k3, batchnorm2d, cno_act2d.  Each class names the rank and the classes of
+this module that it builds its children from."""
+from models import cno_nd
 
-The classes, constructor signatures, attribute names and state_dict layout are the reference's -- nn.Conv2d and
-nn.BatchNorm2d own the parameters and buffers, so a reference checkpoint loads with strict=True -- but no forward here
-calls an ATen kernel for arithmetic: convolutions, BatchNorm and the activation run in librpde_hip.so (rpde.ops
-conv2d_k3, batchnorm2d, cno_act2d).  Where a BatchNorm precedes the activation its apply step is the activation
-kernel's prologue and the normalised tensor is never written.  torch.cat stays torch's: it is a copy.
-"""
-from __future__ import annotations
-
-import torch
-import torch.nn as nn
-
-from rpde import ops
+_ND = cno_nd.RANK[2]
 
 
-def _conv(layer: nn.Conv2d, x):
-    return ops.conv2d_k3(x, layer.weight, layer.bias)
+class CNO_LReLu(cno_nd.CNO_LReLu):
+    nd = _ND
 
 
-def _norm(bn, z, residual=None, act=None):
-    """BatchNorm2d bn on z, then the skip add or CNO_LReLu(*act); bn may be nn.Identity (use_bn=False)"""
-    if isinstance(bn, nn.Identity):
-        if act is not None:
-            return ops.cno_act2d(z, act[0], act[1])
-        return z if residual is None else ops.skip_add(z, residual)
-    momentum = 0.1 if bn.momentum is None else bn.momentum
-    return ops.batchnorm2d(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.training,
-                           momentum, bn.eps, residual=residual, act=act)
+class CNOBlock(cno_nd.CNOBlock):
+    nd, CNO_LReLu = _ND, CNO_LReLu
 
 
-class CNO_LReLu(nn.Module):
-    """upsample to 2 in_size -> LeakyReLU -> downsample to out_size, one kernel (rpde.ops.cno_act2d)"""
-
-    def __init__(self, in_size, out_size):
-        super().__init__()
-        self.in_size, self.out_size = in_size, out_size
-        self.act = nn.LeakyReLU()
-
-    def forward(self, x):
-        return ops.cno_act2d(x, self.in_size, self.out_size, slope=self.act.negative_slope)
+class LiftProjectBlock(cno_nd.LiftProjectBlock):
+    nd, CNOBlock = _ND, CNOBlock
 
 
-class CNOBlock(nn.Module):
-    """Conv2d(k=3) -> BatchNorm2d (optional) -> CNO_LReLu; the resampling in_size -> out_size happens in the activation"""
-
-    def __init__(self, in_channels, out_channels, in_size, out_size, use_bn=True):
-        super().__init__()
-        self.in_channels, self.out_channels = in_channels, out_channels
-        self.in_size, self.out_size = in_size, out_size
-        self.convolution = nn.Conv2d(in_channels, out_channels, kernel_size=3, padding=1)
-        self.batch_norm = nn.BatchNorm2d(out_channels) if use_bn else nn.Identity()
-        self.act = CNO_LReLu(in_size=in_size, out_size=out_size)
-
-    def forward(self, x):
-        return _norm(self.batch_norm, _conv(self.convolution, x), act=(self.in_size, self.out_size))
+class ResidualBlock(cno_nd.ResidualBlock):
+    nd, CNO_LReLu = _ND, CNO_LReLu
 
 
-class LiftProjectBlock(nn.Module):
-    def __init__(self, in_channels, out_channels, size, latent_dim=64):
-        super().__init__()
-        self.inter_CNOBlock = CNOBlock(in_channels, latent_dim, in_size=size, out_size=size, use_bn=False)
-        self.convolution = nn.Conv2d(latent_dim, out_channels, kernel_size=3, padding=1)
-
-    def forward(self, x):
-        return _conv(self.convolution, self.inter_CNOBlock(x))
+class ResNet(cno_nd.ResNet):
+    ResidualBlock = ResidualBlock
 
 
-class ResidualBlock(nn.Module):
-    """x + BN2(Conv2(CNO_LReLu(BN1(Conv1(x)))))"""
-
-    def __init__(self, channels, size, use_bn=True):
-        super().__init__()
-        self.channels, self.size = channels, size
-        self.convolution1 = nn.Conv2d(channels, channels, kernel_size=3, padding=1)
-        self.convolution2 = nn.Conv2d(channels, channels, kernel_size=3, padding=1)
-        self.batch_norm1 = nn.BatchNorm2d(channels) if use_bn else nn.Identity()
-        self.batch_norm2 = nn.BatchNorm2d(channels) if use_bn else nn.Identity()
-        self.act = CNO_LReLu(in_size=size, out_size=size)
-
-    def forward(self, x):
-        out = _norm(self.batch_norm1, _conv(self.convolution1, x), act=(self.size, self.size))
-        return _norm(self.batch_norm2, _conv(self.convolution2, out), residual=x)
-
-
-class ResNet(nn.Module):
-    def __init__(self, channels, size, num_blocks, use_bn=True):
-        super().__init__()
-        self.channels, self.size, self.num_blocks = channels, size, num_blocks
-        self.res_nets = nn.Sequential(*[ResidualBlock(channels, size, use_bn) for _ in range(num_blocks)])
-
-    def forward(self, x):
-        return self.res_nets(x)
-
-
-class CNO2d(nn.Module):
+class CNO2d(cno_nd.CNO):
     """in_dim / out_dim channels on size x size points; N_layers down- and up-sampling levels, N_res residual blocks per
     level and N_res_neck in the neck; level i has channel_multiplier 2^(i-1) channels on (size / 2^i)^2 points.  Inputs
     of another size are resampled by the first activation (F.interpolate(size=...) in the reference does the same)."""
-
-    def __init__(self, in_dim, out_dim, size, N_layers, N_res=4, N_res_neck=4, channel_multiplier=16, use_bn=True):
-        super().__init__()
-        self.N_layers = int(N_layers)
-        self.lift_dim = channel_multiplier // 2
-        self.in_dim, self.out_dim = in_dim, out_dim
-        self.channel_multiplier = channel_multiplier
-        L = self.N_layers
-
-        self.encoder_features = [self.lift_dim] + [2 ** i * channel_multiplier for i in range(L)]
-        self.decoder_features_in = self.encoder_features[1:][::-1]
-        self.decoder_features_out = self.encoder_features[:-1][::-1]
-        for i in range(1, L):                      # the skip connection is concatenated in front of every (U) block but the first
-            self.decoder_features_in[i] *= 2
-        self.encoder_sizes = [size // 2 ** i for i in range(L + 1)]
-        self.decoder_sizes = [size // 2 ** (L - i) for i in range(L + 1)]
-
-        enc, dec_in, dec_out = self.encoder_features, self.decoder_features_in, self.decoder_features_out
-        self.lift = LiftProjectBlock(in_dim, enc[0], size)
-        self.project = LiftProjectBlock(enc[0] + dec_out[-1], out_dim, size)
-        self.encoder = nn.ModuleList([CNOBlock(enc[i], enc[i + 1], self.encoder_sizes[i], self.encoder_sizes[i + 1], use_bn)
-                                      for i in range(L)])
-        self.ED_expansion = nn.ModuleList([CNOBlock(enc[i], enc[i], self.encoder_sizes[i], self.decoder_sizes[L - i], use_bn)
-                                           for i in range(L + 1)])
-        self.decoder = nn.ModuleList([CNOBlock(dec_in[i], dec_out[i], self.decoder_sizes[i], self.decoder_sizes[i + 1], use_bn)
-                                      for i in range(L)])
-        self.N_res, self.N_res_neck = int(N_res), int(N_res_neck)
-        # (built before the neck, registered after it: the reference's order of random draws and of state_dict keys)
-        levels = [ResNet(enc[i], self.encoder_sizes[i], self.N_res, use_bn) for i in range(L)]
-        self.res_net_neck = ResNet(enc[L], self.encoder_sizes[L], self.N_res_neck, use_bn)
-        self.res_nets = nn.Sequential(*levels)
-
-    def forward(self, x):
-        L = self.N_layers
-        x = self.lift(x)
-        skip = []
-        for i in range(L):                         # encoder: the level's ResNet feeds the skip, the (D) block goes down
-            skip.append(self.res_nets[i](x))
-            x = self.encoder[i](x)
-        x = self.res_net_neck(x)
-        for i in range(L):                         # decoder: (I) block on the neck / on the skip, concatenated, then (U)
-            if i == 0:
-                x = self.ED_expansion[L](x)
-            else:
-                x = torch.cat((x, self.ED_expansion[L - i](skip[-i])), 1)
-            x = self.decoder[i](x)
-        x = torch.cat((x, self.ED_expansion[0](skip[0])), 1)
-        return self.project(x)
+    LiftProjectBlock, CNOBlock, ResNet = LiftProjectBlock, CNOBlock, ResNet

@@ -1,7 +1,8 @@
 """The CNO side of rpde.ops (re-exported there): the banded tables of torch's antialiased bicubic resampling, the
 autograd Functions over the fused alias-free activation kernels in 1-D and 2-D, and the rest of a CNO block -- Conv1d /
-Conv2d (k = 3), BatchNorm, the skip add -- over their kernels (csrc/cno.hip, csrc/cno2d.hip, the CNO groups of
-include/rpde.h).
+Conv2d (k = 3), BatchNorm, the skip add -- over their kernels (csrc/cno.hip and csrc/cno2d.hip: the activation of each
+rank; csrc/cno_layers.hip: the rest; the CNO groups of include/rpde.h).  One Function per operation serves both ranks
+and picks the C entry by the tensor's rank; the public names below are the argument-checking fronts.
 
 CNO_LReLu (reference models/CNO1d.py:30-45) is  resample to 2 in_size -> LeakyReLU -> resample to out_size, both
 resamplings being F.interpolate(mode="bicubic", antialias=True, align_corners=False) on a (1, n) image: the identity
@@ -140,19 +141,35 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
     return t if t.is_contiguous() else t.contiguous()
 
 
-class _CnoAct1d(torch.autograd.Function):
+def _bands(t: CnoBand):
+    return t.span.data_ptr(), ptr(t.weights), t.taps
+
+
+class _CnoAct(torch.autograd.Function):
+    """the activation of x's rank: [B, C, n] through rpde_cno_act1d_*, [B, C, H, W] through rpde_cno_act2d_*, whose
+    tables come one per axis (U_y, U_x; the mid and output planes are square, so D serves both axes)"""
+
     @staticmethod
     def forward(ctx, x, scale, shift, n_mid: int, n_out: int, slope: float):
         lib = load()
         x = _f32c(x)
-        B, Cc, n_in = x.shape
         if scale is not None:
             scale, shift = _f32c(scale.detach()), _f32c(shift.detach())
-        U, D = cno_tables(x.device, n_in, n_mid), cno_tables(x.device, n_mid, n_out)
-        out = torch.empty(B, Cc, n_out, dtype=torch.float32, device=x.device)
-        check(lib.rpde_cno_act1d_fwd(ptr(x), ptr(scale), ptr(shift), ptr(out), B, Cc, n_in, n_mid, n_out, slope,
-                                     U.fwd.span.data_ptr(), ptr(U.fwd.weights), U.fwd.taps,
-                                     D.fwd.span.data_ptr(), ptr(D.fwd.weights), D.fwd.taps, stream_ptr()), "cno_act1d_fwd")
+        dev = x.device
+        D = cno_tables(dev, n_mid, n_out)
+        if x.dim() == 3:
+            B, Cc, n_in = x.shape
+            U = cno_tables(dev, n_in, n_mid)
+            out = torch.empty(B, Cc, n_out, dtype=torch.float32, device=dev)
+            check(lib.rpde_cno_act1d_fwd(ptr(x), ptr(scale), ptr(shift), ptr(out), B, Cc, n_in, n_mid, n_out, slope,
+                                         *_bands(U.fwd), *_bands(D.fwd), stream_ptr()), "cno_act1d_fwd")
+        else:
+            B, Cc, h_in, w_in = x.shape
+            Uy, Ux = cno_tables(dev, h_in, n_mid), cno_tables(dev, w_in, n_mid)
+            out = torch.empty(B, Cc, n_out, n_out, dtype=torch.float32, device=dev)
+            check(lib.rpde_cno_act2d_fwd(ptr(x), ptr(scale), ptr(shift), ptr(out), B, Cc, h_in, w_in, n_mid, n_mid, n_out, n_out,
+                                         slope, *_bands(Uy.fwd), *_bands(Ux.fwd), *_bands(D.fwd), *_bands(D.fwd), stream_ptr()),
+                  "cno_act2d_fwd")
         ctx.save_for_backward(x, scale, shift)
         ctx.meta = (n_mid, n_out, slope)
         return out
@@ -162,14 +179,21 @@ class _CnoAct1d(torch.autograd.Function):
         lib = load()
         x, scale, shift = ctx.saved_tensors
         n_mid, n_out, slope = ctx.meta
-        B, Cc, n_in = x.shape
         g = _f32c(g)
-        U, D = cno_tables(x.device, n_in, n_mid), cno_tables(x.device, n_mid, n_out)
+        dev = x.device
+        D = cno_tables(dev, n_mid, n_out)
         gy = torch.empty_like(x)
-        check(lib.rpde_cno_act1d_bwd(ptr(x), ptr(scale), ptr(shift), ptr(g), ptr(gy), B, Cc, n_in, n_mid, n_out, slope,
-                                     U.fwd.span.data_ptr(), ptr(U.fwd.weights), U.fwd.taps,
-                                     U.bwd.span.data_ptr(), ptr(U.bwd.weights), U.bwd.taps,
-                                     D.bwd.span.data_ptr(), ptr(D.bwd.weights), D.bwd.taps, stream_ptr()), "cno_act1d_bwd")
+        if x.dim() == 3:
+            B, Cc, n_in = x.shape
+            U = cno_tables(dev, n_in, n_mid)
+            check(lib.rpde_cno_act1d_bwd(ptr(x), ptr(scale), ptr(shift), ptr(g), ptr(gy), B, Cc, n_in, n_mid, n_out, slope,
+                                         *_bands(U.fwd), *_bands(U.bwd), *_bands(D.bwd), stream_ptr()), "cno_act1d_bwd")
+        else:
+            B, Cc, h_in, w_in = x.shape
+            Uy, Ux = cno_tables(dev, h_in, n_mid), cno_tables(dev, w_in, n_mid)
+            check(lib.rpde_cno_act2d_bwd(ptr(x), ptr(scale), ptr(shift), ptr(g), ptr(gy), B, Cc, h_in, w_in, n_mid, n_mid, n_out,
+                                         n_out, slope, *_bands(Uy.fwd), *_bands(Ux.fwd), *_bands(Uy.bwd), *_bands(Ux.bwd),
+                                         *_bands(D.bwd), *_bands(D.bwd), stream_ptr()), "cno_act2d_bwd")
         return gy, None, None, None, None, None
 
 
@@ -183,45 +207,7 @@ def cno_act1d(x: torch.Tensor, in_size: int, out_size: int, scale: Optional[torc
         raise ValueError(f"cno_act1d: expected [B, C, n], got {tuple(x.shape)}")
     if (scale is None) != (shift is None):
         raise ValueError("cno_act1d: scale and shift come together")
-    return _CnoAct1d.apply(x, scale, shift, 2 * int(in_size), int(out_size), float(slope))
-
-
-def _bands(t: CnoBand):
-    return t.span.data_ptr(), ptr(t.weights), t.taps
-
-
-class _CnoAct2d(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, scale, shift, n_mid: int, n_out: int, slope: float):
-        lib = load()
-        x = _f32c(x)
-        B, Cc, h_in, w_in = x.shape
-        if scale is not None:
-            scale, shift = _f32c(scale.detach()), _f32c(shift.detach())
-        dev = x.device
-        Uy, Ux, D = cno_tables(dev, h_in, n_mid), cno_tables(dev, w_in, n_mid), cno_tables(dev, n_mid, n_out)
-        out = torch.empty(B, Cc, n_out, n_out, dtype=torch.float32, device=dev)
-        check(lib.rpde_cno_act2d_fwd(ptr(x), ptr(scale), ptr(shift), ptr(out), B, Cc, h_in, w_in, n_mid, n_mid, n_out, n_out,
-                                     slope, *_bands(Uy.fwd), *_bands(Ux.fwd), *_bands(D.fwd), *_bands(D.fwd), stream_ptr()),
-              "cno_act2d_fwd")
-        ctx.save_for_backward(x, scale, shift)
-        ctx.meta = (n_mid, n_out, slope)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        lib = load()
-        x, scale, shift = ctx.saved_tensors
-        n_mid, n_out, slope = ctx.meta
-        B, Cc, h_in, w_in = x.shape
-        g = _f32c(g)
-        dev = x.device
-        Uy, Ux, D = cno_tables(dev, h_in, n_mid), cno_tables(dev, w_in, n_mid), cno_tables(dev, n_mid, n_out)
-        gy = torch.empty_like(x)
-        check(lib.rpde_cno_act2d_bwd(ptr(x), ptr(scale), ptr(shift), ptr(g), ptr(gy), B, Cc, h_in, w_in, n_mid, n_mid, n_out,
-                                     n_out, slope, *_bands(Uy.fwd), *_bands(Ux.fwd), *_bands(Uy.bwd), *_bands(Ux.bwd),
-                                     *_bands(D.bwd), *_bands(D.bwd), stream_ptr()), "cno_act2d_bwd")
-        return gy, None, None, None, None, None
+    return _CnoAct.apply(x, scale, shift, 2 * int(in_size), int(out_size), float(slope))
 
 
 def cno_act2d(x: torch.Tensor, in_size: int, out_size: int, scale: Optional[torch.Tensor] = None,
@@ -233,7 +219,7 @@ def cno_act2d(x: torch.Tensor, in_size: int, out_size: int, scale: Optional[torc
         raise ValueError(f"cno_act2d: expected [B, C, H, W], got {tuple(x.shape)}")
     if (scale is None) != (shift is None):
         raise ValueError("cno_act2d: scale and shift come together")
-    return _CnoAct2d.apply(x, scale, shift, 2 * int(in_size), int(out_size), float(slope))
+    return _CnoAct.apply(x, scale, shift, 2 * int(in_size), int(out_size), float(slope))
 
 
 # ----------------------------------------------------------------------------
@@ -256,17 +242,26 @@ def _points(x: torch.Tensor) -> int:
     return int(x.shape[2]) if x.dim() == 3 else int(x.shape[2]) * int(x.shape[3])
 
 
-class _Conv1dK3(torch.autograd.Function):
+class _ConvK3(torch.autograd.Function):
+    """Conv(k = 3, padding = 1) of x's rank: [B, Cin, n] with w [Cout, Cin, 3] through rpde_cno_conv1d_k3_*,
+    [B, Cin, H, W] with w [Cout, Cin, 3, 3] through rpde_cno_conv2d_k3_*"""
+
     @staticmethod
     def forward(ctx, x, w, b):
         lib = load()
         x = _f32c(x)
-        B, Cin, n = x.shape
         Cout = w.shape[0]
-        wt = _f32c(w.detach()).permute(2, 0, 1).contiguous()          # tap-major [3, Cout, Cin]: a layout copy
         bias = None if b is None else _f32c(b.detach())
-        out = torch.empty(B, Cout, n, dtype=torch.float32, device=x.device)
-        check(lib.rpde_cno_conv1d_k3_fwd(ptr(x), ptr(wt), ptr(bias), ptr(out), B, Cin, Cout, n, stream_ptr()), "cno_conv1d_k3_fwd")
+        if x.dim() == 3:
+            B, Cin, n = x.shape
+            wt = _f32c(w.detach()).permute(2, 0, 1).contiguous()          # tap-major [3, Cout, Cin]: a layout copy
+            out = torch.empty(B, Cout, n, dtype=torch.float32, device=x.device)
+            check(lib.rpde_cno_conv1d_k3_fwd(ptr(x), ptr(wt), ptr(bias), ptr(out), B, Cin, Cout, n, stream_ptr()), "cno_conv1d_k3_fwd")
+        else:
+            B, Cin, H, W = x.shape
+            wt = _f32c(w.detach()).permute(2, 3, 0, 1).reshape(9, Cout, Cin).contiguous()    # tap-major: a layout copy
+            out = torch.empty(B, Cout, H, W, dtype=torch.float32, device=x.device)
+            check(lib.rpde_cno_conv2d_k3_fwd(ptr(x), ptr(wt), ptr(bias), ptr(out), B, Cin, Cout, H, W, stream_ptr()), "cno_conv2d_k3_fwd")
         ctx.save_for_backward(x, wt)
         ctx.has_bias = b is not None
         return out
@@ -275,18 +270,27 @@ class _Conv1dK3(torch.autograd.Function):
     def backward(ctx, g):
         lib = load()
         x, wt = ctx.saved_tensors
-        B, Cin, n = x.shape
-        Cout = wt.shape[1]
+        B, Cin, *sizes = x.shape
+        Cout, one_d = wt.shape[1], x.dim() == 3
         g = _f32c(g)
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
             gx = torch.empty_like(x)
-            check(lib.rpde_cno_conv1d_k3_bwd_data(ptr(g), ptr(wt), ptr(gx), B, Cin, Cout, n, stream_ptr()), "cno_conv1d_k3_bwd_data")
+            if one_d:
+                check(lib.rpde_cno_conv1d_k3_bwd_data(ptr(g), ptr(wt), ptr(gx), B, Cin, Cout, *sizes, stream_ptr()), "cno_conv1d_k3_bwd_data")
+            else:
+                check(lib.rpde_cno_conv2d_k3_bwd_data(ptr(g), ptr(wt), ptr(gx), B, Cin, Cout, *sizes, stream_ptr()), "cno_conv2d_k3_bwd_data")
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            gw = torch.empty(Cout, Cin, 3, dtype=torch.float32, device=x.device)
+            gw = torch.empty((Cout, Cin, 3) if one_d else (Cout, Cin, 3, 3), dtype=torch.float32, device=x.device)
             gb = torch.empty(Cout, dtype=torch.float32, device=x.device) if ctx.has_bias else None
-            check(lib.rpde_cno_conv1d_k3_bwd_weight(ptr(x), ptr(g), ptr(gw), ptr(gb), B, Cin, Cout, n, stream_ptr()),
-                  "cno_conv1d_k3_bwd_weight")
+            if one_d:                                  # one slice, no partial sums
+                check(lib.rpde_cno_conv1d_k3_bwd_weight(ptr(x), ptr(g), ptr(gw), ptr(gb), B, Cin, Cout, *sizes, stream_ptr()),
+                      "cno_conv1d_k3_bwd_weight")
+            else:
+                slices = lib.rpde_cno_conv2d_k3_bwd_weight_slices(B, Cin, Cout, *sizes)      # > 1: partial sums per slice
+                part = torch.empty(slices, 9 * Cout * Cin + Cout, dtype=torch.float32, device=x.device) if slices > 1 else None
+                check(lib.rpde_cno_conv2d_k3_bwd_weight(ptr(x), ptr(g), ptr(gw), ptr(gb), B, Cin, Cout, *sizes, ptr(part), slices,
+                                                        stream_ptr()), "cno_conv2d_k3_bwd_weight")
         return gx, gw, gb
 
 
@@ -295,43 +299,7 @@ def conv1d_k3(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor
     B, Cin, n = _bcn(x, "conv1d_k3")
     if weight.dim() != 3 or weight.shape[1] != Cin or weight.shape[2] != 3:
         raise ValueError(f"conv1d_k3: weight {tuple(weight.shape)} does not fit {Cin} input channels and 3 taps")
-    return _Conv1dK3.apply(x, weight, bias)
-
-
-class _Conv2dK3(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, w, b):
-        lib = load()
-        x = _f32c(x)
-        B, Cin, H, W = x.shape
-        Cout = w.shape[0]
-        wt = _f32c(w.detach()).permute(2, 3, 0, 1).reshape(9, Cout, Cin).contiguous()    # tap-major: a layout copy
-        bias = None if b is None else _f32c(b.detach())
-        out = torch.empty(B, Cout, H, W, dtype=torch.float32, device=x.device)
-        check(lib.rpde_cno_conv2d_k3_fwd(ptr(x), ptr(wt), ptr(bias), ptr(out), B, Cin, Cout, H, W, stream_ptr()), "cno_conv2d_k3_fwd")
-        ctx.save_for_backward(x, wt)
-        ctx.has_bias = b is not None
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        lib = load()
-        x, wt = ctx.saved_tensors
-        B, Cin, H, W = x.shape
-        Cout = wt.shape[1]
-        g = _f32c(g)
-        gx = gw = gb = None
-        if ctx.needs_input_grad[0]:
-            gx = torch.empty_like(x)
-            check(lib.rpde_cno_conv2d_k3_bwd_data(ptr(g), ptr(wt), ptr(gx), B, Cin, Cout, H, W, stream_ptr()), "cno_conv2d_k3_bwd_data")
-        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            gw = torch.empty(Cout, Cin, 3, 3, dtype=torch.float32, device=x.device)
-            gb = torch.empty(Cout, dtype=torch.float32, device=x.device) if ctx.has_bias else None
-            slices = lib.rpde_cno_conv2d_k3_bwd_weight_slices(B, Cin, Cout, H, W)      # > 1: partial sums per slice
-            part = torch.empty(slices, 9 * Cout * Cin + Cout, dtype=torch.float32, device=x.device) if slices > 1 else None
-            check(lib.rpde_cno_conv2d_k3_bwd_weight(ptr(x), ptr(g), ptr(gw), ptr(gb), B, Cin, Cout, H, W, ptr(part), slices,
-                                                    stream_ptr()), "cno_conv2d_k3_bwd_weight")
-        return gx, gw, gb
+    return _ConvK3.apply(x, weight, bias)
 
 
 def conv2d_k3(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -339,7 +307,7 @@ def conv2d_k3(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor
     Cin = _bchw(x, "conv2d_k3")[1]
     if weight.dim() != 4 or weight.shape[1] != Cin or tuple(weight.shape[2:]) != (3, 3):
         raise ValueError(f"conv2d_k3: weight {tuple(weight.shape)} does not fit {Cin} input channels and 3 x 3 taps")
-    return _Conv2dK3.apply(x, weight, bias)
+    return _ConvK3.apply(x, weight, bias)
 
 
 def _moments(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
@@ -373,9 +341,8 @@ class _BatchNorm(torch.autograd.Function):
         scale64 = g64 * invstd
         shift64 = beta.detach().double() - mean * scale64
         scale, shift = scale64.float(), shift64.float()
-        ctx.act_fn = _CnoAct1d if z.dim() == 3 else _CnoAct2d
         if act is not None:
-            out = ctx.act_fn.forward(ctx, z, scale, shift, *act)         # saves (z, scale, shift) and meta on ctx
+            out = _CnoAct.forward(ctx, z, scale, shift, *act)         # saves (z, scale, shift) and meta on ctx
         else:
             out = _affine(z, None, scale64, None, shift64, None if residual is None else _f32c(residual))
             ctx.save_for_backward(z, scale, shift)
@@ -390,7 +357,7 @@ class _BatchNorm(torch.autograd.Function):
         z, scale, shift = ctx.saved_tensors
         g64, mean, invstd, scale64 = ctx.stats
         g = _f32c(g)
-        gy = ctx.act_fn.backward(ctx, g)[0] if ctx.act is not None else g
+        gy = _CnoAct.backward(ctx, g)[0] if ctx.act is not None else g
         N = float(z.shape[0] * _points(z))
         s = _moments(gy, z)
         sum_gy, sum_gyz = s[:, 0], s[:, 2]

@@ -79,3 +79,54 @@ def test_generated_dataset_yamls_carry_their_training_resolution(name, res):
     from rpde.config import compose
     ds = compose(os.path.join(DROPIN, "conf"), "config", ["dataset=" + name]).dataset
     assert ds.cno_train_size == res == ds.original_res
+
+
+_EXPORTED = ("CNO_LReLu", "CNOBlock", "LiftProjectBlock", "ResidualBlock", "ResNet")
+
+
+@pytest.mark.parametrize("rank", [1, 2])
+def test_each_rank_exports_its_own_picklable_classes(rank):
+    """both ranks bind one shared module tree; every class still lives under its own module and name, so pickle (and
+    with it torch.save(model)) resolves it there"""
+    import importlib
+    import pickle
+    name = f"CNO{rank}d"
+    mod = importlib.import_module("models." + name)
+    for cls_name in _EXPORTED + (name,):
+        cls = getattr(mod, cls_name)
+        assert (cls.__module__, cls.__qualname__, cls.__name__) == ("models." + name, cls_name, cls_name)
+        assert pickle.loads(pickle.dumps(cls)) is cls
+
+
+def test_the_ranks_stay_distinct_classes():
+    import models.CNO1d
+    import models.CNO2d
+    assert models.CNO1d.CNOBlock is not models.CNO2d.CNOBlock
+    for cls_name in _EXPORTED:
+        a, b = getattr(models.CNO1d, cls_name), getattr(models.CNO2d, cls_name)
+        assert a is not b and not issubclass(a, b) and not issubclass(b, a)
+
+
+@pytest.mark.parametrize("rank", [1, 2])
+def test_a_model_owns_only_layers_and_classes_of_its_rank(rank):
+    import importlib
+    nn = torch.nn
+    mod = importlib.import_module(f"models.CNO{rank}d")
+    own = {1: (nn.Conv1d, nn.BatchNorm1d), 2: (nn.Conv2d, nn.BatchNorm2d)}
+    model = getattr(mod, f"CNO{rank}d")(in_dim=1, out_dim=1, size=16, N_layers=2, N_res=1, N_res_neck=1, channel_multiplier=4)
+    convs = [m for m in model.modules() if isinstance(m, nn.modules.conv._ConvNd)]
+    norms = [m for m in model.modules() if isinstance(m, nn.modules.batchnorm._BatchNorm)]
+    assert convs and norms
+    assert all(type(m) is own[rank][0] for m in convs) and all(type(m) is own[rank][1] for m in norms)
+    other = tuple(own[3 - rank])
+    assert not any(isinstance(m, other) for m in model.modules())
+    # every container in the tree is this module's class, none the other rank's or the shared base itself
+    for m in model.modules():
+        if type(m).__name__ in _EXPORTED:
+            assert type(m).__module__ == mod.__name__ and type(m) is getattr(mod, type(m).__name__)
+    # torch.save(model) pickles the classes by module and name
+    import io
+    buf = io.BytesIO()
+    torch.save(model, buf)
+    back = torch.load(io.BytesIO(buf.getvalue()), weights_only=False)
+    assert type(back) is type(model) and list(back.state_dict()) == list(model.state_dict())

@@ -170,3 +170,25 @@ def test_small_model_against_float64(gpu_device, use_bn, training):
     for k, v in new.items():
         if k.endswith("num_batches_tracked"):
             assert int(dict(model.named_buffers())[k]) == int(v)
+
+
+@pytest.mark.parametrize("B,Cin,Cout,n", [(2, 3, 5, 7), (2, 8, 8, 64)])
+def test_conv1d_k3_is_conv2d_k3_on_one_row(gpu_device, B, Cin, Cout, n):
+    """Conv1d(k = 3) runs the 2-D tap loop on a plane of one row: against conv2d_k3 on x[:, :, None] with the weight in
+    the middle tap row, y and dx are the same GEMMs in the same order, bit for bit.  dw and db come from the 2-D weight
+    gradient, which may split the points into slices that the 1-D one adds in one go: GRAD_TOL, not bits."""
+    from rpde import ops
+    x, w, b, g = _randn(B, Cin, n, seed=11), _randn(Cout, Cin, 3, seed=12) / (3 * Cin) ** 0.5, _randn(Cout, seed=13), _randn(B, Cout, n, seed=14)
+    w2 = torch.zeros(Cout, Cin, 3, 3)
+    w2[:, :, 1] = w
+    one = [t.to(gpu_device).requires_grad_(True) for t in (x, w, b)]
+    two = [t.to(gpu_device).requires_grad_(True) for t in (x[:, :, None], w2, b)]
+    y1 = ops.conv1d_k3(*one)
+    y1.backward(g.to(gpu_device))
+    y2 = ops.conv2d_k3(*two)
+    y2.backward(g[:, :, None].to(gpu_device))
+    e_dw, e_db = _rel(one[1].grad, two[1].grad[:, :, 1]), _rel(one[2].grad, two[2].grad)
+    print(f"conv1d_k3 vs conv2d_k3 at H = 1, B={B} Cin={Cin} Cout={Cout} n={n}: y equal {torch.equal(y1, y2[:, :, 0])}, "
+          f"dx equal {torch.equal(one[0].grad, two[0].grad[:, :, 0])}, dw {e_dw:.2e}, db {e_db:.2e}")
+    assert torch.equal(y1, y2[:, :, 0]) and torch.equal(one[0].grad, two[0].grad[:, :, 0])
+    assert e_dw <= GRAD_TOL and e_db <= GRAD_TOL
