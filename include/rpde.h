@@ -897,6 +897,33 @@ int rpde_cno_conv2d_k3_bwd_weight_slices(int B, int Cin, int Cout, int H, int W)
 int rpde_cno_conv2d_k3_bwd_weight(const float* x, const float* g, float* gw, float* gb, int B, int Cin, int Cout, int H, int W,
                                   float* partial, int partial_slices, void* stream);
 
+/* ---- U-Net (csrc/unet.hip; reference models/unet.py, the PDEBench U-Net): what its blocks need beyond conv k3, the
+ * BatchNorm kernels and conv1x1 above.  Channels first, contiguous fp32; ky = 1 is the 1-D form, a plane of one row
+ * (H = 1) with windows / taps of one row, ky = 2 the 2-D form.  No atomics, fixed summation order.
+ * tanh_pool_fwd: act = tanh(scale[c] z + shift[c]) on [B, C, H, W] (scale, shift [C], or both null) and, when `pooled`
+ *   is given, the maximum over the non-overlapping ky x 2 windows into pooled [B, C, H / ky, W / 2] in the same pass
+ *   (floor division: an odd last row or column belongs to no window; a pooled size of 0 is refused).  A NaN in a window
+ *   wins, as in torch's pooling.
+ * tanh_pool_bwd: gy = (g_act + scatter(g_pool)) (1 - act^2), the gradient with respect to scale z + shift; g_act or
+ *   g_pool may be null, not both.  scatter sends a window's gradient to the first maximum of act in the window's
+ *   row-major scan order, recomputed from act.
+ * upconv_*: ConvTranspose(kernel_size = 2, stride = 2) with torch's weight layout w [Cin][Cout][ky][2] and bias [Cout]
+ *   (or null): out [B, Cout, ky H, 2 W] from x [B, Cin, H, W]; _bwd_data gx from g; _bwd_weight gw (w's layout) and
+ *   gb [Cout] (or null), the points (b, y, x) split into slices whose partial sums go to `partial`
+ *   [slices][ky 2 Cin Cout + Cout] floats (rpde_unet_upconv_bwd_weight_slices gives the count; with one slice the
+ *   buffer is not used and may be null) and are added in slice order. */
+int rpde_unet_tanh_pool_fwd(const float* z, const float* scale, const float* shift, float* act, float* pooled, int B, int C,
+                            int H, int W, int ky, void* stream);
+int rpde_unet_tanh_pool_bwd(const float* act, const float* g_act, const float* g_pool, float* gy, int B, int C, int H, int W,
+                            int ky, void* stream);
+int rpde_unet_upconv_fwd(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int H, int W,
+                         int ky, void* stream);
+int rpde_unet_upconv_bwd_data(const float* g, const float* w, float* gx, int B, int Cin, int Cout, int H, int W, int ky,
+                              void* stream);
+int rpde_unet_upconv_bwd_weight_slices(int B, int Cin, int Cout, int H, int W);
+int rpde_unet_upconv_bwd_weight(const float* x, const float* g, float* gw, float* gb, int B, int Cin, int Cout, int H, int W,
+                                int ky, float* partial, int partial_slices, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

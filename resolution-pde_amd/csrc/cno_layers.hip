@@ -110,6 +110,14 @@ k_cno_conv2d_wsum(const float* __restrict__ part, float* __restrict__ gw, float*
   else if (gb) gb[e - n_gw] = v;
 }
 
+// (rpde_internal.h: the transposed convolution's weight gradient, unet.hip, adds its slices up the same way)
+int sum_slices(const float* part, float* gw, float* gb, long n_gw, long n_gb, int slices, hipStream_t st) {
+  hipLaunchKernelGGL(k_cno_conv2d_wsum, dim3((unsigned)((n_gw + n_gb + 255) / 256)), dim3(256), 0, st, part, gw, gb, n_gw, n_gb,
+                     slices);
+  RPDE_LAUNCH_CHECK();
+  return RPDE_OK;
+}
+
 // slices of the (b, y) rows the Conv2d weight gradient is split over
 static int c2w_slices(int B, int Cin, int Cout, int H, int W) {
   const long tiles = (long)((Cin + CNO_WG - 1) / CNO_WG) * ((Cout + CNO_WG - 1) / CNO_WG);
@@ -245,10 +253,7 @@ static int cno_conv_wgrad(const char* what, const float* x, const float* g, floa
   else hipLaunchKernelGGL(k_cno_conv_wgrad<3>, grid, dim3(256), 0, st, x, g, to_w, to_b, stride, BH, Cin, Cout, H, W, rows_per_slice);
   RPDE_LAUNCH_CHECK();
   if (slices == 1) return RPDE_OK;
-  hipLaunchKernelGGL(k_cno_conv2d_wsum, dim3((unsigned)((n_gw + n_gb + 255) / 256)), dim3(256), 0, st, partial, gw, gb, n_gw,
-                     n_gb, slices);
-  RPDE_LAUNCH_CHECK();
-  return RPDE_OK;
+  return sum_slices(partial, gw, gb, n_gw, n_gb, slices, st);
 }
 
 int rpde_cno_conv1d_k3_fwd(const float* x, const float* wt, const float* bias, float* out, int B, int Cin, int Cout, int n,

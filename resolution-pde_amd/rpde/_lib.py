@@ -207,6 +207,12 @@ _SIGNATURES = {
     "rpde_cno_conv2d_k3_bwd_data": (_I, [_P] * 3 + [_I] * 5 + [_P]),
     "rpde_cno_conv2d_k3_bwd_weight_slices": (_I, [_I] * 5),
     "rpde_cno_conv2d_k3_bwd_weight": (_I, [_P] * 4 + [_I] * 5 + [_P, _I, _P]),
+    "rpde_unet_tanh_pool_fwd": (_I, [_P] * 5 + [_I] * 5 + [_P]),
+    "rpde_unet_tanh_pool_bwd": (_I, [_P] * 4 + [_I] * 5 + [_P]),
+    "rpde_unet_upconv_fwd": (_I, [_P] * 4 + [_I] * 6 + [_P]),
+    "rpde_unet_upconv_bwd_data": (_I, [_P] * 3 + [_I] * 6 + [_P]),
+    "rpde_unet_upconv_bwd_weight_slices": (_I, [_I] * 5),
+    "rpde_unet_upconv_bwd_weight": (_I, [_P] * 4 + [_I] * 6 + [_P, _I, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

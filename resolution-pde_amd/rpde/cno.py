@@ -358,20 +358,27 @@ class _BatchNorm(torch.autograd.Function):
         g64, mean, invstd, scale64 = ctx.stats
         g = _f32c(g)
         gy = _CnoAct.backward(ctx, g)[0] if ctx.act is not None else g
-        N = float(z.shape[0] * _points(z))
-        s = _moments(gy, z)
-        sum_gy, sum_gyz = s[:, 0], s[:, 2]
-        dbeta = sum_gy
-        dgamma = invstd * (sum_gyz - mean * sum_gy)
-        if ctx.batch_stats:
-            # dz = (gamma / sigma) (gy - mean(gy) - zhat mean(gy zhat)),  zhat = (z - mean) / sigma
-            k = g64 * invstd
-            m1, m2 = sum_gy / N, dgamma / N
-            p0, p1, p2 = k, -k * m2 * invstd, -k * m1 + k * m2 * invstd * mean
-            dz = _affine(gy, z, p0, p1, p2)
-        else:
-            dz = _affine(gy, None, scale64, None, torch.zeros_like(scale64))
-        return dz, dgamma.float(), dbeta.float(), None, None, (g if ctx.has_residual else None), None, None
+        dz, dgamma, dbeta = _bn_backward(gy, z, g64, mean, invstd, scale64, ctx.batch_stats)
+        return dz, dgamma, dbeta, None, None, (g if ctx.has_residual else None), None, None
+
+
+def _bn_backward(gy, z, g64, mean, invstd, scale64, batch_stats: bool):
+    """(dz, dgamma, dbeta) of a BatchNorm from gy, the gradient with respect to its output: one moments pass over
+    (gy, z), the C coefficients in float64 by torch, one affine pass"""
+    N = float(z.shape[0] * _points(z))
+    s = _moments(gy, z)
+    sum_gy, sum_gyz = s[:, 0], s[:, 2]
+    dbeta = sum_gy
+    dgamma = invstd * (sum_gyz - mean * sum_gy)
+    if batch_stats:
+        # dz = (gamma / sigma) (gy - mean(gy) - zhat mean(gy zhat)),  zhat = (z - mean) / sigma
+        k = g64 * invstd
+        m1, m2 = sum_gy / N, dgamma / N
+        p0, p1, p2 = k, -k * m2 * invstd, -k * m1 + k * m2 * invstd * mean
+        dz = _affine(gy, z, p0, p1, p2)
+    else:
+        dz = _affine(gy, None, scale64, None, torch.zeros_like(scale64))
+    return dz, dgamma.float(), dbeta.float()
 
 
 def batchnorm1d(z: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, running_mean: Optional[torch.Tensor],
@@ -398,11 +405,10 @@ def batchnorm2d(z: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, runni
                       residual, act, slope)
 
 
-def _batchnorm(what, z, weight, bias, running_mean, running_var, num_batches_tracked, training, momentum, eps, residual, act,
-               slope):
+def _bn_statistics(z, running_mean, running_var, num_batches_tracked, training, momentum, eps):
+    """(mean, invstd, use_batch) of a BatchNorm on z, float64 [C]: the batch statistics with torch's running-buffer
+    update in training mode (or without buffers), the running statistics otherwise"""
     B, n = int(z.shape[0]), _points(z)
-    if residual is not None and act is not None:
-        raise ValueError(f"{what}: residual and act exclude each other")
     use_batch = training or running_mean is None
     if use_batch:
         if B * n <= 1:
@@ -420,7 +426,14 @@ def _batchnorm(what, z, weight, bias, running_mean, running_var, num_batches_tra
                     num_batches_tracked.add_(1)
     else:
         mean, var = running_mean.detach().double(), running_var.detach().double()
-    invstd = torch.rsqrt(var + eps)
+    return mean, torch.rsqrt(var + eps), use_batch
+
+
+def _batchnorm(what, z, weight, bias, running_mean, running_var, num_batches_tracked, training, momentum, eps, residual, act,
+               slope):
+    if residual is not None and act is not None:
+        raise ValueError(f"{what}: residual and act exclude each other")
+    mean, invstd, use_batch = _bn_statistics(z, running_mean, running_var, num_batches_tracked, training, momentum, eps)
     fn_act = None if act is None else (2 * int(act[0]), int(act[1]), float(slope))
     return _BatchNorm.apply(z, weight, bias, mean, invstd, residual, fn_act, use_batch)
 

@@ -1992,6 +1992,11 @@ def darcy2d_residual(pred, a, tables, affine=None, size_average: bool = True, re
 from .cno import (CnoBand, CnoTables, batchnorm1d, batchnorm2d, cno_act1d, cno_act2d, cno_dense,  # noqa: E402,F401
                   cno_resample_table, cno_tables, cno_transpose_band, conv1d_k3, conv2d_k3, skip_add)
 
+# ----------------------------------------------------------------------------
+# U-Net: norm -> tanh (-> MaxPool) in one pass, ConvTranspose(k = 2, stride = 2) (rpde/unet.py)
+# ----------------------------------------------------------------------------
+from .unet import groupnorm_tanh, norm_tanh, tanh_pool, upconv1d, upconv2d  # noqa: E402,F401
+
 
 def warm_plans(model, resolutions, dims: int, in_channels: int = 1, device="cuda") -> None:
     """Build every DFT plan (tables, adjoint tables, operand images: hipMalloc + one stream sync each,
