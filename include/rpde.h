@@ -164,6 +164,24 @@ int rpde_fspectral2d_prepare(const float* w_y, const float* w_x, int M, int N, i
 int rpde_fspectral2d_fwd_prepared(const float* x, const void* prep, float* out, int B, int M, int N, int C, int K,
                                   void* ws, size_t ws_bytes, void* stream);
 
+/* The first layer of FFNO2D, whose input is h0 = W_in u + b_in with a thin u [B,M,N,Cin], Cin <= 4: the spectral branch
+ * forward_fourier(h0) computed from u (the lifting commutes with the DFT and folds into the mode-mix weights).
+ * w_in [C,Cin], b_in [C] or NULL, w_y,w_x [C,C,K,2], out [B,M,N,C].  spec_u: rpde_lifted_fspectral2d_spec_elems floats,
+ * the spectra of u along both axes, all the backward needs besides the weights.  The backward returns the branch's
+ * gradients of W_in, b_in, w_y, w_x (each may be NULL) and none for u.  rpde_lifted_fspectral2d_ok: 1 where the path
+ * covers the shape (the fused 2-D path's shapes; RPDE_LIFTED_SPECTRAL=0 switches it off).  Workspace:
+ * rpde_fspectral2d_ws_bytes(B, M, N, C, K). */
+int rpde_lifted_fspectral2d_ok(int M, int N, int C, int Cin, int K);
+size_t rpde_lifted_fspectral2d_spec_elems(int B, int M, int N, int Cin, int K);
+int rpde_lifted_fspectral2d_fwd(const float* u, const float* w_in, const float* b_in, const float* w_y, const float* w_x,
+                                float* out, float* spec_u, int B, int M, int N, int C, int Cin, int K,
+                                void* ws, size_t ws_bytes, void* stream);
+int rpde_lifted_fspectral2d_bwd(const float* grad_out, const float* spec_u, const float* w_in, const float* b_in,
+                                const float* w_y, const float* w_x,
+                                float* grad_w_in, float* grad_b_in, float* grad_wy, float* grad_wx,
+                                int B, int M, int N, int C, int Cin, int K,
+                                void* ws, size_t ws_bytes, void* stream);
+
 /* ---- SpectralConv1d.forward  (models/spectral_convolution.py:38-55)
  * x [B,Cin,n] channels-first, w [Cin,Cout,K] complex64 (interleaved floats),
  * out [B,Cout,n]; norm 'backward'.  K > n/2+1 -> RPDE_ERR_MODES (quirk Q5).

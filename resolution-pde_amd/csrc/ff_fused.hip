@@ -526,19 +526,18 @@ __global__ __launch_bounds__(1024) void k_ff3_prep_bwd(const float* __restrict__
   for (int it = blockIdx.x * 1024 + tid; it < FF_WAVES * FF_FRAGS * 64; it += gridDim.x * 1024) {
     const int ln = it & 63, f = (it >> 6) % FF_FRAGS, w = it / (64 * FF_FRAGS);
     const int g = ln >> 4, li = ln & 15;
+    // slots 20..23 (once the W1^T fragments of a dx product inside the chain) stay unwritten: dx = du1 . W1 is formed
+    // by the streaming weight-gradient kernel (wgrad_h2.hip), k_ff3_bwd_h2 reads slots 0..19 only
+    if (f >= 20) continue;
     float x[8];
     if (f < 4) {                 // W3^T: hidden tile 2w + (f>>1), reduction over the 64 output features, half f&1
       const int hid = 16 * (2 * w + (f >> 1)) + li;
 #pragma unroll
       for (int j = 0; j < 8; ++j) x[j] = w3[(32 * (f & 1) + frag_perm(g, j)) * 256 + hid] * sc[2];
-    } else if (f < 20) {         // W2^T: hidden-1 tile 2w + ((f-4)>>3), reduction slice kappa of hidden-2
+    } else {                     // W2^T: hidden-1 tile 2w + ((f-4)>>3), reduction slice kappa of hidden-2
       const int hid1 = 16 * (2 * w + ((f - 4) >> 3)) + li, kap = (f - 4) & 7;
 #pragma unroll
       for (int j = 0; j < 8; ++j) x[j] = w2[(32 * kap + frag_perm(g, j)) * 256 + hid1] * sc[1];
-    } else {                     // W1^T: input-feature tile f-20, reduction slice kappa = w of hidden-1
-      const int feat = 16 * (f - 20) + li;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) x[j] = w1[(32 * w + frag_perm(g, j)) * 64 + feat] * sc[0];
     }
     h2_put_frag(img + ((long)(w * FF_FRAGS + f)) * 2048 + ln * 16, x);
   }

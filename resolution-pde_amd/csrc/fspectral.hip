@@ -17,6 +17,7 @@
 #include "pointwise.h"
 #include "fused_spectral.h"
 #include "mix1d.h"
+#include "lifted_spectral.h"
 
 namespace rpde {
 
@@ -397,7 +398,9 @@ size_t rpde_fspectral2d_ws_bytes(int B, int M, int N, int C, int K) {
   axes2d_dims(ay, ax, B, M, N, K);
   const size_t n = ws_max(axis_ws_bytes(ay, C), axis_ws_bytes(ax, C));   // the two axes run back to back and reuse the arena
   if (!fused2d_ok(M, N, C, ay.keff, ax.keff)) return n;
-  return ws_max(n, ws_max(ws_measure<Fused2dFwdWork>(ay, ax, C), ws_measure<Fused2dBwdWork>(ay, ax, C)));
+  // (the first layer's entries on the unlifted input, lifted_spectral.hip, carve from the same workspace)
+  return ws_max(ws_max(n, lifted2d_ws_bytes(B, M, N, K)),
+                ws_max(ws_measure<Fused2dFwdWork>(ay, ax, C), ws_measure<Fused2dBwdWork>(ay, ax, C)));
 }
 size_t rpde_fspectral2d_spec_elems(int B, int M, int N, int C, int K, int axis) {
   Axis ay, ax;

@@ -88,6 +88,18 @@ class FFNO2D(nn.Module):
             return mod(h)
         return ops.linear(h, mod.weight, mod.bias)
 
+    def _lifted_first_layer(self, u, w_in):
+        """Whether the first layer's spectral branch runs on the unlifted input u (ops.lifted_fspectral2d): the lifting
+        is a pointwise linear map, which commutes with the DFT, so it folds into the layer's mode-mix weights.  Needs
+        the full mode mix, a shape of the fused 2-D path, gradients enabled (evaluation keeps the path it can prepare
+        once, ops.frozen_weights) and an input that asks for none (the branch then feeds weights only);
+        RPDE_LIFTED_SPECTRAL=0 keeps the 64-channel path."""
+        if len(self.fourier_layers) == 0 or self.fourier_layers[0].mode != "full":
+            return False
+        if not isinstance(self.in_proj, nn.Linear) or u.requires_grad:
+            return False
+        return ops.lifted_fspectral2d_ok(u, w_in, self.n_modes)
+
     def forward(self, x):
         if self.use_grid:
             gx = gy = None
@@ -96,7 +108,15 @@ class FFNO2D(nn.Module):
             h = ops.concat_grid(x, 2, 0.0, 1.0, channels_last=True, gridx=gx, gridy=gy)
         else:
             h = ops.to_channels_last(x)
-        h = self._apply_linear(self.in_proj, h)
-        for layer in self.fourier_layers:
-            h, _ = layer(h, residual=h)
+        # the effective lifting weight once (weight norm's own autograd carries both uses back to weight_g / weight_v)
+        w_in = self.in_proj.effective_weight() if isinstance(self.in_proj, WNLinear) else self.in_proj.weight
+        u, h = h, ops.linear(h, w_in, self.in_proj.bias)
+        lifted = self._lifted_first_layer(u, w_in)
+        for i, layer in enumerate(self.fourier_layers):
+            if i == 0 and lifted:
+                fw = layer.fourier_weight
+                s = ops.lifted_fspectral2d(u, w_in, self.in_proj.bias, fw[0], fw[1], layer.n_modes)
+                h, _ = layer(h, residual=h, spectral=s)
+            else:
+                h, _ = layer(h, residual=h)
         return ops.to_channels_first(self._apply_linear(self.out_proj, h))

@@ -117,8 +117,12 @@ class FSpectralConv2d(nn.Module):
         return ops.fspectral2d(x, self.fourier_weight[0], self.fourier_weight[1], self.n_modes, self.mode,
                                with_skip=with_skip)
 
-    def forward(self, x, batch_dt=None, residual=None):
-        if self.mode != "no-fourier":
+    def forward(self, x, batch_dt=None, residual=None, spectral=None):
+        """``spectral``: forward_fourier(x) where the caller already has it (FFNO2D's first layer forms it from the
+        unlifted input, ops.lifted_fspectral2d)."""
+        if spectral is not None:
+            x = spectral
+        elif self.mode != "no-fourier":
             if residual is x and torch.is_grad_enabled() and x.requires_grad:
                 x, residual = self.forward_fourier(x, with_skip=True)
             else:

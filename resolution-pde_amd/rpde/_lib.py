@@ -98,6 +98,10 @@ _SIGNATURES = {
     "rpde_feedforward_bwd": (_I, [C.POINTER(FFParams), _P, _PP, _PP, _P, _P, _P, _PP, _PP, _P, _P, _L, _P, _Z, _P]),
     "rpde_feedforward_prepare": (_I, [C.POINTER(FFParams), _P, _Z, _P]),
     "rpde_feedforward_fwd_prepared": (_I, [C.POINTER(FFParams), _P, _P, _P, _L, _P, _Z, _P]),
+    "rpde_lifted_fspectral2d_ok": (_I, [_I, _I, _I, _I, _I]),
+    "rpde_lifted_fspectral2d_spec_elems": (_Z, [_I, _I, _I, _I, _I]),
+    "rpde_lifted_fspectral2d_fwd": (_I, [_P] * 7 + [_I] * 6 + [_P, _Z, _P]),
+    "rpde_lifted_fspectral2d_bwd": (_I, [_P] * 10 + [_I] * 6 + [_P, _Z, _P]),
     "rpde_fspectral2d_prep_bytes": (_Z, [_I, _I, _I, _I]),
     "rpde_fspectral2d_eval_ws_bytes": (_Z, [_I, _I, _I, _I, _I]),
     "rpde_fspectral2d_prepare": (_I, [_P, _P, _I, _I, _I, _I, _P, _Z, _P]),

@@ -208,6 +208,64 @@ def fspectral2d(x, wy, wx, modes: int, mode: str = "full", with_skip: bool = Fal
     return _FSpectral2d.apply(x, wy if full else None, wx if full else None, int(modes), MODE[mode], bool(with_skip))
 
 
+class _LiftedFSpectral2d(torch.autograd.Function):
+    """forward_fourier(u W_in^T + b_in) from the thin u itself (csrc/lifted_spectral.hip): saves the spectra of u only
+    and returns gradients for W_in, b_in and the two mode-mix weights -- none for u."""
+
+    @staticmethod
+    def forward(ctx, u, w_in, b_in, wy, wx, modes: int):
+        lib = load()
+        u, w_in, wyf, wxf = _f32c(u), _f32c(w_in), _f32c(wy), _f32c(wx)
+        b_in = _f32c(b_in) if b_in is not None else None
+        B, M, N, Cin = u.shape
+        Cc = w_in.shape[0]
+        out = torch.empty(B, M, N, Cc, dtype=torch.float32, device=u.device)
+        spec = torch.empty(lib.rpde_lifted_fspectral2d_spec_elems(B, M, N, Cin, modes), dtype=torch.float32, device=u.device)
+        run("lifted_fspectral2d_fwd", lib.rpde_fspectral2d_ws_bytes(B, M, N, Cc, modes), u.device, ptr(u), ptr(w_in),
+            ptr(b_in), ptr(wyf), ptr(wxf), ptr(out), ptr(spec), B, M, N, Cc, Cin, modes)
+        ctx.save_for_backward(spec, w_in, wyf, wxf, *(() if b_in is None else (b_in,)))
+        ctx.dims = (B, M, N, Cc, Cin, modes)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = load()
+        B, M, N, Cc, Cin, modes = ctx.dims
+        spec, w_in, wyf, wxf, *rest = ctx.saved_tensors
+        b_in = rest[0] if rest else None
+        g = _f32c(g)
+        need_in, need_b = ctx.needs_input_grad[1], b_in is not None and ctx.needs_input_grad[2]
+        need_w = ctx.needs_input_grad[3] or ctx.needs_input_grad[4]
+        gw_in = torch.empty_like(w_in) if need_in else None
+        gb_in = torch.empty_like(b_in) if need_b else None
+        gwy = torch.empty_like(wyf) if need_w else None
+        gwx = torch.empty_like(wxf) if need_w else None
+        run("lifted_fspectral2d_bwd", lib.rpde_fspectral2d_ws_bytes(B, M, N, Cc, modes), g.device, ptr(g), ptr(spec),
+            ptr(w_in), ptr(b_in), ptr(wyf), ptr(wxf), ptr(gw_in), ptr(gb_in), ptr(gwy), ptr(gwx), B, M, N, Cc, Cin, modes)
+        return None, gw_in, gb_in, gwy, gwx, None
+
+
+def lifted_fspectral2d_ok(u, w_in, modes: int) -> bool:
+    """whether lifted_fspectral2d covers forward_fourier(linear(u, w_in, .)): a shape of the fused 2-D path, at most
+    four input channels, fp32 on the GPU, and RPDE_LIFTED_SPECTRAL not 0.  Under no_grad the 64-channel path stays
+    (fspectral2d): inside frozen_weights() its mode-mix fragments are built once per scope where W' would be rebuilt on
+    every call, and evaluation is bit-identical with and without that scope"""
+    if not (u.is_cuda and u.dim() == 4 and u.dtype == torch.float32 and w_in.dtype == torch.float32):
+        return False
+    if not torch.is_grad_enabled():
+        return False
+    _, M, N, Cin = u.shape
+    return bool(load().rpde_lifted_fspectral2d_ok(M, N, w_in.shape[0], Cin, int(modes)))
+
+
+def lifted_fspectral2d(u, w_in, b_in, wy, wx, modes: int):
+    """FSpectralConv2d.forward_fourier (mode 'full') of h0 = linear(u, w_in, b_in), u [B,M,N,Cin <= 4] without a
+    gradient of its own, w_in [C,Cin] the EFFECTIVE lifting weight: the lifting commutes with the DFT and folds into the
+    mode-mix weights, so the spectral branch runs on Cin channels instead of C, and its backward needs neither an
+    adjoint mix nor an adjoint synthesis (only weights receive gradients)."""
+    return _LiftedFSpectral2d.apply(u, w_in, b_in, wy, wx, int(modes))
+
+
 # ----------------------------------------------------------------------------
 # dropout masks under a captured hipGraph: a replay repeats its launch arguments, so the seed the FeedForward draws on
 # the host would freeze one mask for ever.  Every dropout kernel therefore also mixes a DEVICE counter into its seed
