@@ -11,6 +11,7 @@
 #include "pointwise.h"
 #include "gemm_kernel.h"
 #include "ff_fused.h"
+#include "ff_bwd_split.h"
 #include "wgrad_h2.h"
 #include "thin_linear.h"
 #include "conv_small.h"
@@ -302,12 +303,24 @@ int rpde_feedforward_bwd(const rpde_ff_params* p, const float* x, const float* c
     float *dz3 = wk.dz3, *part = wk.part;
     void* fimg = wk.fimg;
     int grid = 0;
-    RPDE_TRY(ff3_fused_bwd_launch(p, recompute ? hs : ds, recompute, z_last, grad_out, dz3, buf0, buf1, nullptr, part, &grid, P,
-                                  fimg, st));
     // first layer: du1 feeds both the data gradient and the weight gradient -- one kernel reads it once for both
     const bool both = grad_x && grad_weights && wgrad_h2_dgrad_ok(P, hid, p->dim);
+    // ... and with the stored derivatives that kernel forms du1 itself from du2 (ff_bwd_split.hip): the chain stops at
+    // du2, du1 stays on chip (of its buffer only the first P floats are used, for the per-point bounds of |dz3|)
+    const bool split = both && !recompute && ff_bwd_split_ok(P, hid, p->dim);
+    if (split) {
+      FoldJobs folds;
+      RPDE_TRY(ff_bwd_split_launch(p, ds, z_last, grad_out, x, dz3, buf0, buf1, grad_x, slabs_l[0], grad_weights[0], part,
+                                   &grid, P, fimg, st, &folds));
+      RPDE_TRY(linear_wgrad_impl(hs[1], dz3, grad_weights[2], nullptr, P, hid, p->dim, slabs_l[2], small, st, act_h, &folds));
+      RPDE_TRY(linear_wgrad_impl(hs[0], buf0, grad_weights[1], nullptr, P, hid, hid, slabs_l[1], small, st, act_h, &folds));
+      RPDE_TRY(fold_jobs(folds, st));
+    } else {
+      RPDE_TRY(ff3_fused_bwd_launch(p, recompute ? hs : ds, recompute, z_last, grad_out, dz3, buf0, buf1, nullptr, part, &grid, P,
+                                    fimg, st));
+    }
     if (grad_x && !both) RPDE_TRY(linear_dgrad_impl(buf1, p->weights[0], grad_x, P, p->dim, hid, nullptr, nullptr, st, wt));
-    if (grad_weights) {
+    if (grad_weights && !split) {
       // each weight gradient in its own slab region, the three folds in one launch
       FoldJobs folds;
       RPDE_TRY(linear_wgrad_impl(hs[1], dz3, grad_weights[2], nullptr, P, hid, p->dim, slabs_l[2], small, st, act_h, &folds));

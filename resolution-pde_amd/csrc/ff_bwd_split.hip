@@ -1,0 +1,612 @@
+// Backward of the fused FeedForward 64 -> 256 -> 256 -> 64 with the data-gradient chain of ff_fused.hip cut at du2:
+//
+//   k_ffs_adjoint   g, z3, d2  ->  dz3, du2 = (W3^T dz3) * d2            (and db2, db3, dgamma, dbeta)
+//   k_ffs_layer1    du2, d1, x ->  gx = du1 . W1,  gW1 = du1^T . x        (and db1),  du1 = (W2^T du2) * d1
+//
+// du1 (1 KB per point) is formed and consumed inside one workgroup and never goes to HBM: k_ff3_bwd_h2 wrote it and
+// k_wgrad_h2<.., DG> read it back.  The two upper weight gradients run on dz3 and du2 as before.
+//
+// Both kernels keep the chain's form -- transposed products, wave w owns hidden rows 32w .. 32w+31 of W3^T / W2^T as
+// register fragments (the image of k_ff3_prep_bwd), one scale per point derived from the bound of its |dz3| -- and its
+// tile order (tile = workgroup, workgroup + grid, ..), and they sum the small gradients in the chain's order, so dz3,
+// du2, du1 and the five small gradients have the chain's bits.  Everything else is the plain style of wgrad_h2.hip:
+// loads through registers one tile ahead, waits left to the compiler, lds_barrier().
+//
+// k_ffs_layer1 then hands du1 to the first layer's consumer of wgrad_h2.hip through LDS: each wave writes its 32
+// channels of the tile as half a [hi | lo][32 points][64 channels] panel (stage_off layout) under a running exponent of
+// its own (the maximum so far, as k_wgrad_h2 keeps per panel), x is staged the same way under one running exponent the
+// eight waves agree on, and the consumer is k_wgrad_h2<4, 1, 4, 2, 4, 2, false, true>'s: gW1 += du1^T . x by transposing
+// reads, gx = du1 . W1 against ready-made W1 fragments in LDS.
+#include "ff_bwd_split.h"
+#include "ff_fused.h"
+#include "h2.h"
+#include "pointwise.h"
+#include "wgrad_h2.h"
+
+namespace rpde {
+
+constexpr int FS_WAVES = 8;
+constexpr int FS_MAX_GRID = 256;               // the slab region of the first layer (wgrad_h2_slab_floats) holds 256
+struct FsA {
+  const float* g; const float* z3; const float* d2;
+  float* dz3; float* du2; float* dzb;
+  const char* wimg; const float* consts;
+  const float* gamma; const float* beta;
+  float* part;
+  long P; int layer_norm; float eps; int post_act;
+  DropCfg drop2;
+  int ntiles;
+};
+
+constexpr int FA_DZBUF = 0;                        // [2 parity][2 blk][2 ks][hi|lo][1 KB]: dz3 as B fragments   = 16 KB
+constexpr int FA_VEC = FA_DZBUF + 16384;           // gamma[64] beta[64]
+constexpr int FA_ACC = FA_VEC + 512;               // db2[256] | db3, dgamma, dbeta: [3][8 wave][64]             =  7 KB
+constexpr int FA_INFO = FA_ACC + 7168;             // [2 parity][32 points] bound of |dz3|
+constexpr int FA_LDS = FA_INFO + 256;
+
+__global__ __launch_bounds__(64 * FS_WAVES, 2) void k_ffs_adjoint(const FsA A0) {
+  __shared__ __attribute__((aligned(16))) char smem[FA_LDS];
+  FsA A = A0;
+  A.drop2 = drop_resolve(A0.drop2);
+  const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, g = l >> 4, li = l & 15;
+  f16x8 w3h[2][2], w3l[2][2];
+  {
+    const char* base = A.wimg + (long)w * FF3_WAVE_IMG + l * 16;
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+      w3h[f >> 1][f & 1] = *reinterpret_cast<const f16x8*>(base + f * 2048);
+      w3l[f >> 1][f & 1] = *reinterpret_cast<const f16x8*>(base + f * 2048 + 1024);
+    }
+    float* vecw = reinterpret_cast<float*>(smem + FA_VEC);
+    float* accw = reinterpret_cast<float*>(smem + FA_ACC);
+    for (int i = tid; i < 128; i += 64 * FS_WAVES) vecw[i] = i < 64 ? (A.gamma ? A.gamma[i] : 1.f) : (A.beta ? A.beta[i - 64] : 0.f);
+    for (int i = tid; i < 1792; i += 64 * FS_WAVES) accw[i] = 0.f;
+  }
+  const float* const vec = reinterpret_cast<const float*>(smem + FA_VEC);
+  float* const acc_db2 = reinterpret_cast<float*>(smem + FA_ACC);
+  float* const acc_db3 = acc_db2 + 256;        // [8 wave][64]
+  float* const acc_dg = acc_db2 + 768;         // [8 wave][64]
+  float* const acc_dbt = acc_db2 + 1280;       // [8 wave][64]
+  float* const info = reinterpret_cast<float*>(smem + FA_INFO);
+  const float winv3 = A.consts[2];
+  // the last-layer adjoint works on one POINT per 16-lane row (point 4 w + q3 of the tile), lane li on features 4 li ..
+  const int q3 = l >> 4, feat = 4 * li;
+
+  float4 g4n = make_float4(0.f, 0.f, 0.f, 0.f), z4n = g4n, d2n[4];
+  auto issue = [&](int tile) {
+    const long p = min((long)tile * 32 + 4 * w + q3, A.P - 1);
+    g4n = *reinterpret_cast<const float4*>(A.g + p * 64 + feat);
+    z4n = *reinterpret_cast<const float4*>(A.z3 + p * 64 + feat);
+    // d2 of the wave's hidden rows, in accumulator layout: point 16 blk + li, rows 16 (2 w + t) + 4 g ..
+#pragma unroll
+    for (int blk = 0; blk < 2; ++blk)
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+        d2n[blk * 2 + t] = *reinterpret_cast<const float4*>(A.d2 + min((long)tile * 32 + 16 * blk + li, A.P - 1) * 256 + 16 * (2 * w + t) + 4 * g);
+  };
+#pragma unroll
+  for (int i = 0; i < 4; ++i) d2n[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  if ((int)blockIdx.x < A.ntiles) issue(blockIdx.x);
+  lds_barrier();                               // vectors and zeroed accumulators are in LDS
+
+  int par = 0;
+  for (int tile = blockIdx.x; tile < A.ntiles; tile += gridDim.x, par ^= 1) {
+    const int next_tile = tile + gridDim.x;
+    const long p0 = (long)tile * 32;
+    const int ptl = 4 * w + q3;
+    const long pt3 = p0 + ptl;
+    const bool live3 = pt3 < A.P;
+    const long off3 = min(pt3, A.P - 1) * 64 + feat;
+    const float4 g4 = g4n, z4 = z4n;
+    float4 dq[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) dq[i] = d2n[i];
+    if (next_tile < A.ntiles) issue(next_tile);
+
+    // ---- last-layer adjoint: dropout, LayerNorm, post-activation (k_ff3_bwd_h2's, expression for expression) ----
+    float s4[4] = {1.f, 1.f, 1.f, 1.f};
+    if (A.drop2.on()) drop_scale4(A.drop2, (uint64_t)(pt3 * 64 + feat), s4);
+    const float tz[4] = {z4.x * s4[0], z4.y * s4[1], z4.z * s4[2], z4.w * s4[3]};
+    float gy[4] = {g4.x, g4.y, g4.z, g4.w};
+    if (!live3) { gy[0] = gy[1] = gy[2] = gy[3] = 0.f; }
+    float dz[4], dzb;
+    float dgm[4] = {0.f, 0.f, 0.f, 0.f}, dbt[4] = {0.f, 0.f, 0.f, 0.f};
+    if (A.layer_norm) {
+      const float mean = row_all16<false>((tz[0] + tz[1]) + (tz[2] + tz[3])) * (1.f / 64.f);
+      const float m2 = row_all16<false>((tz[0] - mean) * (tz[0] - mean) + (tz[1] - mean) * (tz[1] - mean) +
+                                        (tz[2] - mean) * (tz[2] - mean) + (tz[3] - mean) * (tz[3] - mean));
+      const float rstd = rsqrtf(m2 * (1.f / 64.f) + A.eps);
+      const float4 gm = *reinterpret_cast<const float4*>(vec + feat);
+      const float4 bt = *reinterpret_cast<const float4*>(vec + 64 + feat);
+      const float gmv[4] = {gm.x, gm.y, gm.z, gm.w}, btv[4] = {bt.x, bt.y, bt.z, bt.w};
+      float xh[4], dxh[4], s1 = 0.f, s2 = 0.f, am = 0.f;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        xh[k] = (tz[k] - mean) * rstd;
+        float dy = gy[k];
+        if (A.post_act) dy *= dact_f(A.post_act, xh[k] * gmv[k] + btv[k]);
+        dgm[k] = dy * xh[k];
+        dbt[k] = dy;
+        dxh[k] = dy * gmv[k];
+        s1 += dxh[k];
+        s2 += dxh[k] * xh[k];
+        am = fmaxf(am, fabsf(dxh[k]));
+      }
+      const float S1 = row_all16<false>(s1) * (1.f / 64.f), S2 = row_all16<false>(s2) * (1.f / 64.f);
+      const float AM = row_all16<true>(am);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) dz[k] = rstd * (dxh[k] - S1 - xh[k] * S2) * s4[k];
+      // bound of this POINT's |dz3|: |xhat| <= sqrt(63) < 8
+      dzb = rstd * (AM + fabsf(S1) + 8.f * fabsf(S2)) * A.drop2.scale;
+    } else {
+      float am = 0.f;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) { dz[k] = gy[k] * dact_f(A.post_act, tz[k]) * s4[k]; am = fmaxf(am, fabsf(dz[k])); }
+      dzb = row_all16<true>(am);
+    }
+    if (live3) *reinterpret_cast<float4*>(A.dz3 + off3) = make_float4(dz[0], dz[1], dz[2], dz[3]);
+    // bias / gamma / beta gradients: sum over the wave's four points, one writer per (wave, feature)
+    {
+      float b[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        b[k] = live3 ? dz[k] : 0.f;
+        b[k] += lane_xor16(b[k]); b[k] += lane_xor32(b[k]);
+        if (A.layer_norm) {
+          dgm[k] += lane_xor16(dgm[k]); dgm[k] += lane_xor32(dgm[k]);
+          dbt[k] += lane_xor16(dbt[k]); dbt[k] += lane_xor32(dbt[k]);
+        }
+      }
+      if (q3 == 0) {
+        float4* a3 = reinterpret_cast<float4*>(acc_db3 + w * 64 + feat);
+        float4 v3 = *a3;
+        v3.x += b[0]; v3.y += b[1]; v3.z += b[2]; v3.w += b[3];
+        *a3 = v3;
+        if (A.layer_norm) {
+          float4* ag = reinterpret_cast<float4*>(acc_dg + w * 64 + feat);
+          float4* ab = reinterpret_cast<float4*>(acc_dbt + w * 64 + feat);
+          float4 vg = *ag, vb = *ab;
+          vg.x += dgm[0]; vg.y += dgm[1]; vg.z += dgm[2]; vg.w += dgm[3];
+          vb.x += dbt[0]; vb.y += dbt[1]; vb.z += dbt[2]; vb.w += dbt[3];
+          *ag = vg;
+          *ab = vb;
+        }
+      }
+    }
+    // dz3 -> B fragments, one scale per point (its bound); the bank-spreading unit permutation of k_ff3_bwd_h2
+    {
+      float sdz, sdzi;
+      h2_scale(dzb, 0, sdz, sdzi);
+      uint2 hi, lo;
+      h2_split4(dz[0] * sdz, dz[1] * sdz, dz[2] * sdz, dz[3] * sdz, hi, lo);
+      const int ksz = li >> 3, cz = li & 3;
+      char* dst = smem + FA_DZBUF + par * 8192 + (((ptl >> 4) * 2 + ksz) * 2) * 1024 + (cz * 16 + ((ptl & 15) ^ cz ^ (4 * ksz))) * 16 +
+                  ((li >> 2) & 1) * 8;
+      *reinterpret_cast<uint2*>(dst) = hi;
+      *reinterpret_cast<uint2*>(dst + 1024) = lo;
+      if (li == 0) {
+        info[par * 32 + ptl] = dzb;
+        if (live3) A.dzb[pt3] = dzb;             // k_ffs_layer1 scales du2 by the bound derived from it
+      }
+    }
+    // (the fragments and bounds are double-buffered by tile parity: a wave writes those of tile i + 2 only behind the
+    //  barrier of tile i + 1, which every wave reaches after its reads of tile i -- one barrier per tile)
+    lds_barrier();
+
+    // ---- du2 = (W3^T dz3) * d2: this wave's 32 hidden rows ----
+    float bsum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int blk = 0; blk < 2; ++blk) {
+      const int zu = (l & 48) | ((l & 15) ^ (l >> 4));             // this lane's unit in the ks = 0 pieces; ks = 1: ^ 4
+      const char* zb = smem + FA_DZBUF + par * 8192 + (blk * 2) * 2048;
+      const f16x8 zh0 = *reinterpret_cast<const f16x8*>(zb + zu * 16), zl0 = *reinterpret_cast<const f16x8*>(zb + 1024 + zu * 16);
+      const f16x8 zh1 = *reinterpret_cast<const f16x8*>(zb + 2048 + (zu ^ 4) * 16), zl1 = *reinterpret_cast<const f16x8*>(zb + 3072 + (zu ^ 4) * 16);
+      const long pt = p0 + 16 * blk + li;
+      float sz, inv_a;
+      h2_scale(info[par * 32 + blk * 16 + li], 0, sz, inv_a);
+      inv_a *= winv3;
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        f32x4v acc = {0.f, 0.f, 0.f, 0.f};
+        acc = h2_mfma32(w3h[t][0], w3l[t][0], zh0, zl0, acc);
+        acc = h2_mfma32(w3h[t][1], w3l[t][1], zh1, zl1, acc);
+        const int hid = 16 * (2 * w + t) + 4 * g;
+        const float4 d = dq[blk * 2 + t];
+        float u[4] = {acc[0] * inv_a * d.x, acc[1] * inv_a * d.y, acc[2] * inv_a * d.z, acc[3] * inv_a * d.w};
+        // (the sum below adds the ROUNDED products, as k_ff3_bwd_h2's does: left alone, the compiler folds the last
+        //  multiplication into the addition here and db2 comes out with other bits than the chain's)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) pin(u[r]);
+        if (pt < A.P) {
+          *reinterpret_cast<float4*>(A.du2 + pt * 256 + hid) = make_float4(u[0], u[1], u[2], u[3]);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) bsum[4 * t + r] += u[r];
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) bsum[i] = row_sum15(bsum[i]);
+    if (li == 15) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) acc_db2[16 * (2 * w + (i >> 2)) + 4 * g + (i & 3)] += bsum[i];
+    }
+  }
+  // ---- per-workgroup sums out: db2 | db3 | dgamma | dbeta of FF3_PART (db1 comes from k_ffs_layer1) ----
+  lds_barrier();
+  {
+    float* part = A.part + (long)blockIdx.x * FF3_PART;
+    for (int i = 256 + tid; i < FF3_PART; i += 64 * FS_WAVES) {
+      float v;
+      if (i < 512) v = acc_db2[i - 256];
+      else {                                                         // the eight waves' sums, in order
+        const float* a8 = acc_db3 + ((i - 512) >> 6) * 512 + ((i - 512) & 63);
+        v = 0.f;
+#pragma unroll
+        for (int ww = 0; ww < FS_WAVES; ++ww) v += a8[ww * 64];
+      }
+      part[i] = v;
+    }
+  }
+}
+
+// ====================================================================================================================
+struct FsB {
+  const float* du2; const float* d1; const float* x; const float* dzb; const float* w1;
+  float* gx; float* slabs; float* part;
+  const char* wimg; const float* consts;
+  long P; float dmax; int ntiles;
+};
+
+constexpr int FL_PANEL = 8192;                     // [hi | lo][32 points][64 channels] f16
+constexpr int FL_DUBUF = 0;                        // [2 blk][8 kappa][hi|lo][1 KB]: du2 as B fragments           = 32 KB
+constexpr int FL_PAN = FL_DUBUF + 32768;           // four du1 panels                                              = 32 KB
+constexpr int FL_X = FL_PAN + 4 * FL_PANEL;        // the x panel                                                  =  8 KB
+constexpr int FL_W1 = FL_X + FL_PANEL;             // [8 k-step][4 n-tile][hi | lo][64 lanes][16 B]: W1            = 64 KB
+constexpr int FL_LDS = FL_W1 + 65536;
+
+__global__ __launch_bounds__(64 * FS_WAVES, 2) void k_ffs_layer1(const FsB A) {
+  __shared__ __attribute__((aligned(16))) char smem[FL_LDS];
+  __shared__ int einfo[FS_WAVES];                 // running exponent of each wave's half panel of du1
+  __shared__ float xmax[FS_WAVES];
+  __shared__ float wmax[FS_WAVES];
+  __shared__ float acc_db1[256];
+  const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, g = l >> 4, li = l & 15;
+  // ---- W2^T rows 32w .. 32w+31 -> registers; W1 -> LDS as B fragments (k = hidden channel, n = input channel) ----
+  f16x8 w2h[2][8], w2l[2][8];
+  {
+    const char* base = A.wimg + (long)w * FF3_WAVE_IMG + l * 16;
+#pragma unroll
+    for (int f = 0; f < 16; ++f) {
+      w2h[f >> 3][f & 7] = *reinterpret_cast<const f16x8*>(base + (4 + f) * 2048);
+      w2l[f >> 3][f & 7] = *reinterpret_cast<const f16x8*>(base + (4 + f) * 2048 + 1024);
+    }
+  }
+  if (tid < 256) acc_db1[tid] = 0.f;
+  char* const wfrag = smem + FL_W1;
+  float w_inv = 1.f;
+  {
+    constexpr int NF = 8 * 4 * 64 / (64 * FS_WAVES);          // (k-step, n-tile, lane) triples per thread
+    float wv[NF][8];
+    float m = 0.f;
+#pragma unroll
+    for (int r = 0; r < NF; ++r) {
+      const int c = tid + r * 64 * FS_WAVES, fl = c & 63, nt = (c >> 6) & 3, ks = c >> 8;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        wv[r][j] = A.w1[(long)(32 * ks + 8 * (fl >> 4) + j) * 64 + 16 * nt + (fl & 15)];
+        m = fmaxf(m, fabsf(wv[r][j]));
+      }
+    }
+    m = wave_max(m);
+    if (l == 0) wmax[w] = m;
+    __syncthreads();
+    m = 0.f;
+#pragma unroll
+    for (int i = 0; i < FS_WAVES; ++i) m = fmaxf(m, wmax[i]);
+    float w_scale;
+    h2_scale(m, 0, w_scale, w_inv);
+#pragma unroll
+    for (int r = 0; r < NF; ++r) {
+      const int c = tid + r * 64 * FS_WAVES, fl = c & 63, nt = (c >> 6) & 3, ks = c >> 8;
+      uint2 h0, l0, h1, l1;
+      h2_split4(wv[r][0] * w_scale, wv[r][1] * w_scale, wv[r][2] * w_scale, wv[r][3] * w_scale, h0, l0);
+      h2_split4(wv[r][4] * w_scale, wv[r][5] * w_scale, wv[r][6] * w_scale, wv[r][7] * w_scale, h1, l1);
+      char* d = wfrag + (ks * 4 + nt) * 2048 + fl * 16;
+      *reinterpret_cast<uint4*>(d) = make_uint4(h0.x, h0.y, h1.x, h1.y);
+      *reinterpret_cast<uint4*>(d + 1024) = make_uint4(l0.x, l0.y, l1.x, l1.y);
+    }
+  }
+  const float winv2 = A.consts[1], c3t = A.consts[3];
+
+  // ---- this thread's loads of a tile: du2 and d1 in accumulator layout (point 16 blk + li, rows 16 (2 w + t) + 4 g ..),
+  // the bounds of its two points, and one float4 of the x panel (row tid / 16, channels 4 (tid & 15) ..) ----
+  const int xrow = tid >> 4, xc = tid & 15;
+  float4 du2r[4], d1r[4], xr;
+  float bzr[2];
+  // (addresses as a per-tile uniform base plus a 32-bit lane offset: a 64-bit pointer per load spilled)
+  const unsigned cb = 32 * w + 4 * g;
+  auto load_du2 = [&](int tile) {
+    const long t0 = (long)tile * 32;
+    const int rmax = (int)min(31L, A.P - 1 - t0);           // rows past P read the last point's (and are not used)
+    const float* __restrict__ src = A.du2 + t0 * 256;
+    const float* __restrict__ bz = A.dzb + t0;
+#pragma unroll
+    for (int blk = 0; blk < 2; ++blk) {
+      const unsigned r = (unsigned)min(16 * blk + li, rmax);
+      bzr[blk] = bz[r];
+#pragma unroll
+      for (int t = 0; t < 2; ++t) du2r[blk * 2 + t] = *reinterpret_cast<const float4*>(src + (r * 256u + cb + 16u * t));
+    }
+  };
+  auto load_d1 = [&](int tile) {
+    const long t0 = (long)tile * 32;
+    const int rmax = (int)min(31L, A.P - 1 - t0);
+    const float* __restrict__ src = A.d1 + t0 * 256;
+#pragma unroll
+    for (int blk = 0; blk < 2; ++blk) {
+      const unsigned r = (unsigned)min(16 * blk + li, rmax);
+#pragma unroll
+      for (int t = 0; t < 2; ++t) d1r[blk * 2 + t] = *reinterpret_cast<const float4*>(src + (r * 256u + cb + 16u * t));
+    }
+  };
+  auto load_x = [&](int tile) {
+    const long t0 = (long)tile * 32;
+    const float* __restrict__ src = A.x + t0 * 64;
+    xr = t0 + xrow < A.P ? *reinterpret_cast<const float4*>(src + (unsigned)(xrow * 64 + 4 * xc)) : make_float4(0.f, 0.f, 0.f, 0.f);
+  };
+
+  // ---- consumer role (k_wgrad_h2<4, 1, 4, 2, 4, 2, false, true>): du1 panel wm against x channels 32 wn .. ----
+  const int wm = w >> 1, wn = w & 1;
+  typedef s16x4v __attribute__((address_space(3))) * lds_tr;
+  f32x4v gw[4][2];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) gw[i][j] = (f32x4v){0.f, 0.f, 0.f, 0.f};
+  int ea_used[2] = {15, 15}, eb_used = 15;     // exponents the accumulators are expressed in
+  int e_run = 15, e_x = 15;                    // running exponents: this wave's du1 channels; x (the same in every wave)
+  const int dg_mt = w & 1, dg_nt = w >> 1;     // this wave's tile of gx: points 16 dg_mt .., input channels 16 dg_nt ..
+
+  if ((int)blockIdx.x < A.ntiles) { load_du2(blockIdx.x); load_d1(blockIdx.x); load_x(blockIdx.x); }
+  lds_barrier();                               // W1 fragments and the zeroed sums are in LDS
+
+  for (int tile = blockIdx.x; tile < A.ntiles; tile += gridDim.x) {
+    const int next_tile = tile + gridDim.x;
+    const bool has_next = next_tile < A.ntiles;
+    const long p0 = (long)tile * 32;
+    // ---- du2 -> B fragments, slice kappa = w, one scale per point: the bound the chain derives from that of dz3 ----
+    float inv_b[2];
+#pragma unroll
+    for (int blk = 0; blk < 2; ++blk) {
+      float s_du2, ai;
+      h2_scale(c3t * bzr[blk] * A.dmax, 0, s_du2, ai);
+      inv_b[blk] = ai * winv2;
+      const float4 a = du2r[blk * 2], b = du2r[blk * 2 + 1];
+      const float hv[8] = {a.x * s_du2, a.y * s_du2, a.z * s_du2, a.w * s_du2, b.x * s_du2, b.y * s_du2, b.z * s_du2, b.w * s_du2};
+      h2_put_frag(smem + FL_DUBUF + ((blk * 8 + w) * 2) * 1024 + l * 16, hv);
+    }
+    {
+      float m = fmaxf(fmaxf(fabsf(xr.x), fabsf(xr.y)), fmaxf(fabsf(xr.z), fabsf(xr.w)));
+      m = wave_max(m);
+      if (l == 0) xmax[w] = m;
+    }
+    lds_barrier();                                                                    // 1: du2 slices and x maxima in LDS
+
+    // ---- du1 = (W2^T du2) * d1: this wave's 32 hidden rows of both point blocks ----
+    float u[4][4];                               // [blk * 2 + t][r]: point 16 blk + li, row 16 (2 w + t) + 4 g + r
+    float bsum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    {
+      f32x4v acc[2][2];
+#pragma unroll
+      for (int blk = 0; blk < 2; ++blk) {
+        acc[blk][0] = (f32x4v){0.f, 0.f, 0.f, 0.f}; acc[blk][1] = (f32x4v){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kap = 0; kap < 8; ++kap) {
+          const char* hb = smem + FL_DUBUF + ((blk * 8 + kap) * 2) * 1024 + l * 16;
+          const f16x8 bh = *reinterpret_cast<const f16x8*>(hb), bl = *reinterpret_cast<const f16x8*>(hb + 1024);
+          acc[blk][0] = h2_mfma32(w2h[0][kap], w2l[0][kap], bh, bl, acc[blk][0]);
+          acc[blk][1] = h2_mfma32(w2h[1][kap], w2l[1][kap], bh, bl, acc[blk][1]);
+        }
+      }
+#pragma unroll
+      for (int blk = 0; blk < 2; ++blk) {
+        const bool live = p0 + 16 * blk + li < A.P;
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          const float4 d4 = d1r[blk * 2 + t];
+          const float d[4] = {d4.x, d4.y, d4.z, d4.w};
+          float* v = u[blk * 2 + t];
+          float s[4];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) { s[r] = acc[blk][t][r] * inv_b[blk]; v[r] = s[r] * d[r]; }
+          if (live) {
+            // (db1 with the chain's bits: there the compiler folds the last multiplication into this addition, the
+            //  opposite of what it does for db2 -- stated here, not left to it)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) bsum[4 * t + r] = __builtin_fmaf(s[r], d[r], bsum[4 * t + r]);
+          } else {                                // a point past the end: its column of the products is not a gradient
+            v[0] = v[1] = v[2] = v[3] = 0.f;
+          }
+        }
+      }
+    }
+    // (the next tile's loads start here, not a phase earlier -- under the 96 products, beside W2^T's 128 registers and
+    //  the 48 accumulators, they spilled -- and not later: started behind the panel writes below, 300 vector instructions
+    //  on, the kernel took 1.93 instead of 1.64 ms.  It lives on how long its loads are in flight)
+    if (has_next) { load_du2(next_tile); load_d1(next_tile); }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) bsum[i] = row_sum15(bsum[i]);
+    if (li == 15) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) acc_db1[16 * (2 * w + (i >> 2)) + 4 * g + (i & 3)] += bsum[i];
+    }
+    // ---- du1 -> this wave's half of panel w / 2 (channels 32 (w & 1) .. of it) under the wave's running exponent ----
+    {
+      float m = 0.f;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) m = fmaxf(fmaxf(m, fmaxf(fabsf(u[i][0]), fabsf(u[i][1]))), fmaxf(fabsf(u[i][2]), fabsf(u[i][3])));
+      m = wave_max(m);
+      e_run = max(e_run, (int)(__float_as_uint(m) >> 23) & 0xff);
+      e_run = min(e_run, 254);
+      const float scale = __uint_as_float((unsigned)(268 - e_run) << 23);          // running maximum -> [2^14, 2^15)
+      char* const dst = smem + FL_PAN + (w >> 1) * FL_PANEL;
+#pragma unroll
+      for (int blk = 0; blk < 2; ++blk)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          const float* v = u[blk * 2 + t];
+          uint2 hi, lo;
+          h2_split4(v[0] * scale, v[1] * scale, v[2] * scale, v[3] * scale, hi, lo);
+          const int off = stage_off(16 * blk + li, (w & 1) * 8 + 4 * t + g);
+          *reinterpret_cast<uint2*>(dst + off) = hi;
+          *reinterpret_cast<uint2*>(dst + 4096 + off) = lo;
+        }
+      if (l == 0) einfo[w] = e_run;
+    }
+    // ---- x -> its panel under the running exponent of the whole panel ----
+    {
+      float m = 0.f;
+#pragma unroll
+      for (int i = 0; i < FS_WAVES; ++i) m = fmaxf(m, xmax[i]);
+      e_x = max(e_x, (int)(__float_as_uint(m) >> 23) & 0xff);
+      e_x = min(e_x, 254);
+      const float scale = __uint_as_float((unsigned)(268 - e_x) << 23);
+      uint2 hi, lo;
+      h2_split4(xr.x * scale, xr.y * scale, xr.z * scale, xr.w * scale, hi, lo);
+      const int off = stage_off(xrow, xc);
+      *reinterpret_cast<uint2*>(smem + FL_X + off) = hi;
+      *reinterpret_cast<uint2*>(smem + FL_X + 4096 + off) = lo;
+    }
+    if (has_next) load_x(next_tile);
+    lds_barrier();                                                                    // 2: du1 and x panels in LDS
+    // (the next tile's staging, at the top of the next pass, writes the du2 slices and the x maxima, last read before
+    //  barrier 2; the panels and exponents, read below, are written again only behind the next barrier 1.  Staging the
+    //  next tile BEFORE the consumer in one wave of each SIMD pair, so that vector and matrix work of the pair overlap
+    //  as in k_wgrad_h2, needs six registers more than there are: it spilled and was not run)
+
+    // (the consumer's LDS addresses are formed here, per tile, from a lane index the compiler cannot see through: hoisted
+    //  out of the loop they stayed in registers beside W2^T and the accumulators, and seven of them spilled)
+    int lc = l;
+    asm volatile("" : "+v"(lc));
+    const int gc = lc >> 4, lic = lc & 15;
+    // ---- gW1 += du1^T . x ----
+    {
+      const int q = lic >> 2, pp = lic & 3;
+      const int tsw = ((q >> 1) & 1) | ((gc & 1) << 1);
+      const int trow = (8 * gc + q) * 128 + pp * 8;
+      auto frag = [&](const char* panel, int tile, f16x8& hi, f16x8& lo) {
+        const char* t = panel + trow + ((tile ^ tsw) << 5);
+        union { struct { s16x4v a, b; } h; f16x8 v; } uh, ul;
+        uh.h.a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(t));
+        uh.h.b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(t + 512));
+        ul.h.a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(t + 4096));
+        ul.h.b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(t + 4096 + 512));
+        hi = uh.v; lo = ul.v;
+      };
+      const int eb = __builtin_amdgcn_readfirstlane(e_x);
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const int ea = __builtin_amdgcn_readfirstlane(einfo[2 * wm + k]);
+        if (ea + eb != ea_used[k] + eb_used) {                               // rare: a new running maximum
+          const int d = (ea_used[k] + eb_used) - (ea + eb);                  // < 0
+          const float f = d > -126 ? __uint_as_float((unsigned)(127 + d) << 23) : 0.f;
+#pragma unroll
+          for (int j = 0; j < 2; ++j) { gw[2 * k][j] *= f; gw[2 * k + 1][j] *= f; }
+        }
+        ea_used[k] = ea;
+      }
+      eb_used = eb;
+      f16x8 bh[2], bl[2];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) frag(smem + FL_X, 2 * wn + j, bh[j], bl[j]);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        f16x8 ah, al;
+        frag(smem + FL_PAN + wm * FL_PANEL, i, ah, al);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) gw[i][j] = h2_mfma32(ah, al, bh[j], bl[j], gw[i][j]);
+      }
+    }
+    // ---- gx = du1 . W1: one half panel (32 hidden channels, one exponent) at a time ----
+    {
+      f32x4v tot = (f32x4v){0.f, 0.f, 0.f, 0.f};
+      const int row = 16 * dg_mt + lic;                     // A fragment: lane = point, 8 consecutive channels
+#pragma unroll
+      for (int hp = 0; hp < 8; ++hp) {
+        const char* pa_ = smem + FL_PAN + (hp >> 1) * FL_PANEL + stage_off(row, 2 * (4 * (hp & 1) + gc));
+        const f16x8 ah = *reinterpret_cast<const f16x8*>(pa_), al = *reinterpret_cast<const f16x8*>(pa_ + 4096);
+        const char* wb = wfrag + (hp * 4 + dg_nt) * 2048 + lc * 16;
+        const f16x8 bh = *reinterpret_cast<const f16x8*>(wb), bl = *reinterpret_cast<const f16x8*>(wb + 1024);
+        const f32x4v part = h2_mfma32(ah, al, bh, bl, (f32x4v){0.f, 0.f, 0.f, 0.f});
+        const int ek = __builtin_amdgcn_readfirstlane(einfo[hp]);
+        const float fk = __uint_as_float((unsigned)(ek - 14) << 23) * w_inv;
+        tot += part * fk;
+      }
+      // lane (g, li) holds points 4 g + r of channel li: a 4 x 4 transpose inside every quad gives one 16-byte store
+      float t0 = tot[0], t1 = tot[1], t2 = tot[2], t3 = tot[3];
+      quad_transpose(t0, t1, t2, t3);
+      const int rq = 16 * dg_mt + 4 * gc + (lic & 3);
+      if (p0 + rq < A.P) *reinterpret_cast<float4*>(A.gx + p0 * 64 + (unsigned)(rq * 64 + 16 * dg_nt + 4 * (lic >> 2))) = make_float4(t0, t1, t2, t3);
+    }
+  }
+
+  // ---- this workgroup's slab [256][64] of gW1 and its db1 ----
+  const float fb = __uint_as_float((unsigned)(eb_used - 14) << 23);
+  float* __restrict__ out = A.slabs + (long)blockIdx.x * 256 * 64;
+  const unsigned o0 = (unsigned)((wm * 64 + 4 * g) * 64 + wn * 32 + li);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float fa = __uint_as_float((unsigned)(ea_used[i >> 1] - 14) << 23);
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) out[o0 + (unsigned)((16 * i + r) * 64 + 16 * j)] = gw[i][j][r] * fa * fb;
+  }
+  lds_barrier();
+  if (tid < 256) A.part[(long)blockIdx.x * FF3_PART + tid] = acc_db1[tid];
+}
+
+// --------------------------------------------------------------------------------------------------------------------
+bool ff_bwd_split_ok(long P, int hid, int dim) { return !switch_off("RPDE_FF_BWD_SPLIT") && wgrad_h2_dgrad_ok(P, hid, dim); }
+
+int ff_bwd_split_launch(const rpde_ff_params* p, const float* const* ds, const float* z_last, const float* grad_out,
+                        const float* x, float* dz3, float* du2, float* dzb, float* gx, float* slabs, float* gw1, float* part,
+                        int* grid_out, long P, void* fimg, hipStream_t st, FoldJobs* folds) {
+  RPDE_CHECK_ARG(ff_bwd_split_ok(P, p->dim * p->factor, p->dim) && ds && ds[0] && ds[1] && gx && gw1 && slabs,
+                 "ff_bwd_split: unsupported call");
+  const char* img;
+  const float* consts;
+  RPDE_TRY(ff3_fused_bwd_prepare(p, fimg, &img, &consts, st));
+  const int ntiles = (int)((P + 31) / 32);
+  int cus;
+  RPDE_HIP(cu_count(&cus));
+  int grid = cus < FS_MAX_GRID ? cus : FS_MAX_GRID;
+  if (ntiles < grid) grid = ntiles;
+  const DropCfg drop2 = make_drop(p->dropout_p, layer_seed(p->seed, 2), p->seed_epoch);   // the forward's mask of layer 3
+
+  FsA a;
+  memset(&a, 0, sizeof(a));
+  a.g = grad_out; a.z3 = z_last; a.d2 = ds[1];
+  a.dz3 = dz3; a.du2 = du2; a.dzb = dzb;
+  a.wimg = img; a.consts = consts; a.gamma = p->ln_gamma; a.beta = p->ln_beta; a.part = part;
+  a.P = P; a.layer_norm = p->layer_norm; a.eps = p->ln_eps; a.post_act = p->post_act;
+  a.drop2 = drop2; a.ntiles = ntiles;
+  hipLaunchKernelGGL(k_ffs_adjoint, dim3(grid), dim3(64 * FS_WAVES), 0, st, a);
+  RPDE_LAUNCH_CHECK();
+
+  FsB b;
+  memset(&b, 0, sizeof(b));
+  b.du2 = du2; b.d1 = ds[0]; b.x = x; b.dzb = dzb; b.w1 = p->weights[0];
+  b.gx = gx; b.slabs = slabs; b.part = part;
+  b.wimg = img; b.consts = consts;
+  b.P = P; b.dmax = 1.13f * drop2.scale;     // |gelu'| <= 1.129, times the dropout scale folded into d (as the chain)
+  b.ntiles = ntiles;
+  hipLaunchKernelGGL(k_ffs_layer1, dim3(grid), dim3(64 * FS_WAVES), 0, st, b);
+  RPDE_LAUNCH_CHECK();
+  *grid_out = grid;
+  const int hid = p->dim * p->factor;
+  if (folds && folds->add(slabs, gw1, hid * p->dim, grid, (long)hid * p->dim)) return RPDE_OK;
+  return reduce_slabs(slabs, gw1, (long)hid * p->dim, grid, (long)hid * p->dim, 1.f, 0, st);
+}
+
+}  // namespace rpde

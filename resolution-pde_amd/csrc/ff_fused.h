@@ -20,4 +20,9 @@ size_t ff3_fused_bwd_part_floats();
 int ff3_fused_bwd_launch(const rpde_ff_params* p, const float* const* ds, int recompute, const float* z_last,
                          const float* grad_out, float* dz3, float* du2, float* du1, float* dx, float* part, int* grid_out,
                          long P, void* ws, hipStream_t st);
+// the backward's weight image alone, for the split backward (ff_bwd_split.hip): per wave w FF3_WAVE_IMG bytes, fragments
+// 0..3 the rows 32w..32w+31 of W3^T, 4..19 of W2^T, each [hi | lo][64 lanes][16 B]; consts: 1/scale of W1, W2, W3, the
+// largest column L1 norm of W3 and of W2
+constexpr int FF3_WAVE_IMG = 24 * 2048;
+int ff3_fused_bwd_prepare(const rpde_ff_params* p, void* ws, const char** img, const float** consts, hipStream_t st);
 }  // namespace rpde

@@ -995,6 +995,16 @@ int ff3_fused_bwd_launch(const rpde_ff_params* p, const float* const* ds, int re
   return RPDE_OK;
 }
 
+static_assert(FF3_WAVE_IMG == FF_FRAGS * 2048, "ff_fused.h states the image layout");
+int ff3_fused_bwd_prepare(const rpde_ff_params* p, void* ws, const char** img_out, const float** consts_out, hipStream_t st) {
+  char* img = static_cast<char*>(ws);
+  float* consts = reinterpret_cast<float*>(img + FF_IMG_BYTES);
+  hipLaunchKernelGGL(k_ff3_prep_bwd, dim3(FF_PREP_BLOCKS), dim3(1024), 0, st, p->weights[0], p->weights[1], p->weights[2], img, consts);
+  RPDE_LAUNCH_CHECK();
+  *img_out = img; *consts_out = consts;
+  return RPDE_OK;
+}
+
 }  // namespace rpde
 
 #ifdef RPDE_STAMPS
