@@ -846,24 +846,32 @@ int rpde_cno_act1d_bwd(const float* x, const float* scale, const float* shift, c
 
 /* ---- CNO: the rest of a block (csrc/cno_layers.hip, both ranks; reference models/CNO1d.py:51-164: Conv1d(k=3,
  * padding=1) -> BatchNorm1d -> CNO_LReLu, and the residual block's second BatchNorm plus skip add).  Channels first,
- * contiguous [B, C, n].
- * conv1d_k3: the three taps as accumulating rpde_gemm_f32 products on shifted views -- the centre tap over the whole
- *   range with the bias, tap 0 onto [1, n), tap 2 onto [0, n - 1) (n = 1: the centre tap alone): conv2d_k3's tap loop
- *   on a plane of one row with one row of taps.  wt is the weight
- *   repacked tap-major, [3][Cout][Cin].  _bwd_data: gx from g with the transposed taps and mirrored shifts.
- *   _bwd_weight: gw [Cout][Cin][3] (torch's layout) and gb [Cout] (or null) by one deterministic reduction over
- *   (batch, x), fp32, fixed order, no atomics: conv2d_k3's kernel with one row of taps, always in one slice.
+ * contiguous [B, C, n] or [B, C, H, W].
+ * conv_k3: Conv(k = 3, padding = 1) of both ranks on [B, C, H, W] with ky rows of three taps: ky = 3 is Conv2d, ky = 1
+ *   Conv1d, a plane of one row (H = 1 required) with the dy = 0 row of taps alone; ky = 3 with H = 1 is legal.  The
+ *   taps are accumulating rpde_gemm_f32 products on shifted views -- the centre tap over the flat H W axis with the
+ *   bias, the two dx = 0 taps flat over (H - 1) W points, the dx != 0 taps row by row through the descriptor's
+ *   two-level batch so that no row wraps; taps without a valid range (H = 1 or W = 1) are skipped, so Conv1d runs
+ *   three products: centre, tap 0 onto [1, n), tap 2 onto [0, n - 1).  wt is the weight repacked tap-major,
+ *   [3 ky][Cout][Cin], tap = 3 ty + tx.  _bwd_data: gx from g with the transposed taps and mirrored shifts.
+ *   _bwd_weight: gw [Cout][Cin][ky][3] (torch's layout) and gb [Cout] (or null), fp32, fixed order, no atomics, on the
+ *   sliced kernel it shares with upconv below: for ky = 3 the image rows (b, y) are split into slices over enough
+ *   workgroups to fill the device when Cout Cin is small, the slices' partial sums go to the caller's `partial`
+ *   [slices][3 ky Cout Cin + Cout] floats (rpde_conv_k3_bwd_weight_slices gives the count; with one slice the buffer
+ *   is not used and may be null) and a second kernel adds them in slice order; ky = 1 always runs one slice.
  * moments: sums [C][4] doubles = (sum a, sum b, sum a b, sum b^2) per channel over (batch, x).  BatchNorm's forward
  *   reads mean and variance of z from (z, z); its backward reads sum gy and sum gy z from (gy, z).
  * affine: out = p0[c] a + p1[c] b + p2[c] (+ residual); b and p1 both null: no b term.  A BatchNorm's apply step (with the
  *   residual block's skip add), its backward dz = p0 gy + p1 z + p2, and a plain skip add (p0 = 1, p2 = 0).  The
  *   coefficients [C] are doubles and the sum is formed in double and rounded once: the backward's terms cancel to
  *   eps / (var + eps) of their size when a channel has few values. */
-int rpde_cno_conv1d_k3_fwd(const float* x, const float* wt, const float* bias, float* out, int B, int Cin, int Cout, int n,
-                           void* stream);
-int rpde_cno_conv1d_k3_bwd_data(const float* g, const float* wt, float* gx, int B, int Cin, int Cout, int n, void* stream);
-int rpde_cno_conv1d_k3_bwd_weight(const float* x, const float* g, float* gw, float* gb, int B, int Cin, int Cout, int n,
-                                  void* stream);
+int rpde_conv_k3_fwd(const float* x, const float* wt, const float* bias, float* out, int B, int Cin, int Cout, int H, int W,
+                     int ky, void* stream);
+int rpde_conv_k3_bwd_data(const float* g, const float* wt, float* gx, int B, int Cin, int Cout, int H, int W, int ky,
+                          void* stream);
+int rpde_conv_k3_bwd_weight_slices(int B, int Cin, int Cout, int H, int W, int ky);
+int rpde_conv_k3_bwd_weight(const float* x, const float* g, float* gw, float* gb, int B, int Cin, int Cout, int H, int W,
+                            int ky, float* partial, int partial_slices, void* stream);
 int rpde_cno_moments(const float* a, const float* b, double* sums, int B, int C, int n, void* stream);
 int rpde_cno_affine(const float* a, const float* b, const double* p0, const double* p1, const double* p2, const float* residual,
                     float* out, int B, int C, int n, void* stream);
@@ -897,24 +905,6 @@ int rpde_cno_act2d_bwd(const float* x, const float* scale, const float* shift, c
                        int uxt_taps, const int32_t* dyt_span, const float* dyt_w, int dyt_taps, const int32_t* dxt_span,
                        const float* dxt_w, int dxt_taps, void* stream);
 
-/* conv2d_k3 (csrc/cno_layers.hip): Conv2d(k = 3, padding = 1) on [B, C, H, W] as nine accumulating rpde_gemm_f32 products
- *   on shifted views -- the centre tap over the flat H W axis with the bias, the two dx = 0 taps flat over (H - 1) W points, the six dx != 0
- *   taps row by row through the descriptor's two-level batch so that no row wraps; taps without a valid range (H = 1 or
- *   W = 1) are skipped.  wt is the weight repacked tap-major, [9][Cout][Cin], tap = 3 ty + tx.  _bwd_data: gx from g with
- *   the transposed taps and mirrored shifts.
- *   _bwd_weight: gw [Cout][Cin][3][3] (torch's layout) and gb [Cout] (or null), fp32, fixed order, no atomics: the image
- *   rows (b, y) are split into slices over enough workgroups to fill the device when Cout Cin is small, the slices'
- *   partial sums go to the caller's `partial` [slices][9 Cout Cin + Cout] floats (rpde_cno_conv2d_k3_bwd_weight_slices
- *   gives the count; with one slice the buffer is not used and may be null) and a second kernel adds them in slice
- *   order. */
-int rpde_cno_conv2d_k3_fwd(const float* x, const float* wt, const float* bias, float* out, int B, int Cin, int Cout, int H,
-                           int W, void* stream);
-int rpde_cno_conv2d_k3_bwd_data(const float* g, const float* wt, float* gx, int B, int Cin, int Cout, int H, int W,
-                                void* stream);
-int rpde_cno_conv2d_k3_bwd_weight_slices(int B, int Cin, int Cout, int H, int W);
-int rpde_cno_conv2d_k3_bwd_weight(const float* x, const float* g, float* gw, float* gb, int B, int Cin, int Cout, int H, int W,
-                                  float* partial, int partial_slices, void* stream);
-
 /* ---- U-Net (csrc/unet.hip; reference models/unet.py, the PDEBench U-Net): what its blocks need beyond conv k3, the
  * BatchNorm kernels and conv1x1 above.  Channels first, contiguous fp32; ky = 1 is the 1-D form, a plane of one row
  * (H = 1) with windows / taps of one row, ky = 2 the 2-D form.  No atomics, fixed summation order.
@@ -927,9 +917,10 @@ int rpde_cno_conv2d_k3_bwd_weight(const float* x, const float* g, float* gw, flo
  *   row-major scan order, recomputed from act.
  * upconv_*: ConvTranspose(kernel_size = 2, stride = 2) with torch's weight layout w [Cin][Cout][ky][2] and bias [Cout]
  *   (or null): out [B, Cout, ky H, 2 W] from x [B, Cin, H, W]; _bwd_data gx from g; _bwd_weight gw (w's layout) and
- *   gb [Cout] (or null), the points (b, y, x) split into slices whose partial sums go to `partial`
- *   [slices][ky 2 Cin Cout + Cout] floats (rpde_unet_upconv_bwd_weight_slices gives the count; with one slice the
- *   buffer is not used and may be null) and are added in slice order. */
+ *   gb [Cout] (or null) on conv_k3's sliced kernel with the operands' roles exchanged, the points (b, y, x) split into
+ *   slices whose partial sums go to `partial` [slices][ky 2 Cin Cout + Cout] floats
+ *   (rpde_unet_upconv_bwd_weight_slices gives the count; with one slice the buffer is not used and may be null) and
+ *   are added in slice order. */
 int rpde_unet_tanh_pool_fwd(const float* z, const float* scale, const float* shift, float* act, float* pooled, int B, int C,
                             int H, int W, int ky, void* stream);
 int rpde_unet_tanh_pool_bwd(const float* act, const float* g_act, const float* g_pool, float* gy, int B, int C, int H, int W,

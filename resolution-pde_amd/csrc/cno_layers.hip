@@ -1,102 +1,48 @@
 // The rest of a CNO block, both ranks (the activation itself: cno.hip in 1-D, cno2d.hip in 2-D): Conv(k = 3,
-// padding = 1) as accumulating GEMMs on shifted views with its own deterministic weight-gradient kernel, and the two
-// kernels of BatchNorm (per-channel moments, per-channel affine combine).  Conv1d is Conv2d on a plane of one row with
-// one row of taps: one tap loop and one weight-gradient kernel serve both.  gfx950 (CDNA4,
-// wave64) only.
-#include "rpde_internal.h"
-#include "wave.h"
-
-#include <algorithm>
+// padding = 1) as accumulating GEMMs on shifted views with a deterministic weight gradient on the sliced scaffold it
+// shares with the transposed convolution (wgrad_sliced.h), and the two kernels of BatchNorm (per-channel moments,
+// per-channel affine combine).  Conv1d is Conv2d on a plane of one row with one row of taps: one tap loop, one
+// weight-gradient path and one set of entries (ky = 1 or 3) serve both.  gfx950
+// (CDNA4, wave64) only.
+#include "wgrad_sliced.h"
 
 namespace rpde {
 
 // ---- Conv(k = 3, padding = 1): weight and bias gradient -----------------------------------------------------------
 // gw[co][ci][ty][tx] = sum_{b,y,x} g[b][co][y][x] * x[b][ci][y + ty - KY / 2][x + tx - 1],  gb[co] = sum g[b][co][y][x],
-// KY rows of taps: 3 for Conv2d, 1 for Conv1d (H = 1, gw [Cout][Cin][3]).  A workgroup owns a 4 x 4 tile of (co, ci)
-// and one slice of the image rows (b, y): every thread walks the slice's points tid, tid + 256, ... with 48 KY + 4
-// accumulators, then the workgroup adds them up in a fixed order (DPP sum inside a wave, the four waves in sequence).
-// With one slice the sums are the result; with more they are partial sums [slice][Cout Cin 9 + Cout], added slice by
-// slice by k_cno_conv2d_wsum.  No atomics.  Conv1d always runs one slice
-constexpr int CNO_WG = 4;
-constexpr int C2W_TARGET = 512;       // workgroups wanted: two per CU
-constexpr int C2W_MIN_POINTS = 256;   // a slice holds at least one point per thread
-
+// KY rows of taps: 3 for Conv2d, 1 for Conv1d (H = 1, gw [Cout][Cin][3]), on the sliced scaffold of wgrad_sliced.h:
+// g is the narrow operand, the 3 KY shifted taps of x the wide one.  The slices are whole image rows (b, y); Conv1d
+// always runs one slice
 template <int KY>
-__global__ void __launch_bounds__(256)
-k_cno_conv_wgrad(const float* __restrict__ x, const float* __restrict__ g, float* __restrict__ gw, float* __restrict__ gb,
-                 long slice_stride, int BH, int Cin, int Cout, int H_, int W, int rows_per_slice) {
-  constexpr int T = 3 * KY, N_GW = CNO_WG * CNO_WG * T;
-  __shared__ float red[4][N_GW + CNO_WG];
-  const int H = KY == 1 ? 1 : H_;
-  const int ci0 = blockIdx.x * CNO_WG, co0 = blockIdx.y * CNO_WG;
-  const int r_lo = blockIdx.z * rows_per_slice, r_hi = min(BH, r_lo + rows_per_slice);
-  float acc[CNO_WG][CNO_WG][T], accb[CNO_WG];
-#pragma unroll
-  for (int j = 0; j < CNO_WG; ++j) {
-    accb[j] = 0.f;
-#pragma unroll
-    for (int i = 0; i < CNO_WG; ++i)
-#pragma unroll
-      for (int t = 0; t < T; ++t) acc[j][i][t] = 0.f;
+struct ConvK3Wgrad {
+  static constexpr int T = 3 * KY;
+  static constexpr bool G_NARROW = true;
+  int H, W, r_lo, b, y, xx;
+  long plane;
+  __device__ ConvK3Wgrad(int H_, int W_, long p_lo) : H(KY == 1 ? 1 : H_), W(W_), r_lo((int)(p_lo / W_)), plane((long)H * W_) {}
+  __device__ __forceinline__ void seek(long i) {               // a slice starts on a row boundary
+    const int r = r_lo + (int)(i / W);
+    xx = (int)(i % W);
+    b = r / H; y = r - b * H;
   }
-  const long plane = (long)H * W;
-  const long total = (long)(r_hi - r_lo) * W;
-  for (long p = threadIdx.x; p < total; p += 256) {
-    const int r = r_lo + (int)(p / W), xx = (int)(p % W);
-    const int b = r / H, y = r - b * H;
-    float gv[CNO_WG];
+  __device__ __forceinline__ float narrow(const float* __restrict__ g, int Cout, int co) const {
+    return co < Cout ? g[((long)b * Cout + co) * plane + (long)y * W + xx] : 0.f;
+  }
+  __device__ __forceinline__ void wide(const float* __restrict__ x, int Cin, int ci, float (&xv)[T]) const {
+    const bool live = ci < Cin;
+    const float* img = x + ((long)b * Cin + (live ? ci : 0)) * plane;
 #pragma unroll
-    for (int j = 0; j < CNO_WG; ++j) {
-      gv[j] = co0 + j < Cout ? g[((long)b * Cout + co0 + j) * plane + (long)y * W + xx] : 0.f;
-      accb[j] += gv[j];
-    }
+    for (int ty = 0; ty < KY; ++ty) {
+      const int yy = y + ty - KY / 2;
+      const bool row_ok = live && yy >= 0 && yy < H;
 #pragma unroll
-    for (int i = 0; i < CNO_WG; ++i) {
-      const bool live = ci0 + i < Cin;
-      const float* img = x + ((long)b * Cin + (live ? ci0 + i : 0)) * plane;
-      float xv[T];
-#pragma unroll
-      for (int ty = 0; ty < KY; ++ty) {
-        const int yy = y + ty - KY / 2;
-        const bool row_ok = live && yy >= 0 && yy < H;
-#pragma unroll
-        for (int tx = 0; tx < 3; ++tx) {
-          const int xs = xx + tx - 1;
-          xv[ty * 3 + tx] = row_ok && xs >= 0 && xs < W ? img[(long)yy * W + xs] : 0.f;
-        }
+      for (int tx = 0; tx < 3; ++tx) {
+        const int xs = xx + tx - 1;
+        xv[ty * 3 + tx] = row_ok && xs >= 0 && xs < W ? img[(long)yy * W + xs] : 0.f;
       }
-#pragma unroll
-      for (int j = 0; j < CNO_WG; ++j)
-#pragma unroll
-        for (int t = 0; t < T; ++t) acc[j][i][t] = fmaf(gv[j], xv[t], acc[j][i][t]);
     }
   }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int j = 0; j < CNO_WG; ++j) {
-#pragma unroll
-    for (int i = 0; i < CNO_WG; ++i)
-#pragma unroll
-      for (int t = 0; t < T; ++t) {
-        const float v = wave_sum_dpp(acc[j][i][t]);
-        if (lane == 0) red[wave][(j * CNO_WG + i) * T + t] = v;
-      }
-    const float v = wave_sum_dpp(accb[j]);
-    if (lane == 0) red[wave][N_GW + j] = v;
-  }
-  __syncthreads();
-  const int k = threadIdx.x;
-  if (k < N_GW + CNO_WG) {
-    const float v = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
-    float* gw_s = gw + blockIdx.z * slice_stride;
-    if (k < N_GW) {
-      const int j = k / (CNO_WG * T), i = (k / T) % CNO_WG, t = k % T;
-      if (co0 + j < Cout && ci0 + i < Cin) gw_s[((long)(co0 + j) * Cin + ci0 + i) * T + t] = v;
-    } else if (gb && blockIdx.x == 0 && co0 + (k - N_GW) < Cout) {
-      gb[blockIdx.z * slice_stride + co0 + k - N_GW] = v;
-    }
-  }
-}
+};
 
 // gw / gb = the slices' partial sums added in slice order
 __global__ void __launch_bounds__(256)
@@ -110,20 +56,12 @@ k_cno_conv2d_wsum(const float* __restrict__ part, float* __restrict__ gw, float*
   else if (gb) gb[e - n_gw] = v;
 }
 
-// (rpde_internal.h: the transposed convolution's weight gradient, unet.hip, adds its slices up the same way)
+// (rpde_internal.h: wgrad_sliced.h's launcher calls it for both convolutions)
 int sum_slices(const float* part, float* gw, float* gb, long n_gw, long n_gb, int slices, hipStream_t st) {
   hipLaunchKernelGGL(k_cno_conv2d_wsum, dim3((unsigned)((n_gw + n_gb + 255) / 256)), dim3(256), 0, st, part, gw, gb, n_gw, n_gb,
                      slices);
   RPDE_LAUNCH_CHECK();
   return RPDE_OK;
-}
-
-// slices of the (b, y) rows the Conv2d weight gradient is split over
-static int c2w_slices(int B, int Cin, int Cout, int H, int W) {
-  const long tiles = (long)((Cin + CNO_WG - 1) / CNO_WG) * ((Cout + CNO_WG - 1) / CNO_WG);
-  const long rows = (long)B * H;
-  long n = std::min<long>(C2W_TARGET / tiles, std::min<long>(rows, rows * W / C2W_MIN_POINTS));
-  return (int)std::max<long>(1, std::min<long>(n, 65535));
 }
 
 // ---- BatchNorm pieces ---------------------------------------------------------------------------------------------
@@ -239,76 +177,45 @@ static int cno_conv_taps(const float* src, const float* wt, const float* bias, f
   return RPDE_OK;
 }
 
-static int cno_conv_wgrad(const char* what, const float* x, const float* g, float* gw, float* gb, int B, int Cin, int Cout,
-                          int KY, int H, int W, int slices, float* partial, hipStream_t st) {
-  const dim3 grid((unsigned)((Cin + CNO_WG - 1) / CNO_WG), (unsigned)((Cout + CNO_WG - 1) / CNO_WG), (unsigned)slices);
-  RPDE_CHECK_ARG(grid.y <= 65535, "%s: too many output channels (%d)", what, Cout);
-  const int BH = B * H, rows_per_slice = (BH + slices - 1) / slices;
-  const long n_gw = (long)Cout * Cin * 3 * KY, n_gb = Cout;
-  // one slice: the sums are the result; more: partial sums, then their sum
-  float* to_w = slices == 1 ? gw : partial;
-  float* to_b = slices == 1 ? gb : partial + n_gw;
-  const long stride = slices == 1 ? 0L : n_gw + n_gb;
-  if (KY == 1) hipLaunchKernelGGL(k_cno_conv_wgrad<1>, grid, dim3(256), 0, st, x, g, to_w, to_b, stride, BH, Cin, Cout, H, W, rows_per_slice);
-  else hipLaunchKernelGGL(k_cno_conv_wgrad<3>, grid, dim3(256), 0, st, x, g, to_w, to_b, stride, BH, Cin, Cout, H, W, rows_per_slice);
-  RPDE_LAUNCH_CHECK();
-  if (slices == 1) return RPDE_OK;
-  return sum_slices(partial, gw, gb, n_gw, n_gb, slices, st);
-}
-
-int rpde_cno_conv1d_k3_fwd(const float* x, const float* wt, const float* bias, float* out, int B, int Cin, int Cout, int n,
-                           void* stream) {
-  RPDE_CHECK_ARG(x && wt && out, "cno_conv1d_k3_fwd: null tensor");
-  RPDE_CHECK_ARG(B > 0 && Cin > 0 && Cout > 0 && n > 0, "cno_conv1d_k3_fwd: bad sizes B=%d Cin=%d Cout=%d n=%d", B, Cin, Cout, n);
-  return cno_conv_taps(x, wt, bias, out, B, Cin, Cout, 1, 1, n, false, as_stream(stream));
-}
-
-int rpde_cno_conv1d_k3_bwd_data(const float* g, const float* wt, float* gx, int B, int Cin, int Cout, int n, void* stream) {
-  RPDE_CHECK_ARG(g && wt && gx, "cno_conv1d_k3_bwd_data: null tensor");
-  RPDE_CHECK_ARG(B > 0 && Cin > 0 && Cout > 0 && n > 0, "cno_conv1d_k3_bwd_data: bad sizes B=%d Cin=%d Cout=%d n=%d", B, Cin, Cout, n);
-  return cno_conv_taps(g, wt, nullptr, gx, B, Cout, Cin, 1, 1, n, true, as_stream(stream));
-}
-
-int rpde_cno_conv1d_k3_bwd_weight(const float* x, const float* g, float* gw, float* gb, int B, int Cin, int Cout, int n,
-                                  void* stream) {
-  RPDE_CHECK_ARG(x && g && gw, "cno_conv1d_k3_bwd_weight: null tensor");
-  RPDE_CHECK_ARG(B > 0 && Cin > 0 && Cout > 0 && n > 0, "cno_conv1d_k3_bwd_weight: bad sizes B=%d Cin=%d Cout=%d n=%d", B, Cin, Cout, n);
-  return cno_conv_wgrad("cno_conv1d_k3_bwd_weight", x, g, gw, gb, B, Cin, Cout, 1, 1, n, 1, nullptr, as_stream(stream));
-}
-
-static int cno_conv2d_check(const char* what, const void* a, const void* b, const void* c, int B, int Cin, int Cout, int H, int W) {
+// ky = 3 with H = 1 is legal (its outer tap rows have no valid range); ky = 1 is the 1-D entry.  At H = 1 the size
+// conditions cannot fail
+static int conv_k3_check(const char* what, const void* a, const void* b, const void* c, int B, int Cin, int Cout, int H, int W,
+                         int ky) {
   RPDE_CHECK_ARG(a && b && c, "%s: null tensor", what);
+  RPDE_CHECK_ARG(ky == 1 || ky == 3, "%s: ky must be 1 (1-D) or 3 (2-D), got %d", what, ky);
   RPDE_CHECK_ARG(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: bad sizes B=%d Cin=%d Cout=%d H=%d W=%d", what, B, Cin,
                  Cout, H, W);
+  RPDE_CHECK_ARG(ky == 3 || H == 1, "%s: ky = 1 is the 1-D entry, a plane of one row (H = %d)", what, H);
   RPDE_CHECK_ARG((long)H * W < (1L << 31) && (long)B * H < (1L << 31), "%s: plane too large (H W and B H must stay below 2^31)", what);
   return RPDE_OK;
 }
 
-int rpde_cno_conv2d_k3_fwd(const float* x, const float* wt, const float* bias, float* out, int B, int Cin, int Cout, int H,
-                           int W, void* stream) {
-  RPDE_TRY(cno_conv2d_check("cno_conv2d_k3_fwd", x, wt, out, B, Cin, Cout, H, W));
-  return cno_conv_taps(x, wt, bias, out, B, Cin, Cout, 3, H, W, false, as_stream(stream));
+// the units the weight gradient's slices are made of: image rows (b, y); Conv1d is one unit and so one slice
+static long conv_k3_units(int B, int H, int ky) { return ky == 1 ? 1 : (long)B * H; }
+
+int rpde_conv_k3_fwd(const float* x, const float* wt, const float* bias, float* out, int B, int Cin, int Cout, int H, int W,
+                     int ky, void* stream) {
+  RPDE_TRY(conv_k3_check("conv_k3_fwd", x, wt, out, B, Cin, Cout, H, W, ky));
+  return cno_conv_taps(x, wt, bias, out, B, Cin, Cout, ky, H, W, false, as_stream(stream));
 }
 
-int rpde_cno_conv2d_k3_bwd_data(const float* g, const float* wt, float* gx, int B, int Cin, int Cout, int H, int W,
-                                void* stream) {
-  RPDE_TRY(cno_conv2d_check("cno_conv2d_k3_bwd_data", g, wt, gx, B, Cin, Cout, H, W));
-  return cno_conv_taps(g, wt, nullptr, gx, B, Cout, Cin, 3, H, W, true, as_stream(stream));
+int rpde_conv_k3_bwd_data(const float* g, const float* wt, float* gx, int B, int Cin, int Cout, int H, int W, int ky,
+                          void* stream) {
+  RPDE_TRY(conv_k3_check("conv_k3_bwd_data", g, wt, gx, B, Cin, Cout, H, W, ky));
+  return cno_conv_taps(g, wt, nullptr, gx, B, Cout, Cin, ky, H, W, true, as_stream(stream));
 }
 
-int rpde_cno_conv2d_k3_bwd_weight_slices(int B, int Cin, int Cout, int H, int W) {
+int rpde_conv_k3_bwd_weight_slices(int B, int Cin, int Cout, int H, int W, int ky) {
   if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return 0;
-  return c2w_slices(B, Cin, Cout, H, W);
+  return wgrad_slices(Cin, Cout, conv_k3_units(B, H, ky), (long)B * H * W);
 }
 
-int rpde_cno_conv2d_k3_bwd_weight(const float* x, const float* g, float* gw, float* gb, int B, int Cin, int Cout, int H, int W,
-                                  float* partial, int partial_slices, void* stream) {
-  const char* what = "cno_conv2d_k3_bwd_weight";
-  RPDE_TRY(cno_conv2d_check(what, x, g, gw, B, Cin, Cout, H, W));
-  const int slices = c2w_slices(B, Cin, Cout, H, W);
-  RPDE_CHECK_ARG(slices == 1 || (partial && partial_slices >= slices),
-                 "%s: partial sums of %d slices needed, the buffer holds %d", what, slices, partial ? partial_slices : 0);
-  return cno_conv_wgrad(what, x, g, gw, gb, B, Cin, Cout, 3, H, W, slices, partial, as_stream(stream));
+int rpde_conv_k3_bwd_weight(const float* x, const float* g, float* gw, float* gb, int B, int Cin, int Cout, int H, int W,
+                            int ky, float* partial, int partial_slices, void* stream) {
+  const char* what = "conv_k3_bwd_weight";
+  RPDE_TRY(conv_k3_check(what, x, g, gw, B, Cin, Cout, H, W, ky));
+  const auto run = ky == 1 ? wgrad_sliced<ConvK3Wgrad<1>> : wgrad_sliced<ConvK3Wgrad<3>>;
+  return run(what, x, g, gw, gb, B, Cin, Cout, H, W, conv_k3_units(B, H, ky), partial, partial_slices, as_stream(stream));
 }
 
 int rpde_cno_moments(const float* a, const float* b, double* sums, int B, int C, int n, void* stream) {

@@ -4,9 +4,7 @@
 // gradient.  1-D is the 2-D entry on a plane of one row with one row of taps (KY = 1).  DESIGN.md 10.18.  gfx950 (CDNA4,
 // wave64) only.
 #include "cno.h"
-#include "wave.h"
-
-#include <algorithm>
+#include "wgrad_sliced.h"
 
 namespace rpde {
 
@@ -275,90 +273,30 @@ k_unet_upconv(const float* __restrict__ src, const float* __restrict__ w, const 
   }
 }
 
-// gw[ci][co][t] = sum_p x[ci][p] g[co T + t][p],  gb[co] = sum_{p, t} g[co T + t][p]: a workgroup owns a 4 x 4 tile of
-// (ci, co) and one slice of the points, as k_cno_conv_wgrad does (cno_layers.hip): every thread walks the slice's points
-// tid, tid + 256, ..., then the workgroup adds up in a fixed order; several slices leave partial sums
-// [slice][Cin Cout T + Cout] that sum_slices adds in slice order.  No atomics
-constexpr int UW_WG = 4;
-constexpr int UW_TARGET = 512;        // workgroups wanted: two per CU
-constexpr int UW_MIN_POINTS = 256;    // a slice holds at least one point per thread
-
+// gw[ci][co][t] = sum_p x[ci][p] g[co T + t][p],  gb[co] = sum_{p, t} g[co T + t][p], on the sliced scaffold of
+// wgrad_sliced.h: x is the narrow operand, the 2 KY taps of g the wide one.  The slices are runs of points
 template <int KY>
-__global__ void __launch_bounds__(256)
-k_unet_upconv_wgrad(const float* __restrict__ x, const float* __restrict__ g, float* __restrict__ gw, float* __restrict__ gb,
-                    long slice_stride, long NP, int Cin, int Cout, int H, int W, long points_per_slice) {
-  constexpr int T = 2 * KY, N_GW = UW_WG * UW_WG * T;
-  __shared__ float red[4][N_GW + UW_WG];
-  const int ci0 = blockIdx.x * UW_WG, co0 = blockIdx.y * UW_WG;
-  const long p_lo = blockIdx.z * points_per_slice, p_hi = p_lo + points_per_slice < NP ? p_lo + points_per_slice : NP;
-  const long plane = (long)H * W, big_plane = plane * T;
-  float acc[UW_WG][UW_WG][T], accb[UW_WG];
-#pragma unroll
-  for (int j = 0; j < UW_WG; ++j) {
-    accb[j] = 0.f;
-#pragma unroll
-    for (int i = 0; i < UW_WG; ++i)
-#pragma unroll
-      for (int t = 0; t < T; ++t) acc[i][j][t] = 0.f;
+struct UpconvWgrad {
+  static constexpr int T = 2 * KY;
+  static constexpr bool G_NARROW = false;
+  int W;
+  long p_lo, plane, big_plane, b, q, y, xx;
+  __device__ UpconvWgrad(int H, int W_, long p_lo_) : W(W_), p_lo(p_lo_), plane((long)H * W_), big_plane(plane * T) {}
+  __device__ __forceinline__ void seek(long i) {
+    const long p = p_lo + i;
+    b = p / plane; q = p - b * plane;
+    y = q / W; xx = q - y * W;
   }
-  for (long p = p_lo + threadIdx.x; p < p_hi; p += 256) {
-    const long b = p / plane, q = p - b * plane;
-    const long y = q / W, xx = q - y * W;
-    float xv[UW_WG], gv[UW_WG][T];
-#pragma unroll
-    for (int i = 0; i < UW_WG; ++i) xv[i] = ci0 + i < Cin ? x[(b * Cin + ci0 + i) * plane + q] : 0.f;
-#pragma unroll
-    for (int j = 0; j < UW_WG; ++j) {
-      const bool live = co0 + j < Cout;
-      const float* at = g + (b * Cout + (live ? co0 + j : 0)) * big_plane + (long)KY * y * 2 * W + 2 * xx;
-#pragma unroll
-      for (int t = 0; t < T; ++t) {
-        gv[j][t] = live ? at[(long)(t >> 1) * 2 * W + (t & 1)] : 0.f;
-        accb[j] += gv[j][t];
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < UW_WG; ++i)
-#pragma unroll
-      for (int j = 0; j < UW_WG; ++j)
-#pragma unroll
-        for (int t = 0; t < T; ++t) acc[i][j][t] = fmaf(xv[i], gv[j][t], acc[i][j][t]);
+  __device__ __forceinline__ float narrow(const float* __restrict__ x, int Cin, int ci) const {
+    return ci < Cin ? x[(b * Cin + ci) * plane + q] : 0.f;
   }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  __device__ __forceinline__ void wide(const float* __restrict__ g, int Cout, int co, float (&gv)[T]) const {
+    const bool live = co < Cout;
+    const float* at = g + (b * Cout + (live ? co : 0)) * big_plane + (long)KY * y * 2 * W + 2 * xx;
 #pragma unroll
-  for (int i = 0; i < UW_WG; ++i)
-#pragma unroll
-    for (int j = 0; j < UW_WG; ++j)
-#pragma unroll
-      for (int t = 0; t < T; ++t) {
-        const float v = wave_sum_dpp(acc[i][j][t]);
-        if (lane == 0) red[wave][(i * UW_WG + j) * T + t] = v;
-      }
-#pragma unroll
-  for (int j = 0; j < UW_WG; ++j) {
-    const float v = wave_sum_dpp(accb[j]);
-    if (lane == 0) red[wave][N_GW + j] = v;
+    for (int t = 0; t < T; ++t) gv[t] = live ? at[(long)(t >> 1) * 2 * W + (t & 1)] : 0.f;
   }
-  __syncthreads();
-  const int k = threadIdx.x;
-  if (k < N_GW + UW_WG) {
-    const float v = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
-    if (k < N_GW) {
-      const int i = k / (UW_WG * T), j = (k / T) % UW_WG, t = k % T;
-      if (ci0 + i < Cin && co0 + j < Cout) gw[blockIdx.z * slice_stride + ((long)(ci0 + i) * Cout + co0 + j) * T + t] = v;
-    } else if (gb && blockIdx.x == 0 && co0 + (k - N_GW) < Cout) {
-      gb[blockIdx.z * slice_stride + co0 + k - N_GW] = v;
-    }
-  }
-}
-
-// slices of the points the weight gradient is split over: the one place the query and the launch take the count from
-static int uw_slices(int B, int Cin, int Cout, int H, int W) {
-  const long tiles = (long)((Cin + UW_WG - 1) / UW_WG) * ((Cout + UW_WG - 1) / UW_WG);
-  const long points = (long)B * H * W;
-  const long n = std::min<long>(UW_TARGET / tiles, points / UW_MIN_POINTS);
-  return (int)std::max<long>(1, std::min<long>(n, 65535));
-}
+};
 
 constexpr int UNET_MAX = 1 << 24;
 
@@ -458,30 +396,15 @@ int rpde_unet_upconv_bwd_data(const float* g, const float* w, float* gx, int B, 
 
 int rpde_unet_upconv_bwd_weight_slices(int B, int Cin, int Cout, int H, int W) {
   if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return 0;
-  return uw_slices(B, Cin, Cout, H, W);
+  return wgrad_slices(Cin, Cout, (long)B * H * W, (long)B * H * W);
 }
 
 int rpde_unet_upconv_bwd_weight(const float* x, const float* g, float* gw, float* gb, int B, int Cin, int Cout, int H, int W,
                                 int ky, float* partial, int partial_slices, void* stream) {
   const char* what = "unet_upconv_bwd_weight";
   RPDE_TRY(upconv_check(what, x, g, gw, B, Cin, Cout, H, W, ky));
-  const int slices = uw_slices(B, Cin, Cout, H, W);
-  RPDE_CHECK_ARG(slices == 1 || (partial && partial_slices >= slices),
-                 "%s: partial sums of %d slices needed, the buffer holds %d", what, slices, partial ? partial_slices : 0);
-  const dim3 grid((unsigned)((Cin + UW_WG - 1) / UW_WG), (unsigned)((Cout + UW_WG - 1) / UW_WG), (unsigned)slices);
-  RPDE_CHECK_ARG(grid.y <= 65535, "%s: too many output channels (%d)", what, Cout);
-  const long NP = (long)B * H * W, per_slice = (NP + slices - 1) / slices;
-  const long n_gw = 2L * ky * Cin * Cout, n_gb = Cout;
-  // one slice: the sums are the result; more: partial sums, then their sum
-  float* to_w = slices == 1 ? gw : partial;
-  float* to_b = slices == 1 ? gb : partial + n_gw;
-  const long stride = slices == 1 ? 0L : n_gw + n_gb;
-  hipStream_t st = as_stream(stream);
-  if (ky == 1) hipLaunchKernelGGL(k_unet_upconv_wgrad<1>, grid, dim3(256), 0, st, x, g, to_w, to_b, stride, NP, Cin, Cout, H, W, per_slice);
-  else hipLaunchKernelGGL(k_unet_upconv_wgrad<2>, grid, dim3(256), 0, st, x, g, to_w, to_b, stride, NP, Cin, Cout, H, W, per_slice);
-  RPDE_LAUNCH_CHECK();
-  if (slices == 1) return RPDE_OK;
-  return sum_slices(partial, gw, gb, n_gw, n_gb, slices, st);
+  const auto run = ky == 1 ? wgrad_sliced<UpconvWgrad<1>> : wgrad_sliced<UpconvWgrad<2>>;
+  return run(what, x, g, gw, gb, B, Cin, Cout, H, W, (long)B * H * W, partial, partial_slices, as_stream(stream));
 }
 
 }  // extern "C"

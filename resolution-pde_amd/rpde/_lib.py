@@ -199,18 +199,15 @@ _SIGNATURES = {
     "rpde_adamw_apply_dev_clip": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _P, _P, _P]),
     "rpde_cno_act1d_fwd": (_I, [_P] * 4 + [_I] * 5 + [_F] + [_P, _P, _I] * 2 + [_P]),
     "rpde_cno_act1d_bwd": (_I, [_P] * 5 + [_I] * 5 + [_F] + [_P, _P, _I] * 3 + [_P]),
-    "rpde_cno_conv1d_k3_fwd": (_I, [_P] * 4 + [_I] * 4 + [_P]),
-    "rpde_cno_conv1d_k3_bwd_data": (_I, [_P] * 3 + [_I] * 4 + [_P]),
-    "rpde_cno_conv1d_k3_bwd_weight": (_I, [_P] * 4 + [_I] * 4 + [_P]),
+    "rpde_conv_k3_fwd": (_I, [_P] * 4 + [_I] * 6 + [_P]),
+    "rpde_conv_k3_bwd_data": (_I, [_P] * 3 + [_I] * 6 + [_P]),
+    "rpde_conv_k3_bwd_weight_slices": (_I, [_I] * 6),
+    "rpde_conv_k3_bwd_weight": (_I, [_P] * 4 + [_I] * 6 + [_P, _I, _P]),
     "rpde_cno_moments": (_I, [_P] * 3 + [_I] * 3 + [_P]),
     "rpde_cno_affine": (_I, [_P] * 7 + [_I] * 3 + [_P]),
     "rpde_cno_act2d_plan": (_I, [_I] * 9 + [_P] * 3),
     "rpde_cno_act2d_fwd": (_I, [_P] * 4 + [_I] * 8 + [_F] + [_P, _P, _I] * 4 + [_P]),
     "rpde_cno_act2d_bwd": (_I, [_P] * 5 + [_I] * 8 + [_F] + [_P, _P, _I] * 6 + [_P]),
-    "rpde_cno_conv2d_k3_fwd": (_I, [_P] * 4 + [_I] * 5 + [_P]),
-    "rpde_cno_conv2d_k3_bwd_data": (_I, [_P] * 3 + [_I] * 5 + [_P]),
-    "rpde_cno_conv2d_k3_bwd_weight_slices": (_I, [_I] * 5),
-    "rpde_cno_conv2d_k3_bwd_weight": (_I, [_P] * 4 + [_I] * 5 + [_P, _I, _P]),
     "rpde_unet_tanh_pool_fwd": (_I, [_P] * 5 + [_I] * 5 + [_P]),
     "rpde_unet_tanh_pool_bwd": (_I, [_P] * 4 + [_I] * 5 + [_P]),
     "rpde_unet_upconv_fwd": (_I, [_P] * 4 + [_I] * 6 + [_P]),

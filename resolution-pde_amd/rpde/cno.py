@@ -2,7 +2,8 @@
 autograd Functions over the fused alias-free activation kernels in 1-D and 2-D, and the rest of a CNO block -- Conv1d /
 Conv2d (k = 3), BatchNorm, the skip add -- over their kernels (csrc/cno.hip and csrc/cno2d.hip: the activation of each
 rank; csrc/cno_layers.hip: the rest; the CNO groups of include/rpde.h).  One Function per operation serves both ranks
-and picks the C entry by the tensor's rank; the public names below are the argument-checking fronts.
+(the activation picks the C entry by the tensor's rank, the convolution's entries take both as a plane with ky rows of
+taps); the public names below are the argument-checking fronts.
 
 CNO_LReLu (reference models/CNO1d.py:30-45) is  resample to 2 in_size -> LeakyReLU -> resample to out_size, both
 resamplings being F.interpolate(mode="bicubic", antialias=True, align_corners=False) on a (1, n) image: the identity
@@ -242,55 +243,53 @@ def _points(x: torch.Tensor) -> int:
     return int(x.shape[2]) if x.dim() == 3 else int(x.shape[2]) * int(x.shape[3])
 
 
+def _plane(x: torch.Tensor, rows: int):
+    """(H, W, ky) of a channels-first tensor as the kernels see it: [B, C, n] is a plane of one row with one row of taps
+    or windows, [B, C, H, W] has `rows` of them"""
+    return (1, int(x.shape[2]), 1) if x.dim() == 3 else (int(x.shape[2]), int(x.shape[3]), rows)
+
+
+def _bwd_weight(entry: str, x, g, gw, gb, dims, ky: int, slice_args) -> None:
+    """gw and gb (or None) from rpde_<entry>(x, g, gw, gb, *dims, ky, partial, slices, stream), the weight gradient of
+    _ConvK3 and of rpde/unet.py's _UpConv: more than one slice leaves partial sums [slices][gw.numel() + Cout]"""
+    lib = load()
+    slices = getattr(lib, f"rpde_{entry}_slices")(*slice_args)
+    part = torch.empty(slices, gw.numel() + dims[2], dtype=torch.float32, device=x.device) if slices > 1 else None
+    check(getattr(lib, f"rpde_{entry}")(ptr(x), ptr(g), ptr(gw), ptr(gb), *dims, ky, ptr(part), slices, stream_ptr()), entry)
+
+
 class _ConvK3(torch.autograd.Function):
-    """Conv(k = 3, padding = 1) of x's rank: [B, Cin, n] with w [Cout, Cin, 3] through rpde_cno_conv1d_k3_*,
-    [B, Cin, H, W] with w [Cout, Cin, 3, 3] through rpde_cno_conv2d_k3_*"""
+    """Conv(k = 3, padding = 1) of x's rank through rpde_conv_k3_*: [B, Cin, n] with w [Cout, Cin, 3] is the plane
+    [B, Cin, 1, n] with one row of taps, [B, Cin, H, W] with w [Cout, Cin, 3, 3] has three"""
 
     @staticmethod
     def forward(ctx, x, w, b):
-        lib = load()
         x = _f32c(x)
-        Cout = w.shape[0]
+        H, W, ky = _plane(x, 3)
+        B, Cin, Cout = int(x.shape[0]), int(x.shape[1]), int(w.shape[0])
         bias = None if b is None else _f32c(b.detach())
-        if x.dim() == 3:
-            B, Cin, n = x.shape
-            wt = _f32c(w.detach()).permute(2, 0, 1).contiguous()          # tap-major [3, Cout, Cin]: a layout copy
-            out = torch.empty(B, Cout, n, dtype=torch.float32, device=x.device)
-            check(lib.rpde_cno_conv1d_k3_fwd(ptr(x), ptr(wt), ptr(bias), ptr(out), B, Cin, Cout, n, stream_ptr()), "cno_conv1d_k3_fwd")
-        else:
-            B, Cin, H, W = x.shape
-            wt = _f32c(w.detach()).permute(2, 3, 0, 1).reshape(9, Cout, Cin).contiguous()    # tap-major: a layout copy
-            out = torch.empty(B, Cout, H, W, dtype=torch.float32, device=x.device)
-            check(lib.rpde_cno_conv2d_k3_fwd(ptr(x), ptr(wt), ptr(bias), ptr(out), B, Cin, Cout, H, W, stream_ptr()), "cno_conv2d_k3_fwd")
+        wt = _f32c(w.detach()).reshape(Cout, Cin, 3 * ky).permute(2, 0, 1).contiguous()    # tap-major [3 ky, Cout, Cin]: a layout copy
+        out = torch.empty((B, Cout) + x.shape[2:], dtype=torch.float32, device=x.device)
+        check(load().rpde_conv_k3_fwd(ptr(x), ptr(wt), ptr(bias), ptr(out), B, Cin, Cout, H, W, ky, stream_ptr()), "conv_k3_fwd")
         ctx.save_for_backward(x, wt)
         ctx.has_bias = b is not None
         return out
 
     @staticmethod
     def backward(ctx, g):
-        lib = load()
         x, wt = ctx.saved_tensors
-        B, Cin, *sizes = x.shape
-        Cout, one_d = wt.shape[1], x.dim() == 3
+        H, W, ky = _plane(x, 3)
+        dims = (int(x.shape[0]), int(x.shape[1]), int(wt.shape[1]), H, W)
+        Cin, Cout = dims[1:3]
         g = _f32c(g)
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
             gx = torch.empty_like(x)
-            if one_d:
-                check(lib.rpde_cno_conv1d_k3_bwd_data(ptr(g), ptr(wt), ptr(gx), B, Cin, Cout, *sizes, stream_ptr()), "cno_conv1d_k3_bwd_data")
-            else:
-                check(lib.rpde_cno_conv2d_k3_bwd_data(ptr(g), ptr(wt), ptr(gx), B, Cin, Cout, *sizes, stream_ptr()), "cno_conv2d_k3_bwd_data")
+            check(load().rpde_conv_k3_bwd_data(ptr(g), ptr(wt), ptr(gx), *dims, ky, stream_ptr()), "conv_k3_bwd_data")
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            gw = torch.empty((Cout, Cin, 3) if one_d else (Cout, Cin, 3, 3), dtype=torch.float32, device=x.device)
+            gw = torch.empty((Cout, Cin) + (3,) * (x.dim() - 2), dtype=torch.float32, device=x.device)
             gb = torch.empty(Cout, dtype=torch.float32, device=x.device) if ctx.has_bias else None
-            if one_d:                                  # one slice, no partial sums
-                check(lib.rpde_cno_conv1d_k3_bwd_weight(ptr(x), ptr(g), ptr(gw), ptr(gb), B, Cin, Cout, *sizes, stream_ptr()),
-                      "cno_conv1d_k3_bwd_weight")
-            else:
-                slices = lib.rpde_cno_conv2d_k3_bwd_weight_slices(B, Cin, Cout, *sizes)      # > 1: partial sums per slice
-                part = torch.empty(slices, 9 * Cout * Cin + Cout, dtype=torch.float32, device=x.device) if slices > 1 else None
-                check(lib.rpde_cno_conv2d_k3_bwd_weight(ptr(x), ptr(g), ptr(gw), ptr(gb), B, Cin, Cout, *sizes, ptr(part), slices,
-                                                        stream_ptr()), "cno_conv2d_k3_bwd_weight")
+            _bwd_weight("conv_k3_bwd_weight", x, g, gw, gb, dims, ky, dims + (ky,))
         return gx, gw, gb
 
 

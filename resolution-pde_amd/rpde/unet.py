@@ -15,17 +15,12 @@ from typing import Optional
 import torch
 
 from ._lib import check, load, ptr, stream_ptr
-from .cno import _affine, _bn_backward, _bn_statistics, _f32c, _moments, _points
-
-
-def _plane(x: torch.Tensor):
-    """(H, W, ky) of a channels-first tensor as the kernels see it"""
-    return (1, int(x.shape[2]), 1) if x.dim() == 3 else (int(x.shape[2]), int(x.shape[3]), 2)
+from .cno import _affine, _bn_backward, _bn_statistics, _bwd_weight, _f32c, _moments, _plane, _points
 
 
 def _tanh_pool_fwd(z, scale, shift, pool: bool, fold_batch: bool):
     """act = tanh(scale z + shift) and, with pool, its MaxPool(2); fold_batch: scale / shift are per (sample, channel)"""
-    H, W, ky = _plane(z)
+    H, W, ky = _plane(z, 2)
     B, Cc = int(z.shape[0]), int(z.shape[1])
     act = torch.empty_like(z)
     pooled = None
@@ -40,7 +35,7 @@ def _tanh_pool_fwd(z, scale, shift, pool: bool, fold_batch: bool):
 
 
 def _tanh_pool_bwd(act, g_act, g_pool):
-    H, W, ky = _plane(act)
+    H, W, ky = _plane(act, 2)
     gy = torch.empty_like(act)
     g_act, g_pool = (None if g is None else _f32c(g) for g in (g_act, g_pool))
     check(load().rpde_unet_tanh_pool_bwd(ptr(act), ptr(g_act), ptr(g_pool), ptr(gy), int(act.shape[0]), int(act.shape[1]), H, W,
@@ -165,7 +160,7 @@ class _UpConv(torch.autograd.Function):
     def forward(ctx, x, w, b):
         x, wc = _f32c(x), _f32c(w.detach())
         bias = None if b is None else _f32c(b.detach())
-        H, W, ky = _plane(x)
+        H, W, ky = _plane(x, 2)
         B, Cin, Cout = int(x.shape[0]), int(x.shape[1]), int(w.shape[1])
         out = torch.empty((B, Cout, 2 * W) if ky == 1 else (B, Cout, 2 * H, 2 * W), dtype=torch.float32, device=x.device)
         check(load().rpde_unet_upconv_fwd(ptr(x), ptr(wc), ptr(bias), ptr(out), B, Cin, Cout, H, W, ky, stream_ptr()), "unet_upconv_fwd")
@@ -175,22 +170,18 @@ class _UpConv(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        lib = load()
         x, wc = ctx.saved_tensors
-        H, W, ky = _plane(x)
-        B, Cin, Cout = int(x.shape[0]), int(x.shape[1]), int(wc.shape[1])
+        H, W, ky = _plane(x, 2)
+        dims = (int(x.shape[0]), int(x.shape[1]), int(wc.shape[1]), H, W)
         g = _f32c(g)
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
             gx = torch.empty_like(x)
-            check(lib.rpde_unet_upconv_bwd_data(ptr(g), ptr(wc), ptr(gx), B, Cin, Cout, H, W, ky, stream_ptr()), "unet_upconv_bwd_data")
+            check(load().rpde_unet_upconv_bwd_data(ptr(g), ptr(wc), ptr(gx), *dims, ky, stream_ptr()), "unet_upconv_bwd_data")
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
             gw = torch.empty_like(wc)
-            gb = torch.empty(Cout, dtype=torch.float32, device=x.device) if ctx.has_bias else None
-            slices = lib.rpde_unet_upconv_bwd_weight_slices(B, Cin, Cout, H, W)      # > 1: partial sums per slice
-            part = torch.empty(slices, wc.numel() + Cout, dtype=torch.float32, device=x.device) if slices > 1 else None
-            check(lib.rpde_unet_upconv_bwd_weight(ptr(x), ptr(g), ptr(gw), ptr(gb), B, Cin, Cout, H, W, ky, ptr(part), slices,
-                                                  stream_ptr()), "unet_upconv_bwd_weight")
+            gb = torch.empty(dims[2], dtype=torch.float32, device=x.device) if ctx.has_bias else None
+            _bwd_weight("unet_upconv_bwd_weight", x, g, gw, gb, dims, ky, dims)
         return gx, gw, gb
 
 

@@ -81,9 +81,12 @@ def test_conv2d_k3(gpu_device, H, W, Cin, Cout):
 
 
 def test_conv2d_weight_gradient_slices():
-    """the slice counts the docstring states (rpde_cno_conv2d_k3_bwd_weight_slices; no device needed)"""
+    """the slice counts the docstring states (rpde_conv_k3_bwd_weight_slices at ky = 3; no device needed)"""
     from rpde import _lib
-    slices = _lib.load().rpde_cno_conv2d_k3_bwd_weight_slices
+    query = _lib.load().rpde_conv_k3_bwd_weight_slices
+
+    def slices(*dims):
+        return query(*dims, 3)
 
     assert [slices(B, 8, 8, 5, 7) for B in (1, 3)] == [1, 1]
     assert [slices(B, 8, 8, 16, 16) for B in (1, 3)] == [1, 3]
@@ -198,9 +201,9 @@ def test_conv2d_weight_gradient_refuses_a_short_partial_buffer(gpu_device):
     x, g = torch.zeros(B, Cin, H, W, device=gpu_device), torch.zeros(B, Cout, H, W, device=gpu_device)
     gw, gb = torch.zeros(Cout, Cin, 3, 3, device=gpu_device), torch.zeros(Cout, device=gpu_device)
     part = torch.zeros(2, 9 * Cout * Cin + Cout, device=gpu_device)
-    args = (_lib.ptr(x), _lib.ptr(g), _lib.ptr(gw), _lib.ptr(gb), B, Cin, Cout, H, W)
+    args = (_lib.ptr(x), _lib.ptr(g), _lib.ptr(gw), _lib.ptr(gb), B, Cin, Cout, H, W, 3)
     for buf, n in ((None, 0), (_lib.ptr(part), 2)):
-        assert lib.rpde_cno_conv2d_k3_bwd_weight(*args, buf, n, _lib.stream_ptr()) == _lib.ERR_ARG
+        assert lib.rpde_conv_k3_bwd_weight(*args, buf, n, _lib.stream_ptr()) == _lib.ERR_ARG
         assert "3 slices" in lib.rpde_last_error().decode()
-    assert lib.rpde_cno_conv2d_k3_bwd_weight(None, *args[1:], None, 0, _lib.stream_ptr()) == _lib.ERR_ARG
+    assert lib.rpde_conv_k3_bwd_weight(None, *args[1:], None, 0, _lib.stream_ptr()) == _lib.ERR_ARG
     assert "null" in lib.rpde_last_error().decode()

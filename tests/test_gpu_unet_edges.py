@@ -15,9 +15,11 @@ tests/test_unet_edges_ref_cpu.py proves without a device that the shapes below l
 * upconv's weight gradient over 2, 3 and 7 slices (a slice of 257 points, a boundary at the batch boundary, inside a
   plane and inside a row, a shorter last slice), with and without bias: integer operands give y, dx, dw, db bit-equal to
   float64; random operands meet the budgets and repeat to the bit.  The weight gradient again through the C ABI with
-  guard words behind x and g: a point loop that runs past the last point adds them in.
+  guard words behind x and g: a point loop that runs past the last point adds them in.  The same for Conv2d(k = 3),
+  whose slices are whole image rows: a short last slice, and a last slice that starts past the last row and must
+  contribute zeros.
 * upconv and Conv(k = 3) at the shipped channel counts on a few points (1024 -> 512: 32 row tiles and 64 K steps of
-  k_unet_upconv, a 256 x 128 grid of k_cno_conv_wgrad), and Conv1d's point loop over four and eight trips: budgets on
+  k_unet_upconv, a 256 x 128 grid of k_wgrad_sliced), and Conv1d's point loop over four and eight trips: budgets on
   random operands; on integer operands dw and db (fmaf chains, fixed-order sums) are bit-equal to float64.
 * UNet2d at width 16 and UNet1d at width 32 (BatchNorm and GroupNorm), one training step against the float64
   stock_forward of tests/unet_ref.py: per tensor max(budget, 3 x floor), the floor being the float32 CPU stock run's own
@@ -63,6 +65,8 @@ UP_WIDE = [(2, 1, 512, 256, 2, 2), (2, 1, 1024, 512, 1, 2), (1, 2, 1024, 512, 1,
 # (B, Cin, Cout, *sizes)
 CONV_1D = [(3, 5, 6, 300), (2, 8, 8, 1024), (2, 1024, 512, 4)]
 CONV_2D = [(2, 512, 256, 2, 2)]
+# (B, Cin, Cout, H, W) -> (slices, image rows per slice) of Conv2d(k = 3)'s weight gradient
+CONV_SLICED = {(3, 5, 6, 33, 20): (7, 15), (3, 5, 6, 3, 180): (6, 2)}
 # (kind, constructor arguments, input, seed); of the seeds 0 .. 5 the one with the lowest worst floor (1.7e-6 to 3.6e-6
 # where they were scanned, 3.1e-6 to 8.1e-6 over all six): the condition floor <= 1e-5 keeps a margin on another host
 MODELS = [("UNet2d", dict(in_channels=3, out_channels=2, width=16), (2, 3, 32, 32), 0),
@@ -333,6 +337,35 @@ def test_upconv_weight_gradient_reads_no_point_past_the_last(gpu_device, case, w
     assert _guards_intact(gw_buf, gw, 7.0) and _guards_intact(part_buf, part, 7.0)
     if with_bias:
         assert torch.equal(gb.cpu().double(), want[3]) and _guards_intact(gb_buf, gb, 7.0)
+
+
+@pytest.mark.parametrize("with_bias", [True, False])
+@pytest.mark.parametrize("case", list(CONV_SLICED))
+def test_conv_weight_gradient_reads_no_row_past_the_last(gpu_device, case, with_bias):
+    """slices x rows-per-slice exceeds the image rows B H: the last slice is short (7 x 15 = 105 > 99) or starts past the
+    last row (slice 5 of 6 x 2 starts at row 10 > 9) and must leave zeros in its partial sums, which start as 5.  Through
+    the C ABI with integer operands (no sum above 1980 x 3 x 3 < 2^24) and guard words of 3 behind x and g, where a point
+    loop that ran to the slice's nominal end would read: dw and db stay bit-equal to float64"""
+    from rpde import _lib
+    lib, dev = _lib.load(), gpu_device
+    B, Cin, Cout, H, W = case
+    slices, rows = CONV_SLICED[case]
+    assert lib.rpde_conv_k3_bwd_weight_slices(B, Cin, Cout, H, W, 3) == slices and slices * rows > B * H
+    x, w, b, up = conv_operands(case, True)
+    ref = _conv_run(lambda *a: F.conv2d(*a, padding=1), *[t.double() for t in (x, w, b, up)])
+    samples_past = (slices * rows - 1) // H + 1 - B                      # whole samples the nominal end reaches into
+    assert samples_past >= 1
+    xg, _ = _guarded(x, samples_past * Cin * H * W, dev, 3.0)
+    gg, _ = _guarded(up, samples_past * Cout * H * W, dev, 3.0)
+    gw, gw_buf = _guarded(torch.full_like(w, 5.0), 64, dev, 7.0)
+    gb, gb_buf = _guarded(torch.full((Cout,), 5.0), 64, dev, 7.0) if with_bias else (None, None)
+    part, part_buf = _guarded(torch.full((slices, w.numel() + Cout), 5.0), 64, dev, 7.0)
+    _lib.check(lib.rpde_conv_k3_bwd_weight(_lib.ptr(xg), _lib.ptr(gg), _lib.ptr(gw), _lib.ptr(gb), B, Cin, Cout, H, W, 3,
+                                           _lib.ptr(part), slices, _lib.stream_ptr()), "conv_k3_bwd_weight")
+    assert torch.equal(gw.cpu().double(), ref["dw"])
+    assert _guards_intact(gw_buf, gw, 7.0) and _guards_intact(part_buf, part, 7.0)
+    if with_bias:
+        assert torch.equal(gb.cpu().double(), ref["db"]) and _guards_intact(gb_buf, gb, 7.0)
 
 
 # ---- 5. Conv(k = 3): the point loop over several trips, the shipped channel counts ------------------------------------

@@ -68,6 +68,19 @@ def test_upconv_slice_table():
         assert query(B, Cin, Cout, H, W) == 1 == R.upconv_slices(B, Cin, Cout, H, W)[0]
 
 
+def test_conv_slice_table():
+    from rpde import _lib
+    query = _lib.load().rpde_conv_k3_bwd_weight_slices
+    for (B, Cin, Cout, H, W), (slices, rows) in E.CONV_SLICED.items():
+        assert query(B, Cin, Cout, H, W, 3) == slices and R.conv_slices(B, Cin, Cout, H, W) == (slices, rows)
+        assert slices * rows > B * H and rows * W > 256           # past the last row; a second trip of the thread loop
+    assert E.CONV_SLICED[(3, 5, 6, 33, 20)] == (7, 15) and 6 * 15 < 99 < 7 * 15        # the last slice is short
+    assert E.CONV_SLICED[(3, 5, 6, 3, 180)] == (6, 2) and 5 * 2 > 9                    # the last slice is empty
+    # Conv1d keeps its one slice whatever the shape
+    for B, Cin, Cout, n in E.CONV_1D:
+        assert query(B, Cin, Cout, 1, n, 1) == 1
+
+
 def test_conv_cases_reach_the_trips_and_the_grid():
     trips = [(B * n + 255) // 256 for B, _, _, n in E.CONV_1D]
     assert trips == [4, 8, 1] and (3 * 300) % 256                 # four trips, the last one ragged; eight whole ones
@@ -92,7 +105,7 @@ def test_upconv_integer_operands_stay_exact_in_fp32(case, with_bias):
     assert bound < 2 ** 24
 
 
-@pytest.mark.parametrize("case", E.CONV_1D + E.CONV_2D)
+@pytest.mark.parametrize("case", E.CONV_1D + E.CONV_2D + list(E.CONV_SLICED))
 def test_conv_integer_operands_stay_exact_in_fp32(case):
     import torch.nn.functional as F
     x, w, b, up = _abs(E.conv_operands(case, True))

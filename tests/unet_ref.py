@@ -117,7 +117,7 @@ def tanh_pool_bwd(act: torch.Tensor, g_act, g_pool) -> torch.Tensor:
     return g * (1.0 - a.detach() * a.detach())
 
 
-# ---- the launch arithmetic of csrc/unet.hip, restated -----------------------------------------------------------------
+# ---- the launch arithmetic of csrc/unet.hip and csrc/wgrad_sliced.h, restated ------------------------------------------
 def tp_items(shape, vec: bool = None):
     """(items, vec) of k_unet_tanh_pool_*: a thread owns ky rows x cw columns, cw = 4 on the 16-byte path (W % 4 == 0
     and aligned pointers: `vec`, by default what a fresh allocation gets) and 2 otherwise; 256 items make a workgroup"""
@@ -129,10 +129,18 @@ def tp_items(shape, vec: bool = None):
 
 
 def upconv_slices(B: int, Cin: int, Cout: int, H: int, W: int):
-    """(slices, points per slice) of k_unet_upconv_wgrad: 4 x 4 channel tiles, 512 workgroups wanted, 256 points at least"""
+    """(slices, points per slice) of upconv's weight gradient: 4 x 4 channel tiles, 512 workgroups wanted, 256 points
+    at least"""
     tiles = ((Cin + 3) // 4) * ((Cout + 3) // 4)
     slices = max(1, min(512 // tiles, B * H * W // 256, 65535))
     return slices, (B * H * W + slices - 1) // slices
+
+
+def conv_slices(B: int, Cin: int, Cout: int, H: int, W: int):
+    """(slices, image rows per slice) of Conv2d(k = 3)'s weight gradient: the same, in whole image rows (b, y)"""
+    tiles = ((Cin + 3) // 4) * ((Cout + 3) // 4)
+    slices = max(1, min(512 // tiles, B * H, B * H * W // 256, 65535))
+    return slices, (B * H + slices - 1) // slices
 
 
 # ---- whole models -----------------------------------------------------------------------------------------------------
