@@ -8,6 +8,7 @@
 // lane's hidden features followed by a sum over the four lane groups.  Nothing but x is read and nothing but out is
 // written.  Covers Cin in {32, 64}, hidden <= 128 (Cin = 32) or <= 64 (Cin = 64), Cout <= 4, S a multiple of 16; the
 // training path (which needs the hidden tensor for backward) and other shapes keep the two-convolution sequence.
+// (tests/test_gpu_eval_cf.py pins the tile loop: 1 .. 3 passes per workgroup, every <KS, MT, CO>, per tile against float64.)
 #include "h2.h"
 
 namespace rpde {

@@ -16,6 +16,7 @@
 // reduction index (frag_perm), so H never changes lanes.  Resident per wave: Wc and W1 as A fragments (registers), the
 // row's spectra t_bm as A fragments (4 loads per row); shared by the workgroup in LDS: the synthesis table Fs as ready B
 // fragments per 16-point tile, b1 and W2.  Plain loads one tile ahead; no hand-counted waits.
+// (tests/test_gpu_eval_cf.py pins the row loop: 1 .. 3 passes per workgroup, every <MT, CO>, N up to 1024, per line against float64.)
 #include "conv_small.h"
 #include "h2.h"
 

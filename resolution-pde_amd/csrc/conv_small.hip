@@ -7,6 +7,7 @@
 // contiguous per wave -- with the weights read from LDS as broadcast 16-byte pieces.  The field is read once and the
 // output written once, at the HBM rate, where the generic GEMM path (activation staged into its k-loop, fp32 MFMA)
 // reaches about half of it.
+// (tests/test_gpu_eval_cf.py pins the synthesis tail <CO, true>: whole and half rows per block, padded outputs, per line against float64.)
 #include "rpde_internal.h"
 #include "conv_small.h"
 

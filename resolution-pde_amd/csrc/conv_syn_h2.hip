@@ -21,6 +21,7 @@
 //     runs per channel like the loads.
 // No workgroup barrier.  A row's slab of x is requested one whole row ahead (two register buffers; the table fragments
 // live in LDS to make room for them).
+// (tests/test_gpu_eval_cf.py pins the row loop: 1 .. 3 passes per workgroup, all twelve instances, per line against float64.)
 #include "conv_small.h"
 #include "cw.h"
 #include "h2.h"
