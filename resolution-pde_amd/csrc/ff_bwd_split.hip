@@ -262,7 +262,16 @@ constexpr int FL_DUBUF = 0;                        // [2 blk][8 kappa][hi|lo][1 
 constexpr int FL_PAN = FL_DUBUF + 32768;           // four du1 panels                                              = 32 KB
 constexpr int FL_X = FL_PAN + 4 * FL_PANEL;        // the x panel                                                  =  8 KB
 constexpr int FL_W1 = FL_X + FL_PANEL;             // [8 k-step][4 n-tile][hi | lo][64 lanes][16 B]: W1            = 64 KB
-constexpr int FL_LDS = FL_W1 + 65536;
+constexpr int FL_W2L = FL_W1 + 65536;             // [8 wave][2 t][64 lanes][16 B]: the lo pieces of W2^T's last k-step  = 16 KB
+constexpr int FL_LDS = FL_W2L + 16384;
+#ifdef RPDE_STAMPS
+// debug build: lane 0 of waves 0, 3 and 6 of workgroup 100 records s_memtime around the phases of tiles 5 .. 12
+__device__ unsigned long long g_flstamps[3 * 64];
+#define FLSTAMP(i) do { if (stamp_on && stamp_t >= 0 && stamp_t < 8) g_flstamps[stamp_w * 64 + stamp_t * 8 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
+#else
+#define FLSTAMP(i) do { } while (0)
+#endif
+constexpr int FL_PARKED = 7;                       // .. fragments (t, kappa = 7): read back at their uses, 8 VGPRs fewer
 
 __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_ffs_layer1(const FsB A) {
   __shared__ __attribute__((aligned(16))) char smem[FL_LDS];
@@ -272,13 +281,17 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_ffs_layer1(const FsB A) {
   __shared__ float acc_db1[256];
   const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, g = l >> 4, li = l & 15;
   // ---- W2^T rows 32w .. 32w+31 -> registers; W1 -> LDS as B fragments (k = hidden channel, n = input channel) ----
-  f16x8 w2h[2][8], w2l[2][8];
+  // (two of the sixteen lo fragments wait in this wave's own 2 KB of LDS: the same values, read where they are used)
+  f16x8 w2h[2][8], w2l[2][FL_PARKED];
+  char* const parked = smem + FL_W2L + w * 2048 + l * 16;
   {
     const char* base = A.wimg + (long)w * FF3_WAVE_IMG + l * 16;
 #pragma unroll
     for (int f = 0; f < 16; ++f) {
       w2h[f >> 3][f & 7] = *reinterpret_cast<const f16x8*>(base + (4 + f) * 2048);
-      w2l[f >> 3][f & 7] = *reinterpret_cast<const f16x8*>(base + (4 + f) * 2048 + 1024);
+      const f16x8 lo = *reinterpret_cast<const f16x8*>(base + (4 + f) * 2048 + 1024);
+      if ((f & 7) < FL_PARKED) w2l[f >> 3][f & 7] = lo;
+      else *reinterpret_cast<f16x8*>(parked + (f >> 3) * 1024) = lo;
     }
   }
   if (tid < 256) acc_db1[tid] = 0.f;
@@ -323,10 +336,15 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_ffs_layer1(const FsB A) {
   const int xrow = tid >> 4, xc = tid & 15;
   float4 du2r[4], d1r[4], xr;
   float bzr[2];
-  // (addresses as a per-tile uniform base plus a 32-bit lane offset: a 64-bit pointer per load spilled)
+  // (addresses as a per-tile uniform base plus a 32-bit lane offset: a 64-bit pointer per load spilled.  Every load is
+  //  issued in every pass and by every lane -- behind the last tile the last tile's again, rows past P the last point's,
+  //  neither used -- so that the number of loads in flight at each use is the same on every path through the loop and
+  //  the compiler's vmcnt waits are the exact ones: with the loads under `has_next` it waited for x with vmcnt(0), that
+  //  is for the next tile's du2 and d1 too)
   const unsigned cb = 32 * w + 4 * g;
+  const int last_tile = A.ntiles - 1;
   auto load_du2 = [&](int tile) {
-    const long t0 = (long)tile * 32;
+    const long t0 = (long)min(tile, last_tile) * 32;
     const int rmax = (int)min(31L, A.P - 1 - t0);           // rows past P read the last point's (and are not used)
     const float* __restrict__ src = A.du2 + t0 * 256;
     const float* __restrict__ bz = A.dzb + t0;
@@ -339,7 +357,7 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_ffs_layer1(const FsB A) {
     }
   };
   auto load_d1 = [&](int tile) {
-    const long t0 = (long)tile * 32;
+    const long t0 = (long)min(tile, last_tile) * 32;
     const int rmax = (int)min(31L, A.P - 1 - t0);
     const float* __restrict__ src = A.d1 + t0 * 256;
 #pragma unroll
@@ -350,9 +368,13 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_ffs_layer1(const FsB A) {
     }
   };
   auto load_x = [&](int tile) {
-    const long t0 = (long)tile * 32;
+    const long t0 = (long)min(tile, last_tile) * 32;
+    const int rmax = (int)min(31L, A.P - 1 - t0);
     const float* __restrict__ src = A.x + t0 * 64;
-    xr = t0 + xrow < A.P ? *reinterpret_cast<const float4*>(src + (unsigned)(xrow * 64 + 4 * xc)) : make_float4(0.f, 0.f, 0.f, 0.f);
+    xr = *reinterpret_cast<const float4*>(src + (unsigned)(min(xrow, rmax) * 64 + 4 * xc));
+  };
+  auto x_of = [&](int tile) {                    // .. where it is used: rows past P are zero
+    return (long)tile * 32 + xrow < A.P ? xr : make_float4(0.f, 0.f, 0.f, 0.f);
   };
 
   // ---- consumer role (k_wgrad_h2<4, 1, 4, 2, 4, 2, false, true>): du1 panel wm against x channels 32 wn .. ----
@@ -367,15 +389,10 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_ffs_layer1(const FsB A) {
   int e_run = 15, e_x = 15;                    // running exponents: this wave's du1 channels; x (the same in every wave)
   const int dg_mt = w & 1, dg_nt = w >> 1;     // this wave's tile of gx: points 16 dg_mt .., input channels 16 dg_nt ..
 
-  if ((int)blockIdx.x < A.ntiles) { load_du2(blockIdx.x); load_d1(blockIdx.x); load_x(blockIdx.x); }
-  lds_barrier();                               // W1 fragments and the zeroed sums are in LDS
-
-  for (int tile = blockIdx.x; tile < A.ntiles; tile += gridDim.x) {
-    const int next_tile = tile + gridDim.x;
-    const bool has_next = next_tile < A.ntiles;
-    const long p0 = (long)tile * 32;
-    // ---- du2 -> B fragments, slice kappa = w, one scale per point: the bound the chain derives from that of dz3 ----
-    float inv_b[2];
+  // ---- staging of a tile, from the registers its loads filled: du2 -> B fragments, slice kappa = w, one scale per point
+  // (the bound the chain derives from that of dz3), the registers free for the tile after; and the wave's maximum of x ----
+  float inv_b[2];
+  auto stage_du2 = [&]() {
 #pragma unroll
     for (int blk = 0; blk < 2; ++blk) {
       float s_du2, ai;
@@ -385,12 +402,32 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_ffs_layer1(const FsB A) {
       const float hv[8] = {a.x * s_du2, a.y * s_du2, a.z * s_du2, a.w * s_du2, b.x * s_du2, b.y * s_du2, b.z * s_du2, b.w * s_du2};
       h2_put_frag(smem + FL_DUBUF + ((blk * 8 + w) * 2) * 1024 + l * 16, hv);
     }
-    {
-      float m = fmaxf(fmaxf(fabsf(xr.x), fabsf(xr.y)), fmaxf(fabsf(xr.z), fabsf(xr.w)));
-      m = wave_max(m);
-      if (l == 0) xmax[w] = m;
-    }
+  };
+  auto stage_xmax = [&](int tile) {
+    const float4 xv = x_of(tile);
+    float m = fmaxf(fmaxf(fabsf(xv.x), fabsf(xv.y)), fmaxf(fabsf(xv.z), fabsf(xv.w)));
+    m = wave_max(m);
+    if (l == 0) xmax[w] = m;
+  };
+
+  load_du2(blockIdx.x); load_d1(blockIdx.x); load_x(blockIdx.x);      // (the grid is at most the number of tiles)
+  lds_barrier();                               // W1 fragments and the zeroed sums are in LDS
+  stage_du2(); stage_xmax(blockIdx.x);
+  load_du2(blockIdx.x + gridDim.x);
+  // (the second-dispatched half of the workgroup loses the issue arbitration against its SIMD partners in every phase:
+  //  one static priority step for it, 1589 -> 1575 us)
+  if (__builtin_amdgcn_readfirstlane(w) >= 4) __builtin_amdgcn_s_setprio(1);
+#ifdef RPDE_STAMPS
+  const bool stamp_on = blockIdx.x == 100 && l == 0 && (w == 0 || w == 3 || w == 6);
+  const int stamp_w = w == 0 ? 0 : (w == 3 ? 1 : 2);
+  int stamp_t = -4;                      // skip the first four tiles (cold caches)
+#endif
+  for (int tile = blockIdx.x; tile < A.ntiles; tile += gridDim.x) {
+    const int next_tile = tile + gridDim.x;
+    const long p0 = (long)tile * 32;
+    FLSTAMP(0);
     lds_barrier();                                                                    // 1: du2 slices and x maxima in LDS
+    FLSTAMP(1);
 
     // ---- du1 = (W2^T du2) * d1: this wave's 32 hidden rows of both point blocks ----
     float u[4][4];                               // [blk * 2 + t][r]: point 16 blk + li, row 16 (2 w + t) + 4 g + r
@@ -404,8 +441,14 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_ffs_layer1(const FsB A) {
         for (int kap = 0; kap < 8; ++kap) {
           const char* hb = smem + FL_DUBUF + ((blk * 8 + kap) * 2) * 1024 + l * 16;
           const f16x8 bh = *reinterpret_cast<const f16x8*>(hb), bl = *reinterpret_cast<const f16x8*>(hb + 1024);
-          acc[blk][0] = h2_mfma32(w2h[0][kap], w2l[0][kap], bh, bl, acc[blk][0]);
-          acc[blk][1] = h2_mfma32(w2h[1][kap], w2l[1][kap], bh, bl, acc[blk][1]);
+          if (kap < FL_PARKED) {
+            acc[blk][0] = h2_mfma32(w2h[0][kap], w2l[0][kap], bh, bl, acc[blk][0]);
+            acc[blk][1] = h2_mfma32(w2h[1][kap], w2l[1][kap], bh, bl, acc[blk][1]);
+          } else {
+            const f16x8 l0 = *reinterpret_cast<const f16x8*>(parked), l1 = *reinterpret_cast<const f16x8*>(parked + 1024);
+            acc[blk][0] = h2_mfma32(w2h[0][kap], l0, bh, bl, acc[blk][0]);
+            acc[blk][1] = h2_mfma32(w2h[1][kap], l1, bh, bl, acc[blk][1]);
+          }
         }
       }
 #pragma unroll
@@ -430,10 +473,9 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_ffs_layer1(const FsB A) {
         }
       }
     }
-    // (the next tile's loads start here, not a phase earlier -- under the 96 products, beside W2^T's 128 registers and
-    //  the 48 accumulators, they spilled -- and not later: started behind the panel writes below, 300 vector instructions
-    //  on, the kernel took 1.93 instead of 1.64 ms.  It lives on how long its loads are in flight)
-    if (has_next) { load_du2(next_tile); load_d1(next_tile); }
+    // (d1's registers are free from here, but the next tile's loads start only behind the consumer: in flight across it
+    //  they are the 16 registers its gx products need to read a half panel ahead -- 1572 -> 1532 us with both)
+    FLSTAMP(2);
 #pragma unroll
     for (int i = 0; i < 8; ++i) bsum[i] = row_sum15(bsum[i]);
     if (li == 15) {
@@ -472,17 +514,31 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_ffs_layer1(const FsB A) {
       e_x = min(e_x, 254);
       const float scale = __uint_as_float((unsigned)(268 - e_x) << 23);
       uint2 hi, lo;
-      h2_split4(xr.x * scale, xr.y * scale, xr.z * scale, xr.w * scale, hi, lo);
+      const float4 xv = x_of(tile);
+      h2_split4(xv.x * scale, xv.y * scale, xv.z * scale, xv.w * scale, hi, lo);
       const int off = stage_off(xrow, xc);
       *reinterpret_cast<uint2*>(smem + FL_X + off) = hi;
       *reinterpret_cast<uint2*>(smem + FL_X + 4096 + off) = lo;
     }
-    if (has_next) load_x(next_tile);
+    load_x(next_tile);
+    FLSTAMP(3);
     lds_barrier();                                                                    // 2: du1 and x panels in LDS
-    // (the next tile's staging, at the top of the next pass, writes the du2 slices and the x maxima, last read before
-    //  barrier 2; the panels and exponents, read below, are written again only behind the next barrier 1.  Staging the
-    //  next tile BEFORE the consumer in one wave of each SIMD pair, so that vector and matrix work of the pair overlap
-    //  as in k_wgrad_h2, needs six registers more than there are: it spilled and was not run)
+    FLSTAMP(4);
+    // ---- the NEXT tile's du2 slices, ahead of this tile's consumer, and the loads of the tile after it ----
+    // No new barrier: the du2 slices were last read by the products above, which every wave has finished (lds_barrier
+    // waits for its LDS reads) before any wave passes barrier 2, and they are read again only behind the next barrier 1;
+    // the x maxima (written at the end of the pass) were last read by the x panel write above, in front of barrier 2
+    // too.  What the consumer below reads -- the panels, einfo -- is written again only behind the next barrier 1, which
+    // no wave passes before all have left the consumer.
+    // (Built and measured, same machine, us per launch in the step, the parent's order 1659: the du2 loads at the end of
+    //  the pass with the staging there 1717; that with waves 4-7 / waves 0-3 staging in front of the consumer as in
+    //  k_wgrad_h2, 1699 / 1702; all eight waves staging here with the loads right behind, 1596 -- kept.  The staging is
+    //  about 110 vector instructions of a pass's 530: what a pair can overlap between two barriers is a few hundred
+    //  cycles of 12 K, less than the later issue of the loads costs)
+
+    stage_du2();
+    load_du2(next_tile + gridDim.x);
+    FLSTAMP(5);
 
     // (the consumer's LDS addresses are formed here, per tile, from a lane index the compiler cannot see through: hoisted
     //  out of the loop they stayed in registers beside W2^T and the accumulators, and seven of them spilled)
@@ -527,17 +583,25 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_ffs_layer1(const FsB A) {
         for (int j = 0; j < 2; ++j) gw[i][j] = h2_mfma32(ah, al, bh[j], bl[j], gw[i][j]);
       }
     }
+    FLSTAMP(6);
     // ---- gx = du1 . W1: one half panel (32 hidden channels, one exponent) at a time ----
     {
       f32x4v tot = (f32x4v){0.f, 0.f, 0.f, 0.f};
       const int row = 16 * dg_mt + lic;                     // A fragment: lane = point, 8 consecutive channels
+      f16x8 ah[2], al[2], bh[2], bl[2];
+      auto frags = [&](int hp) {
+        const char* pa_ = smem + FL_PAN + (hp >> 1) * FL_PANEL + stage_off(row, 2 * (4 * (hp & 1) + gc));
+        ah[hp & 1] = *reinterpret_cast<const f16x8*>(pa_); al[hp & 1] = *reinterpret_cast<const f16x8*>(pa_ + 4096);
+        const char* wb = wfrag + (hp * 4 + dg_nt) * 2048 + lc * 16;
+        bh[hp & 1] = *reinterpret_cast<const f16x8*>(wb); bl[hp & 1] = *reinterpret_cast<const f16x8*>(wb + 1024);
+      };
+      frags(0);
+      // (each half panel's fragments are read under the products of the one before: read, wait, three dependent
+      //  products, scale, eight times in a row, was a fifth of a pass for 24 products -- profiles/ffs_layer1_stamps.py)
 #pragma unroll
       for (int hp = 0; hp < 8; ++hp) {
-        const char* pa_ = smem + FL_PAN + (hp >> 1) * FL_PANEL + stage_off(row, 2 * (4 * (hp & 1) + gc));
-        const f16x8 ah = *reinterpret_cast<const f16x8*>(pa_), al = *reinterpret_cast<const f16x8*>(pa_ + 4096);
-        const char* wb = wfrag + (hp * 4 + dg_nt) * 2048 + lc * 16;
-        const f16x8 bh = *reinterpret_cast<const f16x8*>(wb), bl = *reinterpret_cast<const f16x8*>(wb + 1024);
-        const f32x4v part = h2_mfma32(ah, al, bh, bl, (f32x4v){0.f, 0.f, 0.f, 0.f});
+        if (hp + 1 < 8) frags(hp + 1);
+        const f32x4v part = h2_mfma32(ah[hp & 1], al[hp & 1], bh[hp & 1], bl[hp & 1], (f32x4v){0.f, 0.f, 0.f, 0.f});
         const int ek = __builtin_amdgcn_readfirstlane(einfo[hp]);
         const float fk = __uint_as_float((unsigned)(ek - 14) << 23) * w_inv;
         tot += part * fk;
@@ -548,6 +612,12 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_ffs_layer1(const FsB A) {
       const int rq = 16 * dg_mt + 4 * gc + (lic & 3);
       if (p0 + rq < A.P) *reinterpret_cast<float4*>(A.gx + p0 * 64 + (unsigned)(rq * 64 + 16 * dg_nt + 4 * (lic >> 2))) = make_float4(t0, t1, t2, t3);
     }
+    FLSTAMP(7);
+    load_d1(next_tile);
+    stage_xmax(next_tile);
+#ifdef RPDE_STAMPS
+    ++stamp_t;
+#endif
   }
 
   // ---- this workgroup's slab [256][64] of gW1 and its db1 ----
@@ -610,3 +680,11 @@ int ff_bwd_split_launch(const rpde_ff_params* p, const float* const* ds, const f
 }
 
 }  // namespace rpde
+
+#ifdef RPDE_STAMPS
+extern "C" int rpde_debug_ffl_stamps(unsigned long long* host_out) {
+  RPDE_HIP(hipDeviceSynchronize());
+  RPDE_HIP(hipMemcpyFromSymbol(host_out, HIP_SYMBOL(rpde::g_flstamps), sizeof(unsigned long long) * 3 * 64));
+  return RPDE_OK;
+}
+#endif
