@@ -107,7 +107,7 @@ int mix_prep(const float* w_y, const float* w_x, int K, int keff, int kp, int co
 // ------------------------------------------------------------------------------------------------------------
 struct MixP {
   const float* spec[2];      // [lines][R][64]
-  char* img[2];              // operand blocks of the synthesis (fused_spectral.hip)
+  char* img[2];              // operand blocks of the synthesis (fused_spectral.h)
   const float* amax[2];      // max |spectrum| per line (from the analysis kernel)
   float* inv[2];             // out: 1 / (line scale * table scale)
   int tiles[2];              // line tiles (16 lines) per axis
@@ -122,8 +122,7 @@ constexpr int MIX_LDS = 4 * 3 * 2 * 2 * 1024;
 
 template <int K32, int TG>
 __global__ __launch_bounds__(256, 2) void k_mix_h2(const MixP P) {
-  constexpr int BB = h2_block_bytes(K32, TG);
-  constexpr int NP = h2_np(TG);
+  typedef H2Block<K32, TG> L;
   __shared__ __attribute__((aligned(16))) char smem[MIX_LDS];
   const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, g = l >> 4, li = l & 15;
   int bid = blockIdx.x;
@@ -239,22 +238,19 @@ __global__ __launch_bounds__(256, 2) void k_mix_h2(const MixP P) {
       h2_split4(v[0], v[1], v[2], v[3], h0, l0);
       h2_split4(v[4], v[5], v[6], v[7], h1, l1);
       const uint4 hi = make_uint4(h0.x, h0.y, h1.x, h1.y), lo = make_uint4(l0.x, l0.y, l1.x, l1.y);
-      char* blk = img + (line * 4 + cb) * (long)BB;
+      char* blk = img + (line * 4 + cb) * (long)L::BYTES;
       if (!tail) {
         const int s = q >> 2, gq = q & 3;
-        *reinterpret_cast<uint4*>(blk + s * 1024 + (gq * 16 + li) * 16) = hi;
-        *reinterpret_cast<uint4*>(blk + (K32 + s) * 1024 + (gq * 16 + li) * 16) = lo;
+        *reinterpret_cast<uint4*>(blk + L::hi(s) + (gq * 16 + li) * 16) = hi;
+        *reinterpret_cast<uint4*>(blk + L::lo(s) + (gq * 16 + li) * 16) = lo;
       } else if (TG > 0) {
         const int qt = q - 4 * K32;
+        // (H2Block's store_tail / zero_unused written out: through the helpers five of the six instances get other registers)
 #pragma unroll
-        for (int tt = 0; tt < 3; ++tt) {               // spectrum side of the packed tail: (hi, lo, hi)
-          const int slot = tt * TG + qt;
-          *reinterpret_cast<uint4*>(blk + (2 * K32 + slot / 4) * 1024 + ((slot & 3) * 16 + li) * 16) = tt == 1 ? lo : hi;
-        }
+        for (int tt = 0; tt < 3; ++tt) *L::tail(blk, tt * TG + qt, li) = tt == 1 ? lo : hi;      // spectrum side: (hi, lo, hi)
         if (qt == 0) {                                  // slots no group uses: zero (the table side holds zeros there too)
 #pragma unroll
-          for (int slot = 3 * TG; slot < 4 * NP; ++slot)
-            *reinterpret_cast<uint4*>(blk + (2 * K32 + slot / 4) * 1024 + ((slot & 3) * 16 + li) * 16) = make_uint4(0, 0, 0, 0);
+          for (int slot = 3 * TG; slot < 4 * L::NP; ++slot) *L::tail(blk, slot, li) = make_uint4(0, 0, 0, 0);
         }
       }
       if (q == 0 && cb == 0 && li == 0) P.inv[a][line] = iout;
@@ -424,18 +420,6 @@ int mix_wgrad_h2(const float* spec_y, const float* spec_x, const float* gspec_y,
   return RPDE_OK;
 }
 
-#define RPDE_MIX_DISPATCH(R, ...)                                                           \
-  do {                                                                                          \
-    switch ((R) / 8) {                                                                          \
-      case 1: hipLaunchKernelGGL((k_mix_h2<0, 1>), __VA_ARGS__); break;                         \
-      case 2: hipLaunchKernelGGL((k_mix_h2<0, 2>), __VA_ARGS__); break;                         \
-      case 3: hipLaunchKernelGGL((k_mix_h2<0, 3>), __VA_ARGS__); break;                         \
-      case 4: hipLaunchKernelGGL((k_mix_h2<1, 0>), __VA_ARGS__); break;                         \
-      case 5: hipLaunchKernelGGL((k_mix_h2<1, 1>), __VA_ARGS__); break;                         \
-      default: hipLaunchKernelGGL((k_mix_h2<1, 2>), __VA_ARGS__); break;                        \
-    }                                                                                           \
-  } while (0)
-
 // spectra of both axes -> operand blocks + inverse line scales, one launch
 int mix_h2(const float* spec_y, const float* spec_x, const float* amax_y, const float* amax_x, void* img_y, void* img_x,
            float* inv_y, float* inv_x, long lines_y, long lines_x, int kp, const void* wimg, const float* wc, hipStream_t st) {
@@ -458,7 +442,9 @@ int mix_h2(const float* spec_y, const float* spec_x, const float* amax_y, const 
     nblk[a] = slices * P.nq;
   }
   P.nblk0 = nblk[0];
-  RPDE_MIX_DISPATCH(P.R, dim3(nblk[0] + nblk[1]), dim3(256), 0, st, P);
+  h2_dispatch(P.R, [&](auto k32, auto tg) {
+    hipLaunchKernelGGL((k_mix_h2<k32(), tg()>), dim3(nblk[0] + nblk[1]), dim3(256), 0, st, P);
+  });
   RPDE_LAUNCH_CHECK();
   return RPDE_OK;
 }

@@ -53,38 +53,16 @@ __global__ __launch_bounds__(64) void k_h2_table_ana(const float* __restrict__ s
   *reinterpret_cast<uint4*>(p + 1024) = lo;
 }
 
-// ---- operand blocks of the synthesis MFMAs ----
-// One operand (a 16-row tile of a table, or 16 channels of a spectrum line) over R = 32 K32 + 8 TG reduction rows is
-// stored as K32 "hi" fragments, K32 "lo" fragments (1 KB each: lane l holds rows 32 s + 8 (l >> 4) + j) and NP packed
-// tail fragments.  The tail has only TG < 4 real lane groups per 32-deep fragment, so the three h2 terms
-// (lo*hi, hi*lo, hi*hi) of each real group are laid side by side along the reduction axis: slot t*TG + q holds, on the
-// table side, piece (lo, hi, hi)[t] of group q and on the spectrum side piece (hi, lo, hi)[t]; slot -> fragment
-// slot / 4, lane group slot % 4.  One MFMA on a packed fragment then yields all three terms: R = 40 costs 4 MFMAs and
-// 3 loads per line instead of 6 and 4.  (A 16-deep MFMA for the tail is not an option: a v_mfma_f32_16x16x16_f16 directly
-// behind the v_mfma_f32_16x16x32_f16 it accumulates onto reads a partly written accumulator on gfx950 with ROCm 7.2 --
-// h2.h, profiles/r04_mfma_mix.txt.)
-// (h2_np / h2_block_bytes: fused_spectral.h)
-
-// 8 values of group q (rows 32 K32 + 8 q ..) -> the 16-byte pieces of the three slots they occupy
-__device__ __forceinline__ void h2_store_tail(char* __restrict__ blk, int K32, int TG, int q, int c, bool table, const float (&v)[8]) {
-  uint4 hi, lo;
-  h2_split8(v, hi, lo);
-#pragma unroll
-  for (int t = 0; t < 3; ++t) {
-    const int slot = t * TG + q;
-    const bool use_lo = table ? (t == 0) : (t == 1);
-    *reinterpret_cast<uint4*>(blk + (2 * K32 + slot / 4) * 1024 + ((slot & 3) * 16 + c) * 16) = use_lo ? lo : hi;
-  }
-}
-
-// synthesis operand of S[y][r] = src[y*rs + r*cs] (y < n, r < R), times 2^12: one block per 16-row tile
-__global__ __launch_bounds__(64) void k_h2_table_syn(const float* __restrict__ src, long rs, long cs, int n, int R, int K32,
-                                                     int TG, char* __restrict__ out) {
+// synthesis operand of S[y][r] = src[y*rs + r*cs] (y < n, r < R), times 2^12: one operand block (fused_spectral.h) per
+// 16-row tile
+template <int K32, int TG>
+__global__ __launch_bounds__(64) void k_h2_table_syn(const float* __restrict__ src, long rs, long cs, int n, int R,
+                                                     char* __restrict__ out) {
+  typedef H2Block<K32, TG> L;
   const int yt = blockIdx.x, l = threadIdx.x, g = l >> 4, li = l & 15;
   const int y = 16 * yt + li;
-  char* blk = out + (long)yt * h2_block_bytes(K32, TG);
-  for (int i = l; i < h2_np(TG) * 64; i += 64) *reinterpret_cast<uint4*>(blk + 2 * K32 * 1024 + i * 16) = make_uint4(0, 0, 0, 0);
-  __syncthreads();
+  char* blk = out + (long)yt * L::BYTES;
+#pragma unroll
   for (int s = 0; s <= K32; ++s) {
     if (s == K32 && g >= TG) break;
     float v[8];
@@ -93,16 +71,16 @@ __global__ __launch_bounds__(64) void k_h2_table_syn(const float* __restrict__ s
       const int r = 32 * s + 8 * g + j;
       v[j] = (y < n && r < R) ? src[y * rs + r * cs] * (float)(1 << H2_TABLE_EXP) : 0.f;
     }
+    uint4 hi, lo;
+    h2_split8(v, hi, lo);
     if (s < K32) {
-      uint2 h0, l0, h1, l1;      // (h2_split8 written out: through the helper this loop gets another register assignment)
-      h2_split4(v[0], v[1], v[2], v[3], h0, l0);
-      h2_split4(v[4], v[5], v[6], v[7], h1, l1);
-      *reinterpret_cast<uint4*>(blk + s * 1024 + l * 16) = make_uint4(h0.x, h0.y, h1.x, h1.y);
-      *reinterpret_cast<uint4*>(blk + (K32 + s) * 1024 + l * 16) = make_uint4(l0.x, l0.y, l1.x, l1.y);
+      *reinterpret_cast<uint4*>(blk + L::hi(s) + l * 16) = hi;
+      *reinterpret_cast<uint4*>(blk + L::lo(s) + l * 16) = lo;
     } else {
-      h2_store_tail(blk, K32, TG, g, li, true, v);
+      L::template store_tail<true>(blk, g, li, hi, lo);
     }
   }
+  if (TG > 0 && g == 0) L::zero_unused(blk, li);
 }
 
 size_t h2_ana_bytes(int n, int R) { return (size_t)(n / 32) * ((R + 15) / 16) * 2048; }
@@ -110,7 +88,7 @@ size_t h2_syn_bytes(int n, int R) { return (size_t)((n + 15) / 16) * h2_block_by
 
 int h2_build_tables(rpde_plan* p, hipStream_t st) {
   const int R = 2 * p->kp, n = p->n;
-  const int MT = (R + 15) / 16, K32 = R / 32, TG = (R % 32) / 8;
+  const int MT = (R + 15) / 16;
   for (int i = 0; i < 2; ++i) {
     RPDE_HIP(hipMalloc(&p->h2_ana[i], h2_ana_bytes(n, R)));
     RPDE_HIP(hipMalloc(&p->h2_ana_p[i], h2_ana_bytes(n, R)));
@@ -122,8 +100,10 @@ int h2_build_tables(rpde_plan* p, hipStream_t st) {
   hipLaunchKernelGGL(k_h2_table_ana, ga, dim3(64), 0, st, p->fs, 1L, (long)R, R, n, MT, (char*)p->h2_ana[1], 0);
   hipLaunchKernelGGL(k_h2_table_ana, ga, dim3(64), 0, st, p->fa, (long)p->ldn, 1L, R, n, MT, (char*)p->h2_ana_p[0], 1);
   hipLaunchKernelGGL(k_h2_table_ana, ga, dim3(64), 0, st, p->fs, 1L, (long)R, R, n, MT, (char*)p->h2_ana_p[1], 1);
-  hipLaunchKernelGGL(k_h2_table_syn, gs, dim3(64), 0, st, p->fs, (long)R, 1L, n, R, K32, TG, (char*)p->h2_syn[0]);
-  hipLaunchKernelGGL(k_h2_table_syn, gs, dim3(64), 0, st, p->fa, 1L, (long)p->ldn, n, R, K32, TG, (char*)p->h2_syn[1]);
+  h2_dispatch(R, [&](auto k32, auto tg) {
+    hipLaunchKernelGGL((k_h2_table_syn<k32(), tg()>), gs, dim3(64), 0, st, p->fs, (long)R, 1L, n, R, (char*)p->h2_syn[0]);
+    hipLaunchKernelGGL((k_h2_table_syn<k32(), tg()>), gs, dim3(64), 0, st, p->fa, 1L, (long)p->ldn, n, R, (char*)p->h2_syn[1]);
+  });
   RPDE_LAUNCH_CHECK();
   return RPDE_OK;
 }
@@ -540,6 +520,7 @@ __global__ __launch_bounds__(64 * ANA_WAVES, 2) void k_dft_analysis_rr_h2(const 
 template <int K32, int TG>
 __global__ __launch_bounds__(256) void k_spec_split_h2(const float* __restrict__ spec, char* __restrict__ img,
                                                        float* __restrict__ inv_out, int R) {
+  typedef H2Block<K32, TG> L;
   constexpr int NF = K32 + (TG ? 1 : 0);
   __shared__ float wmax[4];
   const long line = blockIdx.x;
@@ -562,27 +543,21 @@ __global__ __launch_bounds__(256) void k_spec_split_h2(const float* __restrict__
   float scale, inv;
   h2_scale(m, H2_TABLE_EXP, scale, inv);
   if (tid == 0) inv_out[line] = inv;
-  char* blk = img + (line * 4 + cb) * (long)h2_block_bytes(K32, TG);
-  // unused slots of the packed fragments are never loaded (the synthesis masks those lanes)
+  char* blk = img + (line * 4 + cb) * (long)L::BYTES;
 #pragma unroll
   for (int s = 0; s < NF; ++s) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[s][j] *= scale;
+    uint4 hi, lo;
+    h2_split8(v[s], hi, lo);
     if (s < K32) {
-      uint4 hi, lo;
-      h2_split8(v[s], hi, lo);
-      *reinterpret_cast<uint4*>(blk + s * 1024 + l * 16) = hi;
-      *reinterpret_cast<uint4*>(blk + (K32 + s) * 1024 + l * 16) = lo;
+      *reinterpret_cast<uint4*>(blk + L::hi(s) + l * 16) = hi;
+      *reinterpret_cast<uint4*>(blk + L::lo(s) + l * 16) = lo;
     } else if (g < TG) {
-      h2_store_tail(blk, K32, TG, g, li, false, v[s]);
+      L::template store_tail<false>(blk, g, li, hi, lo);
     }
   }
-  // slots of the packed fragments that no group uses: zero (k_dft_synthesis3_h2 feeds whole fragments to the MFMAs)
-  if (TG > 0 && g == 0) {
-#pragma unroll
-    for (int slot = 3 * TG; slot < 4 * h2_np(TG); ++slot)
-      *reinterpret_cast<uint4*>(blk + (2 * K32 + slot / 4) * 1024 + ((slot & 3) * 16 + li) * 16) = make_uint4(0, 0, 0, 0);
-  }
+  if (TG > 0 && g == 0) L::zero_unused(blk, li);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -600,13 +575,14 @@ struct SynP {
 // one operand block in registers
 template <int K32, int TG>
 struct Frag {
-  static constexpr int NP = h2_np(TG);
+  typedef H2Block<K32, TG> L;
+  static constexpr int NP = L::NP;
   f16x8 h[K32 > 0 ? K32 : 1], lo[K32 > 0 ? K32 : 1], pk[NP > 0 ? NP : 1];
   __device__ __forceinline__ void load(const char* __restrict__ p, int l) {
 #pragma unroll
     for (int s = 0; s < K32; ++s) {
-      h[s] = *reinterpret_cast<const f16x8*>(p + s * 1024 + l * 16);
-      lo[s] = *reinterpret_cast<const f16x8*>(p + (K32 + s) * 1024 + l * 16);
+      h[s] = *reinterpret_cast<const f16x8*>(p + L::hi(s) + l * 16);
+      lo[s] = *reinterpret_cast<const f16x8*>(p + L::lo(s) + l * 16);
     }
 #pragma unroll
     for (int q = 0; q < NP; ++q) {
@@ -614,7 +590,7 @@ struct Frag {
       const int slots = q < full ? 4 : 3 * TG - 4 * full;
       const f16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
       pk[q] = z;
-      if ((l >> 4) < slots) pk[q] = *reinterpret_cast<const f16x8*>(p + (2 * K32 + q) * 1024 + l * 16);
+      if ((l >> 4) < slots) pk[q] = *reinterpret_cast<const f16x8*>(p + L::pk(q) + l * 16);
     }
   }
 };
@@ -736,131 +712,120 @@ __global__ __launch_bounds__(256, 2) void k_dft_synthesis2_h2(const SynP P) {
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// synthesis of both axes, 64 x 64 point tiles (round 3)
+// synthesis of both axes, persistent 64-row tiles (rounds 3 and 4): one scaffold, two tile shapes
 // ------------------------------------------------------------------------------------------------------------
 // k_dft_synthesis2_h2 gives every wave a 16 x 16 x 16-channel tile and lets it fetch its 32 spectrum lines itself:
 // 5.5 bytes loaded from L2 per byte stored (3.2 GB per forward at 256^2, B = 32), and that -- not HBM -- bounded it
-// (317 us).  Here an 8-wave workgroup owns 64 x 64 points x 16 channels, so a line's fragments are fetched from L2 once
-// per FOUR 16-point tiles: 1.5 bytes per byte stored.
-//   * the 64 x-lines (columns) and 64 y-lines (rows) of the tile stream through a 3-slot LDS ring in 8 stages of 16
-//     lines, by LDS-DMA (global_load_lds: 1 KB fragment pieces land lane-linear, exactly as the MFMA wants them; no
-//     registers held), two stages ahead; one s_barrier per stage.  The table blocks and the line scales travel the
-//     same way (a 12 KB corner of LDS that holds the x-axis table during the x phase and the y-axis table after it):
-//     no ordinary global load anywhere in the kernel, so the compiler never drains the DMA queue for one.
-//   * wave (mt, p) owns the 16-row block mt and the two 16-column blocks p, p + 2: 128 accumulator registers.  Stages
-//     0-3 form the x-axis part column by column (accumulator rows = m), stages 4-7 the y-axis part row by row
-//     (accumulator rows = n).  Between them the x part is turned into the y layout INSIDE the register file: both
-//     layouts keep the channel on lane & 15, so the turn is sixteen 4 x 4 transposes between the register index and
-//     the lane-row index -- two v_permlane32_swap + two v_permlane16_swap each.  No LDS turning buffer (the old kernel
-//     spent ~200 LDS instructions and 2.1 M bank-conflict cycles per launch there).
-//   * persistent: one workgroup per CU walks over its share of the tiles, and the ring never runs dry -- the first two
+// (317 us).  The two kernels below give an 8-wave workgroup a tile of 64 rows, so a line's fragments are fetched from
+// L2 once per FOUR 16-point tiles.  What they share (SynTile, SynWalk, SynLane):
+//   * the lines of the tile stream through a 3-slot LDS ring in stages of 16 fragments, by LDS-DMA (global_load_lds:
+//     1 KB fragment pieces land lane-linear, exactly as the MFMA wants them; no registers held), two stages ahead; one
+//     s_barrier per stage.  The table blocks and the line scales travel the same way (a 12 KB corner of LDS that holds
+//     the x-axis table during the x phase and the y-axis table after it): no ordinary global load for an operand
+//     anywhere, so the compiler never drains the DMA queue for one.  The waits are counted (cw.h).
+//   * wave (mt, p) owns 128 accumulator registers.  Stages 0-3 form the x-axis part column by column (accumulator rows
+//     = m), the later stages the y-axis part row by row (accumulator rows = n).  Between them the x part is turned into
+//     the y layout INSIDE the register file: both layouts keep the channel on lane & 15, so the turn is sixteen 4 x 4
+//     transposes between the register index and the lane-row index -- two v_permlane32_swap + two v_permlane16_swap
+//     each.  No LDS turning buffer (k_dft_synthesis2_h2 spends ~200 LDS instructions and 2.1 M bank-conflict cycles
+//     per launch there).
+//   * persistent: one workgroup per CU walks over its share of the items, and the ring never runs dry -- the first two
 //     stages (and the tables) of the NEXT tile are requested during the last stages of the current one.  In-kernel
 //     stamps of the first, one-tile-per-workgroup version: 33 % of a workgroup's life was the cold start of its DMA
 //     queue, 29 % the burst of stores at its end.
-//   * it serves the adjoint with a skip gradient (the forward and the adjoint without one run k_dft_synthesis4_h2):
-//     loads of the skip gradient + stores in four batches after the last stage, 16 bytes per lane (a 4 x 4 transpose
-//     inside each quad of lanes gives every lane four consecutive channels of one point).  (The retired forward
-//     instances spread the stores over the eight stages instead; the measurements below are theirs.)
-//   * what bounds it now (measured with the parts switched off one at a time, 256^2, B = 32): DMA skeleton alone 76 us,
-//     + MFMAs 25 us, + stores 130 us; HBM traffic 0.30 GB read + 0.54 GB written in 215-230 us.  Burst or spread, in step
-//     or staggered across XCDs, 4-byte or 16-byte stores: the store time adds to the rest (a CU's memory pipeline
-//     takes a 16-segment store instruction in ~60-90 cycles and DMA pieces through the same queue).
-//   * every line carries its own power-of-two scale (undone on the accumulators, as before).
+//   * every line carries its own power-of-two scale (undone on the accumulators).
+// What differs is the tile (a geometry trait each: item_at, issue_piece, issue_table, issue_inv), the y phase, the way
+// out, and the style of the stage loop:
+//   k_dft_synthesis3_h2  64 x 64 points x 16 channels, 8 stages, 1.5 bytes of fragments per byte stored.  Wave (mt, p)
+//     owns the 16-row block mt and the two 16-column blocks p, p + 2.  It serves the adjoint with a skip gradient: loads
+//     of the skip gradient + stores in four batches after the last stage, 16 bytes per lane (a 4 x 4 transpose inside
+//     each quad of lanes gives every lane four consecutive channels of one point).  (The retired forward instances
+//     spread the stores over the eight stages instead; the measurements below are theirs.)  What bounds it (measured
+//     with the parts switched off one at a time, 256^2, B = 32): DMA skeleton alone 76 us, + MFMAs 25 us, + stores
+//     130 us; HBM traffic 0.30 GB read + 0.54 GB written in 215-230 us.  Burst or spread, in step or staggered across
+//     XCDs, 4-byte or 16-byte stores: the store time adds to the rest (a CU's memory pipeline takes a 16-segment store
+//     instruction in ~60-90 cycles and DMA pieces through the same queue).
+//   k_dft_synthesis4_h2  64 x 32 points x 32 channels, 12 stages; forward and adjoint without a skip gradient.
+//     Kernel 3 owns 16 channels of its points, so every store instruction writes sixteen 64-byte segments -- half cache
+//     lines -- and a CU's memory pipeline takes such an instruction at a quarter of the rate of one that writes eight
+//     whole 128-byte lines (profiles/ubench/storepat.hip: 37 vs 135 GB/s per CU); with the stores in, that kernel ran
+//     225 us against 100 us without them.  Here a workgroup owns a PAIR of channel blocks (32 channels = one 128-byte
+//     line per point) -- the same 128 accumulator registers per lane -- at the price of 2.25 instead of 1.5 bytes of
+//     fragments fetched from L2 per byte stored (the fragments of a channel pair of a sample, 3.1 MB at 256^2, still
+//     fit the XCD's L2 while all its tiles use them).  Wave (mt, p) owns rows 16 mt .., columns 16 p .. of the tile for
+//     BOTH channel blocks a = 0, 1: acc[a][i][jj].  x stages 0-3 (channel block s >> 1, columns 8 (s & 1) .. + 7 of
+//     both column blocks), y stages 4-11 (rows 2 (s - 4), + 1 of the four row blocks, both channel blocks).
+//     12 = 0 mod 3: the ring position is the same for every tile.  A row is final after its y stage and leaves right
+//     there: four store instructions per wave and y stage, each eight points x 128 bytes.  The 4 x 4 quad transpose that
+//     gives a lane four consecutive channels of one point takes its four inputs from BOTH channel blocks -- (a, column)
+//     = (0, 0), (0, 1), (1, 0), (1, 1) -- so the lanes of a quad end up with the two 64-byte halves of two points'
+//     lines: no exchange beyond the transpose itself.
+//     Tried on top and dropped (same-box, 256^2, B = 32; profiles/r04_synthesis_variants.txt): requesting ALL pieces of
+//     stage s + 2 right behind the barrier and issuing the stores of a stage's rows one stage later, behind the next
+//     requests, so that a store has three stages instead of two to be acknowledged before a wait on younger pieces
+//     covers it (the counter is in order) and no request queues behind a burst of stores: 225-230 us against 219 us.
+//     Neither the store segment (this kernel against kernel 3: 219 vs 224-235 us), nor the fragment volume (2.25 vs 1.5
+//     bytes per byte stored), nor the store window moves the time; the same store pattern alone streams at 6.2 TB/s =
+//     87 us (profiles/ubench/storepat.hip, pattern C / D).  What is left is that ONE workgroup per CU runs all its
+//     waves through the same phase at the same time -- wait for pieces | fragments + matrix work | transposes + stores
+//     -- so the three add up instead of overlapping.
+// Both kernels are sensitive to how they compile; the shared pieces are the ones that leave every instance's instruction
+// stream as it was (profiles/isa_streams.py, profiles/synthesis_fold_ab.txt).
 constexpr int SYN3_WAVES = 8;
 
-// one tile of one channel block of one sample
-struct Syn3Item {
-  const char* gx; const char* gy;       // fragment pieces of the tile's first column / first row (this channel block)
+// one item: one tile of one channel block (kernel 3) / channel pair (kernel 4) of one sample
+struct SynItem {
+  const char* gx; const char* gy;       // fragment pieces of the tile's first column / first row (first channel block)
   const char* tx; const char* ty;       // table blocks of the tile's first 16 rows / first 16 columns
   const float* ivx; const float* ivy;   // line scales of the tile's columns / rows
-  long o;                               // float offset of the tile's first point, first channel of the block
+  long o;                               // float offset of the tile's first point, first channel of the item
+};
+
+// a lane's place in the workgroup
+struct SynLane {
+  int l, w, g, li, mt, p;
+  unsigned lane16;
+  __device__ static __forceinline__ SynLane here() {
+    const int tid = threadIdx.x, l = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    return {l, w, l >> 4, l & 15, w & 3, w >> 2, (unsigned)(l * 16)};
+  }
+};
+
+// this workgroup's items.  Blocks b, b + ng, .. share an XCD (an L2): group xg = blockIdx % ng takes the samples
+// xg, xg + ng, ..; its nj workgroups take the items (wps per sample) round-robin from jw, so the ~32 in flight are
+// neighbours that share spectrum lines.  (Placement is a speed matter only.)
+struct SynWalk {
+  int ng, xg, jw, nj;
+  long nitems;
+  __device__ __forceinline__ SynWalk(const SynP& P, int wps)
+      : ng(P.sy), xg(blockIdx.x % ng), jw(blockIdx.x / ng), nj(gridDim.x / ng), nitems((long)((P.B - xg + ng - 1) / ng) * wps) {}
 };
 
 template <int K32, int TG>
-__global__ __launch_bounds__(64 * SYN3_WAVES, 2) void k_dft_synthesis3_h2(const SynP P) {
-  constexpr int NP = h2_np(TG), NF = 2 * K32 + NP;
-  constexpr int BB = NF * 1024;
-  constexpr long LB = 4L * BB;
-  constexpr int SLOT = 16 * BB;                 // one stage: 16 lines
-  static_assert(NF <= 3, "ring of three 16-line slots + the table corner must fit 160 KB");
-  constexpr int TAB = 3 * SLOT, INV = TAB + 4 * BB, LDS_BYTES = INV + 512;
-  __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
-  const int tid = threadIdx.x, l = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), g = l >> 4, li = l & 15;
-  const int mt = w & 3, p = w >> 2;
-  const unsigned lane16 = l * 16;
+struct SynTile {
+  typedef H2Block<K32, TG> L;
   typedef Frag<K32, TG> F;
+  static constexpr int NP = L::NP, NF = L::NF, BB = L::BYTES;
+  static constexpr long LB = 4L * BB;             // bytes per line: 4 channel blocks
+  static constexpr int SLOT = 16 * BB;            // one stage: 16 fragments
+  static_assert(NF <= 3, "ring of three 16-fragment slots + the table corner must fit 160 KB");
+  static constexpr int TAB = 3 * SLOT, INV = TAB + 4 * BB, LDS_BYTES = INV + 512;
+
+  // operands of the LDS-DMA builtin
   typedef __attribute__((address_space(3))) void* lds_ptr;
   typedef const __attribute__((address_space(1))) void* glb_ptr;
-
-  // ---- this workgroup's tiles.  Blocks b, b + 8, .. share an XCD (an L2): group x = blockIdx & 7 takes the samples
-  // x, x + 8, ..; its workgroups take the items round-robin, so the ~32 in flight are neighbours that share spectrum
-  // lines.  (Placement is a speed matter only.)
-  const int tn = P.N >> 6, wps = (P.M >> 6) * tn * 4;
-  const int ng = P.sy;            // groups: 8, or the batch size when that is smaller
-  const int xg = blockIdx.x % ng, jw = blockIdx.x / ng, nj = gridDim.x / ng;
-  const int nsamp = (P.B - xg + ng - 1) / ng;
-  const long nitems = (long)nsamp * wps;
-  auto item_at = [&](long q) {
-    Syn3Item it;
-    const int sb = (int)(q / wps), t = (int)(q - (long)sb * wps);
-    // channel blocks in pairs: first every tile of the sample for blocks 0 and 1, then for 2 and 3.  The ~32 workgroups
-    // of a group then work on ONE pair at a time -- the pair's fragments of a 256^2 sample (3.2 MB) stay in the 4 MB L2
-    // while all sixteen tiles use them (with the four blocks of a tile side by side only half of a sample's tiles ran
-    // together and the other half fetched the lines again: 319 MB for 201 MB of operands) -- and the two blocks of a
-    // pair still complete each other's 128-byte lines in L2.
-    const int half = wps >> 1, hb = t / half, r = t - hb * half;
-    const int b = xg + ng * sb, cb = 2 * hb + (r & 1), tile = r >> 1;
-    const int m0 = (tile / tn) << 6, n0 = (tile % tn) << 6;
-    it.gx = P.imgx + ((long)b * P.N + n0) * LB + cb * BB;
-    it.gy = P.imgy + ((long)b * P.M + m0) * LB + cb * BB;
-    it.tx = P.tabx + (long)(m0 >> 4) * BB;
-    it.ty = P.taby + (long)(n0 >> 4) * BB;
-    it.ivx = P.invx + (long)b * P.N + n0;
-    it.ivy = P.invy + (long)b * P.M + m0;
-    it.o = (((long)b * P.M + m0) * P.N + n0) * 64 + 16 * cb;
-    return it;
-  };
-  long q = jw;
-  if (q >= nitems) return;
-  Syn3Item cur = item_at(q);
-
-  // ---- DMA ----
-  // piece i (of 2 NF) of this wave for stage s of a tile: stage s < 4: columns 8 (s & 1) .. + 7 of the column blocks
-  // (s >> 1) * 2 + {0, 1}; stage s >= 4: rows 4 (s - 4) .. + 3 of the four row blocks
-  auto issue_piece = [&](const Syn3Item& it, int s, int i, int slot) {
-    const int idx = w + 8 * i, ell = idx / NF, f = idx - ell * NF;     // (ell * NF + f == idx: pieces land in order)
-    const char* src;
-    if (s < 4) src = it.gx + (long)(16 * ((ell >> 3) + 2 * (s >> 1)) + 8 * (s & 1) + (ell & 7)) * LB + f * 1024;
-    else src = it.gy + (long)(16 * (ell >> 2) + 4 * (s - 4) + (ell & 3)) * LB + f * 1024;
-    __builtin_amdgcn_global_load_lds((glb_ptr)(src + lane16), (lds_ptr)(smem + slot * SLOT + idx * 1024), 16, 0, 0);
-  };
-  // the four 16-row blocks of a table (x axis: rows m0 .. m0 + 63; y axis: the column blocks p + 2a at [p * 2 + a])
-  auto issue_table = [&](const char* tab, bool yaxis) {
-#pragma unroll
-    for (int i = 0; i < (4 * NF + 7) / 8; ++i) {
-      const int idx = w + 8 * i;
-      if (idx < 4 * NF) {
-        const int blk = idx / NF, f = idx - blk * NF;
-        const int src_blk = yaxis ? (blk >> 1) + 2 * (blk & 1) : blk;
-        __builtin_amdgcn_global_load_lds((glb_ptr)(tab + (long)src_blk * BB + f * 1024 + lane16), (lds_ptr)(smem + TAB + idx * 1024), 16, 0, 0);
-      }
-    }
-  };
-  auto issue_inv = [&](const Syn3Item& it) {          // 64 + 64 floats, one 4-byte DMA each
-    if (w == 6) __builtin_amdgcn_global_load_lds((glb_ptr)(it.ivx + l), (lds_ptr)(smem + INV), 4, 0, 0);
-    if (w == 7) __builtin_amdgcn_global_load_lds((glb_ptr)(it.ivy + l), (lds_ptr)(smem + INV + 256), 4, 0, 0);
-  };
-
-  auto lds_frag = [&](F& f, const char* base) {
+  // one operand block from LDS (base = block + 16 * lane)
+  __device__ static __forceinline__ void lds_frag(F& f, const char* base) {
 #pragma unroll
     for (int s2 = 0; s2 < K32; ++s2) {
-      f.h[s2] = *reinterpret_cast<const f16x8*>(base + s2 * 1024);
-      f.lo[s2] = *reinterpret_cast<const f16x8*>(base + (K32 + s2) * 1024);
+      f.h[s2] = *reinterpret_cast<const f16x8*>(base + L::hi(s2));
+      f.lo[s2] = *reinterpret_cast<const f16x8*>(base + L::lo(s2));
     }
 #pragma unroll
-    for (int qq = 0; qq < NP; ++qq) f.pk[qq] = *reinterpret_cast<const f16x8*>(base + (2 * K32 + qq) * 1024);
-  };
-  auto chain = [&](const F& tab, const F& f) {
+    for (int qq = 0; qq < NP; ++qq) f.pk[qq] = *reinterpret_cast<const f16x8*>(base + L::pk(qq));
+  }
+  // the three h2 terms of table block x line block, small terms first
+  __device__ static __forceinline__ f32x4v chain(const F& tab, const F& f) {
     f32x4v c = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int qq = 0; qq < NP; ++qq) c = __builtin_amdgcn_mfma_f32_16x16x32_f16(tab.pk[qq], f.pk[qq], c, 0, 0, 0);
@@ -871,15 +836,130 @@ __global__ __launch_bounds__(64 * SYN3_WAVES, 2) void k_dft_synthesis3_h2(const 
       c = __builtin_amdgcn_mfma_f32_16x16x32_f16(tab.h[s2], f.h[s2], c, 0, 0, 0);
     }
     return c;
-  };
+  }
+  // x stage s < 4: the eight columns 8 (s & 1) .. of the wave's column block in slot (= ring slot + 16 * lane), into
+  // acc[s >> 1][8 (s & 1) ..][jj] (rows m = 4g + jj); request(c8) between the chains.  Line fragments are read one line ahead of
+  // their MFMAs, no further (the compiler barrier keeps the LDS reads of later lines from being hoisted on top of 128
+  // live accumulators)
+  template <class Req>
+  __device__ static __forceinline__ void x_stage(const SynLane& ln, int s, const char* slot, const F& tx, F (&fq)[2],
+                                                 float (&acc)[2][16][4], Req&& request) {
+    const int a = s >> 1, h = s & 1;
+    lds_frag(fq[0], slot + (ln.p * 8) * BB);
+#pragma unroll
+    for (int c8 = 0; c8 < 8; ++c8) {
+      if (c8 + 1 < 8) lds_frag(fq[(c8 + 1) & 1], slot + (ln.p * 8 + c8 + 1) * BB);
+      asm volatile("" ::: "memory");
+      const f32x4v c = chain(tx, fq[c8 & 1]);
+      request(c8);
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) acc[a][8 * h + c8][jj] = c[jj];
+    }
+  }
+  // x part of one 16 x 16 block -> true units (column i times lane i of invx), then turned into the y layout: physical
+  // register [4 (r >> 2) + j][r & 3] then holds row r, column 4g + j
+  __device__ static __forceinline__ void turn(float (&acc)[16][4], const float& invx) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const float sc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(invx), i));
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) acc[i][jj] *= sc;
+    }
+#pragma unroll
+    for (int jy = 0; jy < 4; ++jy)
+#pragma unroll
+      for (int jr = 0; jr < 4; ++jr) {
+        swap_halves(acc[jy][jr], acc[8 + jy][jr]);
+        swap_halves(acc[4 + jy][jr], acc[12 + jy][jr]);
+        swap_rows(acc[jy][jr], acc[4 + jy][jr]);
+        swap_rows(acc[8 + jy][jr], acc[12 + jy][jr]);
+      }
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) pin(acc[i][jj]);
+  }
+};
 
-  // ---- prologue: tables / scales of the first tile, then its first two stages ----
-  issue_table(cur.tx, false);
-  issue_inv(cur);
+// ---- kernel 3's tile: 64 x 64 points x 16 channels, (M / 64) (N / 64) 4 items per sample ----
+template <int K32, int TG>
+struct Syn3Geom {
+  typedef SynTile<K32, TG> T;
+  // piece i (of 2 NF) of this wave for stage s of a tile: stage s < 4: columns 8 (s & 1) .. + 7 of the column blocks
+  // (s >> 1) * 2 + {0, 1}; stage s >= 4: rows 4 (s - 4) .. + 3 of the four row blocks
+  __device__ static __forceinline__ void issue_piece(char* smem, const SynLane& ln, const SynItem& it, int s, int i, int slot) {
+    constexpr int NF = T::NF;
+    const int idx = ln.w + 8 * i, ell = idx / NF, f = idx - ell * NF;     // (ell * NF + f == idx: pieces land in order)
+    const char* src;
+    if (s < 4) src = it.gx + (long)(16 * ((ell >> 3) + 2 * (s >> 1)) + 8 * (s & 1) + (ell & 7)) * T::LB + f * 1024;
+    else src = it.gy + (long)(16 * (ell >> 2) + 4 * (s - 4) + (ell & 3)) * T::LB + f * 1024;
+    __builtin_amdgcn_global_load_lds((typename T::glb_ptr)(src + ln.lane16), (typename T::lds_ptr)(smem + slot * T::SLOT + idx * 1024), 16, 0, 0);
+  }
+  // the four 16-row blocks of a table (x axis: rows m0 .. m0 + 63; y axis: the column blocks p + 2a at [p * 2 + a])
+  __device__ static __forceinline__ void issue_table(char* smem, const SynLane& ln, const char* tab, bool yaxis) {
+    constexpr int NF = T::NF;
+#pragma unroll
+    for (int i = 0; i < (4 * NF + 7) / 8; ++i) {
+      const int idx = ln.w + 8 * i;
+      if (idx < 4 * NF) {
+        const int blk = idx / NF, f = idx - blk * NF;
+        const int src_blk = yaxis ? (blk >> 1) + 2 * (blk & 1) : blk;
+        __builtin_amdgcn_global_load_lds((typename T::glb_ptr)(tab + (long)src_blk * T::BB + f * 1024 + ln.lane16), (typename T::lds_ptr)(smem + T::TAB + idx * 1024), 16, 0, 0);
+      }
+    }
+  }
+  __device__ static __forceinline__ void issue_inv(char* smem, const SynLane& ln, const SynItem& it) {          // 64 + 64 floats, one 4-byte DMA each
+    if (ln.w == 6) __builtin_amdgcn_global_load_lds((typename T::glb_ptr)(it.ivx + ln.l), (typename T::lds_ptr)(smem + T::INV), 4, 0, 0);
+    if (ln.w == 7) __builtin_amdgcn_global_load_lds((typename T::glb_ptr)(it.ivy + ln.l), (typename T::lds_ptr)(smem + T::INV + 256), 4, 0, 0);
+  }
+};
+
+template <int K32, int TG>
+__global__ __launch_bounds__(64 * SYN3_WAVES, 2) void k_dft_synthesis3_h2(const SynP P) {
+  typedef SynTile<K32, TG> T;
+  typedef Syn3Geom<K32, TG> G;
+  typedef typename T::F F;
+  constexpr int NF = T::NF, BB = T::BB, SLOT = T::SLOT, TAB = T::TAB, INV = T::INV;
+  __shared__ __attribute__((aligned(16))) char smem[T::LDS_BYTES];
+  // (decomposed here, not by SynLane::here(): through it the instances with two fragment pieces spill one scalar less)
+  const int tid = threadIdx.x, l = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), g = l >> 4, li = l & 15;
+  const int mt = w & 3, p = w >> 2;
+  const SynLane ln = {l, w, g, li, mt, p, (unsigned)(l * 16)};
+  // (item_at stays here: as a member of Syn3Geom, like Syn4Geom's, the items-per-sample product compiles differently)
+  const int tn = P.N >> 6, wps = (P.M >> 6) * tn * 4;
+  const SynWalk wk(P, wps);
+  auto item_at = [&](long q) {
+    SynItem it;
+    const int sb = (int)(q / wps), t = (int)(q - (long)sb * wps);
+    // channel blocks in pairs: first every tile of the sample for blocks 0 and 1, then for 2 and 3.  The ~32 workgroups
+    // of a group then work on ONE pair at a time -- the pair's fragments of a 256^2 sample (3.2 MB) stay in the 4 MB L2
+    // while all sixteen tiles use them (with the four blocks of a tile side by side only half of a sample's tiles ran
+    // together and the other half fetched the lines again: 319 MB for 201 MB of operands) -- and the two blocks of a
+    // pair still complete each other's 128-byte lines in L2.
+    const int half = wps >> 1, hb = t / half, r = t - hb * half;
+    const int b = wk.xg + wk.ng * sb, cb = 2 * hb + (r & 1), tile = r >> 1;
+    const int m0 = (tile / tn) << 6, n0 = (tile % tn) << 6;
+    it.gx = P.imgx + ((long)b * P.N + n0) * T::LB + cb * BB;
+    it.gy = P.imgy + ((long)b * P.M + m0) * T::LB + cb * BB;
+    it.tx = P.tabx + (long)(m0 >> 4) * BB;
+    it.ty = P.taby + (long)(n0 >> 4) * BB;
+    it.ivx = P.invx + (long)b * P.N + n0;
+    it.ivy = P.invy + (long)b * P.M + m0;
+    it.o = (((long)b * P.M + m0) * P.N + n0) * 64 + 16 * cb;
+    return it;
+  };
+  long q = wk.jw;
+  if (q >= wk.nitems) return;
+  SynItem cur = item_at(q);
+  auto issue_piece = [&](const SynItem& it, int s, int i, int slot) { G::issue_piece(smem, ln, it, s, i, slot); };
+  // ---- prologue: tables / scales of the first tile, then its first two stages (in place in both kernels: as a shared
+  // function it changes every instance's schedule) ----
+  G::issue_table(smem, ln, cur.tx, false);
+  G::issue_inv(smem, ln, cur);
 #pragma unroll
   for (int i = 0; i < 2 * NF; ++i) issue_piece(cur, 0, i, 0);
-  cw_mark<3>();                 // (tags 3 / 4: the first tile's stages 0 / 1, waited for under `first`; see k_dft_synthesis4_h2)
-#pragma unroll
+  cw_mark<3>();                 // (tags 3 / 4: the first tile's stages 0 / 1, waited for under `first` -- a path-insensitive
+#pragma unroll                  //  check cannot know that `first` and "came from the prologue" are the same thing)
   for (int i = 0; i < 2 * NF; ++i) issue_piece(cur, 1, i, 1);
   cw_mark<4>();
   int ring = 0;                 // slot of the current tile's stage 0
@@ -890,13 +970,11 @@ __global__ __launch_bounds__(64 * SYN3_WAVES, 2) void k_dft_synthesis3_h2(const 
   float acc[2][16][4];
 
   while (true) {
-    const long qn = q + nj;
-    const bool has_next = qn < nitems;
-    Syn3Item nxt = cur;
+    const long qn = q + wk.nj;
+    const bool has_next = qn < wk.nitems;
+    SynItem nxt = cur;
     if (has_next) nxt = item_at(qn);
     F tx, ty[2];
-    // line fragments are read one line ahead of their MFMAs, no further (the compiler barrier keeps the LDS reads of
-    // later lines from being hoisted on top of 128 live accumulators)
     F fq[2];
     float invx_l[2], invy_l;
     // output: after the quad transpose lane (g, 4 qd + pl) holds channels 4 qd .. + 3 of the point (row r, column
@@ -909,7 +987,7 @@ __global__ __launch_bounds__(64 * SYN3_WAVES, 2) void k_dft_synthesis3_h2(const 
       return v;
     };
 #ifdef RPDE_STAMPS
-    const bool stamp_on = l == 0 && w == 5 && blockIdx.x >= 96 && blockIdx.x < 160 && q == jw + 2 * (long)nj;
+    const bool stamp_on = l == 0 && w == 5 && blockIdx.x >= 96 && blockIdx.x < 160 && q == wk.jw + 2 * (long)wk.nj;
     const int stamp_slot = (int)blockIdx.x - 96;
 #endif
     FSTAMP(1, 0);
@@ -920,15 +998,15 @@ __global__ __launch_bounds__(64 * SYN3_WAVES, 2) void k_dft_synthesis3_h2(const 
       // scale pieces issued in between only over-waits
       // (cw.h: the requests of stage s are marked with the tag s % 3 behind their last piece, and the ISA test checks
       //  these counts on the compiled code)
-      const int T = s % 3;
+      const int T3 = s % 3;
       // (every stage requests its pieces, the last tile's stages 6 / 7 a harmless re-read: no count depends on has_next.
       //  The arms below that wait alike are kept apart on purpose: merged, they compile to other register assignments.)
-      if (!first && s < 2) cw_wait_t<63>(T);                       // (behind the 64 loads / stores of the epilogue)
+      if (!first && s < 2) cw_wait_t<63>(T3);                      // (behind the 64 loads / stores of the epilogue)
       else if (first && s < 2) { if (s == 0) cw_wait<3, 2 * NF>(); else cw_wait<4, 2 * NF>(); }
-      else if (first && s < 5) cw_wait_t<2 * NF>(T);
-      else if (s == 0 || s == 1 || s == 6) cw_wait_t<2 * NF>(T);
-      else if (s <= 5) cw_wait_t<2 * NF>(T);
-      else cw_wait_t<2 * NF>(T);
+      else if (first && s < 5) cw_wait_t<2 * NF>(T3);
+      else if (s == 0 || s == 1 || s == 6) cw_wait_t<2 * NF>(T3);
+      else if (s <= 5) cw_wait_t<2 * NF>(T3);
+      else cw_wait_t<2 * NF>(T3);
       FSTAMP(1, 1 + 3 * s);
       lds_barrier();                                               // everyone's have; everyone is done with stage s - 1
       FSTAMP(1, 2 + 3 * s);
@@ -941,30 +1019,30 @@ __global__ __launch_bounds__(64 * SYN3_WAVES, 2) void k_dft_synthesis3_h2(const 
       };
       // tables: the y-axis blocks replace the x-axis blocks once every wave has its x block in registers (stage 0); the
       // next tile's x blocks and scales replace them once every wave has its y blocks (stage 4)
-      if (s == 1) issue_table(cur.ty, true);
-      if (s == 5 && has_next) { issue_table(nxt.tx, false); issue_inv(nxt); }
+      if (s == 1) G::issue_table(smem, ln, cur.ty, true);
+      if (s == 5 && has_next) { G::issue_table(smem, ln, nxt.tx, false); G::issue_inv(smem, ln, nxt); }
       const char* slot = smem + slot_s * SLOT + l * 16;
       if (s < 4) {
-        const int a = s >> 1, h = s & 1;
         if (s == 0) {
-          lds_frag(tx, smem + TAB + mt * BB + l * 16);
+          T::lds_frag(tx, smem + TAB + mt * BB + l * 16);
           invx_l[0] = *reinterpret_cast<const float*>(smem + INV + (16 * p + li) * 4);
           invx_l[1] = *reinterpret_cast<const float*>(smem + INV + (16 * (p + 2) + li) * 4);
           invy_l = *reinterpret_cast<const float*>(smem + INV + 256 + (16 * mt + li) * 4);
         }
-        lds_frag(fq[0], slot + (p * 8) * BB);
+        const int a = s >> 1, h = s & 1;
+        T::lds_frag(fq[0], slot + (p * 8) * BB);
 #pragma unroll
         for (int c8 = 0; c8 < 8; ++c8) {
-          if (c8 + 1 < 8) lds_frag(fq[(c8 + 1) & 1], slot + (p * 8 + c8 + 1) * BB);
+          if (c8 + 1 < 8) T::lds_frag(fq[(c8 + 1) & 1], slot + (p * 8 + c8 + 1) * BB);
           asm volatile("" ::: "memory");
-          const f32x4v c = chain(tx, fq[c8 & 1]);
+          const f32x4v c = T::chain(tx, fq[c8 & 1]);
           request(c8);
 #pragma unroll
           for (int jj = 0; jj < 4; ++jj) acc[a][8 * h + c8][jj] = c[jj];
         }
         cw_mark_t((s + 2) % 3);                        // the pieces of stage s + 2 are all requested
         if (s == 3) {
-          // ---- x part -> true units, then turned into the y layout ----
+          // ---- SynTile::turn written out: through the function all five instances are scheduled differently ----
 #pragma unroll
           for (int a2 = 0; a2 < 2; ++a2) {
 #pragma unroll
@@ -991,19 +1069,19 @@ __global__ __launch_bounds__(64 * SYN3_WAVES, 2) void k_dft_synthesis3_h2(const 
       } else {
         const int sy = s - 4;
         if (sy == 0) {
-          lds_frag(ty[0], smem + TAB + ((p * 2 + 0) * NF) * 1024 + l * 16);
-          lds_frag(ty[1], smem + TAB + ((p * 2 + 1) * NF) * 1024 + l * 16);
+          T::lds_frag(ty[0], smem + TAB + ((p * 2 + 0) * NF) * 1024 + l * 16);
+          T::lds_frag(ty[1], smem + TAB + ((p * 2 + 1) * NF) * 1024 + l * 16);
         }
-        lds_frag(fq[0], slot + (mt * 4) * BB);
+        T::lds_frag(fq[0], slot + (mt * 4) * BB);
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
           const int r = 4 * sy + rr;
-          if (rr + 1 < 4) lds_frag(fq[(rr + 1) & 1], slot + (mt * 4 + rr + 1) * BB);
+          if (rr + 1 < 4) T::lds_frag(fq[(rr + 1) & 1], slot + (mt * 4 + rr + 1) * BB);
           asm volatile("" ::: "memory");
           const float sc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(invy_l), r));
 #pragma unroll
           for (int a = 0; a < 2; ++a) {
-            const f32x4v c = chain(ty[a], fq[rr & 1]);
+            const f32x4v c = T::chain(ty[a], fq[rr & 1]);
             request(2 * rr + a);                                  // (2 NF <= 6 pieces: all out before the stage's stores)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -1051,125 +1129,79 @@ __global__ __launch_bounds__(64 * SYN3_WAVES, 2) void k_dft_synthesis3_h2(const 
   }
 }
 
-// ------------------------------------------------------------------------------------------------------------
-// synthesis of both axes, 64 x 32 point tiles x 32 channels: whole 128-byte lines per store (round 4)
-// ------------------------------------------------------------------------------------------------------------
-// k_dft_synthesis3_h2 owns 16 channels of its points, so every store instruction writes sixteen 64-byte segments -- half
-// cache lines -- and a CU's memory pipeline takes such an instruction at a quarter of the rate of one that writes eight
-// whole 128-byte lines (profiles/ubench/storepat.hip: 37 vs 135 GB/s per CU); with the stores in, that kernel ran 225 us
-// against 100 us without them.  Here a workgroup owns a PAIR of channel blocks (32 channels = one 128-byte line per
-// point) of a 64-row x 32-column tile -- the same 128 accumulator registers per lane -- at the price of 2.25 instead of
-// 1.5 bytes of fragments fetched from L2 per byte stored (the fragments of a channel pair of a sample, 3.1 MB at 256^2,
-// still fit the XCD's L2 while all its tiles use them).
-//   * wave (mt, p) owns rows 16 mt .., columns 16 p .. of the tile for BOTH channel blocks a = 0, 1: acc[a][i][jj].
-//   * twelve stages of 16 (line, channel block) fragments through the same 3-slot ring: x stages 0-3 (channel block
-//     s >> 1, columns 8 (s & 1) .. + 7 of both column blocks), y stages 4-11 (rows 2 (s - 4), + 1 of the four row blocks,
-//     both channel blocks).  12 = 0 mod 3: the ring position is the same for every tile.
-//   * a row is final after its y stage and leaves right there: four store instructions per wave and y stage, each
-//     eight points x 128 bytes.  The 4 x 4 quad transpose that gives a lane four consecutive channels of one point
-//     takes its four inputs from BOTH channel blocks -- (a, column) = (0, 0), (0, 1), (1, 0), (1, 1) -- so the lanes
-//     of a quad end up with the two 64-byte halves of two points' lines: no exchange beyond the transpose itself.
-//   * forward and adjoint without a skip gradient (with one: k_dft_synthesis3_h2).
-template <int S> struct StageC { static constexpr int value = S; };
-
-// Tried on top and dropped (same-box, 256^2, B = 32; profiles/r04_synthesis_variants.txt): requesting ALL pieces of stage
-// s + 2 right behind the barrier and issuing the stores of a stage's rows one stage later, behind the next requests, so
-// that a store has three stages instead of two to be acknowledged before a wait on younger pieces covers it (the counter
-// is in order) and no request queues behind a burst of stores: 225-230 us against 219 us.  Neither the store segment
-// (this kernel against k_dft_synthesis3_h2: 219 vs 224-235 us), nor the fragment volume (2.25 vs 1.5 bytes per byte
-// stored), nor the store window moves the time; the same store pattern alone streams at 6.2 TB/s = 87 us
-// (profiles/ubench/storepat.hip, pattern C / D).  What is left is that ONE workgroup per CU runs all its waves through
-// the same phase at the same time -- wait for pieces | fragments + matrix work | transposes + stores -- so the three
-// add up instead of overlapping.
+// ---- kernel 4's tile: 64 x 32 points x 32 channels, (M / 64) (N / 32) 2 items per sample: within a sample all tiles of
+// channel pair 0, then all of pair 1 (a pair's fragments stay in the group's L2 meanwhile) ----
 template <int K32, int TG>
-__global__ __launch_bounds__(64 * SYN3_WAVES, 2) void k_dft_synthesis4_h2(const SynP P) {
-  constexpr int NP = h2_np(TG), NF = 2 * K32 + NP;
-  constexpr int BB = NF * 1024;
-  constexpr long LB = 4L * BB;
-  constexpr int SLOT = 16 * BB;                 // one stage: 16 fragments
-  static_assert(NF <= 3, "ring of three 16-fragment slots + the table corner must fit 160 KB");
-  constexpr int TAB = 3 * SLOT, INV = TAB + 4 * BB, LDS_BYTES = INV + 512;
-  constexpr int NS = 12;                        // stages per tile
-  __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
-  const int tid = threadIdx.x, l = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), g = l >> 4, li = l & 15;
-  const int mt = w & 3, p = w >> 2;
-  const unsigned lane16 = l * 16;
-  typedef Frag<K32, TG> F;
-  typedef __attribute__((address_space(3))) void* lds_ptr;
-  typedef const __attribute__((address_space(1))) void* glb_ptr;
-
-  // ---- items: (sample, channel pair, tile); group x = blockIdx % ng takes the samples x, x + ng, ..; within a sample all
-  // tiles of channel pair 0, then all of pair 1 (a pair's fragments stay in the group's L2 meanwhile)
-  const int tn = P.N >> 5, tiles = (P.M >> 6) * tn, wps = tiles * 2;
-  const int ng = P.sy;
-  const int xg = blockIdx.x % ng, jw = blockIdx.x / ng, nj = gridDim.x / ng;
-  const int nsamp = (P.B - xg + ng - 1) / ng;
-  const long nitems = (long)nsamp * wps;
-  auto item_at = [&](long q) {
-    Syn3Item it;
+struct Syn4Geom {
+  typedef SynTile<K32, TG> T;
+  int tn, tiles, wps;
+  __device__ __forceinline__ Syn4Geom(const SynP& P) : tn(P.N >> 5), tiles((P.M >> 6) * tn), wps(tiles * 2) {}
+  __device__ __forceinline__ SynItem item_at(const SynP& P, const SynWalk& wk, long q) const {
+    SynItem it;
     const int sb = (int)(q / wps), t = (int)(q - (long)sb * wps);
     const int hb = t / tiles, tile = t - hb * tiles;
-    const int b = xg + ng * sb;
+    const int b = wk.xg + wk.ng * sb;
     const int m0 = (tile / tn) << 6, n0 = (tile % tn) << 5;
-    it.gx = P.imgx + ((long)b * P.N + n0) * LB + (2 * hb) * BB;
-    it.gy = P.imgy + ((long)b * P.M + m0) * LB + (2 * hb) * BB;
-    it.tx = P.tabx + (long)(m0 >> 4) * BB;
-    it.ty = P.taby + (long)(n0 >> 4) * BB;
+    it.gx = P.imgx + ((long)b * P.N + n0) * T::LB + (2 * hb) * T::BB;
+    it.gy = P.imgy + ((long)b * P.M + m0) * T::LB + (2 * hb) * T::BB;
+    it.tx = P.tabx + (long)(m0 >> 4) * T::BB;
+    it.ty = P.taby + (long)(n0 >> 4) * T::BB;
     it.ivx = P.invx + (long)b * P.N + n0;
     it.ivy = P.invy + (long)b * P.M + m0;
     it.o = (((long)b * P.M + m0) * P.N + n0) * 64 + 32 * hb;
     return it;
-  };
-  long q = jw;
-  if (q >= nitems) return;
-  Syn3Item cur = item_at(q);
-
+  }
   // piece i (of 2 NF) of this wave for stage s of a tile
-  auto issue_piece = [&](const Syn3Item& it, int s, int i, int slot) {
-    const int idx = w + 8 * i, ell = idx / NF, f = idx - ell * NF;     // fragment ell of the stage, piece f of it
+  __device__ static __forceinline__ void issue_piece(char* smem, const SynLane& ln, const SynItem& it, int s, int i, int slot) {
+    constexpr int NF = T::NF;
+    const int idx = ln.w + 8 * i, ell = idx / NF, f = idx - ell * NF;     // fragment ell of the stage, piece f of it
     const char* src;
-    if (s < 4) src = it.gx + (long)(16 * (ell >> 3) + 8 * (s & 1) + (ell & 7)) * LB + (s >> 1) * BB + f * 1024;
-    else src = it.gy + (long)(16 * (ell >> 2) + 2 * (s - 4) + ((ell >> 1) & 1)) * LB + (ell & 1) * BB + f * 1024;
-    __builtin_amdgcn_global_load_lds((glb_ptr)(src + lane16), (lds_ptr)(smem + slot * SLOT + idx * 1024), 16, 0, 0);
-  };
-  // nblk consecutive 16-row blocks of a table (x axis: the tile's four row blocks; y axis: its two column blocks)
-  auto issue_table = [&](const char* tab, int nblk) {
+    if (s < 4) src = it.gx + (long)(16 * (ell >> 3) + 8 * (s & 1) + (ell & 7)) * T::LB + (s >> 1) * T::BB + f * 1024;
+    else src = it.gy + (long)(16 * (ell >> 2) + 2 * (s - 4) + ((ell >> 1) & 1)) * T::LB + (ell & 1) * T::BB + f * 1024;
+    __builtin_amdgcn_global_load_lds((typename T::glb_ptr)(src + ln.lane16), (typename T::lds_ptr)(smem + slot * T::SLOT + idx * 1024), 16, 0, 0);
+  }
+  // consecutive 16-row blocks of a table (x axis: the tile's four row blocks; y axis: its two column blocks)
+  __device__ static __forceinline__ void issue_table(char* smem, const SynLane& ln, const char* tab, bool yaxis) {
+    constexpr int NF = T::NF;
+    const int nblk = yaxis ? 2 : 4;
 #pragma unroll
     for (int i = 0; i < (4 * NF + 7) / 8; ++i) {
-      const int idx = w + 8 * i;
-      if (idx < nblk * NF)
-        __builtin_amdgcn_global_load_lds((glb_ptr)(tab + (long)idx * 1024 + lane16), (lds_ptr)(smem + TAB + idx * 1024), 16, 0, 0);
+      const int idx = ln.w + 8 * i;
+      if (idx < nblk * NF) __builtin_amdgcn_global_load_lds((typename T::glb_ptr)(tab + (long)idx * 1024 + ln.lane16), (typename T::lds_ptr)(smem + T::TAB + idx * 1024), 16, 0, 0);
     }
-  };
-  auto issue_inv = [&](const Syn3Item& it) {          // 32 + 64 floats, one 4-byte DMA each
-    if (w == 6 && l < 32) __builtin_amdgcn_global_load_lds((glb_ptr)(it.ivx + l), (lds_ptr)(smem + INV), 4, 0, 0);
-    if (w == 7) __builtin_amdgcn_global_load_lds((glb_ptr)(it.ivy + l), (lds_ptr)(smem + INV + 256), 4, 0, 0);
-  };
-  auto lds_frag = [&](F& f, const char* base) {
-#pragma unroll
-    for (int s2 = 0; s2 < K32; ++s2) {
-      f.h[s2] = *reinterpret_cast<const f16x8*>(base + s2 * 1024);
-      f.lo[s2] = *reinterpret_cast<const f16x8*>(base + (K32 + s2) * 1024);
-    }
-#pragma unroll
-    for (int qq = 0; qq < NP; ++qq) f.pk[qq] = *reinterpret_cast<const f16x8*>(base + (2 * K32 + qq) * 1024);
-  };
-  auto chain = [&](const F& tab, const F& f) {
-    f32x4v c = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int qq = 0; qq < NP; ++qq) c = __builtin_amdgcn_mfma_f32_16x16x32_f16(tab.pk[qq], f.pk[qq], c, 0, 0, 0);
-#pragma unroll
-    for (int s2 = K32 - 1; s2 >= 0; --s2) {
-      c = __builtin_amdgcn_mfma_f32_16x16x32_f16(tab.lo[s2], f.h[s2], c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_16x16x32_f16(tab.h[s2], f.lo[s2], c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_16x16x32_f16(tab.h[s2], f.h[s2], c, 0, 0, 0);
-    }
-    return c;
-  };
+  }
+  __device__ static __forceinline__ void issue_inv(char* smem, const SynLane& ln, const SynItem& it) {          // 32 + 64 floats, one 4-byte DMA each
+    if (ln.w == 6 && ln.l < 32) __builtin_amdgcn_global_load_lds((typename T::glb_ptr)(it.ivx + ln.l), (typename T::lds_ptr)(smem + T::INV), 4, 0, 0);
+    if (ln.w == 7) __builtin_amdgcn_global_load_lds((typename T::glb_ptr)(it.ivy + ln.l), (typename T::lds_ptr)(smem + T::INV + 256), 4, 0, 0);
+  }
+};
 
-  // ---- prologue: tables / scales of the first tile, then its first two stages ----
-  issue_table(cur.tx, 4);
-  issue_inv(cur);
+template <int S> struct StageC { static constexpr int value = S; };
+
+template <int K32, int TG>
+__global__ __launch_bounds__(64 * SYN3_WAVES, 2) void k_dft_synthesis4_h2(const SynP P) {
+  typedef SynTile<K32, TG> T;
+  typedef Syn4Geom<K32, TG> G;
+  typedef typename T::F F;
+  constexpr int NF = T::NF, BB = T::BB, SLOT = T::SLOT, TAB = T::TAB, INV = T::INV;
+  constexpr int NS = 12;                        // stages per tile
+  __shared__ __attribute__((aligned(16))) char smem[T::LDS_BYTES];
+  const SynLane ln = SynLane::here();
+  const int l = ln.l, g = ln.g, li = ln.li, mt = ln.mt, p = ln.p;
+  const G geo(P);
+  const SynWalk wk(P, geo.wps);
+  long q = wk.jw;
+  if (q >= wk.nitems) return;
+  SynItem cur = geo.item_at(P, wk, q);
+  const int w = ln.w;
+  const unsigned lane16 = l * 16;
+  typedef typename T::glb_ptr glb_ptr; typedef typename T::lds_ptr lds_ptr;
+  constexpr long LB = T::LB;
+  auto issue_piece = [&](const SynItem& it, int s, int i, int slot) { G::issue_piece(smem, ln, it, s, i, slot); };
+  // ---- prologue: tables / scales of the first tile, then its first two stages (in place in both kernels: as a shared
+  // function it changes every instance's schedule) ----
+  G::issue_table(smem, ln, cur.tx, false);
+  G::issue_inv(smem, ln, cur);
 #pragma unroll
   for (int i = 0; i < 2 * NF; ++i) issue_piece(cur, 0, i, 0);
   cw_mark<3>();                 // (tags 3 / 4: the first tile's stages 0 / 1, waited for under `first` -- a path-insensitive
@@ -1183,10 +1215,10 @@ __global__ __launch_bounds__(64 * SYN3_WAVES, 2) void k_dft_synthesis4_h2(const 
   float acc[2][16][4];
 
   while (true) {
-    const long qn = q + nj;
-    const bool has_next = qn < nitems;
-    Syn3Item nxt = cur;
-    if (has_next) nxt = item_at(qn);
+    const long qn = q + wk.nj;
+    const bool has_next = qn < wk.nitems;
+    SynItem nxt = cur;
+    if (has_next) nxt = geo.item_at(P, wk, qn);
     F tx, ty;
     F fq[2];
     float invx_l, invy_l;
@@ -1210,80 +1242,49 @@ __global__ __launch_bounds__(64 * SYN3_WAVES, 2) void k_dft_synthesis4_h2(const 
       // than the pieces of stage s are the stores of stage s - 2 (4 if it was a y stage), the pieces of stage s + 1
       // (2 NF) and the stores of stage s - 1; table / scale pieces issued in between only make the wait longer
       // (cw.h: tag = ring slot; tests/test_isa_counted_waits_cpu.py checks these counts on the compiled code)
-      constexpr int T = s % 3;
+      constexpr int T3 = s % 3;
       // (every stage requests its 2 NF pieces, the last tile's stages 10 / 11 a harmless re-read: the counts do not
       //  depend on has_next)
-      if (s == 0) { if (first) cw_wait<3, 2 * NF>(); else cw_wait<T, 2 * NF + 8>(); }
-      else if (s == 1) { if (first) cw_wait<4, 2 * NF>(); else cw_wait<T, 2 * NF + 4>(); }
-      else if (s <= 4) cw_wait<T, 2 * NF>();
-      else if (s == 5) cw_wait<T, 2 * NF + 4>();
-      else cw_wait<T, 2 * NF + 8>();
+      if (s == 0) { if (first) cw_wait<3, 2 * NF>(); else cw_wait<T3, 2 * NF + 8>(); }
+      else if (s == 1) { if (first) cw_wait<4, 2 * NF>(); else cw_wait<T3, 2 * NF + 4>(); }
+      else if (s <= 4) cw_wait<T3, 2 * NF>();
+      else if (s == 5) cw_wait<T3, 2 * NF + 4>();
+      else cw_wait<T3, 2 * NF + 8>();
       lds_barrier();                                               // everyone's have; everyone is done with stage s - 1
       const int slot_s = s % 3, slot_n = (s + 2) % 3;
       auto request = [&](int i) {
         if (i >= 2 * NF) return;
         if (s + 2 < NS) issue_piece(cur, s + 2, i, slot_n);
-        else issue_piece(nxt, s + 2 - NS, i, slot_n);          // (last tile: nxt = cur, a re-read nobody uses)
+        else issue_piece(nxt, s + 2 - NS, i, slot_n);   // (last tile: nxt = cur, a re-read nobody uses)
       };
       // tables: the y-axis blocks replace the x-axis blocks once every wave has its x block in registers (stage 0); the
       // next tile's x blocks and scales replace them once every wave has its y block (stage 4)
-      if (s == 1) issue_table(cur.ty, 2);
-      if (s == 5 && has_next) { issue_table(nxt.tx, 4); issue_inv(nxt); }
+      if (s == 1) G::issue_table(smem, ln, cur.ty, true);
+      if (s == 5 && has_next) { G::issue_table(smem, ln, nxt.tx, false); G::issue_inv(smem, ln, nxt); }
       const char* slot = smem + slot_s * SLOT + l * 16;
       if (s < 4) {
-        const int a = s >> 1, h = s & 1;
         if (s == 0) {
-          lds_frag(tx, smem + TAB + mt * BB + l * 16);
+          T::lds_frag(tx, smem + TAB + mt * BB + l * 16);
           invx_l = *reinterpret_cast<const float*>(smem + INV + (16 * p + li) * 4);
           invy_l = *reinterpret_cast<const float*>(smem + INV + 256 + (16 * mt + li) * 4);
         }
-        lds_frag(fq[0], slot + (p * 8) * BB);
-#pragma unroll
-        for (int c8 = 0; c8 < 8; ++c8) {
-          if (c8 + 1 < 8) lds_frag(fq[(c8 + 1) & 1], slot + (p * 8 + c8 + 1) * BB);
-          asm volatile("" ::: "memory");
-          const f32x4v c = chain(tx, fq[c8 & 1]);
-          request(c8);
-#pragma unroll
-          for (int jj = 0; jj < 4; ++jj) acc[a][8 * h + c8][jj] = c[jj];
-        }
+        T::x_stage(ln, s, slot, tx, fq, acc, request);
         cw_mark<(s + 2) % 3>();                        // the pieces of stage s + 2 are all requested
         if (s == 3) {
-          // ---- x part -> true units, then turned into the y layout (k_dft_synthesis3_h2's turn) ----
 #pragma unroll
-          for (int a2 = 0; a2 < 2; ++a2) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-              const float sc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(invx_l), i));
-#pragma unroll
-              for (int jj = 0; jj < 4; ++jj) acc[a2][i][jj] *= sc;
-            }
-#pragma unroll
-            for (int jy = 0; jy < 4; ++jy)
-#pragma unroll
-              for (int jr = 0; jr < 4; ++jr) {
-                swap_halves(acc[a2][jy][jr], acc[a2][8 + jy][jr]);
-                swap_halves(acc[a2][4 + jy][jr], acc[a2][12 + jy][jr]);
-                swap_rows(acc[a2][jy][jr], acc[a2][4 + jy][jr]);
-                swap_rows(acc[a2][8 + jy][jr], acc[a2][12 + jy][jr]);
-              }
-#pragma unroll
-            for (int i = 0; i < 16; ++i)
-#pragma unroll
-              for (int jj = 0; jj < 4; ++jj) pin(acc[a2][i][jj]);
-          }
+          for (int a2 = 0; a2 < 2; ++a2) T::turn(acc[a2], invx_l);
         }
       } else {
         const int sy = s - 4;
-        if (sy == 0) lds_frag(ty, smem + TAB + p * BB + l * 16);
-        lds_frag(fq[0], slot + (mt * 4) * BB);
+        if (sy == 0) T::lds_frag(ty, smem + TAB + p * BB + l * 16);
+        T::lds_frag(fq[0], slot + (mt * 4) * BB);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {                   // fragment mt * 4 + e: row 2 sy + (e >> 1), channel block e & 1
           const int r = 2 * sy + (e >> 1), a = e & 1;
-          if (e + 1 < 4) lds_frag(fq[(e + 1) & 1], slot + (mt * 4 + e + 1) * BB);
+          if (e + 1 < 4) T::lds_frag(fq[(e + 1) & 1], slot + (mt * 4 + e + 1) * BB);
           asm volatile("" ::: "memory");
           const float sc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(invy_l), r));
-          const f32x4v c = chain(ty, fq[e & 1]);
+          const f32x4v c = T::chain(ty, fq[e & 1]);
           request(2 * e);
           request(2 * e + 1);                           // (2 NF <= 6 pieces: all out before the stage's stores)
 #pragma unroll
@@ -1324,19 +1325,6 @@ bool fused2d_ok(int M, int N, int C, int keff_y, int keff_x) {
 }
 
 size_t fused2d_img_bytes(long lines, int R) { return (size_t)lines * 4 * h2_block_bytes(R / 32, (R % 32) / 8); }
-
-// R = 8 .. 48 in steps of 8 -> (K32, TG) = (0,1) (0,2) (0,3) (1,0) (1,1) (1,2)
-#define RPDE_H2_DISPATCH(KERNEL, R, ...)                                                        \
-  do {                                                                                          \
-    switch ((R) / 8) {                                                                          \
-      case 1: hipLaunchKernelGGL((KERNEL<0, 1>), __VA_ARGS__); break;                           \
-      case 2: hipLaunchKernelGGL((KERNEL<0, 2>), __VA_ARGS__); break;                           \
-      case 3: hipLaunchKernelGGL((KERNEL<0, 3>), __VA_ARGS__); break;                           \
-      case 4: hipLaunchKernelGGL((KERNEL<1, 0>), __VA_ARGS__); break;                           \
-      case 5: hipLaunchKernelGGL((KERNEL<1, 1>), __VA_ARGS__); break;                           \
-      default: hipLaunchKernelGGL((KERNEL<1, 2>), __VA_ARGS__); break;                          \
-    }                                                                                           \
-  } while (0)
 
 // RPDE_ANA_SQ=0: keep the two-read analysis kernel for every shape (A/B, tests).  Default: the one-pass kernel on every
 // square grid (its round-3 predecessor, with a workgroup's rows matched to the grid, was level with the two-read kernel
@@ -1398,7 +1386,9 @@ int fused2d_analysis(const float* x, float* spec_y, float* spec_x, float* amax_y
 
 int fused2d_split(const float* spec, void* img, float* inv, long lines, int R, hipStream_t st) {
   const dim3 grid((unsigned)lines), blk(256);
-  RPDE_H2_DISPATCH(k_spec_split_h2, R, grid, blk, 0, st, spec, (char*)img, inv, R);
+  h2_dispatch(R, [&](auto k32, auto tg) {
+    hipLaunchKernelGGL((k_spec_split_h2<k32(), tg()>), grid, blk, 0, st, spec, (char*)img, inv, R);
+  });
   RPDE_LAUNCH_CHECK();
   return RPDE_OK;
 }
@@ -1415,61 +1405,36 @@ int fused2d_synthesis(const void* imgy, const void* imgx, const float* invy, con
   P.imgy = (const char*)imgy; P.imgx = (const char*)imgx; P.invy = invy; P.invx = invx;
   P.taby = (const char*)py->h2_syn[adjoint]; P.tabx = (const char*)px->h2_syn[adjoint];
   P.out = out; P.skip = skip; P.B = B; P.M = M; P.N = N;
-  const int R3 = 2 * py->kp;
-  const int NF3 = 2 * (R3 / 32) + (3 * ((R3 % 32) / 8) + 3) / 4;
-  if (syn3_ok(M, N) && NF3 <= 3) {
+  const int R = 2 * py->kp;
+  if (syn3_ok(M, N) && 2 * (R / 32) + h2_np((R % 32) / 8) <= 3) {
+    // the persistent kernels (three fragments per block at most, R <= 40): one workgroup per CU, in 8 groups (one per
+    // XCD; fewer when the batch is smaller); never more per group than the busiest group has items.  Without a skip
+    // gradient 64 x 32 x 32-channel tiles, whole 128-byte lines per store: (M / 64) (N / 32) 2 items per sample; with
+    // it 64 x 64 x 16-channel tiles, (M / 64) (N / 64) 4 items per sample
     int cus;
     RPDE_HIP(cu_count(&cus));
-    if (!skip) {
-      // 64 x 32 x 32-channel tiles, whole 128-byte lines per store: (M / 64) (N / 32) 2 items per sample
-      const int ng = B < 8 ? B : 8;
-      P.sy = ng;
-      P.sx = 1;
-      const long wps = (long)(M / 64) * (N / 32) * 2;
-      long per_group = cus / ng;
-      const long most = (long)((B + ng - 1) / ng) * wps;
-      if (per_group > most) per_group = most;
-      if (per_group < 1) per_group = 1;
-      const dim3 grid4((unsigned)(ng * per_group)), blk4(64 * SYN3_WAVES);
-      switch (R3 / 8) {
-        case 1: hipLaunchKernelGGL((k_dft_synthesis4_h2<0, 1>), grid4, blk4, 0, st, P); break;
-        case 2: hipLaunchKernelGGL((k_dft_synthesis4_h2<0, 2>), grid4, blk4, 0, st, P); break;
-        case 3: hipLaunchKernelGGL((k_dft_synthesis4_h2<0, 3>), grid4, blk4, 0, st, P); break;
-        case 4: hipLaunchKernelGGL((k_dft_synthesis4_h2<1, 0>), grid4, blk4, 0, st, P); break;
-        default: hipLaunchKernelGGL((k_dft_synthesis4_h2<1, 1>), grid4, blk4, 0, st, P); break;
-      }
-      RPDE_LAUNCH_CHECK();
-      return RPDE_OK;
-    }
-    // with the skip gradient: 64 x 64 x 16-channel tiles, (M / 64) (N / 64) 4 items per sample.  Persistent: one workgroup
-    // per CU, in 8 groups (one per XCD; fewer when the batch is smaller); never more per group than the busiest group
-    // has tiles
     const int ng = B < 8 ? B : 8;
     P.sy = ng;
     P.sx = 1;
-    const long wps = (long)(M / 64) * (N / 64) * 4;
+    const long wps = skip ? (long)(M / 64) * (N / 64) * 4 : (long)(M / 64) * (N / 32) * 2;
     long per_group = cus / ng;
     const long most = (long)((B + ng - 1) / ng) * wps;
     if (per_group > most) per_group = most;
     if (per_group < 1) per_group = 1;
-    const dim3 grid3((unsigned)(ng * per_group)), blk3(64 * SYN3_WAVES);
-    switch (R3 / 8) {
-      case 1: hipLaunchKernelGGL((k_dft_synthesis3_h2<0, 1>), grid3, blk3, 0, st, P); break;
-      case 2: hipLaunchKernelGGL((k_dft_synthesis3_h2<0, 2>), grid3, blk3, 0, st, P); break;
-      case 3: hipLaunchKernelGGL((k_dft_synthesis3_h2<0, 3>), grid3, blk3, 0, st, P); break;
-      case 4: hipLaunchKernelGGL((k_dft_synthesis3_h2<1, 0>), grid3, blk3, 0, st, P); break;
-      default: hipLaunchKernelGGL((k_dft_synthesis3_h2<1, 1>), grid3, blk3, 0, st, P); break;
-    }
+    const dim3 grid((unsigned)(ng * per_group)), blk(64 * SYN3_WAVES);
+    h2_dispatch</* UP_TO_40 = */ true>(R, [&](auto k32, auto tg) {
+      if (skip) hipLaunchKernelGGL((k_dft_synthesis3_h2<k32(), tg()>), grid, blk, 0, st, P);
+      else hipLaunchKernelGGL((k_dft_synthesis4_h2<k32(), tg()>), grid, blk, 0, st, P);
+    });
     RPDE_LAUNCH_CHECK();
     return RPDE_OK;
   }
   // (super-tile side, measured at B = 32, 256^2, forward + backward: 2 -> 1.52 ms, 4 -> 1.44, 8 -> 1.45, 16 -> 1.53)
   auto side = [](int tiles) { int s = tiles < 8 ? tiles : 8; while (tiles % s) --s; return s; };
   P.sy = side(M / 16); P.sx = side(N / 16);
-  const int R = 2 * py->kp;
   const long tps = (long)(M / 16) * (N / 16);
   const dim3 grid((unsigned)(((B + 7) / 8) * 8 * tps)), blk(256);
-  RPDE_H2_DISPATCH(k_dft_synthesis2_h2, R, grid, blk, 0, st, P);
+  h2_dispatch(R, [&](auto k32, auto tg) { hipLaunchKernelGGL((k_dft_synthesis2_h2<k32(), tg()>), grid, blk, 0, st, P); });
   RPDE_LAUNCH_CHECK();
   return RPDE_OK;
 }

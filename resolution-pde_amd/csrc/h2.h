@@ -77,6 +77,6 @@ __device__ __forceinline__ f32x4v h2_mfma32(f16x8 ah, f16x8 al, f16x8 bh, f16x8 
 //  half of the result is wrong; with s_nop padding between them, or in the order 16-deep -> 32-deep, it is exact.  The
 //  shorter instruction reads its SrcC before the longer one has written all of it, and neither the hardware nor the
 //  compiler's hazard recognizer waits for this opcode pair.  Same-shape chains are handled.  Short reduction tails are
-//  therefore packed into 32-deep fragments -- fused_spectral.hip, h2_store_tail -- which also costs no padding.)
+//  therefore packed into 32-deep fragments -- fused_spectral.h, H2Block -- which also costs no padding.)
 
 }  // namespace rpde

@@ -13,7 +13,7 @@
 //   forward    k_lift_analysis   S_u[line][2kp][Cin] = Fa . u-line, both axes, exact fp32           (25 MB read at 256^2, B = 32)
 //              k_lift_wprime     W' of both axes from W_in, b_in and the two mode-mix weights
 //              k_lift_mix        Cin -> 64 per (line, mode) in fp32, written as the operand blocks + line scales that
-//                                k_spec_split_h2 would write for that spectrum (fused_spectral.hip, "operand blocks")
+//                                k_spec_split_h2 would write for that spectrum (fused_spectral.h, "operand blocks")
 //              fused2d_synthesis unchanged
 //   backward   fused2d_analysis of g (adjoint tables), unchanged
 //              k_lift_tgrad      T[axis][k][j][o] = sum_lines conj(S_u~[line][k][j]) G[line][k][o]: partial sums over
@@ -193,7 +193,7 @@ template <int K32, int TG, int CIN>
 __global__ __launch_bounds__(256) void k_lift_mix(const LiftMixP P) {
   constexpr int NF = K32 + (TG ? 1 : 0);
   constexpr int CA = CIN + 1;
-  constexpr int BB = h2_block_bytes(K32, TG);
+  typedef H2Block<K32, TG> L;
   __shared__ float sl[LIFT_ML * 48 * CIN];
   __shared__ float wmax[2][4];
   const int tid = threadIdx.x, l = tid & 63, cb = tid >> 6, g = l >> 4, li = l & 15;
@@ -249,7 +249,7 @@ __global__ __launch_bounds__(256) void k_lift_mix(const LiftMixP P) {
     float scale, inv;
     h2_scale(m, H2_TABLE_EXP, scale, inv);
     if (tid == 0) P.inv[a][line] = inv;
-    char* blk = P.img[a] + (line * 4 + cb) * (long)BB;
+    char* blk = P.img[a] + (line * 4 + cb) * (long)L::BYTES;
 #pragma unroll
     for (int s = 0; s < NF; ++s) {
 #pragma unroll
@@ -257,21 +257,13 @@ __global__ __launch_bounds__(256) void k_lift_mix(const LiftMixP P) {
       uint4 hi, lo;
       h2_split8(v[s], hi, lo);
       if (s < K32) {
-        *reinterpret_cast<uint4*>(blk + s * 1024 + l * 16) = hi;
-        *reinterpret_cast<uint4*>(blk + (K32 + s) * 1024 + l * 16) = lo;
+        *reinterpret_cast<uint4*>(blk + L::hi(s) + l * 16) = hi;
+        *reinterpret_cast<uint4*>(blk + L::lo(s) + l * 16) = lo;
       } else if (g < TG) {
-#pragma unroll
-        for (int tt = 0; tt < 3; ++tt) {                 // spectrum side of the packed tail: (hi, lo, hi)
-          const int slot = tt * TG + g;
-          *reinterpret_cast<uint4*>(blk + (2 * K32 + slot / 4) * 1024 + ((slot & 3) * 16 + li) * 16) = tt == 1 ? lo : hi;
-        }
+        L::template store_tail<false>(blk, g, li, hi, lo);
       }
     }
-    if (TG > 0 && g == 0) {                              // slots of the packed fragments that no group uses
-#pragma unroll
-      for (int slot = 3 * TG; slot < 4 * h2_np(TG); ++slot)
-        *reinterpret_cast<uint4*>(blk + (2 * K32 + slot / 4) * 1024 + ((slot & 3) * 16 + li) * 16) = make_uint4(0, 0, 0, 0);
-    }
+    if (TG > 0 && g == 0) L::zero_unused(blk, li);
   }
 }
 
@@ -460,18 +452,6 @@ struct LiftBwdWork {
     }                                             \
   } while (0)
 
-template <int CIN>
-static void launch_lift_mix(int R, dim3 grid, hipStream_t st, const LiftMixP& P) {
-  switch (R / 8) {
-    case 1: hipLaunchKernelGGL((k_lift_mix<0, 1, CIN>), grid, dim3(256), 0, st, P); break;
-    case 2: hipLaunchKernelGGL((k_lift_mix<0, 2, CIN>), grid, dim3(256), 0, st, P); break;
-    case 3: hipLaunchKernelGGL((k_lift_mix<0, 3, CIN>), grid, dim3(256), 0, st, P); break;
-    case 4: hipLaunchKernelGGL((k_lift_mix<1, 0, CIN>), grid, dim3(256), 0, st, P); break;
-    case 5: hipLaunchKernelGGL((k_lift_mix<1, 1, CIN>), grid, dim3(256), 0, st, P); break;
-    default: hipLaunchKernelGGL((k_lift_mix<1, 2, CIN>), grid, dim3(256), 0, st, P); break;
-  }
-}
-
 static int lift_plans(const LiftGeom& g, const rpde_plan** py, const rpde_plan** px, hipStream_t st) {
   RPDE_TRY(get_plan(py, g.n[0], g.keff, RPDE_NORM_ORTHO, 0, PLAN_REAL, st));
   return get_plan(px, g.n[1], g.keff, RPDE_NORM_ORTHO, 0, PLAN_REAL, st);
@@ -527,7 +507,9 @@ int rpde_lifted_fspectral2d_fwd(const float* u, const float* w_in, const float* 
   P.wp = wk.wp; P.nblk_y = g.lines[0] / LIFT_ML; P.sqn[0] = sqrtf((float)g.n[0]); P.sqn[1] = sqrtf((float)g.n[1]);
   P.kp = g.kp; P.R = g.R;
   const dim3 mgrid((unsigned)(g.lines[0] / LIFT_ML + g.lines[1] / LIFT_ML));
-  RPDE_LIFT_CIN(Cin, launch_lift_mix<CIN>(g.R, mgrid, st, P));
+  RPDE_LIFT_CIN(Cin, h2_dispatch(g.R, [&](auto k32, auto tg) {
+                  hipLaunchKernelGGL((k_lift_mix<k32(), tg(), CIN>), mgrid, dim3(256), 0, st, P);
+                }));
   RPDE_LAUNCH_CHECK();
   return fused2d_synthesis(wk.imgy, wk.imgx, wk.invy, wk.invx, py, px, 0, out, nullptr, B, M, N, st);
 }

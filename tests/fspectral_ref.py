@@ -147,7 +147,6 @@ def legs(case):
     if not fused_ok(case):
         return []
     B, M, N, C, K = case.dims
-    R = 2 * 4 * ((keffs(case)["dWy"] + 3) // 4)
     full = case.mode == "full"
     out = [("RPDE_FUSED_SPECTRAL", "differ"), ("RPDE_FUSED_MIX", "differ" if full else "same")]
     if M == N:
@@ -155,11 +154,10 @@ def legs(case):
         # every grid of more than one chunk (on 32 points both kernels add the same one chunk)
         out.append(("RPDE_ANA_SQ", "differ" if M > 32 else None))
     if M % 64 == 0 and N % 64 == 0:
-        # where the persistent kernels run (NF3 <= 3) nothing is asserted: all three synthesis kernels feed the same operand
-        # blocks and table fragments to the same MFMA chain per output point, only the tiling differs, and the bits come out
-        # the same (measured on every such case) -- the leg is still held to float64
-        nf3 = 2 * (R // 32) + (3 * ((R % 32) // 8) + 3) // 4
-        out.append(("RPDE_SYN3", None if nf3 <= 3 else "same"))
+        # "same" with and without the persistent kernels (which run where NF3 = 2 (R/32) + (3 (R%32)/8 + 3)/4 <= 3): all
+        # three synthesis kernels feed the same operand blocks and table fragments to the same MFMA chain per output point
+        # and add the two axes in the same order, only the tiling differs -- the switch changes no bit
+        out.append(("RPDE_SYN3", "same"))
     return out
 
 

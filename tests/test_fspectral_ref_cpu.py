@@ -102,7 +102,7 @@ def test_case_tables_reach_the_branches_they_name():
         assert B * M * N * C <= 5 * 256 * 256 * 64                          # no case larger than F-chunk
     sw = {c.name: dict(S.legs(c)) for c in S.CASES_2D}
     assert all(not sw[c.name] for c in S.CASES_2D if not S.fused_ok(c))
-    assert sw["F-r48"]["RPDE_SYN3"] == "same" and sw["F-r8"]["RPDE_SYN3"] is None
+    assert sw["F-r48"]["RPDE_SYN3"] == "same" and sw["F-r8"]["RPDE_SYN3"] == "same"
     assert "RPDE_SYN3" not in sw["F-nyq"] and "RPDE_ANA_SQ" not in sw["F-rect24"]
     assert sw["F-chunk"]["RPDE_ANA_SQ"] == "differ" and sw["F-lowpass"]["RPDE_FUSED_MIX"] == "same"
     # Nyquist on the fused path; the clamp per axis; the partial last chunk of the two-read analysis
