@@ -29,13 +29,17 @@ DROP = (".loc", ".file", ".cfi", ".p2align", ";")
 
 
 def _short(name):
-    """_ZN4rpde19k_dft_synthesis3_h2ILi0ELi1EEEvNS_4SynPE -> k_dft_synthesis3_h2<0,1>"""
+    """_ZN4rpde19k_dft_synthesis3_h2ILi0ELi1EEEvNS_4SynPE -> k_dft_synthesis3_h2<0,1>; bool arguments (Lb0E / Lb1E)
+    are kept as false / true, so that every instance of k_wgrad_h2<.., ACT, DG> or k_ff3_bwd_h2<RECOMP> has its own row"""
     m = re.match(r"_ZN4rpde(\d+)", name)
     if not m:
         return name
     base, rest = name[m.end():m.end() + int(m.group(1))], name[m.end() + int(m.group(1)):]
-    t = re.match(r"I((?:Li\d+E)+)E", rest)
-    return base + ("<" + ",".join(re.findall(r"Li(\d+)E", t.group(1))) + ">" if t else "")
+    t = re.match(r"I((?:L[ib]\d+E)+)E", rest)
+    if not t:
+        return base
+    args = [("false", "true")[int(v)] if k == "b" else v for k, v in re.findall(r"L([ib])(\d+)E", t.group(1))]
+    return base + "<" + ",".join(args) + ">"
 
 
 def stream(body):
@@ -111,19 +115,19 @@ def compare(pa, pb):
     bad = 0
     for src in sorted(set(a) | set(b)):
         print(f"== {src}.hip")
-        print(f"{'kernel':30s} {'stream':8s} {'insts':>13s} {'vgpr':>9s} {'sgpr':>9s} {'lds':>15s} {'scratch':>7s}")
+        print(f"{'kernel':36s} {'stream':8s} {'insts':>13s} {'vgpr':>9s} {'sgpr':>9s} {'lds':>15s} {'scratch':>7s}")
         ka, kb = a.get(src, {}), b.get(src, {})
         for name in sorted(set(ka) | set(kb)):
             x, y = ka.get(name), kb.get(name)
             if x is None or y is None:
                 z = x or y
-                print(f"{name:30s} {'new' if x is None else 'gone':8s} {z['insts']:>13d} {z['vgpr']:>9d} {z['sgpr']:>9d} {z['lds']:>15d} "
+                print(f"{name:36s} {'new' if x is None else 'gone':8s} {z['insts']:>13d} {z['vgpr']:>9d} {z['sgpr']:>9d} {z['lds']:>15d} "
                       f"{z['scratch']:>7d}")
                 bad += y is not None and y["scratch"] > 0
                 continue
             same = x["hash"] == y["hash"]
             pair = lambda k: str(x[k]) if x[k] == y[k] else f"{x[k]}->{y[k]}"
-            print(f"{name:30s} {'same' if same else 'CHANGED':8s} {pair('insts'):>13s} {pair('vgpr'):>9s} {pair('sgpr'):>9s} "
+            print(f"{name:36s} {'same' if same else 'CHANGED':8s} {pair('insts'):>13s} {pair('vgpr'):>9s} {pair('sgpr'):>9s} "
                   f"{pair('lds'):>15s} {pair('scratch'):>7s}")
             if y["scratch"] > x["scratch"] or y["lds"] != x["lds"]:
                 bad += 1

@@ -66,9 +66,7 @@ __global__ __launch_bounds__(512) void k_conv_syn_h2(const float* __restrict__ x
   char* const traw = raw + RAW;
   char* const stage = traw + TRAW;
   const unsigned stage_a = lds_addr(stage), raw_a = lds_addr(raw);
-  const int q = li >> 2, pp = li & 3;
-  const int tsw = ((q >> 1) & 1) | ((g & 1) << 1);
-  const int trow = (8 * g + q) * 128 + pp * 8;
+  const StageTr tr(g, li);                      // transposing-read address of this lane inside a piece (wave.h)
 
   const int nw = N >> 6, rpi = 8 / nw;                 // waves per row, rows per pass of the workgroup
   const int n0 = 64 * (wave % nw), wrow = wave / nw;
@@ -244,7 +242,7 @@ __global__ __launch_bounds__(512) void k_conv_syn_h2(const float* __restrict__ x
       for (int nt = 0; nt < 4; ++nt) a1[mt][nt] = a2[mt][nt] = (f32x4v){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt) {
-      const unsigned ts = stage_a + trow + ((nt ^ tsw) << 5);
+      const unsigned ts = tr.at(stage_a, nt);
       union { struct { u32x2v a, b; } h; f16x8 v; } bh, bl;
       bh.h.a = lds_read_tr16<0>(ts);
       bh.h.b = lds_read_tr16<512>(ts);

@@ -9,19 +9,21 @@
 // Both kernels keep the chain's form -- transposed products, wave w owns hidden rows 32w .. 32w+31 of W3^T / W2^T as
 // register fragments (the image of k_ff3_prep_bwd), one scale per point derived from the bound of its |dz3| -- and its
 // tile order (tile = workgroup, workgroup + grid, ..), and they sum the small gradients in the chain's order, so dz3,
-// du2, du1 and the five small gradients have the chain's bits.  Everything else is the plain style of wgrad_h2.hip:
-// loads through registers one tile ahead, waits left to the compiler, lds_barrier().
+// du2, du1 and the five small gradients have the chain's bits: both call the functions of ff3_bwd.h for them.  Everything
+// else is the plain style of wgrad_h2.hip: loads through registers one tile ahead, waits left to the compiler,
+// lds_barrier().
 //
-// k_ffs_layer1 then hands du1 to the first layer's consumer of wgrad_h2.hip through LDS: each wave writes its 32
-// channels of the tile as half a [hi | lo][32 points][64 channels] panel (stage_off layout) under a running exponent of
-// its own (the maximum so far, as k_wgrad_h2 keeps per panel), x is staged the same way under one running exponent the
-// eight waves agree on, and the consumer is k_wgrad_h2<4, 1, 4, 2, 4, 2, false, true>'s: gW1 += du1^T . x by transposing
+// k_ffs_layer1 then hands du1 to the first layer's weight-gradient consumer through LDS, on the pieces of wgrad_panel.h
+// that k_wgrad_h2 is built from: each wave writes its 32 channels of the tile as half a [hi | lo][32 points][64 channels]
+// panel under a running exponent of its own, x is staged the same way under one running exponent the eight waves agree
+// on, and the consumer has the wave tiling of k_wgrad_h2<4, 1, 4, 2, 4, 2, false, true>: gW1 += du1^T . x by transposing
 // reads, gx = du1 . W1 against ready-made W1 fragments in LDS.
 #include "ff_bwd_split.h"
-#include "ff_fused.h"
+#include "ff3_bwd.h"
 #include "h2.h"
 #include "pointwise.h"
 #include "wgrad_h2.h"
+#include "wgrad_panel.h"
 
 namespace rpde {
 
@@ -51,16 +53,13 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_ffs_adjoint(const FsA A0) 
   const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, g = l >> 4, li = l & 15;
   f16x8 w3h[2][2], w3l[2][2];
   {
-    const char* base = A.wimg + (long)w * FF3_WAVE_IMG + l * 16;
+    const char* base = ff3_img_lane(A.wimg, w, l);
 #pragma unroll
     for (int f = 0; f < 4; ++f) {
-      w3h[f >> 1][f & 1] = *reinterpret_cast<const f16x8*>(base + f * 2048);
-      w3l[f >> 1][f & 1] = *reinterpret_cast<const f16x8*>(base + f * 2048 + 1024);
+      w3h[f >> 1][f & 1] = ff3_img_frag(base, f, 0);
+      w3l[f >> 1][f & 1] = ff3_img_frag(base, f, 1);
     }
-    float* vecw = reinterpret_cast<float*>(smem + FA_VEC);
-    float* accw = reinterpret_cast<float*>(smem + FA_ACC);
-    for (int i = tid; i < 128; i += 64 * FS_WAVES) vecw[i] = i < 64 ? (A.gamma ? A.gamma[i] : 1.f) : (A.beta ? A.beta[i - 64] : 0.f);
-    for (int i = tid; i < 1792; i += 64 * FS_WAVES) accw[i] = 0.f;
+    ff3_bwd_stage_vec<64 * FS_WAVES>(reinterpret_cast<float*>(smem + FA_VEC), A.gamma, A.beta, reinterpret_cast<float*>(smem + FA_ACC), 1792, tid);
   }
   const float* const vec = reinterpret_cast<const float*>(smem + FA_VEC);
   float* const acc_db2 = reinterpret_cast<float*>(smem + FA_ACC);
@@ -103,60 +102,19 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_ffs_adjoint(const FsA A0) 
     for (int i = 0; i < 4; ++i) dq[i] = d2n[i];
     if (next_tile < A.ntiles) issue(next_tile);
 
-    // ---- last-layer adjoint: dropout, LayerNorm, post-activation (k_ff3_bwd_h2's, expression for expression) ----
-    float s4[4] = {1.f, 1.f, 1.f, 1.f};
-    if (A.drop2.on()) drop_scale4(A.drop2, (uint64_t)(pt3 * 64 + feat), s4);
-    const float tz[4] = {z4.x * s4[0], z4.y * s4[1], z4.z * s4[2], z4.w * s4[3]};
-    float gy[4] = {g4.x, g4.y, g4.z, g4.w};
-    if (!live3) { gy[0] = gy[1] = gy[2] = gy[3] = 0.f; }
-    float dz[4], dzb;
-    float dgm[4] = {0.f, 0.f, 0.f, 0.f}, dbt[4] = {0.f, 0.f, 0.f, 0.f};
-    if (A.layer_norm) {
-      const float mean = row_all16<false>((tz[0] + tz[1]) + (tz[2] + tz[3])) * (1.f / 64.f);
-      const float m2 = row_all16<false>((tz[0] - mean) * (tz[0] - mean) + (tz[1] - mean) * (tz[1] - mean) +
-                                        (tz[2] - mean) * (tz[2] - mean) + (tz[3] - mean) * (tz[3] - mean));
-      const float rstd = rsqrtf(m2 * (1.f / 64.f) + A.eps);
+    // ---- last-layer adjoint: dropout, LayerNorm, post-activation ----
+    float dz[4], dzb, dgm[4], dbt[4];
+    ff3_last_adjoint(A, g4, z4, pt3, live3, feat, [&](float (&gmv)[4], float (&btv)[4]) {
       const float4 gm = *reinterpret_cast<const float4*>(vec + feat);
       const float4 bt = *reinterpret_cast<const float4*>(vec + 64 + feat);
-      const float gmv[4] = {gm.x, gm.y, gm.z, gm.w}, btv[4] = {bt.x, bt.y, bt.z, bt.w};
-      float xh[4], dxh[4], s1 = 0.f, s2 = 0.f, am = 0.f;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        xh[k] = (tz[k] - mean) * rstd;
-        float dy = gy[k];
-        if (A.post_act) dy *= dact_f(A.post_act, xh[k] * gmv[k] + btv[k]);
-        dgm[k] = dy * xh[k];
-        dbt[k] = dy;
-        dxh[k] = dy * gmv[k];
-        s1 += dxh[k];
-        s2 += dxh[k] * xh[k];
-        am = fmaxf(am, fabsf(dxh[k]));
-      }
-      const float S1 = row_all16<false>(s1) * (1.f / 64.f), S2 = row_all16<false>(s2) * (1.f / 64.f);
-      const float AM = row_all16<true>(am);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) dz[k] = rstd * (dxh[k] - S1 - xh[k] * S2) * s4[k];
-      // bound of this POINT's |dz3|: |xhat| <= sqrt(63) < 8
-      dzb = rstd * (AM + fabsf(S1) + 8.f * fabsf(S2)) * A.drop2.scale;
-    } else {
-      float am = 0.f;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) { dz[k] = gy[k] * dact_f(A.post_act, tz[k]) * s4[k]; am = fmaxf(am, fabsf(dz[k])); }
-      dzb = row_all16<true>(am);
-    }
+      gmv[0] = gm.x; gmv[1] = gm.y; gmv[2] = gm.z; gmv[3] = gm.w;
+      btv[0] = bt.x; btv[1] = bt.y; btv[2] = bt.z; btv[3] = bt.w;
+    }, dz, dzb, dgm, dbt);
     if (live3) *reinterpret_cast<float4*>(A.dz3 + off3) = make_float4(dz[0], dz[1], dz[2], dz[3]);
     // bias / gamma / beta gradients: sum over the wave's four points, one writer per (wave, feature)
     {
       float b[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        b[k] = live3 ? dz[k] : 0.f;
-        b[k] += lane_xor16(b[k]); b[k] += lane_xor32(b[k]);
-        if (A.layer_norm) {
-          dgm[k] += lane_xor16(dgm[k]); dgm[k] += lane_xor32(dgm[k]);
-          dbt[k] += lane_xor16(dbt[k]); dbt[k] += lane_xor32(dbt[k]);
-        }
-      }
+      ff3_rows_sum(live3, A.layer_norm, dz, b, dgm, dbt);
       if (q3 == 0) {
         float4* a3 = reinterpret_cast<float4*>(acc_db3 + w * 64 + feat);
         float4 v3 = *a3;
@@ -173,15 +131,11 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_ffs_adjoint(const FsA A0) 
         }
       }
     }
-    // dz3 -> B fragments, one scale per point (its bound); the bank-spreading unit permutation of k_ff3_bwd_h2
+    // dz3 -> B fragments, one scale per point (its bound), in the layout of ff3_dz_off
     {
-      float sdz, sdzi;
-      h2_scale(dzb, 0, sdz, sdzi);
       uint2 hi, lo;
-      h2_split4(dz[0] * sdz, dz[1] * sdz, dz[2] * sdz, dz[3] * sdz, hi, lo);
-      const int ksz = li >> 3, cz = li & 3;
-      char* dst = smem + FA_DZBUF + par * 8192 + (((ptl >> 4) * 2 + ksz) * 2) * 1024 + (cz * 16 + ((ptl & 15) ^ cz ^ (4 * ksz))) * 16 +
-                  ((li >> 2) & 1) * 8;
+      ff3_dz_split(dz, dzb, hi, lo);
+      char* dst = smem + FA_DZBUF + par * 8192 + ff3_dz_off(ptl, li);
       *reinterpret_cast<uint2*>(dst) = hi;
       *reinterpret_cast<uint2*>(dst + 1024) = lo;
       if (li == 0) {
@@ -197,56 +151,28 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_ffs_adjoint(const FsA A0) 
     float bsum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int blk = 0; blk < 2; ++blk) {
-      const int zu = (l & 48) | ((l & 15) ^ (l >> 4));             // this lane's unit in the ks = 0 pieces; ks = 1: ^ 4
-      const char* zb = smem + FA_DZBUF + par * 8192 + (blk * 2) * 2048;
-      const f16x8 zh0 = *reinterpret_cast<const f16x8*>(zb + zu * 16), zl0 = *reinterpret_cast<const f16x8*>(zb + 1024 + zu * 16);
-      const f16x8 zh1 = *reinterpret_cast<const f16x8*>(zb + 2048 + (zu ^ 4) * 16), zl1 = *reinterpret_cast<const f16x8*>(zb + 3072 + (zu ^ 4) * 16);
+      f16x8 zh0, zl0, zh1, zl1;
+      ff3_dz_frags(smem + FA_DZBUF + par * 8192, blk, l, zh0, zl0, zh1, zl1);
       const long pt = p0 + 16 * blk + li;
-      float sz, inv_a;
-      h2_scale(info[par * 32 + blk * 16 + li], 0, sz, inv_a);
-      inv_a *= winv3;
+      const float inv_a = ff3_inv_dz3(info[par * 32 + blk * 16 + li], winv3);
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         f32x4v acc = {0.f, 0.f, 0.f, 0.f};
         acc = h2_mfma32(w3h[t][0], w3l[t][0], zh0, zl0, acc);
         acc = h2_mfma32(w3h[t][1], w3l[t][1], zh1, zl1, acc);
         const int hid = 16 * (2 * w + t) + 4 * g;
-        const float4 d = dq[blk * 2 + t];
-        float u[4] = {acc[0] * inv_a * d.x, acc[1] * inv_a * d.y, acc[2] * inv_a * d.z, acc[3] * inv_a * d.w};
-        // (the sum below adds the ROUNDED products, as k_ff3_bwd_h2's does: left alone, the compiler folds the last
-        //  multiplication into the addition here and db2 comes out with other bits than the chain's)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) pin(u[r]);
-        if (pt < A.P) {
-          *reinterpret_cast<float4*>(A.du2 + pt * 256 + hid) = make_float4(u[0], u[1], u[2], u[3]);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) bsum[4 * t + r] += u[r];
-        }
+        float u[4];
+        ff3_du_tile<false>(acc, inv_a, dq[blk * 2 + t], pt < A.P, A.du2 + pt * 256 + hid, u, bsum + 4 * t);
       }
     }
+    ff3_bias_rows(bsum);
+    if (li == 15)
 #pragma unroll
-    for (int i = 0; i < 8; ++i) bsum[i] = row_sum15(bsum[i]);
-    if (li == 15) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) acc_db2[16 * (2 * w + (i >> 2)) + 4 * g + (i & 3)] += bsum[i];
-    }
+      for (int i = 0; i < 8; ++i) acc_db2[ff3_bias_row(w, g, i)] += bsum[i];
   }
   // ---- per-workgroup sums out: db2 | db3 | dgamma | dbeta of FF3_PART (db1 comes from k_ffs_layer1) ----
   lds_barrier();
-  {
-    float* part = A.part + (long)blockIdx.x * FF3_PART;
-    for (int i = 256 + tid; i < FF3_PART; i += 64 * FS_WAVES) {
-      float v;
-      if (i < 512) v = acc_db2[i - 256];
-      else {                                                         // the eight waves' sums, in order
-        const float* a8 = acc_db3 + ((i - 512) >> 6) * 512 + ((i - 512) & 63);
-        v = 0.f;
-#pragma unroll
-        for (int ww = 0; ww < FS_WAVES; ++ww) v += a8[ww * 64];
-      }
-      part[i] = v;
-    }
-  }
+  ff3_part_out<256, FF3_PART, 64 * FS_WAVES>(A.part + (long)blockIdx.x * FF3_PART, acc_db2, acc_db3, tid);
 }
 
 // ====================================================================================================================
@@ -257,7 +183,7 @@ struct FsB {
   long P; float dmax; int ntiles;
 };
 
-constexpr int FL_PANEL = 8192;                     // [hi | lo][32 points][64 channels] f16
+constexpr int FL_PANEL = WG_PANEL;                 // [hi | lo][32 points][64 channels] f16
 constexpr int FL_DUBUF = 0;                        // [2 blk][8 kappa][hi|lo][1 KB]: du2 as B fragments           = 32 KB
 constexpr int FL_PAN = FL_DUBUF + 32768;           // four du1 panels                                              = 32 KB
 constexpr int FL_X = FL_PAN + 4 * FL_PANEL;        // the x panel                                                  =  8 KB
@@ -285,50 +211,18 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_ffs_layer1(const FsB A) {
   f16x8 w2h[2][8], w2l[2][FL_PARKED];
   char* const parked = smem + FL_W2L + w * 2048 + l * 16;
   {
-    const char* base = A.wimg + (long)w * FF3_WAVE_IMG + l * 16;
+    const char* base = ff3_img_lane(A.wimg, w, l);
 #pragma unroll
     for (int f = 0; f < 16; ++f) {
-      w2h[f >> 3][f & 7] = *reinterpret_cast<const f16x8*>(base + (4 + f) * 2048);
-      const f16x8 lo = *reinterpret_cast<const f16x8*>(base + (4 + f) * 2048 + 1024);
+      w2h[f >> 3][f & 7] = ff3_img_frag(base, 4 + f, 0);
+      const f16x8 lo = ff3_img_frag(base, 4 + f, 1);
       if ((f & 7) < FL_PARKED) w2l[f >> 3][f & 7] = lo;
       else *reinterpret_cast<f16x8*>(parked + (f >> 3) * 1024) = lo;
     }
   }
   if (tid < 256) acc_db1[tid] = 0.f;
   char* const wfrag = smem + FL_W1;
-  float w_inv = 1.f;
-  {
-    constexpr int NF = 8 * 4 * 64 / (64 * FS_WAVES);          // (k-step, n-tile, lane) triples per thread
-    float wv[NF][8];
-    float m = 0.f;
-#pragma unroll
-    for (int r = 0; r < NF; ++r) {
-      const int c = tid + r * 64 * FS_WAVES, fl = c & 63, nt = (c >> 6) & 3, ks = c >> 8;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        wv[r][j] = A.w1[(long)(32 * ks + 8 * (fl >> 4) + j) * 64 + 16 * nt + (fl & 15)];
-        m = fmaxf(m, fabsf(wv[r][j]));
-      }
-    }
-    m = wave_max(m);
-    if (l == 0) wmax[w] = m;
-    __syncthreads();
-    m = 0.f;
-#pragma unroll
-    for (int i = 0; i < FS_WAVES; ++i) m = fmaxf(m, wmax[i]);
-    float w_scale;
-    h2_scale(m, 0, w_scale, w_inv);
-#pragma unroll
-    for (int r = 0; r < NF; ++r) {
-      const int c = tid + r * 64 * FS_WAVES, fl = c & 63, nt = (c >> 6) & 3, ks = c >> 8;
-      uint2 h0, l0, h1, l1;
-      h2_split4(wv[r][0] * w_scale, wv[r][1] * w_scale, wv[r][2] * w_scale, wv[r][3] * w_scale, h0, l0);
-      h2_split4(wv[r][4] * w_scale, wv[r][5] * w_scale, wv[r][6] * w_scale, wv[r][7] * w_scale, h1, l1);
-      char* d = wfrag + (ks * 4 + nt) * 2048 + fl * 16;
-      *reinterpret_cast<uint4*>(d) = make_uint4(h0.x, h0.y, h1.x, h1.y);
-      *reinterpret_cast<uint4*>(d + 1024) = make_uint4(l0.x, l0.y, l1.x, l1.y);
-    }
-  }
+  const float w_inv = panel_stage_w<8, 64 * FS_WAVES>(A.w1, 64, wfrag, wmax, tid);
   const float winv2 = A.consts[1], c3t = A.consts[3];
 
   // ---- this thread's loads of a tile: du2 and d1 in accumulator layout (point 16 blk + li, rows 16 (2 w + t) + 4 g ..),
@@ -377,9 +271,9 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_ffs_layer1(const FsB A) {
     return (long)tile * 32 + xrow < A.P ? xr : make_float4(0.f, 0.f, 0.f, 0.f);
   };
 
-  // ---- consumer role (k_wgrad_h2<4, 1, 4, 2, 4, 2, false, true>): du1 panel wm against x channels 32 wn .. ----
+  // ---- consumer role (the wave tiling of k_wgrad_h2<4, 1, 4, 2, 4, 2, false, true>, on the pieces of wgrad_panel.h):
+  // du1 panel wm against x channels 32 wn .. ----
   const int wm = w >> 1, wn = w & 1;
-  typedef s16x4v __attribute__((address_space(3))) * lds_tr;
   f32x4v gw[4][2];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
@@ -395,9 +289,8 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_ffs_layer1(const FsB A) {
   auto stage_du2 = [&]() {
 #pragma unroll
     for (int blk = 0; blk < 2; ++blk) {
-      float s_du2, ai;
-      h2_scale(c3t * bzr[blk] * A.dmax, 0, s_du2, ai);
-      inv_b[blk] = ai * winv2;
+      float s_du2;
+      ff3_scale_du2(bzr[blk], c3t, A.dmax, winv2, s_du2, inv_b[blk]);
       const float4 a = du2r[blk * 2], b = du2r[blk * 2 + 1];
       const float hv[8] = {a.x * s_du2, a.y * s_du2, a.z * s_du2, a.w * s_du2, b.x * s_du2, b.y * s_du2, b.z * s_du2, b.w * s_du2};
       h2_put_frag(smem + FL_DUBUF + ((blk * 8 + w) * 2) * 1024 + l * 16, hv);
@@ -456,6 +349,7 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_ffs_layer1(const FsB A) {
         const bool live = p0 + 16 * blk + li < A.P;
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
+          // (ff3_du_tile<true> written out, plus the zeroing: through the call the kernel takes 256 registers and scratch)
           const float4 d4 = d1r[blk * 2 + t];
           const float d[4] = {d4.x, d4.y, d4.z, d4.w};
           float* v = u[blk * 2 + t];
@@ -463,8 +357,6 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_ffs_layer1(const FsB A) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) { s[r] = acc[blk][t][r] * inv_b[blk]; v[r] = s[r] * d[r]; }
           if (live) {
-            // (db1 with the chain's bits: there the compiler folds the last multiplication into this addition, the
-            //  opposite of what it does for db2 -- stated here, not left to it)
 #pragma unroll
             for (int r = 0; r < 4; ++r) bsum[4 * t + r] = __builtin_fmaf(s[r], d[r], bsum[4 * t + r]);
           } else {                                // a point past the end: its column of the products is not a gradient
@@ -476,32 +368,23 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_ffs_layer1(const FsB A) {
     // (d1's registers are free from here, but the next tile's loads start only behind the consumer: in flight across it
     //  they are the 16 registers its gx products need to read a half panel ahead -- 1572 -> 1532 us with both)
     FLSTAMP(2);
+    ff3_bias_rows(bsum);
+    if (li == 15)
 #pragma unroll
-    for (int i = 0; i < 8; ++i) bsum[i] = row_sum15(bsum[i]);
-    if (li == 15) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) acc_db1[16 * (2 * w + (i >> 2)) + 4 * g + (i & 3)] += bsum[i];
-    }
+      for (int i = 0; i < 8; ++i) acc_db1[ff3_bias_row(w, g, i)] += bsum[i];
     // ---- du1 -> this wave's half of panel w / 2 (channels 32 (w & 1) .. of it) under the wave's running exponent ----
     {
       float m = 0.f;
 #pragma unroll
       for (int i = 0; i < 4; ++i) m = fmaxf(fmaxf(m, fmaxf(fabsf(u[i][0]), fabsf(u[i][1]))), fmaxf(fabsf(u[i][2]), fabsf(u[i][3])));
-      m = wave_max(m);
-      e_run = max(e_run, (int)(__float_as_uint(m) >> 23) & 0xff);
-      e_run = min(e_run, 254);
-      const float scale = __uint_as_float((unsigned)(268 - e_run) << 23);          // running maximum -> [2^14, 2^15)
+      const float scale = panel_run_scale(e_run, wave_max(m));
       char* const dst = smem + FL_PAN + (w >> 1) * FL_PANEL;
 #pragma unroll
       for (int blk = 0; blk < 2; ++blk)
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
           const float* v = u[blk * 2 + t];
-          uint2 hi, lo;
-          h2_split4(v[0] * scale, v[1] * scale, v[2] * scale, v[3] * scale, hi, lo);
-          const int off = stage_off(16 * blk + li, (w & 1) * 8 + 4 * t + g);
-          *reinterpret_cast<uint2*>(dst + off) = hi;
-          *reinterpret_cast<uint2*>(dst + 4096 + off) = lo;
+          panel_put4(dst, 16 * blk + li, (w & 1) * 8 + 4 * t + g, v[0], v[1], v[2], v[3], scale);
         }
       if (l == 0) einfo[w] = e_run;
     }
@@ -510,15 +393,9 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_ffs_layer1(const FsB A) {
       float m = 0.f;
 #pragma unroll
       for (int i = 0; i < FS_WAVES; ++i) m = fmaxf(m, xmax[i]);
-      e_x = max(e_x, (int)(__float_as_uint(m) >> 23) & 0xff);
-      e_x = min(e_x, 254);
-      const float scale = __uint_as_float((unsigned)(268 - e_x) << 23);
-      uint2 hi, lo;
+      const float scale = panel_run_scale(e_x, m);
       const float4 xv = x_of(tile);
-      h2_split4(xv.x * scale, xv.y * scale, xv.z * scale, xv.w * scale, hi, lo);
-      const int off = stage_off(xrow, xc);
-      *reinterpret_cast<uint2*>(smem + FL_X + off) = hi;
-      *reinterpret_cast<uint2*>(smem + FL_X + 4096 + off) = lo;
+      panel_put4(smem + FL_X, xrow, xc, xv.x, xv.y, xv.z, xv.w, scale);
     }
     load_x(next_tile);
     FLSTAMP(3);
@@ -547,38 +424,24 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_ffs_layer1(const FsB A) {
     const int gc = lc >> 4, lic = lc & 15;
     // ---- gW1 += du1^T . x ----
     {
-      const int q = lic >> 2, pp = lic & 3;
-      const int tsw = ((q >> 1) & 1) | ((gc & 1) << 1);
-      const int trow = (8 * gc + q) * 128 + pp * 8;
-      auto frag = [&](const char* panel, int tile, f16x8& hi, f16x8& lo) {
-        const char* t = panel + trow + ((tile ^ tsw) << 5);
-        union { struct { s16x4v a, b; } h; f16x8 v; } uh, ul;
-        uh.h.a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(t));
-        uh.h.b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(t + 512));
-        ul.h.a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(t + 4096));
-        ul.h.b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(t + 4096 + 512));
-        hi = uh.v; lo = ul.v;
-      };
+      const StageTr tr(gc, lic);
       const int eb = __builtin_amdgcn_readfirstlane(e_x);
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
-        const int ea = __builtin_amdgcn_readfirstlane(einfo[2 * wm + k]);
-        if (ea + eb != ea_used[k] + eb_used) {                               // rare: a new running maximum
-          const int d = (ea_used[k] + eb_used) - (ea + eb);                  // < 0
-          const float f = d > -126 ? __uint_as_float((unsigned)(127 + d) << 23) : 0.f;
+        float f;
+        if (panel_exp_moved(ea_used[k], eb_used, __builtin_amdgcn_readfirstlane(einfo[2 * wm + k]), eb, f)) {
 #pragma unroll
           for (int j = 0; j < 2; ++j) { gw[2 * k][j] *= f; gw[2 * k + 1][j] *= f; }
         }
-        ea_used[k] = ea;
       }
       eb_used = eb;
       f16x8 bh[2], bl[2];
 #pragma unroll
-      for (int j = 0; j < 2; ++j) frag(smem + FL_X, 2 * wn + j, bh[j], bl[j]);
+      for (int j = 0; j < 2; ++j) panel_frag_tr(smem + FL_X, tr, 2 * wn + j, bh[j], bl[j]);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         f16x8 ah, al;
-        frag(smem + FL_PAN + wm * FL_PANEL, i, ah, al);
+        panel_frag_tr(smem + FL_PAN + wm * FL_PANEL, tr, i, ah, al);
 #pragma unroll
         for (int j = 0; j < 2; ++j) gw[i][j] = h2_mfma32(ah, al, bh[j], bl[j], gw[i][j]);
       }
@@ -603,7 +466,7 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_ffs_layer1(const FsB A) {
         if (hp + 1 < 8) frags(hp + 1);
         const f32x4v part = h2_mfma32(ah[hp & 1], al[hp & 1], bh[hp & 1], bl[hp & 1], (f32x4v){0.f, 0.f, 0.f, 0.f});
         const int ek = __builtin_amdgcn_readfirstlane(einfo[hp]);
-        const float fk = __uint_as_float((unsigned)(ek - 14) << 23) * w_inv;
+        const float fk = panel_exp_factor(ek) * w_inv;
         tot += part * fk;
       }
       // lane (g, li) holds points 4 g + r of channel li: a 4 x 4 transpose inside every quad gives one 16-byte store
@@ -621,6 +484,7 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_ffs_layer1(const FsB A) {
   }
 
   // ---- this workgroup's slab [256][64] of gW1 and its db1 ----
+  // (written out as in k_wgrad_h2, see there; the factors are panel_exp_factor's)
   const float fb = __uint_as_float((unsigned)(eb_used - 14) << 23);
   float* __restrict__ out = A.slabs + (long)blockIdx.x * 256 * 64;
   const unsigned o0 = (unsigned)((wm * 64 + 4 * g) * 64 + wn * 32 + li);
@@ -633,7 +497,7 @@ __global__ __launch_bounds__(64 * FS_WAVES, 2) void k_ffs_layer1(const FsB A) {
       for (int r = 0; r < 4; ++r) out[o0 + (unsigned)((16 * i + r) * 64 + 16 * j)] = gw[i][j][r] * fa * fb;
   }
   lds_barrier();
-  if (tid < 256) A.part[(long)blockIdx.x * FF3_PART + tid] = acc_db1[tid];
+  ff3_part_out<0, 256, 64 * FS_WAVES>(A.part + (long)blockIdx.x * FF3_PART, acc_db1, nullptr, tid);
 }
 
 // --------------------------------------------------------------------------------------------------------------------

@@ -24,6 +24,7 @@
 // two-piece format, nothing else.
 #include "ff_fused.h"
 #include "cw.h"
+#include "ff3_bwd.h"
 #include "h2.h"
 #include "pointwise.h"
 
@@ -543,7 +544,6 @@ __global__ __launch_bounds__(1024) void k_ff3_prep_bwd(const float* __restrict__
   }
 }
 
-constexpr int FFB_PART = 704;          // per workgroup: db1[256] db2[256] db3[64] dgamma[64] dbeta[64]
 struct FF3B {
   const float* g; const float* z3; const float* d1; const float* d2;
   float* dz3; float* du2; float* du1; float* dx;
@@ -577,30 +577,24 @@ __global__ __launch_bounds__(64 * FF_WAVES, 2) void k_ff3_bwd_h2(const FF3B A0) 
   const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, g = l >> 4, li = l & 15;
   f16x8 w3h[2][2], w2h[2][8], w2l[2][8];
   {
-    const char* base = A.wimg + (long)w * FF_FRAGS * 2048 + l * 16;
+    const char* base = ff3_img_lane(A.wimg, w, l);
 #pragma unroll
     for (int f = 0; f < 4; ++f) {
-      w3h[f >> 1][f & 1] = *reinterpret_cast<const f16x8*>(base + f * 2048);
-      *reinterpret_cast<uint4*>(smem + FB_W3L + (w * 4 + f) * 1024 + l * 16) = *reinterpret_cast<const uint4*>(base + f * 2048 + 1024);
+      w3h[f >> 1][f & 1] = ff3_img_frag(base, f, 0);
+      *reinterpret_cast<f16x8*>(smem + FB_W3L + (w * 4 + f) * 1024 + l * 16) = ff3_img_frag(base, f, 1);
     }
 #pragma unroll
     for (int f = 0; f < 16; ++f) {
-      w2h[f >> 3][f & 7] = *reinterpret_cast<const f16x8*>(base + (4 + f) * 2048);
-      w2l[f >> 3][f & 7] = *reinterpret_cast<const f16x8*>(base + (4 + f) * 2048 + 1024);
+      w2h[f >> 3][f & 7] = ff3_img_frag(base, 4 + f, 0);
+      w2l[f >> 3][f & 7] = ff3_img_frag(base, 4 + f, 1);
     }
-    float* vecw = reinterpret_cast<float*>(smem + FB_VEC);
-    float* accw = reinterpret_cast<float*>(smem + FB_ACC);
-    for (int i = tid; i < 128; i += 64 * FF_WAVES) vecw[i] = i < 64 ? (A.gamma ? A.gamma[i] : 1.f) : (A.beta ? A.beta[i - 64] : 0.f);
-    for (int i = tid; i < 2048; i += 64 * FF_WAVES) accw[i] = 0.f;
+    ff3_bwd_stage_vec<64 * FF_WAVES>(reinterpret_cast<float*>(smem + FB_VEC), A.gamma, A.beta, reinterpret_cast<float*>(smem + FB_ACC), 2048, tid);
   }
-  const float* const vec = reinterpret_cast<const float*>(smem + FB_VEC);
   float* const acc_db1 = reinterpret_cast<float*>(smem + FB_ACC);
   float* const acc_db2 = acc_db1 + 256;
-  float* const acc_db3 = acc_db1 + 512;        // [8 wave][64]
-  float* const acc_dg = acc_db1 + 1024;        // [8 wave][64]
-  float* const acc_dbt = acc_db1 + 1536;       // [8 wave][64]
+  float* const acc_db3 = acc_db1 + 512;        // [8 wave][64]; dgamma and dbeta, [8 wave][64] each, behind it
   float* const info = reinterpret_cast<float*>(smem + FB_INFO);
-  const float winv1 = A.consts[0], winv2 = A.consts[1], winv3 = A.consts[2], c3t = A.consts[3], c2t = A.consts[4];
+  const float winv2 = A.consts[1], winv3 = A.consts[2], c3t = A.consts[3];
   const unsigned lds0 = lds_addr(smem);
   // role in the last-layer adjoint: one POINT per 16-lane row (point 4 w + q of the tile), lane li takes features
   // 4 li .. 4 li + 3 -- the LayerNorm statistics are sums over a row (DPP), no exchange between waves
@@ -654,61 +648,20 @@ __global__ __launch_bounds__(64 * FF_WAVES, 2) void k_ff3_bwd_h2(const FF3B A0) 
     // the eight DMA pieces of the prologue
     asm volatile("s_waitcnt vmcnt(8) ; landed %0 %1" : "+v"(g4n), "+v"(z4n)::"memory");
     const f32x4v g4 = g4n, z4 = z4n;
-    float s4[4] = {1.f, 1.f, 1.f, 1.f};
-    if (A.drop2.on()) drop_scale4(A.drop2, (uint64_t)(pt3 * 64 + feat), s4);
-    const float tz[4] = {z4.x * s4[0], z4.y * s4[1], z4.z * s4[2], z4.w * s4[3]};
-    float gy[4] = {g4.x, g4.y, g4.z, g4.w};
-    if (!live3) { gy[0] = gy[1] = gy[2] = gy[3] = 0.f; }
-    float dz[4], dzb;
-    float dgm[4] = {0.f, 0.f, 0.f, 0.f}, dbt[4] = {0.f, 0.f, 0.f, 0.f};
-    if (A.layer_norm) {
-      const float mean = row_all16<false>((tz[0] + tz[1]) + (tz[2] + tz[3])) * (1.f / 64.f);
-      const float m2 = row_all16<false>((tz[0] - mean) * (tz[0] - mean) + (tz[1] - mean) * (tz[1] - mean) +
-                                        (tz[2] - mean) * (tz[2] - mean) + (tz[3] - mean) * (tz[3] - mean));
-      const float rstd = rsqrtf(m2 * (1.f / 64.f) + A.eps);
+    float dz[4], dzb, dgm[4], dbt[4];
+    ff3_last_adjoint(A, g4, z4, pt3, live3, feat, [&](float (&gmv)[4], float (&btv)[4]) {
       f32x4v gm = lds_read_b128(lds0 + FB_VEC + feat * 4);
       f32x4v bt = lds_read_b128(lds0 + FB_VEC + 256 + feat * 4);
       lds_wait(gm, bt);
-      const float gmv[4] = {gm.x, gm.y, gm.z, gm.w}, btv[4] = {bt.x, bt.y, bt.z, bt.w};
-      float xh[4], dxh[4], s1 = 0.f, s2 = 0.f, am = 0.f;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        xh[k] = (tz[k] - mean) * rstd;
-        float dy = gy[k];
-        if (A.post_act) dy *= dact_f(A.post_act, xh[k] * gmv[k] + btv[k]);
-        dgm[k] = dy * xh[k];
-        dbt[k] = dy;
-        dxh[k] = dy * gmv[k];
-        s1 += dxh[k];
-        s2 += dxh[k] * xh[k];
-        am = fmaxf(am, fabsf(dxh[k]));
-      }
-      const float S1 = row_all16<false>(s1) * (1.f / 64.f), S2 = row_all16<false>(s2) * (1.f / 64.f);
-      const float AM = row_all16<true>(am);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) dz[k] = rstd * (dxh[k] - S1 - xh[k] * S2) * s4[k];
-      // bound of this POINT's |dz3|: |xhat| <= sqrt(63) < 8
-      dzb = rstd * (AM + fabsf(S1) + 8.f * fabsf(S2)) * A.drop2.scale;
-    } else {
-      float am = 0.f;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) { dz[k] = gy[k] * dact_f(A.post_act, tz[k]) * s4[k]; am = fmaxf(am, fabsf(dz[k])); }
-      dzb = row_all16<true>(am);
-    }
+      for (int k = 0; k < 4; ++k) { gmv[k] = gm[k]; btv[k] = bt[k]; }
+    }, dz, dzb, dgm, dbt);
     if (live3) *reinterpret_cast<float4*>(A.dz3 + off3) = make_float4(dz[0], dz[1], dz[2], dz[3]);
     // bias / gamma / beta gradients: sum over the wave's four points (rows), one writer per (wave, feature); the
     // eight waves' sums are combined in fixed order at the end
     {
       float b[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        b[k] = live3 ? dz[k] : 0.f;
-        b[k] += lane_xor16(b[k]); b[k] += lane_xor32(b[k]);
-        if (A.layer_norm) {
-          dgm[k] += lane_xor16(dgm[k]); dgm[k] += lane_xor32(dgm[k]);
-          dbt[k] += lane_xor16(dbt[k]); dbt[k] += lane_xor32(dbt[k]);
-        }
-      }
+      ff3_rows_sum(live3, A.layer_norm, dz, b, dgm, dbt);
       if (q3 == 0) {
         // (asm: an ordinary access here is preceded by vmcnt(0) -- the compiler cannot tell these addresses from the
         //  DMA's landing areas -- i.e. by a wait for the d1 pieces requested a moment ago)
@@ -726,41 +679,17 @@ __global__ __launch_bounds__(64 * FF_WAVES, 2) void k_ff3_bwd_h2(const FF3B A0) 
         }
       }
     }
-    // dz3 -> B fragments (one scale per point, its bound dzb): features 4 li .. 4 li + 3 of point ptl are reduction slots
-    // 4 (li >> 2 & 1) .. + 3 of lane group li & 3 in the fragment (block ptl >> 4, half ks = li >> 3), point column ptl & 15
+    // dz3 -> B fragments, one scale per point (its bound dzb), in the layout of ff3_dz_off
     {
-      float sdz, sdzi;
-      h2_scale(dzb, 0, sdz, sdzi);
       uint2 hi, lo;
-      h2_split4(dz[0] * sdz, dz[1] * sdz, dz[2] * sdz, dz[3] * sdz, hi, lo);
-      // (the 16-byte unit of fragment lane (c, p) = (li & 3, ptl & 15) sits at unit 16 c + (p ^ c ^ 4 ks) of its 1 KB piece:
-      //  written plainly at 16 c + p, the sixteen lanes of a row -- same p, four c, two ks, 256 / 2048 bytes apart -- hit
-      //  two banks (8-way conflicts: 29.4 M conflict cycles per launch in round 3's counters); permuted inside each
-      //  256-byte row they cover all 32.  The reader un-permutes its address; its own banking only sees a row's units
-      //  in another order.)
-      const int ksz = li >> 3, cz = li & 3;
-      const unsigned dst = lds0 + FB_DZBUF + (((ptl >> 4) * 2 + ksz) * 2) * 1024 + (cz * 16 + ((ptl & 15) ^ cz ^ (4 * ksz))) * 16 +
-                           ((li >> 2) & 1) * 8;
+      ff3_dz_split(dz, dzb, hi, lo);
+      const unsigned dst = lds0 + FB_DZBUF + ff3_dz_off(ptl, li);
       lds_write_b64(dst, hi);
       lds_write_b64(dst + 1024, lo);
       if (li == 0) lds_write_b32(lds0 + FB_INFO + ptl * 4, dzb);
     }
     lds_barrier();                                                                    // C: dz3 fragments + bounds in LDS
     FBSTAMP(3);
-
-    // per point: scale of dz3 (its bound), of du2 and du1 (bounds derived from it); recomputed at each use
-    auto bscales = [&](int blk, float& inv_a, float& s_du2, float& inv_b, float& s_du1, float& inv_c) {
-      const float bz = info[blk * 16 + li];
-      float a, ai;
-      h2_scale(bz, 0, a, ai);
-      inv_a = ai * winv3;
-      const float b2 = c3t * bz * A.dmax;
-      h2_scale(b2, 0, a, ai);
-      s_du2 = a; inv_b = ai * winv2;
-      const float b1 = c2t * b2 * A.dmax;
-      h2_scale(b1, 0, a, ai);
-      s_du1 = a; inv_c = ai * winv1;
-    };
 
     // ---- du2 = (W3^T dz3) * d2: this wave's 32 hidden rows ----
     // the d2 pieces of this tile were requested a tile ago.  vmcnt(N) = all but the N youngest operations are done;
@@ -775,13 +704,12 @@ __global__ __launch_bounds__(64 * FF_WAVES, 2) void k_ff3_bwd_h2(const FF3B A0) 
       dq[0] = lds_read_b128(lds0 + FB_D2 + (w * 4 + blk * 2) * 1024 + l * 16);
       dq[1] = lds_read_b128(lds0 + FB_D2 + (w * 4 + blk * 2 + 1) * 1024 + l * 16);
       lds_wait(dq[0], dq[1]);
-      const int zu = (l & 48) | ((l & 15) ^ (l >> 4));             // this lane's unit in the ks = 0 pieces; ks = 1: ^ 4
-      const char* zb = smem + FB_DZBUF + (blk * 2) * 2048;
-      const f16x8 zh0 = *reinterpret_cast<const f16x8*>(zb + zu * 16), zl0 = *reinterpret_cast<const f16x8*>(zb + 1024 + zu * 16);
-      const f16x8 zh1 = *reinterpret_cast<const f16x8*>(zb + 2048 + (zu ^ 4) * 16), zl1 = *reinterpret_cast<const f16x8*>(zb + 3072 + (zu ^ 4) * 16);
+      f16x8 zh0, zl0, zh1, zl1;
+      ff3_dz_frags(smem + FB_DZBUF, blk, l, zh0, zl0, zh1, zl1);
       const long pt = p0 + 16 * blk + li;
-      float inv_a, s_du2, q0, q1, q2;
-      bscales(blk, inv_a, s_du2, q0, q1, q2);
+      const float bz = info[blk * 16 + li], inv_a = ff3_inv_dz3(bz, winv3);
+      float s_du2, q0;
+      ff3_scale_du2(bz, c3t, A.dmax, winv2, s_du2, q0);
       float hv[8];
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
@@ -793,12 +721,8 @@ __global__ __launch_bounds__(64 * FF_WAVES, 2) void k_ff3_bwd_h2(const FF3B A0) 
         const int hid = 16 * (2 * w + t) + 4 * g;
         float4 d = make_float4(dq[t].x, dq[t].y, dq[t].z, dq[t].w);
         if (RECOMP) d = ff_dact4(d, A.drop1, (uint64_t)(pt * 256 + hid));
-        const float u[4] = {acc[0] * inv_a * d.x, acc[1] * inv_a * d.y, acc[2] * inv_a * d.z, acc[3] * inv_a * d.w};
-        if (pt < A.P) {
-          *reinterpret_cast<float4*>(A.du2 + pt * 256 + hid) = make_float4(u[0], u[1], u[2], u[3]);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) bsum[4 * t + r] += u[r];
-        }
+        float u[4];
+        ff3_du_tile<false>(acc, inv_a, d, pt < A.P, A.du2 + pt * 256 + hid, u, bsum + 4 * t);
 #pragma unroll
         for (int r = 0; r < 4; ++r) hv[4 * t + r] = u[r] * s_du2;
       }
@@ -814,12 +738,10 @@ __global__ __launch_bounds__(64 * FF_WAVES, 2) void k_ff3_bwd_h2(const FF3B A0) 
         lds_write_b128(dst + 1024, pl);
       }
     }
+    ff3_bias_rows(bsum);
+    if (li == 15)
 #pragma unroll
-    for (int i = 0; i < 8; ++i) bsum[i] = row_sum15(bsum[i]);
-    if (li == 15) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) acc_db2[16 * (2 * w + (i >> 2)) + 4 * g + (i & 3)] += bsum[i];
-    }
+      for (int i = 0; i < 8; ++i) acc_db2[ff3_bias_row(w, g, i)] += bsum[i];
     if (has_next) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the d2 pieces have been read: their area is free
       d_issue(A.d2, FB_D2, next_tile);
@@ -857,20 +779,15 @@ __global__ __launch_bounds__(64 * FF_WAVES, 2) void k_ff3_bwd_h2(const FF3B A0) 
         dq[1] = lds_read_b128(lds0 + FB_D1 + (w * 4 + blk * 2 + 1) * 1024 + l * 16);
         lds_wait(dq[0], dq[1]);
         const long pt = p0 + 16 * blk + li;
-        float q0, q1, inv_b, s_du1, q2;
-        bscales(blk, q0, q1, inv_b, s_du1, q2);
+        float q0, inv_b;
+        ff3_scale_du2(info[blk * 16 + li], c3t, A.dmax, winv2, q0, inv_b);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
           const int hid = 16 * (2 * w + t) + 4 * g;
           float4 d = make_float4(dq[t].x, dq[t].y, dq[t].z, dq[t].w);
           if (RECOMP) d = ff_dact4(d, A.drop0, (uint64_t)(pt * 256 + hid));
-          const float u[4] = {acc[blk][t][0] * inv_b * d.x, acc[blk][t][1] * inv_b * d.y,
-                              acc[blk][t][2] * inv_b * d.z, acc[blk][t][3] * inv_b * d.w};
-          if (pt < A.P) {
-            *reinterpret_cast<float4*>(A.du1 + pt * 256 + hid) = make_float4(u[0], u[1], u[2], u[3]);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) bsum[4 * t + r] += u[r];
-          }
+          float u[4];
+          ff3_du_tile<true>(acc[blk][t], inv_b, d, pt < A.P, A.du1 + pt * 256 + hid, u, bsum + 4 * t);
         }
       }
     }
@@ -878,12 +795,10 @@ __global__ __launch_bounds__(64 * FF_WAVES, 2) void k_ff3_bwd_h2(const FF3B A0) 
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       d_issue(A.d1, FB_D1, next_tile);
     }
+    ff3_bias_rows(bsum);
+    if (li == 15)
 #pragma unroll
-    for (int i = 0; i < 8; ++i) bsum[i] = row_sum15(bsum[i]);
-    if (li == 15) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) acc_db1[16 * (2 * w + (i >> 2)) + 4 * g + (i & 3)] += bsum[i];
-    }
+      for (int i = 0; i < 8; ++i) acc_db1[ff3_bias_row(w, g, i)] += bsum[i];
     first = false;
 #ifdef RPDE_STAMPS
     ++stamp_t;
@@ -891,20 +806,7 @@ __global__ __launch_bounds__(64 * FF_WAVES, 2) void k_ff3_bwd_h2(const FF3B A0) 
   }
   // ---- per-workgroup sums out ----
   lds_barrier();
-  {
-    float* part = A.part + (long)blockIdx.x * FFB_PART;
-    for (int i = tid; i < FFB_PART; i += 64 * FF_WAVES) {
-      float v;
-      if (i < 512) v = acc_db1[i];                                   // db1, db2
-      else {                                                         // db3 | dgamma | dbeta: the eight waves' sums, in order
-        const float* a8 = acc_db3 + ((i - 512) >> 6) * 512 + ((i - 512) & 63);
-        v = 0.f;
-#pragma unroll
-        for (int ww = 0; ww < FF_WAVES; ++ww) v += a8[ww * 64];
-      }
-      part[i] = v;
-    }
-  }
+  ff3_part_out<0, FF3_PART, 64 * FF_WAVES>(A.part + (long)blockIdx.x * FF3_PART, acc_db1, acc_db3, tid);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -962,7 +864,7 @@ int ff3_fused_fwd(const rpde_ff_params* p, const float* x, const float* residual
   return RPDE_OK;
 }
 
-size_t ff3_fused_bwd_part_floats() { return (size_t)1024 * FFB_PART; }
+size_t ff3_fused_bwd_part_floats() { return (size_t)1024 * FF3_PART; }
 
 // prep + the fused kernel: dz3 [P,64], du2, du1 [P,256], dx [P,64] (may be null), part [grid][704]; returns the grid
 int ff3_fused_bwd_launch(const rpde_ff_params* p, const float* const* ds, int recompute, const float* z_last,

@@ -327,13 +327,10 @@ __global__ __launch_bounds__(256, 2) void k_mix_wgrad_h2(const MixWgP P) {
       *reinterpret_cast<uint2*>(base + 4096 + off) = lo;
     }
   };
-  // transposing-read address of this lane inside a piece (k_dft_analysis_h2's): rows 8g + q / 8g + 4 + q, chunk pp
   typedef s16x4v __attribute__((address_space(3))) * lds_tr;
-  const int q = li >> 2, pp = li & 3;
-  const int tsw = ((q >> 1) & 1) | ((g & 1) << 1);
-  const int trow = (8 * g + q) * 128 + pp * 8;
+  const StageTr tr(g, li);                      // transposing-read address of this lane inside a piece (wave.h)
   auto frag = [&](int piece, int hl, int ctile) {           // 8 lines (k = 8g + j) of channel 16 ctile + li
-    const char* t = smem + piece * 8192 + hl * 4096 + trow + ((ctile ^ tsw) << 5);
+    const char* t = tr.at(smem + piece * 8192 + hl * 4096, ctile);
     union { struct { s16x4v a, b; } h; f16x8 v; } u;
     u.h.a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(t));
     u.h.b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(t + 512));

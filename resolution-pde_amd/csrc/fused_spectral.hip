@@ -136,10 +136,7 @@ __global__ __launch_bounds__(64 * ANA_WAVES, 2) void k_dft_analysis_h2(const Ana
   const int tid = threadIdx.x, l = tid & 63, wave = tid >> 6;
   char* const stage = smem + ANA_MAXKS * MT * 2048 + wave * 8192;
   const int g = l >> 4, li = l & 15;
-  // transposing-read addresses of this lane (piece 0, channel tile 0): rows 8g+q and 8g+4+q, chunk p
-  const int q = li >> 2, pp = li & 3;
-  const int tsw = ((q >> 1) & 1) | ((g & 1) << 1);       // chunk-group XOR of those rows (same for both)
-  const int trow = (8 * g + q) * 128 + pp * 8;
+  const StageTr tr(g, li);                      // transposing-read address of this lane inside a piece (wave.h)
   typedef s16x4v __attribute__((address_space(3))) * lds_tr;
 
   // persistent workgroups: round w, w + gridDim.x, ...; every wave walks the same rounds and owns line `wave` of each
@@ -249,7 +246,7 @@ __global__ __launch_bounds__(64 * ANA_WAVES, 2) void k_dft_analysis_h2(const Ana
     FSTAMP(0, stamp_n * 5 + 2);
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt) {
-      const char* t = stage + trow + ((nt ^ tsw) << 5);
+      const char* t = tr.at(stage, nt);
       union { struct { s16x4v a, b; } h; f16x8 v; } bh, bl;
       bh.h.a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(t));
       bh.h.b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(t + 512));

@@ -121,6 +121,16 @@ __device__ __forceinline__ void pin(float& x) { asm volatile("" : "+v"(x)); }
 __device__ __forceinline__ int stage_off(int k, int c8) {
   return k * 128 + ((c8 ^ ((((k >> 1) & 1) << 2) | (((k >> 3) & 1) << 3))) << 3);
 }
+// the transposing reads' side of it: at(piece, tile) is where lane (g, li) reads its share of the 16-column tile `tile`
+// (0..3) of the staged piece at `piece` (a pointer or an LDS address) -- row 8 g + q (q = li >> 2) and, 512 bytes on, row
+// 8 g + 4 + q, 8-byte chunk li & 3 of the tile; `sw` is the chunk-group XOR of those rows (the same for both)
+struct StageTr {
+  int sw, row;
+  __device__ __forceinline__ StageTr(int g, int li)
+      : sw(((li >> 3) & 1) | ((g & 1) << 1)), row((8 * g + (li >> 2)) * 128 + (li & 3) * 8) {}
+  template <class P>
+  __device__ __forceinline__ P at(P piece, int tile) const { return piece + row + ((tile ^ sw) << 5); }
+};
 
 // reduction slot j (0..7) of lane group g -> index inside a 32-deep reduction step, for operands built from two
 // accumulator tiles (a 16 x 16 accumulator holds rows 4g..4g+3 in lane group g) or loaded as two 16-byte runs per lane;

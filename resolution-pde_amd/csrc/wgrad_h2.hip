@@ -24,14 +24,17 @@
 // are scaled by it, and a consumer wave whose panels' exponents moved rescales its accumulators once (a wave-uniform
 // branch that is taken a handful of times per launch).  No pass over the data to find a global maximum, no
 // per-step accumulator arithmetic, robust to isolated huge points.
+//
+// The panel pieces (scale, writer, transposing reader, rescale test, exponent factor, W -> B fragments) are the functions
+// of wgrad_panel.h; k_ffs_layer1 (ff_bwd_split.hip) runs the first layer's consumer on the same ones.
 #include "h2.h"
 #include "pointwise.h"
 #include "wgrad_h2.h"
+#include "wgrad_panel.h"
 
 namespace rpde {
 
 constexpr int WG_WAVES = 8;
-constexpr int WG_PANEL = 8192;                 // bytes per panel stage: [hi | lo][32 points][64 channels] f16
 constexpr int WG_BLOCKS = 256;                 // one workgroup per CU
 
 struct WgP {
@@ -94,19 +97,10 @@ __global__ __launch_bounds__(64 * WG_WAVES, 2) void k_wgrad_h2(const WgP P) {
     float m = 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) m = fmaxf(fmaxf(m, fmaxf(fabsf(buf[i].x), fabsf(buf[i].y))), fmaxf(fabsf(buf[i].z), fabsf(buf[i].w)));
-    m = wave_max(m);
-    e_run = max(e_run, (int)(__float_as_uint(m) >> 23) & 0xff);
-    e_run = min(e_run, 254);
-    const float scale = __uint_as_float((unsigned)(268 - e_run) << 23);        // running maximum -> [2^14, 2^15)
+    const float scale = panel_run_scale(e_run, wave_max(m));
     char* const dst = smem + st * STAGE + wave * WG_PANEL;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      uint2 hi, lo;
-      h2_split4(buf[i].x * scale, buf[i].y * scale, buf[i].z * scale, buf[i].w * scale, hi, lo);
-      const int off = stage_off(4 * i + g, li);
-      *reinterpret_cast<uint2*>(dst + off) = hi;
-      *reinterpret_cast<uint2*>(dst + 4096 + off) = lo;
-    }
+    for (int i = 0; i < 8; ++i) panel_put4(dst, 4 * i + g, li, buf[i].x, buf[i].y, buf[i].z, buf[i].w, scale);
     if (l == 0) einfo[st][wave] = e_run;
   };
 
@@ -114,20 +108,7 @@ __global__ __launch_bounds__(64 * WG_WAVES, 2) void k_wgrad_h2(const WgP P) {
   const int wm = wave / WN, wn = wave % WN;
   const int m_off = wm * TM * 16, n_off = wn * TN * 16;            // inside the block
   const int pa = m_off >> 6, ta0 = (m_off & 63) >> 4, pb = PA + (n_off >> 6), tb0 = (n_off & 63) >> 4;
-  // transposing-read address of this lane inside a piece: rows 8g+q (and +4), chunk pp of the tile
-  const int q = li >> 2, pp = li & 3;
-  const int tsw = ((q >> 1) & 1) | ((g & 1) << 1);
-  const int trow = (8 * g + q) * 128 + pp * 8;
-  typedef s16x4v __attribute__((address_space(3))) * lds_tr;
-  auto frag = [&](const char* panel, int tile, f16x8& hi, f16x8& lo) {
-    const char* t = panel + trow + ((tile ^ tsw) << 5);
-    union { struct { s16x4v a, b; } h; f16x8 v; } uh, ul;
-    uh.h.a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(t));
-    uh.h.b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(t + 512));
-    ul.h.a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(t + 4096));
-    ul.h.b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(t + 4096 + 512));
-    hi = uh.v; lo = ul.v;
-  };
+  const StageTr tr(g, li);                     // this lane's transposing-read address inside a piece
   f32x4v acc[TM][TN];
 #pragma unroll
   for (int i = 0; i < TM; ++i)
@@ -142,38 +123,7 @@ __global__ __launch_bounds__(64 * WG_WAVES, 2) void k_wgrad_h2(const WgP P) {
   // ---- DG: W as B fragments (k = output channel of the layer, n = input channel), one global power-of-two scale -----
   char* const wfrag = smem + 2 * STAGE;
   float w_inv = 1.f;
-  if (DG && s0 < s1) {
-    constexpr int NF = PA * 2 * 4 * 64 / (64 * WG_WAVES);     // (k-step, n-tile, lane) triples per thread
-    float wv[NF][8];
-    float m = 0.f;
-#pragma unroll
-    for (int r = 0; r < NF; ++r) {
-      const int c = tid + r * 64 * WG_WAVES, fl = c & 63, nt = (c >> 6) & 3, ks = c >> 8;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        wv[r][j] = P.w[(long)(32 * ks + 8 * (fl >> 4) + j) * P.N + 16 * nt + (fl & 15)];
-        m = fmaxf(m, fabsf(wv[r][j]));
-      }
-    }
-    m = wave_max(m);
-    if (l == 0) wmax[wave] = m;
-    __syncthreads();
-    m = 0.f;
-#pragma unroll
-    for (int i = 0; i < WG_WAVES; ++i) m = fmaxf(m, wmax[i]);
-    float w_scale;
-    h2_scale(m, 0, w_scale, w_inv);
-#pragma unroll
-    for (int r = 0; r < NF; ++r) {
-      const int c = tid + r * 64 * WG_WAVES, fl = c & 63, nt = (c >> 6) & 3, ks = c >> 8;
-      uint2 h0, l0, h1, l1;
-      h2_split4(wv[r][0] * w_scale, wv[r][1] * w_scale, wv[r][2] * w_scale, wv[r][3] * w_scale, h0, l0);
-      h2_split4(wv[r][4] * w_scale, wv[r][5] * w_scale, wv[r][6] * w_scale, wv[r][7] * w_scale, h1, l1);
-      char* d = wfrag + (ks * 4 + nt) * 2048 + fl * 16;
-      *reinterpret_cast<uint4*>(d) = make_uint4(h0.x, h0.y, h1.x, h1.y);
-      *reinterpret_cast<uint4*>(d + 1024) = make_uint4(l0.x, l0.y, l1.x, l1.y);
-    }
-  }
+  if (DG && s0 < s1) w_inv = panel_stage_w<PA * 2, 64 * WG_WAVES>(P.w, P.N, wfrag, wmax, tid);
   // this wave's output tile of gx: points 16 (wave & 1) .., input channels 16 (wave >> 1) ..
   const int dg_mt = wave & 1, dg_nt = wave >> 1;
 
@@ -197,10 +147,8 @@ __global__ __launch_bounds__(64 * WG_WAVES, 2) void k_wgrad_h2(const WgP P) {
       const int eb = __builtin_amdgcn_readfirstlane(einfo[cur][pb]);
 #pragma unroll
       for (int k = 0; k < NPA; ++k) {
-        const int ea = __builtin_amdgcn_readfirstlane(einfo[cur][pa + k]);
-        if (ea + eb != ea_used[k] + eb_used) {                               // rare: a new running maximum
-          const int d = (ea_used[k] + eb_used) - (ea + eb);                  // < 0
-          const float f = d > -126 ? __uint_as_float((unsigned)(127 + d) << 23) : 0.f;
+        float f;
+        if (panel_exp_moved(ea_used[k], eb_used, __builtin_amdgcn_readfirstlane(einfo[cur][pa + k]), eb, f)) {
 #pragma unroll
           for (int i = 0; i < TM; ++i)
             if (((ta0 + i) >> 2) == k) {
@@ -208,16 +156,15 @@ __global__ __launch_bounds__(64 * WG_WAVES, 2) void k_wgrad_h2(const WgP P) {
               for (int j = 0; j < TN; ++j) acc[i][j] *= f;
             }
         }
-        ea_used[k] = ea;
       }
       eb_used = eb;
       f16x8 bh[TN], bl[TN];                   // B fragments stay, A fragments stream: TN <= 4 in every instance
 #pragma unroll
-      for (int j = 0; j < TN; ++j) frag(stage + (pb + ((tb0 + j) >> 2)) * WG_PANEL, (tb0 + j) & 3, bh[j], bl[j]);
+      for (int j = 0; j < TN; ++j) panel_frag_tr(stage + (pb + ((tb0 + j) >> 2)) * WG_PANEL, tr, (tb0 + j) & 3, bh[j], bl[j]);
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
         f16x8 ah, al;
-        frag(stage + (pa + ((ta0 + i) >> 2)) * WG_PANEL, (ta0 + i) & 3, ah, al);
+        panel_frag_tr(stage + (pa + ((ta0 + i) >> 2)) * WG_PANEL, tr, (ta0 + i) & 3, ah, al);
 #pragma unroll
         for (int j = 0; j < TN; ++j) acc[i][j] = h2_mfma32(ah, al, bh[j], bl[j], acc[i][j]);
       }
@@ -236,7 +183,7 @@ __global__ __launch_bounds__(64 * WG_WAVES, 2) void k_wgrad_h2(const WgP P) {
             part = h2_mfma32(ah, al, bh, bl, part);
           }
           const int ek = __builtin_amdgcn_readfirstlane(einfo[cur][k]);
-          const float fk = __uint_as_float((unsigned)(ek - 14) << 23) * w_inv;
+          const float fk = panel_exp_factor(ek) * w_inv;
           tot += part * fk;
         }
         // lane (g, li) holds points 4 g + r (r = 0..3) of channel li; a 4 x 4 transpose inside every quad of lanes turns
@@ -257,6 +204,8 @@ __global__ __launch_bounds__(64 * WG_WAVES, 2) void k_wgrad_h2(const WgP P) {
   }
 
   // ---- slab [M][N] of this chunk ------------------------------------------------------------------------------------
+  // (written out here and in k_ffs_layer1, the factors being panel_exp_factor's: shared in any form, it turns one branch
+  //  of every instance around -- profiles/ff_bwd_fold_ab.txt)
   const float fb = __uint_as_float((unsigned)(eb_used - 14) << 23);
   float* __restrict__ out = P.slabs + (long)chunk * P.M * P.N + (long)(mblock * (64 * PA) + m_off) * P.N + n_off;
 #pragma unroll
