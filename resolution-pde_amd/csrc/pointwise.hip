@@ -159,10 +159,13 @@ __global__ __launch_bounds__(256) void k_colsum(const float* __restrict__ x, flo
     for (long r = r0 + tr; r < r1; r += step) acc += x[r * ld + c];
     red[t] = acc;
     __syncthreads();
-    if (tr == 0) {
-      for (int j = 1; j < step; ++j) acc += red[j * N + c];
-      slab[(long)blockIdx.x * N + c] = acc;
+    // the step row-lanes of a column fold as a fixed tree (step is a power of two): one thread adding them in turn
+    // carried a running sum through up to 255 roundings, which for N = 1 was most of the error of the whole column sum
+    for (int w = step >> 1; w >= 1; w >>= 1) {
+      if (tr < w) red[t] += red[t + w * N];
+      __syncthreads();
     }
+    if (tr == 0) slab[(long)blockIdx.x * N + c] = red[t];
   } else {
     for (int c = t; c < N; c += 256) {
       float acc = 0.f;
