@@ -44,26 +44,6 @@ struct ConvK3Wgrad {
   }
 };
 
-// gw / gb = the slices' partial sums added in slice order
-__global__ void __launch_bounds__(256)
-k_cno_conv2d_wsum(const float* __restrict__ part, float* __restrict__ gw, float* __restrict__ gb, long n_gw, long n_gb,
-                  int slices) {
-  const long e = (long)blockIdx.x * 256 + threadIdx.x;
-  if (e >= n_gw + n_gb) return;
-  float v = 0.f;
-  for (int s = 0; s < slices; ++s) v += part[s * (n_gw + n_gb) + e];
-  if (e < n_gw) gw[e] = v;
-  else if (gb) gb[e - n_gw] = v;
-}
-
-// (rpde_internal.h: wgrad_sliced.h's launcher calls it for both convolutions)
-int sum_slices(const float* part, float* gw, float* gb, long n_gw, long n_gb, int slices, hipStream_t st) {
-  hipLaunchKernelGGL(k_cno_conv2d_wsum, dim3((unsigned)((n_gw + n_gb + 255) / 256)), dim3(256), 0, st, part, gw, gb, n_gw, n_gb,
-                     slices);
-  RPDE_LAUNCH_CHECK();
-  return RPDE_OK;
-}
-
 // ---- BatchNorm pieces ---------------------------------------------------------------------------------------------
 // sums[c] = (sum a, sum b, sum a b, sum b^2) over (batch, x) of channel c of two [B, C, n] tensors, in double; one
 // workgroup per channel, fixed order.  The forward takes mean and variance of z from (z, z), the backward sum gy and

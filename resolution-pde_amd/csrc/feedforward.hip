@@ -330,15 +330,14 @@ int rpde_feedforward_bwd(const rpde_ff_params* p, const float* x, const float* c
       RPDE_TRY(fold_jobs(folds, st));
     }
     {   // per-workgroup partial sums -> the five small gradients, one launch
-      ReduceSegs sg;
-      memset(&sg, 0, sizeof(sg));
-      sg.n = FF3_PART; sg.nseg = 5;
+      FoldJobs folds;
       const int off[5] = {0, 256, 512, 576, 640}, len[5] = {hid, hid, p->dim, p->dim, p->dim};
       float* dst[5] = {grad_biases ? grad_biases[0] : nullptr, grad_biases ? grad_biases[1] : nullptr,
                        grad_biases ? grad_biases[2] : nullptr, p->layer_norm ? grad_gamma : nullptr,
                        p->layer_norm ? grad_beta : nullptr};
-      for (int k = 0; k < 5; ++k) { sg.off[k] = off[k]; sg.len[k] = len[k]; sg.dst[k] = dst[k]; }
-      RPDE_TRY(reduce_slabs_seg(part, grid, FF3_PART, sg, st));
+      for (int k = 0; k < 5; ++k)
+        if (dst[k]) folds.add(part + off[k], dst[k], len[k], grid, FF3_PART);
+      RPDE_TRY(fold_jobs(folds, st));
     }
     return RPDE_OK;
   }
@@ -473,13 +472,6 @@ __global__ __launch_bounds__(256) void k_rowsum(const float* __restrict__ g, flo
   }
   if (threadIdx.x == 0) part[blockIdx.x] = red[0];
 }
-__global__ void k_fold_bias(const float* __restrict__ part, float* __restrict__ gb, int B, int C) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  float acc = 0.f;
-  for (int b = 0; b < B; ++b) acc += part[(long)b * C + c];
-  gb[c] = acc;
-}
 }  // namespace rpde
 
 int rpde_conv1x1_bwd(const float* x, const float* w, const float* grad_out, float* grad_x, float* grad_w, float* grad_b,
@@ -506,8 +498,7 @@ int rpde_conv1x1_bwd(const float* x, const float* w, const float* grad_out, floa
   if (grad_b) {
     hipLaunchKernelGGL(k_rowsum, dim3(B * Cout), dim3(256), 0, st, grad_out, part, (long)S);
     RPDE_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_fold_bias, dim3((Cout + 63) / 64), dim3(64), 0, st, part, grad_b, B, Cout);
-    RPDE_LAUNCH_CHECK();
+    RPDE_TRY(reduce_slabs(part, grad_b, Cout, B, Cout, 1.f, 0, st));
   }
   if (grad_x) {
     // gx[b][i,s] = sum_o W[o,i] * g[b][o,s]   (through act'(x) when act_in is set)

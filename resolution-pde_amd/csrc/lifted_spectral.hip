@@ -17,7 +17,7 @@
 //              fused2d_synthesis unchanged
 //   backward   fused2d_analysis of g (adjoint tables), unchanged
 //              k_lift_tgrad      T[axis][k][j][o] = sum_lines conj(S_u~[line][k][j]) G[line][k][o]: partial sums over
-//                                slabs of lines, folded in fixed order by k_lift_tfold (no atomics: run-to-run identical)
+//                                slabs of lines, folded in fixed order by reduce_slabs (no atomics: run-to-run identical)
 //              k_lift_chain_w    gWmix[i][o][k] = sum_j W~[i][j] T[k][j][o]
 //              k_lift_chain_in   gW~[i][j] = sum_{axis,k,o} Re(conj(Wmix[k][i][o]) T[k][j][o])   -> gW_in, gb_in
 // No adjoint mix, no adjoint synthesis and no [P,64] input gradient: the branch's only consumers are weights.
@@ -25,6 +25,7 @@
 #include "fused_spectral.h"
 #include "h2.h"
 #include "lifted_spectral.h"
+#include "pointwise.h"
 #include "workspace.h"
 
 namespace rpde {
@@ -336,26 +337,6 @@ __global__ __launch_bounds__(512) void k_lift_tgrad(const float* __restrict__ g_
   }
 }
 
-// T[e] = sum_slab part[slab][e], in one fixed order: sixteen runs of slabs per output, then a fixed tree over the runs
-__global__ __launch_bounds__(1024) void k_lift_tfold(const float* __restrict__ part, float* __restrict__ T, long n_out, int S) {
-  __shared__ float red[16][64];
-  const int q = threadIdx.x >> 6, c = threadIdx.x & 63;
-  const long e = (long)blockIdx.x * 64 + c;
-  const int per = (S + 15) / 16, s0 = q * per, s1 = min(s0 + per, S);
-  float acc = 0.f;
-  if (e < n_out) {
-#pragma unroll 8
-    for (int s = s0; s < s1; ++s) acc += part[(long)s * n_out + e];
-  }
-  red[q][c] = acc;
-  __syncthreads();
-  for (int h = 8; h >= 1; h >>= 1) {
-    if (q < h) red[q][c] += red[q + h][c];
-    __syncthreads();
-  }
-  if (q == 0 && e < n_out) T[e] = red[0][c];
-}
-
 // gw[i][o][k][2] = sum_j W~[i][j] T[axis][k][j][o];  zero for k >= keff
 template <int CIN>
 __global__ __launch_bounds__(256) void k_lift_chain_w(const float* __restrict__ T, const float* __restrict__ w_in,
@@ -532,8 +513,7 @@ int rpde_lifted_fspectral2d_bwd(const float* grad_out, const float* spec_u, cons
                                         g.lines[1], g.kp, sqrtf((float)g.n[0]), sqrtf((float)g.n[1]), wk.S, wk.part));
   RPDE_LAUNCH_CHECK();
   const long n_out = (long)lift_t_floats(g, Cin);
-  hipLaunchKernelGGL(k_lift_tfold, dim3((unsigned)((n_out + 63) / 64)), dim3(1024), 0, st, wk.part, wk.T, n_out, wk.S);
-  RPDE_LAUNCH_CHECK();
+  RPDE_TRY(reduce_slabs(wk.part, wk.T, n_out, wk.S, n_out, 1.f, 0, st));      // T[e] = sum_slab part[slab][e]
   if (grad_wy || grad_wx) {
     RPDE_LIFT_CIN(Cin, hipLaunchKernelGGL(k_lift_chain_w<CIN>, dim3((unsigned)((4096L * K + 255) / 256), 2), dim3(256), 0, st, wk.T,
                                           w_in, b_in, grad_wy, grad_wx, K, g.keff, g.kp));

@@ -5,25 +5,24 @@
 
 namespace rpde {
 
-int reduce_slabs(const float* slabs, float* out, long n, int S, long stride, float scale, int accumulate, hipStream_t st);
-// out_k[j] = sum_s slabs[s*stride + off_k + j] for up to eight segments of one slab row, one launch; null dst: skipped
-struct ReduceSegs { int n, nseg; int off[8]; int len[8]; float* dst[8]; };
-int reduce_slabs_seg(const float* slabs, int S, long stride, const ReduceSegs& sg, hipStream_t st);
-// folds collected over several kernels and done by ONE launch (the small configurations are launch-bound: a FeedForward
-// backward on the GEMM path has eight of them).  Each job is out[i] = sum_s src[s*stride + i], i < len, summed exactly as
-// reduce_slabs does it (same bits).
+// Every plain fold of partial-sum slabs, out[i] = sum_s src[s*stride + i], i < len, runs in one kernel and one summation
+// order (slab_partial in pointwise.hip).  Folds collected over several kernels are done by ONE launch
+// (the small configurations are launch-bound: a FeedForward backward on the GEMM path has eight of them).
 struct FoldJobs {
   static constexpr int MAX = 12;
   int n = 0;
-  struct Job { const float* src; float* dst; long stride; int len, S, blk0; } j[MAX];
-  bool add(const float* src, float* dst, int len, int S, long stride) {
+  struct Job { const float* src; float* dst; long stride, len; int S, blk0; } j[MAX];
+  bool add(const float* src, float* dst, long len, int S, long stride) {
     if (n >= MAX) return false;
     j[n].src = src; j[n].dst = dst; j[n].len = len; j[n].S = S; j[n].stride = stride; j[n].blk0 = 0;
     ++n;
     return true;
   }
 };
-int fold_jobs(FoldJobs& jobs, hipStream_t st);
+// dst[i] = scale * sum (+ dst[i] when accumulate), the same for every job; empties `jobs`
+int fold_jobs(FoldJobs& jobs, hipStream_t st, float scale = 1.f, int accumulate = 0);
+// the fold of one job
+int reduce_slabs(const float* slabs, float* out, long n, int S, long stride, float scale, int accumulate, hipStream_t st);
 constexpr int REDUCE_CHUNKS = 64;
 // tmp: REDUCE_CHUNKS * n floats of scratch
 int reduce_slabs_2pass(const float* slabs, float* out, long n, int S, long stride, float* tmp, hipStream_t st);

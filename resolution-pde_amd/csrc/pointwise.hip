@@ -5,6 +5,8 @@
 #include "rpde_internal.h"
 #include "pointwise.h"
 
+#include <type_traits>
+
 namespace rpde {
 
 // ---------------------------------------------------------------------------
@@ -36,31 +38,16 @@ __device__ __forceinline__ float slab_partial(const float* __restrict__ slabs, l
   return acc;
 }
 
-__global__ __launch_bounds__(256) void k_reduce_slabs(const float* __restrict__ slabs, float* __restrict__ out, long n,
-                                                      int S, long stride, float scale, int accumulate) {
-  __shared__ float red[4][64];
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const long i = (long)blockIdx.x * 64 + tx;
-  float acc = i < n ? slab_partial(slabs, i, S, stride, ty) : 0.f;
-  red[ty][tx] = acc;
-  __syncthreads();
-  if (ty == 0 && i < n) {
-    acc = (red[0][tx] + red[1][tx]) + (red[2][tx] + red[3][tx]);
-    acc *= scale;
-    if (accumulate) acc += out[i];
-    out[i] = acc;
-  }
-}
-
-// several independent folds, one launch: block -> job by the jobs' first-block numbers
-__global__ __launch_bounds__(256) void k_fold_jobs(const FoldJobs J) {
+// The one fold kernel: several independent folds, one launch; block -> job by the jobs' first-block numbers.
+// dst[i] = scale * sum (+ dst[i] when accumulate); a launch of several jobs passes 1.f, 0 (the product is exact)
+__global__ __launch_bounds__(256) void k_fold_jobs(const FoldJobs J, float scale, int accumulate) {
   __shared__ float red[4][64];
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   int jn = 0;
 #pragma unroll
   for (int q = 1; q < FoldJobs::MAX; ++q)
     if (q < J.n && (int)blockIdx.x >= J.j[q].blk0) jn = q;
-  const float* src = J.j[0].src; float* dst = J.j[0].dst; long stride = J.j[0].stride; int len = J.j[0].len, S = J.j[0].S, b0 = 0;
+  const float* src = J.j[0].src; float* dst = J.j[0].dst; long stride = J.j[0].stride, len = J.j[0].len; int S = J.j[0].S, b0 = 0;
 #pragma unroll
   for (int q = 1; q < FoldJobs::MAX; ++q)          // (selects instead of a dynamically indexed kernel argument)
     if (q == jn) { src = J.j[q].src; dst = J.j[q].dst; stride = J.j[q].stride; len = J.j[q].len; S = J.j[q].S; b0 = J.j[q].blk0; }
@@ -68,56 +55,28 @@ __global__ __launch_bounds__(256) void k_fold_jobs(const FoldJobs J) {
   float acc = i < len ? slab_partial(src, i, S, stride, ty) : 0.f;
   red[ty][tx] = acc;
   __syncthreads();
-  if (ty == 0 && i < len) dst[i] = (red[0][tx] + red[1][tx]) + (red[2][tx] + red[3][tx]);
+  if (ty == 0 && i < len) {
+    acc = (red[0][tx] + red[1][tx]) + (red[2][tx] + red[3][tx]);
+    acc *= scale;
+    if (accumulate) acc += dst[i];
+    dst[i] = acc;
+  }
 }
 
-int fold_jobs(FoldJobs& jobs, hipStream_t st) {
-  if (jobs.n == 0) return RPDE_OK;
+int fold_jobs(FoldJobs& jobs, hipStream_t st, float scale, int accumulate) {
   int blocks = 0;
-  for (int q = 0; q < jobs.n; ++q) { jobs.j[q].blk0 = blocks; blocks += (jobs.j[q].len + 63) / 64; }
-  hipLaunchKernelGGL(k_fold_jobs, dim3((unsigned)blocks), dim3(256), 0, st, jobs);
+  for (int q = 0; q < jobs.n; ++q) { jobs.j[q].blk0 = blocks; blocks += (int)((jobs.j[q].len + 63) / 64); }
+  if (blocks == 0) return RPDE_OK;
+  hipLaunchKernelGGL(k_fold_jobs, dim3((unsigned)blocks), dim3(256), 0, st, jobs, scale, accumulate);
   RPDE_LAUNCH_CHECK();
   jobs.n = 0;
   return RPDE_OK;
 }
 
 int reduce_slabs(const float* slabs, float* out, long n, int S, long stride, float scale, int accumulate, hipStream_t st) {
-  hipLaunchKernelGGL(k_reduce_slabs, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, slabs, out, n, S, stride, scale, accumulate);
-  RPDE_LAUNCH_CHECK();
-  return RPDE_OK;
-}
-
-// the same fold for a row of up to eight segments that go to different tensors (bias / gamma / beta gradients of the fused
-// FeedForward backward: one launch instead of five)
-__global__ __launch_bounds__(256) void k_reduce_slabs_seg(const float* __restrict__ slabs, int S, long stride, ReduceSegs sg) {
-  __shared__ float red[4][64];
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const int i = blockIdx.x * 64 + tx;
-  float acc = 0.f;
-  if (i < sg.n) {
-    float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    int s = ty;
-    for (; s + 28 < S; s += 32) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) a[j] += slabs[(long)(s + 4 * j) * stride + i];
-    }
-    for (; s < S; s += 4) a[0] += slabs[(long)s * stride + i];
-    acc = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
-  }
-  red[ty][tx] = acc;
-  __syncthreads();
-  if (ty == 0 && i < sg.n) {
-    acc = (red[0][tx] + red[1][tx]) + (red[2][tx] + red[3][tx]);
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-      if (k < sg.nseg && i >= sg.off[k] && i < sg.off[k] + sg.len[k] && sg.dst[k]) sg.dst[k][i - sg.off[k]] = acc;
-  }
-}
-
-int reduce_slabs_seg(const float* slabs, int S, long stride, const ReduceSegs& sg, hipStream_t st) {
-  hipLaunchKernelGGL(k_reduce_slabs_seg, dim3((unsigned)((sg.n + 63) / 64)), dim3(256), 0, st, slabs, S, stride, sg);
-  RPDE_LAUNCH_CHECK();
-  return RPDE_OK;
+  FoldJobs one;
+  one.add(slabs, out, n, S, stride);
+  return fold_jobs(one, st, scale, accumulate);
 }
 
 // many slabs, few outputs (per-tile column sums): first fold S slabs into REDUCE_CHUNKS
@@ -127,10 +86,8 @@ __global__ __launch_bounds__(256) void k_reduce_slabs_chunk(const float* __restr
   __shared__ float red[4][64];
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   const long i = (long)blockIdx.x * 64 + tx;
-  const int s0 = blockIdx.y * per_chunk, s1 = min(S, s0 + per_chunk);
-  float acc = 0.f;
-  if (i < n)
-    for (int s = s0 + ty; s < s1; s += 4) acc += slabs[(long)s * stride + i];
+  const int s0 = blockIdx.y * per_chunk, s1 = min(S, s0 + per_chunk);      // (a chunk past the last slab: s1 < s0, sum 0)
+  float acc = i < n ? slab_partial(slabs + (long)s0 * stride, i, s1 - s0, stride, ty) : 0.f;
   red[ty][tx] = acc;
   __syncthreads();
   if (ty == 0 && i < n) tmp[(long)blockIdx.y * n + i] = (red[0][tx] + red[1][tx]) + (red[2][tx] + red[3][tx]);
@@ -175,17 +132,13 @@ __global__ __launch_bounds__(256) void k_colsum(const float* __restrict__ x, flo
   }
 }
 
-size_t colsum_ws_floats(long P, int N) {
-  long nb = (P + 255) / 256;
-  if (nb > 1024) nb = 1024;
-  if (nb < 1) nb = 1;
-  return (size_t)nb * N;
-}
+// the slab-producing kernels run between 1 and 1024 workgroups: one slab each
+static long slab_blocks(long nb) { return nb < 1 ? 1 : nb > 1024 ? 1024 : nb; }
+
+size_t colsum_ws_floats(long P, int N) { return (size_t)slab_blocks((P + 255) / 256) * N; }
 
 int colsum(const float* x, float* out, long P, int N, long ld, float* ws, int accumulate, hipStream_t st) {
-  long nb = (P + 255) / 256;
-  if (nb > 1024) nb = 1024;
-  if (nb < 1) nb = 1;
+  const long nb = slab_blocks((P + 255) / 256);
   const long rpb = (P + nb - 1) / nb;
   hipLaunchKernelGGL(k_colsum, dim3((unsigned)nb), dim3(256), 0, st, x, ws, P, N, ld, rpb);
   RPDE_LAUNCH_CHECK();
@@ -198,6 +151,24 @@ int colsum(const float* x, float* out, long P, int N, long ld, float* ws, int ac
 // 64/G rows.  C must be a multiple of 4 with C/4 in {1,2,4,...,64}; other
 // widths take the one-wave-per-row path below.
 // ---------------------------------------------------------------------------
+static bool tail_vec_ok(int C) {
+  const int G = C / 4;
+  return (C % 4 == 0) && (G == 1 || G == 2 || G == 4 || G == 8 || G == 16 || G == 32 || G == 64);
+}
+// f(G as a constant) for the G = C / 4 of a width that tail_vec_ok accepts
+template <class F>
+static void tail_dispatch(int G, F&& f) {
+  switch (G) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    case 16: f(std::integral_constant<int, 16>{}); break;
+    case 32: f(std::integral_constant<int, 32>{}); break;
+    default: f(std::integral_constant<int, 64>{}); break;
+  }
+}
+
 template <int G>
 __device__ __forceinline__ float group_sum(float v) {
 #pragma unroll
@@ -294,8 +265,7 @@ int ff_tail_fwd(const float* z, const float* res, float* out, long P, int C, int
                 const float* gamma, const float* beta, DropCfg drop, int post_act, hipStream_t st) {
   RPDE_CHECK_ARG(!layer_norm || (gamma && beta), "ff_tail: layer_norm needs gamma/beta");
   const int G = C / 4;
-  const bool vec = (C % 4 == 0) && (G == 1 || G == 2 || G == 4 || G == 8 || G == 16 || G == 32 || G == 64);
-  if (!vec) {
+  if (!tail_vec_ok(C)) {
     RPDE_CHECK_ARG(C <= 512, "ff_tail: width %d > 512 unsupported", C);
     long nb = (P + 3) / 4; if (nb > 4096) nb = 4096;
     hipLaunchKernelGGL(k_ff_tail_fwd_any, dim3((unsigned)nb), dim3(256), 0, st, z, res, out, P, C, layer_norm, eps, gamma, beta, drop, post_act);
@@ -304,13 +274,9 @@ int ff_tail_fwd(const float* z, const float* res, float* out, long P, int C, int
   }
   const long rpb = 256 / G;
   long nb = (P + rpb - 1) / rpb; if (nb > 8192) nb = 8192;
-#define LAUNCH_G(GG) hipLaunchKernelGGL((k_ff_tail_fwd<GG>), dim3((unsigned)nb), dim3(256), 0, st, z, res, out, P, layer_norm, eps, gamma, beta, drop, post_act)
-  switch (G) {
-    case 1: LAUNCH_G(1); break; case 2: LAUNCH_G(2); break; case 4: LAUNCH_G(4); break;
-    case 8: LAUNCH_G(8); break; case 16: LAUNCH_G(16); break; case 32: LAUNCH_G(32); break;
-    default: LAUNCH_G(64); break;
-  }
-#undef LAUNCH_G
+  tail_dispatch(G, [&](auto g_) {
+    hipLaunchKernelGGL((k_ff_tail_fwd<g_()>), dim3((unsigned)nb), dim3(256), 0, st, z, res, out, P, layer_norm, eps, gamma, beta, drop, post_act);
+  });
   RPDE_LAUNCH_CHECK();
   return RPDE_OK;
 }
@@ -474,16 +440,7 @@ __global__ __launch_bounds__(256) void k_ff_tail_bwd_vec(const float* __restrict
   }
 }
 
-static long tail_bwd_blocks(long P) {
-  long nb = (P + 3) / 4;
-  if (nb > 1024) nb = 1024;
-  if (nb < 1) nb = 1;
-  return nb;
-}
-static bool tail_vec_ok(int C) {
-  const int G = C / 4;
-  return (C % 4 == 0) && (G == 1 || G == 2 || G == 4 || G == 8 || G == 16 || G == 32 || G == 64);
-}
+static long tail_bwd_blocks(long P) { return slab_blocks((P + 3) / 4); }
 size_t ff_tail_bwd_ws_floats(long P, int C) { return (size_t)tail_bwd_blocks(P) * 3 * C; }
 
 // grad_bias (optional) receives colsum(dz) when the vector kernel runs; returns whether it did
@@ -499,14 +456,10 @@ int ff_tail_bwd(const float* z, const float* g, float* dz, long P, int C, int la
   if (tail_vec_ok(C)) {
     const int G = C / 4;
     const long rpb = 256 / G;
-    long nb = (P + rpb - 1) / rpb; if (nb > 1024) nb = 1024; if (nb < 1) nb = 1;
-#define LAUNCH_G(GG) hipLaunchKernelGGL((k_ff_tail_bwd_vec<GG>), dim3((unsigned)nb), dim3(256), 0, st, z, g, dz, ws, P, layer_norm, eps, gamma, beta, drop, post_act)
-    switch (G) {
-      case 1: LAUNCH_G(1); break; case 2: LAUNCH_G(2); break; case 4: LAUNCH_G(4); break;
-      case 8: LAUNCH_G(8); break; case 16: LAUNCH_G(16); break; case 32: LAUNCH_G(32); break;
-      default: LAUNCH_G(64); break;
-    }
-#undef LAUNCH_G
+    const long nb = slab_blocks((P + rpb - 1) / rpb);
+    tail_dispatch(G, [&](auto g_) {
+      hipLaunchKernelGGL((k_ff_tail_bwd_vec<g_()>), dim3((unsigned)nb), dim3(256), 0, st, z, g, dz, ws, P, layer_norm, eps, gamma, beta, drop, post_act);
+    });
     RPDE_LAUNCH_CHECK();
     if (layer_norm) {
       if (grad_gamma) RPDE_TRY(fold(ws, grad_gamma, (int)nb, 3L * C));

@@ -136,9 +136,6 @@ __device__ __forceinline__ double wave_sum(double v) {
 }
 
 int launch_gemm(const rpde_gemm_desc& d, hipStream_t stream);
-// gw [n_gw] / gb [n_gb] (or null) = the partial sums part [slices][n_gw + n_gb] of a weight gradient added in slice
-// order (cno_layers.hip)
-int sum_slices(const float* part, float* gw, float* gb, long n_gw, long n_gb, int slices, hipStream_t st);
 // pre-split operands of the split-bf16 GEMM (gemm_bf16x3.hip)
 int split_npad(int N);
 size_t split_bytes(int N, int K);

@@ -7,8 +7,8 @@
 // and gb[co] is the sum of g, wherever it stands.  A workgroup owns a 4 x 4 tile of (ci, co) = (blockIdx.x, blockIdx.y)
 // and one slice of the points: every thread walks the slice's points tid, tid + 256, ... with 16 T + 4 accumulators,
 // then the workgroup adds them up in a fixed order (DPP sum inside a wave, the four waves in sequence).  With one slice
-// the sums are the result; with more they are partial sums [slice][Cin Cout T + Cout], which sum_slices adds in slice
-// order.  No atomics.  DESIGN.md 10.19.
+// the sums are the result; with more they are partial sums [slice][Cin Cout T + Cout], which one fold launch adds in a fixed
+// order (pointwise.h).  No atomics.  DESIGN.md 10.19.
 //
 // An Op is constructed from (H, W, the slice's first point) and supplies
 //   T, G_NARROW        the taps per channel pair; whether g is the narrow operand (then co = blockIdx.y is the narrow
@@ -18,6 +18,7 @@
 //   narrow(src, C, ch) the narrow operand's value of channel ch at the point (0 past the last channel)
 //   wide(src, C, ch, v) v[t] = the wide operand's taps (0 past the last channel and outside the plane)
 #pragma once
+#include "pointwise.h"
 #include "rpde_internal.h"
 #include "wave.h"
 
@@ -129,7 +130,10 @@ int wgrad_sliced(const char* what, const float* x, const float* g, float* gw, fl
   hipLaunchKernelGGL(k_wgrad_sliced<Op>, grid, dim3(256), 0, st, x, g, to_w, to_b, stride, NP, Cin, Cout, H, W, per_slice);
   RPDE_LAUNCH_CHECK();
   if (slices == 1) return RPDE_OK;
-  return sum_slices(partial, gw, gb, n_gw, n_gb, slices, st);
+  FoldJobs folds;
+  folds.add(partial, gw, n_gw, slices, n_gw + n_gb);
+  if (gb) folds.add(partial + n_gw, gb, n_gb, slices, n_gw + n_gb);
+  return fold_jobs(folds, st);
 }
 
 }  // namespace rpde
